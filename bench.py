@@ -45,9 +45,6 @@ for _i, _a in enumerate(sys.argv):          # --edge ipc|rccl: the kind of edge 
 if int(os.environ.get("WORLD_SIZE", "1")) > 1:
     os.environ.setdefault("HPS_RING_TIMEOUT_S", "300")      # a ring that stops making progress fails loudly well inside the driver's limit
 if int(os.environ.get("WORLD_SIZE", "1")) > 1 and "--same-device" not in sys.argv:
-    # For RCCL edges -- HPS_RING_EDGE=rccl, or the fall-back of a ring whose ipc probe message fails (RingTransport).  Before HIP starts: the engine's stream, the ring's send and receive streams and torch's own streams must not end up
-    # sharing a hardware queue (a send queued behind a receive that waits for its data would close a circle around the ring)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     if "--config5" not in sys.argv:
         # A receive posted ahead is an RCCL kernel that waits on the device for its data: by default 16 workgroups for a
         # 1 MB beam block (measured: grid 4096 x 256 threads), i.e. 16 CUs' worth of slots held while the engine runs.  Two
@@ -307,7 +304,36 @@ def emit(obj):
     print(json.dumps(obj), file=_JSON_OUT or sys.stdout, flush=True)
 
 
-def reference_benchmark(nxy):
+DUMP_SAMPLE = 1 << 17      # --dump-outputs: values kept per field component and per particle array (a fixed, seeded sample)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, eng):
+    """--dump-outputs DIR: what the timed engine holds after its last timed slice -- every component of the slab and the plasma
+    particles -- as DIR/field_<component>.npy and DIR/plasma_<array>.npy, float64.  (No checksums: the timed run does not
+    accumulate them.)  An array longer than DUMP_SAMPLE is cut to the same seeded sample of positions in every run of the same
+    deck (33 MiB in all at 1024^2 x 4 ppc), so that two builds can be compared value for value."""
+    import numpy as np
+    from hipace_amd._lib import PL_REAL
+    os.makedirs(out_dir, exist_ok=True)
+
+    def pick(n, seed):
+        return slice(None) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLE, replace=False))
+
+    names = eng.comp_names()
+    slab = eng.slab()
+    slab = slab.reshape(slab.shape[0], -1)
+    idx = pick(slab.shape[1], DUMP_SEED)
+    for c in range(slab.shape[0]):
+        np.save(os.path.join(out_dir, f"field_{names[c] if c < len(names) else c}.npy"), slab[c, idx])
+    real, valid = eng.particles()
+    idx = pick(real.shape[1], DUMP_SEED + 1)
+    for k, name in enumerate(PL_REAL):
+        np.save(os.path.join(out_dir, f"plasma_{name}.npy"), real[k, idx])
+    np.save(os.path.join(out_dir, "plasma_valid.npy"), valid[idx].astype(np.float64))
+
+
+def reference_benchmark(nxy, dump=None):
     """examples/benchmarks/inputs_transverse_benchmark on one GPU (tests/transverse_benchmark.1Rank.sh runs it at nxy = 1023 and
     profiles/r05_reference_decks_host_beams.txt holds its checksums against the reference's file): slices/s of one whole box."""
     import torch
@@ -326,6 +352,8 @@ def reference_benchmark(nxy):
             eng.solve_slice(isl)
         eng.sync()
         times.append(time.perf_counter() - t0)
+    if dump:
+        dump_outputs(dump, eng)
     st = eng.stats()
     emit({
         "metric": f"transverse slices/s of the reference's transverse benchmark deck at {nxy}^2 x 1 ppc (explicit solver)", "value": nz / times[1],
@@ -617,9 +645,12 @@ def main():
                     help="instead of the BASELINE deck: the reference's own transverse scaling benchmark "
                          "(examples/benchmarks/inputs_transverse_benchmark: NXY^2 x 1000 cells, 1 ppc, a fixed_weight_pdf beam of "
                          "10 NXY^2 particles drawn on the host; default NXY = 1023, the size its CI runs) -- one untimed box, one timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed slices, write what the timed engine computed in its last one (fields, plasma particles) "
+                         "as DIR/<name>.npy, float64, a fixed seeded sample of large arrays")
     args = ap.parse_args()
     if args.reference_benchmark:
-        return reference_benchmark(args.reference_benchmark)
+        return reference_benchmark(args.reference_benchmark, args.dump_outputs)
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(respawn_under_torchrun(args.gpus))
@@ -732,7 +763,8 @@ def main():
     if args.fuse:
         for e in engines:
             e.set_fusion(True)
-    short = args.steps < nz and lanes == 1 and not args.ring_self
+    # (a window of K slices behind W warm-up slices has to fit into one box; a longer run times K slices over whole boxes)
+    short = args.steps < nz and args.steps + args.warmup <= nz and lanes == 1 and not args.ring_self
     stride = args.profile_stride if args.profile_stride > 0 else (2 if args.steps < 64 else 16)
     dev = torch.device("cuda", local)
 
@@ -828,6 +860,8 @@ def main():
                          handoff_batch=args.handoff_batch)
         barrier()
         dt = clock["t1"] - clock["t0"]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eng)
         if world == 1 and args.phase_window > 0 and counts[0] + args.phase_window <= nz:
             # the driver's short run times the slices with the light timers (the deposition only: 4 event records per timed
             # slice); the split of a slice over its phases comes from one more window AFTER the timed region, every slice of
@@ -886,6 +920,8 @@ def main():
         dt = time.perf_counter() - t0
         gc.enable()
         gc.unfreeze()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, eng)
     phases, nprof = phases_timed if phases_timed is not None else eng.phase_times()
     eng.set_profiling(False)
     for e in engines[1:]:            # phase times: mean over the lanes (intervals overlap in wall time)
@@ -937,7 +973,7 @@ def main():
                 e.set_fusion(True)
         W = world * L
         lagL = 2                                                 # a stage trails the one ahead by the hand-off of two slices
-        if args.steps < nz:
+        if args.steps < nz and args.steps + lagL * (W - 1) <= nz:
             # steady-state window: every stage runs (untimed) to its place in the box -- stage v `lagL*v` slices behind stage
             # 0 --, then all of them time `steps` slices at once.  The clock is the device's: an event on each engine's
             # stream at the first and behind the last timed slice (one host thread drives the stages and must not stop).

@@ -82,10 +82,8 @@ int main (int argc, char** argv)
     if (deck.dt != 0.0) { std::fprintf(stderr, "pipeline_host hands a static beam on (hipace.dt = 0)\n"); return 2; }
     if (n_steps < 1 || world < 1 || rank < 0 || rank >= world || L < 1) { std::fprintf(stderr, "bad arguments\n"); return 2; }
     if (world > 1) {
-        // before the first HIP call: the ring's receive and send streams and the engines' streams on hardware queues of their
-        // own (hps_ring_init refuses 2+ ranks otherwise), and two RCCL channels per hand-off (a receive posted ahead is a
-        // kernel that holds its workgroups until the data comes).  Values the launcher exported win.
-        setenv("GPU_MAX_HW_QUEUES", "8", 0);
+        // before the first HIP call: two RCCL channels per hand-off (a receive posted ahead is a kernel that holds its
+        // workgroups until the data comes).  A value the launcher exported wins.
         setenv("NCCL_MAX_P2P_NCHANNELS", "2", 0);
     }
     int ndev = 0;

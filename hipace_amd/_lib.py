@@ -5,28 +5,6 @@ import os
 import subprocess
 
 
-def launched_ranks():
-    """How many ranks the launcher says there are: torchrun (WORLD_SIZE), Open MPI, PMI / Hydra, Slurm."""
-    n = 1
-    for k in ("WORLD_SIZE", "OMPI_COMM_WORLD_SIZE", "PMI_SIZE", "SLURM_NTASKS"):
-        try:
-            n = max(n, int(os.environ.get(k, "1") or 1))
-        except ValueError:
-            pass
-    return n
-
-
-def _ring_environment():
-    """RCCL edges only (HPS_RING_EDGE=rccl; the default ipc edge has no device-resident waiter and needs none of this).  A ring
-    of 2+ ranks posts its receives ahead as RCCL kernels that wait on the device: the ring's two streams and the engine's
-    stream must each get a hardware queue of their own (hps_ring_init refuses to start otherwise), and the runtime reads
-    GPU_MAX_HW_QUEUES once, when the process first touches HIP.  Any multi-rank launch therefore gets the variable HERE, at
-    the import of the binding -- before libhpslice.so is loaded, and before torch initialises the device unless the host has
-    already done so (RingTransport checks that and says so)."""
-    if launched_ranks() > 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
-
 def hip_already_started():
     """True if this process has (or may have) touched HIP: torch has initialised the device, or libhpslice.so has been
     loaded and used (an engine, a solver: hipSetDevice) -- GPU_MAX_HW_QUEUES set now would come too late."""
@@ -43,7 +21,6 @@ def hip_already_started():
 _LIB = None
 _HWQ_PRESET = "GPU_MAX_HW_QUEUES" in os.environ     # set by the host's environment, before this process started
 _HIP_STARTED_AT_IMPORT = hip_already_started()
-_ring_environment()
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 SO = os.environ.get("HPS_LIB") or os.path.join(CSRC, "libhpslice.so")      # HPS_LIB: a diagnostic build (make stamps)

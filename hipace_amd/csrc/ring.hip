@@ -376,8 +376,8 @@ extern "C" int hps_ring_init (int rank, int world, int device, const char* id_ed
         // a receive never runs and the ring waits in a circle.  ROCm's default is 4 hardware queues per process; the ring
         // needs every stream of the process on its own queue: refuse to start with fewer than 8 (set before HIP starts).
         // The check can only read the environment: whether the value was there BEFORE the runtime started is the host's
-        // business (hipace_amd/_lib.py sets it at import when WORLD_SIZE > 1, examples/pipeline_host.cpp before its first
-        // HIP call).  HPS_RING_ALLOW_SHARED_QUEUES=1 overrides the refusal (a host that knows its queue assignment).
+        // business (the launcher exports it).  HPS_RING_ALLOW_SHARED_QUEUES=1 overrides the refusal (a host that knows its
+        // queue assignment).
         const char* q = std::getenv("GPU_MAX_HW_QUEUES");
         const char* ovr = std::getenv("HPS_RING_ALLOW_SHARED_QUEUES");
         if ((!q || std::atoi(q) < 8) && !(ovr && std::atoi(ovr) != 0)) {

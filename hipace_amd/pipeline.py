@@ -129,15 +129,14 @@ class RingTransport:
             assert edge in ("ipc", "rccl")
             os.environ["HPS_RING_EDGE"] = edge
         if world > 1 and ring_edge() == "rccl":
-            # hardware queues (see _lib._ring_environment): the variable must have been in the environment before HIP started
+            # hardware queues: the launcher must have exported the variable before HIP started
             override = os.environ.get("HPS_RING_ALLOW_SHARED_QUEUES", "0") not in ("", "0")
             if int(os.environ.get("GPU_MAX_HW_QUEUES", "0") or 0) < 8 and not override:
                 if _lib.hip_already_started():
                     raise RuntimeError("RingTransport: an RCCL ring of %d ranks needs GPU_MAX_HW_QUEUES >= 8 in the environment BEFORE the "
-                                       "process touches the GPU (export it in the launcher; importing hipace_amd._lib sets it under a "
-                                       "multi-rank launcher, but this process had already created an engine or initialised torch.cuda); "
+                                       "process touches the GPU (export it in the launcher; this process had already created an engine "
+                                       "or initialised torch.cuda); "
                                        "HPS_RING_ALLOW_SHARED_QUEUES=1 overrides, HPS_RING_EDGE=ipc needs none of this" % world)
-                os.environ["GPU_MAX_HW_QUEUES"] = "8"
             elif not _lib._HWQ_PRESET and _lib._HIP_STARTED_AT_IMPORT and not override:
                 raise RuntimeError("RingTransport: GPU_MAX_HW_QUEUES was set after torch had initialised the device -- the runtime did "
                                    "not see it; export it in the launcher's environment (HPS_RING_ALLOW_SHARED_QUEUES=1 overrides)")
@@ -609,7 +608,7 @@ def run_pipeline(*args, **kwargs):
     (the whole difference between the ring and the plain slice loop on one GPU).  What exists now is parked in the permanent
     generation for the run.
     Two or more ranks on RCCL: GPU_MAX_HW_QUEUES >= 8 must be in the environment before the process touches the GPU
-    (hipace_amd._lib sets it at import when WORLD_SIZE > 1; RcclTransport refuses a host that initialised the device first)."""
+    (the launcher exports it; RcclTransport refuses a host that initialised the device first)."""
     gc.freeze()                     # (no collection first: that is the 30-50 ms pass this is here to avoid)
     try:
         return _drive([_stage(*args, **kwargs)])[0]

@@ -519,8 +519,7 @@ int hps_ring_sync (void* ring);                 /* host waits for both streams o
  * seconds (environment, default 900) -- hps_ring_sync_timeout with the limit as an argument: a ring whose peer is gone, or
  * whose posted-ahead receives share a hardware queue with the sends they wait for, fails loudly instead of hanging.
  * hps_ring_init refuses to start a ring of 2+ ranks unless GPU_MAX_HW_QUEUES >= 8 is set in the environment -- by the
- * host, BEFORE its first HIP call (the runtime reads it once; the library can only see the string): examples/pipeline_host.cpp
- * does it with setenv at the top of main, hipace_amd/_lib.py at import when WORLD_SIZE > 1.  HPS_RING_ALLOW_SHARED_QUEUES=1
+ * host's launcher, BEFORE its first HIP call (the runtime reads it once; the library can only see the string).  HPS_RING_ALLOW_SHARED_QUEUES=1
  * turns the refusal off for a host that has arranged its queues some other way. */
 int hps_ring_sync_timeout (void* ring, double seconds);
 int hps_ring_stats (void* ring, long* n_sent, long* n_received, long long* bytes_sent, long long* bytes_received);

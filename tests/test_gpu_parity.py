@@ -1008,6 +1008,30 @@ def test_bench_short_run_times_every_slice():
 
 
 @pytest.mark.gpu
+def test_bench_dumps_the_same_outputs_for_the_same_arguments(tmp_path):
+    """--dump-outputs DIR: the last timed slice's fields and plasma particles as float64 .npy files, a seeded sample
+    of the large ones (64 MB at most); two runs with the same arguments compute the same values (atomics: to 1e-12)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                              "--n", "128", "--cpu-slices", "0", "--inflight", "1", "--phase-window", "0", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])["steps"] == 6
+        dumps.append({p.name: np.load(p) for p in sorted(d.iterdir())})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and "field_Psi.npy" in a and "plasma_x.npy" in a
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64) and a[name].shape == b[name].shape and a[name].size > 0, name
+        assert np.abs(a[name] - b[name]).max() <= 1e-12 * max(np.abs(b[name]).max(), 1e-300), name
+
+
+@pytest.mark.gpu
 def test_rccl_ring_carries_the_beam_on_one_gpu(api):
     """The C-ABI ring on RCCL with the one rank a 1-GPU box has: hps_ring_init makes a 1-rank communicator and
     hps_ring_sendrecv_self (MultiBuffer.cpp:299-308, "send to myself") moves every beam block of step 0 into the storage
