@@ -1672,7 +1672,7 @@ def _run_with_env(api, var, value, deck, n_steps, tile_size=16):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", ["gated_push", "lazy_shift", "fuse_sources", "aux_stream", "fold_beam", "fold_hierarchy", "mg_post_fold", "laser_stream_fft", "laser_stream_mg", "ion_tile_skip", "fold_tail", "gated_ion_push", "poisson_blocked", "poisson_tridiag", "poisson_tridiag_dense", "poisson_tridiag_pow2", "pc_speculate", "valid_by_w", "valid_by_psi", "cu_masks", "post_in_push"])
+@pytest.mark.parametrize("case", ["gated_push", "lazy_shift", "fuse_sources", "aux_stream", "fold_beam", "fold_hierarchy", "mg_post_fold", "laser_stream_fft", "laser_stream_mg", "ion_tile_skip", "fold_tail", "gated_ion_push", "poisson_tridiag", "poisson_tridiag_dense", "poisson_tridiag_pow2", "pc_speculate", "valid_by_w", "valid_by_psi", "cu_masks", "post_in_push"])
 def test_schedules_do_not_change_results(api, case):
     """The engine's scheduling choices -- the push enqueued behind the multigrid's V-cycles and gated on its stopping rule,
     the envelope solver on a stream of its own, the tiles of atoms that cannot ionise skipped before their image is loaded --
@@ -1696,13 +1696,12 @@ def test_schedules_do_not_change_results(api, case):
         var, deck, steps = "HPS_VALID_BY_W", decks.blowout_wake(), 2
     elif case == "valid_by_psi":     # the push reads "psi_half != 0" instead of the valid bit of idcpu (absorbing walls: particles do die)
         var, deck, steps = "HPS_VALID_BY_PSI", dict(decks.blowout_wake(), bc=2), 2
-    elif case == "poisson_blocked":  # the Poisson solves' intermediate planes in blocks of 6 rows: three launches, no transposes
-        var, deck, steps = "HPS_POISSON_BLOCKED", decks.blowout_wake(), 1       # (both runs with the y direction as transforms: below)
     elif case.startswith("poisson_tridiag"):
-        # round 6: the y direction of every Poisson solve as tridiagonal solves (k_tridiag_y) against forward DST, inverse
-        # eigenvalues, inverse DST -- the same discrete operator -- behind the own transform (65 = 5 x 13), the dense products
-        # (61 cells: 62 has no built factorisation) and the power-of-two kernel (63 cells)
-        var, steps = "HPS_POISSON_TRIDIAG", 1
+        # round 6: the y direction of every Poisson solve as tridiagonal solves (k_tridiag_y) against the rocFFT back-end's forward
+        # DST, inverse eigenvalues, inverse DST -- the same discrete operator -- behind the own transform (65 = 5 x 13), the dense
+        # products (61 cells: 62 has no built factorisation) and the power-of-two kernel (63 cells).  (With rocFFT the sources
+        # come through k_rhs_all and staging planes: that solver cannot form them itself.)
+        var, steps = "HPS_POISSON_BACKEND", 1
         deck = decks.blowout_wake()
         if case.endswith("dense"):
             deck.update(nx=61, ny=61)
@@ -1726,18 +1725,9 @@ def test_schedules_do_not_change_results(api, case):
         var, steps = {"ion_tile_skip": "HPS_ION_TILE_SKIP", "fold_tail": "HPS_FOLD_TAIL", "gated_ion_push": "HPS_GATED_ION_PUSH"}[case], 2
         deck = decks.laser_ionization_SI()
         deck.update(nx=128, ny=128, nz=60, laser_solver=1, dt=6.0 * 10.0e-6 / 299792458.0, n_steps=2)
-    legacy_y = os.environ.get("HPS_POISSON_TRIDIAG")
-    if case == "poisson_blocked":
-        os.environ["HPS_POISSON_TRIDIAG"] = "0"
-    try:
-        a = _run_with_env(api, var, "0-127" if case == "cu_masks" else "1", deck, steps)
-        b = _run_with_env(api, var, "0", deck, steps)
-    finally:
-        if case == "poisson_blocked":
-            if legacy_y is None:
-                del os.environ["HPS_POISSON_TRIDIAG"]
-            else:
-                os.environ["HPS_POISSON_TRIDIAG"] = legacy_y
+    on, off = ("rocfft", "own") if case.startswith("poisson_tridiag") else ("0-127" if case == "cu_masks" else "1", "0")
+    a = _run_with_env(api, var, on, deck, steps)
+    b = _run_with_env(api, var, off, deck, steps)
     sa, sb = a.slab(), b.slab()
     # two runs of ONE schedule differ by the order of their LDS atomics; two steps of the ionisation deck have shown 1.2e-12
     # (the predictor-corrector loop amplifies that order through its ~5 dependent solves per slice: Bz, five orders of magnitude
