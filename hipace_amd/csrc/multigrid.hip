@@ -33,12 +33,6 @@ namespace hps {
 // (HPS_MG_OFF32: the element's byte offset in 32-bit arithmetic from the view's base -- global_load / global_store with the
 //  base in SGPRs and one offset VGPR instead of a 64-bit address per access: the level-0 passes spend more instructions on
 //  index arithmetic than on fp64; the solver's planes hold at most 2^28 doubles, checked in mg_create)
-// 1: the fused 8-sweep level-0 pass evaluates its V-cycle's gate behind its tile's loads, as the 4-sweep kernels do (0: first, a
-// dependent trip to memory ahead of the loads).  With the gate behind them all of the tile's operands are live across it: 61
-// registers spilled under the 128 the kernel may use for two workgroups per CU (round 4).  Off.
-#ifndef HPS_MG_GATE8_BEHIND
-#define HPS_MG_GATE8_BEHIND 0
-#endif
 #ifndef HPS_MG_OFF32
 #define HPS_MG_OFF32 1
 #endif
@@ -555,55 +549,19 @@ __device__ __forceinline__ void smooth_tile (double (&s_phi)[2][TS::AY*TS::AX], 
 
 // NSW red-black half-sweeps per launch: 4 (one GSRB^4 of the reference) or 8 (the two consecutive
 // GSRB^4 that end a V-cycle on level 0, fused: one pass over HBM instead of two)
-// POST: the launch that ends the last V-cycle enqueued so far also does what k_post_norms does (below): the workgroup that
-// finishes last -- a counter -- evaluates the stopping rule for the kernels gated behind the solve and posts the norms to the
-// host.  One launch (4.7 us between the last V-cycle and the gated push) less on a slice's chain.
-struct PostArgs { const unsigned long long* src; volatile unsigned long long* dst; int nwords; volatile unsigned long long* seq_slot;
-                  unsigned long long seq; int* go_word; StopRule after; unsigned int* counter; };
-
-__device__ __forceinline__ void post_epilogue (const PostArgs& pa)      // every workgroup of the launch, whole, at its end
-{
-    __shared__ int s_last;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // This workgroup's norm atomics (thread 0's, block_max_to) must have been performed before it is counted: wait for
-        // their acknowledgement.  NOT a __threadfence(): a device-scope release on this GPU writes the XCD's L2 back, once per
-        // workgroup -- measured: the launch took 66 us instead of 34.  The norms are device-scope atomics, read back below
-        // by device-scope atomic loads: no cache in between.
-        HPS_OWN_ATOMICS_ACKNOWLEDGED();
-        // two levels of counters (16 + 1): one counter for all workgroups is a chain of ~500 same-address atomics of ~20 ns each
-        const unsigned nb = gridDim.x, c = blockIdx.x & 15u, want = (nb - c + 15u) >> 4;
-        int last = 0;
-        if (atomicAdd(pa.counter + 1 + c, 1u) == want - 1u) {
-            __hip_atomic_store(pa.counter + 1 + c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = (atomicAdd(pa.counter, 1u) == (nb < 16u ? nb : 16u) - 1u) ? 1 : 0;
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) __hip_atomic_store(pa.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    {   const bool act = vcycle_active<true>(pa.after);
-        if (threadIdx.x == 0) *pa.go_word = act ? 0 : 1; }
-    for (int w = threadIdx.x; w < pa.nwords; w += blockDim.x)
-        pa.dst[w] = __hip_atomic_load(pa.src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    HPS_HOST_STORES_ACKNOWLEDGED();
-    __syncthreads();
-    if (threadIdx.x == 0) *pa.seq_slot = pa.seq;
-}
-
-template <class TS, bool CC, int SRC, bool DO_RES, bool FUSE_R, int NSW = 4, bool POST = false, bool RPULL = false>
+template <class TS, bool CC, int SRC, bool DO_RES, bool FUSE_R, int NSW = 4, bool RPULL = false>
 #ifndef HPS_MG_NODAL_WAVES
 #define HPS_MG_NODAL_WAVES 4
 #endif
 __global__ __launch_bounds__(TS::NT, (RPULL && TS::GPAIRS > 1) ? 2 : (CC || NSW == 4) ? 4 : HPS_MG_NODAL_WAVES)      // at most 128 VGPRs: two 512-thread workgroups per CU (several variants sit at 113-130); the pulling smoother with two pairs per thread (36 + 36 loads in flight) gets 256
 void k_smooth (LevBox b, FView phi_out, FView phi_out2, FView rhs, FView acf, FView phi_in, FView crse, FView res_out,
                FView cres_out, double facx, double facy, int ntx, unsigned long long* resnorm,
-               unsigned long long* rhsnorm, StopRule sr, PostArgs pa)
+               unsigned long long* rhsnorm, StopRule sr)
 {
     static_assert(!FUSE_R || (CC && DO_RES), "fused restriction is cell-centred only");
-    static_assert(!POST || NSW != 4, "the post rides on the fused level-0 pass");
-    if (NSW != 4 && !(HPS_MG_GATE8_BEHIND && !POST) && !vcycle_active(sr)) { if (POST) post_epilogue(pa); return; }       // (the 4-sweep kernels read the gate behind their loads, see smooth_tile)
+    // (the 4-sweep kernels read the gate behind their loads, see smooth_tile; the 8-sweep pass first: with the gate behind its
+    //  loads all of the tile's operands are live across it, 61 registers spilled under its 128-register cap, round 4)
+    if (NSW != 4 && !vcycle_active(sr)) return;
     constexpr int GT_X = TS::TX, GT_Y = TS::TY;
     __shared__ double s_phi[2][TS::AY*TS::AX];
     __shared__ double s_red[TS::NT/64];
@@ -622,12 +580,11 @@ void k_smooth (LevBox b, FView phi_out, FView phi_out2, FView rhs, FView acf, FV
     // every swept cell and its ring strictly inside the unknowns' box and off the walls
     const bool interior = (gi0 - 1 >= b.vlx) && (gi0 + GT_X <= b.vhx) && (gj0 - 1 >= b.vly) && (gj0 + GT_Y <= b.vhy)
                        && (gi0 > b.lox) && (gi0 + GT_X - 1 < b.hix) && (gj0 > b.loy) && (gj0 + GT_Y - 1 < b.hiy);
-    constexpr bool GATE_IN = (NSW == 4) || (HPS_MG_GATE8_BEHIND && !POST);
+    constexpr bool GATE_IN = (NSW == 4);
     if (interior) smooth_tile<TS, CC, SRC, DO_RES, FUSE_R, true, NSW, GATE_IN, RPULL>(s_phi, s_red, s_crs, b, phi_out, phi_out2, rhs, acf, phi_in, crse, res_out, cres_out,
                                                              facx, facy, gi0, gj0, resnorm, rhsnorm, sr);
     else          smooth_tile<TS, CC, SRC, DO_RES, FUSE_R, false, NSW, GATE_IN, RPULL>(s_phi, s_red, s_crs, b, phi_out, phi_out2, rhs, acf, phi_in, crse, res_out, cres_out,
                                                               facx, facy, gi0, gj0, resnorm, rhsnorm, sr);
-    if (POST) post_epilogue(pa);
 }
 
 // coarse = R(fine): 4-average (cell-centred) or 9-point full weighting (nodal)
@@ -688,49 +645,26 @@ __device__ __forceinline__ double lprolong (const LView& c, int i, int j)
     return c(ic, jc);
 }
 
-// A level is worked either by the whole workgroup -- its threads as a 32-wide patch swept over the level (no integer divisions in
-// the loops), phases separated by __syncthreads -- or, round 6, by WAVE 0 ALONE: levels of at most LOWV_WAVE_CELLS points (15^2
-// unknowns and below) as a 16 x 4 patch of the 64 lanes, phases separated by a fence only.  A phase of the generic lower V costs
-// ~900 clocks whatever the level holds (the barrier of 16 waves + an LDS round trip: shader-clock stamps, scripts/diag_mg.py,
-// 84 k clocks per V-cycle at 1023^2 of which the 16 sweeps of the 3 x 3 bottom level alone 14.8 k); in one wave it is the LDS
-// round trip.  Same per-point expressions, same values: only who computes them changes.
-// MEASURED (round 6, profiles/r06_lowv_wave_ab.txt, 1023^2): Bx/By solve 371.8 us per slice with every level on the whole workgroup,
-// 396.3 with the levels of <= 17^2 points on wave 0 alone, 488 with the 33^2 level there too: one wave has nothing to hide its own
-// LDS round trips behind (a 15^2 level is four dependent trips per phase), sixteen waves overlap theirs.  Kept as a switch
-// (HPS_MG_LOWV_WAVE=1), parity-tested by the same multigrid tests, OFF by default.
-struct LowMap { int ti, tj, si, sj, lin, nlin; };
-template <bool WAVE>
-__device__ __forceinline__ LowMap low_map ()
-{
-    if (WAVE) return LowMap{(int)(threadIdx.x & 15), (int)((threadIdx.x & 63) >> 4), 16, 4, (int)(threadIdx.x & 63), 64};
-    return LowMap{(int)(threadIdx.x & 31), (int)(threadIdx.x >> 5), 32, (int)(blockDim.x >> 5), (int)threadIdx.x, (int)blockDim.x};
-}
-template <bool WAVE>
-__device__ __forceinline__ void low_sync ()
-{
-    if (WAVE) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }
-    else __syncthreads();
-}
-#define HPS_LOW_FOR_MAP(mp, l, i, j)                                                        \
-    for (int j = (l).b.vly + (mp).tj; j <= (l).b.vhy; j += (mp).sj)                         \
-        for (int i = (l).b.vlx + (mp).ti; i <= (l).b.vhx; i += (mp).si)
-// (whole workgroup, outside the helpers below)
+// Every level is worked by the whole workgroup: its threads as a 32-wide patch swept over the level (no integer divisions in the
+// loops), phases separated by __syncthreads.  (Round 6 measured the levels of at most 17^2 points on wave 0 alone, phases separated
+// by a fence only: slower, 396.3 against 371.8 us per slice at 1023^2, and 336 against 331 with batched phases -- a phase is bound
+// by its instruction stream, not by the barrier: DESIGN section 4 "tried", profiles/r06_lowv_wave_ab.txt.)
 #define HPS_LOW_FOR_VALID(l, i, j)                                                          \
     for (int j = (l).b.vly + (int)(threadIdx.x >> 5); j <= (l).b.vhy; j += (int)(blockDim.x >> 5))   \
         for (int i = (l).b.vlx + (int)(threadIdx.x & 31); i <= (l).b.vhx; i += 32)
 
 __device__ __forceinline__ double low_fac (double f0, int l) { for (int k = 0; k < l; ++k) f0 *= 0.25; return f0; }      // (exact: powers of two)
 
-template <bool CC, bool WAVE>
+template <bool CC>
 __device__ void low_sweeps (lds_double* base, const LowLev& l, double facx, double facy, int nsweeps, int n0 = 0, int n1 = 2)
 {
-    // A half-sweep touches the points of one colour only: the threads are mapped onto THOSE -- a patch 16 half-columns wide
-    // (8 in a lone wave), so a 31^2 level is one trip of 496 threads (8 waves: two per SIMD) instead of 961 threads of which
-    // every other one sits out (16 waves: four per SIMD, all of them issuing the loop's ~150 instructions)
-    const int ti = WAVE ? (int)(threadIdx.x & 7) : (int)(threadIdx.x & 15), tj = WAVE ? (int)((threadIdx.x & 63) >> 3) : (int)(threadIdx.x >> 4);
-    const int si = WAVE ? 8 : 16, sj = WAVE ? 8 : (int)(blockDim.x >> 4);
+    // A half-sweep touches the points of one colour only: the threads are mapped onto THOSE -- a patch 16 half-columns wide,
+    // so a 31^2 level is one trip of 496 threads (8 waves: two per SIMD) instead of 961 threads of which every other one sits
+    // out (16 waves: four per SIMD, all of them issuing the loop's ~150 instructions)
+    const int ti = (int)(threadIdx.x & 15), tj = (int)(threadIdx.x >> 4);
+    const int si = 16, sj = (int)(blockDim.x >> 4);
     const LView cinv = lplane(base, l, 7);
-    if (!WAVE && !CC && l.b.vhy - l.b.vly < sj && l.b.vhx - l.b.vlx < 2*si) {
+    if (!CC && l.b.vhy - l.b.vly < sj && l.b.vhx - l.b.vlx < 2*si) {
         // One trip per thread (every level the node-centred lower V holds): the thread's row is fixed and its point alternates
         // between two columns with the colour -- both points' offsets, coefficients and right-hand sides are set up ONCE, ahead
         // of the half-sweeps, whose bodies are then four neighbour reads, six fp64 operations and a store.  (The stamps had
@@ -782,68 +716,64 @@ __device__ void low_sweeps (lds_double* base, const LowLev& l, double facx, doub
                 }
             }
         }
-        low_sync<WAVE>();
+        __syncthreads();
     }
 }
 
 // coefficient of level c from level f (average_down_acoef) and the inverse diagonals of a level
-template <bool CC, bool WAVE>
+template <bool CC>
 __device__ void low_hier_level (lds_double* base, const LowLev& f, const LowLev& c)
 {
-    const LowMap mp = low_map<WAVE>();
     const LView fine = lplane(base, f, 0), crse = lplane(base, c, 0);
     // (the walls of every plane hold the zeros the kernel starts from: only unknowns are ever written)
-    HPS_LOW_FOR_MAP(mp, c, i, j) crse(i, j) = lrestrict<CC>(fine, i, j);
-    low_sync<WAVE>();
+    HPS_LOW_FOR_VALID(c, i, j) crse(i, j) = lrestrict<CC>(fine, i, j);
+    __syncthreads();
 }
-template <bool CC, bool WAVE>
+template <bool CC>
 __device__ void low_cinv_level (lds_double* base, const LowLev& l, double fx, double fy)
 {
-    const LowMap mp = low_map<WAVE>();
     const LView acf = lplane(base, l, 0), cinv = lplane(base, l, 7);
-    HPS_LOW_FOR_MAP(mp, l, i, j) cinv(i, j) = 1.0/diag_c0<CC>(i, j, l.b, acf(i, j), fx, fy);
+    HPS_LOW_FOR_VALID(l, i, j) cinv(i, j) = 1.0/diag_c0<CC>(i, j, l.b, acf(i, j), fx, fy);
 }
 
 // down-leg of level l: cor = 0, four half-sweeps, residual, its restriction = right-hand side of level c
-template <bool CC, bool WAVE>
+template <bool CC>
 __device__ void low_down_level (lds_double* base, const LowLev& l, const LowLev& c, double facx, double facy, int n0, int n1)
 {
-    const LowMap mp = low_map<WAVE>();
     // cor = 0 and the walls of rescor = 0 (the nodal restriction reads them): both still hold the zeros the kernel starts from --
     // a level is visited once per launch -- so neither costs a phase of its own (round 6: 13 of the ~105 barrier-separated
     // phases of a V-cycle at 1023^2)
-    low_sweeps<CC, WAVE>(base, l, facx, facy, 4, n0, n1);
+    low_sweeps<CC>(base, l, facx, facy, 4, n0, n1);
     {   // residual -> rescor
         const LView acf = lplane(base, l, 0);
-        HPS_LOW_FOR_MAP(mp, l, i, j) {
+        HPS_LOW_FOR_VALID(l, i, j) {
             const double a = acf(i, j);
             for (int n = n0; n < n1; ++n) {
                 const LView rhs = lplane(base, l, 1 + n), phi = lplane(base, l, 3 + n), rc = lplane(base, l, 5 + n);
                 rc(i, j) = residual_at<false>((const lds_double*)&phi(i, j), l.nxb, i, j, l.b, rhs(i, j), a, facx, facy);
             }
         }
-        low_sync<WAVE>();
+        __syncthreads();
     }
     {   // restriction -> res of the next level
-        HPS_LOW_FOR_MAP(mp, c, i, j) {
+        HPS_LOW_FOR_VALID(c, i, j) {
             for (int n = n0; n < n1; ++n) lplane(base, c, 1 + n)(i, j) = lrestrict<CC>(lplane(base, l, 5 + n), i, j);
         }
-        low_sync<WAVE>();
+        __syncthreads();
     }
 }
 // up-leg of level l: cor += P(cor of level c), four half-sweeps
-template <bool CC, bool WAVE>
+template <bool CC>
 __device__ void low_up_level (lds_double* base, const LowLev& l, const LowLev& c, double facx, double facy, int n0, int n1)
 {
-    const LowMap mp = low_map<WAVE>();
-    HPS_LOW_FOR_MAP(mp, l, i, j) {
+    HPS_LOW_FOR_VALID(l, i, j) {
         for (int n = n0; n < n1; ++n) {
             const LView fine = lplane(base, l, 3 + n);
             fine(i, j) = fine(i, j) + lprolong<CC>(lplane(base, c, 3 + n), i, j);
         }
     }
-    low_sync<WAVE>();
-    low_sweeps<CC, WAVE>(base, l, facx, facy, 4, n0, n1);
+    __syncthreads();
+    low_sweeps<CC>(base, l, facx, facy, 4, n0, n1);
 }
 
 // The bottom level of a 2^K - 1 grid holds 3 x 3 unknowns and takes 16+ half-sweeps (HpMultiGrid.cpp:854-1033): as phases of the
@@ -901,129 +831,12 @@ __device__ __forceinline__ void low_bottom_regs_p (lds_double* base, const LowLe
     }
 }
 template <bool CC>
-__device__ void low_bottom_regs (lds_double* base, const LowLev& l, double facx, double facy, int nsweeps, int n0, int n1)
+__device__ void low_bottom_lane (lds_double* base, const LowLev& l, double facx, double facy, int nsweeps, int n0, int n1)
 {
     if (((l.b.vlx + l.b.vly) & 1) == 0) low_bottom_regs_p<CC, 0>(base, l, facx, facy, nsweeps, n0, n1);
     else low_bottom_regs_p<CC, 1>(base, l, facx, facy, nsweeps, n0, n1);
-}
-template <bool CC>
-__device__ void low_bottom_lane (lds_double* base, const LowLev& l, double facx, double facy, int nsweeps, int n0, int n1)
-{
-    low_bottom_regs<CC>(base, l, facx, facy, nsweeps, n0, n1);
     __syncthreads();
 }
-
-// ---- one wave, batched phases -------------------------------------------------------------------------------------------------
-// The lone-wave phases above lose because a phase of several trips is several dependent LDS round trips: the compiler cannot move
-// a trip's reads above the previous trip's writes (it does not know that a phase's outputs and inputs are disjoint planes / colours).
-// Here every phase has a compile-time number of trips (TJ x TI, predicates for the level's real extent), computes ALL of a lane's
-// points into registers first and stores them afterwards: one round trip per phase, as with k_lower_v3's register blocks.
-// Patches: 16 x 4 lanes over all points (TI trips of 16 columns, TJ of 4 rows); 8 x 8 lanes over the half-columns of one colour.
-template <int TJ, int TI, class F>
-__device__ __forceinline__ void wv_all (const LevBox& b, F&& f)            // f(i, j, slot): slot = compile-time-indexable trip number
-{
-    const int lane = (int)(threadIdx.x & 63), ti = lane & 15, tj = lane >> 4;
-#pragma unroll
-    for (int m = 0; m < TJ; ++m)
-#pragma unroll
-        for (int q = 0; q < TI; ++q) {
-            const int j = b.vly + tj + 4*m, i = b.vlx + ti + 16*q;
-            f(i, j, m*TI + q, j <= b.vhy && i <= b.vhx);
-        }
-}
-template <bool CC, int TJ, int TI>          // TJ: trips of 8 rows, TI: trips of 16 columns (8 half-columns)
-__device__ void wv_sweeps (lds_double* base, const LowLev& l, double facx, double facy, int nsweeps, int n0, int n1)
-{
-    const int lane = (int)(threadIdx.x & 63), ti = lane & 7, tj = lane >> 3;
-    const LView cinv = lplane(base, l, 7);
-    const bool two = (n1 - n0) == 2;
-    const LView rhs0 = lplane(base, l, 1 + n0), phi0 = lplane(base, l, 3 + n0), rhs1 = lplane(base, l, n1), phi1 = lplane(base, l, 2 + n1);
-    for (int is = 0; is < nsweeps; ++is) {
-        double o0[TJ*TI], o1[TJ*TI];
-#pragma unroll
-        for (int m = 0; m < TJ; ++m)
-#pragma unroll
-            for (int q = 0; q < TI; ++q) {
-                const int j = l.b.vly + tj + 8*m, i = l.b.vlx + ((l.b.vlx + j + is) & 1) + 2*(ti + 8*q);
-                const bool ok = j <= l.b.vhy && i <= l.b.vhx;
-                const int ic = ok ? i : l.b.vlx, jc = ok ? j : l.b.vly;
-                const double ci = cinv(ic, jc);
-                o0[m*TI + q] = (rhs0(ic, jc) - offdiag<CC, false>((const lds_double*)&phi0(ic, jc), l.nxb, ic, jc, l.b, facx, facy))*ci;
-                o1[m*TI + q] = two ? (rhs1(ic, jc) - offdiag<CC, false>((const lds_double*)&phi1(ic, jc), l.nxb, ic, jc, l.b, facx, facy))*ci : 0.0;
-            }
-#pragma unroll
-        for (int m = 0; m < TJ; ++m)
-#pragma unroll
-            for (int q = 0; q < TI; ++q) {
-                const int j = l.b.vly + tj + 8*m, i = l.b.vlx + ((l.b.vlx + j + is) & 1) + 2*(ti + 8*q);
-                if (j <= l.b.vhy && i <= l.b.vhx) { phi0(i, j) = o0[m*TI + q]; if (two) phi1(i, j) = o1[m*TI + q]; }
-            }
-        low_sync<true>();
-    }
-}
-template <bool CC, int TJ, int TI>
-__device__ void wv_hier_level (lds_double* base, const LowLev& f, const LowLev& c)
-{
-    const LView fine = lplane(base, f, 0), crse = lplane(base, c, 0);
-    double o[TJ*TI];
-    wv_all<TJ, TI>(c.b, [&] (int i, int j, int k, bool ok) { o[k] = lrestrict<CC>(fine, ok ? i : c.b.vlx, ok ? j : c.b.vly); });
-    wv_all<TJ, TI>(c.b, [&] (int i, int j, int k, bool ok) { if (ok) crse(i, j) = o[k]; });
-    low_sync<true>();
-}
-template <bool CC, int TJ, int TI>
-__device__ void wv_cinv_level (lds_double* base, const LowLev& l, double fx, double fy)
-{
-    const LView acf = lplane(base, l, 0), cinv = lplane(base, l, 7);
-    double o[TJ*TI];
-    wv_all<TJ, TI>(l.b, [&] (int i, int j, int k, bool ok) { const int ic = ok ? i : l.b.vlx, jc = ok ? j : l.b.vly; o[k] = 1.0/diag_c0<CC>(ic, jc, l.b, acf(ic, jc), fx, fy); });
-    wv_all<TJ, TI>(l.b, [&] (int i, int j, int k, bool ok) { if (ok) cinv(i, j) = o[k]; });
-}
-template <bool CC, int TJ, int TI, int SJ, int SI>
-__device__ void wv_down_level (lds_double* base, const LowLev& l, const LowLev& c, double facx, double facy, int n0, int n1)
-{
-    wv_sweeps<CC, SJ, SI>(base, l, facx, facy, 4, n0, n1);
-    const bool two = (n1 - n0) == 2;
-    {   // residual -> rescor
-        const LView acf = lplane(base, l, 0);
-        const LView rhs0 = lplane(base, l, 1 + n0), phi0 = lplane(base, l, 3 + n0), rc0 = lplane(base, l, 5 + n0);
-        const LView rhs1 = lplane(base, l, n1), phi1 = lplane(base, l, 2 + n1), rc1 = lplane(base, l, 4 + n1);
-        double o0[TJ*TI], o1[TJ*TI];
-        wv_all<TJ, TI>(l.b, [&] (int i, int j, int k, bool ok) {
-            const int ic = ok ? i : l.b.vlx, jc = ok ? j : l.b.vly;
-            const double a = acf(ic, jc);
-            o0[k] = residual_at<false>((const lds_double*)&phi0(ic, jc), l.nxb, ic, jc, l.b, rhs0(ic, jc), a, facx, facy);
-            o1[k] = two ? residual_at<false>((const lds_double*)&phi1(ic, jc), l.nxb, ic, jc, l.b, rhs1(ic, jc), a, facx, facy) : 0.0; });
-        wv_all<TJ, TI>(l.b, [&] (int i, int j, int k, bool ok) { if (ok) { rc0(i, j) = o0[k]; if (two) rc1(i, j) = o1[k]; } });
-        low_sync<true>();
-    }
-    {   // restriction -> res of the next level
-        const LView rc0 = lplane(base, l, 5 + n0), rc1 = lplane(base, l, 4 + n1), r0 = lplane(base, c, 1 + n0), r1 = lplane(base, c, n1);
-        double o0[TJ*TI], o1[TJ*TI];
-        wv_all<TJ, TI>(c.b, [&] (int i, int j, int k, bool ok) {
-            const int ic = ok ? i : c.b.vlx, jc = ok ? j : c.b.vly;
-            o0[k] = lrestrict<CC>(rc0, ic, jc); o1[k] = two ? lrestrict<CC>(rc1, ic, jc) : 0.0; });
-        wv_all<TJ, TI>(c.b, [&] (int i, int j, int k, bool ok) { if (ok) { r0(i, j) = o0[k]; if (two) r1(i, j) = o1[k]; } });
-        low_sync<true>();
-    }
-}
-template <bool CC, int TJ, int TI, int SJ, int SI>
-__device__ void wv_up_level (lds_double* base, const LowLev& l, const LowLev& c, double facx, double facy, int n0, int n1)
-{
-    const bool two = (n1 - n0) == 2;
-    const LView f0 = lplane(base, l, 3 + n0), f1 = lplane(base, l, 2 + n1), c0 = lplane(base, c, 3 + n0), c1 = lplane(base, c, 2 + n1);
-    double o0[TJ*TI], o1[TJ*TI];
-    wv_all<TJ, TI>(l.b, [&] (int i, int j, int k, bool ok) {
-        const int ic = ok ? i : l.b.vlx, jc = ok ? j : l.b.vly;
-        o0[k] = f0(ic, jc) + lprolong<CC>(c0, ic, jc); o1[k] = two ? f1(ic, jc) + lprolong<CC>(c1, ic, jc) : 0.0; });
-    wv_all<TJ, TI>(l.b, [&] (int i, int j, int k, bool ok) { if (ok) { f0(i, j) = o0[k]; if (two) f1(i, j) = o1[k]; } });
-    low_sync<true>();
-    wv_sweeps<CC, SJ, SI>(base, l, facx, facy, 4, n0, n1);
-}
-// by the level's extent: up to 16 x 16 unknowns batched (trips 4 x 1 over all points, 2 x 1 over a colour); larger ones through the
-// unbatched helpers (batched with 8 x 2 trips the kernel spilled 757 registers under its 1024-thread cap)
-#define HPS_WV_DISPATCH(l, CALL_SMALL, CALL_BIG) do { if ((l).b.vhx - (l).b.vlx < 16 && (l).b.vhy - (l).b.vly < 16) { CALL_SMALL; } else { CALL_BIG; } } while (0)
-
-constexpr int LOWV_WAVE_CELLS = 17*17;      // levels of at most this many points (walls included) are wave 0's alone
 
 // levels lv[0..nl-1] (finest first): cor[0] = lower-V(res[0]); mirrors the single-block bottom
 // solver of the reference (HpMultiGrid.cpp:854-1033), 16+ sweeps on the last level.  Level 0's
@@ -1032,18 +845,15 @@ constexpr int LOWV_WAVE_CELLS = 17*17;      // levels of at most this many point
 template <bool CC>
 __global__ __launch_bounds__(1024)
 void k_lower_v (const LowLev* __restrict__ lv, int nl, const double* __restrict__ acf_g, const double* __restrict__ res_g,
-                double* __restrict__ cor_g, double facx0, double facy0, int nsweeps_bottom, StopRule sr, FView fine_res = FView{},
-                int wave_cells = 0, int bottom_lane = 0)
+                double* __restrict__ cor_g, double facx0, double facy0, int nsweeps_bottom, StopRule sr, FView fine_res = FView{})
 {
     if (!vcycle_active(sr)) return;
     extern __shared__ __attribute__((aligned(16))) double lds_raw[];
     lds_double* base = (lds_double*)lds_raw;
-    // grid = 2 (HPS_MG_LOWV_SPLIT, round 6): one field component per workgroup -- the components only meet in norms this kernel
-    // does not take, so two CUs need no synchronisation and every barrier-separated phase carries half the LDS traffic
+    // grid = 2 on node-centred grids (round 6): one field component per workgroup -- the components only meet in norms this
+    // kernel does not take, so two CUs need no synchronisation and every barrier-separated phase carries half the LDS traffic
+    // (Bx/By solve at 1023^2 375 -> 361 us per slice; 512 threads the same, 256 slower: profiles/r06_lowv_ab.txt)
     const int n0 = gridDim.x == 2 ? (int)blockIdx.x : 0, n1 = gridDim.x == 2 ? n0 + 1 : 2;
-    // nw: first level that wave 0 works alone (nl: none)
-    int nw = nl;
-    for (int il = nl - 1; il >= 0; --il) if (lv[il].cells <= wave_cells) nw = il;
     MG_STAMP(8);
     {   // every plane of every level starts from zero (walls, corrections, the coefficient planes' rims)
         const LowLev last = lv[nl - 1];
@@ -1070,48 +880,23 @@ void k_lower_v (const LowLev* __restrict__ lv, int nl, const double* __restrict_
     }
     // (every level's descriptor is copied out of global memory ONCE per use below: handed on as a reference to lv[il] itself, each
     //  phase behind a barrier began with three to four dependent scalar loads of its fields -- a third of a phase's ~900 clocks)
-    // coefficient hierarchy and inverse diagonals of the levels the whole workgroup works (one division per point and V-cycle)
-    for (int il = 1; il < nw; ++il) { const LowLev f = lv[il - 1], c = lv[il]; low_hier_level<CC, false>(base, f, c); }
+    // coefficient hierarchy and inverse diagonals (one division per point and V-cycle)
+    for (int il = 1; il < nl; ++il) { const LowLev f = lv[il - 1], c = lv[il]; low_hier_level<CC>(base, f, c); }
     MG_STAMP(9);
-    for (int il = 0; il < nw; ++il) { const LowLev l = lv[il]; low_cinv_level<CC, false>(base, l, low_fac(facx0, il), low_fac(facy0, il)); }
+    for (int il = 0; il < nl; ++il) { const LowLev l = lv[il]; low_cinv_level<CC>(base, l, low_fac(facx0, il), low_fac(facy0, il)); }
     __syncthreads();
     MG_STAMP(10);
-    const int nbig_down = nw < nl - 1 ? nw : nl - 1;          // levels 0 .. nbig_down-1 go down (and later up) with the whole workgroup
-    for (int il = 0; il < nbig_down; ++il) { const LowLev l = lv[il], c = lv[il + 1]; low_down_level<CC, false>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1); }
+    for (int il = 0; il < nl - 1; ++il) { const LowLev l = lv[il], c = lv[il + 1]; low_down_level<CC>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1); }
     MG_STAMP(11);
-    if (nw >= nl) {
+    {
         const LowLev l = lv[nl - 1];
-        if (bottom_lane && l.b.vhx - l.b.vlx < 3 && l.b.vhy - l.b.vly < 3)
+        if (l.b.vhx - l.b.vlx < 3 && l.b.vhy - l.b.vly < 3)
             low_bottom_lane<CC>(base, l, low_fac(facx0, nl - 1), low_fac(facy0, nl - 1), nsweeps_bottom, n0, n1);
         else
-        low_sweeps<CC, false>(base, l, low_fac(facx0, nl - 1), low_fac(facy0, nl - 1), nsweeps_bottom, n0, n1);
-    } else {
-        if (threadIdx.x < 64) {
-            // wave 0: what is left of the coefficient hierarchy, the down-legs below the workgroup's levels, the bottom, the up-legs
-            for (int il = nw > 0 ? nw : 1; il < nl; ++il) { const LowLev f = lv[il - 1], c = lv[il];
-                HPS_WV_DISPATCH(c, (wv_hier_level<CC, 4, 1>(base, f, c)), (low_hier_level<CC, true>(base, f, c))); }
-            for (int il = nw; il < nl; ++il) { const LowLev l = lv[il];
-                HPS_WV_DISPATCH(l, (wv_cinv_level<CC, 4, 1>(base, l, low_fac(facx0, il), low_fac(facy0, il))), (low_cinv_level<CC, true>(base, l, low_fac(facx0, il), low_fac(facy0, il)))); }
-            low_sync<true>();
-            for (int il = nw; il < nl - 1; ++il) { const LowLev l = lv[il], c = lv[il + 1];
-                HPS_WV_DISPATCH(l, (wv_down_level<CC, 4, 1, 2, 1>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1)),
-                                   (low_down_level<CC, true>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1))); }
-            {   const LowLev l = lv[nl - 1];
-                if (bottom_lane && l.b.vhx - l.b.vlx < 3 && l.b.vhy - l.b.vly < 3) {
-                    // (one lane per component: thread 0, and thread 1 without the split; the helper's barrier is the workgroup's: not here)
-                    low_bottom_regs<CC>(base, l, low_fac(facx0, nl - 1), low_fac(facy0, nl - 1), nsweeps_bottom, n0, n1);
-                    low_sync<true>();
-                } else
-                HPS_WV_DISPATCH(l, (wv_sweeps<CC, 2, 1>(base, l, low_fac(facx0, nl - 1), low_fac(facy0, nl - 1), nsweeps_bottom, n0, n1)),
-                                   (low_sweeps<CC, true>(base, l, low_fac(facx0, nl - 1), low_fac(facy0, nl - 1), nsweeps_bottom, n0, n1))); }
-            for (int il = nl - 2; il >= nw; --il) { const LowLev l = lv[il], c = lv[il + 1];
-                HPS_WV_DISPATCH(l, (wv_up_level<CC, 4, 1, 2, 1>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1)),
-                                   (low_up_level<CC, true>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1))); }
-        }
-        __syncthreads();
+        low_sweeps<CC>(base, l, low_fac(facx0, nl - 1), low_fac(facy0, nl - 1), nsweeps_bottom, n0, n1);
     }
     MG_STAMP(12);
-    for (int il = nbig_down - 1; il >= 0; --il) { const LowLev l = lv[il], c = lv[il + 1]; low_up_level<CC, false>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1); }
+    for (int il = nl - 2; il >= 0; --il) { const LowLev l = lv[il], c = lv[il + 1]; low_up_level<CC>(base, l, c, low_fac(facx0, il), low_fac(facy0, il), n0, n1); }
     MG_STAMP(13);
     {
         const LowLev l = lv[0];
@@ -1121,18 +906,23 @@ void k_lower_v (const LowLev* __restrict__ lv, int nl, const double* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Cell-centred lower V, register/LDS resident, from the first level with at most 64 x 64 cells.
-// Every level is worked in 2 x 2 cell blocks, one thread per block: the block's correction, rhs and
-// inverse diagonal sit in registers, so a red-black half-sweep updates two cells with two LDS reads
-// each (the other two neighbours are the thread's own cells), the residual's 4-average for the
-// restriction and the piecewise-constant prolongation are thread-local, and the 2 x 2 bottom level is
-// one lane's registers.  LDS: the correction of every level (two ringed planes, for the neighbours);
-// below level A also rhs (2), coefficient and inverse diagonal planes (level A reloads its rhs from
-// HBM for the up-leg).  Levels of at most 64 blocks run in wave 0 alone without workgroup barriers.
-// The first sweep of every down-leg level starts from cor = 0, where the update is rhs/diag exactly.
+// Cell-centred lower V (k_lower_v3), register/LDS resident, from the first level with at most 64 x 64 cells, ONE field
+// component per workgroup (grid = 2).  The two components of the solve only meet in the norm, which the lower V does not
+// take, so two workgroups on two CUs need no synchronisation at all, and every barrier phase of the 64 x 64 and 32 x 32
+// levels carries half the LDS traffic and half the fp64 instruction stream of one workgroup for both (one CU's LDS pipe and
+// VALUs were what bounded those phases: ~1800 cycles per half-sweep).
+// Every level is worked in 2 x 2 cell blocks, one thread per block: the block's correction, rhs and inverse diagonal sit in
+// registers, so a red-black half-sweep updates two cells with two LDS reads each (the other two neighbours are the thread's
+// own cells), the residual's 4-average for the restriction and the piecewise-constant prolongation are thread-local, and
+// the 2 x 2 bottom level is one lane's registers.  LDS per level: level A one ringed plane (cor); below it four: cor | res |
+// acf | 1/diag (level A keeps its rhs in registers).  Levels of at most 64 blocks run in wave 0 alone without workgroup
+// barriers.  The first sweep of every down-leg level starts from cor = 0, where the update is rhs/diag exactly.
+// Level A's inverse diagonals come from k_acf_pyramid (cinv_g: 4 divisions per thread and V-cycle less).  The gate of
+// the speculative V-cycle is evaluated AFTER the level-A loads have been issued: a kernel's first dependent read of
+// global memory costs ~1.5 us behind a kernel boundary (scripts/ubench/launch_floor.hip), and the two now overlap.
 constexpr int LOW2_MAXLEV = 8;
 struct Low2 { int nl; int total; int nx[LOW2_MAXLEV], ny[LOW2_MAXLEV], off[LOW2_MAXLEV];
-              int coff[LOW2_MAXLEV], cbase, ctot; };      // k_lower_v3: the levels' [acf | 1/diag] planes, one contiguous image from cbase
+              int coff[LOW2_MAXLEV], cbase, ctot; };      // the levels' [acf | 1/diag] planes, one contiguous image from cbase
 
 __device__ __forceinline__ LevBox cc_box (int nx, int ny) { return LevBox{0, 0, nx - 1, ny - 1, 0, 0, nx - 1, ny - 1}; }
 
@@ -1148,22 +938,17 @@ __device__ __forceinline__ void lvl_sync ()
 
 // a thread's 2 x 2 block: cells k = 0:(i,j) 1:(i+1,j) 2:(i,j+1) 3:(i+1,j+1); 0 and 3 have colour 0
 struct Blk {
-    lds_double *c0, *c1;      // the block's cell 0 in the two correction planes
+    lds_double* c0;           // the block's cell 0 in the correction plane
     int pitch;
     bool act;                 // this thread has a block on this level
     bool ok[4];               // cell inside the level (odd sizes)
     double fxm[2], fym[2];    // wall multipliers of the block's two columns / rows
-    double v0[4], v1[4];      // correction (both components)
-    double r0[4], r1[4], ci[4];
+    double v0[4];             // correction
+    double r0[4], ci[4];
 };
 
-// TWO = false: the functions below work on ONE component (planes selected by `cmp` in blk_geometry / the callers):
-// the levels that fit a wave are run by two waves, one per component, with no synchronisation between them (the
-// two components only meet in the norm) -- a lone wave is bound by its own instruction latencies, so halving the
-// stream per phase nearly halves the phase.
-
 // half-sweep of parity P (0: cells 0 and 3, 1: cells 1 and 2) + publication of the new values
-template <int P, bool WAVE, bool TWO = true>
+template <int P, bool WAVE>
 __device__ __forceinline__ void blk_sweep (Blk& B)
 {
     if (B.act) {
@@ -1171,123 +956,79 @@ __device__ __forceinline__ void blk_sweep (Blk& B)
         if (P == 0) {
             {   const double w0 = B.c0[-1], s0 = B.c0[-pt];
                 const double n0 = (B.r0[0] - (B.fxm[0]*(w0 + B.v0[1]) + B.fym[0]*(s0 + B.v0[2])))*B.ci[0];
-                if (B.ok[0]) { B.v0[0] = n0; B.c0[0] = n0; }
-                if (TWO) {
-                    const double w1 = B.c1[-1], s1 = B.c1[-pt];
-                    const double n1 = (B.r1[0] - (B.fxm[0]*(w1 + B.v1[1]) + B.fym[0]*(s1 + B.v1[2])))*B.ci[0];
-                    if (B.ok[0]) { B.v1[0] = n1; B.c1[0] = n1; }
-                } }
+                if (B.ok[0]) { B.v0[0] = n0; B.c0[0] = n0; } }
             {   const double e0 = B.c0[pt + 2], t0 = B.c0[2*pt + 1];
                 const double n0 = (B.r0[3] - (B.fxm[1]*(B.v0[2] + e0) + B.fym[1]*(B.v0[1] + t0)))*B.ci[3];
-                if (B.ok[3]) { B.v0[3] = n0; B.c0[pt + 1] = n0; }
-                if (TWO) {
-                    const double e1 = B.c1[pt + 2], t1 = B.c1[2*pt + 1];
-                    const double n1 = (B.r1[3] - (B.fxm[1]*(B.v1[2] + e1) + B.fym[1]*(B.v1[1] + t1)))*B.ci[3];
-                    if (B.ok[3]) { B.v1[3] = n1; B.c1[pt + 1] = n1; }
-                } }
+                if (B.ok[3]) { B.v0[3] = n0; B.c0[pt + 1] = n0; } }
         } else {
             {   const double e0 = B.c0[2], s0 = B.c0[1 - pt];
                 const double n0 = (B.r0[1] - (B.fxm[1]*(B.v0[0] + e0) + B.fym[0]*(s0 + B.v0[3])))*B.ci[1];
-                if (B.ok[1]) { B.v0[1] = n0; B.c0[1] = n0; }
-                if (TWO) {
-                    const double e1 = B.c1[2], s1 = B.c1[1 - pt];
-                    const double n1 = (B.r1[1] - (B.fxm[1]*(B.v1[0] + e1) + B.fym[0]*(s1 + B.v1[3])))*B.ci[1];
-                    if (B.ok[1]) { B.v1[1] = n1; B.c1[1] = n1; }
-                } }
+                if (B.ok[1]) { B.v0[1] = n0; B.c0[1] = n0; } }
             {   const double w0 = B.c0[pt - 1], t0 = B.c0[2*pt];
                 const double n0 = (B.r0[2] - (B.fxm[0]*(w0 + B.v0[3]) + B.fym[1]*(B.v0[0] + t0)))*B.ci[2];
-                if (B.ok[2]) { B.v0[2] = n0; B.c0[pt] = n0; }
-                if (TWO) {
-                    const double w1 = B.c1[pt - 1], t1 = B.c1[2*pt];
-                    const double n1 = (B.r1[2] - (B.fxm[0]*(w1 + B.v1[3]) + B.fym[1]*(B.v1[0] + t1)))*B.ci[2];
-                    if (B.ok[2]) { B.v1[2] = n1; B.c1[pt] = n1; }
-                } }
+                if (B.ok[2]) { B.v0[2] = n0; B.c0[pt] = n0; } }
         }
     }
     lvl_sync<WAVE>();
 }
 
 // down-leg sweeps from cor = 0: sweep 0 is rhs/diag on the colour-0 cells, then sweeps 1 .. nsw-1 (nsw even)
-template <bool WAVE, bool TWO = true>
+template <bool WAVE>
 __device__ __forceinline__ void blk_down_sweeps (Blk& B, int nsw)
 {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { B.v0[k] = 0.0; B.v1[k] = 0.0; }
+    for (int k = 0; k < 4; ++k) B.v0[k] = 0.0;
     if (B.act) {
-        if (B.ok[0]) { B.v0[0] = B.r0[0]*B.ci[0]; B.c0[0] = B.v0[0]; if (TWO) { B.v1[0] = B.r1[0]*B.ci[0]; B.c1[0] = B.v1[0]; } }
-        if (B.ok[3]) { B.v0[3] = B.r0[3]*B.ci[3]; B.c0[B.pitch + 1] = B.v0[3]; if (TWO) { B.v1[3] = B.r1[3]*B.ci[3]; B.c1[B.pitch + 1] = B.v1[3]; } }
+        if (B.ok[0]) { B.v0[0] = B.r0[0]*B.ci[0]; B.c0[0] = B.v0[0]; }
+        if (B.ok[3]) { B.v0[3] = B.r0[3]*B.ci[3]; B.c0[B.pitch + 1] = B.v0[3]; }
     }
     lvl_sync<WAVE>();
-    blk_sweep<1, WAVE, TWO>(B);
-    for (int s = 2; s < nsw; s += 2) { blk_sweep<0, WAVE, TWO>(B); blk_sweep<1, WAVE, TWO>(B); }
+    blk_sweep<1, WAVE>(B);
+    for (int s = 2; s < nsw; s += 2) { blk_sweep<0, WAVE>(B); blk_sweep<1, WAVE>(B); }
 }
 
 // The whole level is this one block (2 x 2 cells or fewer): every neighbour outside the block is the
 // zero ring, so all nsw sweeps from cor = 0 run in the lane's registers; published once at the end.
-template <bool TWO = true>
 __device__ __forceinline__ void blk_single_sweeps (Blk& B, int nsw)
 {
     // (every neighbour outside the block is the zero ring: 0 + v == v exactly, so the sums with it are left out -- this is a
     //  chain of 2 nsw dependent half-sweeps in one lane, every instruction of it is on the V-cycle's critical path)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { B.v0[k] = 0.0; B.v1[k] = 0.0; }
+    for (int k = 0; k < 4; ++k) B.v0[k] = 0.0;
     if (B.act) {
         for (int s = 0; s < nsw; s += 2) {
             {   const double a0 = (B.r0[0] - (B.fxm[0]*B.v0[1] + B.fym[0]*B.v0[2]))*B.ci[0];
                 const double b0 = (B.r0[3] - (B.fxm[1]*B.v0[2] + B.fym[1]*B.v0[1]))*B.ci[3];
                 if (B.ok[0]) B.v0[0] = a0;
-                if (B.ok[3]) B.v0[3] = b0;
-                if (TWO) {
-                    const double a1 = (B.r1[0] - (B.fxm[0]*B.v1[1] + B.fym[0]*B.v1[2]))*B.ci[0];
-                    const double b1 = (B.r1[3] - (B.fxm[1]*B.v1[2] + B.fym[1]*B.v1[1]))*B.ci[3];
-                    if (B.ok[0]) B.v1[0] = a1;
-                    if (B.ok[3]) B.v1[3] = b1;
-                } }
+                if (B.ok[3]) B.v0[3] = b0; }
             {   const double a0 = (B.r0[1] - (B.fxm[1]*B.v0[0] + B.fym[0]*B.v0[3]))*B.ci[1];
                 const double b0 = (B.r0[2] - (B.fxm[0]*B.v0[3] + B.fym[1]*B.v0[0]))*B.ci[2];
                 if (B.ok[1]) B.v0[1] = a0;
-                if (B.ok[2]) B.v0[2] = b0;
-                if (TWO) {
-                    const double a1 = (B.r1[1] - (B.fxm[1]*B.v1[0] + B.fym[0]*B.v1[3]))*B.ci[1];
-                    const double b1 = (B.r1[2] - (B.fxm[0]*B.v1[3] + B.fym[1]*B.v1[0]))*B.ci[2];
-                    if (B.ok[1]) B.v1[1] = a1;
-                    if (B.ok[2]) B.v1[2] = b1;
-                } }
+                if (B.ok[2]) B.v0[2] = b0; }
         }
         const int ok[4] = {0, 1, B.pitch, B.pitch + 1};
 #pragma unroll
-        for (int k = 0; k < 4; ++k) if (B.ok[k]) { B.c0[ok[k]] = B.v0[k]; if (TWO) B.c1[ok[k]] = B.v1[k]; }
+        for (int k = 0; k < 4; ++k) if (B.ok[k]) B.c0[ok[k]] = B.v0[k];
     }
 }
 
 // residuals of the block's four cells (0 for cells outside the level)
-template <bool TWO = true>
 __device__ __forceinline__ void blk_residual (const Blk& B, int i, int j, const LevBox& b, const double (&a)[4],
-                                              double fx, double fy, double (&q0)[4], double (&q1)[4])
+                                              double fx, double fy, double (&q0)[4])
 {
     const int pt = B.pitch;
-    {   const double w00 = B.c0[-1], s00 = B.c0[-pt], e01 = B.c0[2], s01 = B.c0[1 - pt];
-        const double w02 = B.c0[pt - 1], n02 = B.c0[2*pt], e03 = B.c0[pt + 2], n03 = B.c0[2*pt + 1];
-        q0[0] = residual_v<false>(B.v0[0], w00, B.v0[1], s00, B.v0[2], i, j, b, B.r0[0], a[0], fx, fy);
-        q0[1] = residual_v<false>(B.v0[1], B.v0[0], e01, s01, B.v0[3], i + 1, j, b, B.r0[1], a[1], fx, fy);
-        q0[2] = residual_v<false>(B.v0[2], w02, B.v0[3], B.v0[0], n02, i, j + 1, b, B.r0[2], a[2], fx, fy);
-        q0[3] = residual_v<false>(B.v0[3], B.v0[2], e03, B.v0[1], n03, i + 1, j + 1, b, B.r0[3], a[3], fx, fy); }
-    if (TWO) {
-        const double w10 = B.c1[-1], s10 = B.c1[-pt], e11 = B.c1[2], s11 = B.c1[1 - pt];
-        const double w12 = B.c1[pt - 1], n12 = B.c1[2*pt], e13 = B.c1[pt + 2], n13 = B.c1[2*pt + 1];
-        q1[0] = residual_v<false>(B.v1[0], w10, B.v1[1], s10, B.v1[2], i, j, b, B.r1[0], a[0], fx, fy);
-        q1[1] = residual_v<false>(B.v1[1], B.v1[0], e11, s11, B.v1[3], i + 1, j, b, B.r1[1], a[1], fx, fy);
-        q1[2] = residual_v<false>(B.v1[2], w12, B.v1[3], B.v1[0], n12, i, j + 1, b, B.r1[2], a[2], fx, fy);
-        q1[3] = residual_v<false>(B.v1[3], B.v1[2], e13, B.v1[1], n13, i + 1, j + 1, b, B.r1[3], a[3], fx, fy);
-    }
+    const double w00 = B.c0[-1], s00 = B.c0[-pt], e01 = B.c0[2], s01 = B.c0[1 - pt];
+    const double w02 = B.c0[pt - 1], n02 = B.c0[2*pt], e03 = B.c0[pt + 2], n03 = B.c0[2*pt + 1];
+    q0[0] = residual_v<false>(B.v0[0], w00, B.v0[1], s00, B.v0[2], i, j, b, B.r0[0], a[0], fx, fy);
+    q0[1] = residual_v<false>(B.v0[1], B.v0[0], e01, s01, B.v0[3], i + 1, j, b, B.r0[1], a[1], fx, fy);
+    q0[2] = residual_v<false>(B.v0[2], w02, B.v0[3], B.v0[0], n02, i, j + 1, b, B.r0[2], a[2], fx, fy);
+    q0[3] = residual_v<false>(B.v0[3], B.v0[2], e03, B.v0[1], n03, i + 1, j + 1, b, B.r0[3], a[3], fx, fy);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { if (!B.ok[k]) { q0[k] = 0.0; q1[k] = 0.0; } else if (!TWO) q1[k] = 0.0; }
+    for (int k = 0; k < 4; ++k) if (!B.ok[k]) q0[k] = 0.0;
 }
 
-// geometry of thread t's block on a level of nx x ny cells whose planes start at `lev` (pitch nx + 2);
-// cmp: the component whose planes become c0 (one-component mode), 0 otherwise
-__device__ __forceinline__ void blk_geometry (Blk& B, lds_double* lev, int nx, int ny, int t, double fx, double fy, int& i, int& j,
-                                              int cmp = 0)
+// geometry of thread t's block on a level of nx x ny cells whose plane starts at `lev` (pitch nx + 2)
+__device__ __forceinline__ void blk_geometry (Blk& B, lds_double* lev, int nx, int ny, int t, double fx, double fy, int& i, int& j)
 {
     const int nbx = (nx + 1) >> 1, nby = (ny + 1) >> 1;
     const int lg = (nbx <= 1) ? 0 : 32 - __clz(nbx - 1);       // blocks per row rounded up to a power of two
@@ -1295,278 +1036,14 @@ __device__ __forceinline__ void blk_geometry (Blk& B, lds_double* lev, int nx, i
     B.act = (bi < nbx) && (bj < nby);
     i = 2*bi; j = 2*bj;
     B.pitch = nx + 2;
-    const int ps = B.pitch*(ny + 2);
     const int o = B.act ? (j + 1)*B.pitch + i + 1 : B.pitch + 1;
-    B.c0 = lev + cmp*ps + o; B.c1 = B.c0 + ps;
+    B.c0 = lev + o;
     B.ok[0] = B.act; B.ok[1] = B.act && (i + 1 < nx); B.ok[2] = B.act && (j + 1 < ny); B.ok[3] = B.ok[1] && B.ok[2];
     B.fxm[0] = wall_mult<true>(i, 0, nx - 1, fx); B.fxm[1] = wall_mult<true>(i + 1, 0, nx - 1, fx);
     B.fym[0] = wall_mult<true>(j, 0, ny - 1, fy); B.fym[1] = wall_mult<true>(j + 1, 0, ny - 1, fy);
 }
 
 __device__ __forceinline__ double lvl_fac (double f0, int l) { for (int k = 0; k < l; ++k) f0 *= 0.25; return f0; }
-
-// levels >= 1 keep six LDS planes: cor0 cor1 | res0 res1 | acf | 1/diag (all ringed, pitch nx + 2).  With c0 = the
-// correction plane of component cmp: rhs of cmp = c0 + 2 ps, coefficient = c0 + (4 - cmp) ps, 1/diag = c0 + (5 - cmp) ps.
-
-// down-leg of level l >= 1: cor = GSRB^nsw(0), then (unless last) the restricted residual -> rhs of level l+1
-template <bool WAVE, bool TWO = true>
-__device__ __forceinline__ void low_down (lds_double* base, const Low2& d, int l, int t, double fx, double fy, int nsw, bool last,
-                                          int cmp = 0)
-{
-    const int nx = d.nx[l], ny = d.ny[l];
-    Blk B; int i, j;
-    blk_geometry(B, base + d.off[l], nx, ny, t, fx, fy, i, j, cmp);
-    const int ps = B.pitch*(ny + 2);
-    const lds_double* r = B.c0 + 2*ps;
-    const int ok[4] = {0, 1, B.pitch, B.pitch + 1};
-    double a[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int o = B.ok[k] ? ok[k] : 0;
-        B.r0[k] = r[o]; B.r1[k] = TWO ? r[ps + o] : 0.0; a[k] = r[(2 - cmp)*ps + o]; B.ci[k] = r[(3 - cmp)*ps + o];
-    }
-    if (last && nx <= 2 && ny <= 2) { blk_single_sweeps<TWO>(B, nsw); lvl_sync<WAVE>(); }
-    else blk_down_sweeps<WAVE, TWO>(B, nsw);
-    if (!last) {
-        double q0[4], q1[4];
-        blk_residual<TWO>(B, i, j, cc_box(nx, ny), a, fx, fy, q0, q1);
-        if (B.act) {
-            const int pn = d.nx[l+1] + 2, psn = pn*(d.ny[l+1] + 2);
-            lds_double* rn = base + d.off[l+1] + (2 + cmp)*psn + ((j >> 1) + 1)*pn + (i >> 1) + 1;
-            rn[0] = 0.25*(q0[0] + q0[1] + q0[2] + q0[3]);
-            if (TWO) rn[psn] = 0.25*(q1[0] + q1[1] + q1[2] + q1[3]);
-        }
-        lvl_sync<WAVE>();
-    }
-}
-
-// up-leg of level l >= 1: cor += P(cor of level l+1), GSRB^4
-template <bool WAVE, bool TWO = true>
-__device__ __forceinline__ void low_up (lds_double* base, const Low2& d, int l, int t, double fx, double fy, int cmp = 0)
-{
-    const int nx = d.nx[l], ny = d.ny[l];
-    Blk B; int i, j;
-    blk_geometry(B, base + d.off[l], nx, ny, t, fx, fy, i, j, cmp);
-    const int ps = B.pitch*(ny + 2);
-    const lds_double* r = B.c0 + 2*ps;
-    const int ok[4] = {0, 1, B.pitch, B.pitch + 1};
-    const int pn = d.nx[l+1] + 2, psn = pn*(d.ny[l+1] + 2);
-    const lds_double* kc = base + d.off[l+1] + cmp*psn + ((j >> 1) + 1)*pn + (i >> 1) + 1;
-    const double k0 = B.act ? kc[0] : 0.0, k1 = (TWO && B.act) ? kc[psn] : 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int o = B.ok[k] ? ok[k] : 0;
-        B.r0[k] = r[o]; B.r1[k] = TWO ? r[ps + o] : 0.0; B.ci[k] = r[(3 - cmp)*ps + o];
-        const double c0 = B.c0[o];
-        B.v0[k] = B.ok[k] ? c0 + k0 : 0.0;
-        if (B.ok[k]) B.c0[o] = B.v0[k];
-        B.v1[k] = 0.0;
-        if (TWO) {
-            const double c1 = B.c1[o];
-            B.v1[k] = B.ok[k] ? c1 + k1 : 0.0;
-            if (B.ok[k]) B.c1[o] = B.v1[k];
-        }
-    }
-    lvl_sync<WAVE>();
-    blk_sweep<0, WAVE, TWO>(B); blk_sweep<1, WAVE, TWO>(B); blk_sweep<0, WAVE, TWO>(B); blk_sweep<1, WAVE, TWO>(B);
-}
-
-// Levels of at most 8 x 8 cells inside one wave, one lane per cell (lane t <-> cell (t & 7, t >> 3)), one component
-// (cmp) per wave: a lone wave is bound by its own instruction latencies, and a cell per lane is the shortest
-// stream per sweep.
-__device__ __forceinline__ void tiny_down (lds_double* base, const Low2& d, int l, int t, double fx, double fy, int cmp)
-{
-    const int nx = d.nx[l], ny = d.ny[l], pitch = nx + 2, ps = pitch*(ny + 2);
-    const int i = t & 7, j = t >> 3;
-    const bool ok = (i < nx) && (j < ny);
-    const int o = ok ? (j + 1)*pitch + i + 1 : pitch + 1;
-    lds_double* c0 = base + d.off[l] + cmp*ps + o;
-    const double r0 = c0[2*ps], a = c0[(4 - cmp)*ps], ci = c0[(5 - cmp)*ps];
-    const double fxm = wall_mult<true>(i, 0, nx - 1, fx), fym = wall_mult<true>(j, 0, ny - 1, fy);
-    if (ok && (((i + j) & 1) == 0)) c0[0] = r0*ci;                          // sweep 0 from cor = 0
-    lvl_sync<true>();
-    for (int s = 1; s < 4; ++s) {
-        if (ok && (((i + j + s) & 1) == 0)) c0[0] = (r0 - offdiag_m((const lds_double*)c0, pitch, fxm, fym))*ci;
-        lvl_sync<true>();
-    }
-    const LevBox b = cc_box(nx, ny);
-    const double u0 = residual_at<false>((const lds_double*)c0, pitch, i, j, b, r0, a, fx, fy);
-    const double q0 = ok ? u0 : 0.0;
-    const double b0 = __shfl_down(q0, 1), g0 = __shfl_down(q0, 8), e0 = __shfl_down(q0, 9);
-    if (ok && !(i & 1) && !(j & 1)) {
-        const int pn = d.nx[l+1] + 2, psn = pn*(d.ny[l+1] + 2);
-        base[d.off[l+1] + (2 + cmp)*psn + ((j >> 1) + 1)*pn + (i >> 1) + 1] = 0.25*(q0 + b0 + g0 + e0);
-    }
-    lvl_sync<true>();
-}
-
-__device__ __forceinline__ void tiny_up (lds_double* base, const Low2& d, int l, int t, double fx, double fy, int cmp)
-{
-    const int nx = d.nx[l], ny = d.ny[l], pitch = nx + 2, ps = pitch*(ny + 2);
-    const int i = t & 7, j = t >> 3;
-    const bool ok = (i < nx) && (j < ny);
-    const int o = ok ? (j + 1)*pitch + i + 1 : pitch + 1;
-    lds_double* c0 = base + d.off[l] + cmp*ps + o;
-    const double r0 = c0[2*ps], ci = c0[(5 - cmp)*ps];
-    const double fxm = wall_mult<true>(i, 0, nx - 1, fx), fym = wall_mult<true>(j, 0, ny - 1, fy);
-    if (ok) {
-        const int pn = d.nx[l+1] + 2, psn = pn*(d.ny[l+1] + 2);
-        c0[0] = c0[0] + base[d.off[l+1] + cmp*psn + ((j >> 1) + 1)*pn + (i >> 1) + 1];
-    }
-    lvl_sync<true>();
-    for (int s = 0; s < 4; ++s) {
-        if (ok && (((i + j + s) & 1) == 0)) c0[0] = (r0 - offdiag_m((const lds_double*)c0, pitch, fxm, fym))*ci;
-        lvl_sync<true>();
-    }
-}
-
-__global__ __launch_bounds__(1024)
-void k_lower_v2 (const Low2* __restrict__ dp, const double* __restrict__ acf_g, const double* __restrict__ res_g, double* __restrict__ cor_g,
-                 double facx0, double facy0, int nsweeps_bottom, StopRule sr)
-{
-    if (!vcycle_active(sr)) return;
-    extern __shared__ __attribute__((aligned(16))) double lds_raw[];
-    lds_double* base = (lds_double*)lds_raw;
-    const int t = threadIdx.x;
-    const Low2& d = *dp;          // uniform (scalar) loads; a by-value copy indexed by level would live in scratch
-    const int nl = d.nl;
-    MG_STAMP(8);
-    // ---- level A: rhs and coefficient of the thread's block from HBM, inverse diagonals
-    const int nxA = d.nx[0], nyA = d.ny[0], cellsA = nxA*nyA;
-    const LevBox bA = cc_box(nxA, nyA);
-    Blk A; int iA, jA;
-    blk_geometry(A, base + d.off[0], nxA, nyA, t, facx0, facy0, iA, jA);
-    double aA[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = iA + (k & 1), j = jA + (k >> 1);
-        const int g = min(i, nxA - 1) + min(j, nyA - 1)*nxA;
-        const double v0 = res_g[g], v1 = res_g[cellsA + g], v2 = acf_g[g];
-        A.r0[k] = A.ok[k] ? v0 : 0.0; A.r1[k] = A.ok[k] ? v1 : 0.0; aA[k] = A.ok[k] ? v2 : 0.0;
-        A.ci[k] = 1.0/diag_c0<true>(i, j, bA, aA[k], facx0, facy0);
-    }
-    // only the correction planes need zeros (ring + the cells of the colour the first half-sweep skips); the
-    // rhs / coefficient / inverse-diagonal planes are written before they are read
-    for (int l = 0; l < nl; ++l) {
-        const int n2 = 2*(d.nx[l] + 2)*(d.ny[l] + 2);
-        lds_double* c = base + d.off[l];
-        for (int s = t; s < n2; s += 1024) c[s] = 0.0;
-    }
-    __syncthreads();
-    // ---- coefficient hierarchy (average_down_acoef) and inverse diagonals of the levels below
-    if (nl > 1 && A.act) {
-        const int p1 = d.nx[1] + 2, ps1 = p1*(d.ny[1] + 2);
-        base[d.off[1] + 4*ps1 + ((jA >> 1) + 1)*p1 + (iA >> 1) + 1] = 0.25*(aA[0] + aA[1] + aA[2] + aA[3]);
-    }
-    __syncthreads();
-    for (int l = 1; l < nl; ++l) {
-        const double fx = lvl_fac(facx0, l), fy = lvl_fac(facy0, l);
-        const int nx = d.nx[l], ny = d.ny[l];
-        Blk B; int i, j;
-        blk_geometry(B, base + d.off[l], nx, ny, t, fx, fy, i, j);
-        const int ps = B.pitch*(ny + 2);
-        lds_double* acf = B.c0 + 4*ps;
-        const int ok[4] = {0, 1, B.pitch, B.pitch + 1};
-        double a[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            a[k] = B.ok[k] ? acf[ok[k]] : 0.0;
-            if (B.ok[k]) acf[ps + ok[k]] = 1.0/diag_c0<true>(i + (k & 1), j + (k >> 1), cc_box(nx, ny), a[k], fx, fy);
-        }
-        if (l + 1 < nl && B.act) {
-            const int pn = d.nx[l+1] + 2, psn = pn*(d.ny[l+1] + 2);
-            base[d.off[l+1] + 4*psn + ((j >> 1) + 1)*pn + (i >> 1) + 1] = 0.25*(a[0] + a[1] + a[2] + a[3]);
-        }
-        __syncthreads();
-    }
-    MG_STAMP(9);
-    // ---- level A down-leg
-    const bool bottomA = (nl == 1);
-    blk_down_sweeps<false>(A, bottomA ? nsweeps_bottom : 4);
-    if (!bottomA) {
-        double q0[4], q1[4];
-        blk_residual(A, iA, jA, bA, aA, facx0, facy0, q0, q1);
-        if (A.act) {
-            const int p1 = d.nx[1] + 2, ps1 = p1*(d.ny[1] + 2);
-            lds_double* rn = base + d.off[1] + 2*ps1 + ((jA >> 1) + 1)*p1 + (iA >> 1) + 1;
-            rn[0] = 0.25*(q0[0] + q0[1] + q0[2] + q0[3]);
-            rn[ps1] = 0.25*(q1[0] + q1[1] + q1[2] + q1[3]);
-        }
-        __syncthreads();
-    }
-    MG_STAMP(10);
-    if (!bottomA) {
-        // lw = first level whose blocks (and those of every level below it) fit wave 0
-        int lw = 1;
-        for (; lw < nl; ++lw) {
-            const int nbx = (d.nx[lw] + 1) >> 1, nby = (d.ny[lw] + 1) >> 1;
-            int lg = 0; while ((1 << lg) < nbx) ++lg;
-            if ((nby << lg) <= 64) break;
-        }
-        for (int l = 1; l < lw; ++l)
-            low_down<false>(base, d, l, t, lvl_fac(facx0, l), lvl_fac(facy0, l), (l == nl - 1) ? nsweeps_bottom : 4, l == nl - 1);
-        MG_STAMP(11);
-        if (lw < nl) {
-            if (t < 128) {
-                // waves 0 and 1: one component each, no synchronisation between them
-                const int cmp = t >> 6, tl = t & 63;
-                for (int l = lw; l < nl; ++l) {
-                    MG_STAMP(16 + l);
-                    const bool tiny = (d.nx[l] <= 8 && d.ny[l] <= 8 && l < nl - 1);
-                    if (tiny) tiny_down(base, d, l, tl, lvl_fac(facx0, l), lvl_fac(facy0, l), cmp);
-                    else low_down<true, false>(base, d, l, tl, lvl_fac(facx0, l), lvl_fac(facy0, l), (l == nl - 1) ? nsweeps_bottom : 4, l == nl - 1, cmp);
-                }
-                for (int l = nl - 2; l >= lw; --l) {
-                    MG_STAMP(32 + l);
-                    if (d.nx[l] <= 8 && d.ny[l] <= 8) tiny_up(base, d, l, tl, lvl_fac(facx0, l), lvl_fac(facy0, l), cmp);
-                    else low_up<true, false>(base, d, l, tl, lvl_fac(facx0, l), lvl_fac(facy0, l), cmp);
-                }
-            }
-            __syncthreads();
-        }
-        MG_STAMP(12);
-        // level A's rhs left the registers after its residual: fetch it again (L2) behind the up-leg below
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int g = min(iA + (k & 1), nxA - 1) + min(jA + (k >> 1), nyA - 1)*nxA;
-            const double v0 = __builtin_nontemporal_load(res_g + g), v1 = __builtin_nontemporal_load(res_g + cellsA + g);
-            A.r0[k] = A.ok[k] ? v0 : 0.0; A.r1[k] = A.ok[k] ? v1 : 0.0;
-        }
-        for (int l = min(lw - 1, nl - 2); l >= 1; --l)
-            low_up<false>(base, d, l, t, lvl_fac(facx0, l), lvl_fac(facy0, l));
-        // ---- level A up-leg: correction back from LDS, prolongation, 4 sweeps
-        const int p1 = d.nx[1] + 2, ps1 = p1*(d.ny[1] + 2);
-        const lds_double* kc = base + d.off[1] + ((jA >> 1) + 1)*p1 + (iA >> 1) + 1;
-        const double k0 = A.act ? kc[0] : 0.0, k1 = A.act ? kc[ps1] : 0.0;
-        const int ok[4] = {0, 1, A.pitch, A.pitch + 1};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int o = A.ok[k] ? ok[k] : 0;
-            const double c0 = A.c0[o], c1 = A.c1[o];
-            A.v0[k] = A.ok[k] ? c0 + k0 : 0.0; A.v1[k] = A.ok[k] ? c1 + k1 : 0.0;
-            if (A.ok[k]) { A.c0[o] = A.v0[k]; A.c1[o] = A.v1[k]; }
-        }
-        __syncthreads();
-        blk_sweep<0, false>(A); blk_sweep<1, false>(A); blk_sweep<0, false>(A); blk_sweep<1, false>(A);
-    }
-    MG_STAMP(13);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int g = min(iA + (k & 1), nxA - 1) + min(jA + (k >> 1), nyA - 1)*nxA;
-        if (A.ok[k]) { cor_g[g] = A.v0[k]; cor_g[cellsA + g] = A.v1[k]; }
-    }
-    MG_STAMP(14);
-}
-
-// ---------------------------------------------------------------------------------------------
-// k_lower_v3: the same lower V with ONE field component per workgroup (grid = 2).  The two components of the solve only
-// meet in the norm, which the lower V does not take, so two workgroups on two CUs need no synchronisation at all, and
-// every barrier phase of the 64 x 64 and 32 x 32 levels carries half the LDS traffic and half the fp64 instruction
-// stream of k_lower_v2 (one CU's LDS pipe and VALUs were what bounded those phases: ~1800 cycles per half-sweep).
-// LDS per level, single component: level A one ringed plane (cor); below it four: cor | res | acf | 1/diag.
-// Level A's inverse diagonals come from k_acf_pyramid (cinv_g: 4 divisions per thread and V-cycle less).  The gate of
-// the speculative V-cycle is evaluated AFTER the level-A loads have been issued: a kernel's first dependent read of
-// global memory costs ~1.5 us behind a kernel boundary (scripts/ubench/launch_floor.hip), and the two now overlap.
 
 template <bool WAVE>
 __device__ __forceinline__ void low_down_s (lds_double* base, const Low2& d, int l, int t, double fx, double fy, int nsw, bool last)
@@ -1582,13 +1059,13 @@ __device__ __forceinline__ void low_down_s (lds_double* base, const Low2& d, int
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int o = B.ok[k] ? ok[k] : 0;
-        B.r0[k] = r[o]; B.r1[k] = 0.0; a[k] = cf[o]; B.ci[k] = cf[ps + o];
+        B.r0[k] = r[o]; a[k] = cf[o]; B.ci[k] = cf[ps + o];
     }
-    if (last && nx <= 2 && ny <= 2) { blk_single_sweeps<false>(B, nsw); lvl_sync<WAVE>(); }
-    else blk_down_sweeps<WAVE, false>(B, nsw);
+    if (last && nx <= 2 && ny <= 2) { blk_single_sweeps(B, nsw); lvl_sync<WAVE>(); }
+    else blk_down_sweeps<WAVE>(B, nsw);
     if (!last) {
-        double q0[4], q1[4];
-        blk_residual<false>(B, i, j, cc_box(nx, ny), a, fx, fy, q0, q1);
+        double q0[4];
+        blk_residual(B, i, j, cc_box(nx, ny), a, fx, fy, q0);
         if (B.act) {
             const int pn = d.nx[l+1] + 2, psn = pn*(d.ny[l+1] + 2);
             base[d.off[l+1] + psn + ((j >> 1) + 1)*pn + (i >> 1) + 1] = 0.25*(q0[0] + q0[1] + q0[2] + q0[3]);
@@ -1613,14 +1090,13 @@ __device__ __forceinline__ void low_up_s (lds_double* base, const Low2& d, int l
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int o = B.ok[k] ? ok[k] : 0;
-        B.r0[k] = r[o]; B.r1[k] = 0.0; B.ci[k] = cf[ps + o];
+        B.r0[k] = r[o]; B.ci[k] = cf[ps + o];
         const double c0 = B.c0[o];
         B.v0[k] = B.ok[k] ? c0 + k0 : 0.0;
         if (B.ok[k]) B.c0[o] = B.v0[k];
-        B.v1[k] = 0.0;
     }
     lvl_sync<WAVE>();
-    blk_sweep<0, WAVE, false>(B); blk_sweep<1, WAVE, false>(B); blk_sweep<0, WAVE, false>(B); blk_sweep<1, WAVE, false>(B);
+    blk_sweep<0, WAVE>(B); blk_sweep<1, WAVE>(B); blk_sweep<0, WAVE>(B); blk_sweep<1, WAVE>(B);
 }
 
 // levels of at most 8 x 8 cells in one wave, one lane per cell
@@ -1694,7 +1170,7 @@ void k_lower_v3 (const Low2* __restrict__ dp, const double* __restrict__ acf_g, 
         const int g = min(i, nxA - 1) + min(j, nyA - 1)*nxA;
         const double v0 = res_g[g], v2 = acf_g[g], v3 = cinv_g[g];
         rA[k] = A.ok[k] ? v0 : 0.0; aA[k] = A.ok[k] ? v2 : 0.0; A.ci[k] = A.ok[k] ? v3 : 0.0;
-        A.r0[k] = rA[k]; A.r1[k] = 0.0;
+        A.r0[k] = rA[k];
     }
     // The [acf | 1/diag] planes of the levels below A depend on the coefficient only: the first V-cycle of a solve derives
     // them (average_down_acoef + one division per cell) and leaves the image in coef_g, the later ones copy it in.
@@ -1756,10 +1232,10 @@ void k_lower_v3 (const Low2* __restrict__ dp, const double* __restrict__ acf_g, 
     MG_STAMP(9);
     // ---- level A down-leg
     const bool bottomA = (nl == 1);
-    blk_down_sweeps<false, false>(A, bottomA ? nsweeps_bottom : 4);
+    blk_down_sweeps<false>(A, bottomA ? nsweeps_bottom : 4);
     if (!bottomA) {
-        double q0[4], q1[4];
-        blk_residual<false>(A, iA, jA, bA, aA, facx0, facy0, q0, q1);
+        double q0[4];
+        blk_residual(A, iA, jA, bA, aA, facx0, facy0, q0);
         if (A.act) {
             const int p1 = d.nx[1] + 2, ps1 = p1*(d.ny[1] + 2);
             base[d.off[1] + ps1 + ((jA >> 1) + 1)*p1 + (iA >> 1) + 1] = 0.25*(q0[0] + q0[1] + q0[2] + q0[3]);
@@ -1811,7 +1287,7 @@ void k_lower_v3 (const Low2* __restrict__ dp, const double* __restrict__ acf_g, 
             A.r0[k] = rA[k];
         }
         __syncthreads();
-        blk_sweep<0, false, false>(A); blk_sweep<1, false, false>(A); blk_sweep<0, false, false>(A); blk_sweep<1, false, false>(A);
+        blk_sweep<0, false>(A); blk_sweep<1, false>(A); blk_sweep<0, false>(A); blk_sweep<1, false>(A);
     }
     MG_STAMP(13);
 #pragma unroll
@@ -1981,19 +1457,15 @@ __global__ void k_copy2 (LevBox b, FView dst, FView src)
 struct MGLevelDev { LevBox b; long cells; double *acf, *res, *cor, *rescor; };
 
 constexpr long LOWV_MAX_CELLS = 34*34;     // levels with at most ~32x32 unknowns run in k_lower_v (LDS resident)
+constexpr long SMALL_TILE_CELLS = 300L*300L;      // levels up to this many cells are smoothed on TileSmall, larger ones on TileBig
 
 constexpr int MG_GO_WORD = 8;      // int word of the header slot that k_post_norms sets: 1 = the solve is over
 struct SolveRun { int enq, nspec, nzeroed, max_iters; double tol_rel, tol_abs; bool cc; };
 
 struct Multigrid {
     bool cc; int nx, ny; double dx, dy;
-    bool post_fold = false; unsigned int* d_post_counter = nullptr;     // k_post_norms' work in the last V-cycle's level-0 launch (HPS_MG_POST_FOLD=1; measured: 1474 against 1481 slices/s, off)
     bool hierarchy_ready = false;               // mg_solve1_prepare has enqueued the coefficient hierarchy of the next solve
-    bool lowv_bottom_lane = true;                           // k_lower_v: a bottom level of at most 3 x 3 unknowns in one lane's registers (HPS_MG_LOWV_BOTTOM_LANE=0: as phases of the workgroup)
-    int lowv_wave_cells = 0;                                // k_lower_v: levels of at most so many points are worked by wave 0 alone (HPS_MG_LOWV_WAVE=1: 17^2; measured SLOWER, see low_map: off)
-    bool lowv_split = false; int lowv_threads = 1024;      // k_lower_v: one component per workgroup / threads per workgroup (HPS_MG_LOWV_SPLIT, HPS_MG_LOWV_THREADS)
-    bool nodal_pull1 = false;                   // node-centred: level 1's down-leg smoother forms its right-hand side from level 0's residual itself (HPS_MG_NODAL_PULL1=0: a k_restrict launch)
-    bool nodal_pyramid = false;                 // node-centred grids: the coefficient hierarchy in one launch (k_nodal_acf_pyramid; HPS_MG_NODAL_PYRAMID=0: off)
+    bool nodal_pull1 = false;                   // node-centred: level 1's down-leg smoother forms its right-hand side from level 0's residual itself
     std::vector<MGLevelDev> L;
     int lowv_begin = 1;                         // first level handled by k_lower_v
     LowLev* d_low = nullptr; size_t low_lds = 0;
@@ -2008,21 +1480,17 @@ struct Multigrid {
     int last_iters = 1;                         // V-cycles of the previous solve = speculation depth
     SolveRun run{};                             // the solve between mg_solve1_begin and mg_solve1_finish
     bool defer_post = false; bool deferred_valid = false; MgPost deferred{};      // mg_defer_post / mg_take_deferred_post
-    bool use_low2 = false; Low2 low2{}; Low2* d_low2 = nullptr; size_t low2_lds = 0;   // cell-centred register/LDS lower V
-    bool use_low3 = false; Low2 low3{}; Low2* d_low3 = nullptr; size_t low3_lds = 0;   // ... one component per workgroup (k_lower_v3)
+    bool use_low3 = false; Low2 low3{}; Low2* d_low3 = nullptr; size_t low3_lds = 0;   // cell-centred register/LDS lower V (k_lower_v3)
     double* cinvA = nullptr;                    // inverse diagonals of level lowv_begin (written with the coefficient pyramid)
     double* coef_img = nullptr;                 // [acf | 1/diag] planes of the levels below it (left by the first V-cycle of a solve)
     double* tmp0 = nullptr;                     // level-0 scratch: smoothed solution before the last GSRB^4
-    bool init_huge = false;                     // HPS_MG_INIT_HUGE=1: the initial level-0 pass on 64 x 48 tiles (measured: 235 against 230 us per solve)
-    bool fuse_level0 = true, cor_in_tmp = false; // fused 8-sweep end of the V-cycle; which buffer holds cor[0]
-    long small_tile_cells = 300L*300L;          // levels up to this many cells use TileSmall
-    long mid_tile_cells = 0;                    // ... up to this many TileMid
+    bool cor_in_tmp = false;                    // which buffer holds cor[0] (the fused 8-sweep end of the V-cycle is out of place)
     FView sol, rhs, acf0;                       // level-0 user views (set per solve)
 
     ~Multigrid () {
         for (auto& l : L) { (void)hipFree(l.acf); (void)hipFree(l.res); (void)hipFree(l.cor); (void)hipFree(l.rescor); }
         if (getenv("HPS_MG_DEBUG")) fprintf(stderr, "mg: solves %ld trips %ld hist %ld %ld %ld %ld %ld %ld\n", dbg_solves, dbg_trips, dbg_hist[0], dbg_hist[1], dbg_hist[2], dbg_hist[3], dbg_hist[4], dbg_hist[5]);
-        (void)hipFree(d_buf); (void)hipFree(d_post_counter); (void)hipFree(d_low); (void)hipFree(tmp0); (void)hipFree(d_low2); (void)hipFree(d_low3); (void)hipFree(cinvA); (void)hipFree(coef_img);
+        (void)hipFree(d_buf); (void)hipFree(d_low); (void)hipFree(tmp0); (void)hipFree(d_low3); (void)hipFree(cinvA); (void)hipFree(coef_img);
         if (h_buf) (void)hipHostFree(h_buf);
     }
     FView lv (int il, double* p) const {
@@ -2063,76 +1531,45 @@ int mg_create (int nx, int ny, double dx, double dy, Multigrid** out)
         if (!ok) break;
     }
     if (M->nlev() < 2) { delete M; set_error("hps_mg_create: grid too small to coarsen"); return HPS_ERR_ARG; }
-    // (node-centred grids: the split is the default -- Bx/By solve at 1023^2 375 -> 361 us per slice, 512 threads the same, 256 slower:
-    //  profiles/r06_lowv_ab.txt; the cell-centred grids run k_lower_v3, which is built that way)
-    {   const char* v = getenv("HPS_MG_LOWV_SPLIT"); M->lowv_split = v ? atoi(v) != 0 : !M->cc;
-        if (const char* b = getenv("HPS_MG_LOWV_BOTTOM_LANE")) M->lowv_bottom_lane = atoi(b) != 0;
-        if (const char* w = getenv("HPS_MG_LOWV_WAVE")) M->lowv_wave_cells = atoi(w) != 0 ? (atoi(w) == 1 ? LOWV_WAVE_CELLS : atoi(w)) : 0;
-        const char* t = getenv("HPS_MG_LOWV_THREADS"); if (t) { const int n = atoi(t); if (n == 256 || n == 512 || n == 1024) M->lowv_threads = n; } }
-    if (!M->cc) {
-        const char* v = getenv("HPS_MG_NODAL_PYRAMID");
-        M->nodal_pyramid = !(v && atoi(v) == 0);
-        if (M->nodal_pyramid)
-            HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_nodal_acf_pyramid<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nodal_pyramid_lds(NPYR_MAX)));
-    }
-    if (const char* e = getenv("HPS_MG_SMALL_CELLS")) M->small_tile_cells = atol(e);
-    if (const char* e = getenv("HPS_MG_INIT_HUGE")) M->init_huge = atoi(e) != 0;
-    if (const char* e = getenv("HPS_MG_POST_FOLD")) M->post_fold = atoi(e) != 0;
-    if (const char* e = getenv("HPS_MG_MID_CELLS")) M->mid_tile_cells = atol(e);
+    if (!M->cc)
+        HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_nodal_acf_pyramid<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)nodal_pyramid_lds(NPYR_MAX)));
     const int nl = M->nlev();
     M->lowv_begin = nl - 1;
     for (int il = nl - 1; il >= 1; --il) if (M->L[il].cells <= LOWV_MAX_CELLS) M->lowv_begin = il;
-    if (M->cc && !getenv("HPS_MG_OLD_LOWV")) {
-        // first level with at most 64 x 64 cells whose coarser levels all fit 32 x 32
-        const int amax = getenv("HPS_MG_LOW2_MAX") ? atoi(getenv("HPS_MG_LOW2_MAX")) : 64;
+    if (M->cc) {
+        // k_lower_v3 from the first level with at most 64 x 64 cells whose coarser levels all fit 32 x 32 (none: k_lower_v)
         for (int il = 1; il < nl; ++il) {
             const LevBox& b = M->L[il].b;
-            const bool fits = (b.hix + 1 <= amax) && (b.hiy + 1 <= amax) && (nl - il <= LOW2_MAXLEV)
+            const bool fits = (b.hix + 1 <= 64) && (b.hiy + 1 <= 64) && (nl - il <= LOW2_MAXLEV)
                            && (il + 1 >= nl || (M->L[il+1].b.hix + 1 <= 32 && M->L[il+1].b.hiy + 1 <= 32));
             if (!fits) continue;
-            M->use_low2 = true; M->lowv_begin = il;
-            Low2& d = M->low2;
-            d.nl = nl - il;
-            int off2 = 0;
-            for (int k = 0; k < d.nl; ++k) {
+            // one component per workgroup: level A one plane, the others cor | res, then their acf | 1/diag planes
+            M->use_low3 = true; M->lowv_begin = il;
+            Low2& e = M->low3;
+            e.nl = nl - il;
+            int off3 = 0;
+            for (int k = 0; k < e.nl; ++k) {
                 const LevBox& bk = M->L[il + k].b;
-                d.nx[k] = bk.hix + 1; d.ny[k] = bk.hiy + 1; d.off[k] = off2;
-                off2 += (k == 0 ? 2 : 6)*(d.nx[k] + 2)*(d.ny[k] + 2);
+                e.nx[k] = bk.hix + 1; e.ny[k] = bk.hiy + 1; e.off[k] = off3;
+                off3 += (k == 0 ? 1 : 2)*(e.nx[k] + 2)*(e.ny[k] + 2);      // cor [| res]
             }
-            d.total = off2;
-            M->low2_lds = (size_t)off2*sizeof(double);
-            if (M->low2_lds > 64*1024)
-                HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low2_lds));
-            HPS_HIP_CHECK(hipMalloc(&M->d_low2, sizeof(Low2)));
-            HPS_HIP_CHECK(hipMemcpy(M->d_low2, &d, sizeof(Low2), hipMemcpyHostToDevice));
-            if (!getenv("HPS_MG_LOWV2")) {
-                // the same levels, one component per workgroup: level A one plane, the others cor | res | acf | 1/diag
-                M->use_low3 = true;
-                Low2& e = M->low3;
-                e = d;
-                int off3 = 0;
-                for (int k = 0; k < e.nl; ++k) { e.off[k] = off3; off3 += (k == 0 ? 1 : 2)*(e.nx[k] + 2)*(e.ny[k] + 2); }      // cor [| res]
-                e.cbase = off3; e.coff[0] = off3;
-                for (int k = 1; k < e.nl; ++k) { e.coff[k] = off3; off3 += 2*(e.nx[k] + 2)*(e.ny[k] + 2); }                        // acf | 1/diag
-                e.ctot = std::max(off3 - e.cbase, 1);
-                e.total = off3;
-                HPS_HIP_CHECK(hipMalloc(&M->coef_img, (size_t)e.ctot*sizeof(double)));
-                HPS_HIP_CHECK(hipMemset(M->coef_img, 0, (size_t)e.ctot*sizeof(double)));
-                M->low3_lds = (size_t)off3*sizeof(double);
-                if (M->low3_lds > 64*1024)
-                    HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low3_lds));
-                HPS_HIP_CHECK(hipMalloc(&M->d_low3, sizeof(Low2)));
-                HPS_HIP_CHECK(hipMemcpy(M->d_low3, &e, sizeof(Low2), hipMemcpyHostToDevice));
-                HPS_HIP_CHECK(hipMalloc(&M->cinvA, (size_t)d.nx[0]*d.ny[0]*sizeof(double)));
-            }
+            e.cbase = off3; e.coff[0] = off3;
+            for (int k = 1; k < e.nl; ++k) { e.coff[k] = off3; off3 += 2*(e.nx[k] + 2)*(e.ny[k] + 2); }      // acf | 1/diag
+            e.ctot = std::max(off3 - e.cbase, 1);
+            e.total = off3;
+            HPS_HIP_CHECK(hipMalloc(&M->coef_img, (size_t)e.ctot*sizeof(double)));
+            HPS_HIP_CHECK(hipMemset(M->coef_img, 0, (size_t)e.ctot*sizeof(double)));
+            M->low3_lds = (size_t)off3*sizeof(double);
+            if (M->low3_lds > 64*1024)
+                HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low3_lds));
+            HPS_HIP_CHECK(hipMalloc(&M->d_low3, sizeof(Low2)));
+            HPS_HIP_CHECK(hipMemcpy(M->d_low3, &e, sizeof(Low2), hipMemcpyHostToDevice));
+            HPS_HIP_CHECK(hipMalloc(&M->cinvA, (size_t)e.nx[0]*e.ny[0]*sizeof(double)));
             break;
         }
     }
-    if (!M->cc) {
-        // level 1 pulls (vcycle: pulls) when it is a smoother level of its own (not the lower V's top) and the general switch is on
-        const char* g0 = getenv("HPS_MG_NODAL_PULL"); const char* g1 = getenv("HPS_MG_NODAL_PULL1");
-        M->nodal_pull1 = !(g0 && atoi(g0) == 0) && !(g1 && atoi(g1) == 0) && M->lowv_begin > 1;
-    }
+    // node-centred: level 1 pulls (vcycle: pulls) when it is a smoother level of its own, not the lower V's top
+    M->nodal_pull1 = !M->cc && M->lowv_begin > 1;
     std::vector<LowLev> low;
     int off = 0;
     for (int il = M->lowv_begin; il < nl; ++il) {
@@ -2141,15 +1578,13 @@ int mg_create (int nx, int ny, double dx, double dy, Multigrid** out)
         off += 8*(int)l.cells;
     }
     M->low_lds = (size_t)off*sizeof(double);
-    if (!M->use_low2 && M->low_lds > 64*1024) {
+    if (!M->use_low3 && M->low_lds > 64*1024) {
         HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low_lds));
         HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low_lds));
     }
     HPS_HIP_CHECK(hipMalloc(&M->d_low, low.size()*sizeof(LowLev)));
     HPS_HIP_CHECK(hipMemcpy(M->d_low, low.data(), low.size()*sizeof(LowLev), hipMemcpyHostToDevice));
     HPS_HIP_CHECK(hipMalloc(&M->d_buf, (3 + MG_MAX_VCYCLES)*MG_NSUB*sizeof(unsigned long long)));
-    HPS_HIP_CHECK(hipMalloc(&M->d_post_counter, 17*sizeof(unsigned int)));
-    HPS_HIP_CHECK(hipMemset(M->d_post_counter, 0, 17*sizeof(unsigned int)));
     HPS_HIP_CHECK(hipHostMalloc(&M->h_buf, ((3 + MG_MAX_VCYCLES)*MG_NSUB + 8)*sizeof(unsigned long long), hipHostMallocMapped));
     HPS_HIP_CHECK(hipHostGetDevicePointer((void**)&M->h_buf_dev, M->h_buf, 0));
     M->h_seq = M->h_buf + (3 + MG_MAX_VCYCLES)*MG_NSUB; M->h_seq_dev = M->h_buf_dev + (3 + MG_MAX_VCYCLES)*MG_NSUB;
@@ -2166,7 +1601,7 @@ int mg_create (int nx, int ny, double dx, double dy, Multigrid** out)
 template <class TS, bool CC, int SRC, bool DO_RES, int NSW = 4, bool RPULL = false>
 static void launch_smooth_ts (Multigrid* M, int il, FView phi_out, FView phi_out2, FView rhs, FView acf, FView phi_in, FView crse,
                               FView res_out, FView cres_out, unsigned long long* resnorm, unsigned long long* rhsnorm,
-                              const StopRule& sr, hipStream_t st, const PostArgs* post = nullptr)
+                              const StopRule& sr, hipStream_t st)
 {
     const LevBox& b = M->L[il].b;
     constexpr int E = DO_RES ? NSW : NSW - 1;
@@ -2176,15 +1611,8 @@ static void launch_smooth_ts (Multigrid* M, int il, FView phi_out, FView phi_out
     const double ldx = M->dx*fac, ldy = M->dy*fac;
     const double facx = 1.0/(ldx*ldx), facy = 1.0/(ldy*ldy);
     constexpr bool FUSE = CC && DO_RES;
-    if constexpr (NSW != 4) {
-        if (post) {
-            hipLaunchKernelGGL((k_smooth<TS, CC, SRC, DO_RES, FUSE, NSW, true>), dim3(ntx*nty), dim3(TS::NT), 0, st, b, phi_out, phi_out2, rhs, acf,
-                               phi_in, crse, res_out, cres_out, facx, facy, ntx, resnorm, rhsnorm, sr, *post);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_smooth<TS, CC, SRC, DO_RES, FUSE, NSW, false, RPULL>), dim3(ntx*nty), dim3(TS::NT), 0, st, b, phi_out, phi_out2, rhs, acf,
-                       phi_in, crse, res_out, cres_out, facx, facy, ntx, resnorm, rhsnorm, sr, PostArgs{});
+    hipLaunchKernelGGL((k_smooth<TS, CC, SRC, DO_RES, FUSE, NSW, RPULL>), dim3(ntx*nty), dim3(TS::NT), 0, st, b, phi_out, phi_out2, rhs, acf,
+                       phi_in, crse, res_out, cres_out, facx, facy, ntx, resnorm, rhsnorm, sr);
 }
 
 template <bool CC, int SRC, bool DO_RES>
@@ -2192,10 +1620,8 @@ static void launch_smooth (Multigrid* M, int il, FView phi_out, FView phi_out2, 
                            FView res_out, FView cres_out, unsigned long long* resnorm, unsigned long long* rhsnorm,
                            const StopRule& sr, hipStream_t st)
 {
-    if (M->L[il].cells <= M->small_tile_cells)
+    if (M->L[il].cells <= SMALL_TILE_CELLS)
         launch_smooth_ts<TileSmall, CC, SRC, DO_RES>(M, il, phi_out, phi_out2, rhs, acf, phi_in, crse, res_out, cres_out, resnorm, rhsnorm, sr, st);
-    else if (M->L[il].cells <= M->mid_tile_cells)
-        launch_smooth_ts<TileMid, CC, SRC, DO_RES>(M, il, phi_out, phi_out2, rhs, acf, phi_in, crse, res_out, cres_out, resnorm, rhsnorm, sr, st);
     else
         launch_smooth_ts<TileBig, CC, SRC, DO_RES>(M, il, phi_out, phi_out2, rhs, acf, phi_in, crse, res_out, cres_out, resnorm, rhsnorm, sr, st);
 }
@@ -2212,7 +1638,7 @@ static void restrict_residual_if_nodal (Multigrid* M, int il, const StopRule& sr
 // V-cycle k (vcycle :1429-1512).  On entry res[1] = R(rhs - L(cor[0])); on exit again, plus
 // tmp0 = smoothed solution, cor[0] = sol = GSRB^4(tmp0) and the residual norm in d_norms[2+k].
 template <bool CC>
-static bool vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStream_t st, const PostArgs* post = nullptr)      // returns: the post has ridden along
+static void vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStream_t st)
 {
     const int nl = M->nlev();
     const int lb = M->lowv_begin;
@@ -2220,23 +1646,24 @@ static bool vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStre
     const StopRule sr{M->d_norms, k, tol_rel, tol_abs};
     // node-centred levels: the smoother of level il >= 2 forms its right-hand side from level il - 1's residual itself (RPULL);
     // the launch of k_restrict stays where the next consumer is not a smoother (level 0 -> 1 behind the fused pass, the lower V's input)
-    static const bool pull = [] { const char* v = std::getenv("HPS_MG_NODAL_PULL"); return !(v && std::atoi(v) == 0); }();
     // (levels on 32 x 16 tiles only: with the nine reads per cell in flight the 64 x 32 variant spills 108 registers under its cap)
     // (round 6: level 1 too -- on 32 x 32 tiles of 256 threads where it is too large for the 32 x 16 ones: the 64 x 32 variant's 512
     //  threads are what capped its registers -- so the level 0 -> 1 restriction launch is gone as well: M->nodal_pull1)
-    auto pulls = [&] (int il) { return !CC && pull && ((il >= 2 && ((il < lb && M->L[il].cells <= M->small_tile_cells) ||
-                                                                   (il == lb && !M->use_low3 && !M->use_low2))) ||      // (il == lb: k_lower_v's own load)
-                                                      (il == 1 && M->nodal_pull1)); };
+    auto pulls = [&] (int il) { return !CC && ((il >= 2 && ((il < lb && M->L[il].cells <= SMALL_TILE_CELLS) ||
+                                                           (il == lb && !M->use_low3))) ||      // (il == lb: k_lower_v's own load)
+                                              (il == 1 && M->nodal_pull1)); };
     for (int il = 1; il < lb; ++il) {
-        if (pulls(il) && M->L[il].cells > M->small_tile_cells)
-            launch_smooth_ts<TileMid, CC, SRC_ZERO, true, 4, !CC>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
-                                                                  M->lv(il-1, M->L[il-1].rescor), M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
-        else if (pulls(il))
-            launch_smooth_ts<TileSmall, CC, SRC_ZERO, true, 4, !CC>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
-                                                                    M->lv(il-1, M->L[il-1].rescor), M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
-        else
-        launch_smooth<CC, SRC_ZERO, true>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
-                                          none, M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
+        if (!pulls(il))
+            launch_smooth<CC, SRC_ZERO, true>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
+                                              none, M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
+        else if constexpr (!CC) {
+            if (M->L[il].cells > SMALL_TILE_CELLS)
+                launch_smooth_ts<TileMid, CC, SRC_ZERO, true, 4, true>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
+                                                                       M->lv(il-1, M->L[il-1].rescor), M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
+            else
+                launch_smooth_ts<TileSmall, CC, SRC_ZERO, true, 4, true>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
+                                                                         M->lv(il-1, M->L[il-1].rescor), M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
+        }
         if (!pulls(il + 1)) restrict_residual_if_nodal<CC>(M, il, sr, st);
     }
     {
@@ -2247,12 +1674,9 @@ static bool vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStre
         if (M->use_low3)
             hipLaunchKernelGGL(k_lower_v3, dim3(2), dim3(1024), M->low3_lds, st, M->d_low3, M->L[lb].acf, M->cinvA, M->L[lb].res, M->L[lb].cor,
                                M->coef_img, M->low3.nx[0], M->low3.ny[0], M->low3.ctot, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr);
-        else if (M->use_low2)
-            hipLaunchKernelGGL(k_lower_v2, dim3(1), dim3(1024), M->low2_lds, st, M->d_low2, M->L[lb].acf, M->L[lb].res, M->L[lb].cor,
-                               1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr);
-        else
-            hipLaunchKernelGGL(k_lower_v<CC>, dim3(M->lowv_split ? 2 : 1), dim3(M->lowv_threads), M->low_lds, st, M->d_low, nl - lb, M->L[lb].acf, M->L[lb].res,
-                               M->L[lb].cor, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, pulls(lb) ? M->lv(lb-1, M->L[lb-1].rescor) : FView{}, M->lowv_wave_cells, M->lowv_bottom_lane ? 1 : 0);
+        else      // (node-centred: one field component per workgroup)
+            hipLaunchKernelGGL(k_lower_v<CC>, dim3(CC ? 1 : 2), dim3(1024), M->low_lds, st, M->d_low, nl - lb, M->L[lb].acf, M->L[lb].res,
+                               M->L[lb].cor, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, pulls(lb) ? M->lv(lb-1, M->L[lb-1].rescor) : FView{});
     }
     // up-leg: the smoothed correction of level il lands in rescor[il] (out of place)
     for (int il = lb - 1; il >= 1; --il) {
@@ -2267,22 +1691,12 @@ static bool vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStre
         double* crse = (1 == lb) ? M->L[1].cor : M->L[1].rescor;
         double* in = M->cor_in_tmp ? M->tmp0 : M->L[0].cor;
         double* out = M->cor_in_tmp ? M->L[0].cor : M->tmp0;
-        if (M->fuse_level0) {
-            launch_smooth_ts<typename HugeTileOf<CC>::type, CC, SRC_PROLONG, true, 8>(M, 0, M->lv(0, out), M->sol, M->rhs, M->acf0, M->lv(0, in), M->lv(1, crse),
-                                                                 M->lv(0, M->L[0].rescor), M->lv(1, M->L[1].res), M->d_norms + (2 + k)*MG_NSUB,
-                                                                 nullptr, sr, st, CC ? post : nullptr);
-            M->cor_in_tmp = !M->cor_in_tmp;
-            if (!M->nodal_pull1) restrict_residual_if_nodal<CC>(M, 0, sr, st);
-            return CC && post != nullptr;
-        } else {
-            launch_smooth<CC, SRC_PROLONG, false>(M, 0, M->lv(0, M->tmp0), none, M->rhs, M->acf0, M->lv(0, M->L[0].cor), M->lv(1, crse),
-                                                  none, none, nullptr, nullptr, sr, st);
-            launch_smooth<CC, SRC_DIRECT, true>(M, 0, M->lv(0, M->L[0].cor), M->sol, M->rhs, M->acf0, M->lv(0, M->tmp0), none,
-                                                M->lv(0, M->L[0].rescor), M->lv(1, M->L[1].res), M->d_norms + (2 + k)*MG_NSUB, nullptr, sr, st);
-        }
+        launch_smooth_ts<typename HugeTileOf<CC>::type, CC, SRC_PROLONG, true, 8>(M, 0, M->lv(0, out), M->sol, M->rhs, M->acf0, M->lv(0, in), M->lv(1, crse),
+                                                             M->lv(0, M->L[0].rescor), M->lv(1, M->L[1].res), M->d_norms + (2 + k)*MG_NSUB,
+                                                             nullptr, sr, st);
+        M->cor_in_tmp = !M->cor_in_tmp;
     }
     if (!M->nodal_pull1) restrict_residual_if_nodal<CC>(M, 0, sr, st);
-    return false;
 }
 
 // norm slots (and the rider words) -> mapped host memory, sequence number last behind a system-scope fence: the host
@@ -2306,24 +1720,14 @@ template <bool CC>
 static void enqueue_cycles (Multigrid* M, hipStream_t st)
 {
     SolveRun& r = M->run;
-    bool posted = false;
     for (int v = 0; v < r.nspec && r.enq < r.max_iters; ++v, ++r.enq) {
         if (r.enq >= r.nzeroed) {        // more slots than foreseen: zero the next batch (rare)
             const int more = std::min(r.max_iters - r.nzeroed, 64);
             (void)hipMemsetAsync(M->d_norms + (2 + r.nzeroed)*MG_NSUB, 0, more*MG_NSUB*sizeof(unsigned long long), st);
             r.nzeroed += more;
         }
-        const bool last = !(v + 1 < r.nspec && r.enq + 1 < r.max_iters);
-        if (last && M->post_fold) {
-            ++M->seq; ++M->dbg_trips;
-            const PostArgs pa{M->d_buf, (volatile unsigned long long*)M->h_buf_dev, (3 + r.enq + 1)*MG_NSUB, (volatile unsigned long long*)M->h_seq_dev, M->seq,
-                              reinterpret_cast<int*>(M->d_buf) + MG_GO_WORD, StopRule{M->d_norms, r.enq + 1, r.tol_rel, r.tol_abs}, M->d_post_counter};
-            posted = vcycle<CC>(M, r.enq, r.tol_rel, r.tol_abs, st, &pa);
-            if (!posted) { --M->seq; --M->dbg_trips; }
-        } else
         vcycle<CC>(M, r.enq, r.tol_rel, r.tol_abs, st);
     }
-    if (posted) return;
     ++M->seq; ++M->dbg_trips;
     if (M->defer_post) {
         // the caller's next kernel on this stream posts (mg_take_deferred_post): no launch of its own between the last V-cycle and it
@@ -2369,8 +1773,8 @@ static int solve1_hierarchy (Multigrid* M, int max_iters, hipStream_t st, const 
         hipLaunchKernelGGL(k_acf_pyramid, dim3(ceil_div(M->nx, 32), ceil_div(M->ny, 32)), dim3(256), 0, st, M->acf0, M->nx, M->ny, po, np,
                            M->d_norms, nzero_words);
         first = np + 1;
-    } else if (M->nodal_pyramid && lb >= 1) {
-        // node-centred: levels 1..min(lb, 5) in one launch, the norm slots zeroed by it too
+    } else {
+        // node-centred: levels 1..min(lb, 5) in one launch (lb >= 1), the norm slots zeroed by it too
         NodalPyr o{};
         const int np = std::min(lb, NPYR_MAX);
         o.np = np;
@@ -2385,8 +1789,6 @@ static int solve1_hierarchy (Multigrid* M, int max_iters, hipStream_t st, const 
             default: hipLaunchKernelGGL(k_nodal_acf_pyramid<5>, dim3(tx, ty), dim3(256), nodal_pyramid_lds(np), st, M->acf0, o, M->d_norms, nzero_words); break;
         }
         first = np + 1;
-    } else {
-        HPS_HIP_CHECK(hipMemsetAsync(M->d_norms, 0, nzero_words*sizeof(unsigned long long), st));
     }
     for (int il = first; il <= lb; ++il) {
         const LevBox& cb = M->L[il].b;
@@ -2415,11 +1817,6 @@ static int solve1_begin (Multigrid* M, double tol_rel, double tol_abs, int max_i
     if (M->hierarchy_ready) M->hierarchy_ready = false;       // (mg_solve1_prepare has enqueued it; the caller has ordered the streams)
     else if (int e = solve1_hierarchy<CC>(M, max_iters, st)) return e;
     // cor[0] = GSRB^4(sol), residual norm, rhs norm, res[1] = R(residual)  (solve_doit :1319-1346)
-    // (optional 64 x 48 tiles: 494 workgroups at 1024^2 instead of 817 -- measured slower, see init_huge)
-    if (M->init_huge && M->L[0].cells > M->small_tile_cells)
-        launch_smooth_ts<TileHuge, CC, SRC_DIRECT, true>(M, 0, M->lv(0, M->L[0].cor), FView{}, M->rhs, M->acf0, M->sol, FView{}, M->lv(0, M->L[0].rescor),
-                                                         M->lv(1, M->L[1].res), M->d_norms, M->d_norms + MG_NSUB, always, st);
-    else
     launch_smooth<CC, SRC_DIRECT, true>(M, 0, M->lv(0, M->L[0].cor), FView{}, M->rhs, M->acf0, M->sol, FView{}, M->lv(0, M->L[0].rescor),
                                         M->lv(1, M->L[1].res), M->d_norms, M->d_norms + MG_NSUB, always, st);
     if (!M->nodal_pull1) restrict_residual_if_nodal<CC>(M, 0, always, st);
@@ -2540,8 +1937,8 @@ int mg_solve1_prepare_with (void* handle, hps_slab s, int sol_comp, int rhs_comp
 void mg_solve1_forget_hierarchy (void* handle) { if (handle) static_cast<Multigrid*>(handle)->hierarchy_ready = false; }
 // mg_defer_post ahead of mg_solve1_begin: the post of the first batch's norms is not launched but handed out by
 // mg_take_deferred_post -- the caller MUST then enqueue, next on the same stream, a kernel that performs it (k_advance_tiled's
-// MgPost argument), or the solve's finish never sees its norms.  (With HPS_MG_POST_FOLD the last V-cycle has posted already:
-// mg_take_deferred_post returns false and the caller gates on mg_gate_after_enqueued as before.)
+// MgPost argument), or the solve's finish never sees its norms.  (Without mg_defer_post k_post_norms has posted already:
+// mg_take_deferred_post returns false and the caller gates on mg_gate_after_enqueued.)
 void mg_defer_post (void* handle) { Multigrid* M = static_cast<Multigrid*>(handle); M->defer_post = true; M->deferred_valid = false; }
 bool mg_take_deferred_post (void* handle, MgPost* out)
 {

@@ -366,6 +366,7 @@ struct Multigrid2 {
 };
 
 static const long SINGLE_BLOCK_CELLS = LOW2_MAX_CELLS;      // above: the LDS-tiled kernel
+static const long BIG_TILE_CELLS = 256L*256L;               // above: 64 x 32 tiles, else 32 x 16 (32 x 16 on every level measured slower)
 
 // gsrb_4_residual (:742-848): out = 4 sweeps of src (zero | fin | fin + prolonged crse), optionally res = rhs - L(out) and
 // its max-norm.  out must not alias fin.  With crse_res (the next level's right-hand side) the tiled path restricts the
@@ -375,9 +376,8 @@ static bool smooth4 (const Lev2& l, int src_mode, const double* fin, const doubl
                      double* crse_res = nullptr, const Lev2* crl = nullptr)
 {
     if (l.n > SINGLE_BLOCK_CELLS) {
-        static const long big = getenv("HPS_MG2_BIG") ? atol(getenv("HPS_MG2_BIG")) : 256L*256L;      // measured: 65536 = 262144 > all small
         const bool fuse = do_res && crse_res && crl && l.nx % 2 == 0 && l.ny % 2 == 0;
-        if (l.n > big)
+        if (l.n > BIG_TILE_CELLS)
             hipLaunchKernelGGL((k2_smooth_tile<64, 32, 512>), dim3(ceil_div(l.nx, 64), ceil_div(l.ny, 32)), dim3(512), 0, st, l, src_mode, fin, crse,
                                cl ? cl->nx : 0, cl ? cl->n : 0L, out, rhs, acf, do_res ? 1 : 0, res, norm, fuse ? crse_res : (double*)nullptr,
                                fuse ? crl->nx : 0, fuse ? crl->n : 0L);

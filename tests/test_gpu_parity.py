@@ -154,11 +154,13 @@ def test_poisson_batch(api, oracle):
     assert np.all(out[[0, 3, 5]] == 0)
 
 
-@pytest.mark.parametrize("nx,ny", [(64, 64), (32, 32), (96, 48), (63, 63), (31, 63), (512, 512), (1024, 1024), (1023, 1023), (511, 511), (255, 127)])
+@pytest.mark.parametrize("nx,ny", [(64, 64), (32, 32), (96, 48), (63, 63), (31, 63), (512, 512), (1024, 1024), (1023, 1023), (511, 511), (255, 127),
+                                   (132, 66)])
 @pytest.mark.parametrize("warm", [False, True])
 def test_multigrid_solve1(api, oracle, nx, ny, warm):
     """Stand-alone hpmg solve1 against the oracle, up to the headline size (every kernel of the V-cycle: LDS-tiled
-    smoothers of the fine levels, fused level-0 end pass, k_lower_v2 / k_lower_v) with equal V-cycle counts."""
+    smoothers of the fine levels, fused level-0 end pass, k_lower_v3 / k_lower_v) with equal V-cycle counts.  132 x 66 is a
+    cell-centred grid whose coarsening stops at 66 x 33, too large for k_lower_v3: its lower V is k_lower_v<true>."""
     rng = np.random.default_rng(nx + 7 * ny)
     g = G2
     dx, dy = 16.0 / nx, 16.0 / ny
@@ -1672,7 +1674,7 @@ def _run_with_env(api, var, value, deck, n_steps, tile_size=16):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", ["gated_push", "lazy_shift", "fuse_sources", "aux_stream", "fold_beam", "fold_hierarchy", "mg_post_fold", "laser_stream_fft", "laser_stream_mg", "ion_tile_skip", "fold_tail", "gated_ion_push", "poisson_tridiag", "poisson_tridiag_dense", "poisson_tridiag_pow2", "pc_speculate", "valid_by_w", "valid_by_psi", "cu_masks", "post_in_push"])
+@pytest.mark.parametrize("case", ["gated_push", "lazy_shift", "fuse_sources", "aux_stream", "fold_beam", "fold_hierarchy", "laser_stream_fft", "laser_stream_mg", "ion_tile_skip", "fold_tail", "gated_ion_push", "poisson_tridiag", "poisson_tridiag_dense", "poisson_tridiag_pow2", "pc_speculate", "valid_by_w", "valid_by_psi", "cu_masks", "post_in_push"])
 def test_schedules_do_not_change_results(api, case):
     """The engine's scheduling choices -- the push enqueued behind the multigrid's V-cycles and gated on its stopping rule,
     the envelope solver on a stream of its own, the tiles of atoms that cannot ionise skipped before their image is loaded --
@@ -1688,8 +1690,6 @@ def test_schedules_do_not_change_results(api, case):
         var, deck, steps = "HPS_FOLD_BEAM", decks.blowout_wake(), 2
     elif case == "fold_hierarchy":  # the multigrid's coefficient hierarchy in the launch of the -grad Psi / Sx, Sy pass
         var, deck, steps = "HPS_FOLD_HIERARCHY", decks.blowout_wake(), 2
-    elif case == "mg_post_fold":    # the norms' post to the host and the gate of the push by the last workgroup of the last V-cycle's level-0 launch
-        var, deck, steps = "HPS_MG_POST_FOLD", decks.blowout_wake(), 2
     elif case == "aux_stream":      # the beam's deposition and the multigrid's coefficient hierarchy on a stream beside the slice's
         var, deck, steps = "HPS_AUX_STREAM", decks.blowout_wake(), 2
     elif case == "valid_by_w":       # the depositions read "weight != 0" instead of the valid bit of idcpu
