@@ -213,6 +213,15 @@ class FFTPoissonSolver:
     def StagingArea(self):
         return self.staging
 
+    BACKENDS = ("own-sym", "own-pow2", "dense", "rocfft")      # HPS_POISSON_* of include/hpslice.h
+
+    def info(self):
+        """(backend, x_len, tri_rows) the size dispatch chose: backend one of BACKENDS, x_len the length nx + 1 of the own DST
+        kernel along x (0: none), tri_rows the rows per thread M of k_tridiag_y<M, ..> along y (0: none, rocFFT)."""
+        b, n, m = C.c_int(), C.c_int(), C.c_int()
+        check(_lib.lib().hps_poisson_info(self._h, C.byref(b), C.byref(n), C.byref(m)))
+        return self.BACKENDS[b.value], n.value, m.value
+
     def SolvePoissonEquation(self, lhs_fields, comp):
         check(_lib.lib().hps_poisson_solve(self._h, C.c_void_p(self.staging.data_ptr()), lhs_fields.struct(), comp,
                                            _stream()))

@@ -733,7 +733,8 @@ void k_tridiag_y (TriArgs a)
 }
 typedef void (*tri_kernel_t)(TriArgs);
 struct TriImpl { int M, cols; tri_kernel_t kernel; };
-// rows per thread by plane height: at most 64 segments per column
+// rows per thread by plane height: at most 64 segments per column.  tests/test_poisson_dispatch_gpu.py lists these shapes
+// (TRI_ROWS) and solves a grid on both sides of every threshold: a shape added here needs a test grid there (same tests).
 static TriImpl find_tri_impl (int ny)
 {
     if (ny <= 256) return TriImpl{4, 16, k_tridiag_y<4, 16>};
@@ -829,6 +830,8 @@ typedef void (*dst_kernel_t)(DstArgs);
 struct DstImpl { int N, N1, N2; dst_kernel_t kernel, src; int T, nt; bool pow2; };      // pow2: k_dst_rows_pow2 (tables: w_N^k only)
 #define HPS_DST_SYM(N1, N2) DstImpl{(N1)*(N2), N1, N2, k_dst_rows_sym<N1, N2>, k_dst_rows_sym<N1, N2, true>, DSTS_T, DSTS_NT, false}
 #define HPS_DST_POW2(LOGN) DstImpl{1 << (LOGN), 1 << (LOGN), 1, k_dst_rows_pow2<LOGN>, k_dst_rows_pow2<LOGN, true>, DSTP_T, DSTP_NT, true}
+// tests/test_poisson_dispatch_gpu.py lists these lengths (OWN_X) and solves a grid with each: an entry added here needs a test
+// grid there (test_poisson_dispatch_lists_mirror_the_source_tables, test_every_kernel_of_the_dispatch_is_reached).
 static const DstImpl g_dst_impls[] = {
     HPS_DST_SYM(25, 41),    // nx = 1024
     HPS_DST_SYM(19, 27),    // 512
@@ -942,6 +945,7 @@ struct Poisson {
     // own back-end: DST along x, tridiagonal solves along y, DST along x
     dst_kernel_t kx = nullptr;
     dst_kernel_t kx_src = nullptr;      // the x pass with its rows formed from other planes
+    int x_len = 0; bool x_pow2 = false; // its transform length N = nx + 1 and kernel family (hps_poisson_info)
     double2* tab_x = nullptr;           // [fa | fb | tw] concatenated
     const double2 *fa_x = nullptr, *fb_x = nullptr, *tw_x = nullptr;
     size_t lds_x = 0; int tx = 0, ntx = 0;      // LDS bytes, row pairs and threads per workgroup of the x pass
@@ -1040,7 +1044,7 @@ int poisson_create (int nx, int ny, double dx, double dy, bool allow_own, Poisso
     const double pi = 3.14159265358979323846;
     if (ix && ti.kernel) {
         P->pa = ((long)nx + 15)/16*16;        // rows of the intermediate planes start on 128-byte lines (nx = 2^K - 1: 24.7 -> 18 us for the y solves)
-        P->kx = ix->kernel; P->kx_src = ix->src;
+        P->kx = ix->kernel; P->kx_src = ix->src; P->x_len = ix->N; P->x_pow2 = ix->pow2;
         int e;
         size_t nax, nbx;
         if ((e = upload_tables(ix->N1, ix->N2, ix->pow2, &P->tab_x, &nax, &nbx)) || (e = make_tri())) { delete P; return e; }
@@ -1285,6 +1289,17 @@ extern "C" int hps_poisson_solve_batch (void* handle, int nbatch, const double* 
         d[b] = slab_cell00(dst, dst_comps[b]);
     }
     return poisson_solve_batch(P, nbatch, s, P->nx, d, dst.jstride, (hipStream_t)stream);
+}
+
+extern "C" int hps_poisson_info (void* handle, int* backend, int* x_len, int* tri_rows)
+{
+    HPS_REQUIRE(handle, "hps_poisson_info: null handle");
+    const Poisson* P = static_cast<const Poisson*>(handle);
+    const int b = P->own() ? (P->x_pow2 ? HPS_POISSON_OWN_POW2 : HPS_POISSON_OWN_SYM) : P->dense() ? HPS_POISSON_DENSE : HPS_POISSON_ROCFFT;
+    if (backend) *backend = b;
+    if (x_len) *x_len = P->own() ? P->x_len : 0;
+    if (tri_rows) *tri_rows = P->ktri ? P->tri_M : 0;
+    return HPS_OK;
 }
 
 extern "C" int hps_poisson_debug_stamps (void* handle, long long* stamps6_host)      // [4 workgroups][6 stamps]

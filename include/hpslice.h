@@ -151,6 +151,11 @@ int hps_poisson_solve (void* handle, const double* staging, hps_slab dst, int ds
  * their launches this way. */
 int hps_poisson_solve_batch (void* handle, int nbatch, const double* staging, hps_slab dst,
                              const int* dst_comps, hps_stream stream);
+/* Which kernels the size dispatch of hps_poisson_create chose: *backend one of HPS_POISSON_*; *x_len the
+ * length N = nx + 1 of the own DST kernel along x (0 for the dense product and rocFFT); *tri_rows the rows per
+ * thread M of the tridiagonal solve along y, k_tridiag_y<M, ..> (0 for rocFFT).  Null outputs are skipped. */
+enum { HPS_POISSON_OWN_SYM = 0, HPS_POISSON_OWN_POW2 = 1, HPS_POISSON_DENSE = 2, HPS_POISSON_ROCFFT = 3 };
+int hps_poisson_info (void* handle, int* backend, int* x_len, int* tri_rows);
 int hps_poisson_destroy (void* handle);
 
 /* hpmg::MultiGrid, system type 1 (mg_solver/HpMultiGrid.H:48,64-66; .cpp:1169-1190,1307-1427):

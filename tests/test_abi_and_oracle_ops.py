@@ -89,6 +89,65 @@ def test_oracle_poisson_inverts_five_point_laplacian(oracle):
     assert np.abs(lap - rhs).max() < 1e-11
 
 
+def _dispatch_shapes():
+    from tests.test_poisson_dispatch_gpu import SINGLE
+    return sorted({(nx, ny, dx, dy) for nx, ny, (dx, dy), _ in SINGLE})
+
+
+@pytest.mark.parametrize("axis", [0, 1])
+@pytest.mark.parametrize("n", [1, 2, 7, 64, 99, 2047])
+def test_numpy_dst_matches_scipy(n, axis):
+    import scipy.fft
+    from tests.util import dst1
+    x = np.random.default_rng(n).standard_normal((n, 5) if axis == 0 else (5, n))
+    ref = scipy.fft.dst(x, type=1, axis=axis)
+    assert np.abs(dst1(x, axis) - ref).max() <= 1e-13 * np.abs(ref).max()
+    assert np.abs(dst1(dst1(x, axis), axis) / (2 * (n + 1)) - x).max() <= 1e-13 * np.abs(x).max()
+
+
+@pytest.mark.parametrize("nx,ny,dx,dy", [(76, 76, 0.25, 0.2), (98, 40, 0.25, 0.2), (64, 2100, 0.25, 0.2), (300, 300, 1.0, 0.02),
+                                         (64, 2000, 0.02, 1.0), (2, 3, 0.25, 0.2)])
+def test_numpy_poisson_ref_matches_scipy_dstn(nx, ny, dx, dy):
+    import scipy.fft
+    from tests.util import poisson_dirichlet_ref, rel_err
+    rhs = np.random.default_rng(nx + ny).standard_normal((ny, nx))
+    sx = np.sin(np.pi * np.arange(1, nx + 1) / (2 * (nx + 1))) ** 2
+    sy = np.sin(np.pi * np.arange(1, ny + 1) / (2 * (ny + 1))) ** 2
+    ref = scipy.fft.idstn(scipy.fft.dstn(rhs, type=1) / (-4 * sx[None, :] / dx ** 2 - 4 * sy[:, None] / dy ** 2), type=1)
+    assert rel_err(poisson_dirichlet_ref(rhs, dx, dy), ref) < 1e-14
+
+
+@pytest.mark.parametrize("nx,ny,dx,dy", _dispatch_shapes())
+def test_numpy_poisson_ref_matches_oracle_and_inverts_the_laplacian(oracle, nx, ny, dx, dy):
+    """The reference of tests/test_poisson_dispatch_gpu.py at every shape of its table: equal to the oracle's FFTW-convention
+    solve, and the 5-point Laplacian of its solution is the source.  Residual bound: each solution value is off by a few eps
+    of max|F| (O(log n) transforms), and the operator amplifies an error by at most 4/dx^2 + 4/dy^2."""
+    from tests.util import poisson_dirichlet_ref, rel_err
+    rhs = np.random.default_rng(nx * 31 + ny).standard_normal((ny, nx))
+    F = poisson_dirichlet_ref(rhs, dx, dy)
+    assert rel_err(F, oracle.poisson_solve(rhs, dx, dy)) < 1e-14
+    P = np.pad(F, 1)
+    lap = (P[1:-1, 2:] + P[1:-1, :-2] - 2 * P[1:-1, 1:-1]) / dx ** 2 + (P[2:, 1:-1] + P[:-2, 1:-1] - 2 * P[1:-1, 1:-1]) / dy ** 2
+    assert np.abs(lap - rhs).max() <= 64 * np.finfo(float).eps * (4 / dx ** 2 + 4 / dy ** 2) * np.abs(F).max()
+
+
+def test_poisson_dispatch_lists_mirror_the_source_tables():
+    """OWN_X / TRI_ROWS of tests/test_poisson_dispatch_gpu.py are g_dst_impls / find_tri_impl of poisson.hip: an entry added
+    there without a test grid fails here (and the GPU module's completeness test checks the grids reach every entry)."""
+    from tests.test_poisson_dispatch_gpu import OWN_X, TRI_ROWS
+    src = open(os.path.join(ROOT, "hipace_amd", "csrc", "poisson.hip")).read()
+    table = re.search(r"g_dst_impls\[\] = \{(.*?)\};", src, re.S).group(1)
+    table = re.sub(r"//[^\n]*", "", table)
+    own = {int(a) * int(b): "own-sym" for a, b in re.findall(r"HPS_DST_SYM\((\d+),\s*(\d+)\)", table)}
+    own.update({1 << int(k): "own-pow2" for k in re.findall(r"HPS_DST_POW2\((\d+)\)", table)})
+    assert len(own) == len(re.findall(r"HPS_DST_\w+\(", table))
+    assert own == OWN_X
+    body = re.search(r"static TriImpl find_tri_impl \(int ny\)\s*\{(.*?)\n\}", src, re.S).group(1)
+    tri = {int(lim): int(m) for lim, m in re.findall(r"if \(ny <= (\d+)\) return TriImpl\{(\d+),", body)}
+    assert len(tri) == body.count("k_tridiag_y<")
+    assert tri == TRI_ROWS
+
+
 @pytest.mark.parametrize("n", [32, 63])
 def test_oracle_multigrid_residual_and_iteration_count(oracle, n):
     """hpmg converges ~50x per V-cycle: 3 V-cycles to 1e-4 from a zero guess (measured

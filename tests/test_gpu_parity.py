@@ -114,7 +114,9 @@ def test_advance_plasma(api, oracle, order, bc, nsc):
 
 @pytest.mark.parametrize("nx,ny", [(64, 64), (32, 48), (63, 63), (127, 65), (32, 64), (128, 32), (512, 512),
                                    (1024, 1024), (1023, 1023), (256, 256), (256, 100), (48, 500), (600, 520),
-                                   (511, 511), (255, 255), (511, 127), (1023, 511), (2047, 255)])      # every length of the power-of-two kernel (2^6 .. 2^11)
+                                   (511, 511), (255, 255), (511, 127), (1023, 511), (2047, 255)])
+# against the oracle: every length of the power-of-two kernel (2^6 .. 2^11), five of the seven lengths of the symmetric one,
+# three of the four tridiagonal shapes (ny <= 1024); tests/test_poisson_dispatch_gpu.py reaches every kernel of the dispatch
 def test_poisson(api, oracle, nx, ny):
     import torch
     rng = np.random.default_rng(nx * 1000 + ny)
@@ -155,7 +157,7 @@ def test_poisson_batch(api, oracle):
 
 
 @pytest.mark.parametrize("nx,ny", [(64, 64), (32, 32), (96, 48), (63, 63), (31, 63), (512, 512), (1024, 1024), (1023, 1023), (511, 511), (255, 127),
-                                   (132, 66)])
+                                   (132, 66), (2047, 2047)])
 @pytest.mark.parametrize("warm", [False, True])
 def test_multigrid_solve1(api, oracle, nx, ny, warm):
     """Stand-alone hpmg solve1 against the oracle, up to the headline size (every kernel of the V-cycle: LDS-tiled
@@ -299,11 +301,11 @@ def test_full_size_properties(api):
     assert res.abs().max().item() <= 1e-8 * R.abs().max().item() * 1.0001
 
 
-@pytest.mark.parametrize("n,nsl", [(512, 6), (1024, 3), (1023, 3), (511, 5)])
+@pytest.mark.parametrize("n,nsl", [(512, 6), (1024, 3), (1023, 3), (511, 5), (2047, 3)])
 def test_baseline_blowout_configs_head_slices(api, oracle, n, nsl):
     """BASELINE configs 3 and 4 at their full transverse size (blowout_wake n x n x 1024, 4 ppc, explicit solver) -- and the
-    grid the reference recommends, 2^N - 1 = 1023 cells per side (docs/source/run/parameters.rst:313-321: length-1024
-    transforms, node-centred multigrid coarsening) --:
+    grid the reference recommends, 2^N - 1 = 1023 and 2047 cells per side (docs/source/run/parameters.rst:313-321: length-1024
+    and -2048 transforms, node-centred multigrid coarsening; at 2047 the y solves are k_tridiag_y<32, 8>) --:
     a few slices through the driver against the oracle -- every slab component and the V-cycle count.  Both engines
     start on a slice one sigma ahead of the beam centre (the static beam blocks are addressed by slice), where the
     fields are strong from the first slice on.  (The whole box would take the oracle 20 min to 1 h; the decks'

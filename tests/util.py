@@ -59,3 +59,24 @@ def rel_err(a, b):
     b = np.asarray(b)
     scale = max(np.abs(b).max(), 1e-300)
     return np.abs(a - b).max() / scale
+
+
+def dst1(x, axis=-1):
+    """DST-I along `axis` in FFTW's RODFT00 scaling, Y_k = 2 sum_j x_j sin(pi (j+1)(k+1) / (n+1)), from a real FFT of the
+    odd extension (0, x, 0, -reversed x) of length 2(n+1): numpy only, independent of the oracle.  dst1(dst1(x)) = 2(n+1) x."""
+    x = np.moveaxis(np.asarray(x, dtype=np.float64), axis, -1)
+    n = x.shape[-1]
+    z = np.zeros(x.shape[:-1] + (1,))
+    ext = np.concatenate([z, x, z, -x[..., ::-1]], axis=-1)
+    return np.moveaxis(-np.fft.rfft(ext, axis=-1).imag[..., 1:n + 1], -1, axis)
+
+
+def poisson_dirichlet_ref(rhs, dx, dy):
+    """Lap(F) = rhs on an (ny, nx) box, F = 0 one cell outside, with the 5-point Laplacian: DST-I along both directions,
+    division by its eigenvalues -4/dx^2 sin^2(pi k / 2(nx+1)) - 4/dy^2 sin^2(pi l / 2(ny+1)), DST-I back."""
+    ny, nx = rhs.shape
+    sx = np.sin(np.pi * np.arange(1, nx + 1) / (2.0 * (nx + 1))) ** 2
+    sy = np.sin(np.pi * np.arange(1, ny + 1) / (2.0 * (ny + 1))) ** 2
+    eig = -4.0 * sx[None, :] / dx ** 2 - 4.0 * sy[:, None] / dy ** 2
+    u = dst1(dst1(rhs, axis=1), axis=0) / eig
+    return dst1(dst1(u, axis=1), axis=0) / (4.0 * (nx + 1) * (ny + 1))
