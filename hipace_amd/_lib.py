@@ -111,10 +111,13 @@ _SIGS = {
                                 C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p]),
     "hps_mg_solve1_fabs": (C.c_int, [C.c_void_p, Slab, Slab, Slab, C.c_double, C.c_double, C.c_int,
                                      C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p]),
+    "hps_mg_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                              C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hps_mg_destroy": (C.c_int, [C.c_void_p]),
     "hps_mg2_create": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
     "hps_mg2_solve2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
                                  C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p]),
+    "hps_mg2_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hps_mg2_destroy": (C.c_int, [C.c_void_p]),
     "hps_engine_laser_vcycles": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
     "hps_engine_create": (C.c_int, [C.POINTER(Deck), C.c_int, C.POINTER(C.c_void_p)]),

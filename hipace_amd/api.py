@@ -249,6 +249,18 @@ class MultiGrid2:
                                         tol_rel, tol_abs, nummaxiter, C.byref(it), C.byref(rn), _stream()))
         return it.value, rn.value
 
+    BOTTOMS = ("lower-v", "single-block", "per-sweep")      # HPS_MG2_BOTTOM_* of include/hpslice.h
+    TILES = ("single-block", "32x16", "64x32")              # HPS_MG2_TILE_*
+
+    def info(self):
+        """What the size dispatch chose: {"nlev", "low_top" (first level of k2_lower_v, -1: none), "bottom" (one of BOTTOMS:
+        k2_lower_v, or the generic bottom in one k2_sweeps launch or one launch per sweep), "tiles" (one of TILES for each
+        level above the bottom part)}."""
+        nl, top, b, t = C.c_int(), C.c_int(), C.c_int(), (C.c_int * 31)()
+        check(_lib.lib().hps_mg2_info(self._h, C.byref(nl), C.byref(top), C.byref(b), t))
+        return {"nlev": nl.value, "low_top": top.value, "bottom": self.BOTTOMS[b.value],
+                "tiles": tuple(self.TILES[v] for v in t if v >= 0)}
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.lib().hps_mg2_destroy(self._h)
@@ -256,11 +268,34 @@ class MultiGrid2:
 
 
 class MultiGrid:
-    """hpmg::MultiGrid system type 1."""
+    """hpmg::MultiGrid system type 1.
+
+    The levels from the first one with at most 34 x 34 cells down run in one workgroup with all their arrays in LDS
+    (k_lower_v3 / k_lower_v).  Where no level is that small and the coarsest one does not fit one workgroup's LDS (160 KiB:
+    300^2, 129^2 or 1025^2, whose coarsening stops early), the coarsest level is swept in global memory instead, with
+    max(16, longest side rounded up to even) red-black sweeps: the reference's CPU branch, for which it prints the warning
+    that the grid should be a power of two (cell-centred) or one more (node-centred) for the single-block bottom solver
+    (HpMultiGrid.cpp:1076-1089, 1583-1593).  The solution is the reference's either way; info() reports the choice."""
 
     def __init__(self, nx, ny, dx, dy):
         self._h = C.c_void_p()
         check(_lib.lib().hps_mg_create(nx, ny, dx, dy, C.byref(self._h)))
+
+    LOWV = ("v3", "v-cc", "v-nodal", "bottom")                      # HPS_MG_LOWV_* of include/hpslice.h
+    TILES = ("TileSmall", "TileBig", "TileSmall-pull", "TileMid-pull")    # HPS_MG_TILE_*
+
+    def info(self):
+        """What the size dispatch chose: {"cc", "nlev", "lowv_begin", "lowv" (one of LOWV), "lowv_lds" (dynamic LDS bytes of the
+        lower V, 0 for the bottom), "tiles" (one of TILES for level 0's initial pass and the down-leg of levels 1 ..
+        lowv_begin - 1), "nodal_pull1", "pyramid" (levels k_acf_pyramid / k_nodal_acf_pyramid<n> derives), "restricts"
+        (k_restrict launches behind it)}."""
+        cc, nl, lb, kind, npyr, nres, pull1 = (C.c_int() for _ in range(7))
+        lds, t = C.c_long(), (C.c_int * 31)()
+        check(_lib.lib().hps_mg_info(self._h, C.byref(cc), C.byref(nl), C.byref(lb), C.byref(kind), C.byref(lds), t,
+                                     C.byref(pull1), C.byref(npyr), C.byref(nres)))
+        return {"cc": bool(cc.value), "nlev": nl.value, "lowv_begin": lb.value, "lowv": self.LOWV[kind.value],
+                "lowv_lds": lds.value, "tiles": tuple(self.TILES[v] for v in t if v >= 0), "nodal_pull1": bool(pull1.value),
+                "pyramid": npyr.value, "restricts": nres.value}
 
     def solve1(self, fields, sol_comp, rhs_comp, acoef_comp, tol_rel=1e-4, tol_abs=2.2250738585072014e-308,
                nummaxiter=200):

@@ -1454,6 +1454,33 @@ __global__ void k_copy2 (LevBox b, FView dst, FView src)
     dst(i, j, 0) = src(i, j, 0); dst(i, j, 1) = src(i, j, 1);
 }
 
+// The generic bottom: the reference's CPU branch (bottomsolve, HpMultiGrid.cpp:1583-1593), taken when the lower V would need
+// more LDS than one workgroup has (no level of at most LOWV_MAX_CELLS: the coarsest level is large).  The coarsest level's
+// correction is zeroed (is < 0), then swept once per launch, colour (i + j + is) % 2 == 0 in level index space, in global
+// memory.  Neighbours outside a cell-centred box are not read (the wall stencil does not use them); node-centred walls hold 0.
+template <bool CC>
+__global__ __launch_bounds__(256)
+void k_bottom_sweep (LevBox b, FView cor, FView rhs, FView acf, double facx, double facy, int is, StopRule sr)
+{
+    if (!vcycle_active(sr)) return;
+    const int i = b.vlx + blockIdx.x*blockDim.x + threadIdx.x;
+    const int j = b.vly + blockIdx.y;
+    if (i > b.vhx || j > b.vhy) return;
+    if (is < 0) { cor(i, j, 0) = 0.0; cor(i, j, 1) = 0.0; return; }
+    if ((i + j + is) & 1) return;
+    const double ci = 1.0/diag_c0<CC>(i, j, b, acf(i, j, 0), facx, facy);
+    for (int n = 0; n < 2; ++n) {
+        const double w = (i > b.lox) ? cor(i-1, j, n) : 0.0, e = (i < b.hix) ? cor(i+1, j, n) : 0.0;
+        const double s = (j > b.loy) ? cor(i, j-1, n) : 0.0, no = (j < b.hiy) ? cor(i, j+1, n) : 0.0;
+        double lx = facx*(w + e), ly = facy*(s + no);
+        if (CC) {
+            lx = (i == b.lox) ? facx*(4./3.)*e : ((i == b.hix) ? facx*(4./3.)*w : lx);
+            ly = (j == b.loy) ? facy*(4./3.)*no : ((j == b.hiy) ? facy*(4./3.)*s : ly);
+        }
+        cor(i, j, n) = (rhs(i, j, n) - (lx + ly))*ci;
+    }
+}
+
 struct MGLevelDev { LevBox b; long cells; double *acf, *res, *cor, *rescor; };
 
 constexpr long LOWV_MAX_CELLS = 34*34;     // levels with at most ~32x32 unknowns run in k_lower_v (LDS resident)
@@ -1469,6 +1496,7 @@ struct Multigrid {
     std::vector<MGLevelDev> L;
     int lowv_begin = 1;                         // first level handled by k_lower_v
     LowLev* d_low = nullptr; size_t low_lds = 0;
+    bool bottom = false;                        // the lower V does not fit: lowv_begin = coarsest level, swept by k_bottom_sweep
     // device / pinned buffers: one header slot (MG_NSUB words: a caller's counters ride along with the norm
     // read-back, see hps_mg_rider) followed by the norm slots; d_norms / h_norms point at slot 0
     unsigned long long *d_buf = nullptr, *h_buf = nullptr;
@@ -1499,7 +1527,26 @@ struct Multigrid {
         return FView{p, nxb, l.cells, -l.b.lox, -l.b.loy};
     }
     int nlev () const { return (int)L.size(); }
+    bool pulls (int il) const {
+        return !cc && ((il >= 2 && ((il < lowv_begin && L[il].cells <= SMALL_TILE_CELLS) ||
+                                    (il == lowv_begin && !use_low3 && !bottom))) ||      // (il == lowv_begin: k_lower_v's own load)
+                       (il == 1 && nodal_pull1));
+    }
 };
+
+// LDS one workgroup may have (163 840 B on MI355X); queried once.  (The opt-in attribute as well: where a runtime reports a
+// smaller default per-block figure, launches up to the opt-in limit still work after hipFuncSetAttribute.)
+static size_t device_max_lds ()
+{
+    static const size_t lim = [] {
+        int dev = 0, a = 0, b = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return (size_t)0;
+        if (hipDeviceGetAttribute(&a, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) a = 0;
+        if (hipDeviceGetAttribute(&b, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess) b = 0;
+        return (size_t)std::max(a, b);
+    }();
+    return lim;
+}
 
 int mg_create (int nx, int ny, double dx, double dy, Multigrid** out)
 {
@@ -1568,22 +1615,31 @@ int mg_create (int nx, int ny, double dx, double dy, Multigrid** out)
             break;
         }
     }
+    if (!M->use_low3) {
+        long cells = 0;
+        for (int il = M->lowv_begin; il < nl; ++il) cells += M->L[il].cells;
+        M->low_lds = (size_t)(8*cells)*sizeof(double);
+        hipFuncAttributes fa{};
+        HPS_HIP_CHECK(hipFuncGetAttributes(&fa, M->cc ? (const void*)k_lower_v<true> : (const void*)k_lower_v<false>));
+        if (M->low_lds + fa.sharedSizeBytes > device_max_lds()) { M->bottom = true; M->lowv_begin = nl - 1; M->low_lds = 0; }
+    }
     // node-centred: level 1 pulls (vcycle: pulls) when it is a smoother level of its own, not the lower V's top
     M->nodal_pull1 = !M->cc && M->lowv_begin > 1;
-    std::vector<LowLev> low;
-    int off = 0;
-    for (int il = M->lowv_begin; il < nl; ++il) {
-        const MGLevelDev& l = M->L[il];
-        low.push_back(LowLev{l.b, l.b.hix - l.b.lox + 1, (int)l.cells, off});
-        off += 8*(int)l.cells;
+    if (!M->use_low3 && !M->bottom) {
+        std::vector<LowLev> low;
+        int off = 0;
+        for (int il = M->lowv_begin; il < nl; ++il) {
+            const MGLevelDev& l = M->L[il];
+            low.push_back(LowLev{l.b, l.b.hix - l.b.lox + 1, (int)l.cells, off});
+            off += 8*(int)l.cells;
+        }
+        if (M->low_lds > 64*1024) {
+            HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low_lds));
+            HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low_lds));
+        }
+        HPS_HIP_CHECK(hipMalloc(&M->d_low, low.size()*sizeof(LowLev)));
+        HPS_HIP_CHECK(hipMemcpy(M->d_low, low.data(), low.size()*sizeof(LowLev), hipMemcpyHostToDevice));
     }
-    M->low_lds = (size_t)off*sizeof(double);
-    if (!M->use_low3 && M->low_lds > 64*1024) {
-        HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low_lds));
-        HPS_HIP_CHECK(hipFuncSetAttribute((const void*)k_lower_v<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)M->low_lds));
-    }
-    HPS_HIP_CHECK(hipMalloc(&M->d_low, low.size()*sizeof(LowLev)));
-    HPS_HIP_CHECK(hipMemcpy(M->d_low, low.data(), low.size()*sizeof(LowLev), hipMemcpyHostToDevice));
     HPS_HIP_CHECK(hipMalloc(&M->d_buf, (3 + MG_MAX_VCYCLES)*MG_NSUB*sizeof(unsigned long long)));
     HPS_HIP_CHECK(hipHostMalloc(&M->h_buf, ((3 + MG_MAX_VCYCLES)*MG_NSUB + 8)*sizeof(unsigned long long), hipHostMallocMapped));
     HPS_HIP_CHECK(hipHostGetDevicePointer((void**)&M->h_buf_dev, M->h_buf, 0));
@@ -1649,11 +1705,8 @@ static void vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStre
     // (levels on 32 x 16 tiles only: with the nine reads per cell in flight the 64 x 32 variant spills 108 registers under its cap)
     // (round 6: level 1 too -- on 32 x 32 tiles of 256 threads where it is too large for the 32 x 16 ones: the 64 x 32 variant's 512
     //  threads are what capped its registers -- so the level 0 -> 1 restriction launch is gone as well: M->nodal_pull1)
-    auto pulls = [&] (int il) { return !CC && ((il >= 2 && ((il < lb && M->L[il].cells <= SMALL_TILE_CELLS) ||
-                                                           (il == lb && !M->use_low3))) ||      // (il == lb: k_lower_v's own load)
-                                              (il == 1 && M->nodal_pull1)); };
     for (int il = 1; il < lb; ++il) {
-        if (!pulls(il))
+        if (!M->pulls(il))
             launch_smooth<CC, SRC_ZERO, true>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
                                               none, M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
         else if constexpr (!CC) {
@@ -1664,19 +1717,24 @@ static void vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStre
                 launch_smooth_ts<TileSmall, CC, SRC_ZERO, true, 4, true>(M, il, M->lv(il, M->L[il].cor), none, M->lv(il, M->L[il].res), M->lv(il, M->L[il].acf), none,
                                                                          M->lv(il-1, M->L[il-1].rescor), M->lv(il, M->L[il].rescor), M->lv(il+1, M->L[il+1].res), nullptr, nullptr, sr, st);
         }
-        if (!pulls(il + 1)) restrict_residual_if_nodal<CC>(M, il, sr, st);
+        if (!M->pulls(il + 1)) restrict_residual_if_nodal<CC>(M, il, sr, st);
     }
     {
         const double fac = (double)(1 << lb);
         const double ldx = M->dx*fac, ldy = M->dy*fac;
         const LevBox& bb = M->L[nl-1].b;
         const int nsweeps = std::max(16, (std::max(bb.hix - bb.lox + 1, bb.hiy - bb.loy + 1) + 1)/2*2);
-        if (M->use_low3)
+        if (M->bottom) {
+            const FView cor = M->lv(lb, M->L[lb].cor), rhs = M->lv(lb, M->L[lb].res), acf = M->lv(lb, M->L[lb].acf);
+            const dim3 grid(ceil_div(bb.vhx - bb.vlx + 1, 64), bb.vhy - bb.vly + 1);
+            for (int is = -1; is < nsweeps; ++is)
+                hipLaunchKernelGGL(k_bottom_sweep<CC>, grid, dim3(64), 0, st, bb, cor, rhs, acf, 1.0/(ldx*ldx), 1.0/(ldy*ldy), is, sr);
+        } else if (M->use_low3)
             hipLaunchKernelGGL(k_lower_v3, dim3(2), dim3(1024), M->low3_lds, st, M->d_low3, M->L[lb].acf, M->cinvA, M->L[lb].res, M->L[lb].cor,
                                M->coef_img, M->low3.nx[0], M->low3.ny[0], M->low3.ctot, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr);
         else      // (node-centred: one field component per workgroup)
             hipLaunchKernelGGL(k_lower_v<CC>, dim3(CC ? 1 : 2), dim3(1024), M->low_lds, st, M->d_low, nl - lb, M->L[lb].acf, M->L[lb].res,
-                               M->L[lb].cor, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, pulls(lb) ? M->lv(lb-1, M->L[lb-1].rescor) : FView{});
+                               M->L[lb].cor, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, M->pulls(lb) ? M->lv(lb-1, M->L[lb-1].rescor) : FView{});
     }
     // up-leg: the smoothed correction of level il lands in rescor[il] (out of place)
     for (int il = lb - 1; il >= 1; --il) {
@@ -1981,6 +2039,34 @@ extern "C" int hps_mg_create (int nx, int ny, double dx, double dy, void** handl
     Multigrid* M = nullptr;
     if (int e = mg_create(nx, ny, dx, dy, &M)) return e;
     *handle = M;
+    return HPS_OK;
+}
+
+extern "C" int hps_mg_info (void* handle, int* cc, int* nlev, int* lowv_begin, int* lowv_kind, long* lowv_lds, int* tiles,
+                            int* nodal_pull1, int* pyr_levels, int* pyr_restricts)
+{
+    HPS_REQUIRE(handle, "hps_mg_info: null handle");
+    const Multigrid* M = static_cast<const Multigrid*>(handle);
+    const int lb = M->lowv_begin;
+    if (cc) *cc = M->cc;
+    if (nlev) *nlev = M->nlev();
+    if (lowv_begin) *lowv_begin = lb;
+    if (lowv_kind) *lowv_kind = M->bottom ? HPS_MG_LOWV_BOTTOM : M->use_low3 ? HPS_MG_LOWV_V3 : M->cc ? HPS_MG_LOWV_CC : HPS_MG_LOWV_NODAL;
+    if (lowv_lds) *lowv_lds = (long)(M->use_low3 ? M->low3_lds : M->low_lds);
+    if (tiles) {
+        // as launch_smooth and vcycle's pulls choose them: level 0's initial pass, then the down-leg of levels 1 .. lb - 1
+        for (int il = 0; il < HPS_MG_MAXLEV; ++il) {
+            int t = -1;
+            if (il < lb) {
+                const bool small = M->L[il].cells <= SMALL_TILE_CELLS;
+                t = M->pulls(il) ? (small ? HPS_MG_TILE_SMALL_PULL : HPS_MG_TILE_MID_PULL) : (small ? HPS_MG_TILE_SMALL : HPS_MG_TILE_BIG);
+            }
+            tiles[il] = t;
+        }
+    }
+    if (nodal_pull1) *nodal_pull1 = M->nodal_pull1;
+    if (pyr_levels) *pyr_levels = std::min(lb, M->cc ? 5 : NPYR_MAX);
+    if (pyr_restricts) *pyr_restricts = lb - std::min(lb, M->cc ? 5 : NPYR_MAX);
     return HPS_OK;
 }
 

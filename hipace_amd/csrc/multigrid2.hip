@@ -406,6 +406,7 @@ static int mg2_create (int nx, int ny, double dx, double dy, Multigrid2** out)
         if (!ok) break;
         lx /= 2; ly /= 2;
     }
+    if (M->L.size() < 2) { delete M; set_error("hps_mg2_create: grid too small to coarsen"); return HPS_ERR_ARG; }
     for (const Lev2& l : M->L) {
         double* p[4];
         for (int k = 0; k < 4; ++k) { HPS_HIP_CHECK(hipMalloc(&p[k], (size_t)2*l.n*sizeof(double))); HPS_HIP_CHECK(hipMemset(p[k], 0, (size_t)2*l.n*sizeof(double))); }
@@ -567,6 +568,23 @@ extern "C" int hps_mg2_solve2 (void* handle, double* sol2_dev, const double* rhs
     HPS_REQUIRE(handle && sol2_dev && rhs2_dev && acoef_real_dev && acoef_imag_dev, "hps_mg2_solve2: null argument");
     return mg2_solve2(static_cast<Multigrid2*>(handle), sol2_dev, rhs2_dev, acoef_real_dev, acoef_imag_dev, tol_rel, tol_abs,
                       max_iters, iters_host, resnorm_host, (hipStream_t)stream);
+}
+
+extern "C" int hps_mg2_info (void* handle, int* nlev, int* low_top, int* bottom, int* tiles)
+{
+    HPS_REQUIRE(handle, "hps_mg2_info: null handle");
+    const Multigrid2* M = static_cast<const Multigrid2*>(handle);
+    const int nl = (int)M->L.size();
+    const int top = (M->low_top >= 1) ? M->low_top : nl - 1;      // as vcycle2 and smooth4 choose
+    if (nlev) *nlev = nl;
+    if (low_top) *low_top = M->low_top;
+    if (bottom) *bottom = (M->low_top >= 1) ? HPS_MG2_BOTTOM_LOWER_V
+                        : (M->L[nl - 1].n <= SINGLE_BLOCK_CELLS) ? HPS_MG2_BOTTOM_SINGLE_BLOCK : HPS_MG2_BOTTOM_PER_SWEEP;
+    if (tiles)
+        for (int il = 0; il < HPS_MG_MAXLEV; ++il)
+            tiles[il] = (il >= top) ? -1 : (M->L[il].n <= SINGLE_BLOCK_CELLS) ? HPS_MG2_TILE_SINGLE_BLOCK
+                      : (M->L[il].n > BIG_TILE_CELLS) ? HPS_MG2_TILE_BIG : HPS_MG2_TILE_SMALL;
+    return HPS_OK;
 }
 
 extern "C" int hps_mg2_destroy (void* handle)

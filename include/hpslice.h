@@ -174,6 +174,21 @@ int hps_mg_solve1 (void* handle, hps_slab slab, int sol_comp, int rhs_comp, int 
  * acoef1 with one; component 0 of each view is used (point .p at the first component wanted) */
 int hps_mg_solve1_fabs (void* handle, hps_slab sol2, hps_slab rhs2, hps_slab acoef1, double tol_rel, double tol_abs,
                         int max_iters, int* iters_host, double* resnorm_host, hps_stream stream);
+/* Which kernels the size dispatch of hps_mg_create chose.  Null outputs are skipped.
+ *   *cc: 1 cell-centred (even nx, ny), 0 node-centred; *nlev: levels of the hierarchy;
+ *   *lowv_begin: first level of the lower V; *lowv_kind: HPS_MG_LOWV_* -- k_lower_v3, k_lower_v<true>, k_lower_v<false>, or
+ *     the generic bottom (the reference's CPU branch: no level is small enough for one workgroup's LDS, so levels 1 .. nlev - 2
+ *     are smoothed level by level and the coarsest one is swept in global memory); *lowv_lds: its dynamic LDS bytes (0: bottom);
+ *   tiles[HPS_MG_MAXLEV]: HPS_MG_TILE_* of level 0's initial pass and of the down-leg smoother of levels 1 .. lowv_begin - 1,
+ *     -1 from lowv_begin on;
+ *   *nodal_pull1: node-centred level 1 forms its right-hand side from level 0's residual itself;
+ *   *pyr_levels: levels the coefficient pyramid kernel derives (k_acf_pyramid / k_nodal_acf_pyramid<n>), *pyr_restricts:
+ *     k_restrict launches behind it down to lowv_begin. */
+enum { HPS_MG_LOWV_V3 = 0, HPS_MG_LOWV_CC = 1, HPS_MG_LOWV_NODAL = 2, HPS_MG_LOWV_BOTTOM = 3 };
+enum { HPS_MG_TILE_SMALL = 0, HPS_MG_TILE_BIG = 1, HPS_MG_TILE_SMALL_PULL = 2, HPS_MG_TILE_MID_PULL = 3 };
+enum { HPS_MG_MAXLEV = 31 };
+int hps_mg_info (void* handle, int* cc, int* nlev, int* lowv_begin, int* lowv_kind, long* lowv_lds, int* tiles,
+                 int* nodal_pull1, int* pyr_levels, int* pyr_restricts);
 int hps_mg_destroy (void* handle);
 
 /* hpmg::MultiGrid, system type 2 (mg_solver/HpMultiGrid.H:48,84-87 solve2 with an array Re and a scalar Im coefficient;
@@ -186,6 +201,12 @@ int hps_mg2_create (int nx, int ny, double dx, double dy, void** handle);
 int hps_mg2_solve2 (void* handle, double* sol2_dev, const double* rhs2_dev, const double* acoef_real_dev,
                     const double* acoef_imag_dev, double tol_rel, double tol_abs, int max_iters, int* iters_host,
                     double* resnorm_host, hps_stream stream);
+/* Which kernels the size dispatch of hps_mg2_create chose.  Null outputs are skipped.  *nlev: levels; *low_top: first level of
+ * k2_lower_v (-1: none, the generic bottom); *bottom: HPS_MG2_BOTTOM_*; tiles[HPS_MG_MAXLEV]: HPS_MG2_TILE_* of the smoother
+ * of levels 0 .. (low_top or nlev - 1) - 1, -1 below. */
+enum { HPS_MG2_BOTTOM_LOWER_V = 0, HPS_MG2_BOTTOM_SINGLE_BLOCK = 1, HPS_MG2_BOTTOM_PER_SWEEP = 2 };
+enum { HPS_MG2_TILE_SINGLE_BLOCK = 0, HPS_MG2_TILE_SMALL = 1, HPS_MG2_TILE_BIG = 2 };
+int hps_mg2_info (void* handle, int* nlev, int* low_top, int* bottom, int* tiles);
 int hps_mg2_destroy (void* handle);
 
 /* ---- slice engine (Hipace::Evolve / SolveOneSlice, explicit solver; Hipace.cpp:393-728) -- */

@@ -148,6 +148,70 @@ def test_poisson_dispatch_lists_mirror_the_source_tables():
     assert tri == TRI_ROWS
 
 
+@pytest.mark.parametrize("nx,ny,dx,dy", [(64, 64, 0.25, 0.25), (96, 48, 0.4, 0.1), (132, 66, 0.1, 0.1), (4, 64, 0.1, 0.4),
+                                         (63, 63, 0.25, 0.25), (31, 63, 0.1, 0.4), (129, 129, 0.1, 0.1), (7, 15, 0.4, 0.1)])
+def test_numpy_helmholtz1_matches_the_oracle_multigrid(oracle, nx, ny, dx, dy):
+    """The references of tests/test_multigrid_dispatch_gpu.py against the oracle's hpmg solve run to 1e-8, both centrings,
+    anisotropic cells: the numpy residual of the oracle's solution is the resnorm it reports, and the solution is the sparse
+    direct one within ||A^-1|| ||r||; GSRB^4 of a solution near convergence moves it by no more than that bound either."""
+    from tests.util import helmholtz1_direct, helmholtz1_gsrb4, helmholtz1_residual
+    g = G2
+    rng = np.random.default_rng(nx * 7 + ny)
+    rhs = np.zeros((2, ny + 2 * g, nx + 2 * g))
+    rhs[:, g:-g, g:-g] = rng.standard_normal((2, ny, nx))
+    acf = 0.5 + rng.random((ny + 2 * g, nx + 2 * g))
+    sol = np.zeros_like(rhs)
+    it, rn = oracle.mg_solve1(sol, rhs, acf, nx, ny, g, dx, dy, tol_rel=1e-8)
+    assert it >= 1
+    cc = nx % 2 == 0
+    S, R, A = sol[:, g:-g, g:-g], rhs[:, g:-g, g:-g], acf[g:-g, g:-g]
+    r = np.abs(helmholtz1_residual(S, R, A, dx, dy, cc)).max()
+    rounding = 64 * np.finfo(float).eps * (4 / dx ** 2 + 4 / dy ** 2 + A.max()) * np.abs(S).max()      # of one residual
+    assert abs(r - rn) <= 1e-6 * rn + rounding and rn <= 1e-8 * np.abs(R).max()
+    exact, ainv = helmholtz1_direct(R, A, dx, dy, cc)
+    assert ainv <= 1 / A.min() * (1 + 1e-12)
+    assert np.abs(S - exact).max() <= ainv * r * (1 + 1e-9) + 1e-14 * np.abs(exact).max()
+    S4 = helmholtz1_gsrb4(S, R, A, dx, dy, cc)
+    r4 = np.abs(helmholtz1_residual(S4, R, A, dx, dy, cc)).max()
+    assert np.abs(S4 - exact).max() <= ainv * r4 * (1 + 1e-9) + 1e-14 * np.abs(exact).max()
+
+
+def test_multigrid_dispatch_lists_mirror_the_source():
+    """LOWV / TILES / the thresholds of tests/test_multigrid_dispatch_gpu.py are what multigrid.hip and multigrid2.hip launch and
+    decide by, and what the C ABI and api.py name: a kernel or threshold changed there without the tests fails here (the GPU
+    module's completeness test checks that the grids reach every entry)."""
+    from hipace_amd import api as A
+    from tests import test_multigrid_dispatch_gpu as T
+    src = open(os.path.join(ROOT, "hipace_amd", "csrc", "multigrid.hip")).read()
+    src2 = open(os.path.join(ROOT, "hipace_amd", "csrc", "multigrid2.hip")).read()
+    hdr = open(os.path.join(ROOT, "include", "hpslice.h")).read()
+    def const(text, name):
+        return eval(re.search(r"\b" + name + r"\s*=\s*([0-9L* ]+)[;,]", text).group(1).replace("L", ""))
+    assert const(src, "LOWV_MAX_CELLS") == T.LOWV_MAX_CELLS
+    assert const(src, "SMALL_TILE_CELLS") == T.SMALL_TILE_CELLS
+    assert const(src, "NPYR_MAX") == T.NPYR_MAX
+    assert const(src2, "LOW2_MAX_CELLS") == T.LOW2_MAX_CELLS
+    assert const(src2, "BIG_TILE_CELLS") == T.BIG_TILE_CELLS
+    # the lower-V kernels vcycle launches, one per kind
+    vc = re.search(r"static void vcycle \(.*?\n\}", src, re.S).group(0)
+    launched = set(re.findall(r"hipLaunchKernelGGL\((k_\w+(?:<\w+>)?)", vc))
+    assert launched == {"k_bottom_sweep<CC>", "k_lower_v3", "k_lower_v<CC>"}, launched
+    assert len(T.LOWV) == 4 and A.MultiGrid.LOWV == T.LOWV
+    assert re.findall(r"HPS_MG_LOWV_(\w+) = (\d)", hdr) == [("V3", "0"), ("CC", "1"), ("NODAL", "2"), ("BOTTOM", "3")]
+    # the smoother tiles of the down-leg: launch_smooth's two, the pulling TileSmall / TileMid of node-centred levels
+    assert set(re.findall(r"launch_smooth_ts<(Tile\w+), CC, SRC_ZERO, true, 4, true>", vc)) == {"TileSmall", "TileMid"}
+    ls = re.search(r"static void launch_smooth \(.*?\n\}", src, re.S).group(0)
+    assert set(re.findall(r"launch_smooth_ts<(Tile\w+)", ls)) == {"TileSmall", "TileBig"}
+    assert A.MultiGrid.TILES == T.TILES == ("TileSmall", "TileBig", "TileSmall-pull", "TileMid-pull")
+    # every depth of the nodal pyramid kernel
+    hier = re.search(r"static int solve1_hierarchy \(.*?\n\}", src, re.S).group(0)
+    assert sorted(set(int(k) for k in re.findall(r"k_nodal_acf_pyramid<(\d)>", hier))) == list(range(1, T.NPYR_MAX + 1))
+    # multigrid2.hip: its bottoms and tiles
+    assert set(T.MG2_BOTTOMS) | {"single-block"} == set(A.MultiGrid2.BOTTOMS)
+    assert A.MultiGrid2.TILES == T.MG2_TILES
+    assert set(re.findall(r"k2_smooth_tile<(\d+), (\d+), \d+>", src2)) == {("64", "32"), ("32", "16")}
+
+
 @pytest.mark.parametrize("n", [32, 63])
 def test_oracle_multigrid_residual_and_iteration_count(oracle, n):
     """hpmg converges ~50x per V-cycle: 3 V-cycles to 1e-4 from a zero guess (measured

@@ -80,3 +80,83 @@ def poisson_dirichlet_ref(rhs, dx, dy):
     eig = -4.0 * sx[None, :] / dx ** 2 - 4.0 * sy[:, None] / dy ** 2
     u = dst1(dst1(rhs, axis=1), axis=0) / eig
     return dst1(dst1(u, axis=1), axis=0) / (4.0 * (nx + 1) * (ny + 1))
+
+
+# hpmg system type 1 (mg_solver/HpMultiGrid.cpp), restated in float64 numpy on the solve's own grid, independent of the oracle:
+# -acf phi + Lap(phi) = rhs with homogeneous Dirichlet walls.  Cell-centred (even nx, ny): every cell is an unknown and a cell
+# next to the wall takes the 4/3 stencil (laplacian :162-182, gs1 :265-292: the ghost value -2 phi_0 + phi_1 / 3).  Node-centred
+# (odd nx, ny): the nx x ny user cells are the unknowns and the wall nodes one cell outside hold 0.  Arrays are (..., ny, nx).
+WALL = 4.0 / 3.0
+
+
+def _stencil_parts(phi, cc, facx, facy):
+    """(off-diagonal part of Lap phi, diagonal factor of Lap at each cell without acf)."""
+    p = np.asarray(phi, dtype=np.float64)
+    pad = np.zeros(p.shape[:-2] + (p.shape[-2] + 2, p.shape[-1] + 2))
+    pad[..., 1:-1, 1:-1] = p
+    w, e = pad[..., 1:-1, :-2], pad[..., 1:-1, 2:]
+    s, n = pad[..., :-2, 1:-1], pad[..., 2:, 1:-1]
+    ny, nx = p.shape[-2:]
+    lx, ly = facx * (w + e), facy * (s + n)
+    dxx = np.full(nx, -2.0 * facx)
+    dyy = np.full(ny, -2.0 * facy)
+    if cc:
+        lx[..., :, 0] = facx * WALL * e[..., :, 0]
+        lx[..., :, -1] = facx * WALL * w[..., :, -1]
+        ly[..., 0, :] = facy * WALL * n[..., 0, :]
+        ly[..., -1, :] = facy * WALL * s[..., -1, :]
+        dxx[[0, -1]] = -4.0 * facx
+        dyy[[0, -1]] = -4.0 * facy
+    return lx + ly, dxx[None, :] + dyy[:, None]
+
+
+def helmholtz1_residual(sol, rhs, acf, dx, dy, cc):
+    """rhs + acf phi - Lap(phi) (residual1 :184-190) at every unknown."""
+    off, dlap = _stencil_parts(sol, cc, 1.0 / dx ** 2, 1.0 / dy ** 2)
+    return rhs + acf * sol - (off + dlap * sol)
+
+
+def helmholtz1_gsrb4(sol, rhs, acf, dx, dy, cc):
+    """The four red-black half-sweeps (colour (i + j + c) % 2 == 0, c = 0..3) that solve_doit applies after each V-cycle; the
+    parity is the same in user and in level index space.  Points of one colour do not read each other: one vector update each."""
+    phi = np.array(sol, dtype=np.float64)
+    ny, nx = phi.shape[-2:]
+    jj, ii = np.meshgrid(np.arange(ny), np.arange(nx), indexing="ij")
+    diag = None
+    for c in range(4):
+        off, dlap = _stencil_parts(phi, cc, 1.0 / dx ** 2, 1.0 / dy ** 2)
+        if diag is None:
+            diag = dlap - acf
+        m = (ii + jj + c) % 2 == 0
+        phi = np.where(m, (rhs - off) / diag, phi)
+    return phi
+
+
+def helmholtz1_matrix(acf, dx, dy, cc):
+    """A = acf - Lap as a scipy.sparse matrix on the (ny, nx) unknowns, row-major: A phi = -rhs is the equation solved."""
+    import scipy.sparse as sp
+    ny, nx = acf.shape
+    fx, fy = 1.0 / dx ** 2, 1.0 / dy ** 2
+    def lap1(n, f):
+        d = np.full(n, -2.0 * f)
+        up = np.full(n - 1, f)
+        lo = np.full(n - 1, f)
+        if cc:
+            d[[0, -1]] = -4.0 * f
+            up[0] = WALL * f
+            lo[-1] = WALL * f
+        return sp.diags([lo, d, up], [-1, 0, 1], format="csr")
+    lap = sp.kron(sp.identity(ny), lap1(nx, fx)) + sp.kron(lap1(ny, fy), sp.identity(nx))
+    return (sp.diags(np.asarray(acf, dtype=np.float64).ravel()) - lap).tocsc()
+
+
+def helmholtz1_direct(rhs, acf, dx, dy, cc):
+    """(phi, ||A^-1||_inf): the exact solution of -acf phi + Lap(phi) = rhs by a sparse direct solve, for each leading plane of
+    rhs, and the inverse's norm.  A = acf - Lap with acf >= 0 is a weakly diagonally dominant M-matrix, so A^-1 >= 0 entrywise
+    and ||A^-1||_inf = ||A^-1 1||_inf: then ||x - phi||_inf <= ||A^-1||_inf ||r(x)||_inf for any x."""
+    import scipy.sparse.linalg as spl
+    ny, nx = acf.shape
+    lu = spl.splu(helmholtz1_matrix(acf, dx, dy, cc))
+    r = np.asarray(rhs, dtype=np.float64).reshape(-1, ny * nx)
+    phi = np.stack([lu.solve(-b) for b in r]).reshape(np.shape(rhs))
+    return phi, float(np.abs(lu.solve(np.ones(ny * nx))).max())
