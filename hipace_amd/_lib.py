@@ -68,7 +68,12 @@ class Deck(C.Structure):
                 ("plasma_no_neutralize", C.c_int), ("ion_on", C.c_int), ("ion_ppc", C.c_int * 2), ("ion_density", C.c_double),
                 ("ion_mass", C.c_double), ("ion_charge", C.c_double), ("ion_init_level", C.c_int), ("ion_Z", C.c_int),
                 ("ion_energies", C.c_double * 56), ("ion_seed", C.c_ulonglong),
-                ("beam_spin_tracking", C.c_int), ("beam_initial_spin", C.c_double * 3), ("beam_spin_anom", C.c_double)]
+                ("beam_spin_tracking", C.c_int), ("beam_initial_spin", C.c_double * 3), ("beam_spin_anom", C.c_double),
+                ("dt_adaptive", C.c_int), ("nt_per_betatron", C.c_double), ("dt_max", C.c_double),
+                ("adaptive_threshold_uz", C.c_double), ("adaptive_phase_tolerance", C.c_double),
+                ("adaptive_no_predict_step", C.c_int), ("adaptive_no_phase_control", C.c_int), ("adaptive_phase_substeps", C.c_int),
+                ("adaptive_density", C.c_double), ("max_time", C.c_double), ("beam_uz_std", C.c_double),
+                ("ext_Ez_slope", C.c_double)]
 
 
 # engine component names, index = value of the HPS_C_* enum in include/hpslice.h
@@ -156,6 +161,15 @@ _SIGS = {
     "hps_engine_set_profiling_stride": (C.c_int, [C.c_void_p, C.c_int]),
     "hps_engine_set_laser_import": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hps_engine_set_step": (C.c_int, [C.c_void_p, C.c_int]),
+    "hps_engine_set_time": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "hps_engine_beam_moments": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hps_adaptive_create": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "hps_adaptive_set_density_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "hps_adaptive_initial_dt": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_double)]),
+    "hps_adaptive_before_step": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
+    "hps_adaptive_next_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "hps_adaptive_after_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_double)]),
+    "hps_adaptive_destroy": (C.c_int, [C.c_void_p]),
     "hps_engine_export_laser_slice": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "hps_engine_import_laser_slice": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "hps_engine_import_laser_from": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),

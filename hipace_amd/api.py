@@ -320,11 +320,70 @@ class MultiGrid:
             self._h = None
 
 
+class AdaptiveTimeStep:
+    """hipace.dt = adaptive: the reference's controller (utils/AdaptiveTimeStep.cpp) over hps_adaptive_* -- host code, no
+    device.  One per rank / pipeline stage, all initialised alike."""
+
+    def __init__(self, deck, density_profile=None):
+        self.deck = dict(deck)
+        self._dk = _lib.fill_struct(_lib.Deck(), deck)
+        self._h = C.c_void_p()
+        check(_lib.lib().hps_adaptive_create(C.byref(self._dk), C.byref(self._h)))
+        if density_profile is not None:
+            self.set_density_profile(*density_profile)
+
+    @classmethod
+    def for_engine(cls, engine):
+        """a controller for `engine`'s deck and density profile"""
+        return cls(engine.deck, getattr(engine, "density_profile", None))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.lib().hps_adaptive_destroy(self._h)
+            self._h = None
+
+    def set_density_profile(self, r=(), fr=(), ct=(), ft=()):
+        a = [np.ascontiguousarray(v, dtype=np.float64) for v in (r, fr, ct, ft)]
+        assert len(a[0]) == len(a[1]) and len(a[2]) == len(a[3])
+        p = [x.ctypes.data_as(C.c_void_p) if len(x) else None for x in a]
+        check(_lib.lib().hps_adaptive_set_density_profile(self._h, len(a[0]), p[0], p[1], len(a[2]), p[2], p[3]))
+
+    def initial_dt(self, uz_mean=None, uz_std=None, nstages=1):
+        """the head rank's GatherMinUzSlice(beams, true) + CalculateFromMinUz + CalculateFromDensity (Hipace.cpp:275-279);
+        default: the deck's u_mean[2] and beam_uz_std.  -> dt"""
+        um = self.deck["beam_umean"][2] if uz_mean is None else uz_mean
+        us = self.deck.get("beam_uz_std", 0.0) if uz_std is None else uz_std
+        dt = C.c_double()
+        check(_lib.lib().hps_adaptive_initial_dt(self._h, float(um), float(us), int(nstages), C.byref(dt)))
+        return dt.value
+
+    def CalculateFromDensity(self, t):
+        """start of the step at time t: phase-advance control, then hipace.max_time (Hipace.cpp:420-435).  -> its dt"""
+        dt = C.c_double()
+        check(_lib.lib().hps_adaptive_before_step(self._h, float(t), C.byref(dt)))
+        return dt.value
+
+    def next_time(self):
+        """time of the step after the one CalculateFromDensity began (MultiBuffer::put_time; inf: no further step)"""
+        t = C.c_double()
+        check(_lib.lib().hps_adaptive_next_time(self._h, C.byref(t)))
+        return t.value
+
+    def CalculateFromMinUz(self, moments, t, nstages=1):
+        """end of the step that started at t, from its moments (SliceEngine.beam_moments).  -> this controller's next dt"""
+        m = np.ascontiguousarray(moments, dtype=np.float64)
+        assert m.shape == (4,)
+        dt = C.c_double()
+        check(_lib.lib().hps_adaptive_after_step(self._h, m.ctypes.data_as(C.c_void_p), float(t), int(nstages), C.byref(dt)))
+        return dt.value
+
+
 class SliceEngine:
     """Device-resident slice loop for one deck (see hipace_amd/decks.py)."""
 
     def __init__(self, deck, device=0, tile_size=None, sort_period=None):
         self.deck = dict(deck)
+        self.step_times = []            # hipace.dt = adaptive in a pipeline: (step, t, dt) of every step this engine began
         self._dk = _lib.fill_struct(_lib.Deck(), deck)
         self._h = C.c_void_p()
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
@@ -368,7 +427,45 @@ class SliceEngine:
     # ---- ring hand-off of a moving beam (hipace.dt != 0) ------------------------------------------
     @property
     def moving(self):
-        return float(self.deck.get("dt", 0.0)) != 0.0
+        return float(self.deck.get("dt", 0.0)) != 0.0 or self.adaptive
+
+    @property
+    def adaptive(self):
+        """hipace.dt = adaptive: every step's time and dt come from the host (set_time, AdaptiveTimeStep)"""
+        return bool(self.deck.get("dt_adaptive", 0))
+
+    def set_time(self, t, dt):
+        """physical time and dt of the step the next begin_step starts (hps_engine_set_time)"""
+        check(_lib.lib().hps_engine_set_time(self._h, float(t), float(dt)))
+
+    def beam_moments(self):
+        """{sum w, sum w uz/c, sum w (uz/c)^2, min uz/c} of the step last solved, as a float64 array (synchronises)"""
+        out = np.zeros(4, dtype=np.float64)
+        check(_lib.lib().hps_engine_beam_moments(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def run_adaptive(self, n_steps=None, controller=None, on_step_end=None):
+        """hipace.dt = adaptive on this one engine (Hipace::Evolve with one rank, Hipace.cpp:400-490): the head rank's
+        initial dt, then per step CalculateFromDensity + max_time, the step at (t, dt), CalculateFromMinUz on its moments.
+        Runs n_steps (default: the deck's) or stops where hipace.max_time drops the rest; on_step_end(step, t, dt) after each.
+        Returns [(step, t, dt)] of the steps started -- the reference's "started step ... at time = ... with dt = ..." lines."""
+        assert self.adaptive, "run_adaptive needs a deck with dt_adaptive"
+        n = self.deck["n_steps"] if n_steps is None else int(n_steps)
+        ats = controller or AdaptiveTimeStep.for_engine(self)
+        ats.initial_dt(nstages=1)
+        t, log = 0.0, []
+        for step in range(n):
+            if t == float("inf"):
+                break
+            dt = ats.CalculateFromDensity(t)
+            log.append((step, t, dt))
+            self.set_time(t, dt)
+            self.run_step()
+            ats.CalculateFromMinUz(self.beam_moments(), t, 1)
+            if on_step_end is not None:
+                on_step_end(step, t, dt)
+            t = ats.next_time()
+        return log
 
     def beam_capacity(self):
         n = C.c_long()
@@ -414,6 +511,7 @@ class SliceEngine:
 
     def set_density_profile(self, r=(), fr=(), ct=(), ft=()):
         """n(x, y, ct) = density * f_r(r) * f_t(c t): piecewise-linear tables (hps_engine_set_density_profile)."""
+        self.density_profile = (r, fr, ct, ft)
         a = [np.ascontiguousarray(v, dtype=np.float64) for v in (r, fr, ct, ft)]
         assert len(a[0]) == len(a[1]) and len(a[2]) == len(a[3])
         p = [x.ctypes.data_as(C.c_void_p) if len(x) else None for x in a]

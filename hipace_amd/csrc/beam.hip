@@ -19,7 +19,7 @@ namespace hps {
 struct BeamPushConsts {
     double dt;                 // per sub-cycle
     double c, inv_c2, qm, min_z;
-    double ex_slope, ey_slope; // beams.external_E = (ex_slope*x, ey_slope*y, 0)
+    double ex_slope, ey_slope, ez_slope; // beams.external_E = (ex_slope*x, ey_slope*y, ez_slope*z)
     int nsc;
     PartConsts pc;             // geometry, boundary
     // radiation reaction (BeamParticleAdvance.cpp:101-113, 244-297): rr != 0 switches it on
@@ -101,9 +101,10 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
                 Bz += ss*q[cBz*f.ns];
             }
         }
-        // ApplyExternalField (particles/pusher/ExternalFields.H:29-56), E = (ex_slope x, ey_slope y, 0), B = 0
+        // ApplyExternalField (particles/pusher/ExternalFields.H:29-56), E = (ex_slope x, ey_slope y, ez_slope z), B = 0
         ExmBy += k.ex_slope*xp;
         EypBx += k.ey_slope*yp;
+        if (k.ez_slope != 0.0) Ez += k.ez_slope*zp;
         double ux_next = ux + k.dt*k.qm*(ExmBy + (k.c - uz*gi)*By + uy*gi*Bz);
         double uy_next = uy + k.dt*k.qm*(EypBx + (uz*gi - k.c)*Bx - ux*gi*Bz);
         const double ux_i = (ux_next + ux)*0.5, uy_i = (uy_next + uy)*0.5;
@@ -161,19 +162,44 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
 
 // One workgroup: particles of slice p with z < min_z go to the end of the slice's range, the boundary to
 // slice p+1 is lowered past them.  Nothing moves when nothing slipped (the usual case).
+// MOM (hipace.dt = adaptive): the first pass also reduces {sum w, sum w uz/c, sum w (uz/c)^2, min uz/c} over the particles
+// that stay (z >= min_z) and are not absorbed -- GatherMinUzSlice behind shiftSlippedParticles (Hipace.cpp:703-716) -- into
+// mom[0..3], the slot of slice p.  Lane t takes particles t, t + 1024, ... in order, the waves fold by a fixed butterfly and
+// lane 0 of the workgroup adds the 16 waves in order: the result depends on the particles' order only, not on timing.
+template <bool MOM>
 __global__ __launch_bounds__(1024)
-void k_beam_partition (BeamSoA b, BeamSoA scr, long* B, int* nfront, int p, double min_z)
+void k_beam_partition (BeamSoA b, BeamSoA scr, long* B, int* nfront, int p, double min_z, double inv_c, double* mom)
 {
     __shared__ int s_cnt[2];
     __shared__ int s_red[16];
+    __shared__ double s_mom[MOM ? 16 : 1][4];
     const long first = B[p], count = B[p + 1] - first;
     const int t = threadIdx.x;
     int mine = 0;
-    for (long q = t; q < count; q += 1024) mine += (b.z[first + q] < min_z) ? 1 : 0;
+    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = __builtin_huge_val();
+    for (long q = t; q < count; q += 1024) {
+        const double z = b.z[first + q];
+        mine += (z < min_z) ? 1 : 0;
+        if (MOM && z >= min_z && b.nsub[first + q] >= 0) {
+            const double w = b.w[first + q], u = b.uz[first + q]*inv_c;
+            m0 += w; m1 += w*u; m2 += w*u*u; m3 = fmin(m3, u);
+        }
+    }
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+    if (MOM) {
+        for (int o = 32; o > 0; o >>= 1) {
+            m0 += __shfl_xor(m0, o); m1 += __shfl_xor(m1, o); m2 += __shfl_xor(m2, o); m3 = fmin(m3, __shfl_xor(m3, o));
+        }
+        if ((t & 63) == 0) { s_mom[t >> 6][0] = m0; s_mom[t >> 6][1] = m1; s_mom[t >> 6][2] = m2; s_mom[t >> 6][3] = m3; }
+    }
     if ((t & 63) == 0) s_red[t >> 6] = mine;
     if (t < 2) s_cnt[t] = 0;
     __syncthreads();
+    if (MOM && t == 0) {
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = __builtin_huge_val();
+        for (int w = 0; w < 16; ++w) { a0 += s_mom[w][0]; a1 += s_mom[w][1]; a2 += s_mom[w][2]; a3 = fmin(a3, s_mom[w][3]); }
+        mom[0] = a0; mom[1] = a1; mom[2] = a2; mom[3] = a3;
+    }
     int nslip = 0;
     for (int w = 0; w < 16; ++w) nslip += s_red[w];
     if (nslip == 0) { if (t == 0) nfront[p + 1] = 0; return; }
@@ -194,6 +220,21 @@ void k_beam_partition (BeamSoA b, BeamSoA scr, long* B, int* nfront, int p, doub
         if (b.sx) { b.sx[ip] = scr.sx[q]; b.sy[ip] = scr.sy[q]; b.sz[ip] = scr.sz[q]; }
     }
     if (t == 0) { B[p + 1] = first + count - nslip; nfront[p + 1] = nslip; }
+}
+
+// mom[nz + 1][4]: one slot per slice (head first) and the step's total behind them; an empty slice keeps {0, 0, 0, +inf}
+__global__ void k_beam_moments_reset (double* mom, int nz)
+{
+    for (int i = threadIdx.x; i < 4*(nz + 1); i += blockDim.x) mom[i] = (i & 3) == 3 ? __builtin_huge_val() : 0.0;
+}
+// the step's total: the nz slots folded head to tail, one lane per moment (a fixed order: no atomics on doubles)
+__global__ void k_beam_moments_fold (double* mom, int nz)
+{
+    const int k = threadIdx.x;
+    if (k >= 4) return;
+    double a = mom[k];
+    for (int p = 1; p < nz; ++p) a = (k == 3) ? fmin(a, mom[4*p + k]) : a + mom[4*p + k];
+    mom[4*nz + k] = a;
 }
 
 // ---- ring hand-off (MultiBuffer::put_data / get_data, utils/MultiBuffer.cpp:444-609) ----------------------------
@@ -260,11 +301,11 @@ static BeamPushConsts push_consts (const Engine& E, int islice)
     BeamPushConsts k{};
     const hps_deck& d = E.d;
     k.nsc = d.beam_n_subcycles > 0 ? d.beam_n_subcycles : 10;
-    k.dt = d.dt/k.nsc;
+    k.dt = E.step_dt/k.nsc;
     k.c = E.gm.c; k.inv_c2 = 1.0/(E.gm.c*E.gm.c);
     k.qm = d.beam_charge/(d.beam_mass != 0.0 ? d.beam_mass : 1.0);
     k.min_z = d.lo[2] + islice*E.gm.dz;
-    k.ex_slope = d.ext_E_slope[0]; k.ey_slope = d.ext_E_slope[1];
+    k.ex_slope = d.ext_E_slope[0]; k.ey_slope = d.ext_E_slope[1]; k.ez_slope = d.ext_Ez_slope;
     k.pc = base_consts(E.gm);
     // radiation reaction constants (:101-113), PhysConstSI of utils/Constants.H:15-24
     const double cSI = 299792458.0, qeSI = 1.602176634e-19, meSI = 9.1093837015e-31, ep0SI = 8.8541878128e-12, reSI = 2.817940326204929e-15;
@@ -295,11 +336,25 @@ int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz)
     return HPS_OK;
 }
 
+int beam_moments_reset (Engine& E)
+{
+    hipLaunchKernelGGL(k_beam_moments_reset, dim3(1), dim3(256), 0, E.st, E.d_mom, E.d.nz);
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
 int beam_push_moving (Engine& E, int islice)
 {
     const int p = E.d.nz - 1 - islice;
     const long bound = E.beam_bound(p);
-    if (bound <= 0) return HPS_OK;
+    if (bound > 0) { if (int e = beam_push_slice(E, islice, p, bound)) return e; }
+    if (E.d_mom && islice == 0) hipLaunchKernelGGL(k_beam_moments_fold, dim3(1), dim3(64), 0, E.st, E.d_mom, E.d.nz);      // the step's last slice
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
+int beam_push_slice (Engine& E, int islice, int p, long bound)
+{
     const SlabView f(E.slab);
     const BeamPushConsts k = push_consts(E, islice);
     const dim3 grid((unsigned)std::min<long>(ceil_div(bound, 256), 2048)), block(256);
@@ -309,7 +364,10 @@ int beam_push_moving (Engine& E, int islice)
 #define CALL(O) hipLaunchKernelGGL(k_beam_push<O>, grid, block, 0, E.st, f, E.bm, E.d_B, p, cP, cE, cX, cY, cZ, k)
     HPS_BEAM_ORDER(E.d.order, CALL)
 #undef CALL
-    hipLaunchKernelGGL(k_beam_partition, dim3(1), dim3(1024), 0, E.st, E.bm, E.bm_scr, E.d_B, E.d_nfront, p, k.min_z);
+    if (E.d_mom)
+        hipLaunchKernelGGL(k_beam_partition<true>, dim3(1), dim3(1024), 0, E.st, E.bm, E.bm_scr, E.d_B, E.d_nfront, p, k.min_z, 1.0/k.c, E.d_mom + 4*p);
+    else
+        hipLaunchKernelGGL(k_beam_partition<false>, dim3(1), dim3(1024), 0, E.st, E.bm, E.bm_scr, E.d_B, E.d_nfront, p, k.min_z, 1.0/k.c, nullptr);
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }

@@ -22,6 +22,18 @@ void set_error (const std::string& msg);
         }                                                                                \
     } while (0)
 
+// piecewise-linear table, constant beyond its ends; n = 0: the factor is 1 (density profiles: engine.hip, adaptive.hip)
+__host__ __device__ inline double table_value (const double* x, const double* f, int n, double v)
+{
+    if (n <= 0) return 1.0;
+    if (v <= x[0]) return f[0];
+    if (v >= x[n - 1]) return f[n - 1];
+    int k = 1;
+    while (x[k] < v) ++k;
+    const double t = (v - x[k - 1])/(x[k] - x[k - 1]);
+    return f[k - 1] + t*(f[k] - f[k - 1]);
+}
+
 #define HPS_REQUIRE(cond, msg)                                                           \
     do { if (!(cond)) { hps::set_error(msg); return HPS_ERR_ARG; } } while (0)
 

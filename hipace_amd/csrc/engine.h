@@ -70,6 +70,11 @@ struct Engine {
     bool gate_push = true;                      // push enqueued behind the multigrid's V-cycles, gated on its stopping rule (HPS_GATED_PUSH=0: off)
     int step_index = -1;           // physical time step that has begun (density profile's time factor, ionisation draws)
     int next_step = -1;            // hps_engine_set_step: the step the next begin_step starts (-1: the one after step_index)
+    // hps_engine_set_time (hipace.dt = adaptive): time and dt of the step the next begin_step starts; step_dt is what the
+    // beam push of the step that has begun uses (the deck's dt unless set)
+    bool time_set = false; double next_t = 0.0, next_dt = 0.0, step_dt = 0.0;
+    bool host_beam = false;        // hps_engine_set_beam_particles has given the beam
+    double* d_mom = nullptr;       // hipace.dt = adaptive: beam moments [nz + 1][4] (beam.hip: k_beam_partition<true>)
     IonArgs ion_args (int islice);             // ionization.hip: kernel arguments of this slice's ionisation
     int ionize_slice (int islice);             // ...: launch of the per-particle form
     int ionize_collect ();                     // ...: wait for the electron count of the slice
@@ -203,6 +208,8 @@ int laser_import_slice (Engine& E, int islice, const double* msg_dev);
 int laser_import_from (Engine& E, int islice, Engine& src);
 int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz);      // beam.hip
 int beam_push_moving (Engine& E, int islice);
+int beam_push_slice (Engine& E, int islice, int p, long bound);
+int beam_moments_reset (Engine& E);
 int beam_export_slice (Engine& E, int islice, double* msg_dev, long cap);
 int beam_import_slice (Engine& E, int islice, const double* msg_dev, long cap);
 

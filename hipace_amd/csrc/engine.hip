@@ -251,18 +251,6 @@ void k_checksum (SlabView f, int ncomp, double* acc)
     (void)ncomp;
 }
 
-// piecewise-linear table, constant beyond its ends; n = 0: the factor is 1
-__host__ __device__ inline double table_value (const double* x, const double* f, int n, double v)
-{
-    if (n <= 0) return 1.0;
-    if (v <= x[0]) return f[0];
-    if (v >= x[n - 1]) return f[n - 1];
-    int k = 1;
-    while (x[k] < v) ++k;
-    const double t = (v - x[k - 1])/(x[k] - x[k - 1]);
-    return f[k - 1] + t*(f[k] - f[k - 1]);
-}
-
 // weight = density(x, y, c t) * scale_fac (PlasmaParticleContainerInit.cpp:246-313) with the tabulated profile
 // density * f_r(r) * f_t: prof = [r[nr] | f_r[nr]] on the device, ft the time factor of this step; a lattice point
 // whose density is <= 0 holds no particle (the reference does not create it: here its slot is invalid)
@@ -355,6 +343,7 @@ Engine::~Engine ()
     (void)hipFree(pl_real_alt); (void)hipFree(pl_alt.idcpu); (void)hipFree(pl_alt.ion_lev); 
     (void)hipFree(staging); (void)hipFree(d_open_mom); (void)hipFree(beam_data); (void)hipFree(beam_init);
     (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr); (void)hipFree(d_B); (void)hipFree(d_nfront);
+    (void)hipFree(d_mom);
     (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow); (void)hipFree(d_nqsa); (void)hipFree(d_checksum);
     (void)hipFree(d_pc); (void)hipFree(d_pc_aux); (void)hipFree(d_pc_go); if (h_pc) (void)hipHostFree(h_pc);
     (void)hipFree(d_laser_sum);
@@ -451,6 +440,7 @@ int Engine::set_beam_particles (long n, const double* soa, long* n_outside)
         const long j = next[(size_t)p]++;
         for (int k = 0; k < 7; ++k) h[k][(size_t)j] = soa[(size_t)k*n + i];
     }
+    host_beam = true;
     HPS_HIP_CHECK(hipStreamSynchronize(st));
     (void)hipFree(beam_data); (void)hipFree(beam_init); (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr);
     (void)hipFree(d_B); (void)hipFree(d_nfront); (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow);
@@ -494,7 +484,7 @@ int Engine::install_beam (std::vector<double> (&h)[7])
         HPS_HIP_CHECK(hipMemcpy(beam_data, beam_init, 7*nbeam*sizeof(double), hipMemcpyDeviceToDevice));
         beam_cur = beam_data;
     }
-    moving = (d.dt != 0.0);
+    moving = (d.dt != 0.0 || d.dt_adaptive);
     if (moving) {
         // global SoA in head-first order + device boundaries (beam.hip)
         const long nb = std::max(nbeam, 1L);
@@ -534,6 +524,10 @@ int Engine::install_beam (std::vector<double> (&h)[7])
         for (int p = 0; p < d.nz; ++p) mx = std::max(mx, beam_off[p + 1] - beam_off[p]);
         beam_cap = std::max(2*mx, 1L);                 // particles a slice may hold in a hand-off message
         if (nbeam > 0) beam_box = beam_box_init = full_box;          // a moving beam may go anywhere (no beam at all, e.g. a laser driver: the box stays empty)
+        if (d.dt_adaptive && !d_mom) {
+            HPS_HIP_CHECK(hipMalloc(&d_mom, (size_t)4*(d.nz + 1)*sizeof(double)));
+            if (int e = beam_moments_reset(*this)) return e;
+        }
     }
     return HPS_OK;
 }
@@ -678,7 +672,9 @@ int Engine::create (const hps_deck& deck, int device)
     if (const char* v = std::getenv("HPS_LAZY_SHIFT")) lazy_shift = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_FUSE_SOURCES")) fuse_sources = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_SORT_FALLBACK_DIV")) { const long q = std::atol(v); if (q >= 1) fallback_div = q; }
-    HPS_REQUIRE(!(d.beam_spin_tracking && d.dt == 0.0), "hps_engine_create: spin tracking needs a moving beam (hipace.dt != 0)");
+    HPS_REQUIRE(!(d.beam_spin_tracking && d.dt == 0.0 && !d.dt_adaptive), "hps_engine_create: spin tracking needs a moving beam (hipace.dt != 0)");
+    HPS_REQUIRE(!(d.dt_adaptive && d.laser_on), "hps_engine_create: hipace.dt = adaptive cannot be used with a laser (Hipace.cpp:408)");
+    step_dt = d.dt;
     if (d.predcorr_tol > 0.0) pc_tol = d.predcorr_tol;
     if (d.predcorr_max_iter > 0) pc_max_iter = d.predcorr_max_iter;
     if (d.predcorr_mix > 0.0) pc_mix = d.predcorr_mix;
@@ -857,6 +853,8 @@ int Engine::resort ()
 
 int Engine::begin_step ()
 {
+    HPS_REQUIRE(!(d.dt_adaptive && steps_begun == 0 && d.beam_profile < 0 && !host_beam),
+                "hps_engine_begin_step: hipace.dt = adaptive needs a beam (beam_profile = -1 and no hps_engine_set_beam_particles: the sum of weights is 0)");
     if (int e = setup_tiling()) return e;
     if (moving && steps_begun > 0) {
         // a slice that outgrew the hand-off capacity during the previous step lost particles: refuse to go on
@@ -901,8 +899,16 @@ int Engine::begin_step ()
     step_index = (next_step >= 0) ? next_step : step_index + 1;      // Hipace::m_physical_time (PlasmaParticleContainerInit.cpp:90)
     next_step = -1;
     ahead_for = -2;
+    if (d_mom) { if (int e = beam_moments_reset(*this)) return e; }
     // time factor of the density profile at z = c t of this step (UpdateDensityFunction, PlasmaParticleContainer.cpp:211-217)
-    prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*d.dt*step_index);
+    if (time_set) {          // hps_engine_set_time
+        step_dt = next_dt;
+        prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*next_t);
+        time_set = false;
+    } else {
+        step_dt = d.dt;
+        prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*d.dt*step_index);
+    }
     if (int e = ionize_collect()) return e;
     np = np_init; pl.n = np; pl_alt.n = np;
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : std::numeric_limits<double>::infinity();
@@ -2318,6 +2324,22 @@ extern "C" int hps_engine_set_step (void* h, int step)
     Engine* E = static_cast<Engine*>(h);
     HPS_REQUIRE(E && step >= 0, "hps_engine_set_step: bad argument");
     E->next_step = step;
+    return HPS_OK;
+}
+extern "C" int hps_engine_set_time (void* h, double t, double dt)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && std::isfinite(t) && std::isfinite(dt), "hps_engine_set_time: bad argument");
+    E->next_t = t; E->next_dt = dt; E->time_set = true;
+    return HPS_OK;
+}
+extern "C" int hps_engine_beam_moments (void* h, double* out4)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && out4, "hps_engine_beam_moments: null argument");
+    HPS_REQUIRE(E->d_mom, "hps_engine_beam_moments: the deck has no adaptive time step (dt_adaptive)");
+    HPS_HIP_CHECK(hipMemcpyAsync(out4, E->d_mom + 4*E->d.nz, 4*sizeof(double), hipMemcpyDeviceToHost, E->st));
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     return HPS_OK;
 }
 extern "C" int hps_engine_set_laser_import (void* h, int on, int step)

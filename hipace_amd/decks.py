@@ -61,6 +61,17 @@ _DEFAULT = dict(
     beam_spin_tracking=0, beam_initial_spin=(1.0, 0.0, 0.0), beam_spin_anom=0.00115965218128,
 )
 
+# hipace.dt = adaptive and beams.external_E's z term.  Kept apart from _DEFAULT (whose decks the full-size fixtures record
+# key by key); a deck without these keys has them at 0, which is what every value below is.  0 = the reference's default
+# (utils/AdaptiveTimeStep.H:25-42): nt_per_betatron (20), dt_max (inf), adaptive_threshold_uz (2), adaptive_phase_tolerance
+# (4e-4), adaptive_predict_step / adaptive_control_phase_advance (inverted: 0 keeps them on), adaptive_phase_substeps (2000),
+# plasmas.adaptive_density, hipace.max_time (0: none), the initial estimate's <beam>.u_std[2]; ext_Ez_slope: external Ez = s*z
+ADAPTIVE_DEFAULT = dict(
+    dt_adaptive=0, nt_per_betatron=0.0, dt_max=0.0, adaptive_threshold_uz=0.0, adaptive_phase_tolerance=0.0,
+    adaptive_no_predict_step=0, adaptive_no_phase_control=0, adaptive_phase_substeps=0,
+    adaptive_density=0.0, max_time=0.0, beam_uz_std=0.0, ext_Ez_slope=0.0,
+)
+
 # Ionisation energies in eV of a few elements: NIST Atomic Spectra Database (Kramida, Ralchenko, Reader and NIST ASD
 # Team, ver. 5.2), the values the reference tabulates in utils/IonizationEnergiesTable.H.
 IONIZATION_ENERGIES_EV = {
@@ -135,6 +146,21 @@ def beam_evolution():
              plasma_ppc=(0, 0), plasma_density=0.0,
              beam_profile=1, beam_zmin=-10.0, beam_zmax=10.0, beam_radius=1.0, beam_density=1.0e-8,
              beam_umean=(0.0, 0.0, 1.0e3), beam_ppc=(4, 4, 1), n_steps=21, dt=3.0, ext_E_slope=(0.5, 0.5))
+    return d
+
+
+def adaptive_time_step(sign=1):
+    """tests/adaptive_time_step.1Rank.sh: the beam_in_vacuum deck on 32 x 32 x 32 cells in [-2, 2]^3, a flattop beam of
+    u_z = 1000 (ppc 4 4 1, four sub-cycles) in beams.external_E = (0, 0, sign * 0.5 z), no plasma, hipace.dt = adaptive with
+    nt_per_betatron = 89.7597901025655 and plasmas.adaptive_density = 1, max_step = 20 (21 steps), tile size 8.
+    sign = -1 is the script's first run (negative_gradient.txt), +1 its second, whose output the checksums record."""
+    d = copy.deepcopy(_DEFAULT)
+    d.update(ADAPTIVE_DEFAULT)
+    d.update(nx=32, ny=32, nz=32, lo=(-2.0, -2.0, -2.0), hi=(2.0, 2.0, 2.0), order=2,
+             plasma_ppc=(0, 0), plasma_density=0.0,
+             beam_profile=1, beam_zmin=-10.0, beam_zmax=10.0, beam_radius=1.0, beam_density=1.0,
+             beam_umean=(0.0, 0.0, 1.0e3), beam_ppc=(4, 4, 1), beam_n_subcycles=4, n_steps=21, dt=0.0,
+             dt_adaptive=1, nt_per_betatron=89.7597901025655, adaptive_density=1.0, ext_Ez_slope=0.5 * sign)
     return d
 
 

@@ -632,6 +632,9 @@ def run_lanes(engines, rank, world, n_steps, device, on_step_end=None, slices_pe
     Returns the number of slices solved by this process."""
     L = len(engines)
     W = world * L
+    if any(getattr(e, "adaptive", False) for e in engines):
+        _refuse_adaptive_ring(world)
+    clock = {0: 0.0}                               # hipace.dt = adaptive: step -> its physical time, handed from stage to stage
     own = transport is None and world > 1
     ringT = make_transport(rank, world, device) if own else transport
     edges = [LocalEdge() for _ in range(L)]        # edges[j]: stage j -> stage j + 1 of this process (the last one closes the loop when world == 1)
@@ -646,7 +649,7 @@ def run_lanes(engines, rank, world, n_steps, device, on_step_end=None, slices_pe
         T = StageTransport(eng, rx, tx)
         ose = (lambda step, e=eng: on_step_end(step, e)) if on_step_end is not None else None
         osl = (lambda m, q, jj=j: on_slice(jj, m, q)) if on_slice is not None else None
-        gens.append(_stage(eng, rank * L + j, W, n_steps, device, ose, slices_per_step, T, laser_lookahead, osl, handoff_batch))
+        gens.append(_stage(eng, rank * L + j, W, n_steps, device, ose, slices_per_step, T, laser_lookahead, osl, handoff_batch, clock))
     gc.freeze()
     try:
         import os
@@ -659,8 +662,14 @@ def run_lanes(engines, rank, world, n_steps, device, on_step_end=None, slices_pe
     return sum(solved)
 
 
+def _refuse_adaptive_ring(world):
+    if world > 1:
+        raise NotImplementedError("hipace.dt = adaptive needs every stage in one process (run_local_pipeline / run_lanes with "
+                                  "world = 1): a ring that leaves the process does not carry the step's time (MultiBuffer::put_time)")
+
+
 def _stage(engine, rank, world, n_steps, device, on_step_end=None, slices_per_step=None, transport=None,
-           laser_lookahead=8, on_slice=None, handoff_batch=1):
+           laser_lookahead=8, on_slice=None, handoff_batch=1, clock=None):
     """Stage `rank` of a ring of `world` stages (a generator, see `_drive`): run steps rank, rank+world, ... < n_steps of
     `engine` with the per-slice hand-off.  Yields "work" between the two halves of a slice (solve_slice_begin /
     solve_slice_finish) and "wait" while a local edge has no message / no posted receive for it yet.
@@ -676,6 +685,10 @@ def _stage(engine, rank, world, n_steps, device, on_step_end=None, slices_per_st
     that many slices later (a longer pipeline fill).  Measured on the RCCL ring of one GPU: no difference in the rate
     (the events are not what a hand-off costs), so the default stays 1.  A moving beam and a laser are always handed on
     slice by slice.
+    clock: hipace.dt = adaptive, the stages of one process: {step: physical time}, written by the stage that runs the step
+    before (MultiBuffer::put_time / get_time) ahead of its slices.  Each stage keeps its own controller (api.AdaptiveTimeStep,
+    initialised alike, predicting over `world` stages); it reads the moments of its previous step just before its next
+    begin_step.  The time does not travel through a transport: an adaptive deck with stages in other processes is refused.
     Returns the number of slices this rank solved.
     """
     nz = engine.deck["nz"]
@@ -691,6 +704,18 @@ def _stage(engine, rank, world, n_steps, device, on_step_end=None, slices_per_st
     assert 1 <= per <= nz and per_prev <= nz
     moving = bool(getattr(engine, "moving", False))
     laser = bool(getattr(engine, "has_laser", False))
+    adaptive = bool(getattr(engine, "adaptive", False))
+    ats = None
+    if adaptive:
+        if clock is None:
+            _refuse_adaptive_ring(world)
+            clock = {0: 0.0}
+        if float(engine.deck.get("max_time", 0.0)) != 0.0:
+            raise NotImplementedError("hipace.max_time drops steps: SliceEngine.run_adaptive runs it, the pipeline does not")
+        from .api import AdaptiveTimeStep
+        ats = AdaptiveTimeStep.for_engine(engine)
+        ats.initial_dt(nstages=world)                  # what the head rank's broadcast leaves on every rank
+        t_prev = None
     assert not (moving and (per != nz or per_prev != nz)), "a moving beam (hipace.dt != 0) needs whole steps"
     my_steps = steps_of_rank(rank, world, n_steps)
     own_transport = transport is None and world > 1
@@ -778,6 +803,16 @@ def _stage(engine, rank, world, n_steps, device, on_step_end=None, slices_per_st
             engine.set_laser_import(fed, step)
         if hasattr(engine, "set_step"):
             engine.set_step(step)                      # the physical step: density profile's time factor, ionisation draws
+        if adaptive:
+            if t_prev is not None:                     # CalculateFromMinUz of this stage's previous step (Hipace.cpp:482)
+                ats.CalculateFromMinUz(engine.beam_moments(), t_prev, world)
+            while step not in clock:                   # get_time: the stage of the step before has not begun it yet
+                yield tag_in
+            t_prev = clock.pop(step)
+            dt = ats.CalculateFromDensity(t_prev)
+            clock[step + 1] = ats.next_time()          # put_time, before any slice is solved
+            engine.set_time(t_prev, dt)
+            engine.step_times.append((step, t_prev, dt))
         engine.begin_step()
         imported = -1
         for q in range(per):

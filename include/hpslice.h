@@ -268,6 +268,18 @@ typedef struct {
      * 218-238; spin_anom = anomalous magnetic moment as given: the electron's is 0.00115965218128, 0 is pure Thomas precession).  The spin travels with the
      * particle through the slipped-particle hand-off and the ring messages (3 more rows). */
     int beam_spin_tracking; double beam_initial_spin[3]; double beam_spin_anom;
+    /* hipace.dt = adaptive (utils/AdaptiveTimeStep.cpp; Hipace.cpp:270-282, 400-490): dt_adaptive = 1 makes a moving-beam deck
+     * whatever dt says; each step's time and dt come from the host (hps_engine_set_time), computed by the controller
+     * hps_adaptive_* below from the beam moments the engine reduces per slice (hps_engine_beam_moments).
+     * hipace.nt_per_betatron (0 -> 20), dt_max (0 -> infinity), adaptive_threshold_uz (0 -> 2), adaptive_phase_tolerance
+     * (0 -> 4e-4), adaptive_predict_step = 0 / adaptive_control_phase_advance = 0 (the ABI reads the negations, so that 0 keeps
+     * the reference's default "on"), adaptive_phase_substeps (0 -> 2000), plasmas.adaptive_density, hipace.max_time (0 -> none),
+     * and the initial estimate's <beam>.u_std[2] (beam_uz_std; 0 for a fixed_ppc beam).  Not with a laser (Hipace.cpp:408). */
+    int dt_adaptive; double nt_per_betatron, dt_max, adaptive_threshold_uz, adaptive_phase_tolerance;
+    int adaptive_no_predict_step, adaptive_no_phase_control, adaptive_phase_substeps;
+    double adaptive_density, max_time, beam_uz_std;
+    /* beams.external_E(x,y,z,t) = ... ext_Ez_slope*z (z of the particle; ExternalFields.H:29-56), beside ext_E_slope */
+    double ext_Ez_slope;
 } hps_deck;
 
 /* slab component indices of the engine (explicit-solver layout of fields/Fields.cpp:70-122) */
@@ -291,6 +303,17 @@ int hps_engine_begin_step (void* handle);                 /* Evolve :401-471: re
  * Without a call an engine counts its own begin_step calls -- right for one engine running every step; a pipeline stage
  * that runs steps r, r + N, ... (Hipace.cpp:400-401) must say which step it is about to run. */
 int hps_engine_set_step (void* handle, int step);
+/* The physical time t and the time step dt of the step the next hps_engine_begin_step starts (hipace.dt = adaptive:
+ * Hipace::m_physical_time and m_dt of that step, Hipace.cpp:411-435).  That step's density profile takes f_t(c t), its beam
+ * push dt / beam_n_subcycles.  The ionisation key still follows hps_engine_set_step.  Without a call the step runs at
+ * t = deck dt * step with the deck's dt, as before. */
+int hps_engine_set_time (void* handle, double t, double dt);
+/* hipace.dt = adaptive: {sum w, sum w uz/c, sum w (uz/c)^2, min uz/c} over the beam particles of the step last solved, each
+ * counted on the slice it stays on after its push (GatherMinUzSlice(beams, false) behind shiftSlippedParticles,
+ * Hipace.cpp:703-716; absorbed particles skipped).  Reduced per slice in the beam's partition kernel and folded head to tail
+ * in a fixed order: equal inputs give bit-identical moments.  Zero with min = +infinity for an empty beam.  Synchronises
+ * the engine's stream; HPS_ERR_ARG unless the deck has dt_adaptive. */
+int hps_engine_beam_moments (void* handle, double* out4_host);
 int hps_engine_solve_slice (void* handle, int islice);    /* SolveOneSlice :556-728               */
 /* The slice in two halves, for ONE host thread that keeps several engines (time steps in flight on one device, the
  * stages of a pipeline) busy: begin enqueues everything up to and including the speculated V-cycles of the Bx/By solve
@@ -500,6 +523,34 @@ int hps_engine_record_event (void* handle, int slot, void** event_out);
 int hps_stream_pool_shared_pairs (int device);
 int hps_engine_wait_event (void* handle, void* event);
 int hps_engine_copy_async (void* handle, void* dst_dev, const void* src_dev, long bytes);
+
+/* ---- adaptive time step controller (utils/AdaptiveTimeStep.cpp): host only, no device call ---------------------------
+ * One controller per rank (or pipeline stage), created from the deck (dt_adaptive and the fields behind it; beam charge
+ * and mass, beam_charge = 0: the beam does not set dt; units; the plasma species' densities and charges).  Its dt starts
+ * at 0.  rho_max(z) = max(|adaptive_density q_e|, |plasma_charge n(0,0,z)|, |ion_charge n_ion(0,0,z)|) with n(0,0,z) the
+ * species' density on the axis, n0 f_r(0) f_t(z) (MultiPlasma::maxChargeDensity). */
+int hps_adaptive_create (const hps_deck* deck, void** handle);
+/* the tables of hps_engine_set_density_profile (pass the engine's); replaces the profile, none = factor 1 */
+int hps_adaptive_set_density_profile (void* handle, int nr, const double* r_host, const double* fr_host, int nt,
+                                      const double* ct_host, const double* ft_host);
+/* The head rank's initialisation (Hipace.cpp:275-279): the moments estimated from the beam's u_mean / u_std (uz/c)
+ * -- {1, uz_mean, uz_mean^2 + uz_std^2, uz_mean - 4 uz_std} --, then CalculateFromMinUz (predicted over nstages steps, the
+ * number of ranks / pipeline stages) and CalculateFromDensity at t = 0.  *dt: the controller's dt afterwards; every stage of
+ * a pipeline initialises its own controller alike (what the broadcast of dt and min uz m/q leaves on every rank). */
+int hps_adaptive_initial_dt (void* handle, double uz_mean, double uz_std, int nstages, double* dt_host);
+/* At the start of the step that starts at time t (Hipace.cpp:420-435): CalculateFromDensity (the moments are reset, the
+ * phase advance over adaptive_phase_substeps cuts dt where the density changes), then hipace.max_time: the step that would
+ * pass it is clipped to end on it, the step that starts on it runs with dt = 0.  *dt: the step's dt. */
+int hps_adaptive_before_step (void* handle, double t, double* dt_host);
+/* the time the step begun by the last hps_adaptive_before_step hands to the next one (MultiBuffer::put_time): t + dt,
+ * max_time for a clipped step, +infinity behind the step that starts on max_time (every later step is dropped) */
+int hps_adaptive_next_time (void* handle, double* t_next_host);
+/* At the end of the step that started at time t (CalculateFromMinUz, Hipace.cpp:482-483): the step's moments
+ * (hps_engine_beam_moments) give dt = 2 pi / omega_b / nt_per_betatron of the slowest part of the beam, predicted over
+ * nstages steps (this dt is used nstages steps later), clamped by dt_max.  *dt: the dt of this controller's next step.
+ * HPS_ERR_ARG if the sum of weights is 0 (no beam) or rho_max <= 0. */
+int hps_adaptive_after_step (void* handle, const double* moments4_host, double t, int nstages, double* dt_host);
+int hps_adaptive_destroy (void* handle);
 
 /* ---- ring pipeline over time steps: the transport (utils/MultiBuffer.H:21-34; MultiBuffer.cpp:287-609) --------
  * One process per GPU; rank r runs time steps r, r+N, ... (Hipace.cpp:400-401) and hands every pushed beam slice (and
