@@ -106,6 +106,15 @@ _SIGS = {
                                              C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hps_advance_plasma_tiled": (C.c_int, [Slab, Plasma, Geom, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hps_deposit_current_tiled_laser": (C.c_int, [Slab, Plasma, Geom, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int,
+                                                  C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hps_explicit_deposit_tiled_laser": (C.c_int, [Slab, Plasma, Geom, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hps_advance_plasma_tiled_laser": (C.c_int, [Slab, Plasma, Geom, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hps_tiling_set_validity": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hps_particles_record": (C.c_int, [C.c_int]),
+    "hps_particles_recorded": (C.c_int, [C.c_char_p, C.c_long, C.POINTER(C.c_long)]),
     "hps_poisson_create": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
     "hps_poisson_solve": (C.c_int, [C.c_void_p, C.c_void_p, Slab, C.c_int, C.c_void_p]),
     "hps_poisson_solve_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, Slab, C.c_void_p, C.c_void_p]),

@@ -141,6 +141,11 @@ class Tiling:
         check(_lib.lib().hps_reorder_particles(self._h, plasma.struct(), out.struct(), geom.c, _stream()))
         return out
 
+    def set_validity(self, by_weight=False, by_psi_half=False):
+        """The caller's promise that every invalid particle of the sheet has w == 0 (by_weight) / psi_half == 0
+        (by_psi_half): the tiled operators then take the engine's variants that read validity from there."""
+        check(_lib.lib().hps_tiling_set_validity(self._h, int(by_weight), int(by_psi_half)))
+
     def info(self):
         nt, off, perm = C.c_int(), C.c_void_p(), C.c_void_p()
         check(_lib.lib().hps_tiling_info(self._h, C.byref(nt), C.byref(off), C.byref(perm)))
@@ -163,42 +168,58 @@ class Tiling:
 
 
 def DepositCurrent(plasma, fields, geom, charge, mass, depos_order, jx=-1, jy=-1, jz=-1, rho=-1, chi=-1,
-                   rhomjz=-1, max_qsa_weighting_factor=35.0, can_ionize=False, n_qsa=None, tiling=None):
+                   rhomjz=-1, max_qsa_weighting_factor=35.0, can_ionize=False, n_qsa=None, tiling=None, aabs=-1):
+    """aabs: slab component holding the laser's |a|^2 (-1: no laser)."""
     comp = _iarr([jx, jy, jz, rho, chi, rhomjz])
     nq = C.c_void_p(n_qsa.data_ptr()) if n_qsa is not None else None
     if tiling is None:
-        check(_lib.lib().hps_deposit_current(fields.struct(), plasma.struct(), geom.c, comp, charge, mass,
-                                             depos_order, max_qsa_weighting_factor, int(can_ionize), nq, _stream()))
+        check(_lib.lib().hps_deposit_current_laser(fields.struct(), plasma.struct(), geom.c, comp, aabs, charge, mass,
+                                                   depos_order, max_qsa_weighting_factor, int(can_ionize), nq, _stream()))
     else:
-        check(_lib.lib().hps_deposit_current_tiled(fields.struct(), plasma.struct(), geom.c, comp, charge, mass,
-                                                   depos_order, max_qsa_weighting_factor, int(can_ionize), nq,
-                                                   tiling._h, C.c_void_p(tiling.fallback.data_ptr()), _stream()))
+        check(_lib.lib().hps_deposit_current_tiled_laser(fields.struct(), plasma.struct(), geom.c, comp, aabs, charge, mass,
+                                                         depos_order, max_qsa_weighting_factor, int(can_ionize), nq,
+                                                         tiling._h, C.c_void_p(tiling.fallback.data_ptr()), _stream()))
 
 
 def ExplicitDeposition(plasma, fields, geom, charge, mass, depos_order, Bz, Ez, ExmBy, EypBx, Sy, Sx,
-                       derivative_type=2, can_ionize=False, tiling=None):
+                       derivative_type=2, can_ionize=False, tiling=None, aabs=-1):
     if tiling is None:
-        check(_lib.lib().hps_explicit_deposit(fields.struct(), plasma.struct(), geom.c, _iarr([Bz, Ez, ExmBy, EypBx]),
-                                              _iarr([Sy, Sx]), charge, mass, depos_order, derivative_type,
-                                              int(can_ionize), _stream()))
+        check(_lib.lib().hps_explicit_deposit_laser(fields.struct(), plasma.struct(), geom.c, _iarr([Bz, Ez, ExmBy, EypBx]),
+                                                    aabs, _iarr([Sy, Sx]), charge, mass, depos_order, derivative_type,
+                                                    int(can_ionize), _stream()))
     else:
-        check(_lib.lib().hps_explicit_deposit_tiled(fields.struct(), plasma.struct(), geom.c,
-                                                    _iarr([Bz, Ez, ExmBy, EypBx]), _iarr([Sy, Sx]), charge, mass,
-                                                    depos_order, derivative_type, int(can_ionize), tiling._h,
-                                                    C.c_void_p(tiling.fallback.data_ptr()), _stream()))
+        check(_lib.lib().hps_explicit_deposit_tiled_laser(fields.struct(), plasma.struct(), geom.c,
+                                                          _iarr([Bz, Ez, ExmBy, EypBx]), aabs, _iarr([Sy, Sx]), charge, mass,
+                                                          depos_order, derivative_type, int(can_ionize), tiling._h,
+                                                          C.c_void_p(tiling.fallback.data_ptr()), _stream()))
 
 
 def AdvancePlasmaParticles(plasma, fields, geom, charge, mass, depos_order, Psi, Ez, Bx, By, Bz,
-                           temp_slice=False, n_subcycles=1, can_ionize=False, tiling=None):
+                           temp_slice=False, n_subcycles=1, can_ionize=False, tiling=None, aabs=-1):
     if tiling is None:
-        check(_lib.lib().hps_advance_plasma(fields.struct(), plasma.struct(), geom.c, _iarr([Psi, Ez, Bx, By, Bz]),
-                                            charge, mass, depos_order, int(temp_slice), n_subcycles,
-                                            int(can_ionize), _stream()))
+        check(_lib.lib().hps_advance_plasma_laser(fields.struct(), plasma.struct(), geom.c, _iarr([Psi, Ez, Bx, By, Bz]),
+                                                  aabs, charge, mass, depos_order, int(temp_slice), n_subcycles,
+                                                  int(can_ionize), _stream()))
     else:
-        check(_lib.lib().hps_advance_plasma_tiled(fields.struct(), plasma.struct(), geom.c,
-                                                  _iarr([Psi, Ez, Bx, By, Bz]), charge, mass, depos_order,
-                                                  int(temp_slice), n_subcycles, int(can_ionize), tiling._h,
-                                                  C.c_void_p(tiling.fallback.data_ptr()), _stream()))
+        check(_lib.lib().hps_advance_plasma_tiled_laser(fields.struct(), plasma.struct(), geom.c,
+                                                        _iarr([Psi, Ez, Bx, By, Bz]), aabs, charge, mass, depos_order,
+                                                        int(temp_slice), n_subcycles, int(can_ionize), tiling._h,
+                                                        C.c_void_p(tiling.fallback.data_ptr()), _stream()))
+
+
+def record_particle_dispatch(on=True):
+    """Switch the dispatch record of the tiled particle kernels on (emptying it) or off (hps_particles_record)."""
+    check(_lib.lib().hps_particles_record(int(on)))
+
+
+def recorded_particle_dispatch():
+    """The set of tiled particle kernel instances launched since record_particle_dispatch(True), such as
+    'k_deposit_tiled<2,16,51,0,1>' (template arguments as integers)."""
+    n = C.c_long()
+    check(_lib.lib().hps_particles_recorded(None, 0, C.byref(n)))
+    buf = C.create_string_buffer(n.value + 1)
+    check(_lib.lib().hps_particles_recorded(buf, n.value + 1, C.byref(n)))
+    return set(buf.value.decode().split())
 
 
 class FFTPoissonSolver:

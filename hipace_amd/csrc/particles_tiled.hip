@@ -17,9 +17,32 @@
 #include "mg_gate.h"
 #include "beam_deposit.h"
 
+#include <algorithm>
+#include <atomic>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <set>
+#include <string>
 
 namespace hps {
+
+// Dispatch record (hps_particles_record): the names of the kernel instances the four dispatchers below launched since it was
+// switched on, e.g. "k_deposit_tiled<2,16,51,0,1>" (template arguments as integers).  Off: one predictable branch per launch.
+static std::atomic<bool> g_record{false};
+static std::mutex g_record_mu;
+static std::set<std::string> g_recorded;
+static void record_launch (const char* kernel, std::initializer_list<int> args)
+{
+    std::string n(kernel);
+    char sep = '<';
+    for (int a : args) { char b[16]; std::snprintf(b, sizeof b, "%c%d", sep, a); n += b; sep = ','; }
+    n += '>';
+    std::lock_guard<std::mutex> lk(g_record_mu);
+    g_recorded.insert(n);
+}
+#define HPS_RECORD(kernel, ...) do { if (__builtin_expect(g_record.load(std::memory_order_relaxed), 0)) record_launch(kernel, {__VA_ARGS__}); } while (0)
 
 // LDS row pitch of the explicit deposition's images: R + PAD doubles.  PAD 2 is the best for the row-by-row numbering of
 // a tile's cells (measured -2.5 % against 0; PAD 8 with it: 136.5 against 124.8 us); PAD 8 (pitch 36 = +4 mod 32) goes
@@ -239,7 +262,6 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
         const Rec cur = rec[u];
         const uint64_t id = cur.id;
         if (!(id & HPS_ID_VALID)) continue;
-        if (k.can_ionize && cur.ion == 0) continue;      // a neutral atom deposits nothing (every term carries its level)
 #if HPS_DEP_FAST_RCP
         // v_rcp_f64 + one Newton step (as the push: particle_math.h fast_rcp) instead of the IEEE division's eleven
         // instructions; psi = 0 must still give the inf the QSA test below drops the particle on (Newton would make it a NaN)
@@ -274,6 +296,9 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
             if (pl.psi_half) pl.psi_half[ip] = 0.0;      // (Tiling::valid_by_psi)
             continue;
         }
+        // a neutral atom deposits nothing (every term carries its level) -- but it takes the QSA test above, as in
+        // PlasmaDepositCurrent.cpp:190-203 and the per-particle kernel
+        if (k.can_ionize && cur.ion == 0) continue;
         // per-component weights in DepComps order
         const double wv[6] = {vx_c, vy_c, (gamma_psi - 1.0)*k.c, gamma_psi, q_mu0_mass*psi_inv, 1.0};
         if (local) {
@@ -1331,11 +1356,11 @@ int deposit_current_tiled (const hps_slab& slab, const hps_plasma& pl, const hps
     const size_t lds = ((size_t)na*R*(R + HPS_DEP_PAD) + (aabs_comp >= 0 ? (size_t)R*R : 0))*sizeof(double);
     SlabView f(slab);
     int mask = 0; for (int c = 0; c < 6; ++c) mask |= (comp[c] >= 0) << c;
-#define CALLM(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M>, lds)) return e; \
+#define CALLM(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M>, lds)) return e; HPS_RECORD("k_deposit_tiled", O, S, M, 0, 0); \
         hipLaunchKernelGGL((k_deposit_tiled<O, S, M>), dim3(T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, cm, k, n_qsa, n_fallback, tile_flag, tw, bw, go); }
-#define CALLL(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M, true>, lds)) return e; \
+#define CALLL(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M, true>, lds)) return e; HPS_RECORD("k_deposit_tiled", O, S, M, 1, 0); \
         hipLaunchKernelGGL((k_deposit_tiled<O, S, M, true>), dim3(T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, cm, k, n_qsa, n_fallback, tile_flag, tw, bw, go); }
-#define CALLV(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M, false, true>, lds)) return e; \
+#define CALLV(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M, false, true>, lds)) return e; HPS_RECORD("k_deposit_tiled", O, S, M, 0, 1); \
         hipLaunchKernelGGL((k_deposit_tiled<O, S, M, false, true>), dim3(T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, cm, k, n_qsa, n_fallback, tile_flag, tw, bw, go); }
 #define CALL(O, S) { if (aabs_comp >= 0) { if (mask == 51) CALLL(O, S, 51) else CALLL(O, S, -1) } \
                      else if (k.valid_by_w && mask == 51) CALLV(O, S, 51) else if (k.valid_by_w && mask == 3) CALLV(O, S, 3) \
@@ -1365,7 +1390,7 @@ int explicit_deposit_tiled (const hps_slab& slab, const hps_plasma& pl, const hp
     const int pad = expl_pad();
     const size_t lds = (size_t)(aabs_comp >= 0 ? 7 : 6)*R*(R + pad)*sizeof(double);
     SlabView f(slab);
-#define HPS_EXPL_LAUNCH(O, D, S, L, P, V) { if (int e = set_lds(k_explicit_tiled<O, D, S, L, P, V>, lds)) return e; \
+#define HPS_EXPL_LAUNCH(O, D, S, L, P, V) { if (int e = set_lds(k_explicit_tiled<O, D, S, L, P, V>, lds)) return e; HPS_RECORD("k_explicit_tiled", O, D, S, L, P, V); \
         hipLaunchKernelGGL((k_explicit_tiled<O, D, S, L, P, V>), dim3(T->g.ntiles + tw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, \
                            cache[0], cache[1], cache[2], cache[3], depos[0], depos[1], k, n_fallback, tile_flag, tw); }
 #define HPS_EXPL_PADS(O, D, S, L) { if (pad == 8) HPS_EXPL_LAUNCH(O, D, S, L, 8, false) else if (!L && D == 2 && k.valid_by_w) HPS_EXPL_LAUNCH(O, D, S, false, 2, true) else HPS_EXPL_LAUNCH(O, D, S, L, 2, false) }
@@ -1405,7 +1430,7 @@ int advance_plasma_tiled (const hps_slab& slab, const hps_plasma& pl, const hps_
     const MgPost mp = post ? *post : MgPost{};
     // (the variant without the idcpu read exists for order 2 on 16 x 16 tiles, as the depositions' <.., VBW>)
     const bool vbp = T->valid_by_psi && !ion && !can_ionize && order == 2 && T->g.ts == 16;
-#define HPS_ADV(O, S, L, I, V) { if (int e = set_lds(k_advance_tiled<O, S, L, I, V>, lds)) return e; \
+#define HPS_ADV(O, S, L, I, V) { if (int e = set_lds(k_advance_tiled<O, S, L, I, V>, lds)) return e; HPS_RECORD("k_advance_tiled", O, S, L, I, V, 0); \
         hipLaunchKernelGGL((k_advance_tiled<O, S, L, I, V>), dim3(T->g.ntiles + tw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, \
                            comp[0], comp[1], comp[2], comp[3], comp[4], k, n_fallback, ia, go, tw, mp, DepTail{}); }
 #define CALL(O, S) { if (ion) { if (aabs_comp >= 0) HPS_ADV(O, S, true, true, false) else HPS_ADV(O, S, false, true, false) } \
@@ -1440,6 +1465,7 @@ int advance_deposit_tiled (const hps_slab& slab, const hps_plasma& pl, const hps
         const size_t lds5 = (size_t)5*R*R*sizeof(double);
         DepTail dt{cm, kd.a, kd.b, max_qsa, n_qsa};
         const IonArgs ia{}; const TailWork tw0{}; const MgPost mp0{};
+        HPS_RECORD("k_advance_tiled", 2, 16, 0, 0, 0, mask);
         if (mask == 51) { if (int e = set_lds(k_advance_tiled<2, 16, false, false, false, 51>, lds5)) return e;
             hipLaunchKernelGGL((k_advance_tiled<2, 16, false, false, false, 51>), dim3(T->g.ntiles), dim3(256), lds5, st, f, pl, T->offsets, T->g.ntx,
                                comp[0], comp[1], comp[2], comp[3], comp[4], k, n_fallback, ia, (const int*)nullptr, tw0, mp0, dt); }
@@ -1453,7 +1479,7 @@ int advance_deposit_tiled (const hps_slab& slab, const hps_plasma& pl, const hps
     static int nt = 0;
     // (measured at 1024^2 x 4 ppc: 256 threads 285 us, 512 threads 316 us -- against 175 + 77 us for the two kernels)
     if (nt == 0) { nt = 256; if (const char* e = std::getenv("HPS_FUSED_THREADS")) { const int v = std::atoi(e); if (v == 256 || v == 512) nt = v; } }
-#define HPS_AD(O, S, M, N) { if (int e = set_lds(k_advance_deposit_tiled<O, S, M, N>, lds)) return e; \
+#define HPS_AD(O, S, M, N) { if (int e = set_lds(k_advance_deposit_tiled<O, S, M, N>, lds)) return e; HPS_RECORD("k_advance_deposit_tiled", O, S, M, N); \
         hipLaunchKernelGGL((k_advance_deposit_tiled<O, S, M, N>), dim3(T->g.ntiles), dim3(N), lds, st, f, pl, T->offsets, T->g.ntx, \
                            comp[0], comp[1], comp[2], comp[3], comp[4], k, cm, kd, n_qsa, n_fallback); }
 #define CALL(O, S) { if (nt == 512) { if (mask == 51) HPS_AD(O, S, 51, 512) else HPS_AD(O, S, 59, 512) } \
@@ -1496,38 +1522,104 @@ static int check_tiling (void* tiling, const hps_slab& s, const hps_plasma& pl, 
     return HPS_OK;
 }
 
-extern "C" int hps_deposit_current_tiled (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[6], double charge,
-                                          double mass, int order, double max_qsa, int can_ionize, int* n_qsa,
-                                          void* tiling, int* n_fallback, hps_stream stream)
+static int deposit_current_tiled_entry (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[6], int aabs_comp, double charge,
+                                        double mass, int order, double max_qsa, int can_ionize, int* n_qsa,
+                                        void* tiling, int* n_fallback, hps_stream stream)
 {
+    HPS_REQUIRE(aabs_comp >= -1 && aabs_comp < slab.ncomp, "hps_deposit_current_tiled: bad aabs component");
     HPS_REQUIRE(order >= 0 && order <= 3, "hps_deposit_current_tiled: depos_order must be 0..3");
     if (int e = check_stencil(slab, (order + 1)/2, "hps_deposit_current_tiled")) return e;
     if (int e = check_tiling(tiling, slab, pl, "hps_deposit_current_tiled")) return e;
     for (int c = 0; c < 6; ++c) HPS_REQUIRE(comp[c] >= -1 && comp[c] < slab.ncomp, "hps_deposit_current_tiled: bad component");
+    Tiling* T = static_cast<Tiling*>(tiling);
     return deposit_current_tiled(slab, pl, g, comp, charge, mass, order, max_qsa, can_ionize, n_qsa,
-                                 static_cast<Tiling*>(tiling), n_fallback, (hipStream_t)stream, -1, nullptr, TailWork{}, nullptr, nullptr, false);
+                                 T, n_fallback, (hipStream_t)stream, aabs_comp, nullptr, TailWork{}, nullptr, nullptr, T->valid_by_w);
+}
+
+extern "C" int hps_deposit_current_tiled (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[6], double charge,
+                                          double mass, int order, double max_qsa, int can_ionize, int* n_qsa,
+                                          void* tiling, int* n_fallback, hps_stream stream)
+{
+    return deposit_current_tiled_entry(slab, pl, g, comp, -1, charge, mass, order, max_qsa, can_ionize, n_qsa, tiling, n_fallback, stream);
+}
+extern "C" int hps_deposit_current_tiled_laser (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[6], int aabs_comp,
+                                                double charge, double mass, int order, double max_qsa, int can_ionize, int* n_qsa,
+                                                void* tiling, int* n_fallback, hps_stream stream)
+{
+    return deposit_current_tiled_entry(slab, pl, g, comp, aabs_comp, charge, mass, order, max_qsa, can_ionize, n_qsa, tiling, n_fallback, stream);
+}
+
+static int explicit_deposit_tiled_entry (hps_slab slab, hps_plasma pl, hps_geom g, const int cache[4], int aabs_comp, const int depos[2],
+                                         double charge, double mass, int order, int dtype, int can_ionize, void* tiling,
+                                         int* n_fallback, hps_stream stream)
+{
+    HPS_REQUIRE(aabs_comp >= -1 && aabs_comp < slab.ncomp, "hps_explicit_deposit_tiled: bad aabs component");
+    HPS_REQUIRE(order >= 0 && order <= 3, "hps_explicit_deposit_tiled: depos_order must be 0..3");
+    if (dtype != 1 && dtype != 2) { set_error("hps_explicit_deposit_tiled: derivative_type 1 or 2 only"); return HPS_ERR_UNSUPPORTED; }
+    if (int e = check_stencil(slab, (order + 1)/2 + 1, "hps_explicit_deposit_tiled")) return e;
+    if (int e = check_tiling(tiling, slab, pl, "hps_explicit_deposit_tiled")) return e;
+    Tiling* T = static_cast<Tiling*>(tiling);
+    return explicit_deposit_tiled(slab, pl, g, cache, depos, charge, mass, order, dtype, can_ionize,
+                                  T, n_fallback, (hipStream_t)stream, aabs_comp, nullptr, TailWork{}, T->valid_by_w);
 }
 
 extern "C" int hps_explicit_deposit_tiled (hps_slab slab, hps_plasma pl, hps_geom g, const int cache[4], const int depos[2],
                                            double charge, double mass, int order, int dtype, int can_ionize, void* tiling,
                                            int* n_fallback, hps_stream stream)
 {
-    HPS_REQUIRE(order >= 0 && order <= 3, "hps_explicit_deposit_tiled: depos_order must be 0..3");
-    if (dtype != 1 && dtype != 2) { set_error("hps_explicit_deposit_tiled: derivative_type 1 or 2 only"); return HPS_ERR_UNSUPPORTED; }
-    if (int e = check_stencil(slab, (order + 1)/2 + 1, "hps_explicit_deposit_tiled")) return e;
-    if (int e = check_tiling(tiling, slab, pl, "hps_explicit_deposit_tiled")) return e;
-    return explicit_deposit_tiled(slab, pl, g, cache, depos, charge, mass, order, dtype, can_ionize,
-                                  static_cast<Tiling*>(tiling), n_fallback, (hipStream_t)stream, -1, nullptr, TailWork{}, false);
+    return explicit_deposit_tiled_entry(slab, pl, g, cache, -1, depos, charge, mass, order, dtype, can_ionize, tiling, n_fallback, stream);
+}
+extern "C" int hps_explicit_deposit_tiled_laser (hps_slab slab, hps_plasma pl, hps_geom g, const int cache[4], int aabs_comp,
+                                                 const int depos[2], double charge, double mass, int order, int dtype, int can_ionize,
+                                                 void* tiling, int* n_fallback, hps_stream stream)
+{
+    return explicit_deposit_tiled_entry(slab, pl, g, cache, aabs_comp, depos, charge, mass, order, dtype, can_ionize, tiling, n_fallback, stream);
+}
+
+static int advance_plasma_tiled_entry (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[5], int aabs_comp, double charge,
+                                       double mass, int order, int temp_slice, int n_subcycles, int can_ionize,
+                                       void* tiling, int* n_fallback, hps_stream stream)
+{
+    HPS_REQUIRE(aabs_comp >= -1 && aabs_comp < slab.ncomp, "hps_advance_plasma_tiled: bad aabs component");
+    HPS_REQUIRE(order >= 0 && order <= 3, "hps_advance_plasma_tiled: depos_order must be 0..3");
+    HPS_REQUIRE(n_subcycles >= 1, "hps_advance_plasma_tiled: n_subcycles must be >= 1");
+    if (int e = check_stencil(slab, (order + 1)/2 + 1, "hps_advance_plasma_tiled")) return e;
+    if (int e = check_tiling(tiling, slab, pl, "hps_advance_plasma_tiled")) return e;
+    return advance_plasma_tiled(slab, pl, g, comp, charge, mass, order, temp_slice, n_subcycles, can_ionize,
+                                static_cast<Tiling*>(tiling), n_fallback, (hipStream_t)stream, aabs_comp, nullptr, nullptr, TailWork{}, nullptr);
 }
 
 extern "C" int hps_advance_plasma_tiled (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[5], double charge,
                                          double mass, int order, int temp_slice, int n_subcycles, int can_ionize,
                                          void* tiling, int* n_fallback, hps_stream stream)
 {
-    HPS_REQUIRE(order >= 0 && order <= 3, "hps_advance_plasma_tiled: depos_order must be 0..3");
-    HPS_REQUIRE(n_subcycles >= 1, "hps_advance_plasma_tiled: n_subcycles must be >= 1");
-    if (int e = check_stencil(slab, (order + 1)/2 + 1, "hps_advance_plasma_tiled")) return e;
-    if (int e = check_tiling(tiling, slab, pl, "hps_advance_plasma_tiled")) return e;
-    return advance_plasma_tiled(slab, pl, g, comp, charge, mass, order, temp_slice, n_subcycles, can_ionize,
-                                static_cast<Tiling*>(tiling), n_fallback, (hipStream_t)stream, -1, nullptr, nullptr, TailWork{}, nullptr);
+    return advance_plasma_tiled_entry(slab, pl, g, comp, -1, charge, mass, order, temp_slice, n_subcycles, can_ionize, tiling, n_fallback, stream);
+}
+extern "C" int hps_advance_plasma_tiled_laser (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[5], int aabs_comp,
+                                               double charge, double mass, int order, int temp_slice, int n_subcycles, int can_ionize,
+                                               void* tiling, int* n_fallback, hps_stream stream)
+{
+    return advance_plasma_tiled_entry(slab, pl, g, comp, aabs_comp, charge, mass, order, temp_slice, n_subcycles, can_ionize, tiling, n_fallback, stream);
+}
+
+extern "C" int hps_particles_record (int on)
+{
+    std::lock_guard<std::mutex> lk(g_record_mu);
+    if (on) g_recorded.clear();
+    g_record.store(on != 0, std::memory_order_relaxed);
+    return HPS_OK;
+}
+
+extern "C" int hps_particles_recorded (char* buf, long cap, long* len)
+{
+    std::string all;
+    {   std::lock_guard<std::mutex> lk(g_record_mu);
+        for (const std::string& n : g_recorded) { all += n; all += '\n'; } }
+    if (len) *len = (long)all.size();
+    if (buf && cap > 0) {
+        const size_t k = std::min((size_t)cap - 1, all.size());
+        std::memcpy(buf, all.data(), k);
+        buf[k] = 0;
+    }
+    return HPS_OK;
 }

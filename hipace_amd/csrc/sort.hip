@@ -321,3 +321,12 @@ extern "C" int hps_tiling_info (void* tiling, int* ntiles, const int** offsets_d
 }
 
 extern "C" int hps_tiling_destroy (void* tiling) { delete static_cast<Tiling*>(tiling); return HPS_OK; }
+
+extern "C" int hps_tiling_set_validity (void* tiling, int by_weight, int by_psi_half)
+{
+    if (!tiling) { set_error("hps_tiling_set_validity: null tiling"); return HPS_ERR_ARG; }
+    Tiling* T = static_cast<Tiling*>(tiling);
+    T->valid_by_w = by_weight != 0;
+    T->valid_by_psi = by_psi_half != 0;
+    return HPS_OK;
+}

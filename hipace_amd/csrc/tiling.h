@@ -20,8 +20,11 @@ struct Tiling {
     int* cell_first = nullptr;                    // [ntiles*ts*ts + 2] run starts of the cell keys
     // the sheet is one whose every invalidation also zeroes psi_half (the engine's own electron sheet: k_init_plasma, the QSA drop of
     // the depositions, the absorbing boundary of the pushes): the tile push then takes "psi_half != 0" for the valid bit and does
-    // not read idcpu (HPS_VALID_BY_PSI=0: off).  Never set for a caller's sheet (hps_tiling_create).
+    // not read idcpu (HPS_VALID_BY_PSI=0: off).  Off for a caller's sheet unless the caller promises it (hps_tiling_set_validity).
     bool valid_by_psi = false;
+    // the same promise for the weight (every invalid particle has w == 0): the C entries of the depositions then take the
+    // "w != 0" variants (PartConsts::valid_by_w) as the engine does.  Set by hps_tiling_set_validity only.
+    bool valid_by_w = false;
     ~Tiling ();
 };
 

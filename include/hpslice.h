@@ -135,6 +135,31 @@ int hps_advance_plasma_tiled (hps_slab slab, hps_plasma plasma, hps_geom geom, c
                               double charge, double mass, int depos_order, int temp_slice,
                               int n_subcycles, int can_ionize, void* tiling, int* n_fallback,
                               hps_stream stream);
+/* The same three with a laser envelope, as the untiled *_laser calls: aabs_comp = slab component holding |a|^2, -1 = no laser. */
+int hps_deposit_current_tiled_laser (hps_slab slab, hps_plasma plasma, hps_geom geom, const int comp[6], int aabs_comp,
+                                     double charge, double mass, int depos_order, double max_qsa_weighting,
+                                     int can_ionize, int* n_qsa_violation, void* tiling, int* n_fallback,
+                                     hps_stream stream);
+int hps_explicit_deposit_tiled_laser (hps_slab slab, hps_plasma plasma, hps_geom geom, const int cache[4], int aabs_comp,
+                                      const int depos[2], double charge, double mass, int depos_order,
+                                      int derivative_type, int can_ionize, void* tiling, int* n_fallback,
+                                      hps_stream stream);
+int hps_advance_plasma_tiled_laser (hps_slab slab, hps_plasma plasma, hps_geom geom, const int comp[5], int aabs_comp,
+                                    double charge, double mass, int depos_order, int temp_slice,
+                                    int n_subcycles, int can_ionize, void* tiling, int* n_fallback,
+                                    hps_stream stream);
+/* The caller's promise about the sheet ordered through `tiling`: by_weight = every particle whose valid bit is clear has
+ * w == 0, by_psi_half = it has psi_half == 0.  The tiled calls then take "w != 0" (depositions) / "psi_half != 0" (push)
+ * for the valid bit, as the engine does for its own sheet, and do not read idcpu.  Both off after hps_tiling_create.
+ * Every path of these calls that clears a valid bit also zeroes w and psi_half, so the promise, once true, stays true. */
+int hps_tiling_set_validity (void* tiling, int by_weight, int by_psi_half);
+
+/* Dispatch record of the tiled particle kernels: hps_particles_record(1) empties it and switches it on, (0) switches it off
+ * (the default).  hps_particles_recorded writes the names of the instances launched while it was on, one per line, e.g.
+ * "k_deposit_tiled<2,16,51,0,1>" (template arguments as integers), into buf (NUL-terminated, at most cap bytes); *len =
+ * length of the whole list without the NUL. */
+int hps_particles_record (int on);
+int hps_particles_recorded (char* buf, long cap, long* len);
 
 /* ---- transverse field solvers ------------------------------------------------------------ */
 

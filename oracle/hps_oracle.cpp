@@ -2162,6 +2162,20 @@ void orc_explicit_deposit (orc_slab s, orc_plasma p, orc_geom g, const int* cach
 void orc_advance_plasma (orc_slab s, orc_plasma p, orc_geom g, const int* comp, double q, double m, int order, int temp_slice, int n_subcycles) {
     advance_plasma(mk_slab(s), mk_pl(p), mk_geom(g), comp, q, m, order, temp_slice, n_subcycles, 0);
 }
+// the same three with ion levels (can_ionize) and a laser envelope (aabs_comp = slab component of |a|^2, -1: none); the
+// entries above keep their signatures for existing callers
+long orc_deposit_current_laser (orc_slab s, orc_plasma p, orc_geom g, const int* comp, double q, double m, int order, double max_qsa,
+                                int can_ionize, int aabs_comp) {
+    return deposit_current(mk_slab(s), mk_pl(p), mk_geom(g), comp, q, m, order, max_qsa, can_ionize, aabs_comp);
+}
+void orc_explicit_deposit_laser (orc_slab s, orc_plasma p, orc_geom g, const int* cache, const int* depos, double q, double m, int order,
+                                 int dtype, int can_ionize, int aabs_comp) {
+    explicit_deposit(mk_slab(s), mk_pl(p), mk_geom(g), cache, depos, q, m, order, dtype, can_ionize, aabs_comp);
+}
+void orc_advance_plasma_laser (orc_slab s, orc_plasma p, orc_geom g, const int* comp, double q, double m, int order, int temp_slice,
+                               int n_subcycles, int can_ionize, int aabs_comp) {
+    advance_plasma(mk_slab(s), mk_pl(p), mk_geom(g), comp, q, m, order, temp_slice, n_subcycles, can_ionize, aabs_comp);
+}
 void orc_gather (orc_slab s, orc_geom g, const int* comp, int order, double xp, double yp, double* out6) {
     double a=0,b=0,c=0,d=0,e=0,f=0;
     gather(order, xp, yp, a, b, c, d, e, f, mk_slab(s), comp, 1.0/g.dx, 1.0/g.dy, g.xoff, g.yoff);

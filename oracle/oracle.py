@@ -108,10 +108,19 @@ def lib():
         L.orc_deriv_shape.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_deposit_current.restype = C.c_long
         L.orc_deposit_current.argtypes = [Slab, Plasma, Geom, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double]
+        L.orc_deposit_current_laser.restype = C.c_long
+        L.orc_deposit_current_laser.argtypes = [Slab, Plasma, Geom, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double,
+                                                C.c_int, C.c_int]
         L.orc_explicit_deposit.restype = None
         L.orc_explicit_deposit.argtypes = [Slab, Plasma, Geom, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int]
+        L.orc_explicit_deposit_laser.restype = None
+        L.orc_explicit_deposit_laser.argtypes = [Slab, Plasma, Geom, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
+                                                 C.c_int, C.c_int, C.c_int]
         L.orc_advance_plasma.restype = None
         L.orc_advance_plasma.argtypes = [Slab, Plasma, Geom, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]
+        L.orc_advance_plasma_laser.restype = None
+        L.orc_advance_plasma_laser.argtypes = [Slab, Plasma, Geom, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int]
         L.orc_gather.restype = None
         L.orc_gather.argtypes = [Slab, Geom, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p]
         L.orc_tile_sort.restype = None
@@ -231,23 +240,25 @@ def deriv_shape(dtype, order, xmid, ix):
     return cell, s.value, ds.value
 
 
-def deposit_current(slab, nx, ny, g, real, valid, ion, geom, comp, q, m, order, max_qsa=35.0):
+def deposit_current(slab, nx, ny, g, real, valid, ion, geom, comp, q, m, order, max_qsa=35.0, can_ionize=False, aabs=-1):
+    """aabs: slab component holding the laser's |a|^2 (-1: no laser); can_ionize: charges scale with ion_lev."""
     c = np.asarray(comp, dtype=np.int32)
-    return lib().orc_deposit_current(slab_struct(slab, nx, ny, g), plasma_struct(real, valid, ion), geom,
-                                     _ptr(c), q, m, order, max_qsa)
+    return lib().orc_deposit_current_laser(slab_struct(slab, nx, ny, g), plasma_struct(real, valid, ion), geom,
+                                           _ptr(c), q, m, order, max_qsa, int(can_ionize), aabs)
 
 
-def explicit_deposit(slab, nx, ny, g, real, valid, ion, geom, cache, depos, q, m, order, dtype=2):
+def explicit_deposit(slab, nx, ny, g, real, valid, ion, geom, cache, depos, q, m, order, dtype=2, can_ionize=False, aabs=-1):
     c = np.asarray(cache, dtype=np.int32)
     d = np.asarray(depos, dtype=np.int32)
-    lib().orc_explicit_deposit(slab_struct(slab, nx, ny, g), plasma_struct(real, valid, ion), geom,
-                               _ptr(c), _ptr(d), q, m, order, dtype)
+    lib().orc_explicit_deposit_laser(slab_struct(slab, nx, ny, g), plasma_struct(real, valid, ion), geom,
+                                     _ptr(c), _ptr(d), q, m, order, dtype, int(can_ionize), aabs)
 
 
-def advance_plasma(slab, nx, ny, g, real, valid, ion, geom, comp, q, m, order, temp_slice=0, n_subcycles=1):
+def advance_plasma(slab, nx, ny, g, real, valid, ion, geom, comp, q, m, order, temp_slice=0, n_subcycles=1, can_ionize=False,
+                   aabs=-1):
     c = np.asarray(comp, dtype=np.int32)
-    lib().orc_advance_plasma(slab_struct(slab, nx, ny, g), plasma_struct(real, valid, ion), geom,
-                             _ptr(c), q, m, order, temp_slice, n_subcycles)
+    lib().orc_advance_plasma_laser(slab_struct(slab, nx, ny, g), plasma_struct(real, valid, ion), geom,
+                                   _ptr(c), q, m, order, int(temp_slice), n_subcycles, int(can_ionize), aabs)
 
 
 def gather(slab, nx, ny, g, geom, comp, order, xp, yp):

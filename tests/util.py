@@ -160,3 +160,78 @@ def helmholtz1_direct(rhs, acf, dx, dy, cc):
     r = np.asarray(rhs, dtype=np.float64).reshape(-1, ny * nx)
     phi = np.stack([lu.solve(-b) for b in r]).reshape(np.shape(rhs))
     return phi, float(np.abs(lu.solve(np.ones(ny * nx))).max())
+
+
+# DepositCurrent (particles/deposition/PlasmaDepositCurrent.cpp:155-246) restated in float64 numpy, independent of the oracle
+# and of the kernels: the shape factors of orders 0 to 3 and the per-component weights of each particle.
+DEP_COMPS = ("jx", "jy", "jz", "rho", "chi", "rhomjz")
+
+
+def shape_factors(order, xmid):
+    """(first cell, (n, order + 1) weights) of the plain shape of `order` at the positions xmid (in cells)."""
+    xmid = np.asarray(xmid, dtype=np.float64)
+    if order == 0:
+        return np.floor(xmid + 0.5).astype(np.int64), np.ones(xmid.shape + (1,))
+    if order == 1:
+        j = np.floor(xmid)
+        t = xmid - j
+        return j.astype(np.int64), np.stack([1.0 - t, t], axis=-1)
+    if order == 2:
+        j = np.floor(xmid + 0.5)
+        t = xmid - j
+        return j.astype(np.int64) - 1, np.stack([0.5 * (0.5 - t) ** 2, 0.75 - t * t, 0.5 * (0.5 + t) ** 2], axis=-1)
+    j = np.floor(xmid)
+    t = xmid - j
+    u = 1.0 - t
+    return j.astype(np.int64) - 1, np.stack([u ** 3 / 6.0, 2.0 / 3.0 - t * t + 0.5 * t ** 3,
+                                             2.0 / 3.0 - u * u + 0.5 * u ** 3, t ** 3 / 6.0], axis=-1)
+
+
+def deposit_weights(real, valid, ion, slab, ng, geom, q, m, order, max_qsa=35.0, can_ionize=False, aabs=-1):
+    """Per particle of the sheet: (survives, dropped, (6, n) per-component weight w_c, charge density q w level / vol,
+    stencil (i0, sx, j0, sy)).  A valid particle whose gamma/psi fails the QSA test is dropped (NaN passes, as in the
+    reference); w_c in DEP_COMPS order: ux/psi, uy/psi, (gamma_psi - 1) c, gamma_psi, q mu0 level/(m psi), 1.
+    |a|^2 (slab component aabs) is gathered with the deposition's own shape, times laser_norm (times level^2)."""
+    x, y, w, ux, uy, psi = (np.asarray(real[k], dtype=np.float64) for k in range(6))
+    lev = np.asarray(ion, dtype=np.float64) if can_ionize else np.ones(x.size)
+    vol_inv = 1.0 if geom.normalized else 1.0 / (geom.dx * geom.dy * geom.dz)
+    i0, sx = shape_factors(order, (x - geom.xoff) / geom.dx)
+    j0, sy = shape_factors(order, (y - geom.yoff) / geom.dy)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        psi_inv = 1.0 / psi
+        vx, vy = ux * psi_inv, uy * psi_inv
+        A = np.zeros(x.size)
+        if aabs >= 0:
+            on = np.asarray(valid) != 0
+            for iy in range(order + 1):
+                for ix in range(order + 1):
+                    jj = np.where(on, j0 + iy + ng, 0)
+                    ii = np.where(on, i0 + ix + ng, 0)
+                    A += sx[:, ix] * sy[:, iy] * slab[aabs][jj, ii]
+            A *= ((q / geom.q_e) * (geom.m_e / m)) ** 2 * lev * lev
+        c = geom.c
+        gp = 0.5 * ((1.0 + 0.5 * A) * psi_inv ** 2 + (vx / c) ** 2 + (vy / c) ** 2 + 1.0)
+        bad = (gp < 0.0) | (gp > max_qsa) | (psi_inv < 0.0)
+        wc = np.stack([vx, vy, (gp - 1.0) * c, gp, q * geom.mu0 * lev / m * psi_inv, np.ones(x.size)])
+    valid = np.asarray(valid) != 0
+    dropped = valid & bad
+    return valid & ~bad, dropped, wc, q * vol_inv * w * lev, (i0, sx, j0, sy)
+
+
+def deposit_current_ref(slab, ng, real, valid, ion, geom, comp, q, m, order, max_qsa=35.0, can_ionize=False, aabs=-1):
+    """DepositCurrent into a copy of slab (ncomp, ny + 2 ng, nx + 2 ng): comp = slab component per DEP_COMPS entry (-1: not
+    deposited).  Returns (slab, valid, w, n_qsa): the dropped particles lose their valid bit and their weight."""
+    out = np.array(slab, dtype=np.float64)
+    live, dropped, wc, rho, (i0, sx, j0, sy) = deposit_weights(real, valid, ion, slab, ng, geom, q, m, order, max_qsa,
+                                                               can_ionize, aabs)
+    idx = np.nonzero(live)[0]
+    for iy in range(order + 1):
+        for ix in range(order + 1):
+            cd = rho[idx] * sx[idx, ix] * sy[idx, iy]
+            jj, ii = j0[idx] + iy + ng, i0[idx] + ix + ng
+            for k, c in enumerate(comp):
+                if c >= 0:
+                    np.add.at(out[c], (jj, ii), cd * wc[k, idx])
+    v = np.where(dropped, 0, np.asarray(valid)).astype(np.int32)
+    w = np.where(dropped, 0.0, np.asarray(real[2], dtype=np.float64))
+    return out, v, w, int(dropped.sum())
