@@ -30,40 +30,23 @@
 namespace hps {
 
 // 2-D multi-component view in level index space: (i,j,n) -> p[(i+oi) + (j+oj)*js + n*ns]
-// (HPS_MG_OFF32: the element's byte offset in 32-bit arithmetic from the view's base -- global_load / global_store with the
+// (the element's byte offset in 32-bit arithmetic from the view's base -- global_load / global_store with the
 //  base in SGPRs and one offset VGPR instead of a 64-bit address per access: the level-0 passes spend more instructions on
 //  index arithmetic than on fp64; the solver's planes hold at most 2^28 doubles, checked in mg_create)
-#ifndef HPS_MG_OFF32
-#define HPS_MG_OFF32 1
-#endif
-// HPS_MG_BLOCKROWS: a thread's GPAIRS cell pairs sit in GPAIRS consecutive rows of the tile (a 2 x GPAIRS block of cells) instead
+// Block rows (BR in smooth_tile): a thread's GPAIRS cell pairs sit in GPAIRS consecutive rows of the tile (a 2 x GPAIRS block of cells) instead
 // of rows NT/PR apart, and the values it has written last stay in registers: of the four neighbours of a cell it updates, the
 // partner in its pair and the cells above / below inside its block come from registers, not from LDS -- 5 instead of 12 LDS reads
 // per half-sweep and component for GPAIRS = 3.  (The sweeps of the fused level-0 pass ran at 1900 cycles per half-sweep, which is
 // what the LDS pipe carries for two workgroups of 123 KB each.)
 // Measured (round 4): the kernels with GPAIRS = 2 (64 x 32 tiles: the initial level-0 pass 24.4 -> 22.0 us, the level-1 passes
 // 9.1 -> 8.2) gain; the fused 8-sweep level-0 pass (GPAIRS = 3, 128 registers for two workgroups per CU) does not have the 24
-// registers for the values and takes 39.2 instead of 32.2 us: block rows up to HPS_MG_BLOCKROWS_MAXG pairs per thread only.
-#ifndef HPS_MG_BLOCKROWS
-#define HPS_MG_BLOCKROWS 1
-#endif
-// ... and, HPS_MG_BLOCKROWS_INTERIOR, for any number of pairs in the tiles that touch no wall (their path has no wall multipliers
-// and masks in registers)
-#ifndef HPS_MG_BLOCKROWS_INTERIOR
-#define HPS_MG_BLOCKROWS_INTERIOR 1
-#endif
-#ifndef HPS_MG_BLOCKROWS_MAXG
-#define HPS_MG_BLOCKROWS_MAXG 2
-#endif
+// registers for the values and takes 39.2 instead of 32.2 us: block rows up to two pairs per thread only,
+// and for any number of pairs in the tiles that touch no wall (their path has no wall multipliers and masks in registers).
 struct FView {
     double* p; long js, ns; int oi, oj;
     __device__ __forceinline__ double& operator() (int i, int j, int n) const {
-#if HPS_MG_OFF32
         const unsigned o = (unsigned)((i + oi) + (j + oj)*(int)js + n*(int)ns)*8u;
         return *reinterpret_cast<double*>(reinterpret_cast<char*>(p) + o);
-#else
-        return p[(long)(i + oi) + (long)(j + oj)*js + (long)n*ns];
-#endif
     }
 };
 
@@ -97,22 +80,15 @@ struct TileShape {
     static constexpr int GPAIRS = TX*TY/2/NT;                // cell pairs per thread
     static_assert(TX*TY/2 % NT == 0 && NT % 64 == 0 && (PR == 16 || PR == 32), "tile shape");
 };
-#ifndef HPS_MG_BIG
-#define HPS_MG_BIG 64, 32, 512
-#endif
-using TileBig = TileShape<HPS_MG_BIG>;
+using TileBig = TileShape<64, 32, 512>;
 using TileMid = TileShape<32, 32, 256>;
-#ifndef HPS_MG_HUGE
-#define HPS_MG_HUGE 64, 48, 512
-#endif
-using TileHuge = TileShape<HPS_MG_HUGE>;      // the fused 8-sweep pass of level 0 (rim 8: 48 x 32 of 64 x 48 final)
+// (64 x 64 tiles with 512 or 1024 threads and 64 x 32 were measured for this pass: multigrid 0.293 / 0.282 / 0.290 against
+// 0.278 ms per slice; 64 x 96: profiles/r04_mg_level0_tile.txt)
+using TileHuge = TileShape<64, 48, 512>;      // the fused 8-sweep pass of level 0 (rim 8: 48 x 32 of 64 x 48 final)
 // ... of the node-centred hierarchy (2^K - 1 cells per side): on 64 x 48 tiles that pass spills 37 registers under its cap
 // (no fused restriction: the residual planes are stored, the prolongation is bilinear) -- 64 x 32 tiles (two pairs per thread)
 // do not: Bx/By solve at 1023^2 413 -> 391 us per slice (profiles/r05_nodal_multigrid.txt); the cell-centred pass keeps 64 x 48
-#ifndef HPS_MG_HUGE_NODAL
-#define HPS_MG_HUGE_NODAL 64, 32, 512
-#endif
-using TileHugeNodal = TileShape<HPS_MG_HUGE_NODAL>;
+using TileHugeNodal = TileShape<64, 32, 512>;
 template <bool CC> struct HugeTileOf { using type = TileHuge; };
 template <> struct HugeTileOf<false> { using type = TileHugeNodal; };
 using TileSmall = TileShape<32, 16, 256>;
@@ -221,7 +197,7 @@ __device__ __forceinline__ void block_max_to (unsigned long long* slot, double v
     __syncthreads();
 }
 
-// row (within the tile) and pair index of a thread's m-th cell pair (BR: block rows, see HPS_MG_BLOCKROWS)
+// row (within the tile) and pair index of a thread's m-th cell pair (BR: block rows, see the note above FView)
 #define MG_ROWPK(m) const int jj = BR ? (tid / PR)*GPAIRS + (m) : (tid + MG_NT*(m)) / PR, pk = BR ? (tid & (PR - 1)) : (tid + MG_NT*(m)) - jj*PR
 // phi_out = GSRB^4(start), start = 0 | phi_in | phi_in + P(crse);
 // DO_RES: residual r = rhs - L(phi_out), max|r| (and max|rhs|) -> norms;
@@ -240,7 +216,7 @@ __device__ __forceinline__ void smooth_tile (double (&s_phi)[2][TS::AY*TS::AX], 
     constexpr int E = DO_RES ? NSW : NSW - 1;         // rim of the swept tile that is not final
     constexpr int GT_X = TS::TX, GT_Y = TS::TY, GA_X = TS::AX, GA_Y = TS::AY, MG_NT = TS::NT, GPAIRS = TS::GPAIRS, PR = TS::PR;
     constexpr int AXH = GA_X/2, CH = GA_Y*AXH;        // entries per row / per plane of one colour
-    constexpr bool BR = HPS_MG_BLOCKROWS && (GPAIRS <= HPS_MG_BLOCKROWS_MAXG || (INTERIOR && HPS_MG_BLOCKROWS_INTERIOR));
+    constexpr bool BR = GPAIRS <= 2 || INTERIOR;
     const int tid = threadIdx.x;
     const int cpar = (gi0 + gj0) & 1;                 // colour of ringed cell (0, 0) is (gi0 - 1 + gj0 - 1) & 1
     MG_STAMP(0);
@@ -550,10 +526,7 @@ __device__ __forceinline__ void smooth_tile (double (&s_phi)[2][TS::AY*TS::AX], 
 // NSW red-black half-sweeps per launch: 4 (one GSRB^4 of the reference) or 8 (the two consecutive
 // GSRB^4 that end a V-cycle on level 0, fused: one pass over HBM instead of two)
 template <class TS, bool CC, int SRC, bool DO_RES, bool FUSE_R, int NSW = 4, bool RPULL = false>
-#ifndef HPS_MG_NODAL_WAVES
-#define HPS_MG_NODAL_WAVES 4
-#endif
-__global__ __launch_bounds__(TS::NT, (RPULL && TS::GPAIRS > 1) ? 2 : (CC || NSW == 4) ? 4 : HPS_MG_NODAL_WAVES)      // at most 128 VGPRs: two 512-thread workgroups per CU (several variants sit at 113-130); the pulling smoother with two pairs per thread (36 + 36 loads in flight) gets 256
+__global__ __launch_bounds__(TS::NT, (RPULL && TS::GPAIRS > 1) ? 2 : 4)      // at most 128 VGPRs: two 512-thread workgroups per CU (several variants sit at 113-130); the pulling smoother with two pairs per thread (36 + 36 loads in flight) gets 256
 void k_smooth (LevBox b, FView phi_out, FView phi_out2, FView rhs, FView acf, FView phi_in, FView crse, FView res_out,
                FView cres_out, double facx, double facy, int ntx, unsigned long long* resnorm,
                unsigned long long* rhsnorm, StopRule sr)

@@ -56,10 +56,7 @@ static int expl_pad ()
     }
     return pad;
 }
-#ifndef HPS_TILE_HALO
-#define HPS_TILE_HALO 6
-#endif
-constexpr int TILE_HALO = HPS_TILE_HALO;
+constexpr int TILE_HALO = 6;
 
 // optional shader-clock stamps of one workgroup (hps_particles_debug_stamps)
 #ifdef HPS_STAMPS      // diagnostic build only (make stamps): reading the pointer is a dependent trip to memory at the head of the kernel
@@ -138,29 +135,10 @@ constexpr int TAIL_ORIGIN = -(1 << 24);      // "tile origin" of a tail workgrou
 template <int R, int RP = R, int NT = 256, int NC = 6>
 __device__ __forceinline__ void load_region (double* img, const SlabView& f, const int* comps, int nc, int ox, int oy, int tid);
 
-// Row pitch of the deposition's LDS accumulators = R + HPS_DEP_PAD doubles.  The lanes of a wave work on particles of 64
+// Row pitch of the deposition's LDS accumulators = R doubles, unpadded.  The lanes of a wave work on particles of 64
 // consecutive cells (four tile rows at the sort's (rank, cell) order): with pitch 20 the four rows fall on the 32 eight-byte
-// bank slots at offsets 0, 20, 8, 28 -- three rows deep on some slots, one on others; with pitch 48 (HPS_DEP_PAD=28) rows
-// alternate between the two halves of the banks.
-// the explicit deposition in two passes (image particles straight-line, slab particles behind them; 0: one loop with the choice at every stencil cell)
-#ifndef HPS_EXPL_TWO_PASS
-#define HPS_EXPL_TWO_PASS 1
-#endif
-#ifndef HPS_EXPL_ROW_BARRIER
-#define HPS_EXPL_ROW_BARRIER 1
-#endif
-#ifndef HPS_DEP_PAD
-#define HPS_DEP_PAD 0
-#endif
-#ifndef HPS_DEP_FAST_RCP
-#define HPS_DEP_FAST_RCP 0
-#endif
-#ifndef HPS_DEP_NB
-#define HPS_DEP_NB 4
-#endif
-#ifndef HPS_DEP_PIPE
-#define HPS_DEP_PIPE 0
-#endif
+// bank slots at offsets 0, 20, 8, 28 -- three rows deep on some slots, one on others.  Pitch 48 (a pad of 28: rows alternate
+// between the two halves of the banks) was measured: 72.4 -> 70.3 us, 1473 -> 1478 slices/s at 2.4 x the LDS; left at 20.
 // (An XCD-chunked tile order -- contiguous tile runs per XCD -- was measured slower here: 916 vs 953 slices/s.)
 // MASK: compile-time set of deposited components (bit c = DepComps entry c), -1 = decide at run time.
 // With a compile-time set the 9x4 accumulations are straight-line ds_add_f64 with immediate offsets.
@@ -181,7 +159,7 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
         return;
     }
     constexpr int R = TS + 2*TILE_HALO;
-    constexpr int RP = R + HPS_DEP_PAD, PL = RP*R;      // row pitch and plane size of the accumulators (HPS_DEP_PAD, below)
+    constexpr int RP = R, PL = RP*R;      // row pitch (unpadded, see above) and plane size of the accumulators
     // an ionisable species: tiles that hold no charged ion have nothing to deposit (flag written by the species' push)
     if (tile_flag && !tile_flag[offsets[gridDim.x + 2 + blockIdx.x]]) return;
     extern __shared__ __attribute__((aligned(16))) double acc[];     // [active comps][R][RP]
@@ -216,15 +194,12 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
     // of them is processed: the kernel is bound by memory-level parallelism, not by issue slots.
     // The first batch (the whole tile at nominal density) is requested before the accumulators are
     // zeroed, so its HBM latency hides behind the zeroing.
-    // HPS_DEP_PIPE: the next batch is requested while the current one is worked on (the loads of a workgroup then overlap
-    // its own LDS atomics, not only those of the other workgroups of the CU).  Measured with HPS_DEP_NB = 2 and 1 (76 VGPRs,
-    // 6 waves per SIMD instead of 4): 71.0 / 74.8 us against 71.4 -- no gain: on a lattice sheet the kernel moves its 235 MB at
+    // Requesting the next batch while the current one is worked on (the loads of a workgroup then overlap its own LDS
+    // atomics, not only those of the other workgroups of the CU) was measured with NB = 2 and 1 (76 VGPRs, 6 waves per
+    // SIMD instead of 4): 71.0 / 74.8 us against 71.4 -- no gain: on a lattice sheet the kernel moves its 235 MB at
     // 3.9 TB/s (59.9 us, scripts/diag_deposit.py 0.0; a device copy reaches 5.4), behind the driver at 3.3
-    constexpr int NB = HPS_DEP_NB;
+    constexpr int NB = 4;
     Rec rec[NB];
-#if HPS_DEP_PIPE
-    Rec nxt[NB];
-#endif
     const int ipb = lrec.y + tid;
     if (ipb < pend) {
 #pragma unroll
@@ -240,21 +215,10 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
     PT_STAMP(1);
 
     for (int ip0 = ipb; ip0 < pend; ip0 += 256*NB) {
-#if HPS_DEP_PIPE
-      if (ip0 != ipb) {
-#pragma unroll
-        for (int u = 0; u < NB; ++u) rec[u] = nxt[u];
-      }
-      if (ip0 + 256*NB < pend) {
-#pragma unroll
-        for (int u = 0; u < NB; ++u) nxt[u] = fetch(min(ip0 + 256*NB + 256*u, pend - 1));
-      }
-#else
       if (ip0 != ipb) {
 #pragma unroll
         for (int u = 0; u < NB; ++u) rec[u] = fetch(min(ip0 + 256*u, pend - 1));
       }
-#endif
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
         const int ip = ip0 + 256*u;
@@ -262,13 +226,9 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
         const Rec cur = rec[u];
         const uint64_t id = cur.id;
         if (!(id & HPS_ID_VALID)) continue;
-#if HPS_DEP_FAST_RCP
-        // v_rcp_f64 + one Newton step (as the push: particle_math.h fast_rcp) instead of the IEEE division's eleven
-        // instructions; psi = 0 must still give the inf the QSA test below drops the particle on (Newton would make it a NaN)
-        const double psi_inv = cur.psi != 0.0 ? fast_rcp(cur.psi) : __builtin_huge_val();
-#else
-        const double psi_inv = 1.0/cur.psi;      // (IEEE: the QSA test below must see inf for psi = 0)
-#endif
+        // (IEEE: the QSA test below must see inf for psi = 0.  v_rcp_f64 + one Newton step, as the push's fast_rcp, with
+        // psi = 0 mapped to inf by hand was measured: 69.0 against 69.2 us per launch, no gain)
+        const double psi_inv = 1.0/cur.psi;
         const double vx_c = cur.ux*psi_inv;
         const double vy_c = cur.uy*psi_inv;
         double q_invvol = k.a*cur.w;
@@ -422,7 +382,6 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
     }
     __syncthreads();
 
-#if HPS_EXPL_TWO_PASS
     // Two passes over the workgroup's particles.  The first deposits every particle whose stencil lies inside the tile's image --
     // all but one in ten thousand -- through LDS, as straight-line code: the choice "image or slab" is made once per particle, not
     // at each of its 21 stencil cells (84 exec-mask branches per particle before; hoisting them was tried in round 2 and spilled,
@@ -430,6 +389,7 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
     // in flight, as in the push).  The second pass, entered only by a workgroup that met such a particle (or a tail workgroup),
     // fetches the sheet again and deposits the others through the slab.  Per row the products with sy / dsy are formed once:
     //   Sy += sx (sy ty + a6 dsy) + (a5 sy) dsx     (14 instead of 17 fp64 operations per inner cell, 2 instead of 3 on the ring)
+    // (One loop with "image or slab" chosen at every stencil cell and 17 operations per cell: 96.1 against 89.4 us.)
     int nfb = 0;
     bool slow = false;
     auto one = [&] (const Rec& cur, auto LC) __attribute__((always_inline)) -> bool {
@@ -464,6 +424,9 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
         }
         const double qp = q_mass*psi_inv;
         const double vxvy = vx*vy, gy = gp - vy*vy, gx = gp - vx*vx;
+        // the source terms of ExplicitDeposition.cpp:225-252 are linear in the cached fields and in the (derivative)
+        // shapes: collect the per-particle coefficients once,
+        //   Sy += ss*(a1 Bz + a2 Ez + a3 ExmBy + a4 EypBx) + a5 dxs + a6 sdy,   Sx likewise with b1..b6
         const double cq = cdm*qp, cqc = cq*k.c_inv, cc = cdm*k.c;
         const double a1 = cq*vx, a2 = -cqc*vy, a3 = cqc*vxvy, a4 = -cqc*gy, a5 = cc*vxvy, a6 = -cc*(gy - 1.0);
         const double b1 = cq*vy, b2 = cqc*vx, b3 = cqc*gx, b4 = -cqc*vxvy, b5 = cc*(gx - 1.0), b6 = -cc*vxvy;
@@ -471,9 +434,9 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
         for (int m = 0; m < NS; ++m) { dsx[m] *= k.dx_inv; dsy[m] *= k.dy_inv; }
 #pragma unroll
         for (int iy = 0; iy < NS; ++iy) {
-#if HPS_EXPL_ROW_BARRIER
             if constexpr (LOCAL) asm volatile("" ::: "memory");      // one stencil row of LDS reads in flight at a time
-#endif
+            // centred-derivative shapes (DT == 2): the plain shape vanishes on the outer ring of the stencil (s[0] = s[NS-1] = 0
+            // for every order), so there the cached fields do not enter at all: no LDS reads for 12 of the 21 cells (order 2)
             const bool yedge = (DT == 2) && (iy == 0 || iy == NS - 1);
             const double a5s = a5*sy[iy], b5s = b5*sy[iy], ay = a6*dsy[iy], by = b6*dsy[iy];
 #pragma unroll
@@ -526,119 +489,7 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
 #pragma unroll 1
         for (int ip = ipb; ip < pend; ip += 256) { const Rec cur = fetch(ip); (void)one(cur, std::false_type{}); }
     }
-#else
-    int nfb = 0;
-#ifdef HPS_DIAG_EXPL_NO_ATOMICS
-    double diag_sink = 0.0;
-#endif
-    for (int ip = ipb; ip < pend; ip += 256) {
-        const Rec cur = nxt;
-        if (ip + 256 < pend) nxt = fetch(ip + 256);
-        if (!(cur.id & HPS_ID_VALID)) continue;
-        if (k.can_ionize && cur.ion == 0) continue;      // a neutral atom deposits nothing (every term carries its level)
-        const double psi_inv = fast_rcp(cur.psi);
-        const double vx = cur.ux*psi_inv*k.c_inv;
-        const double vy = cur.uy*psi_inv*k.c_inv;
-        double q_invvol_mu0 = k.a, q_mass = k.b;
-        if (k.can_ionize) { const double il = (double)cur.ion; q_invvol_mu0 *= il; q_mass *= il; }
-        const double cdm = q_invvol_mu0*cur.w;
-        const double xmid = (cur.x - k.xoff)*k.dx_inv;
-        const double ymid = (cur.y - k.yoff)*k.dy_inv;
-        double sx[NS], dsx[NS], sy[NS], dsy[NS];
-        int i0, j0;
-        if constexpr (DT == 2) { i0 = centred_weights<ORDER>(xmid, sx, dsx); j0 = centred_weights<ORDER>(ymid, sy, dsy); }
-        else                   { i0 = nodal_weights<ORDER>(xmid, sx, dsx);   j0 = nodal_weights<ORDER>(ymid, sy, dsy); }
-        const int li = i0 - ox, lj = j0 - oy;
-        // the whole stencil, and with a laser also the ring around its inner cells (the gradient of |a|^2), inside the image
-        const bool local = LASER ? (li >= 1 && li + NS + 1 <= R && lj >= 1 && lj + NS + 1 <= R)
-                                 : (li >= 0 && li + NS <= R && lj >= 0 && lj + NS <= R);
-        double gp;
-        if constexpr (LASER) {
-            double lx[ORDER + 1], ly[ORDER + 1];
-            const int ai = shape_weights<ORDER>(xmid, lx), aj = shape_weights<ORDER>(ymid, ly);
-            const double A = (local ? laser_gather_lds<ORDER>(aimg, RP, ai - ox, aj - oy, lx, ly)
-                                    : laser_gather<ORDER>(f, k.aabs, xmid, ymid))*k.laser_fac*q_mass*q_mass;
-            gp = 0.5*((1.0 + 0.5*A)*psi_inv*psi_inv + vx*vx + vy*vy + 1.0);
-        } else {
-            gp = 0.5*(psi_inv*psi_inv + vx*vx + vy*vy + 1.0);
-        }
-        const double qp = q_mass*psi_inv;
-        const double vxvy = vx*vy, gy = gp - vy*vy, gx = gp - vx*vx;
-        // the source terms of ExplicitDeposition.cpp:225-252 are linear in the cached fields and in the
-        // (derivative) shapes: collect the per-particle coefficients once,
-        //   Sy += ss*(a1 Bz + a2 Ez + a3 ExmBy + a4 EypBx) + a5 dxs + a6 sdy,   Sx likewise with b1..b6,
-        // 17 fp64 operations per stencil cell instead of 30
-        const double cq = cdm*qp, cqc = cq*k.c_inv, cc = cdm*k.c;
-        const double a1 = cq*vx, a2 = -cqc*vy, a3 = cqc*vxvy, a4 = -cqc*gy, a5 = cc*vxvy, a6 = -cc*(gy - 1.0);
-        const double b1 = cq*vy, b2 = cqc*vx, b3 = cqc*gx, b4 = -cqc*vxvy, b5 = cc*(gx - 1.0), b6 = -cc*vxvy;
-#pragma unroll
-        for (int m = 0; m < NS; ++m) { dsx[m] *= k.dx_inv; dsy[m] *= k.dy_inv; }
-        if (!local && !tail) ++nfb;
-#pragma unroll
-        for (int iy = 0; iy < NS; ++iy) {
-#pragma unroll
-            for (int ix = 0; ix < NS; ++ix) {
-                // centred-derivative shapes (DT == 2): the plain shape vanishes on the outer ring of the stencil
-                // (s[0] = s[NS-1] = 0 for every order), so there the cached fields do not enter at all -- only one of the
-                // two derivative terms does: no LDS reads for 12 of the 21 cells (order 2)
-                const bool xedge = (DT == 2) && (ix == 0 || ix == NS - 1), yedge = (DT == 2) && (iy == 0 || iy == NS - 1);
-                if (xedge && yedge) continue;
-                const bool ring = xedge || yedge;
-                double* gp_ = nullptr; int ls = 0;
-                if (local) ls = (lj + iy)*RP + li + ix;
-                else       gp_ = f.p + f.off(i0 + ix, j0 + iy);
-                double sy_add, sx_add;
-                if (ring) {
-                    // xedge: sx = 0 -> only dsx*sy survives; yedge: sy = 0 -> only sx*dsy
-                    const double dd = xedge ? dsx[ix]*sy[iy] : sx[ix]*dsy[iy];
-                    sy_add = (xedge ? a5 : a6)*dd;
-                    sx_add = (xedge ? b5 : b6)*dd;
-                } else {
-                    double Bz, Ez, ExmBy, EypBx;
-#ifdef HPS_DIAG_EXPL_NO_READS      // (diagnostic build: what the kernel costs without its field reads; results are wrong)
-                    if (local) { Bz = 1.0 + ls; Ez = 2.0; ExmBy = 3.0; EypBx = 4.0; }
-#else
-                    if (local) { Bz = lds_get(img + ls); Ez = lds_get(img + PL + ls); ExmBy = lds_get(img + 2*PL + ls); EypBx = lds_get(img + 3*PL + ls); }
-#endif
-                    else       { Bz = gp_[cBz*f.ns]; Ez = gp_[cEz*f.ns]; ExmBy = gp_[cExmBy*f.ns]; EypBx = gp_[cEypBx*f.ns]; }
-                    const double ss = sx[ix]*sy[iy];
-                    const double dxs = dsx[ix]*sy[iy];
-                    const double sdy = sx[ix]*dsy[iy];
-                    double ty = fma(a1, Bz, fma(a2, Ez, fma(a3, ExmBy, a4*EypBx)));
-                    double tx = fma(b1, Bz, fma(b2, Ez, fma(b3, ExmBy, b4*EypBx)));
-                    if constexpr (LASER) {
-                        // gradient of |a|^2 at this stencil cell (ExplicitDeposition.cpp:211-226), from the slab
-                        if (ss != 0.0) {
-                            const double lf = 0.25*cq*qp*k.laser_fac*k.c;
-                            double ady, adx;
-                            if (local) {
-                                const double* a = aimg + ls;
-                                ady = lds_get(a + RP) - lds_get(a - RP); adx = lds_get(a + 1) - lds_get(a - 1);
-                            } else {
-                                const double* a = f.p + k.aabs*f.ns + f.off(i0 + ix, j0 + iy);
-                                ady = a[f.js] - a[-f.js]; adx = a[1] - a[-1];
-                            }
-                            ty = fma(lf*0.5*k.dy_inv, ady, ty);
-                            tx = fma(-lf*0.5*k.dx_inv, adx, tx);
-                        }
-                    }
-                    sy_add = fma(ss, ty, fma(a5, dxs, a6*sdy));
-                    sx_add = fma(ss, tx, fma(b5, dxs, b6*sdy));
-                }
-#ifdef HPS_DIAG_EXPL_NO_ATOMICS    // (diagnostic build: without the LDS atomics; results are wrong)
-                if (local) { diag_sink += sy_add + sx_add; }
-#else
-                if (local) { lds_add(acc + ls, sy_add); lds_add(acc + PL + ls, sx_add); }
-#endif
-                else       { atomic_add_f64(gp_ + cSy*f.ns, sy_add); atomic_add_f64(gp_ + cSx*f.ns, sx_add); }
-            }
-        }
-    }
-#endif
     if (n_fallback && nfb) atomicAdd(n_fallback, nfb);
-#ifdef HPS_DIAG_EXPL_NO_ATOMICS
-    if (diag_sink == 1.2345e-300 && n_fallback) atomicAdd(n_fallback, 1);
-#endif
     __syncthreads();
 #ifdef HPS_DIAG_EXPL_NO_FLUSH
     if (acc[tid] == 1.2345e-300 && n_fallback) atomicAdd(n_fallback, 1);
@@ -660,52 +511,17 @@ template <class T> __device__ __forceinline__ T ldo (const T* base, unsigned o) 
 template <class T> __device__ __forceinline__ void sto (T* base, unsigned o, T v) { *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + o) = v; }
 // the same with the non-temporal hint (global_load / global_store ... nt): for arrays only this kernel touches -- the
 // half-step momenta -- so that they do not push what the next deposition reads (x, y, w, ux, uy, psi) out of the caches
-#ifndef HPS_PUSH_NT
-#define HPS_PUSH_NT 1
-#endif
-template <class T> __device__ __forceinline__ T ldo_nt (const T* base, unsigned o)
-{
-#if HPS_PUSH_NT
-    return __builtin_nontemporal_load(reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + o));
-#else
-    return ldo(base, o);
-#endif
-}
-template <class T> __device__ __forceinline__ void sto_nt (T* base, unsigned o, T v)
-{
-#if HPS_PUSH_NT
-    __builtin_nontemporal_store(v, reinterpret_cast<T*>(reinterpret_cast<char*>(base) + o));
-#else
-    sto(base, o, v);
-#endif
-}
+template <class T> __device__ __forceinline__ T ldo_nt (const T* base, unsigned o) { return __builtin_nontemporal_load(reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + o)); }
+template <class T> __device__ __forceinline__ void sto_nt (T* base, unsigned o, T v) { __builtin_nontemporal_store(v, reinterpret_cast<T*>(reinterpret_cast<char*>(base) + o)); }
 
 // IONIZE: the species can be field-ionised (ADK, ionization.hip).  The decision needs exactly the fields the push gathers,
 // so it is taken here, between the gather and the push (the reference ionises, then pushes: Hipace.cpp:693-701): the ion's
 // level goes up, its electron is appended to the product species, and the push runs with the new charge.  A neutral
 // atom at rest is not pushed at all (zero charge: the push would leave every quantity as it is).
-// the six sub-steps of a particle through taylor2_substep_pre (particle_math.h; 0: taylor2_substep, the dual-number form)
-#ifndef HPS_PUSH_ALGEBRA
-#define HPS_PUSH_ALGEBRA 1
-#endif
-#ifndef HPS_PUSH_GATHER_PIPE
-#define HPS_PUSH_GATHER_PIPE 0
-#endif
-#ifndef HPS_PUSH_SPLIT_GATHER
-#define HPS_PUSH_SPLIT_GATHER 1
-#endif
-#ifndef HPS_PUSH_W3
-#define HPS_PUSH_W3 1
-#endif
-#ifndef HPS_PUSH_WAVES
-#define HPS_PUSH_WAVES 3
-#endif
-#ifndef HPS_PUSH_WAVES_ION
-#define HPS_PUSH_WAVES_ION 2
-#endif
-#ifndef HPS_PUSH_PF_LASER
-#define HPS_PUSH_PF_LASER 1
-#endif
+// The six sub-steps of a particle go through taylor2_substep_pre (particle_math.h: the field products hoisted, the zeta
+// derivative written out by hand, 42 instead of the dual-number form's 62 fp64 instructions each: 142 -> 132.5 us).
+// Three waves per SIMD (168 VGPRs), two for an ionisable species; at four (128 VGPRs) the kernel spilled 36 registers,
+// 148 B of scratch per lane: 240.8 against 134 us.
 // VBP: the engine's own electron sheet -- a particle is valid iff its psi_half is not 0 (Tiling::valid_by_psi: every path that
 // clears the valid bit of idcpu also zeroes psi_half, which only the push reads): idcpu is not read, 40 instead of 48 B in per
 // particle in the one particle kernel that is bound by its bytes.
@@ -717,7 +533,7 @@ template <class T> __device__ __forceinline__ void sto_nt (T* base, unsigned o, 
 // next slice would fetch), and the next slice needs no deposition launch.  Static beam, no laser, no ionisable species.
 struct DepTail { DepComps cm; double a, b, max_qsa; int* n_qsa; };
 template <int ORDER, int TS, bool LASER = false, bool IONIZE = false, bool VBP = false, int DEP = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IONIZE ? HPS_PUSH_WAVES_ION : HPS_PUSH_WAVES)))
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(IONIZE ? 2 : 3)))
 void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets, int ntx,
                       int cPsi, int cEz, int cBx, int cBy, int cBz, PartConsts k, int* n_fallback, IonArgs ia, const int* go, TailWork tw, MgPost mp,
                       DepTail dt)
@@ -770,16 +586,11 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
         return q;
     };
     // the thread's first particle is requested ahead of the field image: its six values arrive with the image's
-    // (HPS_PUSH_PF_LASER=0: the laser variant without the prefetch -- 12 instead of 20 B of scratch per lane under the
-    // 168-register cap, and slower: config 5 946 against 968 slices/s)
-#ifndef HPS_PUSH_NO_PREFETCH
-    constexpr bool PF = HPS_PUSH_PF_LASER || !LASER;
-#else
-    constexpr bool PF = false;
-#endif
+    // (the laser variant without this prefetch was measured: 12 instead of 20 B of scratch per lane under the 168-register
+    // cap, and slower: config 5 946 against 968 slices/s)
     unsigned ip = (unsigned)lrec.y + tid;
     PIn nxt{0, 0.0, 0.0, 0.0, 0.0, 1.0};
-    if constexpr (PF) { if (ip < pend) nxt = fetch(ip); }
+    if (ip < pend) nxt = fetch(ip);
     const int cc[5] = {cPsi, cEz, cBx, cBy, cBz};
     load_region<R, R, 256, 5>(img, f, cc, 5, ox, oy, tid);
     double* aimg = img + 5*R*R;           // LASER: |a|^2 over the tile region
@@ -797,9 +608,8 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
     // pass otherwise keeps a 64-bit pointer per array and iteration in VGPRs, 24 registers here).
     for (; ip < pend; ip += 256) {
         __builtin_assume(ip < (1u << 28));
-        PIn cur;
-        if constexpr (PF) { cur = nxt; if (ip + 256 < pend) nxt = fetch(ip + 256); }
-        else cur = fetch(ip);               // one batch of six loads, one trip to memory per particle
+        const PIn cur = nxt;
+        if (ip + 256 < pend) nxt = fetch(ip + 256);
         const unsigned o8 = ip*8u;
         const uint64_t id = cur.id;
         if (!(id & HPS_ID_VALID)) continue;
@@ -811,7 +621,7 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
             double xp = isc == 0 ? cur.xp : ldo(pl.x_prev, o8);
             double yp = isc == 0 ? cur.yp : ldo(pl.y_prev, o8);
             double sx[NS], dsx[NS], sy[NS], dsy[NS];
-            constexpr bool W3 = HPS_PUSH_W3 && ORDER == 2 && HPS_PUSH_SPLIT_GATHER && !HPS_PUSH_GATHER_PIPE;
+            constexpr bool W3 = ORDER == 2;
             double pxw[3] = {0.0, 0.0, 0.0}, pyw[3] = {0.0, 0.0, 0.0}; bool xhw = false, yhw = false;
             int i0, j0;
             if constexpr (W3) {      // the three plain weights and their offset straight from the polynomial (common.h)
@@ -826,72 +636,19 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
             if (!local && !tail) ++nfb;
             Fld F{0, 0, 0, 0, 0, 0};
             if (local) {
-                // tensor-product gather: x sums per stencil row, then one y weight per row and component
-                // (reading only the (NS-1) x (NS-1) cells on which the plain weights of Ez, Bx, By, Bz are non-zero -- one
-                // of s[0], s[NS-1] is always exactly 0 -- was measured: 52 instead of 80 LDS reads per particle, but the
-                // lane-dependent base address costs more than the reads save: 171 against 166 us)
+                // tensor-product gather: x sums per stencil row, then one y weight per row and component.
                 const double* b = img + lj*R + li;
-#if HPS_PUSH_SPLIT_GATHER
                 // Psi needs all NS x NS cells (its derivative weights are full); Ez, Bx, By, Bz only the (NS-1) x (NS-1) cells on
                 // which the plain weights live: one of s[0], s[NS-1] is exactly 0, which one depends on the particle's half of
                 // its cell -- 16 + 4 x 9 = 52 LDS reads per particle instead of 80 (order 2), 416 instead of 640 B through the LDS
                 // pipe, 88 instead of 120 FMAs; the skipped terms are exact zeros.  (Round 3 measured this slower, 171 against
-                // 166 us, when the kernel still waited for three dependent trips to memory per particle.)
-#if HPS_PUSH_GATHER_PIPE
-                // the LDS reads of a row are requested one step ahead of the arithmetic that uses the previous ones: Psi's NS x NS
-                // cells and the first row of the plain fields are in flight together, then row k + 1 while row k is summed.
-                // Measured (round 4, call 18): 20 registers spilled under the 168 cap (11 without the particle prefetch):
-                // 168.6 / 135 against 131.5 us -- the kernel has no registers left for more reads in flight.  Off.
-                const bool xhi = !(sx[NS - 1] == 0.0), yhi = !(sy[NS - 1] == 0.0);
-                const double* bq = b + R*R + (yhi ? R : 0) + (xhi ? 1 : 0);
-                double vp[NS][NS];
-#pragma unroll
-                for (int iy = 0; iy < NS; ++iy)
-#pragma unroll
-                    for (int ix = 0; ix < NS; ++ix) vp[iy][ix] = lds_get(b + iy*R + ix);
-                double vq[2][4][NS - 1];
-                auto req = [&] (int ky, int slot) __attribute__((always_inline)) {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-#pragma unroll
-                        for (int kx = 0; kx < NS - 1; ++kx) vq[slot][c][kx] = lds_get(bq + c*R*R + ky*R + kx);
-                };
-                req(0, 0);
-                asm volatile("" ::: "memory");
+                // 166 us, when the kernel still waited for three dependent trips to memory per particle: the lane-dependent base
+                // address then cost more than the reads saved.)
+                // Requesting the LDS reads of a row one step ahead of the arithmetic on the previous one (Psi's NS x NS cells and
+                // the first row of the plain fields in flight together) was measured in round 4: 20 registers spilled under the
+                // 168 cap (11 without the particle prefetch): 168.6 / 135 against 131.5 us -- no registers left for more reads in flight.
 #pragma unroll
                 for (int iy = 0; iy < NS; ++iy) {
-                    double rp = 0.0, rd = 0.0;
-#pragma unroll
-                    for (int ix = 0; ix < NS; ++ix) { rp = fma(sx[ix], vp[iy][ix], rp); rd = fma(dsx[ix], vp[iy][ix], rd); }
-                    F.ExmBy = fma(sy[iy], rd, F.ExmBy);
-                    F.EypBx = fma(dsy[iy], rp, F.EypBx);
-                }
-                double px[NS - 1], py[NS - 1];
-#pragma unroll
-                for (int m = 0; m < NS - 1; ++m) { px[m] = xhi ? sx[m + 1] : sx[m]; py[m] = yhi ? sy[m + 1] : sy[m]; }
-#pragma unroll
-                for (int ky = 0; ky < NS - 1; ++ky) {
-                    if (ky + 1 < NS - 1) req(ky + 1, (ky + 1) & 1);
-                    asm volatile("" ::: "memory");
-                    double rez = 0.0, rbx = 0.0, rby = 0.0, rbz = 0.0;
-#pragma unroll
-                    for (int kx = 0; kx < NS - 1; ++kx) {
-                        rez = fma(px[kx], vq[ky & 1][0][kx], rez);
-                        rbx = fma(px[kx], vq[ky & 1][1][kx], rbx);
-                        rby = fma(px[kx], vq[ky & 1][2][kx], rby);
-                        rbz = fma(px[kx], vq[ky & 1][3][kx], rbz);
-                    }
-                    F.Ez  = fma(py[ky], rez, F.Ez);
-                    F.Bxc = fma(py[ky], rbx, F.Bxc);
-                    F.Byc = fma(py[ky], rby, F.Byc);
-                    F.Bz  = fma(py[ky], rbz, F.Bz);
-                }
-#else
-#pragma unroll
-                for (int iy = 0; iy < NS; ++iy) {
-#ifdef HPS_PUSH_PSI_BARRIER
-                    asm volatile("" ::: "memory");
-#endif
                     double rp = 0.0, rd = 0.0;
 #pragma unroll
                     for (int ix = 0; ix < NS; ++ix) {
@@ -912,7 +669,7 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
                 const double* bq = b + R*R + (yhi ? R : 0) + (xhi ? 1 : 0);
 #pragma unroll
                 for (int ky = 0; ky < NS - 1; ++ky) {
-                    asm volatile("" ::: "memory");
+                    asm volatile("" ::: "memory");      // one stencil row of LDS reads in flight at a time
                     double rez = 0.0, rbx = 0.0, rby = 0.0, rbz = 0.0;
 #pragma unroll
                     for (int kx = 0; kx < NS - 1; ++kx) {
@@ -927,37 +684,6 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
                     F.Byc = fma(py[ky], rby, F.Byc);
                     F.Bz  = fma(py[ky], rbz, F.Bz);
                 }
-#endif
-#else
-#ifndef HPS_PUSH_ROLLED_ROWS
-#pragma unroll
-#else
-#pragma unroll 1
-#endif
-                for (int iy = 0; iy < NS; ++iy) {
-#ifndef HPS_PUSH_ROLLED_ROWS
-                    asm volatile("" ::: "memory");      // one stencil row of LDS reads in flight at a time
-#endif
-                    double rp = 0.0, rd = 0.0, rez = 0.0, rbx = 0.0, rby = 0.0, rbz = 0.0;
-#pragma unroll
-                    for (int ix = 0; ix < NS; ++ix) {
-                        const int ls = iy*R + ix;
-                        const double psi_c = lds_get(b + ls);
-                        rp = fma(sx[ix], psi_c, rp);
-                        rd = fma(dsx[ix], psi_c, rd);
-                        rez = fma(sx[ix], lds_get(b + R*R + ls), rez);
-                        rbx = fma(sx[ix], lds_get(b + 2*R*R + ls), rbx);
-                        rby = fma(sx[ix], lds_get(b + 3*R*R + ls), rby);
-                        rbz = fma(sx[ix], lds_get(b + 4*R*R + ls), rbz);
-                    }
-                    F.ExmBy = fma(sy[iy], rd, F.ExmBy);
-                    F.EypBx = fma(dsy[iy], rp, F.EypBx);
-                    F.Ez  = fma(sy[iy], rez, F.Ez);
-                    F.Bxc = fma(sy[iy], rbx, F.Bxc);
-                    F.Byc = fma(sy[iy], rby, F.Byc);
-                    F.Bz  = fma(sy[iy], rbz, F.Bz);
-                }
-#endif
                 F.ExmBy *= k.dx_inv;
                 F.EypBx *= k.dy_inv;
             } else {
@@ -1010,20 +736,10 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
             }
             const double dz = k.dz, sdz = dz*0.25;
             double ux = isc == 0 ? cur.uxh : ldo(pl.ux_half, o8), uy = isc == 0 ? cur.uyh : ldo(pl.uy_half, o8), psi = isc == 0 ? cur.psih : ldo(pl.psi_half, o8);
-#if HPS_PUSH_ALGEBRA
             const PushForce PFc = push_force(F, Lf, k.c_inv, qmc);
             const double h2 = 0.5*sdz*sdz;
 #pragma unroll 1
             for (int s = 0; s < 4; ++s) taylor2_substep_pre<LASER>(ux, uy, psi, PFc, sdz, h2);
-#else
-            if constexpr (LASER) {
-#pragma unroll 1
-                for (int s = 0; s < 4; ++s) taylor2_substep_laser(ux, uy, psi, F, Lf, k.c_inv, qmc, sdz);
-            } else {
-#pragma unroll 1
-                for (int s = 0; s < 4; ++s) taylor2_substep(ux, uy, psi, F, k.c_inv, qmc, sdz);
-            }
-#endif
             const double pinv = fast_rcp(psi);
             xp += dz*k.c_inv*(ux*pinv);
             yp += dz*k.c_inv*(uy*pinv);
@@ -1040,18 +756,8 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
                 if (pl.x_prev != pl.x) sto(pl.x_prev, o8, xp);      // (aliased by the engine: already stored)
                 if (pl.y_prev != pl.y) sto(pl.y_prev, o8, yp);
             }
-#if HPS_PUSH_ALGEBRA
 #pragma unroll 1
             for (int s = 0; s < 2; ++s) taylor2_substep_pre<LASER>(ux, uy, psi, PFc, sdz, h2);
-#else
-            if constexpr (LASER) {
-#pragma unroll 1
-                for (int s = 0; s < 2; ++s) taylor2_substep_laser(ux, uy, psi, F, Lf, k.c_inv, qmc, sdz);
-            } else {
-#pragma unroll 1
-                for (int s = 0; s < 2; ++s) taylor2_substep(ux, uy, psi, F, k.c_inv, qmc, sdz);
-            }
-#endif
             sto(pl.ux, o8, ux); sto(pl.uy, o8, uy); sto(pl.psi, o8, psi);
         }
     }
@@ -1353,7 +1059,7 @@ int deposit_current_tiled (const hps_slab& slab, const hps_plasma& pl, const hps
         // (kernel variants exist for the hot component sets without a laser; the tail's released electrons keep idcpu)
         k.valid_by_w = valid_by_w && !tw.nwg && aabs_comp < 0 && (m == 51 || m == 3); }
     const int R = T->g.ts + 2*TILE_HALO;
-    const size_t lds = ((size_t)na*R*(R + HPS_DEP_PAD) + (aabs_comp >= 0 ? (size_t)R*R : 0))*sizeof(double);
+    const size_t lds = ((size_t)na*R*R + (aabs_comp >= 0 ? (size_t)R*R : 0))*sizeof(double);
     SlabView f(slab);
     int mask = 0; for (int c = 0; c < 6; ++c) mask |= (comp[c] >= 0) << c;
 #define CALLM(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M>, lds)) return e; HPS_RECORD("k_deposit_tiled", O, S, M, 0, 0); \

@@ -171,9 +171,6 @@ __device__ __forceinline__ void load_row_pairs_src (lds_double* cbuf, const DstA
     }
 }
 
-#ifndef HPS_PRE_B128
-#define HPS_PRE_B128 1
-#endif
 // Z entries of both rows of a pair -> W[p] and W[N-p] (registers), rows read from LDS
 template <int T, int N, int PP, int NT = 256>
 __device__ __forceinline__ void pre_to_regs (const lds_double* cbuf, int tid, double (&wr)[T][PP], double (&wi)[T][PP],
@@ -186,17 +183,10 @@ __device__ __forceinline__ void pre_to_regs (const lds_double* cbuf, int tid, do
             const int p = tid + NT*m;
             wr[t][m] = wi[t][m] = vr[t][m] = vi[t][m] = 0.0;
             if (p <= N/2) {
-#if HPS_PRE_B128
                 // three 16-byte reads (lanes 32 B apart: 2-way bank conflicts) instead of six 8-byte ones (4-way)
                 auto gc = [&] (int j) { return ldc(cbuf, t*N + j); };
                 const double2 e1 = odd_ext2(2*p + 1, N, gc), e0 = odd_ext2(2*p - 1, N, gc), e2 = odd_ext2(2*p, N, gc);
                 const double are = e1.x - e0.x, aim = e2.x, bre = e1.y - e0.y, bim = e2.y;
-#else
-                auto ga = [&] (int j) { return (double)cbuf[2*(t*N + j)]; };
-                auto gb = [&] (int j) { return (double)cbuf[2*(t*N + j) + 1]; };
-                const double are = odd_ext(2*p + 1, N, ga) - odd_ext(2*p - 1, N, ga), aim = odd_ext(2*p, N, ga);
-                const double bre = odd_ext(2*p + 1, N, gb) - odd_ext(2*p - 1, N, gb), bim = odd_ext(2*p, N, gb);
-#endif
                 wr[t][m] = are - bim; wi[t][m] = aim + bre;      // W[p]
                 vr[t][m] = are + bim; vi[t][m] = bre - aim;      // W[N-p]
             }
@@ -271,16 +261,13 @@ __device__ __forceinline__ int pow2_pos (int k)
 // apart: 16 lanes of a ds_read_b128 on the same four banks.  With the base-4 digits a0..a4 of the index, the low two digits are
 // stored as (a1 ^ a2 ^ a3, a0 ^ a2 ^ a4): every access pattern of the kernel -- natural order, the five passes, the digit-reversed
 // reads -- then varies the stored low digits over all 16 values within 16 consecutive lanes.
-#ifndef HPS_DSTP_SWIZZLE
-#define HPS_DSTP_SWIZZLE 1
-#endif
 template <int LOGN>
 __device__ __forceinline__ int pow2_swz (int i)
 {
-    if constexpr (LOGN == 10 && HPS_DSTP_SWIZZLE) {
+    if constexpr (LOGN == 10) {
         const int a2 = (i >> 4) & 3, a3 = (i >> 6) & 3, a4 = (i >> 8) & 3;
         return i ^ (((a2 ^ a3) << 2) | (a2 ^ a4));
-    } else if constexpr (LOGN == 9 && HPS_DSTP_SWIZZLE) {
+    } else if constexpr (LOGN == 9) {
         // N = 4^4 * 2 (quarter spans 128, 32, 8, 2, then the radix-2 pass; digit-reversed reads vary bits 5..8): by bits b4..b8
         const int b4 = (i >> 4) & 1, b5 = (i >> 5) & 1, b6 = (i >> 6) & 1, b7 = (i >> 7) & 1, b8 = (i >> 8) & 1;
         return i ^ ((b4 ^ b7) | ((b4 ^ b8) << 1) | (b5 << 2) | ((b5 ^ b6) << 3));
@@ -386,13 +373,7 @@ __device__ __forceinline__ void post_store_map (const lds_double* cbuf, const Ds
 }
 template <int LOGN> struct Pow2Pos { static __device__ __forceinline__ int at (int q) { return pow2_swz<LOGN>(pow2_pos<LOGN>(q)); } };
 
-#ifndef HPS_DSTP_T
-#define HPS_DSTP_T 2
-#endif
-#ifndef HPS_DSTP_NT
-#define HPS_DSTP_NT 256
-#endif
-constexpr int DSTP_T = HPS_DSTP_T, DSTP_NT = HPS_DSTP_NT;      // row pairs and threads per workgroup of the power-of-two kernel
+constexpr int DSTP_T = 2, DSTP_NT = 256;      // row pairs and threads per workgroup of the power-of-two kernel
 // SRC: the rows are formed from other planes while they are loaded (DstArgs::sp / sq / sc, as k_dst_rows_sym<.., true>)
 template <int LOGN, bool SRC = false>
 __global__ __launch_bounds__(DSTP_NT)
@@ -448,21 +429,9 @@ void k_dst_rows_pow2 (DstArgs a)
 //   X_0 = x_0 + sum_n s_n,   X_k = x_0 + P_k + i Q_k,   X_{M-k} = x_0 + P_k - i Q_k   (k = 1..H)
 //   P_k = sum_{n=1..H} s_n cos(2 pi n k / M),   Q_k = sum_{n=1..H} d_n sin(2 pi n k / M)
 // i.e. M^2 real FMAs per DFT instead of 4 M^2, with one (cos, sin) table read per 4 FMAs.
-#ifndef HPS_SYM_UNROLL
-#define HPS_SYM_UNROLL 2
-#endif
-#ifndef HPS_DSTS_T
-#define HPS_DSTS_T 3
-#endif
-#ifndef HPS_DSTS_NT
-#define HPS_DSTS_NT 512
-#endif
-constexpr int DSTS_T = HPS_DSTS_T;
-constexpr int DSTS_NT = HPS_DSTS_NT;        // threads per workgroup of the symmetric kernel
+constexpr int DSTS_T = 3;
+constexpr int DSTS_NT = 512;        // threads per workgroup of the symmetric kernel
 
-#ifndef HPS_SYM_LEFTOVER
-#define HPS_SYM_LEFTOVER 1
-#endif
 constexpr int cmin_i (int a, int b) { return a < b ? a : b; }
 
 // does sym_stage<M, .., ITEMS_PER_T, .., T, NWAVES> take the LEFTOVER scheme (below)?  Its caller then keeps the stage's table in LDS.
@@ -478,7 +447,7 @@ constexpr bool sym_stage_leftover ()
     // of 3 instead of 8) -7.7 us per slice (Poisson 64.6 -> 56.9 us, 3331 -> 3407 slices/s); the 41-point stage of 1024^2 (75 items,
     // H = 20: 6 wave-tasks of blocks of 4 instead of 8 of 5) +4.7 us on row-major planes and +37 us on blocked ones -- the second
     // loop body costs the kernel 27 VGPRs (76 -> 103; the two-transform kernel 115 -> 132: one workgroup per CU).  Small factors only.
-    return HPS_SYM_LEFTOVER && M <= 27 && NGX0 >= 2 && (FULL*NGX + 1)*(6 + 4*KBX) < NW*NGU*(6 + 4*KB);
+    return M <= 27 && NGX0 >= 2 && (FULL*NGX + 1)*(6 + 4*KBX) < NW*NGU*(6 + 4*KB);
 }
 
 // ltab: the stage's (cos, sin) table in LDS ([H][H] complex) for the wave of the remaining items, or null: plain scheme only
@@ -527,7 +496,7 @@ __device__ __forceinline__ void sym_stage (lds_double* cbuf, const double2* __re
         if (!lw) {
             const int k0s = 1 + gs*KBE;
             // (requesting step n+1's data pair and table row ahead of step n's FMAs by hand was measured slower)
-#pragma unroll HPS_SYM_UNROLL
+#pragma unroll 2
             for (int n = 1; n <= H; ++n) {
                 const double2 xa = ldc(cbuf, base + n*STRIDE), xb = ldc(cbuf, base + (M - n)*STRIDE);
                 const double sr = xa.x + xb.x, si = xa.y + xb.y, dr = xa.x - xb.x, di = xa.y - xb.y;
@@ -763,15 +732,12 @@ struct GemmArgs {
 // double-buffered (one barrier per slab), two accumulator chains.  Measured on config 2 (bench.py --config2, two runs each):
 // depth 1 2894-2924 slices/s, 2 2999-3016, 4 2943-3010, 8 (all slabs of a 256-deep product, 252 VGPRs) 2970-2973: the
 // product is not waiting for its operands; 2 it is.
-#ifndef HPS_DENSE_DEPTH
-#define HPS_DENSE_DEPTH 2
-#endif
 typedef double mfma_d4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256)
 void k_dense_product (GemmArgs g)
 {
     if (g.gate && *g.gate == 0) return;
-    constexpr int D = HPS_DENSE_DEPTH;
+    constexpr int D = 2;
     // pitches chosen so that the 32 lanes of one LDS pass hit 32 different 8-byte slots: A rows 34 apart, B rows 48
     __shared__ double As[2][32][34];
     __shared__ double Bs[2][32][48];

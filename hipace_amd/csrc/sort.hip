@@ -23,13 +23,7 @@
 
 namespace hps {
 
-#ifndef HPS_CELL_BLOCK_W
-#define HPS_CELL_BLOCK_W 32     /* >= tile size: row by row.  4 (blocks of 4 x 8 cells) was measured: deposit 75.2 -> 73.9 us, explicit deposit 124.8 -> 133.4 us, 1222 -> 1211 slices/s */
-#endif
-#ifndef HPS_RANK_CAP
-#define HPS_RANK_CAP 16
-#endif
-constexpr int RANK_CAP = HPS_RANK_CAP;
+constexpr int RANK_CAP = 16;
 
 // Number of cell (x, y) inside its tile.  The particles of a tile are interleaved over its cells in this order, so 32
 // consecutive numbers are the cells the lanes of a half-wave work on at the same time, and their LDS words must fall
@@ -156,7 +150,9 @@ int tiling_create (int nx, int ny, int ts, long capacity, Tiling** out)
     Tiling* T = new Tiling;
     T->g.nx = nx; T->g.ny = ny; T->g.ts = ts;
     T->g.ntx = (nx + ts - 1)/ts; T->g.nty = (ny + ts - 1)/ts; T->g.ntiles = T->g.ntx*T->g.nty;
-    T->g.bw = HPS_CELL_BLOCK_W;
+    // >= tile size: row by row.  4 (blocks of 4 x 8 cells) was measured: deposit 75.2 -> 73.9 us, explicit deposit
+    // 124.8 -> 133.4 us, 1222 -> 1211 slices/s
+    T->g.bw = 32;
     if (const char* e = std::getenv("HPS_CELL_BLOCK_W")) { const int v = std::atoi(e); if (v == 4 || v == 8 || v == 16 || v == 32) T->g.bw = v; }
     if (T->g.bw > ts) T->g.bw = ts;
     T->capacity = capacity;

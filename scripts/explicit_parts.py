@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """What the explicit deposition's time is made of: the shipped kernel (k_explicit_tiled<2,2,16>) timed on the engine's own
-sheet and slab at a slice of the headline deck, through whichever library HPS_LIB names -- diagnostic builds with parts of the
-kernel compiled out (scripts/build_variant.sh <name> particles_tiled.hip -DHPS_DIAG_EXPL_NO_ATOMICS / _NO_READS / _NO_FLUSH;
-their results are wrong, only their time is of interest).   python scripts/explicit_parts.py [--slice 715]"""
+sheet and slab at a slice of the headline deck, through whichever library HPS_LIB names -- e.g. the diagnostic build without
+the kernel's flush (scripts/build_variant.sh <name> particles_tiled.hip -DHPS_DIAG_EXPL_NO_FLUSH; its results are wrong, only
+its time is of interest).   python scripts/explicit_parts.py [--slice 715]"""
 import argparse, ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
