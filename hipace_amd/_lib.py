@@ -73,7 +73,9 @@ class Deck(C.Structure):
                 ("adaptive_threshold_uz", C.c_double), ("adaptive_phase_tolerance", C.c_double),
                 ("adaptive_no_predict_step", C.c_int), ("adaptive_no_phase_control", C.c_int), ("adaptive_phase_substeps", C.c_int),
                 ("adaptive_density", C.c_double), ("max_time", C.c_double), ("beam_uz_std", C.c_double),
-                ("ext_Ez_slope", C.c_double)]
+                ("ext_Ez_slope", C.c_double),
+                ("beam_do_salame", C.c_int), ("salame_n_iter", C.c_int), ("salame_relative_tolerance", C.c_double),
+                ("salame_no_advance", C.c_int), ("salame_Ez_target_slope", C.c_double)]
 
 
 # engine component names, index = value of the HPS_C_* enum in include/hpslice.h
@@ -85,6 +87,8 @@ CIDX = {n: i for i, n in enumerate(COMPS)}
 COMPS_PC = ["N_jx", "N_jy", "ExmBy", "EypBx", "Ez", "Bx", "By", "Bz", "Psi", "jx", "jy", "jz", "rhomjz",
             "P_Bx", "P_By", "P_jx", "P_jy", "Ion_rhomjz", "It_Bx", "It_By", "PIt_Bx", "PIt_By", "rho"]
 CIDX_PC = {n: i for i, n in enumerate(COMPS_PC)}
+# the SALAME slice, index = value of the HPS_SAL_* enum; appended behind the engine's own components in a beam_do_salame deck
+COMPS_SALAME = ["Ez_target", "Ez_no_salame", "Ez", "jx", "jy", "jz_beam", "Bx", "By", "Sy", "Sx", "Sy_back", "Sx_back"]
 ID_VALID = 1 << 63
 
 _SIGS = {
@@ -230,6 +234,12 @@ _SIGS = {
     "hps_ring_can_send": (C.c_int, [C.c_void_p]),
     "hps_ring_recv_landed": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hps_ring_engine_wait": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hps_engine_salame_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hps_salame_only_advance": (C.c_int, [Slab, Plasma, Geom, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "hps_salame_jxjy_from_bxby": (C.c_int, [Slab, Geom, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hps_salame_sxsy_from_jz": (C.c_int, [Slab, Geom, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hps_salame_get_w": (C.c_int, [Slab, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hps_salame_scale_beam_slice": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p]),
     "hps_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_device_count": (C.c_int, [C.POINTER(C.c_int)]),

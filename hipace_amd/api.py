@@ -521,8 +521,9 @@ class SliceEngine:
         check(_lib.lib().hps_engine_import_beam_slice(self._h, islice, C.c_void_p(msg.data_ptr())))
 
     def beam_state(self):
-        """hipace.dt != 0: (boundaries int64 [nz+1], soa float64 [7, nbeam]) of the moving beam; slice p from the head
-        is soa[:, boundaries[p]:boundaries[p+1]] (rows x y z ux uy uz w)."""
+        """(boundaries int64 [nz+1], soa float64 [7, nbeam]) of the beam as it is now; slice p from the head is
+        soa[:, boundaries[p]:boundaries[p+1]] (rows x y z ux uy uz w).  A static beam (hipace.dt = 0) comes in the same
+        layout, with the weights SALAME has left."""
         nbeam, _ = self.beam_layout()
         nz = self.deck["nz"]
         bnd = np.zeros(nz + 1, dtype=np.int64)
@@ -732,11 +733,24 @@ class SliceEngine:
         return out
 
     def comp_names(self):
-        """Names of the slab components of this engine (rho and aabs are optional and come last)."""
+        """Names of the slab components of this engine (rho and aabs are optional and come last; behind them the twelve
+        planes of the SALAME slice, "Salame_<name>", in a beam_do_salame deck -- slab() holds them, checksums() does not)."""
         if self.deck.get("bxby_solver", 0):
             return list(_lib.COMPS_PC[:22]) + (["rho"] if self.deck.get("deposit_rho", 0) else [])
         return list(COMPS[:21]) + (["rho"] if self.deck.get("deposit_rho", 0) else []) + \
-            (["aabs"] if self.deck.get("laser_on", 0) else [])
+            (["aabs"] if self.deck.get("laser_on", 0) else []) + \
+            (["Salame_" + n for n in _lib.COMPS_SALAME] if self.deck.get("beam_do_salame", 0) else [])
+
+    def salame_stats(self):
+        """<beam>.do_salame: dict of arrays [nz] (index = islice) -- "W" the last weight factor, "W_total" = W * sum(jz) of
+        that iteration (SalameGetW), "iterations", "converged", "overloaded" -- of the slices SALAME ran on in step 0; zeros
+        elsewhere ("ran" says where)."""
+        nz = self.deck["nz"]
+        out = np.zeros((nz, 4), dtype=np.float64)
+        check(_lib.lib().hps_engine_salame_stats(self._h, out.ctypes.data_as(C.c_void_p)))
+        flags = out[:, 3].astype(np.int64)
+        return {"W": out[:, 0].copy(), "W_total": out[:, 1].copy(), "iterations": out[:, 2].astype(np.int64),
+                "converged": (flags & 1) != 0, "overloaded": (flags & 2) != 0, "ran": out[:, 2] > 0}
 
     def pc_stats(self):
         """(predictor-corrector iterations so far, sum over slices of the final relative B-field error)."""

@@ -189,6 +189,14 @@ struct Engine {
     bool lazy_shift = true, shift_pending = false;      // ShiftSlices deferred to the next slice's InitializeSlices pass (HPS_LAZY_SHIFT=0: off)
     void flush_shift ();
     bool fuse_sources = true;       // the Poisson sources formed inside the first transform pass (HPS_FUSE_SOURCES=0: k_rhs_all + staging planes)
+    // <beam>.do_salame (salame/Salame.cpp): c_sal = first of the HPS_SAL_NCOMP planes behind the engine's own (-1: none);
+    // state of the run of consecutive slices (Hipace::m_salame_last_slice, m_salame_overloaded, m_salame_zeta_initial);
+    // d_sal = scratch of the W reduction; sal_stats = [nz][4] {W, W_total, iterations, flags}
+    int c_sal = -1; int sal_last_slice = -2; bool sal_overloaded = false; double sal_zeta_initial = 0.0;
+    double* d_sal = nullptr; std::vector<double> sal_stats;
+    bool salame_now () const { return c_sal >= 0 && step_index == 0; }      // MultiBeam::isSalameNow without the particle count
+    int salame_module (int islice);
+    int salame_solve_ez ();
     int run_step ();
 };
 
@@ -212,6 +220,8 @@ int beam_push_slice (Engine& E, int islice, int p, long bound);
 int beam_moments_reset (Engine& E);
 int beam_export_slice (Engine& E, int islice, double* msg_dev, long cap);
 int beam_import_slice (Engine& E, int islice, const double* msg_dev, long cap);
+int salame_get_w_enqueue (const hps_slab& slab, int cT, int cN, int cE, int cJ, double* scratch, hipStream_t st);      // salame.hip
+const double* salame_get_w_result (const double* scratch);
 
 } // namespace hps
 #endif

@@ -204,8 +204,9 @@ void k_grad_psi (SlabView f, int cPsi, int cExmBy, int cEypBx, double hdx_inv, d
 // beam contribution to the Bx/By sources (Hipace::InitializeSxSyWithBeam, Hipace.cpp:744-790)
 __global__ __launch_bounds__(256)
 void k_sxsy_beam (SlabView f, int cSx, int cSy, int cJzb, int cNx, int cNy, int cPx, int cPy,
-                  double mu0, double dx2, double dy2, double dz2, CellBox bb)
+                  double mu0, double dx2, double dy2, double dz2, CellBox bb, int cBackX = -1, int cBackY = -1)
 {
+    // cBackX, cBackY >= 0 (SALAME, Salame.cpp:175-179): the backed-up result of the explicit deposition is added on top
     // whole plane: the guard cells are set to 0 here (they are not part of InitializeSlices' zero list any more)
     const int i = blockIdx.x*blockDim.x + threadIdx.x - f.ng;
     const int j = blockIdx.y - f.ng;
@@ -214,15 +215,16 @@ void k_sxsy_beam (SlabView f, int cSx, int cSy, int cJzb, int cNx, int cNy, int 
     // no beam current within reach (bb is in padded-array cells): the sources are 0 without a load
     const int ia = i + f.ng, ja = j + f.ng;
     if (i < 0 || i >= f.nx || j < 0 || j >= f.ny || ia < bb.ilo || ia > bb.ihi || ja < bb.jlo || ja > bb.jhi) {
-        f.p[cSy*f.ns + o] = 0.0; f.p[cSx*f.ns + o] = 0.0; return;
+        f.p[cSy*f.ns + o] = cBackY >= 0 ? f.p[cBackY*f.ns + o] : 0.0; f.p[cSx*f.ns + o] = cBackX >= 0 ? f.p[cBackX*f.ns + o] : 0.0; return;
     }
     const double* J = f.p + cJzb*f.ns + o;
     const double dx_jzb = (J[1] - J[-1])/dx2;
     const double dy_jzb = (J[f.js] - J[-f.js])/dy2;
     const double dz_jxb = (f.p[cPx*f.ns + o] - f.p[cNx*f.ns + o])/dz2;
     const double dz_jyb = (f.p[cPy*f.ns + o] - f.p[cNy*f.ns + o])/dz2;
-    f.p[cSy*f.ns + o] =  mu0*(-dy_jzb + dz_jyb);
-    f.p[cSx*f.ns + o] = -mu0*(-dx_jzb + dz_jxb);
+    const double sy =  mu0*(-dy_jzb + dz_jyb), sx = -mu0*(-dx_jzb + dz_jxb);
+    f.p[cSy*f.ns + o] = cBackY >= 0 ? sy + f.p[cBackY*f.ns + o] : sy;
+    f.p[cSx*f.ns + o] = cBackX >= 0 ? sx + f.p[cBackX*f.ns + o] : sx;
 }
 
 // -grad Psi (k_grad_psi) and the beam part of Sx, Sy (k_sxsy_beam) in one pass over the plane: one launch less per slice
@@ -343,7 +345,7 @@ Engine::~Engine ()
     (void)hipFree(pl_real_alt); (void)hipFree(pl_alt.idcpu); (void)hipFree(pl_alt.ion_lev); 
     (void)hipFree(staging); (void)hipFree(d_open_mom); (void)hipFree(beam_data); (void)hipFree(beam_init);
     (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr); (void)hipFree(d_B); (void)hipFree(d_nfront);
-    (void)hipFree(d_mom);
+    (void)hipFree(d_mom); (void)hipFree(d_sal);
     (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow); (void)hipFree(d_nqsa); (void)hipFree(d_checksum);
     (void)hipFree(d_pc); (void)hipFree(d_pc_aux); (void)hipFree(d_pc_go); if (h_pc) (void)hipHostFree(h_pc);
     (void)hipFree(d_laser_sum);
@@ -674,6 +676,18 @@ int Engine::create (const hps_deck& deck, int device)
     if (const char* v = std::getenv("HPS_SORT_FALLBACK_DIV")) { const long q = std::atol(v); if (q >= 1) fallback_div = q; }
     HPS_REQUIRE(!(d.beam_spin_tracking && d.dt == 0.0 && !d.dt_adaptive), "hps_engine_create: spin tracking needs a moving beam (hipace.dt != 0)");
     HPS_REQUIRE(!(d.dt_adaptive && d.laser_on), "hps_engine_create: hipace.dt = adaptive cannot be used with a laser (Hipace.cpp:408)");
+    if (d.beam_do_salame) {
+        // <beam>.do_salame
+        if (pc) { set_error("hps_engine_create: beam_do_salame needs the explicit solver (Hipace.cpp:152), not the predictor-corrector"); return HPS_ERR_UNSUPPORTED; }
+        if (d.beam_profile == 0 && !(std::isfinite(d.beam_zmin) && std::isfinite(d.beam_zmax))) {
+            set_error("hps_engine_create: beam_do_salame with a gaussian beam profile needs finite beam_zmin and beam_zmax (BeamParticleContainer.cpp:149)"); return HPS_ERR_ARG; }
+        if (d.ion_on) { set_error("hps_engine_create: beam_do_salame with the ionisable species (ion_on) is not supported"); return HPS_ERR_UNSUPPORTED; }
+        if (d.laser_on) { set_error("hps_engine_create: beam_do_salame with a laser is not supported"); return HPS_ERR_UNSUPPORTED; }
+        if (d.dt != 0.0 || d.dt_adaptive) { set_error("hps_engine_create: beam_do_salame needs a static beam (hipace.dt = 0)"); return HPS_ERR_UNSUPPORTED; }
+        HPS_REQUIRE(d.salame_n_iter >= 0 && d.salame_relative_tolerance >= 0.0, "hps_engine_create: salame_n_iter and salame_relative_tolerance must not be negative");
+        if (d.salame_n_iter == 0) d.salame_n_iter = 5;                                    // hipace.salame_n_iter (Hipace.H)
+        if (d.salame_relative_tolerance == 0.0) d.salame_relative_tolerance = 1.0e-4;      // hipace.salame_relative_tolerance
+    }
     step_dt = d.dt;
     if (d.predcorr_tol > 0.0) pc_tol = d.predcorr_tol;
     if (d.predcorr_max_iter > 0) pc_max_iter = d.predcorr_max_iter;
@@ -710,10 +724,16 @@ int Engine::create (const hps_deck& deck, int device)
     gm.plo[0] = d.lo[0]; gm.plo[1] = d.lo[1]; gm.phi[0] = d.hi[0]; gm.phi[1] = d.hi[1];
     gm.bc = d.bc; gm.normalized = d.si_units ? 0 : 1;
 
-    slab.nx = d.nx; slab.ny = d.ny; slab.ng = g; slab.ncomp = ncomp;
+    // the SALAME slice: twelve planes behind the engine's own (`ncomp` stays the count of those: checksums, hps_engine_info)
+    if (d.beam_do_salame) {
+        c_sal = ncomp;
+        HPS_HIP_CHECK(hipMalloc(&d_sal, (size_t)4*257*sizeof(double)));
+        sal_stats.assign((size_t)4*d.nz, 0.0);
+    }
+    slab.nx = d.nx; slab.ny = d.ny; slab.ng = g; slab.ncomp = ncomp + (c_sal >= 0 ? (int)HPS_SAL_NCOMP : 0);
     slab.jstride = d.nx + 2*g; slab.nstride = slab.jstride*(d.ny + 2*g);
-    HPS_HIP_CHECK(hipMalloc(&slab.p, (size_t)slab.nstride*ncomp*sizeof(double)));
-    HPS_HIP_CHECK(hipMemset(slab.p, 0, (size_t)slab.nstride*ncomp*sizeof(double)));
+    HPS_HIP_CHECK(hipMalloc(&slab.p, (size_t)slab.nstride*slab.ncomp*sizeof(double)));
+    HPS_HIP_CHECK(hipMemset(slab.p, 0, (size_t)slab.nstride*slab.ncomp*sizeof(double)));
     HPS_HIP_CHECK(hipMalloc(&staging, (size_t)3*d.nx*d.ny*sizeof(double)));
 
     const int nppc = d.plasma_ppc[0]*d.plasma_ppc[1];
@@ -744,7 +764,8 @@ int Engine::create (const hps_deck& deck, int device)
         HPS_HIP_CHECK(hipMalloc(&p.ion_lev, (size_t)cap*sizeof(int32_t)));
         return HPS_OK;
     };
-    if (np_cap > 0) { if (int e = alloc_sheet(pl, pl_real, np_cap, !pc)) return e; }
+    // (SALAME pushes to the temporary slice from x_prev, as the predictor-corrector does: separate arrays there too)
+    if (np_cap > 0) { if (int e = alloc_sheet(pl, pl_real, np_cap, !pc && c_sal < 0)) return e; }
     if (ion.n > 0) { ion.pl.n = ion.n; if (int e = alloc_sheet(ion.pl, ion.real, ion.n, !pc)) return e; }
     HPS_HIP_CHECK(hipMalloc(&d_laser_sum, sizeof(double)));
     HPS_HIP_CHECK(hipMemset(d_laser_sum, 0, sizeof(double)));
@@ -821,7 +842,7 @@ int Engine::setup_tiling ()
     if (int e = tiling_create(d.nx, d.ny, tile_size, np_cap, &tiling)) return e;
     {   const char* v = std::getenv("HPS_VALID_BY_PSI");       // the electrons' push without its idcpu read (tiling.h)
         tiling->valid_by_psi = (v && std::atoi(v) != 0); }       // (measured: the push takes the same time with and without, off)
-    if (int e = second(pl_alt, pl_real_alt, np_cap, !pc)) return e;
+    if (int e = second(pl_alt, pl_real_alt, np_cap, !pc && c_sal < 0)) return e;
     pl_alt.n = np;
     if (ion.n > 0) {
         // the ionisable species on the engine's tile size.  (Round 2 gave a species with at most one particle per cell 32 x 32-cell
@@ -882,7 +903,7 @@ int Engine::begin_step ()
     }
     shift_pending = false;      // (the slab is cleared whole below)
     // ResetAllQuantities (Hipace.cpp:730-742)
-    HPS_HIP_CHECK(hipMemsetAsync(slab.p, 0, (size_t)slab.nstride*ncomp*sizeof(double), st));
+    HPS_HIP_CHECK(hipMemsetAsync(slab.p, 0, (size_t)slab.nstride*slab.ncomp*sizeof(double), st));
     // predictor-corrector: nothing but the cold plasma has been deposited in this sweep yet.  Not so from the first slice on
     // with a grid current, and with a second species as particles (or no neutralising background): there the serial path's
     // charges cancel to rounding only, it iterates on that residue itself, and the literal rule on the engine's residue is its
@@ -899,6 +920,7 @@ int Engine::begin_step ()
     step_index = (next_step >= 0) ? next_step : step_index + 1;      // Hipace::m_physical_time (PlasmaParticleContainerInit.cpp:90)
     next_step = -1;
     ahead_for = -2;
+    if (salame_now()) { sal_last_slice = -2; sal_overloaded = false; std::fill(sal_stats.begin(), sal_stats.end(), 0.0); }
     if (d_mom) { if (int e = beam_moments_reset(*this)) return e; }
     // time factor of the density profile at z = c t of this step (UpdateDensityFunction, PlasmaParticleContainer.cpp:211-217)
     if (time_set) {          // hps_engine_set_time
@@ -1175,8 +1197,9 @@ void k_insitu_plasma (hps_plasma pl, double clight_inv, double radius_sq, double
 // the block [B[p] + nfront[p], B[p+1]) of the SoA, nsub < 0 = absorbed.
 __global__ __launch_bounds__(256)
 void k_insitu_beam (BeamView b, const int* __restrict__ nsub, const long* __restrict__ B, const int* __restrict__ nfront, int p,
-                    long count_static, double clight_inv, double radius_sq, double* out, int nz, int islice)
+                    long count_static, double clight_inv, double radius_sq, double* out, int nz, int islice, int skip_zero_w = 0)
 {
+    // skip_zero_w (SALAME deck): a particle whose weight SALAME has set to 0 no longer exists (the reference invalidates it)
     long first = 0, count = count_static;
     if (B) { first = B[p] + nfront[p]; count = B[p + 1] - first; }
     double s[23];
@@ -1185,7 +1208,7 @@ void k_insitu_beam (BeamView b, const int* __restrict__ nsub, const long* __rest
     for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
         const long ip = first + t;
         const double x = b.x[ip], y = b.y[ip], z = b.z[ip];
-        if ((nsub && nsub[ip] < 0) || x*x + y*y > radius_sq) continue;
+        if ((nsub && nsub[ip] < 0) || x*x + y*y > radius_sq || (skip_zero_w && b.w[ip] == 0.0)) continue;
         const double ux = b.ux[ip]*clight_inv, uy = b.uy[ip]*clight_inv, uz = b.uz[ip]*clight_inv, w = b.w[ip];
         const double uz_inv = uz == 0.0 ? 0.0 : 1.0/uz;
         const double gamma = sqrt(1.0 + ux*ux + uy*uy + uz*uz);
@@ -1226,7 +1249,7 @@ void Engine::insitu_beam (int islice)
         double* blk = beam_cur + 7*first0;
         const BeamView b{blk, blk + count, blk + 2*count, blk + 3*count, blk + 4*count, blk + 5*count, blk + 6*count};
         hipLaunchKernelGGL(k_insitu_beam, dim3((unsigned)std::min<long>(ceil_div(count, 256), 64)), dim3(256), 0, st, b, (const int*)nullptr,
-                           (const long*)nullptr, (const int*)nullptr, 0, count, 1.0/gm.c, r2, d_insitu_bm, d.nz, islice);
+                           (const long*)nullptr, (const int*)nullptr, 0, count, 1.0/gm.c, r2, d_insitu_bm, d.nz, islice, c_sal >= 0 ? 1 : 0);
     }
 }
 
@@ -1785,7 +1808,10 @@ int Engine::solve_slice_begin (int islice)
         if ((e = laser_update_aabs(*this, islice, diagnostics ? d_laser_sum : nullptr))) return e;
     }
     // the auxiliary stream may start on the beam's planes (zeroed above)
-    const bool aux = aux_on && st_aux && !pc && !ahead && !prof_now;
+    // SALAME's step 0 (MultiBeam::isSalameNow): the slice runs through the plain sequence -- no paired / folded beam deposit, no
+    // auxiliary stream, no fused or gated push, no deferred shift -- and the beam deposits no jx, jy on Next (MultiBeam.cpp:50-56)
+    const bool sal = salame_now();
+    const bool aux = aux_on && st_aux && !pc && !ahead && !prof_now && !sal;
     if (aux) { HPS_HIP_CHECK(hipEventRecord(ev_aux[0], st)); HPS_HIP_CHECK(hipStreamWaitEvent(st_aux, ev_aux[0], 0)); }
 
     mark();   // b1
@@ -1801,7 +1827,7 @@ int Engine::solve_slice_begin (int islice)
     // static beam: jz of this slice and jx, jy of the next one in one go (Hipace.cpp:613-614, 656-657), as extra workgroups of
     // the plasma's deposition where that runs on tiles; a moving beam keeps the two calls (the next slice's block is only
     // final once this slice's push has handed its slipped particles on -- it is deposited after the solves below as before)
-    const bool pair = !moving && nbeam > 0;
+    const bool pair = !moving && nbeam > 0 && !sal;
     BeamPairWork bw;
     if (pair) {
         const long fA = beam_off[d.nz - 1 - islice], cA = beam_off[d.nz - islice] - fA;
@@ -1892,7 +1918,7 @@ int Engine::solve_slice_begin (int islice)
                            HPS_C_EXMBY, HPS_C_EYPBX, 0.5*(1.0/gm.dx), 0.5*(1.0/gm.dy));
         mark();   // b3
         // beam jx, jy of the next slice; beam part of Sx, Sy (Hipace.cpp:656-660)
-        if ((e = deposit_beam_slice(islice - 1, HPS_C_N_JXB, HPS_C_N_JYB, -1))) return e;
+        if (!sal) { if ((e = deposit_beam_slice(islice - 1, HPS_C_N_JXB, HPS_C_N_JYB, -1))) return e; }
         hipLaunchKernelGGL(k_sxsy_beam, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, HPS_C_SX, HPS_C_SY, HPS_C_JZB, HPS_C_N_JXB, HPS_C_N_JYB,
                            HPS_C_P_JXB, HPS_C_P_JYB, gm.mu0, 2.0*gm.dx, 2.0*gm.dy, 2.0*gm.dz, bb);
     }
@@ -1907,12 +1933,12 @@ int Engine::solve_slice_begin (int islice)
     // species, nothing that reads the fields between the solve and the push) enqueues the push BEHIND the speculated
     // V-cycles, gated on the solve's own stopping rule, and only then waits for the norms: the device goes from the last
     // V-cycle straight into the push instead of idling until the host has seen the norms and launched it.
-    const bool fuse = fuse_push_deposit && tiling && islice > 0 && !moving && c_aabs < 0 && ion.n == 0 && np > 0 && tiling->sorted_n == np;
-    const bool gated = gate_push && tiling && !fuse && ion.n == 0 && np > 0 && tiling->sorted_n == np && !diagnostics && !d_fd && !d_insitu;
+    const bool fuse = fuse_push_deposit && tiling && islice > 0 && !moving && c_aabs < 0 && ion.n == 0 && np > 0 && tiling->sorted_n == np && !sal;
+    const bool gated = gate_push && tiling && !fuse && ion.n == 0 && np > 0 && tiling->sorted_n == np && !diagnostics && !d_fd && !d_insitu && !sal;
     // ... and with an ionisable species on tiles: its field bounds, its push (which takes the ADK decisions and appends the
     // electrons) and the electrons' push, all behind the speculated V-cycles; the two pushes are gated (HPS_GATED_ION_PUSH=0: off)
     const bool gated_ion = gate_push && gate_ion_push && tiling && !fuse && ion.n > 0 && ion.tiling && np > 0 && tiling->sorted_n > 0 && fold_tail
-                           && !diagnostics && !d_fd && !d_insitu;
+                           && !diagnostics && !d_fd && !d_insitu && !sal;
     const int comp_push[5] = {HPS_C_PSI, HPS_C_EZ, HPS_C_BX, HPS_C_BY, HPS_C_BZ};
     {
         // the plain gated push also posts the solve's norms to the host (k_advance_tiled's MgPost): no k_post_norms launch between
@@ -1980,6 +2006,12 @@ int Engine::solve_slice_finish (int islice)
             if (pl.n > pend_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(pl, pend_covered, pl.n - pend_covered), gm, comp_push, c_aabs, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
         } }
 
+    // SalameModule (Hipace.cpp:673-678): behind the Bx/By solve, ahead of the diagnostics and the push, on a slice whose beam
+    // block holds particles
+    if (salame_now() && !moving && nbeam > 0 && beam_off[d.nz - islice] - beam_off[d.nz - 1 - islice] > 0) {
+        if ((e = salame_module(islice))) return e;
+    }
+
     if (!gated && !gated_ion) {
     mark();   // b6
     if (diagnostics)
@@ -2037,12 +2069,136 @@ int Engine::solve_slice_finish (int islice)
     // (lazy_shift: left to the start of the next slice, where it shares a pass with InitializeSlices; anything that looks at
     //  the slab in between -- hps_engine_slab, _sync, the diagnostics' accessors -- runs it first: flush_shift)
     if (ahead_for != islice - 1) {
-        if (lazy_shift && islice > 0) shift_pending = true;
+        if (lazy_shift && islice > 0 && !salame_now()) shift_pending = true;
         else hipLaunchKernelGGL(k_shift_slices, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb);
     }
     mark();   // b9
     HPS_HIP_CHECK(hipGetLastError());
     ++slices_done;
+    return HPS_OK;
+}
+
+
+// SolvePoissonEz(WhichSlice::Salame) (fields/Fields.cpp:960-1006): Ez of the SALAME slice from its jx, jy
+int Engine::salame_solve_ez ()
+{
+    const double fa = 1.0/(gm.ep0*gm.c);
+    hipLaunchKernelGGL(k_rhs_lincomb, dim3(ceil_div(d.nx, 256), d.ny), dim3(256), 0, st, SlabView(slab), c_sal + HPS_SAL_JX, 0,
+                       fa*0.5*(1.0/gm.dx), c_sal + HPS_SAL_JY, 1, fa*0.5*(1.0/gm.dy), staging);
+    if (int e = open_boundary(1, 0x1u)) return e;       // (Ez: no physical monopole, fields/Fields.cpp:727-731)
+    return hps_poisson_solve(ps, staging, slab, c_sal + HPS_SAL_EZ, st);
+}
+
+// SalameModule (salame/Salame.cpp:13-189) on level 0 with one beam species, statement by statement.  The fields of This
+// are solved; the sheet holds the committed state of this slice (x_prev, y_prev, u_half) and is pushed to the temporary
+// slice only.  The host reads W once per iteration, as the reference does.
+int Engine::salame_module (int islice)
+{
+    SlabView f(slab);
+    const long plane = slab.nstride;
+    const dim3 b256(256), gplane(ceil_div(plane, 256)), gvalid(ceil_div(d.nx, 256), d.ny);
+    const CellBox bb{beam_box.ilo, beam_box.ihi, beam_box.jlo, beam_box.jhi}, none{0, -1, 0, -1};
+    const int S = c_sal;
+    const int comp_push[5] = {HPS_C_PSI, HPS_C_EZ, HPS_C_BX, HPS_C_BY, HPS_C_BZ};
+    const int dep_jxjy[6] = {S + HPS_SAL_JX, S + HPS_SAL_JY, -1, -1, -1, -1};
+    auto zero = [&] (std::initializer_list<int> cs) {
+        CompList z{0, {}}; for (int c : cs) z.c[z.n++] = c;
+        hipLaunchKernelGGL(k_zero_comps, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, z, CompList{0, {}}, none);
+    };
+    auto copy = [&] (std::initializer_list<int> dst, std::initializer_list<int> src) {
+        CompList a{0, {}}, b{0, {}}; for (int c : dst) a.c[a.n++] = c; for (int c : src) b.c[b.n++] = c;
+        hipLaunchKernelGGL(k_copy_comps, gplane, b256, 0, st, slab.p, slab.nstride, plane, a, b);
+    };
+    auto solve_bxby = [&] (int cB, int cS) -> int {
+        int iters = 0;
+        if (int e = hps_mg_solve1(mg, slab, cB, cS, HPS_C_CHI, d.mg_tol_rel, d.mg_tol_abs, 200, &iters, nullptr, st)) return e;
+        total_vcycles += iters;
+        return HPS_OK;
+    };
+    int e;
+
+    // always the Ez from before SALAME started, for a whole run of consecutive slices (:20-30)
+    if (islice + 1 != sal_last_slice) {
+        copy({S + HPS_SAL_EZ_TARGET}, {HPS_C_EZ});
+        sal_overloaded = false;
+        sal_zeta_initial = islice*gm.dz + d.lo[2] + 0.5*gm.dz;       // GetPosOffset(2, geom, domain) = lo_z + dz/2
+    }
+    sal_last_slice = islice;
+
+    // Sx, Sy of the plasma alone, backed up ahead of any push (:32-39)
+    zero({HPS_C_SY, HPS_C_SX});
+    {   const int cache[4] = {HPS_C_BZ, HPS_C_EZ, HPS_C_EXMBY, HPS_C_EYPBX};
+        const int depos[2] = {HPS_C_SY, HPS_C_SX};
+        if ((e = species_explicit(pl, tiling, cache, depos, d.plasma_charge, d.plasma_mass, 0))) return e; }
+    copy({S + HPS_SAL_SY_BACK, S + HPS_SAL_SX_BACK}, {HPS_C_SY, HPS_C_SX});
+
+    const long first0 = beam_off[d.nz - 1 - islice], count = beam_off[d.nz - islice] - first0;
+    double W = 1.0, W_total = 0.0;
+    int iter = 0, used = 0; bool converged = false, undetermined = false;
+    for (; iter < d.salame_n_iter; ++iter) {
+        // STEP 1: Ez of the next slice with the beam at its present weight (:43-73)
+        if ((e = species_advance(pl, tiling, comp_push, d.plasma_charge, d.plasma_mass, 1, 0))) return e;
+        copy({S + HPS_SAL_JX, S + HPS_SAL_JY}, {HPS_C_N_JXB, HPS_C_N_JYB});
+        if ((e = species_deposit(pl, tiling, dep_jxjy, d.plasma_charge, d.plasma_mass, 0))) return e;
+        zero({S + HPS_SAL_EZ, S + HPS_SAL_JZB, S + HPS_SAL_SY, S + HPS_SAL_SX, S + HPS_SAL_BX, S + HPS_SAL_BY});
+        if ((e = salame_solve_ez())) return e;
+        copy({S + HPS_SAL_EZ_NO_SALAME}, {S + HPS_SAL_EZ});
+
+        // STEP 2: Ez of the SALAME beam alone (:75-121)
+        if ((e = deposit_beam_slice(islice, -1, -1, S + HPS_SAL_JZB))) return e;
+        if ((e = hps_salame_sxsy_from_jz(slab, gm, S + HPS_SAL_JZB, S + HPS_SAL_SY, S + HPS_SAL_SX, st))) return e;
+        if ((e = solve_bxby(S + HPS_SAL_BX, S + HPS_SAL_SY))) return e;       // zero guess, This chi
+        zero({S + HPS_SAL_EZ, S + HPS_SAL_JX, S + HPS_SAL_JY});
+        if (!d.salame_no_advance) {
+            if (pl.n > 0) { if ((e = hps_salame_only_advance(slab, pl, gm, S + HPS_SAL_BX, S + HPS_SAL_BY, d.plasma_charge, d.plasma_mass, d.order, 0, st))) return e; }
+            if ((e = species_deposit(pl, tiling, dep_jxjy, d.plasma_charge, d.plasma_mass, 0))) return e;
+        } else {
+            if ((e = hps_salame_jxjy_from_bxby(slab, gm, S + HPS_SAL_BX, S + HPS_SAL_BY, HPS_C_CHI, S + HPS_SAL_JX, S + HPS_SAL_JY, st))) return e;
+        }
+        if ((e = salame_solve_ez())) return e;
+
+        // STEP 3: the weight factor (:123-158)
+        zero({S + HPS_SAL_JZB});
+        if ((e = deposit_beam_slice(islice, -1, -1, S + HPS_SAL_JZB))) return e;
+        double s4[4];
+        if ((e = salame_get_w_enqueue(slab, S + HPS_SAL_EZ_TARGET, S + HPS_SAL_EZ_NO_SALAME, S + HPS_SAL_EZ, S + HPS_SAL_JZB, d_sal, st))) return e;
+        HPS_HIP_CHECK(hipMemcpyAsync(s4, salame_get_w_result(d_sal), sizeof(s4), hipMemcpyDeviceToHost, st));
+        HPS_HIP_CHECK(hipStreamSynchronize(st));
+        {   const double sum_jz = s4[3];
+            double ez_target = s4[0]/sum_jz;
+            const double ez_no = s4[1]/sum_jz, ez_only = s4[2]/sum_jz;
+            const double zeta = (islice - 1)*gm.dz + d.lo[2] + 0.5*gm.dz;        // the Ez of the next slice (SalameGetW :395-400)
+            ez_target += d.salame_Ez_target_slope*(zeta - sal_zeta_initial);    // salame_Ez_target(zeta, zeta_initial, Ez_initial)
+            W = (ez_target - ez_no)/ez_only + 1.0;
+            W_total = W*sum_jz;
+            // No weight can be derived (the reference divides all the same and would multiply the weights by NaN).  A slice
+            // without current -- every weight already 0, e.g. the dropped tail of an overloaded beam loaded again -- has nothing
+            // to scale: W = 0, the run of slices is not marked overloaded by it.  A beam whose own Ez vanishes (sum jz != 0) keeps
+            // its weights: W = 1.  Either way this was the slice's last iteration.
+            // (Behind an overload the weight is 0 whatever the sums say, as before.)
+            if (sal_overloaded) { }
+            else if (sum_jz == 0.0) { W = 0.0; W_total = 0.0; undetermined = true; }
+            else if (!std::isfinite(W)) { W = 1.0; W_total = sum_jz; undetermined = true; } }
+        used = iter + 1;
+        bool last = undetermined;
+        if (!undetermined && (W < 0.0 || sal_overloaded)) { W = 0.0; W_total = 0.0; last = true; sal_overloaded = true; }
+        if (!undetermined && !sal_overloaded && iter >= 1 && std::fabs(W - 1.0) < d.salame_relative_tolerance) { last = true; converged = true; }
+        if ((e = hps_salame_scale_beam_slice(beam_cur + 7*first0 + 6*count, count, W, st))) return e;
+
+        // STEP 4: the fields of This with the new weight (:160-182)
+        {   CompList zb{0, {}}; zb.c[zb.n++] = HPS_C_JZB;
+            hipLaunchKernelGGL(k_zero_comps, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, CompList{0, {}}, zb, bb); }
+        if ((e = deposit_beam_slice(islice, -1, -1, HPS_C_JZB))) return e;
+        deposit_grid_current(islice, HPS_C_JZB);
+        // InitializeSxSyWithBeam writes Sx, Sy as whole planes (no zeroing pass), with Sy_back, Sx_back added in the same pass
+        hipLaunchKernelGGL(k_sxsy_beam, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, HPS_C_SX, HPS_C_SY, HPS_C_JZB, HPS_C_N_JXB, HPS_C_N_JYB,
+                           HPS_C_P_JXB, HPS_C_P_JYB, gm.mu0, 2.0*gm.dx, 2.0*gm.dy, 2.0*gm.dz, bb, S + HPS_SAL_SX_BACK, S + HPS_SAL_SY_BACK);
+        if ((e = solve_bxby(HPS_C_BX, HPS_C_SY))) return e;
+        if (last) break;
+    }
+    double* o = sal_stats.data() + (size_t)4*islice;
+    o[0] = W; o[1] = W_total; o[2] = (double)used; o[3] = (converged ? 1.0 : 0.0) + (sal_overloaded ? 2.0 : 0.0);
+    HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
 
@@ -2512,7 +2668,18 @@ extern "C" int hps_engine_import_beam_slice (void* h, int islice, const double* 
 extern "C" int hps_engine_beam_state (void* h, long* boundaries_host, double* soa_host)
 {
     Engine* E = static_cast<Engine*>(h);
-    HPS_REQUIRE(E->moving, "hps_engine_beam_state: the engine's beam is static (hipace.dt = 0)");
+    if (!E->moving) {
+        // static beam: the slice-major blocks [slice p][7][count_p] gathered into the same global layout
+        HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+        if (boundaries_host) for (int p = 0; p <= E->d.nz; ++p) boundaries_host[p] = E->beam_off[p];
+        if (soa_host && E->nbeam > 0)
+            for (int p = 0; p < E->d.nz; ++p) {
+                const long first = E->beam_off[p], cnt = E->beam_off[p + 1] - first;
+                for (int k = 0; k < 7 && cnt > 0; ++k)
+                    HPS_HIP_CHECK(hipMemcpy(soa_host + (size_t)k*E->nbeam + first, E->beam_cur + 7*first + (size_t)k*cnt, cnt*sizeof(double), hipMemcpyDeviceToHost));
+            }
+        return HPS_OK;
+    }
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     {   int ov = 0;
         HPS_HIP_CHECK(hipMemcpy(&ov, E->d_beam_overflow, sizeof(int), hipMemcpyDeviceToHost));
@@ -2521,6 +2688,15 @@ extern "C" int hps_engine_beam_state (void* h, long* boundaries_host, double* so
     if (soa_host && E->nbeam > 0)
         for (int k = 0; k < 7; ++k)
             HPS_HIP_CHECK(hipMemcpy(soa_host + (size_t)k*E->nbeam, E->bm_store + (size_t)k*std::max(E->nbeam, 1L), E->nbeam*sizeof(double), hipMemcpyDeviceToHost));
+    return HPS_OK;
+}
+extern "C" int hps_engine_salame_stats (void* h, double* out)
+{
+    HPS_REQUIRE(h && out, "hps_engine_salame_stats: null argument");
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E->c_sal >= 0, "hps_engine_salame_stats: the deck has no beam_do_salame");
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    std::memcpy(out, E->sal_stats.data(), E->sal_stats.size()*sizeof(double));
     return HPS_OK;
 }
 extern "C" int hps_engine_assume_initial_beam_support (void* h)

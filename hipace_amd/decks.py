@@ -72,6 +72,12 @@ ADAPTIVE_DEFAULT = dict(
     adaptive_density=0.0, max_time=0.0, beam_uz_std=0.0, ext_Ez_slope=0.0,
 )
 
+# <beam>.do_salame (salame/Salame.cpp).  Kept apart from _DEFAULT like ADAPTIVE_DEFAULT; 0 = off / the reference's default:
+# hipace.salame_n_iter (5), salame_relative_tolerance (1e-4), salame_do_advance (inverted: 0 keeps it on), and the slope of
+# the linear target Ez_initial + slope (zeta - zeta_initial) that stands in for the parsed hipace.salame_Ez_target
+SALAME_DEFAULT = dict(beam_do_salame=0, salame_n_iter=0, salame_relative_tolerance=0.0, salame_no_advance=0,
+                      salame_Ez_target_slope=0.0)
+
 # Ionisation energies in eV of a few elements: NIST Atomic Spectra Database (Kramida, Ralchenko, Reader and NIST ASD
 # Team, ver. 5.2), the values the reference tabulates in utils/IonizationEnergiesTable.H.
 IONIZATION_ENERGIES_EV = {
@@ -316,6 +322,50 @@ def grid_current():
     d.update(nx=32, ny=32, nz=32, lo=(-8.0, -8.0, -6.0), hi=(8.0, 8.0, 6.0), n_steps=2, order=0, beam_profile=0, beam_density=0.2,
              beam_radius=1.0, beam_pos_mean=(0.0, 0.0, 0.0), beam_pos_std=(0.3, 0.3, 1.41), beam_ppc=(1, 1, 1),
              grid_current_on=1, grid_current_peak=0.2, grid_current_mean=(0.0, 0.0, 0.0), grid_current_std=(0.3, 0.3, 1.41))
+    return d
+
+
+def salame_grid_current(zmin=-1.4, zmax=0.78, density=0.5):
+    """The SALAME test deck (<beam>.do_salame behind a grid_current.* driver; salame/Salame.cpp): explicit solver, order 2,
+    64 x 64 cells over +-8, 100 slices over z in [-8, 6] (dz = 0.14), plasma 2 x 2 ppc, MG_tolerance_rel = 1e-10.  Driver: a
+    Gaussian grid current of peak -0.5 (electron-like) at z = 3, sigma (0.5, 0.5, 1).  Witness: a flat-top fixed_ppc electron
+    beam of radius 0.3 with u = (0, 0, 2000) exactly (jx_beam = jy_beam = 0), 4 x 4 x 1 ppc, z in [zmin, zmax) = slices 47 .. 62 (length 2.2).
+
+    Placement, from the CPU oracle's run of the deck without the witness (on-axis Ez, mean of the four central cells):
+        z      5.23   3.83   2.43   1.31   0.75   0.47   0.19  -0.37  -0.65  -0.93  -1.49  -1.77  -2.05  -2.61  -3.17
+        Ez    0.003  0.045  0.084  0.001 -0.061 -0.092 -0.120 -0.162 -0.171 -0.167 -0.110 -0.056  0.009  0.123  0.171
+    The head (slice 62, z = 0.75) sits where Ez = -0.061 < 0; over the witness the unloaded Ez goes to -0.171 and back to
+    -0.13, a change of 180 % of the head value.  Ez changes sign at z = -2.0: `salame_grid_current_overload` reaches past it.
+    On the MI355X SALAME scales the slices' weights by 3.2 (head), 4.3 (third slice), then almost linearly down to 0.83 (slice
+    47): W > 0 everywhere.  The same witness would run out of wake at slice 44; a head at z = 0.47 does so 12 slices in.
+    """
+    d = copy.deepcopy(_DEFAULT)
+    d.update(SALAME_DEFAULT)
+    d.update(nx=64, ny=64, nz=100, lo=(-8.0, -8.0, -8.0), hi=(8.0, 8.0, 6.0), order=2, plasma_ppc=(2, 2), mg_tol_rel=1.0e-10, n_steps=1,
+             grid_current_on=1, grid_current_peak=-0.5, grid_current_mean=(0.0, 0.0, 3.0), grid_current_std=(0.5, 0.5, 1.0),
+             beam_profile=1, beam_zmin=zmin, beam_zmax=zmax, beam_radius=0.3, beam_density=density, beam_umean=(0.0, 0.0, 2000.0),
+             beam_pos_mean=(0.0, 0.0, 0.0), beam_ppc=(4, 4, 1), beam_charge=-1.0, beam_do_salame=1)
+    return d
+
+
+def salame_grid_current_overload():
+    """`salame_grid_current` with the witness reaching to z = -3.0 (slice 36), past the point (z = -2.0) where the unloaded Ez changes
+    sign: no positive weight holds the target there, W < 0 must occur and the rest of the witness is dropped."""
+    return salame_grid_current(zmin=-3.0)
+
+
+def salame_grid_current_SI(**kw):
+    """`salame_grid_current` scaled to SI units with kp_inv = 10 um, as the project's other SI twins are."""
+    kp_inv = 10.0e-6
+    ne = _ne_SI(kp_inv)
+    E0 = SI["m_e"] * SI["c"] ** 2 / (SI["q_e"] * kp_inv)        # cold wave-breaking field m c wp / e
+    d = salame_grid_current(**kw)
+    sc = lambda v: tuple(x * kp_inv for x in v)
+    d.update(si_units=1, lo=sc(d["lo"]), hi=sc(d["hi"]), plasma_density=ne, plasma_charge=-SI["q_e"], plasma_mass=SI["m_e"],
+             beam_zmin=d["beam_zmin"] * kp_inv, beam_zmax=d["beam_zmax"] * kp_inv, beam_radius=d["beam_radius"] * kp_inv,
+             beam_density=d["beam_density"] * ne, beam_charge=-SI["q_e"], beam_mass=SI["m_e"],
+             grid_current_peak=d["grid_current_peak"] * ne * SI["q_e"] * SI["c"], grid_current_mean=sc(d["grid_current_mean"]),
+             grid_current_std=sc(d["grid_current_std"]), salame_Ez_target_slope=d["salame_Ez_target_slope"] * E0 / kp_inv)
     return d
 
 

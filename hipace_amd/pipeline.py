@@ -630,6 +630,7 @@ def run_lanes(engines, rank, world, n_steps, device, on_step_end=None, slices_pe
     slices_per_step: as `_stage`'s; a list has one entry per STAGE of the whole ring (world*L).
     world > 1: the same requirement on GPU_MAX_HW_QUEUES as `run_pipeline`.
     Returns the number of slices solved by this process."""
+    _refuse_salame(engines)
     L = len(engines)
     W = world * L
     if any(getattr(e, "adaptive", False) for e in engines):
@@ -662,6 +663,14 @@ def run_lanes(engines, rank, world, n_steps, device, on_step_end=None, slices_pe
     return sum(solved)
 
 
+def _refuse_salame(engines):
+    """<beam>.do_salame changes the beam's weights during step 0; the hand-off between stages does not carry them"""
+    for e in engines:
+        if getattr(e, "deck", None) and e.deck.get("beam_do_salame", 0):
+            raise NotImplementedError("beam_do_salame: SALAME runs on one engine (SliceEngine.run_step); the pipeline's hand-off does "
+                                      "not carry the weights it changes in step 0")
+
+
 def _refuse_adaptive_ring(world):
     if world > 1:
         raise NotImplementedError("hipace.dt = adaptive needs every stage in one process (run_local_pipeline / run_lanes with "
@@ -691,6 +700,7 @@ def _stage(engine, rank, world, n_steps, device, on_step_end=None, slices_per_st
     begin_step.  The time does not travel through a transport: an adaptive deck with stages in other processes is refused.
     Returns the number of slices this rank solved.
     """
+    _refuse_salame([engine])
     nz = engine.deck["nz"]
     if slices_per_step is None:
         counts = [nz] * world
@@ -933,4 +943,5 @@ def run_local_pipeline(engines, n_steps, device, on_step_end=None, slices_per_st
     by stream events (`LocalEdge`; MultiBuffer.cpp:299-308, the reference's in-process "send to myself").  While one step
     sits in a latency-bound phase -- the lower multigrid levels, a DST pass, a launch gap -- the kernels of the others fill
     the device.  One host thread drives all engines (round 2 had one thread per engine).  Returns the number of slices solved."""
+    _refuse_salame(engines)
     return run_lanes(engines, 0, 1, n_steps, device, on_step_end, slices_per_step)

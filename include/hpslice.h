@@ -305,7 +305,20 @@ typedef struct {
     double adaptive_density, max_time, beam_uz_std;
     /* beams.external_E(x,y,z,t) = ... ext_Ez_slope*z (z of the particle; ExternalFields.H:29-56), beside ext_E_slope */
     double ext_Ez_slope;
+    /* <beam>.do_salame (salame/Salame.cpp; Hipace.cpp:673-678): during step 0 the weights of every beam slice are scaled so
+     * that the jz-weighted mean of Ez on the slice behind it follows the target.  hipace.salame_n_iter (0 -> 5),
+     * salame_relative_tolerance (0 -> 1e-4), salame_do_advance (the ABI reads the negation, so that 0 keeps the default "on").
+     * The reference's parsed salame_Ez_target(zeta, zeta_initial, Ez_initial) is the linear family Ez_initial +
+     * salame_Ez_target_slope (zeta - zeta_initial) here (slope 0: the reference's default).  Explicit solver, static beam
+     * (hipace.dt = 0), a grid current as the driver; DESIGN 8e says what is refused. */
+    int beam_do_salame; int salame_n_iter; double salame_relative_tolerance; int salame_no_advance;
+    double salame_Ez_target_slope;
 } hps_deck;
+
+/* The SALAME slice (fields/Fields.cpp:111-114): twelve planes appended behind the engine's own components (and behind
+ * "aabs"), only in a deck with beam_do_salame: the first one is component hps_engine_slab().ncomp - HPS_SAL_NCOMP. */
+enum { HPS_SAL_EZ_TARGET = 0, HPS_SAL_EZ_NO_SALAME, HPS_SAL_EZ, HPS_SAL_JX, HPS_SAL_JY, HPS_SAL_JZB, HPS_SAL_BX, HPS_SAL_BY,
+       HPS_SAL_SY, HPS_SAL_SX, HPS_SAL_SY_BACK, HPS_SAL_SX_BACK, HPS_SAL_NCOMP };
 
 /* slab component indices of the engine (explicit-solver layout of fields/Fields.cpp:70-122) */
 enum { HPS_C_N_JXB = 0, HPS_C_N_JYB, HPS_C_CHI, HPS_C_SY, HPS_C_SX, HPS_C_EXMBY, HPS_C_EYPBX,
@@ -506,7 +519,9 @@ int hps_engine_set_beam_storage (void* handle, double* storage_dev /* [7*nbeam] 
 int hps_engine_initial_beam (void* handle, double* dst_dev);
 /* hipace.dt != 0: the beam lives in one SoA over all particles (head slice first) whose slice boundaries move when
  * particles slip (hipace_amd/csrc/beam.hip).  Copies the boundaries [nz+1] and, if soa_host != NULL, the seven
- * arrays x y z ux uy uz w ([7][nbeam], nbeam = hps_engine_beam_info) to the host; synchronises the stream. */
+ * arrays x y z ux uy uz w ([7][nbeam], nbeam = hps_engine_beam_info) to the host; synchronises the stream.  A static beam
+ * (hipace.dt = 0) is returned in the same layout, with the offsets of hps_engine_beam_info as boundaries: the weights
+ * SALAME has left are read this way. */
 int hps_engine_beam_state (void* handle, long* boundaries_host, double* soa_host);
 /* Ring hand-off of the moving beam (MultiBuffer::put_data / get_data, utils/MultiBuffer.cpp:444-609).  A message is
  * 1 + 7*cap doubles on the device: [count | x[cap] y[cap] z[cap] ux[cap] uy[cap] uz[cap] w[cap]], cap =
@@ -548,6 +563,31 @@ int hps_engine_record_event (void* handle, int slot, void** event_out);
 int hps_stream_pool_shared_pairs (int device);
 int hps_engine_wait_event (void* handle, void* event);
 int hps_engine_copy_async (void* handle, void* dst_dev, const void* src_dev, long bytes);
+
+/* ---- SALAME (salame/Salame.cpp): the engine's module and its operators ------------------------------------------------
+ * Per slice of step 0 on which the module ran: out_host[4*islice + {0, 1, 2, 3}] = the last weight factor W, W_total =
+ * W * sum(jz) of that iteration (SalameGetW), the iterations used, and flags (bit 0: converged, bit 1: overloaded), the
+ * last two as doubles.  All zeros where it did not run.  Synchronises the stream; HPS_ERR_ARG without beam_do_salame. */
+int hps_engine_salame_stats (void* handle, double* out_host /* [4*nz] */);
+/* SalameOnlyAdvancePlasma (Salame.cpp:262-339): every valid particle gathers Bx, By (components bx_comp, by_comp) at
+ * (x_prev, y_prev) with the plain shape of depos_order and stores ux = 1.5 dz (q/m) By, uy = -1.5 dz (q/m) Bx, q times
+ * ion_lev with can_ionize.  Nothing else of the sheet is touched. */
+int hps_salame_only_advance (hps_slab slab, hps_plasma plasma, hps_geom geom, int bx_comp, int by_comp, double charge,
+                             double mass, int depos_order, int can_ionize, hps_stream stream);
+/* SalameGetJxJyFromBxBy (:228-260), valid cells: jx = 1.5 dz chi By / mu0, jy = -1.5 dz chi Bx / mu0 */
+int hps_salame_jxjy_from_bxby (hps_slab slab, hps_geom geom, int bx_comp, int by_comp, int chi_comp, int jx_comp, int jy_comp,
+                               hps_stream stream);
+/* SalameInitializeSxSyWithBeam (:192-225), valid cells: Sy = -mu0 d_y jz, Sx = mu0 d_x jz (centred differences) */
+int hps_salame_sxsy_from_jz (hps_slab slab, hps_geom geom, int jz_comp, int sy_comp, int sx_comp, hps_stream stream);
+/* The four sums of SalameGetW (:341-405) over the valid cells, in one pass: out4_host = {sum jz Ez_target, sum jz
+ * Ez_no_salame, sum jz Ez, sum jz}.  Deterministic (fixed cell-to-lane map, fixed butterfly, ordered fold of the
+ * workgroups' partial sums, no atomics): equal planes give bit-equal sums.  scratch_dev: 4*257 doubles on the device.
+ * Synchronises the stream. */
+int hps_salame_get_w (hps_slab slab, int ez_target_comp, int ez_no_salame_comp, int ez_comp, int jz_comp, double* scratch_dev,
+                      double* out4_host, hps_stream stream);
+/* SalameMultiplyBeamWeight (:407-437) on the n weights at w_dev: w *= W; W = 0 stores an exact 0 (such a particle
+ * deposits nothing and is left out of the in-situ beam count of a SALAME deck). */
+int hps_salame_scale_beam_slice (double* w_dev, long n, double W, hps_stream stream);
 
 /* ---- adaptive time step controller (utils/AdaptiveTimeStep.cpp): host only, no device call ---------------------------
  * One controller per rank (or pipeline stage), created from the deck (dt_adaptive and the fields behind it; beam charge
