@@ -74,7 +74,9 @@ class Fields:
 class PlasmaSheet:
     """Pure-SoA plasma sheet (particles/plasma/PlasmaParticleContainer.H:21-50)."""
 
-    def __init__(self, real, valid=None, ion_lev=None, device="cuda"):
+    def __init__(self, real, valid=None, ion_lev=None, device="cuda", key=None):
+        """key: per-particle integers, unique within the sheet, stored as key + 1 in the id bits of idcpu (what the
+        engine's lattice particles carry: the key of the ionisation and collision draws); None: id 1 for every particle."""
         real = np.ascontiguousarray(real, dtype=np.float64)
         assert real.shape[0] == 11
         self.n = real.shape[1]
@@ -82,6 +84,9 @@ class PlasmaSheet:
         if valid is None:
             valid = np.ones(self.n, dtype=np.int32)
         idcpu = np.where(np.asarray(valid) != 0, np.uint64(ID_VALID | (1 << 24)), np.uint64(1 << 24)).astype(np.uint64)
+        if key is not None:
+            ids = (np.asarray(key, dtype=np.uint64) + np.uint64(1)) << np.uint64(24)
+            idcpu = (idcpu & np.uint64(ID_VALID)) | ids
         self.idcpu = torch.as_tensor(idcpu.view(np.int64)).to(device).contiguous()
         if ion_lev is None:
             ion_lev = np.zeros(self.n, dtype=np.int32)
@@ -205,6 +210,23 @@ def AdvancePlasmaParticles(plasma, fields, geom, charge, mass, depos_order, Psi,
                                                         _iarr([Psi, Ez, Bx, By, Bz]), aabs, charge, mass, depos_order,
                                                         int(temp_slice), n_subcycles, int(can_ionize), tiling._h,
                                                         C.c_void_p(tiling.fallback.data_ptr()), _stream()))
+
+
+def CoulombCollision(plasma_a, plasma_b, geom, charge_a, mass_a, charge_b=None, mass_b=None, can_ionize_a=False,
+                     can_ionize_b=False, coulomb_log=-1.0, background_density_SI=0.0, seed=0, collision=0, step=0, islice=0,
+                     tiling_a=None, tiling_b=None):
+    """doPlasmaPlasmaCoulombCollision (particles/collisions/CoulombCollision.cpp:59-236) over two PlasmaSheets -- the same
+    sheet twice collides a species with itself.  ux_half, uy_half, psi_half are rewritten in place.  Returns (pairs
+    collided, overfull cells); see hps_collide_plasma."""
+    if plasma_b is plasma_a or charge_b is None:
+        charge_b, mass_b, can_ionize_b = charge_a, mass_a, can_ionize_a
+    pairs, over = C.c_long(), C.c_long()
+    check(_lib.lib().hps_collide_plasma(plasma_a.struct(), tiling_a._h if tiling_a is not None else None,
+                                        plasma_b.struct(), tiling_b._h if tiling_b is not None else None, geom.c, geom.nx, geom.ny,
+                                        charge_a, mass_a, int(can_ionize_a), charge_b, mass_b, int(can_ionize_b), coulomb_log,
+                                        background_density_SI, seed, collision, step, islice, C.byref(pairs), C.byref(over),
+                                        _stream()))
+    return pairs.value, over.value
 
 
 def record_particle_dispatch(on=True):
@@ -410,6 +432,8 @@ class SliceEngine:
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
         if tile_size is not None:
             check(_lib.lib().hps_engine_set_tiling(self._h, tile_size, sort_period or 128))
+        for a, b, coulomb_log, seed in deck.get("collisions", ()):      # not a member of hps_deck: applied through the setter
+            self.add_collision(a, b, coulomb_log, seed)
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -444,6 +468,16 @@ class SliceEngine:
 
     def set_tiling(self, tile_size=16, sort_period=128):
         check(_lib.lib().hps_engine_set_tiling(self._h, tile_size, sort_period))
+
+    def add_collision(self, species_a=0, species_b=0, coulomb_log=-1.0, seed=0):
+        """hipace.collisions: one more Coulomb collision between species 0 (plasma) / 1 (ion), before the first begin_step
+        (hps_engine_add_collision); coulomb_log <= 0 = computed per pair."""
+        check(_lib.lib().hps_engine_add_collision(self._h, species_a, species_b, coulomb_log, seed))
+
+    def collision_stats(self):
+        a, b = C.c_long(), C.c_long()
+        check(_lib.lib().hps_engine_collision_stats(self._h, C.byref(a), C.byref(b)))
+        return dict(pairs_collided=a.value, overfull_cells=b.value)
 
     # ---- ring hand-off of a moving beam (hipace.dt != 0) ------------------------------------------
     @property

@@ -42,6 +42,15 @@ struct LaserState;      // laser.hip
 struct BeamSoA { double *x, *y, *z, *ux, *uy, *uz, *w; int* nsub;      // moving beam (beam.hip); nsub < 0: absorbed
                  double *sx, *sy, *sz; };                              // spin (do_spin_tracking), null otherwise
 
+// cell lists of the collision kernels (collisions.hip): per species slot the exclusive cell offsets [ncells + 1] and the
+// cell-sorted particle indices; cnt [ncells + 1] is shared (zero between launches); stats = {pairs collided, overfull cells}
+struct CollScratch {
+    unsigned *cnt = nullptr, *off[2] = {nullptr, nullptr}, *perm[2] = {nullptr, nullptr};
+    long cap[2] = {0, 0}; int ncells = 0; void* temp = nullptr; size_t temp_bytes = 0; unsigned long long* stats = nullptr;
+    CollScratch () = default; CollScratch (const CollScratch&) = delete; CollScratch& operator= (const CollScratch&) = delete;
+    ~CollScratch ();
+};
+
 struct Engine {
     hps_deck d{};
     hps_geom gm{};
@@ -198,6 +207,11 @@ struct Engine {
     int salame_module (int islice);
     int salame_solve_ez ();
     int run_step ();
+    // hipace.collisions (collisions.hip): plasma-plasma Coulomb collisions, species 0 = plasma, 1 = ion; run in order at the
+    // end of every slice (Hipace.cpp:711-712).  Empty: no launch, no allocation.
+    struct Collision { int a, b; double coulomb_log; unsigned long long seed; };
+    std::vector<Collision> coll; CollScratch coll_scratch; bool step_begun = false;
+    int collide_slice (int islice);
 };
 
 int ion_create (Engine& E);                                                  // ionization.hip

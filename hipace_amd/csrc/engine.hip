@@ -877,6 +877,7 @@ int Engine::begin_step ()
     HPS_REQUIRE(!(d.dt_adaptive && steps_begun == 0 && d.beam_profile < 0 && !host_beam),
                 "hps_engine_begin_step: hipace.dt = adaptive needs a beam (beam_profile = -1 and no hps_engine_set_beam_particles: the sum of weights is 0)");
     if (int e = setup_tiling()) return e;
+    step_begun = true;
     if (moving && steps_begun > 0) {
         // a slice that outgrew the hand-off capacity during the previous step lost particles: refuse to go on
         int ov = 0;
@@ -938,7 +939,7 @@ int Engine::begin_step ()
         const int nppc = d.plasma_ppc[0]*d.plasma_ppc[1];
         hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(np, 256)), dim3(256), 0, st, pl, np, d.nx, d.ny,
                            d.plasma_ppc[0], d.plasma_ppc[1], d.lo[0], d.lo[1], gm.dx, gm.dy,
-                           d.plasma_density*(d.si_units ? gm.dx*gm.dy*gm.dz/nppc : 1.0/nppc), 0, 0,     // scale_fac, PlasmaParticleContainerInit.cpp:40-41
+                           d.plasma_density*(d.si_units ? gm.dx*gm.dy*gm.dz/nppc : 1.0/nppc), 0, coll.empty() ? 0 : 1,     // scale_fac, PlasmaParticleContainerInit.cpp:40-41; collisions: lattice index in the id bits
                            d_prof_r, (int)prof_r.size(), prof_ft, radius_sq);
     }
     if (tiling) { if (int e = resort()) return e; }
@@ -1733,6 +1734,7 @@ int Engine::solve_slice_pc_finish (int islice)
     else        { if ((e = hps_advance_plasma(slab, pl, gm, comp_push, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
     insitu_beam(islice);
     if (moving && nbeam > 0) { if ((e = beam_push_moving(*this, islice))) return e; }
+    if (!coll.empty()) { if ((e = collide_slice(islice))) return e; }      // doCoulombCollision (Hipace.cpp:711-712)
     mark();   // b8
     // ShiftSlices (fields/Fields.cpp:600-603): PCPrevIter <- Previous <- This for Bx By, Previous <- This for jx jy
     {   CompList dst{6, {HPS_PC_PIT_BX, HPS_PC_PIT_BY, HPS_PC_P_BX, HPS_PC_P_BY, HPS_PC_P_JX, HPS_PC_P_JY}};
@@ -1933,7 +1935,7 @@ int Engine::solve_slice_begin (int islice)
     // species, nothing that reads the fields between the solve and the push) enqueues the push BEHIND the speculated
     // V-cycles, gated on the solve's own stopping rule, and only then waits for the norms: the device goes from the last
     // V-cycle straight into the push instead of idling until the host has seen the norms and launched it.
-    const bool fuse = fuse_push_deposit && tiling && islice > 0 && !moving && c_aabs < 0 && ion.n == 0 && np > 0 && tiling->sorted_n == np && !sal;
+    const bool fuse = fuse_push_deposit && coll.empty() && tiling && islice > 0 && !moving && c_aabs < 0 && ion.n == 0 && np > 0 && tiling->sorted_n == np && !sal;
     const bool gated = gate_push && tiling && !fuse && ion.n == 0 && np > 0 && tiling->sorted_n == np && !diagnostics && !d_fd && !d_insitu && !sal;
     // ... and with an ionisable species on tiles: its field bounds, its push (which takes the ADK decisions and appends the
     // electrons) and the electrons' push, all behind the speculated V-cycles; the two pushes are gated (HPS_GATED_ION_PUSH=0: off)
@@ -2064,6 +2066,7 @@ int Engine::solve_slice_finish (int islice)
     // beam push and hand-off of the slipped particles (Hipace.cpp:704-706)
     insitu_beam(islice);
     if (moving && nbeam > 0) { if ((e = beam_push_moving(*this, islice))) return e; }
+    if (!coll.empty()) { if ((e = collide_slice(islice))) return e; }      // doCoulombCollision (Hipace.cpp:711-712)
     mark();   // b8
     // ShiftSlices (fields/Fields.cpp:588-604)
     // (lazy_shift: left to the start of the next slice, where it shares a pass with InitializeSlices; anything that looks at

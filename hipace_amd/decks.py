@@ -258,6 +258,15 @@ def blowout_wake_SI():
     return d
 
 
+def collisions_SI(coulomb_log=-1.0, seed=0):
+    """tests/collisions.SI.1Rank.sh: examples/blowout_wake/inputs_SI with hipace.collisions = collision1, collision1.species =
+    plasma plasma (CoulombLog not given: computed per pair).  `collisions` is no member of hps_deck: SliceEngine turns the
+    entry (species_a, species_b, CoulombLog, seed) into hps_engine_add_collision calls."""
+    d = blowout_wake_SI()
+    d["collisions"] = [(0, 0, coulomb_log, seed)]
+    return d
+
+
 def linear_wake_SI():
     """tests/linear_wake.SI.1Rank.sh (examples/linear_wake/inputs_SI + rho)."""
     d = linear_wake()

@@ -692,6 +692,37 @@ int hps_ring_recv_landed (void* ring, void* done_event);          /* 1: that rec
  * thread polls hps_ring_recv_landed first and gives its other stages their turn (examples/pipeline_host.cpp). */
 int hps_ring_engine_wait (void* ring, void* engine, void* done_event);
 
+/* ---- binary Coulomb collisions between plasma species (hipace.collisions) ------------------------------------------------
+ * doPlasmaPlasmaCoulombCollision (particles/collisions/CoulombCollision.cpp:59-236, with ElasticCollisionPerez.H,
+ * UpdateMomentumPerez.H, ComputeTemperature.H, ShuffleFisherYates.H): the particles of sheet a and sheet b that share a cell
+ * of the nx x ny box (cell = int((x - geom.plo[0])/dx), int((y - geom.plo[1])/dy)) collide pairwise and have ux_half, uy_half,
+ * psi_half rewritten; the same sheet twice = collisions within one species.  Invalid particles (valid bit clear or w == 0)
+ * and particles outside the box take no part.  coulomb_log <= 0: computed per pair.  In normalised units
+ * background_density_SI must be > 0.  can_ionize: the charge is multiplied by ion_lev as the reference does it.
+ * Random numbers are counter based: a draw is a function of (seed, collision, step, islice, cell, pair, draw index), and a
+ * cell's list is ordered by the id bits of idcpu (bits 24..62, which must be unique within a sheet) before it is shuffled, so
+ * the result does not depend on the order of the sheets.  tiling_a / tiling_b: the tilings the sheets are ordered by, or
+ * NULL; the cell lists are built from the positions for every sheet, so they do not change the result.
+ * Allocates its cell lists and synchronises the stream (the test surface of the kernels; the engine keeps its lists).
+ * *pairs_collided_host: pairs with relative momentum (the others are left as they are); *overfull_cells_host: cells whose
+ * lists did not fit the LDS stage and were worked on in global memory.  Either may be NULL. */
+int hps_collide_plasma (hps_plasma a, void* tiling_a, hps_plasma b, void* tiling_b, hps_geom geom, int nx, int ny,
+                        double charge_a, double mass_a, int can_ionize_a, double charge_b, double mass_b, int can_ionize_b,
+                        double coulomb_log, double background_density_SI, unsigned long long seed, int collision,
+                        int step, int islice, long* pairs_collided_host, long* overfull_cells_host, hps_stream stream);
+/* Engine: one more collision between species_a and species_b (0 = the plasma, 1 = the species "ion"), run in the order of
+ * the calls at the end of every slice, behind the plasma and beam pushes and ahead of ShiftSlices (Hipace.cpp:711-712); the
+ * predictor-corrector loop collides once per slice, behind its committing push.  Call after hps_engine_create and before the
+ * first hps_engine_begin_step.  coulomb_log <= 0: automatic.  With a collision configured the plasma's particles carry their
+ * lattice index in the id bits, and the fused push + deposit schedule (hps_engine_set_fusion) is off: it would deposit the
+ * pushed momenta before they collide.  Refused: normalised units without background_density_SI; species 1 without ion_on;
+ * a call after the first hps_engine_begin_step (HPS_ERR_ARG each); an ion species that can still ionise (ion_init_level <
+ * ion_Z: released electrons carry no unique key; HPS_ERR_UNSUPPORTED).  An engine without a collision launches nothing new. */
+#define HPS_MAX_COLLISIONS 8
+int hps_engine_add_collision (void* handle, int species_a, int species_b, double coulomb_log, unsigned long long seed);
+/* pairs collided and overfull cells since hps_engine_create; synchronises the stream */
+int hps_engine_collision_stats (void* handle, long* pairs_collided, long* overfull_cells);
+
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);
 int hps_memcpy_h2d (void* dst_dev, const void* src_host, long bytes);
