@@ -38,6 +38,10 @@ class Plasma(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in PL_REAL] + [("idcpu", C.c_void_p), ("ion_lev", C.c_void_p), ("n", C.c_long)]
 
 
+class BeamSlice(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("x", "y", "z", "ux", "uy", "uz", "w")] + [("nsub", C.c_void_p), ("n", C.c_long)]
+
+
 class Geom(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("dx", "dy", "dz", "xoff", "yoff", "c", "ep0", "mu0", "q_e", "m_e")] + \
                [("plo", C.c_double * 2), ("phi", C.c_double * 2), ("bc", C.c_int), ("normalized", C.c_int)]
@@ -245,6 +249,10 @@ _SIGS = {
                                      C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_void_p]),
     "hps_engine_add_collision": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_ulonglong]),
     "hps_engine_collision_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "hps_collide_beam_plasma": (C.c_int, [BeamSlice, Plasma, Geom, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          C.c_int, C.c_double, C.c_double, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_double,
+                                          C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_void_p]),
+    "hps_engine_add_beam_collision": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_ulonglong]),
     "hps_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_device_count": (C.c_int, [C.POINTER(C.c_int)]),

@@ -229,6 +229,43 @@ def CoulombCollision(plasma_a, plasma_b, geom, charge_a, mass_a, charge_b=None, 
     return pairs.value, over.value
 
 
+class BeamSlice:
+    """A beam slice on the device for BeamPlasmaCollision: soa = (7, n) array x y z ux uy uz w (the rows of
+    SliceEngine.beam_state), nsub = per-particle sub-cycle counters (< 0: absorbed) or None."""
+
+    def __init__(self, soa, nsub=None, device="cuda"):
+        soa = np.ascontiguousarray(soa, dtype=np.float64)
+        assert soa.ndim == 2 and soa.shape[0] == 7
+        self.n = soa.shape[1]
+        self.soa = torch.as_tensor(soa).to(device).contiguous()
+        self.nsub = None if nsub is None else torch.as_tensor(np.ascontiguousarray(nsub, dtype=np.int32)).to(device).contiguous()
+        assert self.nsub is None or self.nsub.numel() == self.n
+
+    def struct(self):
+        b = _lib.BeamSlice()
+        base = self.soa.data_ptr()
+        for k, name in enumerate(("x", "y", "z", "ux", "uy", "uz", "w")):
+            setattr(b, name, base + 8 * k * self.n)
+        b.nsub = self.nsub.data_ptr() if self.nsub is not None else None
+        b.n = self.n
+        return b
+
+    def numpy(self):
+        return self.soa.cpu().numpy()
+
+
+def BeamPlasmaCollision(beam, plasma, geom, charge_beam, mass_beam, charge_plasma, mass_plasma, dt, can_ionize_plasma=False,
+                        coulomb_log=-1.0, background_density_SI=0.0, seed=0, collision=0, step=0, islice=0):
+    """doBeamPlasmaCoulombCollision (particles/collisions/CoulombCollision.cpp:238-348) over a BeamSlice and a PlasmaSheet: the
+    beam's ux, uy, uz and the sheet's ux_half, uy_half, psi_half are rewritten in place.  dt: the run's time step in seconds
+    (hipace.dt over omega_p in normalised units).  Returns (pairs collided, overfull cells); see hps_collide_beam_plasma."""
+    pairs, over = C.c_long(), C.c_long()
+    check(_lib.lib().hps_collide_beam_plasma(beam.struct(), plasma.struct(), geom.c, geom.nx, geom.ny, charge_beam, mass_beam,
+                                             charge_plasma, mass_plasma, int(can_ionize_plasma), coulomb_log, background_density_SI,
+                                             seed, collision, step, islice, dt, C.byref(pairs), C.byref(over), _stream()))
+    return pairs.value, over.value
+
+
 def record_particle_dispatch(on=True):
     """Switch the dispatch record of the tiled particle kernels on (emptying it) or off (hps_particles_record)."""
     check(_lib.lib().hps_particles_record(int(on)))
@@ -432,8 +469,11 @@ class SliceEngine:
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
         if tile_size is not None:
             check(_lib.lib().hps_engine_set_tiling(self._h, tile_size, sort_period or 128))
-        for a, b, coulomb_log, seed in deck.get("collisions", ()):      # not a member of hps_deck: applied through the setter
-            self.add_collision(a, b, coulomb_log, seed)
+        for a, b, coulomb_log, seed in deck.get("collisions", ()):      # not a member of hps_deck: applied through the setters
+            if a == "beam":                                             # ("beam", plasma species, CoulombLog, seed)
+                self.add_beam_collision(b, coulomb_log, seed)
+            else:
+                self.add_collision(a, b, coulomb_log, seed)
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -473,6 +513,12 @@ class SliceEngine:
         """hipace.collisions: one more Coulomb collision between species 0 (plasma) / 1 (ion), before the first begin_step
         (hps_engine_add_collision); coulomb_log <= 0 = computed per pair."""
         check(_lib.lib().hps_engine_add_collision(self._h, species_a, species_b, coulomb_log, seed))
+
+    def add_beam_collision(self, plasma_species=0, coulomb_log=-1.0, seed=0):
+        """hipace.collisions with <collision>.species = beam <plasma>: one more collision, between the moving beam and species
+        0 (plasma) / 1 (ion), in the same ordered list as add_collision (hps_engine_add_beam_collision).  With a static beam
+        (hipace.dt = 0) it is accepted and does nothing: every pair's scattering parameter is 0 there."""
+        check(_lib.lib().hps_engine_add_beam_collision(self._h, plasma_species, coulomb_log, seed))
 
     def collision_stats(self):
         a, b = C.c_long(), C.c_long()

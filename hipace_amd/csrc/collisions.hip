@@ -1,4 +1,4 @@
-// collisions.hip -- binary Coulomb collisions between plasma species (gfx950).
+// collisions.hip -- binary Coulomb collisions between plasma species, and between the moving beam and a plasma species (gfx950).
 //
 // Restates particles/collisions/CoulombCollision.cpp::doPlasmaPlasmaCoulombCollision with ElasticCollisionPerez.H,
 // UpdateMomentumPerez.H, ComputeTemperature.H and ShuffleFisherYates.H of the reference (Perez et al., Phys. Plasmas 19,
@@ -14,9 +14,18 @@
 // workgroup, ten workgroups per CU); a cell with more particles works on its
 // segment of the global index list in place and is counted (overfull cells).  Momenta are written by the lane that owns
 // the pair; the only device-wide atomics are the integer cell counters and the two statistics words.
+//
+// Beam-plasma (doBeamPlasmaCoulombCollision, CoulombCollision.cpp:238-348; every is_beam_coll branch of ElasticCollisionPerez.H and
+// ComputeTemperature.H): side 0 of the cell kernel is a beam slice -- BeamSoA plus a range that is read on the device --
+// which carries uz where a plasma particle carries psi.  The functions below take side 0's type as a template argument
+// (hps_plasma or BeamSoA); the plasma-plasma instantiation is the code it was.  A beam particle carries no id: a cell's
+// beam list is put in the lexicographic order of the bit patterns of (x, y, z, ux, uy, uz, w).  The beam's cell list is
+// built first, and the plasma's count and fill passes enter a particle only where the beam has one (k_coll_*_gated), so the
+// plasma list and the cell kernel's work follow the beam's footprint, not the sheet.
 #include "engine.h"
 #include <rocprim/device/device_scan.hpp>
 #include <cfloat>
+#include <type_traits>
 
 namespace hps {
 
@@ -86,14 +95,40 @@ __device__ __forceinline__ unsigned long long coll_pkey (const hps_plasma& p, un
 {
     return (p.idcpu[ip] >> 24) & ((1ULL << 39) - 1);
 }
+// a beam particle's key: the bit patterns of (x, y, z, ux, uy, uz, w), compared lexicographically as unsigned integers.
+// Two particles that tie on all seven are interchangeable, so the order of a list is a function of the set of particles.
+struct BeamKey {
+    unsigned long long k[7];
+    __device__ __forceinline__ bool operator> (const BeamKey& o) const
+    {
+        for (int q = 0; q < 7; ++q) if (k[q] != o.k[q]) return k[q] > o.k[q];
+        return false;
+    }
+    __device__ __forceinline__ bool operator<= (const BeamKey& o) const { return !(*this > o); }
+};
+__device__ __forceinline__ BeamKey coll_pkey (const BeamSoA& b, unsigned ip)
+{
+    return BeamKey{{(unsigned long long)__double_as_longlong(b.x[ip]), (unsigned long long)__double_as_longlong(b.y[ip]),
+                    (unsigned long long)__double_as_longlong(b.z[ip]), (unsigned long long)__double_as_longlong(b.ux[ip]),
+                    (unsigned long long)__double_as_longlong(b.uy[ip]), (unsigned long long)__double_as_longlong(b.uz[ip]),
+                    (unsigned long long)__double_as_longlong(b.w[ip])}};
+}
+// the three momentum rows a collision rewrites: (ux_half, uy_half, psi_half) of a sheet, (ux, uy, uz) of a beam slice
+__device__ __forceinline__ double* coll_ux (const hps_plasma& p) { return p.ux_half; }
+__device__ __forceinline__ double* coll_uy (const hps_plasma& p) { return p.uy_half; }
+__device__ __forceinline__ double* coll_u3 (const hps_plasma& p) { return p.psi_half; }
+__device__ __forceinline__ double* coll_ux (const BeamSoA& b) { return b.ux; }
+__device__ __forceinline__ double* coll_uy (const BeamSoA& b) { return b.uy; }
+__device__ __forceinline__ double* coll_u3 (const BeamSoA& b) { return b.uz; }
 
-// canonical order: ascending id bits (unique within the species).  Insertion sort for short lists, heap sort beyond.
-template <class Idx>
-__device__ void coll_order (const Idx& I, int n, const hps_plasma& p)
+// canonical order: ascending keys (a sheet's id bits, unique within the species; a beam slice's BeamKey).  Insertion sort
+// for short lists, heap sort beyond.
+template <class Idx, class Side>
+__device__ void coll_order (const Idx& I, int n, const Side& p)
 {
     if (n <= COLL_LDS_CAP) {
         for (int i = 1; i < n; ++i) {
-            const unsigned v = I[i]; const unsigned long long kv = coll_pkey(p, v);
+            const unsigned v = I[i]; const auto kv = coll_pkey(p, v);
             int j = i - 1;
             while (j >= 0 && coll_pkey(p, I[j]) > kv) { I[j + 1] = I[j]; --j; }
             I[j + 1] = v;
@@ -101,12 +136,12 @@ __device__ void coll_order (const Idx& I, int n, const hps_plasma& p)
         return;
     }
     auto sift = [&] (int root, int end) {
-        const unsigned v = I[root]; const unsigned long long kv = coll_pkey(p, v);
+        const unsigned v = I[root]; const auto kv = coll_pkey(p, v);
         for (;;) {
             int ch = 2*root + 1;
             if (ch >= end) break;
-            unsigned long long kc = coll_pkey(p, I[ch]);
-            if (ch + 1 < end) { const unsigned long long k2 = coll_pkey(p, I[ch + 1]); if (k2 > kc) { kc = k2; ++ch; } }
+            auto kc = coll_pkey(p, I[ch]);
+            if (ch + 1 < end) { const auto k2 = coll_pkey(p, I[ch + 1]); if (k2 > kc) { kc = k2; ++ch; } }
             if (kc <= kv) break;
             I[root] = I[ch]; root = ch;
         }
@@ -126,17 +161,18 @@ __device__ void coll_shuffle (const Idx& I, int n, unsigned long long cell_key, 
     }
 }
 
-// ComputeTemperature (plasma branch)
-template <class Idx>
-__device__ double coll_temperature (const Idx& I, int n, const hps_plasma& p, double m, double c, double inv_c2)
+// ComputeTemperature: the plasma branch for a sheet, the beam branch (is_beam_coll, :30-34) for a beam slice
+template <class Idx, class Side>
+__device__ double coll_temperature (const Idx& I, int n, const Side& p, double m, double c, double inv_c2)
 {
+    constexpr bool BEAM = std::is_same<Side, BeamSoA>::value;
     if (n == 0) return 0.0;
     double vx = 0.0, vy = 0.0, vz = 0.0, vs = 0.0;
     for (int i = 0; i < n; ++i) {
         const unsigned ip = I[i];
-        const double ux = p.ux_half[ip], uy = p.uy_half[ip], psi = p.psi_half[ip];
-        const double gm = (1.0 + (ux*ux + uy*uy)*inv_c2 + psi*psi)/(2.0*psi);
-        const double uz = c*(gm - psi);
+        const double ux = coll_ux(p)[ip], uy = coll_uy(p)[ip], psi = coll_u3(p)[ip];
+        const double gm = BEAM ? sqrt(1.0 + (ux*ux + uy*uy + psi*psi)*inv_c2) : (1.0 + (ux*ux + uy*uy)*inv_c2 + psi*psi)/(2.0*psi);
+        const double uz = BEAM ? psi : c*(gm - psi);
         const double us = ux*ux + uy*uy + uz*uz;
         vx += ux/gm; vy += uy/gm; vz += uz/gm; vs += us/gm/gm;
     }
@@ -266,11 +302,13 @@ __device__ bool coll_update (double& u1x, double& u1y, double& u1z, const double
     return true;
 }
 
-// ElasticCollisionPerez over the lists I1[0, NI1) of species side 0 and I2[0, NI2) of species side 1
-template <class Idx>
-__device__ unsigned coll_elastic (const CollArgs& a, const Idx& I1, int NI1, const Idx& I2, int NI2, unsigned long long cell_key)
+// ElasticCollisionPerez over the lists I1[0, NI1) of species side 0 (P1: a sheet, or a beam slice -- is_beam_coll) and
+// I2[0, NI2) of species side 1
+template <class Idx, class Side>
+__device__ unsigned coll_elastic (const CollArgs& a, const Side& P1, const Idx& I1, int NI1, const Idx& I2, int NI2, unsigned long long cell_key)
 {
-    const hps_plasma& P1 = a.s[0].p; const hps_plasma& P2 = a.s[1].p;
+    constexpr bool BEAM = std::is_same<Side, BeamSoA>::value;
+    const hps_plasma& P2 = a.s[1].p;
     double q1 = a.s[0].q, q2 = a.s[1].q;
     const double m1 = a.s[0].m, m2 = a.s[1].m;
     double T1t = -1.0, T2t = -1.0;
@@ -304,18 +342,19 @@ __device__ unsigned coll_elastic (const CollArgs& a, const Idx& I1, int NI1, con
     for (int k = 0; k < NK; ++k) {
         const unsigned a1 = I1[i1], a2 = I2[i2];
         // the charge follows the ion's level; the reference's product runs on from pair to pair
-        if (a.s[0].can_ionize) q1 *= P1.ion_lev[a1];
+        if constexpr (!BEAM) { if (a.s[0].can_ionize) q1 *= P1.ion_lev[a1]; }      // (can_ionize1 = false for a beam)
         if (a.s[1].can_ionize) q2 *= P2.ion_lev[a2];
-        double u1x = P1.ux_half[a1], u1y = P1.uy_half[a1]; const double psi1 = P1.psi_half[a1];
+        double u1x = coll_ux(P1)[a1], u1y = coll_uy(P1)[a1]; const double psi1 = coll_u3(P1)[a1];      // a beam's "psi1" is its uz
         double u2x = P2.ux_half[a2], u2y = P2.uy_half[a2]; const double psi2 = P2.psi_half[a2];
-        double g1 = (1.0 + u1x*u1x*a.inv_c2 + u1y*u1y*a.inv_c2 + psi1*psi1)/(2.0*psi1);
+        double g1 = BEAM ? sqrt(1.0 + (u1x*u1x + u1y*u1y + psi1*psi1)*a.inv_c2)
+                         : (1.0 + u1x*u1x*a.inv_c2 + u1y*u1y*a.inv_c2 + psi1*psi1)/(2.0*psi1);
         double g2 = (1.0 + u2x*u2x*a.inv_c2 + u2y*u2y*a.inv_c2 + psi2*psi2)/(2.0*psi2);
-        double u1z = a.c*(g1 - psi1), u2z = a.c*(g2 - psi2);
-        const double dt_fac = 0.5*(g1/psi1 + g2/psi2);
+        double u1z = BEAM ? psi1 : a.c*(g1 - psi1), u2z = a.c*(g2 - psi2);
+        const double dt_fac = BEAM ? 1.0 : 0.5*(g1/psi1 + g2/psi2);
         if (coll_update(u1x, u1y, u1z, g1, u2x, u2y, u2z, g2, n1, n2, n12, q1, m1, P1.w[a1], q2, m2, P2.w[a2],
                         a.dt*dt_fac, a.L, lmdD, a.normalized != 0, cell_key, (unsigned)k)) ++collided;
         g1 = sqrt(1.0 + (u1x*u1x + u1y*u1y + u1z*u1z)*a.inv_c2);
-        P1.ux_half[a1] = u1x; P1.uy_half[a1] = u1y; P1.psi_half[a1] = g1 - u1z*a.inv_c;
+        coll_ux(P1)[a1] = u1x; coll_uy(P1)[a1] = u1y; coll_u3(P1)[a1] = BEAM ? u1z : g1 - u1z*a.inv_c;
         g2 = sqrt(1.0 + (u2x*u2x + u2y*u2y + u2z*u2z)*a.inv_c2);
         P2.ux_half[a2] = u2x; P2.uy_half[a2] = u2y; P2.psi_half[a2] = g2 - u2z*a.inv_c;
         ++i1; if (i1 == NI1) i1 = 0;
@@ -332,11 +371,11 @@ __device__ unsigned coll_cell (const CollArgs& a, const Idx& IA, int nA, const I
         const int half = nA/2;                       // (start + stop)/2 of the reference, relative to start
         coll_shuffle(IA, half, cell_key, 0u);
         Idx I2 = IA; I2.b = &IA[half];
-        return coll_elastic(a, IA, half, I2, nA - half, cell_key);
+        return coll_elastic(a, a.s[0].p, IA, half, I2, nA - half, cell_key);
     }
     coll_order(IA, nA, a.s[0].p); coll_order(IB, nB, a.s[1].p);
     coll_shuffle(IA, nA, cell_key, 0u); coll_shuffle(IB, nB, cell_key, 1u);
-    return coll_elastic(a, IA, nA, IB, nB, cell_key);
+    return coll_elastic(a, a.s[0].p, IA, nA, IB, nB, cell_key);
 }
 
 __global__ __launch_bounds__(COLL_WG)
@@ -360,6 +399,122 @@ void k_coll_cells (CollArgs a)
         atomicAdd(a.stats + 1, 1ULL);
         IdxGlb IA{a.s[0].perm + sA}, IB{a.s[1].perm + sB};
         collided = coll_cell(a, IA, (int)nA, IB, (int)nB, cell_key);
+    }
+    if (collided) atomicAdd(a.stats, (unsigned long long)collided);
+}
+
+// ---- beam-plasma: the beam side's cell list, the plasma's gated on it, the cell kernel with a beam slice as side 0 ------
+// The beam side: slice p of the moving beam, [B[p], B[p + 1]) read on the device -- behind k_beam_partition of that slice, so
+// particles that slipped on to slice p + 1 are outside it --, or [0, n) of the free operator (B null).  size: length of the
+// SoA's arrays; cap: entries the index list has room for.  Both clamp the range: the launch is sized from a host-side bound.
+struct CollBeam { BeamSoA b; const long* B; int p; long n, size, cap; };
+
+__device__ __forceinline__ void coll_beam_range (const CollBeam& m, long* first, long* count)
+{
+    long f = 0, c = m.n;
+    if (m.B) { f = m.B[m.p]; c = m.B[m.p + 1] - f; }
+    if (f < 0) f = 0;
+    if (f > m.size) f = m.size;
+    if (c > m.size - f) c = m.size - f;
+    if (c > m.cap) c = m.cap;
+    if (c < 0) c = 0;
+    *first = f; *count = c;
+}
+
+// absorbed particles (nsub < 0), particles without weight and particles outside the box are in no cell
+__device__ __forceinline__ bool coll_beam_cell_of (const CollArgs& a, const BeamSoA& b, long ip, int* cell)
+{
+    if ((b.nsub && b.nsub[ip] < 0) || b.w[ip] == 0.0) return false;
+    const int i = (int)((b.x[ip] - a.plo0)*a.dxi), j = (int)((b.y[ip] - a.plo1)*a.dyi);
+    if (b.x[ip] < a.plo0 || b.y[ip] < a.plo1 || i < 0 || i >= a.nx || j < 0 || j >= a.ny) return false;
+    *cell = i + j*a.nx;
+    return true;
+}
+
+__global__ __launch_bounds__(256)
+void k_coll_beam_count (CollArgs a, CollBeam m, unsigned* cnt)
+{
+    long first, count;
+    coll_beam_range(m, &first, &count);
+    for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
+        int cell;
+        if (coll_beam_cell_of(a, m.b, first + t, &cell)) atomicAdd(cnt + cell, 1u);
+    }
+}
+
+__global__ __launch_bounds__(256)
+void k_coll_beam_fill (CollArgs a, CollBeam m, unsigned* cnt)
+{
+    long first, count;
+    coll_beam_range(m, &first, &count);
+    for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
+        int cell;
+        if (coll_beam_cell_of(a, m.b, first + t, &cell))
+            a.s[0].perm[a.s[0].off[cell] + atomicSub(cnt + cell, 1u) - 1u] = (unsigned)(first + t);
+    }
+}
+
+// coll_cell_of for the plasma side of a beam collision: only where the beam has a particle (side 0's offsets are final).
+// The cell comes from x, y alone, so a particle outside the beam's footprint costs two loads.
+__device__ __forceinline__ bool coll_cell_of_gated (const CollArgs& a, const hps_plasma& p, long ip, int* cell)
+{
+    const double x = p.x[ip], y = p.y[ip];
+    const int i = (int)((x - a.plo0)*a.dxi), j = (int)((y - a.plo1)*a.dyi);
+    if (x < a.plo0 || y < a.plo1 || i < 0 || i >= a.nx || j < 0 || j >= a.ny) return false;
+    const int c = i + j*a.nx;
+    if (a.s[0].off[c + 1] == a.s[0].off[c]) return false;
+    if (!(p.idcpu[ip] & HPS_ID_VALID) || p.w[ip] == 0.0) return false;
+    *cell = c;
+    return true;
+}
+
+__global__ __launch_bounds__(256)
+void k_coll_count_gated (CollArgs a, unsigned* cnt)
+{
+    const long ip = (long)blockIdx.x*blockDim.x + threadIdx.x;
+    int cell;
+    if (ip < a.s[1].p.n && coll_cell_of_gated(a, a.s[1].p, ip, &cell)) atomicAdd(cnt + cell, 1u);
+}
+
+__global__ __launch_bounds__(256)
+void k_coll_fill_gated (CollArgs a, unsigned* cnt)
+{
+    const long ip = (long)blockIdx.x*blockDim.x + threadIdx.x;
+    int cell;
+    if (ip < a.s[1].p.n && coll_cell_of_gated(a, a.s[1].p, ip, &cell))
+        a.s[1].perm[a.s[1].off[cell] + atomicSub(cnt + cell, 1u) - 1u] = (unsigned)ip;
+}
+
+// is_same_species = false: both lists ordered and shuffled (slot 0 the beam, slot 1 the plasma), then the pairs
+template <class Idx>
+__device__ unsigned coll_cell_beam (const CollArgs& a, const BeamSoA& b, const Idx& IA, int nA, const Idx& IB, int nB, unsigned long long cell_key)
+{
+    coll_order(IA, nA, b); coll_order(IB, nB, a.s[1].p);
+    coll_shuffle(IA, nA, cell_key, 0u); coll_shuffle(IB, nB, cell_key, 1u);
+    return coll_elastic(a, b, IA, nA, IB, nB, cell_key);
+}
+
+__global__ __launch_bounds__(COLL_WG)
+void k_coll_cells_beam (CollArgs a, BeamSoA b)
+{
+    __shared__ unsigned lds[COLL_LDS_CAP*COLL_WG];
+    const int cell = blockIdx.x*COLL_WG + threadIdx.x;
+    if (cell >= a.nx*a.ny) return;
+    const unsigned sA = a.s[0].off[cell], nA = a.s[0].off[cell + 1] - sA;
+    if (nA < 1) return;                              // no beam particle here: the plasma's list is empty too
+    const unsigned sB = a.s[1].off[cell], nB = a.s[1].off[cell + 1] - sB;
+    if (nB < 1) return;
+    const unsigned long long cell_key = coll_hash(a.key, (unsigned long long)cell);
+    unsigned collided;
+    if (nA + nB <= (unsigned)COLL_LDS_CAP) {
+        IdxLds IA{lds + threadIdx.x}, IB{lds + threadIdx.x + nA*COLL_WG};
+        for (unsigned i = 0; i < nA; ++i) IA[i] = a.s[0].perm[sA + i];
+        for (unsigned i = 0; i < nB; ++i) IB[i] = a.s[1].perm[sB + i];
+        collided = coll_cell_beam(a, b, IA, (int)nA, IB, (int)nB, cell_key);
+    } else {
+        atomicAdd(a.stats + 1, 1ULL);
+        IdxGlb IA{a.s[0].perm + sA}, IB{a.s[1].perm + sB};
+        collided = coll_cell_beam(a, b, IA, (int)nA, IB, (int)nB, cell_key);
     }
     if (collided) atomicAdd(a.stats, (unsigned long long)collided);
 }
@@ -395,6 +550,22 @@ static int coll_reserve (CollScratch& S, int ncells, long n0, long n1)
     return HPS_OK;
 }
 
+// what a plasma-plasma and a beam-plasma collision share: geometry, units, dt in seconds, the slice key
+static CollArgs coll_args (CollScratch& S, const hps_geom& gm, int nx, int ny, double dt, double coulomb_log, double background_density_SI,
+                           unsigned long long seed, int collision, int step, int islice)
+{
+    CollArgs a{};
+    a.nx = nx; a.ny = ny; a.plo0 = gm.plo[0]; a.plo1 = gm.plo[1]; a.dxi = 1.0/gm.dx; a.dyi = 1.0/gm.dy;
+    a.dt = dt;
+    a.L = coulomb_log;
+    // normalised weights are densities in units of the background density; SI weights are numbers of particles
+    a.dens_fac = gm.normalized ? background_density_SI : (1.0/gm.dx)*(1.0/gm.dy)*(1.0/gm.dz);
+    a.c = gm.c; a.inv_c = 1.0/gm.c; a.inv_c2 = 1.0/(gm.c*gm.c); a.normalized = gm.normalized;
+    a.key = coll_hash(coll_hash(coll_hash(coll_hash(seed, 0ULL), (unsigned long long)collision), (unsigned long long)step), (unsigned long long)islice);
+    a.stats = S.stats;
+    return a;
+}
+
 // One collision over two sheets (the same sheet twice: same species), enqueued on st.  S keeps the cell lists.
 int collide_plasma (CollScratch& S, const hps_plasma& pa, const hps_plasma& pb, bool same, const hps_geom& gm, int nx, int ny,
                     double qa, double ma, int can_ionize_a, double qb, double mb, int can_ionize_b, double coulomb_log,
@@ -406,19 +577,11 @@ int collide_plasma (CollScratch& S, const hps_plasma& pa, const hps_plasma& pb, 
     if (pa.n == 0 || pb.n == 0) return HPS_OK;
     const int ncells = nx*ny;
     if (int e = coll_reserve(S, ncells, pa.n, same ? 0 : pb.n)) return e;
-    CollArgs a{};
+    const double wp = std::sqrt(background_density_SI*SI_QE*SI_QE/(SI_EP0*SI_ME));
+    CollArgs a = coll_args(S, gm, nx, ny, gm.normalized ? gm.dz/wp : gm.dz/SI_C, coulomb_log, background_density_SI, seed, collision, step, islice);
     a.s[0] = CollSide{pa, qa, ma, can_ionize_a, S.off[0], S.perm[0]};
     a.s[1] = same ? a.s[0] : CollSide{pb, qb, mb, can_ionize_b, S.off[1], S.perm[1]};
     a.same = same ? 1 : 0;
-    a.nx = nx; a.ny = ny; a.plo0 = gm.plo[0]; a.plo1 = gm.plo[1]; a.dxi = 1.0/gm.dx; a.dyi = 1.0/gm.dy;
-    const double wp = std::sqrt(background_density_SI*SI_QE*SI_QE/(SI_EP0*SI_ME));
-    a.dt = gm.normalized ? gm.dz/wp : gm.dz/SI_C;
-    a.L = coulomb_log;
-    // normalised weights are densities in units of the background density; SI weights are numbers of particles
-    a.dens_fac = gm.normalized ? background_density_SI : (1.0/gm.dx)*(1.0/gm.dy)*(1.0/gm.dz);
-    a.c = gm.c; a.inv_c = 1.0/gm.c; a.inv_c2 = 1.0/(gm.c*gm.c); a.normalized = gm.normalized;
-    a.key = coll_hash(coll_hash(coll_hash(coll_hash(seed, 0ULL), (unsigned long long)collision), (unsigned long long)step), (unsigned long long)islice);
-    a.stats = S.stats;
     for (int side = 0; side < (same ? 1 : 2); ++side) {
         const long n = a.s[side].p.n;
         const dim3 grid((unsigned)((n + 255)/256));
@@ -429,6 +592,40 @@ int collide_plasma (CollScratch& S, const hps_plasma& pa, const hps_plasma& pb, 
         hipLaunchKernelGGL(k_coll_fill, grid, dim3(256), 0, st, a, side, S.cnt);
     }
     hipLaunchKernelGGL(k_coll_cells, dim3((unsigned)((ncells + COLL_WG - 1)/COLL_WG)), dim3(COLL_WG), 0, st, a);
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
+// One collision between a beam slice (side 0) and a sheet, enqueued on st.  bound: host-side upper bound of the slice's
+// size (it sizes the beam's launches; the kernels read the range on the device); dt: the run's time step in seconds.
+// Seven launches: the beam's count, scan and fill, the plasma's gated on the beam's counts, the cell kernel.
+int collide_beam_plasma (CollScratch& S, CollBeam m, long bound, const hps_plasma& pl, const hps_geom& gm, int nx, int ny,
+                         double q_beam, double m_beam, double q_pl, double m_pl, int can_ionize_pl, double coulomb_log,
+                         double background_density_SI, double dt, unsigned long long seed, int collision, int step, int islice, hipStream_t st)
+{
+    HPS_REQUIRE(nx > 0 && ny > 0 && (long)nx*ny < (1L << 31) - 1, "collisions: bad grid");
+    HPS_REQUIRE(pl.n >= 0 && pl.n < (1L << 32) - 1 && m.size >= 0 && m.size < (1L << 32) - 1, "collisions: sheets and beams of up to 2^32 - 2 particles");
+    HPS_REQUIRE(!gm.normalized || background_density_SI > 0.0, "collisions: normalised units need hipace.background_density_SI (Hipace.cpp:239-243)");
+    if (bound <= 0 || m.size == 0 || pl.n == 0) return HPS_OK;
+    const int ncells = nx*ny;
+    // the beam's index list has room for the whole beam: the bound grows from slice to slice, the list is allocated once
+    if (int e = coll_reserve(S, ncells, m.size, pl.n)) return e;
+    m.cap = S.cap[0];
+    CollArgs a = coll_args(S, gm, nx, ny, dt, coulomb_log, background_density_SI, seed, collision, step, islice);
+    a.s[0] = CollSide{hps_plasma{}, q_beam, m_beam, 0, S.off[0], S.perm[0]};
+    a.s[1] = CollSide{pl, q_pl, m_pl, can_ionize_pl, S.off[1], S.perm[1]};
+    a.same = 0;
+    const dim3 gb((unsigned)std::max<long>(1, std::min<long>((std::min(bound, m.size) + 255)/256, 2048))), gp((unsigned)((pl.n + 255)/256));
+    size_t tb = S.temp_bytes;
+    // (cnt is all zero here: allocated so, and the fill kernels count it down again)
+    hipLaunchKernelGGL(k_coll_beam_count, gb, dim3(256), 0, st, a, m, S.cnt);
+    HPS_HIP_CHECK(rocprim::exclusive_scan(S.temp, tb, S.cnt, S.off[0], 0u, (size_t)(ncells + 1), rocprim::plus<unsigned>(), st));
+    hipLaunchKernelGGL(k_coll_beam_fill, gb, dim3(256), 0, st, a, m, S.cnt);
+    hipLaunchKernelGGL(k_coll_count_gated, gp, dim3(256), 0, st, a, S.cnt);
+    tb = S.temp_bytes;
+    HPS_HIP_CHECK(rocprim::exclusive_scan(S.temp, tb, S.cnt, S.off[1], 0u, (size_t)(ncells + 1), rocprim::plus<unsigned>(), st));
+    hipLaunchKernelGGL(k_coll_fill_gated, gp, dim3(256), 0, st, a, S.cnt);
+    hipLaunchKernelGGL(k_coll_cells_beam, dim3((unsigned)((ncells + COLL_WG - 1)/COLL_WG)), dim3(COLL_WG), 0, st, a, m.b);
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
@@ -450,6 +647,20 @@ int Engine::collide_slice (int islice)
         const Collision& c = coll[i];
         const hps_plasma* sp[2] = {&pl, &ion.pl};
         const double q[2] = {d.plasma_charge, d.ion_charge}, m[2] = {d.plasma_mass, d.ion_mass};
+        if (c.beam) {
+            // Species 1 is the beam's slice behind its push and the slipped-particle shift (Hipace.cpp:704-712).  A static beam
+            // (hipace.dt = 0) sits in the per-slice blocks, and every pair's s is 0 there: nothing is launched.  No beam: nothing.
+            if (!moving || nbeam <= 0) continue;
+            const int p = d.nz - 1 - islice;
+            const long bound = beam_bound(p);
+            if (bound <= 0) continue;
+            const double wp = std::sqrt(d.background_density_SI*SI_QE*SI_QE/(SI_EP0*SI_ME));
+            const double dt = gm.normalized ? step_dt/wp : step_dt;      // m_dt, the time step of the run (not dz)
+            const CollBeam bs{bm, d_B, p, 0, nbeam, 0};
+            if (int e = collide_beam_plasma(coll_scratch, bs, bound, *sp[c.b], gm, d.nx, d.ny, d.beam_charge, d.beam_mass != 0.0 ? d.beam_mass : 1.0,
+                                            q[c.b], m[c.b], c.b, c.coulomb_log, d.background_density_SI, dt, c.seed, (int)i, step_index, islice, st)) return e;
+            continue;
+        }
         if (int e = collide_plasma(coll_scratch, *sp[c.a], *sp[c.b], c.a == c.b, gm, d.nx, d.ny, q[c.a], m[c.a], c.a, q[c.b], m[c.b], c.b,
                                    c.coulomb_log, d.background_density_SI, c.seed, (int)i, step_index, islice, st)) return e;
     }
@@ -489,6 +700,47 @@ extern "C" int hps_engine_add_collision (void* h, int species_a, int species_b, 
         return HPS_ERR_UNSUPPORTED;
     }
     E->coll.push_back(Engine::Collision{species_a, species_b, coulomb_log, seed});
+    return HPS_OK;
+}
+
+extern "C" int hps_collide_beam_plasma (hps_beam_slice beam, hps_plasma plasma, hps_geom geom, int nx, int ny, double charge_beam,
+                                        double mass_beam, double charge_plasma, double mass_plasma, int can_ionize_plasma,
+                                        double coulomb_log, double background_density_SI, unsigned long long seed, int collision,
+                                        int step, int islice, double dt, long* pairs_collided_host, long* overfull_cells_host,
+                                        hps_stream stream)
+{
+    HPS_REQUIRE(beam.n >= 0 && (beam.n == 0 || (beam.x && beam.y && beam.z && beam.ux && beam.uy && beam.uz && beam.w)),
+                "hps_collide_beam_plasma: the beam slice needs its seven arrays");
+    hipStream_t st = (hipStream_t)stream;
+    CollScratch S;
+    const CollBeam bs{BeamSoA{beam.x, beam.y, beam.z, beam.ux, beam.uy, beam.uz, beam.w, beam.nsub, nullptr, nullptr, nullptr},
+                      nullptr, 0, beam.n, beam.n, 0};
+    if (int e = collide_beam_plasma(S, bs, beam.n, plasma, geom, nx, ny, charge_beam, mass_beam, charge_plasma, mass_plasma, can_ionize_plasma,
+                                    coulomb_log, background_density_SI, dt, seed, collision, step, islice, st)) return e;
+    return coll_read_stats(S, pairs_collided_host, overfull_cells_host, st);
+}
+
+extern "C" int hps_engine_add_beam_collision (void* h, int plasma_species, double coulomb_log, unsigned long long seed)
+{
+    HPS_REQUIRE(h, "hps_engine_add_beam_collision: null engine");
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(plasma_species == 0 || plasma_species == 1, "hps_engine_add_beam_collision: the plasma species is 0 (plasma) or 1 (ion)");
+    HPS_REQUIRE(!E->step_begun, "hps_engine_add_beam_collision: call before the first hps_engine_begin_step");
+    HPS_REQUIRE((int)E->coll.size() < HPS_MAX_COLLISIONS, "hps_engine_add_beam_collision: at most HPS_MAX_COLLISIONS collisions, of both kinds together");
+    HPS_REQUIRE(E->d.si_units || E->d.background_density_SI > 0.0, "hps_engine_add_beam_collision: collisions in normalised units need hipace.background_density_SI");
+    HPS_REQUIRE(plasma_species == 0 || E->d.ion_on, "hps_engine_add_beam_collision: species 1 needs the species \"ion\" (ion_on)");
+    if (E->d.ion_on && E->d.ion_init_level < E->d.ion_Z) {
+        set_error("hps_engine_add_beam_collision: the species \"ion\" can still ionise, and the electrons it releases carry no unique key for the collision draws");
+        return HPS_ERR_UNSUPPORTED;
+    }
+    if (E->d.dt_adaptive) {
+        set_error("hps_engine_add_beam_collision: hipace.dt = adaptive is not supported with a beam collision: the reference gathers the beam's "
+                  "moments behind the collisions (GatherMinUzSlice, Hipace.cpp:713-716), the engine reduces them inside k_beam_partition, ahead of them");
+        return HPS_ERR_UNSUPPORTED;
+    }
+    Engine::Collision c{0, plasma_species, coulomb_log, seed};
+    c.beam = true;
+    E->coll.push_back(c);
     return HPS_OK;
 }
 

@@ -207,9 +207,10 @@ struct Engine {
     int salame_module (int islice);
     int salame_solve_ez ();
     int run_step ();
-    // hipace.collisions (collisions.hip): plasma-plasma Coulomb collisions, species 0 = plasma, 1 = ion; run in order at the
-    // end of every slice (Hipace.cpp:711-712).  Empty: no launch, no allocation.
-    struct Collision { int a, b; double coulomb_log; unsigned long long seed; };
+    // hipace.collisions (collisions.hip): Coulomb collisions between plasma species, species 0 = plasma, 1 = ion, and between
+    // the moving beam and plasma species b (beam; a is unused); one list, run in order at the end of every slice, behind the
+    // beam's push and partition (Hipace.cpp:704-712).  Empty: no launch, no allocation.
+    struct Collision { int a, b; double coulomb_log; unsigned long long seed; bool beam = false; };
     std::vector<Collision> coll; CollScratch coll_scratch; bool step_begun = false;
     int collide_slice (int islice);
 };

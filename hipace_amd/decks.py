@@ -267,6 +267,16 @@ def collisions_SI(coulomb_log=-1.0, seed=0):
     return d
 
 
+def collisions_beam_SI(coulomb_log=-1.0, seed=0):
+    """tests/collisions_beam.SI.1Rank.sh: examples/blowout_wake/inputs_SI with hipace.collisions = collision1, collision1.species =
+    beam plasma, max_step = 0 and no hipace.dt: the beam is static, the collision's dt is 0 and no pair scatters.  The entry
+    ("beam", plasma species, CoulombLog, seed) reaches hps_engine_add_beam_collision through the SliceEngine constructor."""
+    d = blowout_wake_SI()
+    d["n_steps"] = 1
+    d["collisions"] = [("beam", 0, coulomb_log, seed)]
+    return d
+
+
 def linear_wake_SI():
     """tests/linear_wake.SI.1Rank.sh (examples/linear_wake/inputs_SI + rho)."""
     d = linear_wake()

@@ -22,8 +22,10 @@ the reference's MultiBuffer does with its default unlimited `max_leading_slices`
 1024^2: they are posted `laser_lookahead` slices ahead when the ring does not close (n_steps <= ranks) and a whole step
 ahead when it does (the reference's requirement max_trailing_slices * n_ranks > nslices, MultiBuffer.cpp:87-91).
 
-Collisions (hipace.collisions) need nothing from the hand-off: they act on the plasma sheets of a stage's own engine, and a
-deck's `collisions` entry reaches every stage through the SliceEngine constructor's hps_engine_add_collision calls.
+Collisions (hipace.collisions) need nothing new from the hand-off.  Those between plasma species act on the plasma sheets of a
+stage's own engine.  A beam-plasma collision rewrites the momenta of the moving beam's slice behind its push, on the engine's
+stream, ahead of the slice's export: the message of a slice carries the collided momenta.  A deck's `collisions` entry reaches
+every stage through the SliceEngine constructor's hps_engine_add_collision / hps_engine_add_beam_collision calls.
 
 Dependencies: solving slice k of step s+1 needs the beam of slices k and k-1 of step s (the next slice's jx / jy feed
 the explicit source term, Hipace.cpp:639-657), so a rank trails its predecessor by two slices.

@@ -720,6 +720,42 @@ int hps_collide_plasma (hps_plasma a, void* tiling_a, hps_plasma b, void* tiling
  * ion_Z: released electrons carry no unique key; HPS_ERR_UNSUPPORTED).  An engine without a collision launches nothing new. */
 #define HPS_MAX_COLLISIONS 8
 int hps_engine_add_collision (void* handle, int species_a, int species_b, double coulomb_log, unsigned long long seed);
+/* ---- Coulomb collisions between the moving beam and a plasma species -------------------------------------------------------
+ * doBeamPlasmaCoulombCollision (CoulombCollision.cpp:238-348; the is_beam_coll branches of ElasticCollisionPerez.H and
+ * ComputeTemperature.H): the beam particles of a slice and the sheet's particles that share a cell collide pairwise; the beam
+ * has ux, uy, uz rewritten (gamma = sqrt(1 + u^2/c^2), no 0.5 (g1/psi1 + g2/psi2) factor on dt), the sheet ux_half, uy_half,
+ * psi_half.  A beam slice is seven device arrays of n entries and, optionally, the sub-cycle counters (NULL: none). */
+typedef struct {
+    double *x, *y, *z, *ux, *uy, *uz, *w;
+    int32_t* nsub;               /* nsub[i] < 0: absorbed at the boundary, in no cell; may be NULL */
+    long n;
+} hps_beam_slice;
+/* The free operator (the test surface of the kernels; allocates its cell lists and synchronises the stream).  A beam particle
+ * takes part if nsub >= 0, w != 0 and x, y lie inside the box; the others come back untouched.  The sheet as in
+ * hps_collide_plasma.  dt: the time step of the run IN SECONDS (hipace.dt / omega_p in normalised units, hipace.dt in SI
+ * units) -- not dz.  Draws: the chain of hps_collide_plasma, shuffle slot 0 the beam, slot 1 the plasma.  A beam particle
+ * carries no id: before the shuffle a cell's beam list is ordered lexicographically by the 64-bit patterns of (x, y, z, ux,
+ * uy, uz, w), so the result is a function of the set of particles (two that tie on all seven are interchangeable).  The
+ * plasma's cell list holds only the cells in which the beam has a particle.  Statistics as for hps_collide_plasma. */
+int hps_collide_beam_plasma (hps_beam_slice beam, hps_plasma plasma, hps_geom geom, int nx, int ny, double charge_beam,
+                             double mass_beam, double charge_plasma, double mass_plasma, int can_ionize_plasma,
+                             double coulomb_log, double background_density_SI, unsigned long long seed, int collision,
+                             int step, int islice, double dt, long* pairs_collided_host, long* overfull_cells_host,
+                             hps_stream stream);
+/* Engine: one more collision, between the beam and plasma species plasma_species (0 = the plasma, 1 = the species "ion").  It
+ * joins the ordered list of hps_engine_add_collision (HPS_MAX_COLLISIONS holds for both kinds together; a collision's index
+ * in that list is the `collision` of its draws) and runs where that list runs: behind the beam's push and the hand-over of
+ * the slipped particles to the next slice (Hipace.cpp:704-712), on the beam particles that stay on the slice -- the ones
+ * that slipped collide on the next slice's turn.  dt is the time step of the step that has begun (hipace.dt, over omega_p of
+ * background_density_SI in normalised units).  Slices exported behind the slice (hps_engine_export_beam_slice) carry the
+ * collided momenta.  A static beam (hipace.dt = 0) is accepted and launches nothing: the reference's s is dt times a factor,
+ * 0 for every pair, its scattering angle 0, and the static beam lives in the per-slice blocks, not in the moving beam's
+ * arrays; sheet and slab are those of the engine without the collision.  An engine without a beam accepts it and does nothing.
+ * Refused: normalised units without background_density_SI; species 1 without ion_on; a call after the first
+ * hps_engine_begin_step; more than HPS_MAX_COLLISIONS (HPS_ERR_ARG each); an ion species that can still ionise; hipace.dt =
+ * adaptive, whose beam moments the engine reduces ahead of the collisions where the reference gathers them behind
+ * (HPS_ERR_UNSUPPORTED each). */
+int hps_engine_add_beam_collision (void* handle, int plasma_species, double coulomb_log, unsigned long long seed);
 /* pairs collided and overfull cells since hps_engine_create; synchronises the stream */
 int hps_engine_collision_stats (void* handle, long* pairs_collided, long* overfull_cells);
 
