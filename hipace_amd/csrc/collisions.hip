@@ -6,8 +6,10 @@
 // draw is a function of (seed, collision, time step, slice, cell, pair, draw) -- coll_uniform below -- and every cell's list is
 // put in the order of the particles' id bits before it is shuffled, so the result does not depend on the order of the sheet.
 //
-// Four launches per sheet and collision: count per cell, exclusive scan (rocprim), fill (cell-sorted index list), and the
-// cell kernel: ONE LANE PER CELL runs the reference's serial per-cell loop (order, shuffle, densities, temperatures, pairs).
+// Two kernel templates.  k_coll_list<Src, FILL> builds a cell-sorted index list of one source of particles, a sheet (CollSheet) or
+// a beam slice (CollBeam): the count pass (integer atomics per cell), an exclusive scan (rocprim), the fill pass -- three
+// launches per list, coll_build_list.  k_coll_cells<Side0> then collides the cells: ONE LANE PER CELL runs the reference's
+// serial per-cell loop (order, shuffle, densities, temperatures, pairs).
 // The wrap-around pairing makes the pairs of a cell depend on each other (a particle collides twice), and the reference's
 // running charge product is serial too, so a cell is not split over lanes.  A cell's index list is staged in LDS
 // (COLL_LDS_CAP = 64 entries per lane, lane-interleaved so that the lanes of a wave hit different banks: 16 KB per 64-lane
@@ -16,12 +18,12 @@
 // the pair; the only device-wide atomics are the integer cell counters and the two statistics words.
 //
 // Beam-plasma (doBeamPlasmaCoulombCollision, CoulombCollision.cpp:238-348; every is_beam_coll branch of ElasticCollisionPerez.H and
-// ComputeTemperature.H): side 0 of the cell kernel is a beam slice -- BeamSoA plus a range that is read on the device --
-// which carries uz where a plasma particle carries psi.  The functions below take side 0's type as a template argument
-// (hps_plasma or BeamSoA); the plasma-plasma instantiation is the code it was.  A beam particle carries no id: a cell's
+// ComputeTemperature.H): side 0 of the cell kernel is a beam slice -- BeamSoA, with a range that the list kernel reads on the
+// device -- which carries uz where a plasma particle carries psi.  The functions below take side 0's type as a template
+// argument (hps_plasma or BeamSoA); side 1 is always a sheet.  A beam particle carries no id: a cell's
 // beam list is put in the lexicographic order of the bit patterns of (x, y, z, ux, uy, uz, w).  The beam's cell list is
-// built first, and the plasma's count and fill passes enter a particle only where the beam has one (k_coll_*_gated), so the
-// plasma list and the cell kernel's work follow the beam's footprint, not the sheet.
+// built first, and the plasma's count and fill passes enter a particle only where the beam has one (the gate of
+// coll_cell_of), so the plasma list and the cell kernel's work follow the beam's footprint, not the sheet.
 #include "engine.h"
 #include <rocprim/device/device_scan.hpp>
 #include <cfloat>
@@ -32,14 +34,16 @@ namespace hps {
 constexpr int COLL_LDS_CAP = 64;        // index entries per lane in LDS (both species of a cell together)
 constexpr int COLL_WG = 64;             // one wave per workgroup
 
-struct CollSide { hps_plasma p; double q, m; int can_ionize; const unsigned* off; unsigned* perm; };
+// side 1 is a sheet (p1); side 0's particles are the cell kernel's second argument, a sheet or a beam slice
+struct CollSide { double q, m; int can_ionize; const unsigned* off; unsigned* perm; };
 struct CollArgs {
-    CollSide s[2]; int same;
+    CollSide s[2]; hps_plasma p1; int same;
     int nx, ny; double plo0, plo1, dxi, dyi;
     double dt, L, dens_fac, c, inv_c, inv_c2; int normalized;
     unsigned long long key;              // coll_hash chain of (seed, collision, step, slice)
     unsigned long long* stats;           // {pairs collided, overfull cells}
 };
+
 
 // ---- counter-based generator: chained two-round splitmix64 finaliser (the construction of ion_uniform) ---------------
 __host__ __device__ inline unsigned long long coll_hash (unsigned long long h, unsigned long long v)
@@ -59,33 +63,78 @@ __device__ __forceinline__ double coll_uniform (unsigned long long cell_key, uns
     return coll_unit(coll_hash(coll_hash(coll_hash(cell_key, stream), a), b));
 }
 
-__device__ __forceinline__ bool coll_cell_of (const CollArgs& a, const hps_plasma& p, long ip, int* cell)
+// ---- the cell lists: the two kinds of source, each with its range, x, y and who takes part ----------------------------------
+// A sheet, [0, n): invalid particles (valid bit clear) and particles without weight are in no cell.
+struct CollSheet {
+    hps_plasma p;
+    static constexpr bool thread_per_particle = true;
+    __device__ __forceinline__ void range (long* first, long* count) const { *first = 0; *count = p.n; }
+    __device__ __forceinline__ double x (long ip) const { return p.x[ip]; }
+    __device__ __forceinline__ double y (long ip) const { return p.y[ip]; }
+    __device__ __forceinline__ bool takes_part (long ip) const { return (p.idcpu[ip] & HPS_ID_VALID) && p.w[ip] != 0.0; }
+};
+// A beam slice: slice p of the moving beam, [B[p], B[p + 1]) read on the device -- behind k_beam_partition of that slice, so
+// particles that slipped on to slice p + 1 are outside it --, or [0, n) of the free operator (B null).  size: length of the
+// SoA's arrays; cap: entries the index list has room for.  Both clamp the range: the launch is sized from a host-side bound.
+// Absorbed particles (nsub < 0) and particles without weight are in no cell.
+struct CollBeam {
+    BeamSoA b; const long* B; int p; long n, size, cap;
+    static constexpr bool thread_per_particle = false;      // the range is known on the device only: at most 2048 workgroups stride over it
+    __device__ __forceinline__ void range (long* first, long* count) const
+    {
+        long f = 0, c = n;
+        if (B) { f = B[p]; c = B[p + 1] - f; }
+        if (f < 0) f = 0;
+        if (f > size) f = size;
+        if (c > size - f) c = size - f;
+        if (c > cap) c = cap;
+        if (c < 0) c = 0;
+        *first = f; *count = c;
+    }
+    __device__ __forceinline__ double x (long ip) const { return b.x[ip]; }
+    __device__ __forceinline__ double y (long ip) const { return b.y[ip]; }
+    __device__ __forceinline__ bool takes_part (long ip) const { return !(b.nsub && b.nsub[ip] < 0) && b.w[ip] != 0.0; }
+};
+
+// The cell of particle ip of src, or false if it is in none.  The cell comes from x, y alone -- findParticlesInEachTile(bx, 1,
+// ...): int((pos - plo)*dxi), truncation as the reference's static_cast; a particle outside the box is in no bin.  gate, where
+// not null, is the final cell offsets of the beam's list: the plasma side of a beam collision enters a particle only where
+// the beam has one, and the loads that say whether the particle takes part come last, so a plasma particle outside the
+// beam's footprint costs two loads and no atomic.
+template <class Src>
+__device__ __forceinline__ bool coll_cell_of (const CollArgs& a, const Src& src, long ip, const unsigned* gate, int* cell)
 {
-    if (!(p.idcpu[ip] & HPS_ID_VALID) || p.w[ip] == 0.0) return false;
-    // findParticlesInEachTile(bx, 1, ...): int((pos - plo)*dxi), truncation as the reference's static_cast
-    const int i = (int)((p.x[ip] - a.plo0)*a.dxi), j = (int)((p.y[ip] - a.plo1)*a.dyi);
-    if (p.x[ip] < a.plo0 || p.y[ip] < a.plo1 || i < 0 || i >= a.nx || j < 0 || j >= a.ny) return false;      // outside the box: in no bin
-    *cell = i + j*a.nx;
+    const double x = src.x(ip), y = src.y(ip);
+    const int i = (int)((x - a.plo0)*a.dxi), j = (int)((y - a.plo1)*a.dyi);
+    if (x < a.plo0 || y < a.plo1 || i < 0 || i >= a.nx || j < 0 || j >= a.ny) return false;
+    const int c = i + j*a.nx;
+    if (gate && gate[c + 1] == gate[c]) return false;
+    if (!src.takes_part(ip)) return false;
+    *cell = c;
     return true;
 }
 
+// The count pass (FILL = false) and the fill pass of species slot's list, grid-stride over the source's range.  A sheet's
+// launch has a thread per particle, and its one trip is compiled as one: most lanes of a gated pass are done after two or
+// three dependent loads, the pass is bound by that latency, and without a loop head to come back to the compiler keeps the
+// early exits and loads each kernel argument where it is first needed.  The fill pass counts cnt down to 0
+// again: position = off[cell] + (what is left of the cell's count) - 1.
+template <class Src, bool FILL>
 __global__ __launch_bounds__(256)
-void k_coll_count (CollArgs a, int side, unsigned* cnt)
+void k_coll_list (CollArgs a, Src src, int slot, const unsigned* gate, unsigned* cnt)
 {
-    const long ip = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    int cell;
-    if (ip < a.s[side].p.n && coll_cell_of(a, a.s[side].p, ip, &cell)) atomicAdd(cnt + cell, 1u);
+    long first, count;
+    src.range(&first, &count);
+    for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
+        int cell;
+        if (coll_cell_of(a, src, first + t, gate, &cell)) {
+            if constexpr (FILL) a.s[slot].perm[a.s[slot].off[cell] + atomicSub(cnt + cell, 1u) - 1u] = (unsigned)(first + t);
+            else atomicAdd(cnt + cell, 1u);
+        }
+        if constexpr (Src::thread_per_particle) break;
+    }
 }
 
-// cnt counts down to 0 again: position = off[cell] + (what is left of the cell's count) - 1
-__global__ __launch_bounds__(256)
-void k_coll_fill (CollArgs a, int side, unsigned* cnt)
-{
-    const long ip = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    int cell;
-    if (ip < a.s[side].p.n && coll_cell_of(a, a.s[side].p, ip, &cell))
-        a.s[side].perm[a.s[side].off[cell] + atomicSub(cnt + cell, 1u) - 1u] = (unsigned)ip;
-}
 
 // index lists: lane-interleaved LDS (entry i of this lane at b[i*COLL_WG]) or a segment of the global list
 struct IdxLds { unsigned* b; __device__ __forceinline__ unsigned& operator[] (int i) const { return b[i*COLL_WG]; } };
@@ -308,7 +357,7 @@ template <class Idx, class Side>
 __device__ unsigned coll_elastic (const CollArgs& a, const Side& P1, const Idx& I1, int NI1, const Idx& I2, int NI2, unsigned long long cell_key)
 {
     constexpr bool BEAM = std::is_same<Side, BeamSoA>::value;
-    const hps_plasma& P2 = a.s[1].p;
+    const hps_plasma& P2 = a.p1;
     double q1 = a.s[0].q, q2 = a.s[1].q;
     const double m1 = a.s[0].m, m2 = a.s[1].m;
     double T1t = -1.0, T2t = -1.0;
@@ -363,161 +412,53 @@ __device__ unsigned coll_elastic (const CollArgs& a, const Side& P1, const Idx& 
     return collided;
 }
 
-template <class Idx>
-__device__ unsigned coll_cell (const CollArgs& a, const Idx& IA, int nA, const Idx& IB, int nB, unsigned long long cell_key)
+// One cell: both lists in canonical order, shuffled (slot 0 is side 0, slot 1 the sheet of side 1), then the pairs.  Same
+// species (sheets only): the one list is split at its middle, the first half shuffled, the halves collided.
+template <class Idx, class Side>
+__device__ unsigned coll_cell (const CollArgs& a, const Side& p0, const Idx& IA, int nA, const Idx& IB, int nB, unsigned long long cell_key)
 {
-    if (a.same) {
-        coll_order(IA, nA, a.s[0].p);
+    if constexpr (std::is_same<Side, hps_plasma>::value) if (a.same) {
+        coll_order(IA, nA, p0);
         const int half = nA/2;                       // (start + stop)/2 of the reference, relative to start
         coll_shuffle(IA, half, cell_key, 0u);
         Idx I2 = IA; I2.b = &IA[half];
-        return coll_elastic(a, a.s[0].p, IA, half, I2, nA - half, cell_key);
+        return coll_elastic(a, p0, IA, half, I2, nA - half, cell_key);
     }
-    coll_order(IA, nA, a.s[0].p); coll_order(IB, nB, a.s[1].p);
+    coll_order(IA, nA, p0); coll_order(IB, nB, a.p1);
     coll_shuffle(IA, nA, cell_key, 0u); coll_shuffle(IB, nB, cell_key, 1u);
-    return coll_elastic(a, a.s[0].p, IA, nA, IB, nB, cell_key);
+    return coll_elastic(a, p0, IA, nA, IB, nB, cell_key);
 }
 
+template <class Side0>
 __global__ __launch_bounds__(COLL_WG)
-void k_coll_cells (CollArgs a)
+void k_coll_cells (CollArgs a, Side0 p0)
 {
     __shared__ unsigned lds[COLL_LDS_CAP*COLL_WG];
     const int cell = blockIdx.x*COLL_WG + threadIdx.x;
     if (cell >= a.nx*a.ny) return;
     const unsigned sA = a.s[0].off[cell], nA = a.s[0].off[cell + 1] - sA;
     unsigned sB = 0, nB = 0;
-    if (a.same) { if (nA <= 1) return; }
-    else { sB = a.s[1].off[cell]; nB = a.s[1].off[cell + 1] - sB; if (nA < 1 || nB < 1) return; }
+    if (std::is_same<Side0, hps_plasma>::value && a.same) { if (nA <= 1) return; }
+    else {
+        if (nA < 1) return;                          // (no beam particle here: the gated plasma list is empty too)
+        sB = a.s[1].off[cell]; nB = a.s[1].off[cell + 1] - sB;
+        if (nB < 1) return;
+    }
     const unsigned long long cell_key = coll_hash(a.key, (unsigned long long)cell);
     unsigned collided;
     if (nA + nB <= (unsigned)COLL_LDS_CAP) {
         IdxLds IA{lds + threadIdx.x}, IB{lds + threadIdx.x + nA*COLL_WG};
         for (unsigned i = 0; i < nA; ++i) IA[i] = a.s[0].perm[sA + i];
         for (unsigned i = 0; i < nB; ++i) IB[i] = a.s[1].perm[sB + i];
-        collided = coll_cell(a, IA, (int)nA, IB, (int)nB, cell_key);
+        collided = coll_cell(a, p0, IA, (int)nA, IB, (int)nB, cell_key);
     } else {
         atomicAdd(a.stats + 1, 1ULL);
         IdxGlb IA{a.s[0].perm + sA}, IB{a.s[1].perm + sB};
-        collided = coll_cell(a, IA, (int)nA, IB, (int)nB, cell_key);
+        collided = coll_cell(a, p0, IA, (int)nA, IB, (int)nB, cell_key);
     }
     if (collided) atomicAdd(a.stats, (unsigned long long)collided);
 }
 
-// ---- beam-plasma: the beam side's cell list, the plasma's gated on it, the cell kernel with a beam slice as side 0 ------
-// The beam side: slice p of the moving beam, [B[p], B[p + 1]) read on the device -- behind k_beam_partition of that slice, so
-// particles that slipped on to slice p + 1 are outside it --, or [0, n) of the free operator (B null).  size: length of the
-// SoA's arrays; cap: entries the index list has room for.  Both clamp the range: the launch is sized from a host-side bound.
-struct CollBeam { BeamSoA b; const long* B; int p; long n, size, cap; };
-
-__device__ __forceinline__ void coll_beam_range (const CollBeam& m, long* first, long* count)
-{
-    long f = 0, c = m.n;
-    if (m.B) { f = m.B[m.p]; c = m.B[m.p + 1] - f; }
-    if (f < 0) f = 0;
-    if (f > m.size) f = m.size;
-    if (c > m.size - f) c = m.size - f;
-    if (c > m.cap) c = m.cap;
-    if (c < 0) c = 0;
-    *first = f; *count = c;
-}
-
-// absorbed particles (nsub < 0), particles without weight and particles outside the box are in no cell
-__device__ __forceinline__ bool coll_beam_cell_of (const CollArgs& a, const BeamSoA& b, long ip, int* cell)
-{
-    if ((b.nsub && b.nsub[ip] < 0) || b.w[ip] == 0.0) return false;
-    const int i = (int)((b.x[ip] - a.plo0)*a.dxi), j = (int)((b.y[ip] - a.plo1)*a.dyi);
-    if (b.x[ip] < a.plo0 || b.y[ip] < a.plo1 || i < 0 || i >= a.nx || j < 0 || j >= a.ny) return false;
-    *cell = i + j*a.nx;
-    return true;
-}
-
-__global__ __launch_bounds__(256)
-void k_coll_beam_count (CollArgs a, CollBeam m, unsigned* cnt)
-{
-    long first, count;
-    coll_beam_range(m, &first, &count);
-    for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
-        int cell;
-        if (coll_beam_cell_of(a, m.b, first + t, &cell)) atomicAdd(cnt + cell, 1u);
-    }
-}
-
-__global__ __launch_bounds__(256)
-void k_coll_beam_fill (CollArgs a, CollBeam m, unsigned* cnt)
-{
-    long first, count;
-    coll_beam_range(m, &first, &count);
-    for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
-        int cell;
-        if (coll_beam_cell_of(a, m.b, first + t, &cell))
-            a.s[0].perm[a.s[0].off[cell] + atomicSub(cnt + cell, 1u) - 1u] = (unsigned)(first + t);
-    }
-}
-
-// coll_cell_of for the plasma side of a beam collision: only where the beam has a particle (side 0's offsets are final).
-// The cell comes from x, y alone, so a particle outside the beam's footprint costs two loads.
-__device__ __forceinline__ bool coll_cell_of_gated (const CollArgs& a, const hps_plasma& p, long ip, int* cell)
-{
-    const double x = p.x[ip], y = p.y[ip];
-    const int i = (int)((x - a.plo0)*a.dxi), j = (int)((y - a.plo1)*a.dyi);
-    if (x < a.plo0 || y < a.plo1 || i < 0 || i >= a.nx || j < 0 || j >= a.ny) return false;
-    const int c = i + j*a.nx;
-    if (a.s[0].off[c + 1] == a.s[0].off[c]) return false;
-    if (!(p.idcpu[ip] & HPS_ID_VALID) || p.w[ip] == 0.0) return false;
-    *cell = c;
-    return true;
-}
-
-__global__ __launch_bounds__(256)
-void k_coll_count_gated (CollArgs a, unsigned* cnt)
-{
-    const long ip = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    int cell;
-    if (ip < a.s[1].p.n && coll_cell_of_gated(a, a.s[1].p, ip, &cell)) atomicAdd(cnt + cell, 1u);
-}
-
-__global__ __launch_bounds__(256)
-void k_coll_fill_gated (CollArgs a, unsigned* cnt)
-{
-    const long ip = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    int cell;
-    if (ip < a.s[1].p.n && coll_cell_of_gated(a, a.s[1].p, ip, &cell))
-        a.s[1].perm[a.s[1].off[cell] + atomicSub(cnt + cell, 1u) - 1u] = (unsigned)ip;
-}
-
-// is_same_species = false: both lists ordered and shuffled (slot 0 the beam, slot 1 the plasma), then the pairs
-template <class Idx>
-__device__ unsigned coll_cell_beam (const CollArgs& a, const BeamSoA& b, const Idx& IA, int nA, const Idx& IB, int nB, unsigned long long cell_key)
-{
-    coll_order(IA, nA, b); coll_order(IB, nB, a.s[1].p);
-    coll_shuffle(IA, nA, cell_key, 0u); coll_shuffle(IB, nB, cell_key, 1u);
-    return coll_elastic(a, b, IA, nA, IB, nB, cell_key);
-}
-
-__global__ __launch_bounds__(COLL_WG)
-void k_coll_cells_beam (CollArgs a, BeamSoA b)
-{
-    __shared__ unsigned lds[COLL_LDS_CAP*COLL_WG];
-    const int cell = blockIdx.x*COLL_WG + threadIdx.x;
-    if (cell >= a.nx*a.ny) return;
-    const unsigned sA = a.s[0].off[cell], nA = a.s[0].off[cell + 1] - sA;
-    if (nA < 1) return;                              // no beam particle here: the plasma's list is empty too
-    const unsigned sB = a.s[1].off[cell], nB = a.s[1].off[cell + 1] - sB;
-    if (nB < 1) return;
-    const unsigned long long cell_key = coll_hash(a.key, (unsigned long long)cell);
-    unsigned collided;
-    if (nA + nB <= (unsigned)COLL_LDS_CAP) {
-        IdxLds IA{lds + threadIdx.x}, IB{lds + threadIdx.x + nA*COLL_WG};
-        for (unsigned i = 0; i < nA; ++i) IA[i] = a.s[0].perm[sA + i];
-        for (unsigned i = 0; i < nB; ++i) IB[i] = a.s[1].perm[sB + i];
-        collided = coll_cell_beam(a, b, IA, (int)nA, IB, (int)nB, cell_key);
-    } else {
-        atomicAdd(a.stats + 1, 1ULL);
-        IdxGlb IA{a.s[0].perm + sA}, IB{a.s[1].perm + sB};
-        collided = coll_cell_beam(a, b, IA, (int)nA, IB, (int)nB, cell_key);
-    }
-    if (collided) atomicAdd(a.stats, (unsigned long long)collided);
-}
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 CollScratch::~CollScratch ()
@@ -566,68 +507,75 @@ static CollArgs coll_args (CollScratch& S, const hps_geom& gm, int nx, int ny, d
     return a;
 }
 
+// the refusals of both kinds.  n0, n1: the sizes of the two sides' arrays
+static int coll_check (const hps_geom& gm, int nx, int ny, long n0, long n1, double background_density_SI)
+{
+    HPS_REQUIRE(nx > 0 && ny > 0 && (long)nx*ny < (1L << 31) - 1, "collisions: bad grid");
+    HPS_REQUIRE(n0 >= 0 && n1 >= 0 && n0 < (1L << 32) - 1 && n1 < (1L << 32) - 1, "collisions: sheets and beams of up to 2^32 - 2 particles");
+    HPS_REQUIRE(!gm.normalized || background_density_SI > 0.0, "collisions: normalised units need hipace.background_density_SI (Hipace.cpp:239-243)");
+    return HPS_OK;
+}
+
+// Species slot's cell list of src: count, scan, fill, with `threads` threads in the two passes.  gate: see coll_cell_of.
+template <class Src>
+static int coll_build_list (CollScratch& S, const CollArgs& a, const Src& src, int slot, long threads, const unsigned* gate, hipStream_t st)
+{
+    const dim3 grid((unsigned)((threads + 255)/256));
+    // (cnt is all zero here: allocated so, and the fill pass counts it down again)
+    hipLaunchKernelGGL((k_coll_list<Src, false>), grid, dim3(256), 0, st, a, src, slot, gate, S.cnt);
+    size_t tb = S.temp_bytes;
+    HPS_HIP_CHECK(rocprim::exclusive_scan(S.temp, tb, S.cnt, S.off[slot], 0u, (size_t)(a.nx*a.ny + 1), rocprim::plus<unsigned>(), st));
+    hipLaunchKernelGGL((k_coll_list<Src, true>), grid, dim3(256), 0, st, a, src, slot, gate, S.cnt);
+    return HPS_OK;
+}
+
+template <class Side0>
+static int coll_cells (const CollArgs& a, const Side0& p0, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_coll_cells<Side0>, dim3((unsigned)((a.nx*a.ny + COLL_WG - 1)/COLL_WG)), dim3(COLL_WG), 0, st, a, p0);
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
 // One collision over two sheets (the same sheet twice: same species), enqueued on st.  S keeps the cell lists.
 int collide_plasma (CollScratch& S, const hps_plasma& pa, const hps_plasma& pb, bool same, const hps_geom& gm, int nx, int ny,
                     double qa, double ma, int can_ionize_a, double qb, double mb, int can_ionize_b, double coulomb_log,
                     double background_density_SI, unsigned long long seed, int collision, int step, int islice, hipStream_t st)
 {
-    HPS_REQUIRE(nx > 0 && ny > 0 && (long)nx*ny < (1L << 31) - 1, "collisions: bad grid");
-    HPS_REQUIRE(pa.n >= 0 && pb.n >= 0 && pa.n < (1L << 32) - 1 && pb.n < (1L << 32) - 1, "collisions: sheets of up to 2^32 - 2 particles");
-    HPS_REQUIRE(!gm.normalized || background_density_SI > 0.0, "collisions: normalised units need hipace.background_density_SI (Hipace.cpp:239-243)");
+    if (int e = coll_check(gm, nx, ny, pa.n, pb.n, background_density_SI)) return e;
     if (pa.n == 0 || pb.n == 0) return HPS_OK;
-    const int ncells = nx*ny;
-    if (int e = coll_reserve(S, ncells, pa.n, same ? 0 : pb.n)) return e;
+    if (int e = coll_reserve(S, nx*ny, pa.n, same ? 0 : pb.n)) return e;
     const double wp = std::sqrt(background_density_SI*SI_QE*SI_QE/(SI_EP0*SI_ME));
     CollArgs a = coll_args(S, gm, nx, ny, gm.normalized ? gm.dz/wp : gm.dz/SI_C, coulomb_log, background_density_SI, seed, collision, step, islice);
-    a.s[0] = CollSide{pa, qa, ma, can_ionize_a, S.off[0], S.perm[0]};
-    a.s[1] = same ? a.s[0] : CollSide{pb, qb, mb, can_ionize_b, S.off[1], S.perm[1]};
+    a.s[0] = CollSide{qa, ma, can_ionize_a, S.off[0], S.perm[0]};
+    a.s[1] = same ? a.s[0] : CollSide{qb, mb, can_ionize_b, S.off[1], S.perm[1]};
+    a.p1 = same ? pa : pb;
     a.same = same ? 1 : 0;
-    for (int side = 0; side < (same ? 1 : 2); ++side) {
-        const long n = a.s[side].p.n;
-        const dim3 grid((unsigned)((n + 255)/256));
-        // (cnt is all zero here: allocated so, and k_coll_fill counts it down again)
-        hipLaunchKernelGGL(k_coll_count, grid, dim3(256), 0, st, a, side, S.cnt);
-        size_t tb = S.temp_bytes;
-        HPS_HIP_CHECK(rocprim::exclusive_scan(S.temp, tb, S.cnt, S.off[side], 0u, (size_t)(ncells + 1), rocprim::plus<unsigned>(), st));
-        hipLaunchKernelGGL(k_coll_fill, grid, dim3(256), 0, st, a, side, S.cnt);
-    }
-    hipLaunchKernelGGL(k_coll_cells, dim3((unsigned)((ncells + COLL_WG - 1)/COLL_WG)), dim3(COLL_WG), 0, st, a);
-    HPS_HIP_CHECK(hipGetLastError());
-    return HPS_OK;
+    if (int e = coll_build_list(S, a, CollSheet{pa}, 0, pa.n, nullptr, st)) return e;
+    if (!same) if (int e = coll_build_list(S, a, CollSheet{pb}, 1, pb.n, nullptr, st)) return e;
+    return coll_cells(a, pa, st);
 }
 
 // One collision between a beam slice (side 0) and a sheet, enqueued on st.  bound: host-side upper bound of the slice's
-// size (it sizes the beam's launches; the kernels read the range on the device); dt: the run's time step in seconds.
-// Seven launches: the beam's count, scan and fill, the plasma's gated on the beam's counts, the cell kernel.
+// size (it sizes the beam's launches, at most 2048 workgroups; the kernels read the range on the device); dt: the run's time
+// step in seconds.  Seven launches: the beam's count, scan and fill, the plasma's gated on the beam's offsets, the cell kernel.
 int collide_beam_plasma (CollScratch& S, CollBeam m, long bound, const hps_plasma& pl, const hps_geom& gm, int nx, int ny,
                          double q_beam, double m_beam, double q_pl, double m_pl, int can_ionize_pl, double coulomb_log,
                          double background_density_SI, double dt, unsigned long long seed, int collision, int step, int islice, hipStream_t st)
 {
-    HPS_REQUIRE(nx > 0 && ny > 0 && (long)nx*ny < (1L << 31) - 1, "collisions: bad grid");
-    HPS_REQUIRE(pl.n >= 0 && pl.n < (1L << 32) - 1 && m.size >= 0 && m.size < (1L << 32) - 1, "collisions: sheets and beams of up to 2^32 - 2 particles");
-    HPS_REQUIRE(!gm.normalized || background_density_SI > 0.0, "collisions: normalised units need hipace.background_density_SI (Hipace.cpp:239-243)");
+    if (int e = coll_check(gm, nx, ny, m.size, pl.n, background_density_SI)) return e;
     if (bound <= 0 || m.size == 0 || pl.n == 0) return HPS_OK;
-    const int ncells = nx*ny;
     // the beam's index list has room for the whole beam: the bound grows from slice to slice, the list is allocated once
-    if (int e = coll_reserve(S, ncells, m.size, pl.n)) return e;
+    if (int e = coll_reserve(S, nx*ny, m.size, pl.n)) return e;
     m.cap = S.cap[0];
     CollArgs a = coll_args(S, gm, nx, ny, dt, coulomb_log, background_density_SI, seed, collision, step, islice);
-    a.s[0] = CollSide{hps_plasma{}, q_beam, m_beam, 0, S.off[0], S.perm[0]};
-    a.s[1] = CollSide{pl, q_pl, m_pl, can_ionize_pl, S.off[1], S.perm[1]};
+    a.s[0] = CollSide{q_beam, m_beam, 0, S.off[0], S.perm[0]};
+    a.s[1] = CollSide{q_pl, m_pl, can_ionize_pl, S.off[1], S.perm[1]};
+    a.p1 = pl;
     a.same = 0;
-    const dim3 gb((unsigned)std::max<long>(1, std::min<long>((std::min(bound, m.size) + 255)/256, 2048))), gp((unsigned)((pl.n + 255)/256));
-    size_t tb = S.temp_bytes;
-    // (cnt is all zero here: allocated so, and the fill kernels count it down again)
-    hipLaunchKernelGGL(k_coll_beam_count, gb, dim3(256), 0, st, a, m, S.cnt);
-    HPS_HIP_CHECK(rocprim::exclusive_scan(S.temp, tb, S.cnt, S.off[0], 0u, (size_t)(ncells + 1), rocprim::plus<unsigned>(), st));
-    hipLaunchKernelGGL(k_coll_beam_fill, gb, dim3(256), 0, st, a, m, S.cnt);
-    hipLaunchKernelGGL(k_coll_count_gated, gp, dim3(256), 0, st, a, S.cnt);
-    tb = S.temp_bytes;
-    HPS_HIP_CHECK(rocprim::exclusive_scan(S.temp, tb, S.cnt, S.off[1], 0u, (size_t)(ncells + 1), rocprim::plus<unsigned>(), st));
-    hipLaunchKernelGGL(k_coll_fill_gated, gp, dim3(256), 0, st, a, S.cnt);
-    hipLaunchKernelGGL(k_coll_cells_beam, dim3((unsigned)((ncells + COLL_WG - 1)/COLL_WG)), dim3(COLL_WG), 0, st, a, m.b);
-    HPS_HIP_CHECK(hipGetLastError());
-    return HPS_OK;
+    if (int e = coll_build_list(S, a, m, 0, std::min<long>(std::min(bound, m.size), 2048L*256), nullptr, st)) return e;
+    if (int e = coll_build_list(S, a, CollSheet{pl}, 1, pl.n, S.off[0], st)) return e;
+    return coll_cells(a, m.b, st);
 }
 
 int coll_read_stats (CollScratch& S, long* pairs, long* overfull, hipStream_t st)
@@ -686,20 +634,30 @@ extern "C" int hps_collide_plasma (hps_plasma a, void* tiling_a, hps_plasma b, v
     return coll_read_stats(S, pairs_collided_host, overfull_cells_host, st);
 }
 
-extern "C" int hps_engine_add_collision (void* h, int species_a, int species_b, double coulomb_log, unsigned long long seed)
+// the refusals that hps_engine_add_collision and hps_engine_add_beam_collision share, in the words of fn.  species_ok /
+// species_msg: the caller's own check of its species arguments, which comes second; ion: the collision names species 1
+static int coll_add_check (const void* h, const std::string& fn, bool species_ok, const char* species_msg, bool ion, const char* at_most)
 {
-    HPS_REQUIRE(h, "hps_engine_add_collision: null engine");
-    Engine* E = static_cast<Engine*>(h);
-    HPS_REQUIRE((species_a == 0 || species_a == 1) && (species_b == 0 || species_b == 1), "hps_engine_add_collision: species are 0 (plasma) or 1 (ion)");
-    HPS_REQUIRE(!E->step_begun, "hps_engine_add_collision: call before the first hps_engine_begin_step");
-    HPS_REQUIRE((int)E->coll.size() < HPS_MAX_COLLISIONS, "hps_engine_add_collision: at most HPS_MAX_COLLISIONS collisions");
-    HPS_REQUIRE(E->d.si_units || E->d.background_density_SI > 0.0, "hps_engine_add_collision: collisions in normalised units need hipace.background_density_SI");
-    HPS_REQUIRE((species_a == 0 && species_b == 0) || E->d.ion_on, "hps_engine_add_collision: species 1 needs the species \"ion\" (ion_on)");
+    HPS_REQUIRE(h, fn + ": null engine");
+    const Engine* E = static_cast<const Engine*>(h);
+    HPS_REQUIRE(species_ok, fn + species_msg);
+    HPS_REQUIRE(!E->step_begun, fn + ": call before the first hps_engine_begin_step");
+    HPS_REQUIRE((int)E->coll.size() < HPS_MAX_COLLISIONS, fn + at_most);
+    HPS_REQUIRE(E->d.si_units || E->d.background_density_SI > 0.0, fn + ": collisions in normalised units need hipace.background_density_SI");
+    HPS_REQUIRE(!ion || E->d.ion_on, fn + ": species 1 needs the species \"ion\" (ion_on)");
     if (E->d.ion_on && E->d.ion_init_level < E->d.ion_Z) {
-        set_error("hps_engine_add_collision: the species \"ion\" can still ionise, and the electrons it releases carry no unique key for the collision draws");
+        set_error(fn + ": the species \"ion\" can still ionise, and the electrons it releases carry no unique key for the collision draws");
         return HPS_ERR_UNSUPPORTED;
     }
-    E->coll.push_back(Engine::Collision{species_a, species_b, coulomb_log, seed});
+    return HPS_OK;
+}
+
+extern "C" int hps_engine_add_collision (void* h, int species_a, int species_b, double coulomb_log, unsigned long long seed)
+{
+    if (int e = coll_add_check(h, "hps_engine_add_collision", (species_a == 0 || species_a == 1) && (species_b == 0 || species_b == 1),
+                               ": species are 0 (plasma) or 1 (ion)", species_a == 1 || species_b == 1,
+                               ": at most HPS_MAX_COLLISIONS collisions")) return e;
+    static_cast<Engine*>(h)->coll.push_back(Engine::Collision{species_a, species_b, coulomb_log, seed});
     return HPS_OK;
 }
 
@@ -722,17 +680,10 @@ extern "C" int hps_collide_beam_plasma (hps_beam_slice beam, hps_plasma plasma, 
 
 extern "C" int hps_engine_add_beam_collision (void* h, int plasma_species, double coulomb_log, unsigned long long seed)
 {
-    HPS_REQUIRE(h, "hps_engine_add_beam_collision: null engine");
+    if (int e = coll_add_check(h, "hps_engine_add_beam_collision", plasma_species == 0 || plasma_species == 1,
+                               ": the plasma species is 0 (plasma) or 1 (ion)", plasma_species == 1,
+                               ": at most HPS_MAX_COLLISIONS collisions, of both kinds together")) return e;
     Engine* E = static_cast<Engine*>(h);
-    HPS_REQUIRE(plasma_species == 0 || plasma_species == 1, "hps_engine_add_beam_collision: the plasma species is 0 (plasma) or 1 (ion)");
-    HPS_REQUIRE(!E->step_begun, "hps_engine_add_beam_collision: call before the first hps_engine_begin_step");
-    HPS_REQUIRE((int)E->coll.size() < HPS_MAX_COLLISIONS, "hps_engine_add_beam_collision: at most HPS_MAX_COLLISIONS collisions, of both kinds together");
-    HPS_REQUIRE(E->d.si_units || E->d.background_density_SI > 0.0, "hps_engine_add_beam_collision: collisions in normalised units need hipace.background_density_SI");
-    HPS_REQUIRE(plasma_species == 0 || E->d.ion_on, "hps_engine_add_beam_collision: species 1 needs the species \"ion\" (ion_on)");
-    if (E->d.ion_on && E->d.ion_init_level < E->d.ion_Z) {
-        set_error("hps_engine_add_beam_collision: the species \"ion\" can still ionise, and the electrons it releases carry no unique key for the collision draws");
-        return HPS_ERR_UNSUPPORTED;
-    }
     if (E->d.dt_adaptive) {
         set_error("hps_engine_add_beam_collision: hipace.dt = adaptive is not supported with a beam collision: the reference gathers the beam's "
                   "moments behind the collisions (GatherMinUzSlice, Hipace.cpp:713-716), the engine reduces them inside k_beam_partition, ahead of them");

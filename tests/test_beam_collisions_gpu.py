@@ -11,8 +11,8 @@ import pytest
 from hipace_amd import decks
 from tests import collision_beam_reference as B
 from tests import collision_reference as R
+from tests.collision_util import deviation, from_gpu, geometry, sheet_arrays, sheet_from, small_deck, to_gpu, write_thermal
 from tests.test_beam_collisions_cpu import CONSERVATION_BOUND, conservation_cases, conservation_error
-from tests.test_collisions_gpu import _sheet_arrays, _sheet_from, _write_thermal, deviation, from_gpu, geometry, to_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -139,6 +139,25 @@ def match(a, b):
     return idx
 
 
+def _head_slice_twins(api, deck, beam, u_std, add):
+    """(engine with the collisions that add(engine) configures, its twin without any): the beam set, thermal momenta written
+    into the sheet behind begin_step, the head slice solved"""
+    from hipace_amd import _lib
+    engines = []
+    for collide in (True, False):
+        e = api.SliceEngine(deck, tile_size=0)
+        e.set_beam_particles(beam, allow_outside=True)
+        if collide:
+            add(e)
+        e.begin_step()
+        e.sync()
+        write_thermal(_lib.lib().hps_engine_plasma(e._h), 1, u_std)
+        e.solve_slice(deck["nz"] - 1)
+        e.sync()
+        engines.append(e)
+    return engines
+
+
 def test_engine_collides_the_beam_slice_behind_its_push_with_the_slice_key_and_the_step_dt(api):
     from hipace_amd import _lib
     L = _lib.lib()
@@ -146,19 +165,7 @@ def test_engine_collides_the_beam_slice_behind_its_push_with_the_slice_key_and_t
     beam = moving_beam(deck)
     u_std = 0.05
     nz = deck["nz"]
-    engines = []
-    for collide in (True, False):
-        e = api.SliceEngine(deck, tile_size=0)
-        e.set_beam_particles(beam, allow_outside=True)
-        if collide:
-            e.add_beam_collision(0, -1.0, 42)
-        e.begin_step()
-        e.sync()
-        _write_thermal(L.hps_engine_plasma(e._h), 1, u_std)
-        e.solve_slice(nz - 1)
-        e.sync()
-        engines.append(e)
-    with_c, without = engines
+    with_c, without = _head_slice_twins(api, deck, beam, u_std, lambda e: e.add_beam_collision(0, -1.0, 42))
     st = with_c.collision_stats()
     assert st["pairs_collided"] > 100
     _, off0 = with_c.beam_layout()
@@ -168,11 +175,11 @@ def test_engine_collides_the_beam_slice_behind_its_push_with_the_slice_key_and_t
     stay, slipped = slice(bc[0], bc[1]), slice(bc[1], off0[1])
     assert bc[1] - bc[0] > 50 and off0[1] - bc[1] > 10                    # the head slice keeps particles and hands some on
     # the twin's slice and sheet through the free operator with the engine's key and the run's time step
-    el_c, id_c, lev_c = _sheet_arrays(api, L.hps_engine_plasma(with_c._h))
-    el_p, _, _ = _sheet_arrays(api, L.hps_engine_plasma(without._h))
+    el_c, id_c, lev_c = sheet_arrays(api, L.hps_engine_plasma(with_c._h))
+    el_p, _, _ = sheet_arrays(api, L.hps_engine_plasma(without._h))
     assert np.array_equal((id_c >> np.uint64(24)) & np.uint64((1 << 39) - 1), np.arange(1, len(id_c) + 1, dtype=np.uint64))
     geom = api.Geometry(deck["nx"], deck["ny"], deck["lo"][:2], deck["hi"][:2], (deck["hi"][2] - deck["lo"][2]) / nz, bc=deck["bc"])
-    gb, gs = api.BeamSlice(sp[:, stay]), _sheet_from(api, el_p, id_c, lev_c)
+    gb, gs = api.BeamSlice(sp[:, stay]), sheet_from(api, el_p, id_c, lev_c)
     pairs, _ = api.BeamPlasmaCollision(gb, gs, geom, deck["beam_charge"], deck["beam_mass"], deck["plasma_charge"], deck["plasma_mass"],
                                        deck["dt"] / B.omega_p(BG), coulomb_log=-1.0, background_density_SI=BG, seed=42, collision=0, step=0,
                                        islice=nz - 1)
@@ -192,6 +199,62 @@ def test_engine_collides_the_beam_slice_behind_its_push_with_the_slice_key_and_t
     print(f"engine against operator: beam {dev_b:.3e} plasma {dev_p:.3e}; pairs {pairs}; changed by the collision: beam {changed_b:.3e} "
           f"plasma {changed_p:.3e}; slipped particles, engine with against engine without: {slipped_dev:.3e}")
     assert changed_b > 1e2 * OPERATOR_BOUND and changed_p > 1e2 * OPERATOR_BOUND
+    assert slipped_dev <= OPERATOR_BOUND
+    assert dev_b <= OPERATOR_BOUND and dev_p <= OPERATOR_BOUND
+
+
+@pytest.mark.parametrize("kinds", [("plasma", "beam"), ("beam", "plasma")], ids="_then_".join)
+def test_engine_runs_a_list_that_holds_both_kinds_in_its_order(api, kinds):
+    """One list with a same-species collision and a beam collision, in either order, on the head slice of the moving deck.  The
+    two kinds share the engine's cell lists: the counters must be all zero again behind every fill pass, slot 0 holds the
+    sheet's list for one kind and the beam's for the other, and its offsets are the gate of the beam collision's plasma
+    passes.  The twin engine's sheet and kept beam slice go through the two free operators in the list's order, with the
+    collision index by position, the engine's seeds and the head slice's key; engine and replay run the same kernels on the
+    same particles, so this file's OPERATOR_BOUND holds as in the test above."""
+    from hipace_amd import _lib
+    L = _lib.lib()
+    deck = moving_deck()
+    beam = moving_beam(deck)
+    u_std = 0.05
+    nz = deck["nz"]
+    seed = dict(plasma=42, beam=43)
+
+    def add(e):
+        for k in kinds:
+            e.add_collision(0, 0, -1.0, seed[k]) if k == "plasma" else e.add_beam_collision(0, -1.0, seed[k])
+    with_c, without = _head_slice_twins(api, deck, beam, u_std, add)
+    st = with_c.collision_stats()
+    _, off0 = with_c.beam_layout()
+    bc, sc = with_c.beam_state()
+    bp, sp = without.beam_state()
+    assert np.array_equal(bc, bp) and bc[0] == 0
+    stay, slipped = slice(bc[0], bc[1]), slice(bc[1], off0[1])
+    assert bc[1] - bc[0] > 50 and off0[1] - bc[1] > 10
+    el_c, id_c, lev_c = sheet_arrays(api, L.hps_engine_plasma(with_c._h))
+    el_p, _, _ = sheet_arrays(api, L.hps_engine_plasma(without._h))
+    geom = api.Geometry(deck["nx"], deck["ny"], deck["lo"][:2], deck["hi"][:2], (deck["hi"][2] - deck["lo"][2]) / nz, bc=deck["bc"])
+    gb, gs = api.BeamSlice(sp[:, stay]), sheet_from(api, el_p, id_c, lev_c)
+    pairs = {}
+    for i, k in enumerate(kinds):
+        key = dict(coulomb_log=-1.0, background_density_SI=BG, seed=seed[k], collision=i, step=0, islice=nz - 1)
+        if k == "plasma":
+            pairs[k], _ = api.CoulombCollision(gs, gs, geom, deck["plasma_charge"], deck["plasma_mass"], **key)
+        else:
+            pairs[k], _ = api.BeamPlasmaCollision(gb, gs, geom, deck["beam_charge"], deck["beam_mass"], deck["plasma_charge"],
+                                                  deck["plasma_mass"], deck["dt"] / B.omega_p(BG), **key)
+    # 4 particles per cell over 256 cells, and the beam pairs the test above requires of this deck: both kinds have work
+    assert pairs["plasma"] > 100 and pairs["beam"] > 100, pairs
+    assert st["pairs_collided"] == pairs["plasma"] + pairs["beam"]
+    want = gb.numpy()
+    m = match(want[:3], sc[:3, stay])
+    got = sc[:, stay][:, m]
+    dev_b = (np.abs(got[3:6] - want[3:6]).max(axis=0) / np.sqrt((want[3:6] ** 2).sum(axis=0))).max()
+    scale = np.array([u_std, u_std, 0.05])[:, None]
+    dev_p = (np.abs(np.stack(from_gpu(gs)) - el_c[8:]) / scale).max()
+    ms = match(sp[:3, slipped], sc[:3, slipped])
+    slipped_dev = (np.abs(sc[3:6, slipped][:, ms] - sp[3:6, slipped]).max(axis=0) / np.sqrt((sp[3:6, slipped] ** 2).sum(axis=0))).max()
+    print(f"{kinds}: engine against operators: beam {dev_b:.3e} plasma {dev_p:.3e}; pairs {pairs}, engine {st}; slipped particles, "
+          f"engine with against engine without: {slipped_dev:.3e}")
     assert slipped_dev <= OPERATOR_BOUND
     assert dev_b <= OPERATOR_BOUND and dev_p <= OPERATOR_BOUND
 
@@ -254,7 +317,6 @@ def test_static_beam_collides_nothing_and_holds_the_reference_checksums(api):
 
 def test_refusals(api):
     from hipace_amd._lib import HpsError
-    from tests.test_collisions_gpu import _small
 
     def refused(deck, args, status, text, begin=False):
         e = api.SliceEngine(deck, tile_size=0)
@@ -263,13 +325,13 @@ def test_refusals(api):
         with pytest.raises(HpsError) as err:
             e.add_beam_collision(*args)
         assert f"status {status}:" in str(err.value) and text in str(err.value), str(err.value)
-    small = _small(decks.blowout_wake(), dt=1.0)
+    small = small_deck(decks.blowout_wake(), dt=1.0)
     dense = dict(small, background_density_SI=1e24)
     refused(small, (0, -1.0, 0), 1, "background_density_SI")
     refused(dense, (1, -1.0, 0), 1, "ion_on")
     refused(dense, (2, -1.0, 0), 1, "is 0 (plasma) or 1 (ion)")
     refused(dense, (0, -1.0, 0), 1, "before the first hps_engine_begin_step", begin=True)
-    refused(_small(decks.ionization_SI(), plasma_ppc=(0, 0)), (1, -1.0, 0), 7, "can still ionise")
+    refused(small_deck(decks.ionization_SI(), plasma_ppc=(0, 0)), (1, -1.0, 0), 7, "can still ionise")
     adaptive = dict(decks.adaptive_time_step(), background_density_SI=1e24)
     refused(adaptive, (0, -1.0, 0), 7, "k_beam_partition")
     # the plasma-plasma setter still takes an adaptive deck, and still refuses species 2 in its own words

@@ -1,6 +1,5 @@
 """Binary Coulomb collisions on the GPU: the operator against the numpy restatement particle by particle, order
 independence, conservation, the engine's placement and keys, the refusals, and the reference's checksum file."""
-import ctypes as C
 import json
 import os
 
@@ -9,6 +8,7 @@ import pytest
 
 from hipace_amd import decks
 from tests import collision_reference as R
+from tests.collision_util import deviation, from_gpu, geometry, sheet_arrays, sheet_from, small_deck, to_gpu, write_thermal
 from tests.test_collisions_cpu import CONSERVATION_BOUND, conservation_cases, conservation_error
 
 pytestmark = pytest.mark.gpu
@@ -28,38 +28,6 @@ def api():
     from hipace_amd import _lib, api as A
     _lib.lib()
     return A
-
-
-def to_gpu(api, s):
-    n = len(s["x"])
-    real = np.zeros((11, n))
-    real[0], real[1], real[2] = s["x"], s["y"], s["w"]
-    real[3], real[4], real[5] = s["ux"], s["uy"], s["psi"]
-    real[6], real[7] = s["x"], s["y"]
-    real[8], real[9], real[10] = s["ux"], s["uy"], s["psi"]
-    return api.PlasmaSheet(real, valid=s["valid"], ion_lev=s["ion_lev"], key=s["key"])
-
-
-def from_gpu(sheet):
-    real, _ = sheet.numpy()
-    return real[8], real[9], real[10]
-
-
-def geometry(api, lo, dx, si):
-    hi = (lo[0] + R.NX * dx, lo[1] + R.NY * dx)
-    consts = (R.C_SI, R.EP0, 4.0e-7 * np.pi, R.QE, R.ME) if si else (1.0,) * 5
-    return api.Geometry(R.NX, R.NY, lo, hi, dx, bc=1, normalized=not si, consts=consts)
-
-
-def deviation(s_ref, gpu, c, lo, dx):
-    """max over particles of |du| / rms(u of the cell), u = (ux, uy, c psi) as the collisions leave them"""
-    worst = 0.0
-    for cell, lst in R.cell_lists(s_ref, R.NX, R.NY, lo, dx, dx).items():
-        ref = np.stack([s_ref["ux"][lst], s_ref["uy"][lst], c * s_ref["psi"][lst]])
-        got = np.stack([gpu[0][lst], gpu[1][lst], c * gpu[2][lst]])
-        rms = np.sqrt((ref[:2] ** 2).sum() / len(lst))      # (psi is about 1: the thermal u sets the scale, c psi rounds finer)
-        worst = max(worst, np.abs(got - ref).max() / rms)
-    return worst
 
 
 # name: (si, two species, kwargs of thermal_cells for species a, weight scale, coulomb_log, background density, tail, expected branches)
@@ -183,48 +151,14 @@ def test_gpu_conserves_momentum_and_energy_per_cell(api):
 
 
 # ---- the engine --------------------------------------------------------------------------------------------------------
-def _sheet_arrays(api, p):
-    from hipace_amd import _lib
-    n = p.n
-    real = np.empty((11, n))
-    idc = np.empty(n, dtype=np.uint64)
-    lev = np.empty(n, dtype=np.int32)
-    for k, nm in enumerate(_lib.PL_REAL):
-        _lib.check(_lib.lib().hps_memcpy_d2h(real[k].ctypes.data_as(C.c_void_p), C.c_void_p(getattr(p, nm)), real[k].nbytes))
-    _lib.check(_lib.lib().hps_memcpy_d2h(idc.ctypes.data_as(C.c_void_p), C.c_void_p(p.idcpu), idc.nbytes))
-    _lib.check(_lib.lib().hps_memcpy_d2h(lev.ctypes.data_as(C.c_void_p), C.c_void_p(p.ion_lev), lev.nbytes))
-    return real, idc, lev
-
-
-def _write_thermal(p, seed, u_std):
-    from hipace_amd import _lib
-    rng = np.random.default_rng(seed)
-    for nm in ("ux_half", "uy_half"):
-        u = rng.normal(0.0, u_std, p.n)
-        _lib.check(_lib.lib().hps_memcpy_h2d(C.c_void_p(getattr(p, nm)), u.ctypes.data_as(C.c_void_p), u.nbytes))
-
-
-def _small(deck, **kw):
-    d = dict(deck, nx=32, ny=32, nz=8, n_steps=1, plasma_ppc=(2, 2))
-    d["lo"] = tuple(d["lo"][:2]) + (d["lo"][2] * 0.08,)
-    d["hi"] = tuple(d["hi"][:2]) + (d["hi"][2] * 0.08,)
-    d.update(kw)
-    return d
-
-
-def _sheet_from(api, real, idc, lev):
-    key = ((idc >> np.uint64(24)) & np.uint64((1 << 39) - 1)).astype(np.int64) - 1
-    return api.PlasmaSheet(real, valid=((idc >> np.uint64(63)) & np.uint64(1)).astype(np.int32), ion_lev=lev, key=key)
-
-
 @pytest.mark.parametrize("pair", [(0, 0), (0, 1)])
 def test_engine_collides_behind_the_push_with_the_slice_key(api, pair):
     from hipace_amd import _lib
     L = _lib.lib()
     if pair == (0, 0):
-        deck = _small(decks.blowout_wake(), background_density_SI=1.0e24)
+        deck = small_deck(decks.blowout_wake(), background_density_SI=1.0e24)
     else:
-        deck = _small(decks.ion_motion_SI(), ion_ppc=(2, 2))
+        deck = small_deck(decks.ion_motion_SI(), ion_ppc=(2, 2))
     si = bool(deck["si_units"])
     u_std = 0.05 * (R.C_SI if si else 1.0)
     engines = []
@@ -234,26 +168,26 @@ def test_engine_collides_behind_the_push_with_the_slice_key(api, pair):
             e.add_collision(pair[0], pair[1], -1.0, 42)
         e.begin_step()
         e.sync()
-        _write_thermal(L.hps_engine_plasma(e._h), 1, u_std)
+        write_thermal(L.hps_engine_plasma(e._h), 1, u_std)
         if pair[1] == 1:
-            _write_thermal(L.hps_engine_ions(e._h), 2, u_std / 50.0)
+            write_thermal(L.hps_engine_ions(e._h), 2, u_std / 50.0)
         e.solve_slice(deck["nz"] - 1)
         e.sync()
         engines.append(e)
     with_c, without = engines
     assert with_c.collision_stats()["pairs_collided"] > 1000
-    el_c, id_c, lev_c = _sheet_arrays(api, L.hps_engine_plasma(with_c._h))
-    el_p, _, _ = _sheet_arrays(api, L.hps_engine_plasma(without._h))
+    el_c, id_c, lev_c = sheet_arrays(api, L.hps_engine_plasma(with_c._h))
+    el_p, _, _ = sheet_arrays(api, L.hps_engine_plasma(without._h))
     assert np.abs(el_c[8:] - el_p[8:]).max() > 1e-6 * u_std          # the collision did something
     # tile size 0 keeps the lattice order: the colliding engine's keys are the plain engine's particle indices
     assert np.array_equal((id_c >> np.uint64(24)) & np.uint64((1 << 39) - 1), np.arange(1, len(id_c) + 1, dtype=np.uint64))
     geom = api.Geometry(deck["nx"], deck["ny"], deck["lo"][:2], deck["hi"][:2], (deck["hi"][2] - deck["lo"][2]) / deck["nz"], bc=deck["bc"],
                         normalized=not si, consts=(R.C_SI, R.EP0, 4.0e-7 * np.pi, R.QE, R.ME) if si else (1.0,) * 5)
-    sa = _sheet_from(api, el_p, id_c, lev_c)
+    sa = sheet_from(api, el_p, id_c, lev_c)
     if pair[1] == 1:
-        ion_c, iid_c, ilev_c = _sheet_arrays(api, L.hps_engine_ions(with_c._h))
-        ion_p, _, ilev_p = _sheet_arrays(api, L.hps_engine_ions(without._h))
-        sb = _sheet_from(api, ion_p, iid_c, ilev_p)
+        ion_c, iid_c, ilev_c = sheet_arrays(api, L.hps_engine_ions(with_c._h))
+        ion_p, _, ilev_p = sheet_arrays(api, L.hps_engine_ions(without._h))
+        sb = sheet_from(api, ion_p, iid_c, ilev_p)
         api.CoulombCollision(sa, sb, geom, deck["plasma_charge"], deck["plasma_mass"], deck["ion_charge"], deck["ion_mass"], can_ionize_b=True,
                              coulomb_log=-1.0, background_density_SI=deck["background_density_SI"], seed=42, collision=0, step=0,
                              islice=deck["nz"] - 1)
@@ -309,12 +243,12 @@ def test_refusals(api):
         with pytest.raises(HpsError) as err:
             e.add_collision(*args)
         assert f"status {status}:" in str(err.value) and text in str(err.value), str(err.value)
-    small = _small(decks.blowout_wake())
+    small = small_deck(decks.blowout_wake())
     refused(small, (0, 0, -1.0, 0), 1, "background_density_SI")
     refused(dict(small, background_density_SI=1e24), (0, 1, -1.0, 0), 1, "ion_on")
     refused(dict(small, background_density_SI=1e24), (0, 2, -1.0, 0), 1, "species are 0")
     refused(dict(small, background_density_SI=1e24), (0, 0, -1.0, 0), 1, "before the first hps_engine_begin_step", begin=True)
-    refused(_small(decks.ionization_SI(), plasma_ppc=(0, 0)), (0, 1, -1.0, 0), 7, "can still ionise")
+    refused(small_deck(decks.ionization_SI(), plasma_ppc=(0, 0)), (0, 1, -1.0, 0), 7, "can still ionise")
     e = api.SliceEngine(dict(small, background_density_SI=1e24), tile_size=0)
     for _ in range(8):
         e.add_collision(0, 0, 5.0, 0)
