@@ -166,6 +166,17 @@ class Tiling:
             check(_lib.lib().hps_memcpy_d2h(p.ctypes.data_as(C.c_void_p), C.c_void_p(perm), p.nbytes))
         return o, p
 
+    def launch_order(self):
+        """-> (order int32 (ntiles,), records int32 (ntiles, 4)): workgroup b of a tile kernel works on tile order[b];
+        records[b] = {tile, first particle, end, 0}.  Read-only copies of what the last reorder left on the device."""
+        torch.cuda.synchronize()
+        nt, off, _ = self.info()
+        order = np.empty(nt, dtype=np.int32)
+        rec = np.empty((nt, 4), dtype=np.int32)
+        check(_lib.lib().hps_memcpy_d2h(order.ctypes.data_as(C.c_void_p), C.c_void_p(off + 4 * (nt + 2)), order.nbytes))
+        check(_lib.lib().hps_memcpy_d2h(rec.ctypes.data_as(C.c_void_p), C.c_void_p(off + 4 * ((2 * nt + 2 + 3) & ~3)), rec.nbytes))
+        return order, rec
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.lib().hps_tiling_destroy(self._h)

@@ -8,12 +8,18 @@
 // cells (consecutive LDS addresses).  Measured at 1024^2 x 4 ppc: particles of one cell next to
 // each other cost 200 us per deposition (same-address LDS atomics serialise), a random order
 // 125 us, the interleaved order 70 us.
-//   pass 1: stable sort by (tile, cell in tile) of the particle's nearest cell, invalid ones last;
-//           rank = position within the run of equal keys, capped at RANK_CAP - 1
-//   pass 2: stable sort by (tile, rank, cell in tile)
-// Both are rocPRIM radix_sort_pairs (stable), so the permutation is reproducible bit for bit by the
-// CPU restatement (oracle: orc_tile_sort).  All 11 real arrays + idcpu + ion_lev are then gathered
-// through the permutation into a second SoA buffer.
+//   sort:  stable rocPRIM radix_sort_pairs by (tile, cell in tile) of the particle's nearest cell, invalid ones last;
+//          rank = position within the run of equal keys, capped at RANK_CAP - 1
+//   place: the order of a stable sort by (tile, rank, cell in tile), in closed form from the run starts of the cell
+//          keys (k_tile_place, one workgroup per tile): with n[c] particles in cell c of the tile, the particle at
+//          position r of cell c's run goes to
+//            r < RANK_CAP - 1:   sum_{q < r} #{c' : n[c'] > q}  +  #{c' < c : n[c'] > r}
+//            r >= RANK_CAP - 1:  sum_{q < RANK_CAP - 1} #{c' : n[c'] > q}  +  sum_{c' < c} max(n[c'] - (RANK_CAP - 1), 0)  +  r - (RANK_CAP - 1)
+//          inside its tile; the invalid particles keep the order of the sort.
+// The permutation is the one two stable sorts give, reproducible bit for bit by the CPU restatement (oracle:
+// orc_tile_sort).  All 11 real arrays + idcpu + ion_lev are then gathered through the permutation into a second SoA
+// buffer.  The launch order of the tile kernels (heaviest tile first) is ranked by counting (k_tile_launch_order); grids
+// of more than ORDER_COUNT_MAX tiles keep a rocPRIM sort of the tile weights for it.
 #include "common.h"
 #include "tiling.h"
 
@@ -74,27 +80,73 @@ void k_run_starts (const unsigned int* keys, long n, int nkeys, int* first)
     for (int k = prev + 1; k <= cur; ++k) first[k] = (int)p;
 }
 
-// second key from the position inside the run of equal cell keys
+// perm and offsets from the run starts of the sorted cell keys: workgroup t places the particles of tile t.  Thread i
+// owns the cells i, i + 256, ... (K of them) of the tile, so a wave ballot covers 64 consecutive cells.  The particles
+// of the tile come in RANK_CAP groups -- rank 0 .. RANK_CAP - 2 with at most one particle per cell, then the capped
+// rest -- and each group in cell order: base[(group*K + k)*4 + wave] is the number of the tile's particles ahead of the
+// 64 cells that `wave` holds in its k-th ballot of `group` (an exclusive scan over all the wave totals), the ballot's
+// lower lanes give the rest.  All workgroups share the copy of the invalid tail.
+template <int K>
 __global__ __launch_bounds__(256)
-void k_rank_keys (const unsigned int* ckeys, const int* first, long n, int ncell, unsigned int* keys2)
+void k_tile_place (const int* __restrict__ cell_first, const unsigned int* __restrict__ idx_sorted, int ntiles, int n,
+                   unsigned int* __restrict__ perm, int* __restrict__ offsets)
 {
-    const long p = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const unsigned int ck = ckeys[p];
-    const int rank = min((int)p - first[ck], RANK_CAP - 1);
-    const unsigned int tile = ck / ncell, cit = ck - tile*ncell;
-    keys2[p] = (tile*RANK_CAP + rank)*ncell + cit;
-}
-
-// offsets[t] = first sorted position whose tile (= key / per_tile) is >= t, t = 0 .. ntiles+1
-__global__ __launch_bounds__(256)
-void k_tile_offsets (const unsigned int* keys, long n, int ntiles, int per_tile, int* offsets)
-{
-    const long p = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    if (p > n) return;
-    const int prev = (p == 0) ? -1 : (int)(keys[p - 1]/per_tile);
-    const int cur = (p == n) ? ntiles + 1 : (int)(keys[p]/per_tile);
-    for (int t = prev + 1; t <= cur; ++t) offsets[t] = (int)p;
+    constexpr int NW = 4, NE = RANK_CAP*K*NW, PER = NE/64, CAP = RANK_CAP - 1;
+    __shared__ int base[NE];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c0 = t*(K*256);
+    int first[K], cnt[K], capx[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c = c0 + k*256 + tid;
+        first[k] = cell_first[c];
+        cnt[k] = cell_first[c + 1] - first[k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int r = 0; r < CAP; ++r) {
+            const unsigned long long b = __ballot(cnt[k] > r);
+            if (lane == 0) base[(r*K + k)*NW + w] = __popcll(b);
+        }
+        const int over = max(cnt[k] - CAP, 0);
+        int incl = over;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+        capx[k] = incl - over;
+        if (lane == 63) base[(CAP*K + k)*NW + w] = incl;
+    }
+    __syncthreads();
+    if (w == 0) {       // exclusive scan of the NE wave totals, PER consecutive ones per lane
+        int v[PER], s = 0;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) { v[j] = base[lane*PER + j]; s += v[j]; }
+        int incl = s;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(incl, d); if (lane >= d) incl += u; }
+        int run = incl - s;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) { base[lane*PER + j] = run; run += v[j]; }
+    }
+    __syncthreads();
+    const int tfirst = cell_first[c0];
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        for (int r = 0; r < CAP; ++r) {
+            const unsigned long long b = __ballot(cnt[k] > r);
+            if (b == 0) break;                      // the same in every lane of the wave
+            if (cnt[k] > r) perm[tfirst + base[(r*K + k)*NW + w] + __popcll(b & below)] = idx_sorted[first[k] + r];
+        }
+        const int place = tfirst + base[(CAP*K + k)*NW + w] + capx[k];
+        for (int r = CAP; r < cnt[k]; ++r) perm[place + r - CAP] = idx_sorted[first[k] + r];
+    }
+    const int inv0 = cell_first[ntiles*(K*256)];
+    if (tid == 0) {
+        offsets[t] = tfirst;
+        if (t == 0) { offsets[ntiles] = inv0; offsets[ntiles + 1] = n; }
+    }
+    for (long p = (long)inv0 + (long)t*256 + tid; p < n; p += (long)gridDim.x*256) perm[p] = idx_sorted[p];
 }
 
 // launch order of the tile kernels: workgroup b works on tile order[b], heaviest tile first (longest-processing-time
@@ -122,6 +174,55 @@ void k_tile_launch_info (const int* offsets, int ntiles, int4* launch)
     if (b >= ntiles) return;
     const int t = offsets[ntiles + 2 + b];
     launch[b] = make_int4(t, offsets[t], offsets[t + 1], 0);
+}
+
+// The launch order by counting, and the launch records, in one launch: tile t goes to
+//   position(t) = #{u : cnt[u] > cnt[t]} + #{u < t : cnt[u] == cnt[t]}
+// (heaviest first, ties by ascending tile: what a stable sort of 0xFFFFFFFF - cnt gives).  A workgroup ranks ORDER_TILES
+// tiles: every workgroup stages all the counts in LDS, lane (tile j, part q) counts over the q-th of ORDER_PARTS
+// stretches of them (16-byte reads), and the partial counts are summed over the lanes of a wave and then through LDS.
+// ntiles^2 compares: 4096 tiles take 256 workgroups x 16 waves x 64 counts per lane.  Beyond ORDER_COUNT_MAX tiles (the
+// LDS, and the quadratic work) tiling_sort sorts the weights with rocPRIM instead.
+constexpr int ORDER_TILES = 16, ORDER_PARTS = 64, ORDER_THREADS = ORDER_TILES*ORDER_PARTS, ORDER_COUNT_MAX = 8192;
+__global__ __launch_bounds__(ORDER_THREADS)
+void k_tile_launch_order (int* offsets, int ntiles, int4* launch)
+{
+    constexpr int NPAD = ORDER_COUNT_MAX + 4*ORDER_PARTS, PER = NPAD/ORDER_THREADS + 1;
+    __shared__ __attribute__((aligned(16))) int cnt[NPAD];
+    __shared__ int part[ORDER_THREADS/64][ORDER_TILES];
+    const int tid = threadIdx.x;
+    const int len = ((ntiles + ORDER_PARTS - 1)/ORDER_PARTS + 3) & ~3;        // counts per part, whole int4s
+    int first[PER], end[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {                 // every load of the thread in flight before the first use
+        const int i = min(tid + k*ORDER_THREADS, ntiles - 1);
+        first[k] = offsets[i]; end[k] = offsets[i + 1];
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int i = tid + k*ORDER_THREADS;
+        if (i < len*ORDER_PARTS) cnt[i] = i < ntiles ? end[k] - first[k] : -1;   // -1: behind every tile
+    }
+    __syncthreads();
+    const int j = tid & (ORDER_TILES - 1), q = tid/ORDER_TILES;
+    const int t = blockIdx.x*ORDER_TILES + j;
+    const int c = cnt[min(t, ntiles - 1)];
+    int pos = 0;
+    for (int u = q*len; u < (q + 1)*len; u += 4) {      // cnt[u] counts if > c, or, for u < t, if >= c
+        const int4 v = *reinterpret_cast<const int4*>(&cnt[u]);
+        pos += (v.x > c - (u < t)) + (v.y > c - (u + 1 < t)) + (v.z > c - (u + 2 < t)) + (v.w > c - (u + 3 < t));
+    }
+#pragma unroll
+    for (int d = ORDER_TILES; d < 64; d <<= 1) pos += __shfl_xor(pos, d);    // the lanes of the wave with the same tile
+    if ((tid & 63) < ORDER_TILES) part[tid >> 6][j] = pos;
+    __syncthreads();
+    if (tid < ORDER_TILES && t < ntiles) {
+        int p = 0;
+#pragma unroll
+        for (int k = 0; k < ORDER_THREADS/64; ++k) p += part[k][tid];
+        offsets[ntiles + 2 + p] = t;
+        launch[p] = make_int4(t, offsets[t], offsets[t + 1], 0);
+    }
 }
 
 __global__ __launch_bounds__(256)
@@ -161,24 +262,23 @@ int tiling_create (int nx, int ny, int ts, long capacity, Tiling** out)
     hipLaunchKernelGGL(k_tile_order_identity, dim3(ceil_div(T->g.ntiles, 256)), dim3(256), 0, (hipStream_t)0, T->offsets + T->g.ntiles + 2, T->g.ntiles);
     hipLaunchKernelGGL(k_tile_launch_info, dim3(ceil_div(T->g.ntiles, 256)), dim3(256), 0, (hipStream_t)0, T->offsets, T->g.ntiles, reinterpret_cast<int4*>(T->offsets + tile_launch_offset(T->g.ntiles)));
     HPS_HIP_CHECK(hipDeviceSynchronize());
-    HPS_HIP_CHECK(hipMalloc(&T->okeys, 3*(size_t)T->g.ntiles*sizeof(unsigned int)));
-    HPS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, T->otemp_bytes, T->okeys, T->okeys, T->okeys, T->okeys, (size_t)T->g.ntiles, 0, 32, (hipStream_t)0));
-    HPS_HIP_CHECK(hipMalloc(&T->otemp, T->otemp_bytes));
+    if (T->g.ntiles > ORDER_COUNT_MAX) {        // the launch order of a grid this large is sorted, not counted
+        HPS_HIP_CHECK(hipMalloc(&T->okeys, 3*(size_t)T->g.ntiles*sizeof(unsigned int)));
+        HPS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, T->otemp_bytes, T->okeys, T->okeys, T->okeys, T->okeys, (size_t)T->g.ntiles, 0, 32, (hipStream_t)0));
+        HPS_HIP_CHECK(hipMalloc(&T->otemp, T->otemp_bytes));
+    }
     HPS_HIP_CHECK(hipMalloc(&T->keys_a, capacity*sizeof(unsigned int)));
     HPS_HIP_CHECK(hipMalloc(&T->keys_b, capacity*sizeof(unsigned int)));
     HPS_HIP_CHECK(hipMalloc(&T->idx_a, capacity*sizeof(unsigned int)));
     HPS_HIP_CHECK(hipMalloc(&T->idx_b, capacity*sizeof(unsigned int)));
     const long ncell = (long)ts*ts;
     const long nkeys1 = (long)T->g.ntiles*ncell + 1;                 // cell keys, + the invalid key
-    const long nkeys2 = ((long)T->g.ntiles*RANK_CAP + 1)*ncell;      // (tile, rank, cell) keys
-    if (nkeys2 >= (1L << 31)) { delete T; set_error("hps_tiling_create: grid too large for 32-bit sort keys"); return HPS_ERR_ARG; }
+    if (nkeys1 >= (1L << 31)) { delete T; set_error("hps_tiling_create: grid too large for 32-bit sort keys"); return HPS_ERR_ARG; }
     int bits = 1; while ((1L << bits) < nkeys1) ++bits;
     T->key_bits = bits;
-    bits = 1; while ((1L << bits) < nkeys2) ++bits;
-    T->key2_bits = bits;
     HPS_HIP_CHECK(hipMalloc(&T->cell_first, (nkeys1 + 1)*sizeof(int)));
     HPS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, T->temp_bytes, T->keys_a, T->keys_b, T->idx_a, T->idx_b,
-                                            (size_t)capacity, 0, T->key2_bits, (hipStream_t)0));
+                                            (size_t)capacity, 0, T->key_bits, (hipStream_t)0));
     HPS_HIP_CHECK(hipMalloc(&T->temp, T->temp_bytes));
     *out = T;
     return HPS_OK;
@@ -202,18 +302,19 @@ int tiling_sort (Tiling* T, const hps_plasma& src, const hps_plasma& dst, const 
     HPS_HIP_CHECK(rocprim::radix_sort_pairs(T->temp, tb, T->keys_a, T->keys_b, T->idx_a, T->idx_b, (size_t)n, 0,
                                             T->key_bits, st));
     hipLaunchKernelGGL(k_run_starts, gn1, b256, 0, st, T->keys_b, n, nkeys1, T->cell_first);
-    hipLaunchKernelGGL(k_rank_keys, gn, b256, 0, st, T->keys_b, T->cell_first, n, ncell, T->keys_a);
-    tb = T->temp_bytes;
-    HPS_HIP_CHECK(rocprim::radix_sort_pairs(T->temp, tb, T->keys_a, T->keys_b, T->idx_b, T->idx_a, (size_t)n, 0,
-                                            T->key2_bits, st));
-    hipLaunchKernelGGL(k_tile_offsets, gn1, b256, 0, st, T->keys_b, n, T->g.ntiles, RANK_CAP*ncell, T->offsets);
+    if (ncell == 256) hipLaunchKernelGGL(k_tile_place<1>, dim3(T->g.ntiles), b256, 0, st, T->cell_first, T->idx_b, T->g.ntiles, (int)n, T->idx_a, T->offsets);
+    else hipLaunchKernelGGL(k_tile_place<4>, dim3(T->g.ntiles), b256, 0, st, T->cell_first, T->idx_b, T->g.ntiles, (int)n, T->idx_a, T->offsets);
     hipLaunchKernelGGL(k_permute, dim3(ceil_div(n, 256)), dim3(256), 0, st, src, dst, T->idx_a);
-    {   const int nt = T->g.ntiles;
+    const int nt = T->g.ntiles;
+    int4* launch = reinterpret_cast<int4*>(T->offsets + tile_launch_offset(nt));
+    if (nt <= ORDER_COUNT_MAX)
+        hipLaunchKernelGGL(k_tile_launch_order, dim3(ceil_div(nt, ORDER_TILES)), dim3(ORDER_THREADS), 0, st, T->offsets, nt, launch);
+    else {
         unsigned int *ka = T->okeys, *kb = T->okeys + nt, *va = T->okeys + 2*nt;
         hipLaunchKernelGGL(k_tile_order_keys, dim3(ceil_div(nt, 256)), b256, 0, st, T->offsets, nt, ka, va);
         size_t ob = T->otemp_bytes;
         HPS_HIP_CHECK(rocprim::radix_sort_pairs(T->otemp, ob, ka, kb, va, reinterpret_cast<unsigned int*>(T->offsets + nt + 2), (size_t)nt, 0, 32, st));
-        hipLaunchKernelGGL(k_tile_launch_info, dim3(ceil_div(nt, 256)), b256, 0, st, T->offsets, nt, reinterpret_cast<int4*>(T->offsets + tile_launch_offset(nt))); }
+        hipLaunchKernelGGL(k_tile_launch_info, dim3(ceil_div(nt, 256)), b256, 0, st, T->offsets, nt, launch); }
     HPS_HIP_CHECK(hipGetLastError());
     T->sorted_n = n;
     return HPS_OK;

@@ -14,9 +14,9 @@ struct Tiling {
     long capacity = 0, sorted_n = 0;
     int* offsets = nullptr;                       // [ntiles + 2] offsets, then [ntiles] launch order (heaviest tile first), then (16-byte
                                                   // aligned, tile_launch_offset) [ntiles] int4 {tile, first, end, 0} per workgroup, device
-    unsigned int *okeys = nullptr; void* otemp = nullptr; size_t otemp_bytes = 0;      // scratch of the launch-order sort
+    unsigned int *okeys = nullptr; void* otemp = nullptr; size_t otemp_bytes = 0;      // scratch of the launch-order sort (grids the counting kernel does not take)
     unsigned int *keys_a = nullptr, *keys_b = nullptr, *idx_a = nullptr, *idx_b = nullptr;
-    void* temp = nullptr; size_t temp_bytes = 0; int key_bits = 0, key2_bits = 0;
+    void* temp = nullptr; size_t temp_bytes = 0; int key_bits = 0;
     int* cell_first = nullptr;                    // [ntiles*ts*ts + 2] run starts of the cell keys
     // the sheet is one whose every invalidation also zeroes psi_half (the engine's own electron sheet: k_init_plasma, the QSA drop of
     // the depositions, the absorbing boundary of the pushes): the tile push then takes "psi_half != 0" for the valid bit and does
