@@ -472,7 +472,10 @@ class AdaptiveTimeStep:
 class SliceEngine:
     """Device-resident slice loop for one deck (see hipace_amd/decks.py)."""
 
-    def __init__(self, deck, device=0, tile_size=None, sort_period=None):
+    def __init__(self, deck, device=0, tile_size=None, sort_period=None, fine_patch=None, fine_transition_cells=None):
+        """fine_patch: plasmas.fine_patch(x,y) as a callable f(x, y) over numpy arrays (> 0 / True = fine) or a boolean
+        (ny, nx) mask, with fine_transition_cells (default 5, the reference's) cells of transition around it; default: the
+        deck's "fine_patch" / "fine_transition_cells" entries.  Needs plasma_fine_ppc and / or ion_fine_ppc in the deck."""
         self.deck = dict(deck)
         self.step_times = []            # hipace.dt = adaptive in a pipeline: (step, t, dt) of every step this engine began
         self._dk = _lib.fill_struct(_lib.Deck(), deck)
@@ -480,6 +483,17 @@ class SliceEngine:
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
         if tile_size is not None:
             check(_lib.lib().hps_engine_set_tiling(self._h, tile_size, sort_period or 128))
+        # not members of hps_deck: applied through the setters, fine_ppc ahead of the patch
+        pf, jf = tuple(deck.get("plasma_fine_ppc", (0, 0))), tuple(deck.get("ion_fine_ppc", (0, 0)))
+        hollow = float(deck.get("plasma_hollow_core_radius", 0.0))
+        if any(pf) or any(jf) or hollow != 0.0:
+            check(_lib.lib().hps_engine_set_plasma_init(self._h, (C.c_int * 2)(*pf), (C.c_int * 2)(*jf), hollow))
+        if fine_patch is None:
+            fine_patch = deck.get("fine_patch")
+        if fine_patch is not None:
+            if fine_transition_cells is None:
+                fine_transition_cells = deck.get("fine_transition_cells", 5)
+            self.set_fine_patch(fine_patch, fine_transition_cells)
         for a, b, coulomb_log, seed in deck.get("collisions", ()):      # not a member of hps_deck: applied through the setters
             if a == "beam":                                             # ("beam", plasma species, CoulombLog, seed)
                 self.add_beam_collision(b, coulomb_log, seed)
@@ -519,6 +533,29 @@ class SliceEngine:
 
     def set_tiling(self, tile_size=16, sort_period=128):
         check(_lib.lib().hps_engine_set_tiling(self._h, tile_size, sort_period))
+
+    def fine_patch_mask(self, fine_patch):
+        """plasmas.fine_patch(x,y) > 0 at the cell centres lo + (i + 0.5) dx as a (ny, nx) uint8 array; a mask is passed on"""
+        nx, ny = self.deck["nx"], self.deck["ny"]
+        if callable(fine_patch):
+            lo, hi = self.deck["lo"], self.deck["hi"]
+            dx, dy = (hi[0] - lo[0]) / nx, (hi[1] - lo[1]) / ny
+            x = lo[0] + (np.arange(nx) + 0.5) * dx
+            y = lo[1] + (np.arange(ny) + 0.5) * dy
+            fine_patch = np.broadcast_to(np.asarray(fine_patch(x[None, :], y[:, None])), (ny, nx)) > 0
+        m = np.ascontiguousarray(np.asarray(fine_patch) != 0, dtype=np.uint8)
+        if m.shape != (ny, nx):
+            raise ValueError(f"fine_patch: the mask must have the shape (ny, nx) = {(ny, nx)}, not {m.shape}")
+        return m
+
+    def set_fine_patch(self, fine_patch, transition_cells=5):
+        """plasmas.fine_patch(x,y) and fine_transition_cells (hps_engine_set_fine_patch), before the first begin_step:
+        fine_patch is a callable f(x, y) over numpy arrays or a boolean (ny, nx) mask."""
+        m = self.fine_patch_mask(fine_patch)
+        check(_lib.lib().hps_engine_set_fine_patch(self._h, m.ctypes.data_as(C.c_void_p), int(transition_cells)))
+        npart = C.c_long()
+        check(_lib.lib().hps_engine_info(self._h, None, None, C.byref(npart)))
+        self.nparticles = npart.value
 
     def add_collision(self, species_a=0, species_b=0, coulomb_log=-1.0, seed=0):
         """hipace.collisions: one more Coulomb collision between species 0 (plasma) / 1 (ion), before the first begin_step

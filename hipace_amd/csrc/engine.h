@@ -73,6 +73,14 @@ struct Engine {
                 } ion;
     // tabulated plasma density profile (hps_engine_set_density_profile): radial table on the device, time table on the host
     std::vector<double> prof_r, prof_t, prof_f_t; double* d_prof_r = nullptr; double prof_ft = 1.0;
+    // <plasma>.fine_patch / fine_ppc / fine_transition_cells / hollow_core_radius (plasma_init.hip): the level map
+    // [ny][nx] (0 coarse, 1..T transition, T + 1 fine) and the x-fastest list of the cells with level > 0, shared by the species
+    int fine_ppc[2] = {0, 0}, ion_fine_ppc[2] = {0, 0}; double hollow_core_radius = 0.0;
+    bool fine_patch_set = false; int fine_T = 0; long fine_ncells = 0; int* d_fine_level = nullptr; int* d_fine_cells = nullptr;
+    long sheet_slots (const int ppc[2], const int fine[2]) const;
+    int alloc_sheets ();
+    int set_plasma_init (const int* plasma_fine, const int* ion_fine, double hollow_core);
+    int set_fine_patch (const unsigned char* mask_host, int transition_cells);
     // fused push(k) + deposit(k-1) (k_advance_deposit_tiled): ahead_for = slice whose plasma currents are already deposited
     bool fuse_push_deposit = false; int ahead_for = -2;
     long fallback_div = 256;                    // re-sort once more than np / fallback_div particle visits since the last sort left their tile's halo (HPS_SORT_FALLBACK_DIV)
@@ -218,6 +226,9 @@ struct Engine {
 int ion_create (Engine& E);                                                  // ionization.hip
 void ion_destroy (Engine& E);
 unsigned event_flags (bool timing);                                           // engine.hip
+// plasma_init.hip: InitParticles with the fine patch and / or the hollow core for one species' sheet
+int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
+                      double radius_sq);
 int laser_create (Engine& E);                                                // laser.hip
 void laser_destroy (Engine& E);
 int laser_begin_step (Engine& E);

@@ -351,7 +351,7 @@ Engine::~Engine ()
     (void)hipFree(d_laser_sum);
     if (laser) laser_destroy(*this);
     ion_destroy(*this);
-    (void)hipFree(d_prof_r);
+    (void)hipFree(d_prof_r); (void)hipFree(d_fine_level); (void)hipFree(d_fine_cells);
     (void)hipFree(d_fd); (void)hipFree(d_fd_comps); (void)hipFree(d_insitu); (void)hipFree(d_insitu_pl); (void)hipFree(d_insitu_bm);
     for (auto e : ev) (void)hipEventDestroy(e);
     for (auto e : hand_ev) if (e) (void)hipEventDestroy(e);
@@ -644,6 +644,49 @@ static hipError_t create_engine_stream (hipStream_t* s, int device, bool* pooled
     return hipExtStreamCreateWithCUMask(s, 8, mask);
 }
 
+// Slots of a species' sheet: ppc per cell, and fine_ppc in the cells of the fine patch and its transition
+long Engine::sheet_slots (const int ppc[2], const int fine[2]) const
+{
+    const long cells = (long)d.nx*d.ny, nc = (long)ppc[0]*ppc[1];
+    if (!(fine_patch_set && fine[0] > 0)) return nc*cells;
+    return nc*cells + ((long)fine[0]*fine[1] - nc)*fine_ncells;
+}
+
+// The sheets of both species, sized by what InitParticles creates; hps_engine_set_plasma_init / hps_engine_set_fine_patch
+// call it again (before the first step: nothing else holds a pointer into them yet)
+int Engine::alloc_sheets ()
+{
+    (void)hipFree(pl_real); (void)hipFree(pl.idcpu); (void)hipFree(pl.ion_lev); pl_real = nullptr;
+    (void)hipFree(ion.real); (void)hipFree(ion.pl.idcpu); (void)hipFree(ion.pl.ion_lev); ion.real = nullptr;
+    std::memset(&ion.pl, 0, sizeof(ion.pl));
+    np = (d.plasma_density > 0.0) ? sheet_slots(d.plasma_ppc, fine_ppc) : 0;
+    np_init = np; np_cap = np;
+    if (d.ion_on) {
+        ion.n = sheet_slots(d.ion_ppc, ion_fine_ppc);
+        // every ion can release Z - initial level electrons into the first species
+        np_cap = np_init + ion.n*(long)(d.ion_Z - d.ion_init_level);
+    }
+    std::memset(&pl, 0, sizeof(pl));
+    pl.n = np;
+    auto alloc_sheet = [&] (hps_plasma& p, double*& real, long cap, bool alias) -> int {
+        HPS_HIP_CHECK(hipMalloc(&real, (size_t)cap*11*sizeof(double)));
+        double** arr[11] = {&p.x, &p.y, &p.w, &p.ux, &p.uy, &p.psi, &p.x_prev, &p.y_prev, &p.ux_half, &p.uy_half, &p.psi_half};
+        for (int k = 0; k < 11; ++k) *arr[k] = real + (size_t)k*cap;
+        // explicit solver: every push commits its state (temp_slice = false), so x_prev == x and y_prev == y at
+        // all times (PlasmaParticleAdvance.cpp:176-188): alias them -- two arrays less to write per push and to
+        // move per re-sort.  The C ABI keeps 11 pointers; the kernels skip the second store when two coincide.
+        // (the predictor-corrector pushes to temporary slices from x_prev: separate arrays there)
+        if (alias) { p.x_prev = p.x; p.y_prev = p.y; }
+        HPS_HIP_CHECK(hipMalloc(&p.idcpu, (size_t)cap*sizeof(uint64_t)));
+        HPS_HIP_CHECK(hipMalloc(&p.ion_lev, (size_t)cap*sizeof(int32_t)));
+        return HPS_OK;
+    };
+    // (SALAME pushes to the temporary slice from x_prev, as the predictor-corrector does: separate arrays there too)
+    if (np_cap > 0) { if (int e = alloc_sheet(pl, pl_real, np_cap, !pc && c_sal < 0)) return e; }
+    if (ion.n > 0) { ion.pl.n = ion.n; if (int e = alloc_sheet(ion.pl, ion.real, ion.n, !pc)) return e; }
+    return HPS_OK;
+}
+
 int Engine::create (const hps_deck& deck, int device)
 {
     d = deck;
@@ -736,37 +779,14 @@ int Engine::create (const hps_deck& deck, int device)
     HPS_HIP_CHECK(hipMemset(slab.p, 0, (size_t)slab.nstride*slab.ncomp*sizeof(double)));
     HPS_HIP_CHECK(hipMalloc(&staging, (size_t)3*d.nx*d.ny*sizeof(double)));
 
-    const int nppc = d.plasma_ppc[0]*d.plasma_ppc[1];
-    np = (d.plasma_density > 0.0) ? (long)nppc*d.nx*d.ny : 0;
-    np_init = np; np_cap = np;
     if (d.ion_on) {
         // (predictor-corrector: every species is pushed to the temporary slice and deposited in turn inside the loop; the ADK
         //  decisions are taken once per slice, ahead of the committing push, as Hipace.cpp:693-701 has them)
         HPS_REQUIRE(d.ion_ppc[0] >= 1 && d.ion_ppc[1] >= 1 && d.ion_density > 0.0 && d.ion_mass > 0.0 && d.ion_charge != 0.0,
                     "hps_engine_create: the ion species needs ppc, density, mass and charge");
-        ion.n = (long)d.ion_ppc[0]*d.ion_ppc[1]*d.nx*d.ny;
         if (int e = ion_create(*this)) return e;
-        // every ion can release Z - initial level electrons into the first species
-        np_cap = np_init + ion.n*(long)(d.ion_Z - d.ion_init_level);
     }
-    std::memset(&pl, 0, sizeof(pl));
-    pl.n = np;
-    auto alloc_sheet = [&] (hps_plasma& p, double*& real, long cap, bool alias) -> int {
-        HPS_HIP_CHECK(hipMalloc(&real, (size_t)cap*11*sizeof(double)));
-        double** arr[11] = {&p.x, &p.y, &p.w, &p.ux, &p.uy, &p.psi, &p.x_prev, &p.y_prev, &p.ux_half, &p.uy_half, &p.psi_half};
-        for (int k = 0; k < 11; ++k) *arr[k] = real + (size_t)k*cap;
-        // explicit solver: every push commits its state (temp_slice = false), so x_prev == x and y_prev == y at
-        // all times (PlasmaParticleAdvance.cpp:176-188): alias them -- two arrays less to write per push and to
-        // move per re-sort.  The C ABI keeps 11 pointers; the kernels skip the second store when two coincide.
-        // (the predictor-corrector pushes to temporary slices from x_prev: separate arrays there)
-        if (alias) { p.x_prev = p.x; p.y_prev = p.y; }
-        HPS_HIP_CHECK(hipMalloc(&p.idcpu, (size_t)cap*sizeof(uint64_t)));
-        HPS_HIP_CHECK(hipMalloc(&p.ion_lev, (size_t)cap*sizeof(int32_t)));
-        return HPS_OK;
-    };
-    // (SALAME pushes to the temporary slice from x_prev, as the predictor-corrector does: separate arrays there too)
-    if (np_cap > 0) { if (int e = alloc_sheet(pl, pl_real, np_cap, !pc && c_sal < 0)) return e; }
-    if (ion.n > 0) { ion.pl.n = ion.n; if (int e = alloc_sheet(ion.pl, ion.real, ion.n, !pc)) return e; }
+    if (int e = alloc_sheets()) return e;
     HPS_HIP_CHECK(hipMalloc(&d_laser_sum, sizeof(double)));
     HPS_HIP_CHECK(hipMemset(d_laser_sum, 0, sizeof(double)));
     HPS_HIP_CHECK(hipMalloc(&d_nqsa, sizeof(int)));
@@ -876,6 +896,9 @@ int Engine::begin_step ()
 {
     HPS_REQUIRE(!(d.dt_adaptive && steps_begun == 0 && d.beam_profile < 0 && !host_beam),
                 "hps_engine_begin_step: hipace.dt = adaptive needs a beam (beam_profile = -1 and no hps_engine_set_beam_particles: the sum of weights is 0)");
+    // (PlasmaParticleContainer.cpp:167-169)
+    HPS_REQUIRE(fine_patch_set == (fine_ppc[0] > 0 || ion_fine_ppc[0] > 0),
+                "hps_engine_begin_step: both fine_ppc (hps_engine_set_plasma_init) and the fine patch (hps_engine_set_fine_patch) must be given to use the fine plasma patch");
     if (int e = setup_tiling()) return e;
     step_begun = true;
     if (moving && steps_begun > 0) {
@@ -935,7 +958,9 @@ int Engine::begin_step ()
     if (int e = ionize_collect()) return e;
     np = np_init; pl.n = np; pl_alt.n = np;
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : std::numeric_limits<double>::infinity();
-    if (np > 0) {
+    if (np > 0 && (hollow_core_radius > 0.0 || (fine_patch_set && fine_ppc[0] > 0))) {
+        if (int e = init_plasma_fine(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq)) return e;
+    } else if (np > 0) {
         const int nppc = d.plasma_ppc[0]*d.plasma_ppc[1];
         hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(np, 256)), dim3(256), 0, st, pl, np, d.nx, d.ny,
                            d.plasma_ppc[0], d.plasma_ppc[1], d.lo[0], d.lo[1], gm.dx, gm.dy,
@@ -956,10 +981,14 @@ int Engine::begin_step ()
         // the species "ion": every macro-ion back on its lattice point at its initial level; the product species is back
         // to its own InitParticles count
         const int inppc = d.ion_ppc[0]*d.ion_ppc[1];
-        hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(ion.n, 256)), dim3(256), 0, st, ion.pl, ion.n, d.nx, d.ny,
-                           d.ion_ppc[0], d.ion_ppc[1], d.lo[0], d.lo[1], gm.dx, gm.dy,
-                           d.ion_density*(d.si_units ? gm.dx*gm.dy*gm.dz/inppc : 1.0/inppc), d.ion_init_level, 1,
-                           d_prof_r, (int)prof_r.size(), prof_ft, radius_sq);
+        if (hollow_core_radius > 0.0 || (fine_patch_set && ion_fine_ppc[0] > 0)) {
+            if (int e = init_plasma_fine(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq)) return e;
+        } else {
+            hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(ion.n, 256)), dim3(256), 0, st, ion.pl, ion.n, d.nx, d.ny,
+                               d.ion_ppc[0], d.ion_ppc[1], d.lo[0], d.lo[1], gm.dx, gm.dy,
+                               d.ion_density*(d.si_units ? gm.dx*gm.dy*gm.dz/inppc : 1.0/inppc), d.ion_init_level, 1,
+                               d_prof_r, (int)prof_r.size(), prof_ft, radius_sq);
+        }
         if (ion.tiling) {
             ion.pl_alt.n = ion.n;
             if (int e = tiling_sort(ion.tiling, ion.pl, ion.pl_alt, gm, st)) return e;
@@ -2751,6 +2780,16 @@ extern "C" int hps_engine_set_fusion (void* h, int on)
 {
     static_cast<Engine*>(h)->fuse_push_deposit = (on != 0);
     return HPS_OK;
+}
+extern "C" int hps_engine_set_plasma_init (void* h, const int* plasma_fine_ppc, const int* ion_fine_ppc, double hollow_core_radius)
+{
+    HPS_REQUIRE(h, "hps_engine_set_plasma_init: null engine");
+    return static_cast<Engine*>(h)->set_plasma_init(plasma_fine_ppc, ion_fine_ppc, hollow_core_radius);
+}
+extern "C" int hps_engine_set_fine_patch (void* h, const unsigned char* mask_host, int transition_cells)
+{
+    HPS_REQUIRE(h, "hps_engine_set_fine_patch: null engine");
+    return static_cast<Engine*>(h)->set_fine_patch(mask_host, transition_cells);
 }
 extern "C" int hps_engine_fallbacks (void* h, long* n)
 {

@@ -78,6 +78,12 @@ ADAPTIVE_DEFAULT = dict(
 SALAME_DEFAULT = dict(beam_do_salame=0, salame_n_iter=0, salame_relative_tolerance=0.0, salame_no_advance=0,
                       salame_Ez_target_slope=0.0)
 
+# <plasma>.fine_ppc, <ion>.fine_ppc and <plasma>.hollow_core_radius (PlasmaParticleContainer.cpp:123-169).  Kept apart from
+# _DEFAULT like ADAPTIVE_DEFAULT; 0 = off.  Like "collisions" they are not members of hps_deck: SliceEngine applies them
+# through hps_engine_set_plasma_init.  The patch itself (plasmas.fine_patch(x,y)) and fine_transition_cells are arguments
+# of SliceEngine; a deck may carry them as "fine_patch" (a callable f(x, y) or a (ny, nx) mask) and "fine_transition_cells".
+PLASMA_INIT_DEFAULT = dict(plasma_fine_ppc=(0, 0), ion_fine_ppc=(0, 0), plasma_hollow_core_radius=0.0)
+
 # Ionisation energies in eV of a few elements: NIST Atomic Spectra Database (Kramida, Ralchenko, Reader and NIST ASD
 # Team, ver. 5.2), the values the reference tabulates in utils/IonizationEnergiesTable.H.
 IONIZATION_ENERGIES_EV = {
@@ -109,6 +115,31 @@ def with_ion_species(d, element, density, ppc=(1, 1), mass_Da=None, initial_leve
 def blowout_wake():
     d = copy.deepcopy(_DEFAULT)
     d["n_steps"] = 2
+    return d
+
+
+class fine_patch_disc:
+    """plasmas.fine_patch(x,y) = "sqrt(x^2+y^2) < radius" (a class, so that a deck that carries it can be pickled)"""
+
+    def __init__(self, radius):
+        self.radius = float(radius)
+
+    def __call__(self, x, y):
+        return x * x + y * y < self.radius * self.radius
+
+    def __eq__(self, other):
+        return isinstance(other, fine_patch_disc) and other.radius == self.radius
+
+    def __hash__(self):
+        return hash(self.radius)
+
+
+def blowout_wake_fine_patch(radius=2.0, transition_cells=2):
+    """The 64 x 64 blowout deck with 1 x 1 particles per cell, 4 x 4 inside the disc r < radius around the axis and
+    `transition_cells` cells of transition around it (<plasma>.fine_ppc, plasmas.fine_patch, fine_transition_cells)."""
+    d = blowout_wake()
+    d.update(PLASMA_INIT_DEFAULT)
+    d.update(plasma_ppc=(1, 1), plasma_fine_ppc=(4, 4), fine_patch=fine_patch_disc(radius), fine_transition_cells=transition_cells)
     return d
 
 

@@ -477,6 +477,32 @@ int hps_engine_fallbacks (void* handle, long* n_fallback_host);
  * (min_density = 0).  Applies to every plasma species from the next hps_engine_begin_step on. */
 int hps_engine_set_density_profile (void* handle, int nr, const double* r_host, const double* fr_host, int nt,
                                     const double* ct_host, const double* ft_host);
+/* The plasma fine patch and the hollow core (InitParticles, PlasmaParticleContainerInit.cpp:36-313; get_position_unit_cell_fine,
+ * ParticleUtil.H:66-104; the keys, PlasmaParticleContainer.cpp:123-169).  These values are not members of hps_deck (its layout
+ * is pinned); 0 = off.
+ *   hps_engine_set_plasma_init: <plasma>.fine_ppc and <ion>.fine_ppc ([2] each, NULL or {0, 0}: that species keeps its uniform
+ *     ppc lattice) and <plasma>.hollow_core_radius, the inner counterpart of plasma_radius, which like it holds for both
+ *     species: no particle with x^2 + y^2 < hollow_core_radius^2 (:165, :218, :278).
+ *   hps_engine_set_fine_patch: plasmas.fine_patch(x,y) > 0, evaluated by the caller at the cell centres lo + (i + 0.5) dx (the
+ *     only place the reference evaluates it, :108-110; the input parser is out of scope), as mask_host[ny][nx], != 0 = fine,
+ *     and plasmas.fine_transition_cells = T.  The patch is shared by the species.  The level of a cell is T + 1 inside the
+ *     patch and falls by one per cell of Manhattan distance around it (T passes of max(own, neighbour - 1), :117-138), on the
+ *     cell box cropped to plasma_radius where that is finite (:70-82): mask cells outside that box are ignored and the
+ *     transition does not grow past its edges.  A cell of level 0 owns ppc_x ppc_y slots of the sheet on the ppc lattice
+ *     with weight density / (ppc_x ppc_y); a cell of level L > 0 owns fine_x fine_y slots with weight density / (fine_x
+ *     fine_y), each placed between its coarse and its fine lattice point at s = L / (T + 1), s <- 1.5 s - 0.5 s^3
+ *     (ParticleUtil.H:84-103).  Slot order: i_part outermost, the cells that own it x-fastest (:192-239).  The number of slots
+ *     is fixed from this call on (hps_engine_info, the sheet arrays, the tiling capacity follow it); a slot beyond the radius,
+ *     inside the hollow core or without density is an invalid one, so the count does not change with the profile's time factor.
+ * Both: after hps_engine_create and before the first hps_engine_begin_step, in either order, before or after
+ * hps_engine_set_tiling; each call allocates the sheets anew.  HPS_ERR_ARG: fine_ppc not positive or not divisible by ppc,
+ * component by component (PlasmaParticleContainer.cpp:158-163); ion fine_ppc without the ion species; hollow_core_radius < 0
+ * or >= plasma_radius (:126-128); transition_cells < 0; a call after the first hps_engine_begin_step.  Exactly one of
+ * fine_ppc and the patch given (:167-169): HPS_ERR_ARG from the first hps_engine_begin_step.  Every engine mode takes the
+ * non-uniform sheet, the fused schedule (hps_engine_set_fusion) included.  Decks without these calls run k_init_plasma as
+ * before, bit for bit.  Not restated: prevent_centered_particle, do_symmetrize, temperature_in_ev / u_std. */
+int hps_engine_set_plasma_init (void* handle, const int* plasma_fine_ppc, const int* ion_fine_ppc, double hollow_core_radius);
+int hps_engine_set_fine_patch (void* handle, const unsigned char* mask_host, int transition_cells);
 /* Fused schedule: the gather + push of slice k also deposits the pushed particles' currents into slice k-1 (one pass over
  * the sheet instead of two; the slab is shifted / cleared before it).  After hps_engine_solve_slice(k) the components jx,
  * jy, chi, rhomjz [, rho] then already belong to slice k-1; everything else, the per-slice checksums and diagnostics are
