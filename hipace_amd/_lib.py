@@ -207,6 +207,8 @@ _SIGS = {
     "hps_engine_set_density_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "hps_engine_set_plasma_init": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_double]),
     "hps_engine_set_fine_patch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "hps_engine_set_plasma_momentum": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_ulonglong]),
+    "hps_engine_set_plasma_symmetry": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hps_engine_sorts": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
     "hps_engine_assume_initial_beam_support": (C.c_int, [C.c_void_p]),
     "hps_engine_beam_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, decks as _decks
 from ._lib import CIDX, COMPS, ID_VALID, PL_REAL, check
 
 
@@ -488,6 +488,15 @@ class SliceEngine:
         hollow = float(deck.get("plasma_hollow_core_radius", 0.0))
         if any(pf) or any(jf) or hollow != 0.0:
             check(_lib.lib().hps_engine_set_plasma_init(self._h, (C.c_int * 2)(*pf), (C.c_int * 2)(*jf), hollow))
+        # warm plasmas (decks.PLASMA_THERMAL_DEFAULT): a deck without these keys, or with all of them zero, makes no call
+        for sp, name in enumerate(("plasma", "ion")):
+            u_mean = tuple(float(v) for v in deck.get(name + "_u_mean", (0.0, 0.0, 0.0)))
+            u_std = _decks.thermal_u_std(deck, name)
+            if any(u_mean) or any(u_std):
+                self.set_plasma_momentum(sp, u_mean, u_std, deck.get("plasma_seed", 0))
+        sym, prevent = deck.get("plasmas_do_symmetrize", 0), deck.get("plasmas_prevent_centered_particle", 0)
+        if sym or prevent:
+            self.set_plasma_symmetry(sym, prevent)
         if fine_patch is None:
             fine_patch = deck.get("fine_patch")
         if fine_patch is not None:
@@ -553,6 +562,19 @@ class SliceEngine:
         fine_patch is a callable f(x, y) over numpy arrays or a boolean (ny, nx) mask."""
         m = self.fine_patch_mask(fine_patch)
         check(_lib.lib().hps_engine_set_fine_patch(self._h, m.ctypes.data_as(C.c_void_p), int(transition_cells)))
+        npart = C.c_long()
+        check(_lib.lib().hps_engine_info(self._h, None, None, C.byref(npart)))
+        self.nparticles = npart.value
+
+    def set_plasma_momentum(self, species=0, u_mean=(0.0, 0.0, 0.0), u_std=(0.0, 0.0, 0.0), seed=0):
+        """<plasma>.u_mean / u_std of species 0 (plasma) / 1 (ion) in units of c and the seed of its momentum draws
+        (hps_engine_set_plasma_momentum), before the first begin_step."""
+        check(_lib.lib().hps_engine_set_plasma_momentum(self._h, int(species), (C.c_double * 3)(*u_mean), (C.c_double * 3)(*u_std), int(seed)))
+
+    def set_plasma_symmetry(self, do_symmetrize=False, prevent_centered_particle=False):
+        """plasmas.do_symmetrize and prevent_centered_particle, one value for both species (hps_engine_set_plasma_symmetry),
+        before the first begin_step; the particle count follows the four mirrored copies."""
+        check(_lib.lib().hps_engine_set_plasma_symmetry(self._h, int(bool(do_symmetrize)), int(bool(prevent_centered_particle))))
         npart = C.c_long()
         check(_lib.lib().hps_engine_info(self._h, None, None, C.byref(npart)))
         self.nparticles = npart.value

@@ -45,18 +45,7 @@ struct CollArgs {
 };
 
 
-// ---- counter-based generator: chained two-round splitmix64 finaliser (the construction of ion_uniform) ---------------
-__host__ __device__ inline unsigned long long coll_hash (unsigned long long h, unsigned long long v)
-{
-    unsigned long long z = h + 0x9E3779B97F4A7C15ULL*(v + 1);
-    for (int r = 0; r < 2; ++r) {
-        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ULL;
-        z ^= z >> 27; z *= 0x94D049BB133111EBULL;
-        z ^= z >> 31;
-    }
-    return z;
-}
-__device__ __forceinline__ double coll_unit (unsigned long long z) { return (double)(z >> 11)*(1.0/9007199254740992.0); }
+// ---- counter-based generator: coll_hash / coll_unit (particle_math.h) ----------------------------------------------------
 // stream 0: the pairs' draws (a = pair k, b = draw index); stream 1 + slot: the shuffle of species slot (a = position, b = 0)
 __device__ __forceinline__ double coll_uniform (unsigned long long cell_key, unsigned stream, unsigned a, unsigned b)
 {

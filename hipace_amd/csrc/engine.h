@@ -77,6 +77,20 @@ struct Engine {
     // [ny][nx] (0 coarse, 1..T transition, T + 1 fine) and the x-fastest list of the cells with level > 0, shared by the species
     int fine_ppc[2] = {0, 0}, ion_fine_ppc[2] = {0, 0}; double hollow_core_radius = 0.0;
     bool fine_patch_set = false; int fine_T = 0; long fine_ncells = 0; int* d_fine_level = nullptr; int* d_fine_cells = nullptr;
+    // <plasma>.u_mean / u_std (temperature_in_ev), plasmas.do_symmetrize, prevent_centered_particle (plasma_init.hip):
+    // species 0 = plasma, 1 = ion; the two switches hold for both species
+    struct Thermal { double u_mean[3] = {0.0, 0.0, 0.0}, u_std[3] = {0.0, 0.0, 0.0}; unsigned long long seed = 0;
+                     bool warm () const { for (int q = 0; q < 3; ++q) if (u_mean[q] != 0.0 || u_std[q] != 0.0) return true; return false; }
+                   } thermal[2];
+    bool do_symmetrize = false, prevent_centered = false;
+    bool shifted (const int ppc[2], int dir) const { return prevent_centered && (dir == 0 ? d.nx : d.ny) % 2 == 1 && ppc[dir] % 2 == 1; }
+    // does this species' sheet come from k_init_plasma_warm?  (false: the kernels and arguments of a deck without these keys)
+    bool warm_init (int species) const {
+        const int* ppc = species == 0 ? d.plasma_ppc : d.ion_ppc;
+        return thermal[species].warm() || do_symmetrize || shifted(ppc, 0) || shifted(ppc, 1);
+    }
+    int set_plasma_momentum (int species, const double* u_mean, const double* u_std, unsigned long long seed);
+    int set_plasma_symmetry (int symmetrize, int prevent_centered_particle);
     long sheet_slots (const int ppc[2], const int fine[2]) const;
     int alloc_sheets ();
     int set_plasma_init (const int* plasma_fine, const int* ion_fine, double hollow_core);
@@ -229,6 +243,9 @@ unsigned event_flags (bool timing);                                           //
 // plasma_init.hip: InitParticles with the fine patch and / or the hollow core for one species' sheet
 int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
                       double radius_sq);
+// ...: the same sheet with Gaussian momenta, its mirror copies and / or the lattice shifted off the axis (Engine::warm_init)
+int init_plasma_warm (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
+                      double radius_sq, int species);
 int laser_create (Engine& E);                                                // laser.hip
 void laser_destroy (Engine& E);
 int laser_begin_step (Engine& E);

@@ -648,8 +648,9 @@ static hipError_t create_engine_stream (hipStream_t* s, int device, bool* pooled
 long Engine::sheet_slots (const int ppc[2], const int fine[2]) const
 {
     const long cells = (long)d.nx*d.ny, nc = (long)ppc[0]*ppc[1];
-    if (!(fine_patch_set && fine[0] > 0)) return nc*cells;
-    return nc*cells + ((long)fine[0]*fine[1] - nc)*fine_ncells;
+    const long copies = do_symmetrize ? 4 : 1;       // do_symmetrize: the sheet and its three mirror copies
+    if (!(fine_patch_set && fine[0] > 0)) return copies*nc*cells;
+    return copies*(nc*cells + ((long)fine[0]*fine[1] - nc)*fine_ncells);
 }
 
 // The sheets of both species, sized by what InitParticles creates; hps_engine_set_plasma_init / hps_engine_set_fine_patch
@@ -932,7 +933,8 @@ int Engine::begin_step ()
     // with a grid current, and with a second species as particles (or no neutralising background): there the serial path's
     // charges cancel to rounding only, it iterates on that residue itself, and the literal rule on the engine's residue is its
     // match (any non-zero byte pattern reads as "disturbed")
-    if (d_pc_dist) HPS_HIP_CHECK(hipMemsetAsync(d_pc_dist, (d.grid_current_on || d.ion_on || d.plasma_no_neutralize) ? 1 : 0, sizeof(int), st));
+    // A warm plasma deposits real jx, jy from the first slice on.
+    if (d_pc_dist) HPS_HIP_CHECK(hipMemsetAsync(d_pc_dist, (d.grid_current_on || d.ion_on || d.plasma_no_neutralize || thermal[0].warm() || thermal[1].warm()) ? 1 : 0, sizeof(int), st));
     HPS_HIP_CHECK(hipMemsetAsync(d_checksum, 0, HPS_PC_NCOMP_MAX*sizeof(double), st));
     HPS_HIP_CHECK(hipMemsetAsync(d_laser_sum, 0, sizeof(double), st));
     if (int e = join_laser()) return e;        // the time levels rotate: the last slice's envelope must be in
@@ -958,7 +960,9 @@ int Engine::begin_step ()
     if (int e = ionize_collect()) return e;
     np = np_init; pl.n = np; pl_alt.n = np;
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : std::numeric_limits<double>::infinity();
-    if (np > 0 && (hollow_core_radius > 0.0 || (fine_patch_set && fine_ppc[0] > 0))) {
+    if (np > 0 && warm_init(0)) {
+        if (int e = init_plasma_warm(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq, 0)) return e;
+    } else if (np > 0 && (hollow_core_radius > 0.0 || (fine_patch_set && fine_ppc[0] > 0))) {
         if (int e = init_plasma_fine(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq)) return e;
     } else if (np > 0) {
         const int nppc = d.plasma_ppc[0]*d.plasma_ppc[1];
@@ -981,7 +985,9 @@ int Engine::begin_step ()
         // the species "ion": every macro-ion back on its lattice point at its initial level; the product species is back
         // to its own InitParticles count
         const int inppc = d.ion_ppc[0]*d.ion_ppc[1];
-        if (hollow_core_radius > 0.0 || (fine_patch_set && ion_fine_ppc[0] > 0)) {
+        if (warm_init(1)) {
+            if (int e = init_plasma_warm(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq, 1)) return e;
+        } else if (hollow_core_radius > 0.0 || (fine_patch_set && ion_fine_ppc[0] > 0)) {
             if (int e = init_plasma_fine(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq)) return e;
         } else {
             hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(ion.n, 256)), dim3(256), 0, st, ion.pl, ion.n, d.nx, d.ny,
@@ -2785,6 +2791,16 @@ extern "C" int hps_engine_set_plasma_init (void* h, const int* plasma_fine_ppc, 
 {
     HPS_REQUIRE(h, "hps_engine_set_plasma_init: null engine");
     return static_cast<Engine*>(h)->set_plasma_init(plasma_fine_ppc, ion_fine_ppc, hollow_core_radius);
+}
+extern "C" int hps_engine_set_plasma_momentum (void* h, int species, const double* u_mean, const double* u_std, unsigned long long seed)
+{
+    HPS_REQUIRE(h, "hps_engine_set_plasma_momentum: null engine");
+    return static_cast<Engine*>(h)->set_plasma_momentum(species, u_mean, u_std, seed);
+}
+extern "C" int hps_engine_set_plasma_symmetry (void* h, int do_symmetrize, int prevent_centered_particle)
+{
+    HPS_REQUIRE(h, "hps_engine_set_plasma_symmetry: null engine");
+    return static_cast<Engine*>(h)->set_plasma_symmetry(do_symmetrize, prevent_centered_particle);
 }
 extern "C" int hps_engine_set_fine_patch (void* h, const unsigned char* mask_host, int transition_cells)
 {

@@ -104,7 +104,7 @@ void k_ion_field_bounds (SlabView f, int cPsi, int cEz, int cBx, int cBy, int ts
 
 int Engine::ion_field_bounds ()
 {
-    if (!ion.tiling || !ion.d_fbound) return HPS_OK;
+    if (!ion.tiling || !ion.d_fbound || thermal[1].warm()) return HPS_OK;
     const TileGeom& g = ion.tiling->g;
     const int cP = pc ? (int)HPS_PC_PSI : (int)HPS_C_PSI, cE = pc ? (int)HPS_PC_EZ : (int)HPS_C_EZ, cX = pc ? (int)HPS_PC_BX : (int)HPS_C_BX, cY = pc ? (int)HPS_PC_BY : (int)HPS_C_BY;
     hipLaunchKernelGGL(k_ion_field_bounds, dim3(g.ntiles), dim3(256), 0, st, SlabView(slab), cP, cE, cX, cY, g.ts, g.ntx, g.nty,
@@ -180,7 +180,8 @@ IonArgs Engine::ion_args (int islice)
     a.Z = d.ion_Z; a.seed = d.ion_seed; a.step = (unsigned long long)step_index; a.islice = (unsigned long long)islice;
     a.cap = np_cap; a.tile_flag = ion.d_tile_flag;
     a.product_init_lev = 0;       // the product species is the first (electron) species: not ionisable here, its particles carry level 0
-    a.fbound = (ion.tiling && ion.d_fbound) ? ion.d_fbound : nullptr;
+    // (the tile skip is a bound for atoms at rest: neutral atoms with momentum move, their tiles are pushed -- DESIGN 8i)
+    a.fbound = (ion.tiling && ion.d_fbound && !thermal[1].warm()) ? ion.d_fbound : nullptr;
     if (ion.tiling) { a.fb_ntx = ion.tiling->g.ntx; a.fb_nty = ion.tiling->g.nty; }
     a.fb_dx_inv = 1.0/gm.dx; a.fb_dy_inv = 1.0/gm.dy; a.fb_c = gm.c;
     a.seq = ++ion.seq;

@@ -213,6 +213,20 @@ __device__ __forceinline__ double ion_uniform (unsigned long long seed, unsigned
     return (double)(z >> 11)*(1.0/9007199254740992.0);
 }
 
+// counter-based generator of the collisions and of the warm plasma's momentum draws: chained two-round splitmix64 finaliser
+// (the construction of ion_uniform), one link per key
+__host__ __device__ inline unsigned long long coll_hash (unsigned long long h, unsigned long long v)
+{
+    unsigned long long z = h + 0x9E3779B97F4A7C15ULL*(v + 1);
+    for (int r = 0; r < 2; ++r) {
+        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ULL;
+        z ^= z >> 27; z *= 0x94D049BB133111EBULL;
+        z ^= z >> 31;
+    }
+    return z;
+}
+__device__ __forceinline__ double coll_unit (unsigned long long z) { return (double)(z >> 11)*(1.0/9007199254740992.0); }
+
 struct IonArgs {
     hps_plasma el;                       // product species: electrons are appended behind cnt[0] particles
     const double* adk;                   // [prefactor[Z] | exp_prefactor[Z] | power[Z] | field below which nothing can ionise[Z]]

@@ -9,6 +9,10 @@
 //     k >= ncoarse:                       i_part = ppc_x ppc_y + (k - ncoarse) / #cells,      cell = cells[(k - ncoarse) mod #cells]
 // The count is static: a slot beyond the radius, inside the hollow core or without density is an invalid slot, as in
 // k_init_plasma (engine.hip), which decks without these keys keep using.
+//
+// <plasma>.u_mean / u_std, do_symmetrize and prevent_centered_particle (:52-64, 173-177, 317-370, ParticleUtil.H:113-124;
+// DESIGN 8i) go through k_init_plasma_warm: the same slots with a Gaussian momentum from a counter-based draw, three mirror
+// copies of the whole sheet behind it, and the lattice moved by half a cell where the cell count and ppc are both odd.
 #include "engine.h"
 
 #include <algorithm>
@@ -26,12 +30,12 @@ struct FineInit {
     double radius_sq, hollow_sq;
 };
 
-__global__ __launch_bounds__(256)
-void k_init_plasma_fine (hps_plasma pl, long n, int nx, int ny, FineInit a, double lox, double loy, double dx, double dy,
-                         int level, int keyed, const double* __restrict__ prof, int nr, double ft)
+// Slot k of the sheet: its position, its weight and whether it holds a particle.  xoff, yoff: 0, or -0.5 in a direction
+// that prevent_centered_particle shifts (:52-64) -- there the cells are the nodes 1 .. n - 1, and index 0 owns no particle
+struct SlotInit { double x, y, w; bool live; };
+__device__ __forceinline__ SlotInit init_slot (long k, int nx, int ny, const FineInit& a, double lox, double loy, double dx, double dy,
+                                               const double* __restrict__ prof, int nr, double ft, double xoff = 0.0, double yoff = 0.0)
 {
-    const long k = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    if (k >= n) return;
     const long cells = (long)nx*ny;
     int ip, L = 0;
     long c;
@@ -60,23 +64,92 @@ void k_init_plasma_fine (hps_plasma pl, long n, int nx, int ny, FineInit a, doub
         rx = ((0.5 + ixc)/a.cx)*(1.0 - s) + ((0.5 + ixf)/a.fx)*s;
         ry = ((0.5 + iyc)/a.cy)*(1.0 - s) + ((0.5 + iyf)/a.fy)*s;
     }
-    const double x = lox + (i + rx)*dx;
-    const double y = loy + (j + ry)*dy;
+    const double x = lox + (i + rx + xoff)*dx;
+    const double y = loy + (j + ry + yoff)*dy;
     // <plasma>.radius, hollow_core_radius and the density (PlasmaParticleContainerInit.cpp:274-279)
     const double rsq = x*x + y*y;
-    const double fac = (rsq > a.radius_sq || rsq < a.hollow_sq) ? 0.0 : ft*table_value(prof, prof + nr, nr, sqrt(rsq));
+    double fac = (rsq > a.radius_sq || rsq < a.hollow_sq) ? 0.0 : ft*table_value(prof, prof + nr, nr, sqrt(rsq));
+    if ((xoff != 0.0 && i == 0) || (yoff != 0.0 && j == 0)) fac = 0.0;
     const double weight = L == 0 ? a.w_coarse : a.w_fine;      // (:289-294)
-    pl.x[k] = x; pl.y[k] = y; pl.w[k] = fac > 0.0 ? weight*fac : 0.0;
+    return {x, y, fac > 0.0 ? weight*fac : 0.0, fac > 0.0};
+}
+
+__global__ __launch_bounds__(256)
+void k_init_plasma_fine (hps_plasma pl, long n, int nx, int ny, FineInit a, double lox, double loy, double dx, double dy,
+                         int level, int keyed, const double* __restrict__ prof, int nr, double ft)
+{
+    const long k = (long)blockIdx.x*blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const SlotInit s = init_slot(k, nx, ny, a, lox, loy, dx, dy, prof, nr, ft);
+    const double x = s.x, y = s.y;
+    const bool live = s.live;
+    pl.x[k] = x; pl.y[k] = y; pl.w[k] = s.w;
     pl.ux[k] = 0.0; pl.uy[k] = 0.0; pl.psi[k] = 1.0;
     pl.x_prev[k] = x; pl.y_prev[k] = y;
-    pl.ux_half[k] = 0.0; pl.uy_half[k] = 0.0; pl.psi_half[k] = fac > 0.0 ? 1.0 : 0.0;
+    pl.ux_half[k] = 0.0; pl.uy_half[k] = 0.0; pl.psi_half[k] = live ? 1.0 : 0.0;
     // a keyed species carries its slot index + 1 in the id bits (k_init_plasma)
-    pl.idcpu[k] = (fac > 0.0 ? HPS_ID_VALID : 0ULL) | ((keyed ? (unsigned long long)(k + 1) : 1ULL) << 24);
+    pl.idcpu[k] = (live ? HPS_ID_VALID : 0ULL) | ((keyed ? (unsigned long long)(k + 1) : 1ULL) << 24);
     pl.ion_lev[k] = level;
 }
 
-int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
-                      double radius_sq)
+// <plasma>.u_mean, u_std: u = u_mean + u_std n with three standard normal deviates per primary slot k (ParticleUtil.H:113-124).
+// Every draw is a function of (seed, species, time step, slot, draw) -- `key` is the chain up to the step -- so the sheet
+// does not depend on the launch: Box-Muller on draws (0, 1) gives n_x, n_y, its cosine branch on draws (2, 3) n_z.
+// do_symmetrize (:317-370): the primary slots are [0, nq), copy m = 1, 2, 3 of slot k is slot k + m nq at the position
+// mirrored in x, in y, in both, with the momentum mirrored likewise; the weights arrive divided by 4 (:173-177).
+struct WarmInit {
+    double u_mean[3], u_std[3], c; unsigned long long key;
+    double xoff, yoff, x_mid2, y_mid2;
+};
+
+__device__ __forceinline__ void normal_pair (unsigned long long zk, unsigned draw, double& nc, double& ns)
+{
+    const double u1 = 1.0 - coll_unit(coll_hash(zk, draw)), u2 = coll_unit(coll_hash(zk, draw + 1));      // u1 in (0, 1]
+    const double r = sqrt(-2.0*log(u1));
+    sincos(2.0*M_PI*u2, &ns, &nc);
+    nc *= r; ns *= r;
+}
+
+template <bool SYM>
+__global__ __launch_bounds__(256)
+void k_init_plasma_warm (hps_plasma pl, long nq, int nx, int ny, FineInit a, WarmInit t, double lox, double loy, double dx, double dy,
+                         int level, int keyed, const double* __restrict__ prof, int nr, double ft)
+{
+    const long k = (long)blockIdx.x*blockDim.x + threadIdx.x;
+    if (k >= nq) return;
+    const SlotInit s = init_slot(k, nx, ny, a, lox, loy, dx, dy, prof, nr, ft, t.xoff, t.yoff);
+    const bool live = s.live;
+    const unsigned long long zk = coll_hash(t.key, (unsigned long long)k);
+    double u[3] = {t.u_mean[0], t.u_mean[1], t.u_mean[2]};
+    if (t.u_std[0] != 0.0 || t.u_std[1] != 0.0) {
+        double n0, n1;
+        normal_pair(zk, 0u, n0, n1);
+        if (t.u_std[0] != 0.0) u[0] += t.u_std[0]*n0;
+        if (t.u_std[1] != 0.0) u[1] += t.u_std[1]*n1;
+    }
+    if (t.u_std[2] != 0.0) {
+        double n2, unused;
+        normal_pair(zk, 2u, n2, unused);
+        u[2] += t.u_std[2]*n2;
+    }
+    const double ux = u[0]*t.c, uy = u[1]*t.c;
+    const double psi = sqrt(1.0 + u[0]*u[0] + u[1]*u[1] + u[2]*u[2]) - u[2];      // (:298) > 0 always
+#pragma unroll
+    for (int m = 0; m < (SYM ? 4 : 1); ++m) {
+        const long o = k + m*nq;
+        const double x = (m & 1) ? t.x_mid2 - s.x : s.x, y = (m & 2) ? t.y_mid2 - s.y : s.y;
+        const double mux = (m & 1) ? -ux : ux, muy = (m & 2) ? -uy : uy;
+        pl.x[o] = x; pl.y[o] = y; pl.w[o] = s.w;
+        pl.ux[o] = mux; pl.uy[o] = muy; pl.psi[o] = psi;
+        pl.x_prev[o] = x; pl.y_prev[o] = y;
+        pl.ux_half[o] = mux; pl.uy_half[o] = muy; pl.psi_half[o] = live ? psi : 0.0;
+        pl.idcpu[o] = (live ? HPS_ID_VALID : 0ULL) | ((keyed ? (unsigned long long)(o + 1) : 1ULL) << 24);
+        pl.ion_lev[o] = level;
+    }
+}
+
+// the kernels' view of one species' patch and weights; wdiv = 4 with do_symmetrize (:173-177)
+static FineInit fine_args (const Engine& E, const int ppc[2], const int fine[2], double density, double radius_sq, double wdiv)
 {
     const hps_deck& d = E.d;
     const bool patch = E.fine_patch_set && fine[0] > 0;
@@ -89,16 +162,54 @@ int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], 
     a.T = E.fine_T;
     a.ncoarse = (long)a.cx*a.cy*d.nx*d.ny;
     const double vol = d.si_units ? E.gm.dx*E.gm.dy*E.gm.dz : 1.0;
-    a.w_coarse = density*(vol/(a.cx*a.cy));
-    a.w_fine = density*(vol/(a.fx*a.fy));
+    a.w_coarse = density*(vol/(a.cx*a.cy))/wdiv;
+    a.w_fine = density*(vol/(a.fx*a.fy))/wdiv;
     a.radius_sq = radius_sq;
     a.hollow_sq = E.hollow_core_radius*E.hollow_core_radius;
+    return a;
+}
+
+int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
+                      double radius_sq)
+{
+    const hps_deck& d = E.d;
+    const FineInit a = fine_args(E, ppc, fine, density, radius_sq, 1.0);
     if (n != a.ncoarse + (long)(a.fx*a.fy - a.cx*a.cy)*a.ncells) { set_error("init_plasma_fine: the sheet does not have the patch's slot count"); return HPS_ERR_ARG; }
     hipLaunchKernelGGL(k_init_plasma_fine, dim3(ceil_div(n, 256)), dim3(256), 0, E.st, p, n, d.nx, d.ny, a, d.lo[0], d.lo[1],
                        E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft);
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
+
+int init_plasma_warm (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
+                      double radius_sq, int species)
+{
+    const hps_deck& d = E.d;
+    const bool sym = E.do_symmetrize;
+    const FineInit a = fine_args(E, ppc, fine, density, radius_sq, sym ? 4.0 : 1.0);
+    const long nq = a.ncoarse + (long)(a.fx*a.fy - a.cx*a.cy)*a.ncells;
+    if (n != (sym ? 4 : 1)*nq) { set_error("init_plasma_warm: the sheet does not have the slot count of its keys"); return HPS_ERR_ARG; }
+    const Engine::Thermal& th = E.thermal[species];
+    WarmInit t{};
+    for (int q = 0; q < 3; ++q) { t.u_mean[q] = th.u_mean[q]; t.u_std[q] = th.u_std[q]; }
+    t.c = E.gm.c;
+    t.key = coll_hash(coll_hash(th.seed, (unsigned long long)species), (unsigned long long)E.step_index);
+    t.xoff = E.shifted(ppc, 0) ? -0.5 : 0.0;
+    t.yoff = E.shifted(ppc, 1) ? -0.5 : 0.0;
+    t.x_mid2 = d.lo[0] + d.hi[0]; t.y_mid2 = d.lo[1] + d.hi[1];       // of the particle boundary box (:319-320)
+    const dim3 grid(ceil_div(nq, 256)), block(256);
+    if (sym)
+        hipLaunchKernelGGL(k_init_plasma_warm<true>, grid, block, 0, E.st, p, nq, d.nx, d.ny, a, t, d.lo[0], d.lo[1], E.gm.dx, E.gm.dy,
+                           level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft);
+    else
+        hipLaunchKernelGGL(k_init_plasma_warm<false>, grid, block, 0, E.st, p, nq, d.nx, d.ny, a, t, d.lo[0], d.lo[1], E.gm.dx, E.gm.dy,
+                           level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft);
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
+// (PlasmaParticleContainerInit.cpp:52-64: with the fine patch the level map would have to live on the shifted box)
+static const char* const PREVENT_VS_PATCH = "prevent_centered_particle cannot be combined with the fine plasma patch (fine_ppc, fine_patch)";
 
 static bool divisible (const int* fine, const int* ppc)
 {
@@ -115,6 +226,7 @@ int Engine::set_plasma_init (const int* plasma_fine, const int* ion_fine, double
     // (PlasmaParticleContainer.cpp:158-163)
     HPS_REQUIRE(!p_on || (d.plasma_density > 0.0 && divisible(pf, d.plasma_ppc)), "hps_engine_set_plasma_init: plasma fine_ppc must be positive and divisible by ppc, component by component");
     HPS_REQUIRE(!i_on || (d.ion_on && divisible(jf, d.ion_ppc)), "hps_engine_set_plasma_init: ion fine_ppc needs the ion species and must be positive and divisible by its ppc, component by component");
+    HPS_REQUIRE(!(prevent_centered && (p_on || i_on)), PREVENT_VS_PATCH);
     // (:126-128; radius 0 = infinite)
     HPS_REQUIRE(hollow_core >= 0.0 && (d.plasma_radius <= 0.0 || hollow_core < d.plasma_radius),
                 "hps_engine_set_plasma_init: the hollow core radius must not be negative and must be smaller than the plasma radius");
@@ -124,10 +236,34 @@ int Engine::set_plasma_init (const int* plasma_fine, const int* ion_fine, double
     return alloc_sheets();
 }
 
+int Engine::set_plasma_momentum (int species, const double* u_mean, const double* u_std, unsigned long long seed)
+{
+    HPS_REQUIRE(!step_begun && !tiling, "hps_engine_set_plasma_momentum: call before the first hps_engine_begin_step");
+    HPS_REQUIRE(species == 0 || species == 1, "hps_engine_set_plasma_momentum: species must be 0 (plasma) or 1 (ion)");
+    HPS_REQUIRE(species == 0 ? d.plasma_density > 0.0 : d.ion_on != 0, "hps_engine_set_plasma_momentum: the deck does not have this species (no plasma, or no ion species)");
+    HPS_REQUIRE(u_mean && u_std, "hps_engine_set_plasma_momentum: null argument");
+    for (int q = 0; q < 3; ++q)
+        HPS_REQUIRE(std::isfinite(u_mean[q]) && std::isfinite(u_std[q]) && u_std[q] >= 0.0, "hps_engine_set_plasma_momentum: u_std must not be negative (and u_mean, u_std finite)");
+    Thermal& th = thermal[species];
+    for (int q = 0; q < 3; ++q) { th.u_mean[q] = u_mean[q]; th.u_std[q] = u_std[q]; }
+    th.seed = seed;
+    return HPS_OK;
+}
+
+int Engine::set_plasma_symmetry (int symmetrize, int prevent_centered_particle)
+{
+    HPS_REQUIRE(!step_begun && !tiling, "hps_engine_set_plasma_symmetry: call before the first hps_engine_begin_step");
+    HPS_REQUIRE(!(prevent_centered_particle && (fine_patch_set || fine_ppc[0] > 0 || ion_fine_ppc[0] > 0)), PREVENT_VS_PATCH);
+    do_symmetrize = symmetrize != 0; prevent_centered = prevent_centered_particle != 0;
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    return alloc_sheets();
+}
+
 int Engine::set_fine_patch (const unsigned char* mask_host, int transition_cells)
 {
     HPS_REQUIRE(!step_begun && !tiling, "hps_engine_set_fine_patch: call before the first hps_engine_begin_step");
     HPS_REQUIRE(mask_host, "hps_engine_set_fine_patch: null mask");
+    HPS_REQUIRE(!prevent_centered, PREVENT_VS_PATCH);
     HPS_REQUIRE(transition_cells >= 0, "hps_engine_set_fine_patch: fine_transition_cells must not be negative");
     const int nx = d.nx, ny = d.ny, T = transition_cells;
     // the map lives on the cell box cropped to the plasma radius (:70-82); nothing outside it is looked at

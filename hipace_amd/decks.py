@@ -84,6 +84,30 @@ SALAME_DEFAULT = dict(beam_do_salame=0, salame_n_iter=0, salame_relative_toleran
 # of SliceEngine; a deck may carry them as "fine_patch" (a callable f(x, y) or a (ny, nx) mask) and "fine_transition_cells".
 PLASMA_INIT_DEFAULT = dict(plasma_fine_ppc=(0, 0), ion_fine_ppc=(0, 0), plasma_hollow_core_radius=0.0)
 
+# Warm plasmas: <plasma>.u_mean, u_std, temperature_in_ev of the species "plasma" and "ion", plasmas.do_symmetrize and
+# prevent_centered_particle (PlasmaParticleContainer.cpp:125-145, 170).  Kept apart from _DEFAULT like PLASMA_INIT_DEFAULT and
+# applied by SliceEngine through hps_engine_set_plasma_momentum / hps_engine_set_plasma_symmetry; None / 0 = not given.
+# u_mean and u_std are three numbers in units of c (the input parser is out of scope); a temperature stands for an isotropic
+# u_std (thermal_u_std) and excludes u_std; plasma_seed is the seed of both species' momentum draws.
+PLASMA_THERMAL_DEFAULT = dict(plasma_u_mean=(0.0, 0.0, 0.0), plasma_u_std=None, plasma_temperature_in_ev=None,
+                              ion_u_mean=(0.0, 0.0, 0.0), ion_u_std=None, ion_temperature_in_ev=None, plasma_seed=0,
+                              plasmas_do_symmetrize=0, plasmas_prevent_centered_particle=0)
+
+
+def thermal_u_std(deck, species="plasma"):
+    """u_std of species "plasma" / "ion" from the deck's <species>_u_std or <species>_temperature_in_ev:
+    u_std = sqrt(T q_e / (M c^2)) in every direction with the species' mass M in kg (PlasmaParticleContainer.cpp:138-145; a
+    normalised deck's masses are in electron masses).  Both given: ValueError, as the reference asserts."""
+    u_std, T = deck.get(species + "_u_std"), deck.get(species + "_temperature_in_ev")
+    if u_std is not None and T is not None:
+        raise ValueError(f"{species}: please specify exclusively either a temperature or the thermal momentum")
+    if T is None:
+        return tuple(float(v) for v in (u_std if u_std is not None else (0.0, 0.0, 0.0)))
+    q_e_SI, m_e_SI, c_SI = 1.602176634e-19, 9.1093837015e-31, 299792458.0
+    mass = float(deck[species + "_mass"]) * (1.0 if deck.get("si_units", 0) else m_e_SI)
+    return (((float(T) * q_e_SI) / (mass * c_SI * c_SI)) ** 0.5,) * 3
+
+
 # Ionisation energies in eV of a few elements: NIST Atomic Spectra Database (Kramida, Ralchenko, Reader and NIST ASD
 # Team, ver. 5.2), the values the reference tabulates in utils/IonizationEnergiesTable.H.
 IONIZATION_ENERGIES_EV = {
@@ -140,6 +164,17 @@ def blowout_wake_fine_patch(radius=2.0, transition_cells=2):
     d = blowout_wake()
     d.update(PLASMA_INIT_DEFAULT)
     d.update(plasma_ppc=(1, 1), plasma_fine_ppc=(4, 4), fine_patch=fine_patch_disc(radius), fine_transition_cells=transition_cells)
+    return d
+
+
+def blowout_wake_warm(temperature_in_ev=50.0, do_symmetrize=True, seed=1, ppc=(1, 1)):
+    """The 64 x 64 blowout deck with a warm plasma: <plasma>.temperature_in_ev, and plasmas.do_symmetrize (four mirrored
+    copies of every particle, so that the thermal noise does not seed hosing: the reference recommends it with a temperature)."""
+    d = blowout_wake()
+    d.update(PLASMA_INIT_DEFAULT)
+    d.update(PLASMA_THERMAL_DEFAULT)
+    d.update(plasma_ppc=tuple(ppc), plasma_temperature_in_ev=float(temperature_in_ev), plasma_seed=int(seed),
+             plasmas_do_symmetrize=int(bool(do_symmetrize)))
     return d
 
 

@@ -500,9 +500,33 @@ int hps_engine_set_density_profile (void* handle, int nr, const double* r_host, 
  * or >= plasma_radius (:126-128); transition_cells < 0; a call after the first hps_engine_begin_step.  Exactly one of
  * fine_ppc and the patch given (:167-169): HPS_ERR_ARG from the first hps_engine_begin_step.  Every engine mode takes the
  * non-uniform sheet, the fused schedule (hps_engine_set_fusion) included.  Decks without these calls run k_init_plasma as
- * before, bit for bit.  Not restated: prevent_centered_particle, do_symmetrize, temperature_in_ev / u_std. */
+ * before, bit for bit.  prevent_centered_particle, do_symmetrize and u_mean / u_std: the two setters below.  Not restated:
+ * prevent_centered_particle together with the fine patch (HPS_ERR_ARG from whichever call comes second). */
 int hps_engine_set_plasma_init (void* handle, const int* plasma_fine_ppc, const int* ion_fine_ppc, double hollow_core_radius);
 int hps_engine_set_fine_patch (void* handle, const unsigned char* mask_host, int transition_cells);
+/* Warm plasmas (InitParticles, PlasmaParticleContainerInit.cpp:52-64, 173-177, 246-313, 317-370; get_gaussian_random_momentum,
+ * ParticleUtil.H:113-124).  Not members of hps_deck either; all zero = off: such a deck launches the kernels it launched before.
+ *   hps_engine_set_plasma_momentum: <plasma>.u_mean and u_std ([3] each, in units of c) of species 0 (plasma) or 1 (ion).  Every
+ *     slot starts with u = u_mean + u_std n, n three standard normal deviates: ux = u_x c, uy = u_y c, psi = sqrt(1 + u.u) - u_z,
+ *     the half-step copies equal.  The deviates are counter based: with z(draw) = hash(hash(hash(hash(seed, species), step),
+ *     slot), draw) (the generator of the collisions) Box-Muller on draws (0, 1) gives n_x, n_y and its cosine branch on draws
+ *     (2, 3) n_z; `step` is the engine's step index (hps_engine_set_step), so every step's re-injection draws anew, and the sheet
+ *     does not depend on the launch or on the tiling.  A component with u_std = 0 is exactly u_mean.  temperature_in_ev is the
+ *     caller's conversion to u_std = sqrt(T q_e / (M c^2)) (PlasmaParticleContainer.cpp:138-145).  The predictor-corrector
+ *     iterates from the first slice on, and an ionisable species with momentum takes no neutral-tile skip: its atoms move.
+ *   hps_engine_set_plasma_symmetry, one value for both species:
+ *     do_symmetrize: the slots [0, n/4) are the sheet as it is without the key, the fine patch included, with a quarter of the
+ *     weight; copy m = 1, 2, 3 of slot k is slot k + m n/4 at (x_mid2 - x, y), (x, y_mid2 - y), (x_mid2 - x, y_mid2 - y) with
+ *     the signs (-,+), (+,-), (-,-) on (ux, uy); x_mid2 = lo + hi.  The copy of an invalid slot is invalid.  hps_engine_info,
+ *     the sheet arrays and the tiling capacity follow the four-fold count.
+ *     prevent_centered_particle: in a direction whose cell count and ppc are both odd the lattice moves by half a cell onto the
+ *     nodes 1 .. n - 1, x = lo + (i + r - 0.5) dx; the slot count stays ppc nx ny, the slots of index 0 are invalid ones.
+ * Both: after hps_engine_create and before the first hps_engine_begin_step, in any order relative to each other and to
+ * hps_engine_set_tiling, hps_engine_set_plasma_init and hps_engine_set_fine_patch.  HPS_ERR_ARG: a negative u_std; species 1
+ * without the ion species (species 0 without a plasma); prevent_centered_particle together with fine_ppc or the patch; a call
+ * after the first hps_engine_begin_step.  Not restated: fields.do_symmetrize; per-species symmetry switches. */
+int hps_engine_set_plasma_momentum (void* handle, int species, const double u_mean[3], const double u_std[3], unsigned long long seed);
+int hps_engine_set_plasma_symmetry (void* handle, int do_symmetrize, int prevent_centered_particle);
 /* Fused schedule: the gather + push of slice k also deposits the pushed particles' currents into slice k-1 (one pass over
  * the sheet instead of two; the slab is shifted / cleared before it).  After hps_engine_solve_slice(k) the components jx,
  * jy, chi, rhomjz [, rho] then already belong to slice k-1; everything else, the per-slice checksums and diagnostics are
