@@ -192,6 +192,13 @@ _SIGS = {
     "hps_engine_import_laser_from": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "hps_engine_laser_envelope": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hps_engine_laser_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "hps_engine_set_laser_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
+    "hps_engine_laser_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hps_engine_laser_chi": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hps_laser_interp_aabs": (C.c_int, [Slab, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                        Geom, C.c_int, C.c_void_p]),
+    "hps_laser_interp_chi": (C.c_int, [Slab, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                       C.c_double, Geom, C.c_int, C.c_int, C.c_void_p]),
     "hps_deposit_current_laser": (C.c_int, [Slab, Plasma, Geom, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double,
                                             C.c_int, C.c_void_p, C.c_void_p]),
     "hps_explicit_deposit_laser": (C.c_int, [Slab, Plasma, Geom, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_int,

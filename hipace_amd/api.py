@@ -292,6 +292,37 @@ def recorded_particle_dispatch():
     return set(buf.value.decode().split())
 
 
+class LaserInterp:
+    """The two grid-to-grid interpolations of a laser envelope on a grid of its own (lasers.n_cell / patch_lo / patch_hi /
+    interp_order) as operators: UpdateLaserAabs (laser/MultiLaser.cpp:253-284) and InterpolateChi (:334-407).  The laser grid
+    is n_cell = (nxl, nyl) cells on patch_lo .. patch_hi (x, y); geom is the field slab's Geometry."""
+
+    def __init__(self, n_cell, patch_lo, patch_hi, order=1):
+        self.nxl, self.nyl = int(n_cell[0]), int(n_cell[1])
+        self.dxl, self.dyl = (patch_hi[0] - patch_lo[0]) / self.nxl, (patch_hi[1] - patch_lo[1]) / self.nyl
+        self.xoffl = 0.5 * (patch_lo[0] + patch_hi[0] - self.dxl * (self.nxl - 1))      # GetPosOffset of the laser box
+        self.yoffl = 0.5 * (patch_lo[1] + patch_hi[1] - self.dyl * (self.nyl - 1))
+        self.order = int(order)
+
+    def _plane(self, t, dtype):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and tuple(t.shape) == (self.nyl, self.nxl)
+        return C.c_void_p(t.data_ptr())
+
+    def aabs(self, fields, geom, aabs_comp, a):
+        """slab component aabs_comp (guard cells included) <- |a|^2 of the complex128 device tensor a (nyl, nxl)"""
+        check(_lib.lib().hps_laser_interp_aabs(fields.struct(), int(aabs_comp), self._plane(a, torch.complex128), self.nxl, self.nyl,
+                                               self.dxl, self.dyl, self.xoffl, self.yoffl, geom.c, self.order, _stream()))
+
+    def chi(self, fields, geom, chi_comp, chi_initial, shrink=None):
+        """-> float64 device tensor (nyl, nxl): slab component chi_comp interpolated on the laser cells that lie on the field box
+        shrunk by `shrink` cells (default: the slab's guard width, as the engine), chi_initial (nyl, nxl) elsewhere"""
+        out = torch.empty((self.nyl, self.nxl), dtype=torch.float64, device=chi_initial.device)
+        check(_lib.lib().hps_laser_interp_chi(fields.struct(), int(chi_comp), self._plane(chi_initial, torch.float64),
+                                              C.c_void_p(out.data_ptr()), self.nxl, self.nyl, self.dxl, self.dyl, self.xoffl, self.yoffl,
+                                              geom.c, fields.ng if shrink is None else int(shrink), self.order, _stream()))
+        return out
+
+
 class FFTPoissonSolver:
     """Lap(F) = S, F = 0 one cell outside the box; S lives in the staging area."""
 
@@ -497,6 +528,10 @@ class SliceEngine:
         sym, prevent = deck.get("plasmas_do_symmetrize", 0), deck.get("plasmas_prevent_centered_particle", 0)
         if sym or prevent:
             self.set_plasma_symmetry(sym, prevent)
+        # lasers.n_cell / patch_lo / patch_hi / interp_order (decks.LASER_GRID_DEFAULT): a deck without these keys makes no call
+        if _decks.has_laser_grid(deck):
+            self.set_laser_grid(deck.get("laser_n_cell"), deck.get("laser_patch_lo"), deck.get("laser_patch_hi"),
+                                deck.get("laser_interp_order", 1))
         if fine_patch is None:
             fine_patch = deck.get("fine_patch")
         if fine_patch is not None:
@@ -578,6 +613,27 @@ class SliceEngine:
         npart = C.c_long()
         check(_lib.lib().hps_engine_info(self._h, None, None, C.byref(npart)))
         self.nparticles = npart.value
+
+    def set_laser_grid(self, n_cell=None, patch_lo=None, patch_hi=None, interp_order=1):
+        """lasers.n_cell (2), patch_lo, patch_hi (3 each; None: the field grid's) and interp_order: the envelope on a grid of its
+        own (hps_engine_set_laser_grid, decks.laser_geometry), before the first begin_step."""
+        n = (C.c_int * 2)(*[int(v) for v in n_cell]) if n_cell is not None else None
+        lo = (C.c_double * 3)(*[float(v) for v in patch_lo]) if patch_lo is not None else None
+        hi = (C.c_double * 3)(*[float(v) for v in patch_hi]) if patch_hi is not None else None
+        check(_lib.lib().hps_engine_set_laser_grid(self._h, n, lo, hi, int(1 if interp_order is None else interp_order)))
+
+    def laser_grid(self):
+        """(nxl, nyl, zeta_lo, zeta_hi) as the engine holds them; without set_laser_grid (nx, ny, 0, nz - 1)"""
+        v = [C.c_int() for _ in range(4)]
+        check(_lib.lib().hps_engine_laser_grid(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def laser_chi(self):
+        """chi on the laser grid as the last envelope advance read it: (nyl, nxl); needs set_laser_grid and an evolving envelope"""
+        nxl, nyl, _, _ = self.laser_grid()
+        out = np.empty((nyl, nxl), dtype=np.float64)
+        check(_lib.lib().hps_engine_laser_chi(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def add_collision(self, species_a=0, species_b=0, coulomb_log=-1.0, seed=0):
         """hipace.collisions: one more Coulomb collision between species 0 (plasma) / 1 (ion), before the first begin_step
@@ -857,7 +913,8 @@ class SliceEngine:
         return bool(self.deck.get("laser_on", 0))
 
     def laser_message_doubles(self):
-        return 4 * self.deck["nx"] * self.deck["ny"]
+        nxl, nyl, _, _ = self.laser_grid()
+        return 4 * nxl * nyl
 
     def set_step(self, step):
         """physical time step of the next begin_step (pipeline stages run steps r, r + N, ...)"""
@@ -876,9 +933,9 @@ class SliceEngine:
         check(_lib.lib().hps_engine_import_laser_from(self._h, islice, src._h))
 
     def laser_envelope(self):
-        """a_n of the step that has begun: complex array [nz, ny, nx]."""
-        d = self.deck
-        out = np.empty((d["nz"], d["ny"], d["nx"]), dtype=np.complex128)
+        """a_n of the step that has begun: complex array [nz, ny, nx]; with a laser grid [zeta_hi - zeta_lo + 1, nyl, nxl]."""
+        nxl, nyl, zlo, zhi = self.laser_grid()
+        out = np.empty((zhi - zlo + 1, nyl, nxl), dtype=np.complex128)
         check(_lib.lib().hps_engine_laser_envelope(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 

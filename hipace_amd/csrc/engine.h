@@ -177,6 +177,13 @@ struct Engine {
     double pc_tol = 4e-2, pc_mix = 0.05; int pc_max_iter = 30;
     int c_aabs = -1; double* d_laser_sum = nullptr;       // laser: slab component of |a|^2, device sum of |a| (diagnostics)
     LaserState* laser = nullptr;                          // envelope arrays + solver (laser.hip)
+    // lasers.n_cell / patch_lo / patch_hi / interp_order (hps_engine_set_laser_grid): the envelope on a grid of its
+    // own -- nx x ny cells on the patch lo .. hi (z snapped to the field slices zlo .. zhi), GetPosOffset xoff, yoff of that
+    // box.  Not set: the envelope lives on the field grid and chi, |a|^2 pass cell by cell.
+    struct LaserGrid { bool set = false; int nx = 0, ny = 0, zlo = 0, zhi = -1, order = 1;
+                       double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, dx = 0.0, dy = 0.0, xoff = 0.0, yoff = 0.0; } lgrid;
+    int set_laser_grid (const int* n_cell, const double* patch_lo, const double* patch_hi, int interp_order);
+    bool laser_has_slice (int islice) const { return !lgrid.set || (islice >= lgrid.zlo && islice <= lgrid.zhi); }      // UseLaser(islice)
     // The envelope's advance of a slice needs chi of the slice and the envelope of the slices before it -- nothing else
     // of the slice needs its result.  It runs on a stream of its own beside the explicit deposition, the Bx/By multigrid
     // and the push (HPS_LASER_ASYNC=0: on the engine's stream, in the reference's place, Hipace.cpp:637).
@@ -252,6 +259,9 @@ int laser_begin_step (Engine& E);
 int laser_update_aabs (Engine& E, int islice, double* sum_abs);
 int laser_advance_slice (Engine& E, int islice);
 int laser_copy_envelope (Engine& E, double* out_host);
+int laser_chi_initial (Engine& E);                                           // SetInitialChi, once per step (laser grid only)
+int laser_copy_chi (Engine& E, double* out_host);
+void laser_sizes (Engine& E, int* nx, int* ny, int* nz);
 long laser_mg_vcycles (Engine& E);
 int laser_set_import (Engine& E, int on, int step);
 int laser_export_slice (Engine& E, int islice, double* msg_dev);

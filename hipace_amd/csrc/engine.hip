@@ -957,6 +957,7 @@ int Engine::begin_step ()
         step_dt = d.dt;
         prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*d.dt*step_index);
     }
+    if (laser && lgrid.set) { if (int e = laser_chi_initial(*this)) return e; }      // SetInitialChi: density(x, y, c t) of this step
     if (int e = ionize_collect()) return e;
     np = np_init; pl.n = np; pl_alt.n = np;
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : std::numeric_limits<double>::infinity();
@@ -1931,7 +1932,7 @@ int Engine::solve_slice_begin (int islice)
     // dopant; stream priority makes no difference).  Multigrid solver (0.7 ms, latency-bound, holds the host once per
     // V-cycle): enqueued further down, when the engine's stream has the explicit deposition and the Bx/By V-cycles
     // queued (545 -> 706 slices/s).
-    const bool laser_now = c_aabs >= 0 && d.laser_solver >= 1 && d.dt != 0.0;
+    const bool laser_now = c_aabs >= 0 && d.laser_solver >= 1 && d.dt != 0.0 && laser_has_slice(islice);      // UseLaser(islice)
     const bool laser_split = laser_now && laser_stream() != st;
     if (laser_now && !laser_split) { if ((e = laser_advance_slice(*this, islice))) return e; }
     if (laser_split) { if ((e = fork_laser())) return e; }
@@ -2559,6 +2560,9 @@ extern "C" int hps_engine_import_laser_from (void* h, int islice, void* src)
     Engine* E = static_cast<Engine*>(h); Engine* S = static_cast<Engine*>(src);
     HPS_REQUIRE(E->laser && S && S->laser && islice >= 0 && islice < E->d.nz && S->d.nx == E->d.nx && S->d.ny == E->d.ny && S->d.nz == E->d.nz,
                 "hps_engine_import_laser_from: bad argument");
+    {   const Engine::LaserGrid &a = E->lgrid, &b = S->lgrid;
+        HPS_REQUIRE(a.set == b.set && (!a.set || (a.nx == b.nx && a.ny == b.ny && a.zlo == b.zlo && a.zhi == b.zhi)),
+                    "hps_engine_import_laser_from: the two engines' laser grids differ"); }
     return laser_import_from(*E, islice, *S);
 }
 extern "C" int hps_engine_laser_envelope (void* h, double* out_host)
@@ -2566,6 +2570,58 @@ extern "C" int hps_engine_laser_envelope (void* h, double* out_host)
     Engine* E = static_cast<Engine*>(h);
     HPS_REQUIRE(E->laser && out_host, "hps_engine_laser_envelope: no laser");
     return laser_copy_envelope(*E, out_host);
+}
+// MultiLaser::MakeLaserGeometry (laser/MultiLaser.cpp:58-115): the field grid and box unless given; zeta snapped to whole field
+// cells, so that laser slice k sits at the z of field slice k
+int Engine::set_laser_grid (const int* n_cell, const double* patch_lo, const double* patch_hi, int interp_order)
+{
+    HPS_REQUIRE(laser, "hps_engine_set_laser_grid: the deck has no laser (laser_on)");
+    HPS_REQUIRE(!step_begun, "hps_engine_set_laser_grid: must be called before the first hps_engine_begin_step");
+    HPS_REQUIRE(interp_order >= 0 && interp_order <= 3, "hps_engine_set_laser_grid: lasers.interp_order must be 0, 1, 2 or 3");
+    LaserGrid G;
+    G.set = true; G.order = interp_order;
+    G.nx = n_cell ? n_cell[0] : d.nx; G.ny = n_cell ? n_cell[1] : d.ny;
+    for (int q = 0; q < 3; ++q) { G.lo[q] = patch_lo ? patch_lo[q] : d.lo[q]; G.hi[q] = patch_hi ? patch_hi[q] : d.hi[q]; }
+    HPS_REQUIRE(G.nx >= 1 && G.ny >= 1, "hps_engine_set_laser_grid: lasers.n_cell must be positive");
+    for (int q = 0; q < 3; ++q) HPS_REQUIRE(std::isfinite(G.lo[q]) && std::isfinite(G.hi[q]), "hps_engine_set_laser_grid: lasers.patch_lo / patch_hi must be finite");
+    const double poff_z = 0.5*(d.lo[2] + d.hi[2] - gm.dz*(d.nz - 1)), dz_inv = 1.0/gm.dz;
+    const double zl = std::max(0.0, std::round((G.lo[2] - poff_z)*dz_inv)), zh = std::min((double)(d.nz - 1), std::round((G.hi[2] - poff_z)*dz_inv));
+    HPS_REQUIRE(zl <= zh, "hps_engine_set_laser_grid: the laser patch holds no field slice (empty zeta range)");
+    G.zlo = (int)zl; G.zhi = (int)zh;
+    G.lo[2] = (G.zlo - 0.5)*gm.dz + poff_z; G.hi[2] = (G.zhi + 0.5)*gm.dz + poff_z;
+    HPS_REQUIRE(G.hi[0] > G.lo[0] && G.hi[1] > G.lo[1] && G.hi[2] > G.lo[2], "hps_engine_set_laser_grid: Laser box must have positive volume");
+    G.dx = (G.hi[0] - G.lo[0])/G.nx; G.dy = (G.hi[1] - G.lo[1])/G.ny;
+    G.xoff = 0.5*(G.lo[0] + G.hi[0] - G.dx*(G.nx - 1));
+    G.yoff = 0.5*(G.lo[1] + G.hi[1] - G.dy*(G.ny - 1));
+    if (d.laser_solver == 2 && d.dt != 0.0 && (G.nx % 2 || G.ny % 2)) {
+        set_error("hps_engine_set_laser_grid: the multigrid envelope solver needs even lasers.n_cell (cell-centred hpmg box)"); return HPS_ERR_UNSUPPORTED; }
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    laser_destroy(*this);
+    lgrid = G;
+    return laser_create(*this);
+}
+extern "C" int hps_engine_set_laser_grid (void* h, const int* n_cell, const double* patch_lo, const double* patch_hi, int interp_order)
+{
+    HPS_REQUIRE(h, "hps_engine_set_laser_grid: null handle");
+    return static_cast<Engine*>(h)->set_laser_grid(n_cell, patch_lo, patch_hi, interp_order);
+}
+extern "C" int hps_engine_laser_grid (void* h, int* nxl, int* nyl, int* zeta_lo, int* zeta_hi)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_laser_grid: no laser");
+    int nx = 0, ny = 0, nz = 0;
+    laser_sizes(*E, &nx, &ny, &nz);
+    if (nxl) *nxl = nx;
+    if (nyl) *nyl = ny;
+    if (zeta_lo) *zeta_lo = E->lgrid.set ? E->lgrid.zlo : 0;
+    if (zeta_hi) *zeta_hi = E->lgrid.set ? E->lgrid.zhi : E->d.nz - 1;
+    return HPS_OK;
+}
+extern "C" int hps_engine_laser_chi (void* h, double* out_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser && out_host, "hps_engine_laser_chi: no laser");
+    return laser_copy_chi(*E, out_host);
 }
 extern "C" int hps_engine_laser_info (void* h, int* aabs_comp, double* sum_host)
 {

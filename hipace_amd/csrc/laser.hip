@@ -8,12 +8,16 @@
 //
 // Layout: three complex arrays [nz][ny][nx] (a at time steps n-1, n, n+1), 16 B per cell, resident in HBM for the whole
 // run -- 1024^2 x 2048 slices are 3 x 34 GB, which is what 288 GB per GPU are for; the reference streams them through
-// host buffers.  The laser grid is the field grid (lasers.n_cell / patch_* not given), lasers.interp_order = 1, so chi
-// and |a|^2 pass between the two grids cell by cell.
+// host buffers.  Without lasers.n_cell / patch_* the laser grid is the field grid and lasers.interp_order = 1, so chi
+// and |a|^2 pass between the two grids cell by cell.  With them (hps_engine_set_laser_grid) the arrays are
+// [zeta_hi - zeta_lo + 1][nyl][nxl] on the laser's patch and two interpolation kernels carry |a|^2 to the field grid
+// (UpdateLaserAabs :253-284) and chi to the laser grid (SetInitialChi :293-332, InterpolateChi :334-407).
 #include "common.h"
 #include "engine.h"
 
 #include <rocfft/rocfft.h>
+#include <algorithm>
+#include <cmath>
 
 namespace hps {
 
@@ -25,7 +29,11 @@ int mg2_solve_internal (void* h, double* sol, const double* rhs, const double* a
 void mg2_destroy_internal (void* h);
 
 struct LaserState {
-    int nx = 0, ny = 0, nz = 0;
+    int nx = 0, ny = 0, nz = 0;                                    // cells of the laser grid (the field grid's unless a grid is set)
+    int zlo = 0;                                                   // field slice of the laser's slice 0
+    double dx = 0.0, dy = 0.0, xoff = 0.0, yoff = 0.0, lenx = 0.0, leny = 0.0;      // cell size, GetPosOffset, patch length
+    bool grid = false;                                             // hps_engine_set_laser_grid
+    double *chi = nullptr, *chi_initial = nullptr;                 // [ny][nx], grid only: chi the envelope solver reads, chi of the unperturbed plasma
     double2 *nm1 = nullptr, *n00 = nullptr, *np1 = nullptr;      // [nz][ny][nx]
     double2* work = nullptr;                                       // [ny][nx] right-hand side / solution
     LaserPhase* phase = nullptr;
@@ -42,6 +50,7 @@ struct LaserState {
         (void)hipFree(nm1); (void)hipFree(n00); (void)hipFree(np1); (void)hipFree(work); (void)hipFree(phase); (void)hipFree(fft_work);
         if (mg) mg2_destroy_internal(mg);
         (void)hipFree(mg_sol); (void)hipFree(mg_rhs); (void)hipFree(mg_acf_real); (void)hipFree(mg_acf_imag);
+        (void)hipFree(chi); (void)hipFree(chi_initial);
     }
 };
 
@@ -98,6 +107,99 @@ void k_laser_aabs (SlabView f, int c_aabs, const double2* __restrict__ a, double
     }
 }
 
+// UpdateLaserAabs on a laser grid of its own (:253-284): one thread per field cell, guard cells included (the reference
+// runs over the grown box); |a|^2 is formed in the gather -- the laser plane is small and stays in L2, no |a|^2 plane is
+// written.  Laser cells outside 0 .. nxl-1 x 0 .. nyl-1 contribute nothing, so a field cell away from the patch gets 0.
+template <int ORDER>
+__global__ __launch_bounds__(256)
+void k_laser_interp_aabs (SlabView f, int c_aabs, const double2* __restrict__ a, int nxl, int nyl, double dxf, double dyf,
+                          double xofff, double yofff, double dxl_inv, double dyl_inv, double xoffl, double yoffl)
+{
+    const int i = blockIdx.x*blockDim.x + threadIdx.x - f.ng;
+    const int j = blockIdx.y - f.ng;
+    if (i >= f.nx + f.ng) return;
+    const double xmid = (i*dxf + xofff - xoffl)*dxl_inv;
+    const double ymid = (j*dyf + yofff - yoffl)*dyl_inv;
+    double v = 0.0;
+    // (the stencil of a point further than 3 cells from the patch holds no laser cell; also keeps floor() in int range)
+    if (xmid > -3.0 && xmid < nxl + 2.0 && ymid > -3.0 && ymid < nyl + 2.0) {
+        double sx[4], sy[4];
+        const int i0 = shape_weights<ORDER>(xmid, sx), j0 = shape_weights<ORDER>(ymid, sy);
+        for (int iy = 0; iy <= ORDER; ++iy) {
+            const int cy = j0 + iy;
+            if (cy < 0 || cy >= nyl) continue;
+            for (int ix = 0; ix <= ORDER; ++ix) {
+                const int cx = i0 + ix;
+                if (cx < 0 || cx >= nxl) continue;
+                const double2 e = a[(long)cy*nxl + cx];
+                v += sx[ix]*sy[iy]*(e.x*e.x + e.y*e.y);
+            }
+        }
+    }
+    f.p[c_aabs*f.ns + f.off(i, j)] = v;
+}
+
+// sum |a_n| over the cells of one laser plane (the "laserEnvelope" checksum with a laser grid)
+__global__ __launch_bounds__(256)
+void k_laser_sum_abs (const double2* __restrict__ a, long n, double* sum_abs)
+{
+    const long o = (long)blockIdx.x*blockDim.x + threadIdx.x;
+    double mag = 0.0;
+    if (o < n) { const double2 e = a[o]; mag = sqrt(e.x*e.x + e.y*e.y); }
+    for (int s = 32; s > 0; s >>= 1) mag += __shfl_xor(mag, s);
+    __shared__ double part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mag;
+    __syncthreads();
+    if (threadIdx.x == 0) atomic_add_f64(sum_abs, part[0] + part[1] + part[2] + part[3]);
+}
+
+// SetInitialChi (:293-332): chi of the unperturbed plasma on the laser grid, "as if it were deposited there" -- the sum over
+// the species of density(x, y, c t) q^2 mu0 / m (times init_level^2 for the ionisable one), with the engine's density:
+// <plasma>.density, radius, hollow_core_radius and the tabulated f_r f_t.  f0, f1: density q^2 mu0 / m of the two species.
+__global__ __launch_bounds__(256)
+void k_laser_chi_initial (double* __restrict__ out, int nxl, int nyl, double dxl, double dyl, double xoffl, double yoffl, double f0, double f1,
+                          const double* __restrict__ prof, int nr, double ft, double radius_sq, double hollow_sq)
+{
+    const int i = blockIdx.x*blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
+    if (i >= nxl) return;
+    const double x = i*dxl + xoffl, y = j*dyl + yoffl;
+    const double rsq = x*x + y*y;
+    const double fac = (rsq > radius_sq || rsq < hollow_sq) ? 0.0 : ft*table_value(prof, prof + nr, nr, sqrt(rsq));
+    out[(long)j*nxl + i] = fac*f0 + fac*f1;
+}
+
+// InterpolateChi (:334-407): one thread per laser cell.  Inside x_lo .. x_hi, y_lo .. y_hi (the laser cells on the field box
+// shrunk by the guard width, :358-372) chi of the slab, interpolated; outside, chi of the unperturbed plasma.
+template <int ORDER>
+__global__ __launch_bounds__(256)
+void k_laser_interp_chi (SlabView f, int c_chi, const double* __restrict__ chi_initial, double* __restrict__ chi_out, int nxl, int nyl,
+                         double dxl, double dyl, double xoffl, double yoffl, double dxf_inv, double dyf_inv, double xofff, double yofff,
+                         int x_lo, int x_hi, int y_lo, int y_hi)
+{
+    const int i = blockIdx.x*blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
+    if (i >= nxl) return;
+    const long o = (long)j*nxl + i;
+    if (!(x_lo <= i && i <= x_hi && y_lo <= j && j <= y_hi)) { chi_out[o] = chi_initial[o]; return; }
+    const double xmid = (i*dxl + xoffl - xofff)*dxf_inv;
+    const double ymid = (j*dyl + yoffl - yofff)*dyf_inv;
+    double sx[4], sy[4];
+    const int i0 = shape_weights<ORDER>(xmid, sx), j0 = shape_weights<ORDER>(ymid, sy);
+    const double* __restrict__ src = f.p + c_chi*f.ns;
+    double chi = 0.0;
+    for (int iy = 0; iy <= ORDER; ++iy) {
+        const int cy = j0 + iy;
+        if (cy < -f.ng || cy >= f.ny + f.ng) continue;        // (a stencil wider than shrink + guard width: never in the engine)
+        for (int ix = 0; ix <= ORDER; ++ix) {
+            const int cx = i0 + ix;
+            if (cx < -f.ng || cx >= f.nx + f.ng) continue;
+            chi += sx[ix]*sy[iy]*src[f.off(cx, cy)];
+        }
+    }
+    chi_out[o] = chi;
+}
+
 // on-axis phases of a_n on slices j, j+1, j+2 (the sum of the 1, 2 or 4 cells nearest the axis, as Wake-T; :651-697)
 // -> exp(i(t_j - t_j+1)), exp(i(t_j - t_j+2)) and D_j^n.  One lane.
 __global__ void k_laser_phase (const double2* j00, const double2* jp1, const double2* jp2, int nx, int ny, int use_phase, double dz,
@@ -134,13 +236,12 @@ struct LaserSlices { const double2 *n00j00, *n00jp1, *n00jp2, *nm1j00, *nm1jp1, 
 
 // right-hand side of the envelope equation (:700-749)
 __global__ __launch_bounds__(256)
-void k_laser_rhs (LaserSlices S, SlabView f, int c_chi, double chi0, int gshrink, const LaserPhase* ph, int step,
-                  double dx, double dy, double dz, double c, double dt, double k0, double2* rhs,
+void k_laser_rhs (LaserSlices S, SlabView f, int c_chi, double chi0, int gshrink, const double* __restrict__ chi_plane, int nx, int ny,
+                  const LaserPhase* ph, int step, double dx, double dy, double dz, double c, double dt, double k0, double2* rhs,
                   double* mg_rhs, double* mg_acf_real, double* mg_acf_imag)
 {
     const int i = blockIdx.x*blockDim.x + threadIdx.x;
     const int j = blockIdx.y;
-    const int nx = f.nx, ny = f.ny;
     if (i >= nx) return;
     const long o = (long)j*nx + i;
     auto ld = [o] (const double2* p) { return p ? p[o] : make_double2(0.0, 0.0); };
@@ -152,9 +253,10 @@ void k_laser_rhs (LaserSlices S, SlabView f, int c_chi, double chi0, int gshrink
         lap.x = (xp.x + xm.x - 2.0*c0.x)/(dx*dx) + (yp.x + ym.x - 2.0*c0.x)/(dy*dy);
         lap.y = (xp.y + xm.y - 2.0*c0.y)/(dx*dx) + (yp.y + ym.y - 2.0*c0.y)/(dy*dy);
     }
-    // InterpolateChi (:334-407): chi of the slab inside the box shrunk by the guard width, the initial chi outside
+    // InterpolateChi (:334-407): chi of the slab inside the box shrunk by the guard width, the initial chi outside; on a laser
+    // grid of its own k_laser_interp_chi has done that (nx, ny are the laser's, the slab is not read)
     const bool inside = i >= gshrink && i < nx - gshrink && j >= gshrink && j < ny - gshrink;
-    const double chi = inside ? f.p[c_chi*f.ns + f.off(i, j)] : chi0;
+    const double chi = chi_plane ? chi_plane[o] : (inside ? f.p[c_chi*f.ns + f.off(i, j)] : chi0);
     const double2 an00j00 = ld(S.n00j00), anp1jp1 = ld(S.np1jp1), anp1jp2 = ld(S.np1jp2);
     const double cdz = 1.0/(c*dt*dz), cdt = 1.0/(c*dt);
     // chi term: 2 chi a_n on the right-hand side (fft, :713-740); multigrid with MG_average_rhs = 1: chi a_n (first step)
@@ -232,8 +334,16 @@ int laser_create (Engine& E)
     LaserState* L = new LaserState;
     E.laser = L;
     const hps_deck& d = E.d;
-    L->nx = d.nx; L->ny = d.ny; L->nz = d.nz;
-    const size_t plane = (size_t)d.nx*d.ny, tot = plane*d.nz;
+    const Engine::LaserGrid& G = E.lgrid;
+    L->grid = G.set;
+    if (G.set) {
+        L->nx = G.nx; L->ny = G.ny; L->nz = G.zhi - G.zlo + 1; L->zlo = G.zlo;
+        L->dx = G.dx; L->dy = G.dy; L->xoff = G.xoff; L->yoff = G.yoff; L->lenx = G.hi[0] - G.lo[0]; L->leny = G.hi[1] - G.lo[1];
+    } else {
+        L->nx = d.nx; L->ny = d.ny; L->nz = d.nz; L->zlo = 0;
+        L->dx = E.gm.dx; L->dy = E.gm.dy; L->xoff = E.gm.xoff; L->yoff = E.gm.yoff; L->lenx = d.hi[0] - d.lo[0]; L->leny = d.hi[1] - d.lo[1];
+    }
+    const size_t plane = (size_t)L->nx*L->ny, tot = plane*L->nz;
     HPS_HIP_CHECK(hipMalloc(&L->n00, tot*sizeof(double2)));
     HPS_HIP_CHECK(hipMalloc(&L->phase, sizeof(LaserPhase)));
     if (d.laser_solver >= 1 && d.dt != 0.0) {
@@ -241,10 +351,16 @@ int laser_create (Engine& E)
         HPS_HIP_CHECK(hipMalloc(&L->np1, tot*sizeof(double2)));
         HPS_HIP_CHECK(hipMemset(L->nm1, 0, tot*sizeof(double2)));
         HPS_HIP_CHECK(hipMemset(L->np1, 0, tot*sizeof(double2)));
+        if (L->grid) {
+            HPS_HIP_CHECK(hipMalloc(&L->chi, plane*sizeof(double)));
+            HPS_HIP_CHECK(hipMalloc(&L->chi_initial, plane*sizeof(double)));
+            HPS_HIP_CHECK(hipMemset(L->chi, 0, plane*sizeof(double)));
+            HPS_HIP_CHECK(hipMemset(L->chi_initial, 0, plane*sizeof(double)));
+        }
     }
     if (d.laser_solver == 2 && d.dt != 0.0) {
-        if (d.nx % 2 || d.ny % 2) { set_error("laser: the multigrid envelope solver needs even nx, ny (cell-centred hpmg box)"); return HPS_ERR_UNSUPPORTED; }
-        if (int e = mg2_create_internal(d.nx, d.ny, E.gm.dx, E.gm.dy, &L->mg)) return e;
+        if (L->nx % 2 || L->ny % 2) { set_error("laser: the multigrid envelope solver needs even nx, ny (cell-centred hpmg box)"); return HPS_ERR_UNSUPPORTED; }
+        if (int e = mg2_create_internal(L->nx, L->ny, L->dx, L->dy, &L->mg)) return e;
         HPS_HIP_CHECK(hipMalloc(&L->mg_sol, 2*plane*sizeof(double)));
         HPS_HIP_CHECK(hipMemset(L->mg_sol, 0, 2*plane*sizeof(double)));
         HPS_HIP_CHECK(hipMalloc(&L->mg_rhs, 2*plane*sizeof(double)));
@@ -255,7 +371,7 @@ int laser_create (Engine& E)
         HPS_HIP_CHECK(hipMalloc(&L->work, plane*sizeof(double2)));
         static bool setup = false;
         if (!setup) { rocfft_setup(); setup = true; }
-        const size_t len[2] = {(size_t)d.nx, (size_t)d.ny};
+        const size_t len[2] = {(size_t)L->nx, (size_t)L->ny};
         if (rocfft_plan_create(&L->fwd, rocfft_placement_inplace, rocfft_transform_type_complex_forward, rocfft_precision_double, 2, len, 1, nullptr) != rocfft_status_success ||
             rocfft_plan_create(&L->bwd, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, rocfft_precision_double, 2, len, 1, nullptr) != rocfft_status_success) {
             set_error("laser: rocfft_plan_create failed"); return HPS_ERR_FFT;
@@ -275,6 +391,8 @@ int laser_create (Engine& E)
 
 void laser_destroy (Engine& E) { delete E.laser; E.laser = nullptr; }
 
+void laser_sizes (Engine& E, int* nx, int* ny, int* nz) { *nx = E.laser->nx; *ny = E.laser->ny; *nz = E.laser->nz; }
+
 // start of a time step: the first one evaluates the Gaussian on every slice, later ones hand the time levels on
 // (a_{n+1} -> a_n -> a_{n-1}; MultiBuffer.cpp:840-852, 913-925)
 int laser_begin_step (Engine& E)
@@ -284,9 +402,10 @@ int laser_begin_step (Engine& E)
     if (L->import_mode) {
         L->initialised = true;       // levels are filled slice by slice; the driver has set the step index
     } else if (!L->initialised) {
-        const double zoff = 0.5*(d.lo[2] + d.hi[2] - E.gm.dz*(d.nz - 1));
-        hipLaunchKernelGGL(k_laser_init, dim3(ceil_div(d.nx, 256), d.ny, d.nz), dim3(256), 0, E.st, L->n00, d.nx, d.ny, d.nz, laser_pars(d),
-                           E.gm.dx, E.gm.dy, E.gm.dz, E.gm.xoff, E.gm.yoff, zoff);
+        // a laser slice with global index k sits at the z of field slice k (the patch's z limits are snapped to whole field cells)
+        const double zoff = 0.5*(d.lo[2] + d.hi[2] - E.gm.dz*(d.nz - 1)) + L->zlo*E.gm.dz;
+        hipLaunchKernelGGL(k_laser_init, dim3(ceil_div(L->nx, 256), L->ny, L->nz), dim3(256), 0, E.st, L->n00, L->nx, L->ny, L->nz, laser_pars(d),
+                           L->dx, L->dy, E.gm.dz, L->xoff, L->yoff, zoff);
         L->initialised = true; L->steps = 0;
     } else if (L->np1) {
         double2* old = L->nm1; L->nm1 = L->n00; L->n00 = L->np1; L->np1 = old;
@@ -296,33 +415,105 @@ int laser_begin_step (Engine& E)
     return HPS_OK;
 }
 
+// SetInitialChi (Hipace.cpp, once per step): needs the density profile's time factor of the step that begins
+int laser_chi_initial (Engine& E)
+{
+    LaserState* L = E.laser;
+    if (!L->chi_initial) return HPS_OK;
+    const hps_deck& d = E.d;
+    const double f0 = d.plasma_density > 0.0 ? d.plasma_density*d.plasma_charge*d.plasma_charge*E.gm.mu0/d.plasma_mass : 0.0;
+    const double f1 = d.ion_on ? d.ion_density*d.ion_charge*d.ion_charge*E.gm.mu0/d.ion_mass*(double)d.ion_init_level*(double)d.ion_init_level : 0.0;
+    const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : INFINITY;
+    hipLaunchKernelGGL(k_laser_chi_initial, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), 0, E.st, L->chi_initial, L->nx, L->ny, L->dx, L->dy,
+                       L->xoff, L->yoff, f0, f1, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, radius_sq, E.hollow_core_radius*E.hollow_core_radius);
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
+static int launch_interp_aabs (SlabView f, int c_aabs, const double2* a, int nxl, int nyl, double dxl, double dyl, double xoffl, double yoffl,
+                               const hps_geom& gm, int order, hipStream_t st)
+{
+    const dim3 grid(ceil_div(f.js, 256), f.ny + 2*f.ng), block(256);
+#define HPS_LAUNCH_AABS(O) hipLaunchKernelGGL(k_laser_interp_aabs<O>, grid, block, 0, st, f, c_aabs, a, nxl, nyl, gm.dx, gm.dy, gm.xoff, gm.yoff, \
+                                              1.0/dxl, 1.0/dyl, xoffl, yoffl)
+    switch (order) {
+        case 0: HPS_LAUNCH_AABS(0); break;
+        case 1: HPS_LAUNCH_AABS(1); break;
+        case 2: HPS_LAUNCH_AABS(2); break;
+        default: HPS_LAUNCH_AABS(3); break;
+    }
+#undef HPS_LAUNCH_AABS
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
+static int launch_interp_chi (SlabView f, int c_chi, const double* chi_initial, double* chi_out, int nxl, int nyl, double dxl, double dyl,
+                              double xoffl, double yoffl, const hps_geom& gm, int shrink, int order, hipStream_t st)
+{
+    // the laser cells where the field box, shrunk by the guard width, ends (:358-372)
+    const double pos_x_lo = shrink*gm.dx + gm.xoff, pos_x_hi = (f.nx - 1 - shrink)*gm.dx + gm.xoff;
+    const double pos_y_lo = shrink*gm.dy + gm.yoff, pos_y_hi = (f.ny - 1 - shrink)*gm.dy + gm.yoff;
+    const double dxl_inv = 1.0/dxl, dyl_inv = 1.0/dyl;
+    auto clamp = [] (double v, int n) { return (int)std::min(std::max(v, -1.0), (double)n); };
+    const int x_lo = clamp(std::ceil((pos_x_lo - xoffl)*dxl_inv), nxl), x_hi = clamp(std::floor((pos_x_hi - xoffl)*dxl_inv), nxl);
+    const int y_lo = clamp(std::ceil((pos_y_lo - yoffl)*dyl_inv), nyl), y_hi = clamp(std::floor((pos_y_hi - yoffl)*dyl_inv), nyl);
+    const dim3 grid(ceil_div(nxl, 256), nyl), block(256);
+#define HPS_LAUNCH_CHI(O) hipLaunchKernelGGL(k_laser_interp_chi<O>, grid, block, 0, st, f, c_chi, chi_initial, chi_out, nxl, nyl, dxl, dyl, xoffl, yoffl, \
+                                             1.0/gm.dx, 1.0/gm.dy, gm.xoff, gm.yoff, x_lo, x_hi, y_lo, y_hi)
+    switch (order) {
+        case 0: HPS_LAUNCH_CHI(0); break;
+        case 1: HPS_LAUNCH_CHI(1); break;
+        case 2: HPS_LAUNCH_CHI(2); break;
+        default: HPS_LAUNCH_CHI(3); break;
+    }
+#undef HPS_LAUNCH_CHI
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
 int laser_update_aabs (Engine& E, int islice, double* sum_abs)
 {
     LaserState* L = E.laser;
     SlabView f(E.slab);
-    hipLaunchKernelGGL(k_laser_aabs, dim3(ceil_div(E.slab.jstride, 256), E.d.ny + 2*E.g), dim3(256), 0, E.st, f, E.c_aabs,
-                       L->n00 + (size_t)islice*L->nx*L->ny, sum_abs);
-    return HPS_OK;
+    if (!L->grid) {
+        hipLaunchKernelGGL(k_laser_aabs, dim3(ceil_div(E.slab.jstride, 256), E.d.ny + 2*E.g), dim3(256), 0, E.st, f, E.c_aabs,
+                           L->n00 + (size_t)islice*L->nx*L->ny, sum_abs);
+        return HPS_OK;
+    }
+    if (!E.laser_has_slice(islice)) {        // no laser on this slice: aabs = 0 (:223-230)
+        HPS_HIP_CHECK(hipMemsetAsync(E.slab.p + (size_t)E.c_aabs*E.slab.nstride, 0, (size_t)E.slab.nstride*sizeof(double), E.st));
+        return HPS_OK;
+    }
+    const size_t plane = (size_t)L->nx*L->ny;
+    const double2* a = L->n00 + (size_t)(islice - L->zlo)*plane;
+    if (sum_abs) hipLaunchKernelGGL(k_laser_sum_abs, dim3(ceil_div((long)plane, 256)), dim3(256), 0, E.st, a, (long)plane, sum_abs);
+    return launch_interp_aabs(f, E.c_aabs, a, L->nx, L->ny, L->dx, L->dy, L->xoff, L->yoff, E.gm, E.lgrid.order, E.st);
 }
 
 // MultiLaser::AdvanceSlice: lasers.solver_type = fft (AdvanceSliceFFT) or multigrid (AdvanceSliceMG)
 int laser_advance_slice (Engine& E, int islice)
 {
     LaserState* L = E.laser;
-    if (!L->np1) return HPS_OK;
+    if (!L->np1 || !E.laser_has_slice(islice)) return HPS_OK;       // UseLaser(islice)
     const hipStream_t ls = E.laser_stream();       // ordered against the engine's stream by Engine::fork_laser / join_laser
     const hps_deck& d = E.d;
-    const size_t plane = (size_t)d.nx*d.ny;
-    auto at = [&] (const double2* base, int sl) -> const double2* { return sl < d.nz ? base + (size_t)sl*plane : nullptr; };
-    const LaserSlices S{at(L->n00, islice), at(L->n00, islice + 1), at(L->n00, islice + 2),
-                        at(L->nm1, islice), at(L->nm1, islice + 1), at(L->nm1, islice + 2),
-                        at(L->np1, islice + 1), at(L->np1, islice + 2)};
+    const size_t plane = (size_t)L->nx*L->ny;
+    const int nx = L->nx, ny = L->ny, k = islice - L->zlo;
+    // beyond the head = beyond the laser's last slice (zeta_hi)
+    auto at = [&] (const double2* base, int sl) -> const double2* { return sl < L->nz ? base + (size_t)sl*plane : nullptr; };
+    const LaserSlices S{at(L->n00, k), at(L->n00, k + 1), at(L->n00, k + 2),
+                        at(L->nm1, k), at(L->nm1, k + 1), at(L->nm1, k + 2),
+                        at(L->np1, k + 1), at(L->np1, k + 2)};
     const double k0 = 2.0*3.14159265358979323846/d.laser_lambda0;
-    hipLaunchKernelGGL(k_laser_phase, dim3(1), dim3(1), 0, ls, S.n00j00, S.n00jp1, S.n00jp2, d.nx, d.ny, d.laser_use_phase, E.gm.dz, L->phase);
-    const dim3 grid(ceil_div(d.nx, 256), d.ny), block(256);
+    if (L->grid) {
+        if (int e = launch_interp_chi(SlabView(E.slab), (int)HPS_C_CHI, L->chi_initial, L->chi, nx, ny, L->dx, L->dy, L->xoff, L->yoff, E.gm,
+                                      E.g, E.lgrid.order, ls)) return e;
+    }
+    hipLaunchKernelGGL(k_laser_phase, dim3(1), dim3(1), 0, ls, S.n00j00, S.n00jp1, S.n00jp2, nx, ny, d.laser_use_phase, E.gm.dz, L->phase);
+    const dim3 grid(ceil_div(nx, 256), ny), block(256);
     const double chi0 = d.plasma_density > 0.0 ? d.plasma_density*d.plasma_charge*d.plasma_charge*E.gm.mu0/d.plasma_mass : 0.0;
-    hipLaunchKernelGGL(k_laser_rhs, grid, block, 0, ls, S, SlabView(E.slab), (int)HPS_C_CHI, chi0, E.g, L->phase, L->steps,
-                       E.gm.dx, E.gm.dy, E.gm.dz, E.gm.c, d.dt, k0, L->work, L->mg_rhs, L->mg_acf_real, L->mg_acf_imag);
+    hipLaunchKernelGGL(k_laser_rhs, grid, block, 0, ls, S, SlabView(E.slab), (int)HPS_C_CHI, chi0, E.g, L->chi, nx, ny, L->phase, L->steps,
+                       L->dx, L->dy, E.gm.dz, E.gm.c, d.dt, k0, L->work, L->mg_rhs, L->mg_acf_real, L->mg_acf_imag);
     if (L->mg) {
         // MultiLaser::AdvanceSliceMG (:430-608): hpmg system type 2, at most 200 V-cycles; the initial guess is the solution
         // of the slice solved before this one (np1j00 is left in place by ShiftLaserSlices, :208)
@@ -330,23 +521,24 @@ int laser_advance_slice (Engine& E, int islice)
         if (int e = mg2_solve_internal(L->mg, L->mg_sol, L->mg_rhs, L->mg_acf_real, L->mg_acf_imag,
                                        d.laser_mg_tol_rel > 0.0 ? d.laser_mg_tol_rel : 1.0e-4, d.laser_mg_tol_abs, 200, &iters, ls)) return e;
         L->mg_vcycles += iters;
-        hipLaunchKernelGGL(k_laser_from_planar, dim3(ceil_div((long)plane, 256)), block, 0, ls, L->mg_sol, L->np1 + (size_t)islice*plane, (long)plane);
+        hipLaunchKernelGGL(k_laser_from_planar, dim3(ceil_div((long)plane, 256)), block, 0, ls, L->mg_sol, L->np1 + (size_t)k*plane, (long)plane);
         HPS_HIP_CHECK(hipGetLastError());
         return HPS_OK;
     }
     void* buf[1] = {L->work};
     if (rocfft_execute(L->fwd, buf, nullptr, L->info) != rocfft_status_success) { set_error("laser: forward FFT failed"); return HPS_ERR_FFT; }
-    hipLaunchKernelGGL(k_laser_divide, grid, block, 0, ls, L->work, d.nx, d.ny, 2.0*3.14159265358979323846/(d.hi[0] - d.lo[0]),
-                       2.0*3.14159265358979323846/(d.hi[1] - d.lo[1]), L->phase, L->steps, E.gm.dz, E.gm.c, d.dt, k0);
+    hipLaunchKernelGGL(k_laser_divide, grid, block, 0, ls, L->work, nx, ny, 2.0*3.14159265358979323846/L->lenx,
+                       2.0*3.14159265358979323846/L->leny, L->phase, L->steps, E.gm.dz, E.gm.c, d.dt, k0);
     if (rocfft_execute(L->bwd, buf, nullptr, L->info) != rocfft_status_success) { set_error("laser: backward FFT failed"); return HPS_ERR_FFT; }
-    hipLaunchKernelGGL(k_laser_store, dim3(ceil_div((long)plane, 256)), block, 0, ls, L->work, L->np1 + (size_t)islice*plane, (long)plane,
+    hipLaunchKernelGGL(k_laser_store, dim3(ceil_div((long)plane, 256)), block, 0, ls, L->work, L->np1 + (size_t)k*plane, (long)plane,
                        1.0/(double)plane);
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
 
 // ring hand-off of the envelope (MultiBuffer.cpp:840-852, 913-925): a stage passes {a_{n+1}, a_n} of a slice on, the next
-// one stores them as its {a_n, a_{n-1}}.  msg = [2][ny][nx] complex on the device; both asynchronous on the stream.
+// one stores them as its {a_n, a_{n-1}}.  msg = [2][ny][nx] complex of the laser grid on the device; both asynchronous on the
+// stream.  A slice without a laser (outside the grid's zeta range) has no message: nothing is done.
 int laser_set_import (Engine& E, int on, int step)
 {
     E.laser->import_mode = (on != 0); E.laser->steps = step;
@@ -354,20 +546,22 @@ int laser_set_import (Engine& E, int on, int step)
 }
 int laser_export_slice (Engine& E, int islice, double* msg_dev)
 {
+    if (!E.laser_has_slice(islice)) return HPS_OK;
     if (int e = E.join_laser()) return e;
     LaserState* L = E.laser;
-    const size_t plane = (size_t)L->nx*L->ny;
+    const size_t plane = (size_t)L->nx*L->ny, k = (size_t)(islice - L->zlo);
     const double2* newest = L->np1 ? L->np1 : L->n00;
-    HPS_HIP_CHECK(hipMemcpyAsync(msg_dev, newest + (size_t)islice*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
-    HPS_HIP_CHECK(hipMemcpyAsync(msg_dev + 2*plane, L->n00 + (size_t)islice*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
+    HPS_HIP_CHECK(hipMemcpyAsync(msg_dev, newest + k*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
+    HPS_HIP_CHECK(hipMemcpyAsync(msg_dev + 2*plane, L->n00 + k*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
     return HPS_OK;
 }
 int laser_import_slice (Engine& E, int islice, const double* msg_dev)
 {
+    if (!E.laser_has_slice(islice)) return HPS_OK;
     LaserState* L = E.laser;
-    const size_t plane = (size_t)L->nx*L->ny;
-    HPS_HIP_CHECK(hipMemcpyAsync(L->n00 + (size_t)islice*plane, msg_dev, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
-    if (L->nm1) HPS_HIP_CHECK(hipMemcpyAsync(L->nm1 + (size_t)islice*plane, msg_dev + 2*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
+    const size_t plane = (size_t)L->nx*L->ny, k = (size_t)(islice - L->zlo);
+    HPS_HIP_CHECK(hipMemcpyAsync(L->n00 + k*plane, msg_dev, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
+    if (L->nm1) HPS_HIP_CHECK(hipMemcpyAsync(L->nm1 + k*plane, msg_dev + 2*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
     return HPS_OK;
 }
 
@@ -375,12 +569,13 @@ int laser_import_slice (Engine& E, int islice, const double* msg_dev)
 // the previous step, on the receiving engine's stream (the caller has made it wait for the sender's slice event)
 int laser_import_from (Engine& E, int islice, Engine& src)
 {
+    if (!E.laser_has_slice(islice)) return HPS_OK;
     LaserState* L = E.laser; LaserState* P = src.laser;
-    const size_t plane = (size_t)L->nx*L->ny;
+    const size_t plane = (size_t)L->nx*L->ny, k = (size_t)(islice - L->zlo);
     const double2* newest = P->np1 ? P->np1 : P->n00;
     // a_n -> a_{n-1} first: with one stage in flight source and destination are the same engine
-    if (L->nm1) HPS_HIP_CHECK(hipMemcpyAsync(L->nm1 + (size_t)islice*plane, P->n00 + (size_t)islice*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
-    if (newest != L->n00) HPS_HIP_CHECK(hipMemcpyAsync(L->n00 + (size_t)islice*plane, newest + (size_t)islice*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
+    if (L->nm1) HPS_HIP_CHECK(hipMemcpyAsync(L->nm1 + k*plane, P->n00 + k*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
+    if (newest != L->n00) HPS_HIP_CHECK(hipMemcpyAsync(L->n00 + k*plane, newest + k*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
     return HPS_OK;
 }
 
@@ -395,4 +590,39 @@ int laser_copy_envelope (Engine& E, double* out_host)
     return HPS_OK;
 }
 
+int laser_copy_chi (Engine& E, double* out_host)
+{
+    LaserState* L = E.laser;
+    HPS_REQUIRE(L && L->chi, "hps_engine_laser_chi: needs a laser grid (hps_engine_set_laser_grid) and an evolving envelope (laser_solver >= 1, dt != 0)");
+    if (int e = E.join_laser()) return e;
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));
+    HPS_HIP_CHECK(hipMemcpy(out_host, L->chi, (size_t)L->nx*L->ny*sizeof(double), hipMemcpyDeviceToHost));
+    return HPS_OK;
+}
+
 } // namespace hps
+
+// The two grid-to-grid interpolations of the laser grid as operators of their own (the engine's kernels and launch code).
+// a_plane: [nyl][nxl] complex (re, im interleaved) on the device; the laser grid is nxl x nyl cells of dxl x dyl with cell 0 at
+// xoffl, yoffl; geom is the field slab's geometry.
+extern "C" int hps_laser_interp_aabs (hps_slab slab, int c_aabs, const double* a_plane, int nxl, int nyl, double dxl, double dyl,
+                                      double xoffl, double yoffl, hps_geom geom, int order, void* stream)
+{
+    using namespace hps;
+    HPS_REQUIRE(slab.p && a_plane && c_aabs >= 0 && c_aabs < slab.ncomp, "hps_laser_interp_aabs: bad slab, plane or component");
+    HPS_REQUIRE(nxl > 0 && nyl > 0 && dxl > 0.0 && dyl > 0.0, "hps_laser_interp_aabs: the laser grid needs cells of positive size");
+    HPS_REQUIRE(order >= 0 && order <= 3, "hps_laser_interp_aabs: lasers.interp_order must be 0, 1, 2 or 3");
+    return launch_interp_aabs(SlabView(slab), c_aabs, reinterpret_cast<const double2*>(a_plane), nxl, nyl, dxl, dyl, xoffl, yoffl, geom, order,
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" int hps_laser_interp_chi (hps_slab slab, int c_chi, const double* chi_initial, double* chi_out, int nxl, int nyl, double dxl,
+                                     double dyl, double xoffl, double yoffl, hps_geom geom, int shrink, int order, void* stream)
+{
+    using namespace hps;
+    HPS_REQUIRE(slab.p && chi_initial && chi_out && c_chi >= 0 && c_chi < slab.ncomp, "hps_laser_interp_chi: bad slab, plane or component");
+    HPS_REQUIRE(nxl > 0 && nyl > 0 && dxl > 0.0 && dyl > 0.0, "hps_laser_interp_chi: the laser grid needs cells of positive size");
+    HPS_REQUIRE(order >= 0 && order <= 3 && shrink >= 0, "hps_laser_interp_chi: lasers.interp_order must be 0, 1, 2 or 3 and shrink must not be negative");
+    return launch_interp_chi(SlabView(slab), c_chi, chi_initial, chi_out, nxl, nyl, dxl, dyl, xoffl, yoffl, geom, shrink, order,
+                             static_cast<hipStream_t>(stream));
+}

@@ -15,6 +15,7 @@ per-slice hot path.  The named decks restate
                          ppc 2x2) used by bench.py.
 """
 import copy
+import math
 
 _DEFAULT = dict(
     nx=64, ny=64, nz=100,
@@ -304,6 +305,64 @@ def config5(n=1024, nz=2048, solver=1, si=False, ionize=True):
         with_ion_species(d, "N", 0.2, ppc=(1, 1), initial_level=0, seed=5)
         d["background_density_SI"] = 2.8239587008591567e23      # kp_inv = 10 um (hipace.background_density_SI)
     return d
+
+
+def config5_laser_patch(n=1024, nz=2048, n_laser=256, solver=1, si=False, ionize=True):
+    """config5 with the envelope on a centred n_laser x n_laser patch whose cells are the field's (lasers.n_cell, patch_lo,
+    patch_hi; all slices): the pulse (w0 = 4 kp^-1 of a 40 kp^-1 box) needs no more."""
+    d = config5(n, nz, solver, si, ionize)
+    dx, dy = (d["hi"][0] - d["lo"][0]) / n, (d["hi"][1] - d["lo"][1]) / n
+    cx, cy = 0.5 * (d["lo"][0] + d["hi"][0]), 0.5 * (d["lo"][1] + d["hi"][1])
+    d.update(laser_n_cell=(n_laser, n_laser), laser_patch_lo=(cx - 0.5 * n_laser * dx, cy - 0.5 * n_laser * dy, d["lo"][2]),
+             laser_patch_hi=(cx + 0.5 * n_laser * dx, cy + 0.5 * n_laser * dy, d["hi"][2]), laser_interp_order=1)
+    return d
+
+
+# lasers.n_cell, patch_lo, patch_hi, interp_order (MultiLaser::MakeLaserGeometry, laser/MultiLaser.cpp:58-115): the envelope on a
+# grid of its own.  Kept apart from _DEFAULT like PLASMA_INIT_DEFAULT and applied by SliceEngine through
+# hps_engine_set_laser_grid; None = the field grid's cells / the field box.  A deck without any of the four keys makes no call.
+LASER_GRID_DEFAULT = dict(laser_n_cell=None, laser_patch_lo=None, laser_patch_hi=None, laser_interp_order=1)
+
+
+def has_laser_grid(deck):
+    return any(deck.get(k) is not None for k in ("laser_n_cell", "laser_patch_lo", "laser_patch_hi")) or "laser_interp_order" in deck
+
+
+def _round_half_away(v):
+    return math.copysign(math.floor(abs(v) + 0.5), v)        # std::round
+
+
+def laser_geometry(deck):
+    """The laser grid of `deck` as the engine makes it (hps_engine_set_laser_grid): -> (nxl, nyl, zeta_lo, zeta_hi, lo3, hi3, dxl,
+    dyl, xoffl, yoffl).  n_cell and the patch default to the field grid and box; zeta is snapped to whole field cells, so laser
+    slice k sits at the z of field slice k; xoffl, yoffl: GetPosOffset of the laser box (position of laser cell 0).
+    ValueError: an empty zeta range, a box without volume, interp_order outside 0 .. 3, odd n_cell with the multigrid solver."""
+    nx, ny, nz, lo, hi = deck["nx"], deck["ny"], deck["nz"], deck["lo"], deck["hi"]
+    order = deck.get("laser_interp_order", 1)
+    if order is None or int(order) != order or not 0 <= order <= 3:
+        raise ValueError("lasers.interp_order must be 0, 1, 2 or 3")
+    n_cell = deck.get("laser_n_cell")
+    nxl, nyl = (int(n_cell[0]), int(n_cell[1])) if n_cell is not None else (nx, ny)
+    if nxl < 1 or nyl < 1:
+        raise ValueError("lasers.n_cell must be positive")
+    plo = [float(v) for v in (deck.get("laser_patch_lo") if deck.get("laser_patch_lo") is not None else lo)]
+    phi = [float(v) for v in (deck.get("laser_patch_hi") if deck.get("laser_patch_hi") is not None else hi)]
+    dz = (hi[2] - lo[2]) / nz
+    poff_z, dz_inv = 0.5 * (lo[2] + hi[2] - dz * (nz - 1)), 1.0 / dz
+    zl = max(0.0, _round_half_away((plo[2] - poff_z) * dz_inv))
+    zh = min(float(nz - 1), _round_half_away((phi[2] - poff_z) * dz_inv))
+    if not zl <= zh:
+        raise ValueError("the laser patch holds no field slice (empty zeta range)")
+    zeta_lo, zeta_hi = int(zl), int(zh)
+    plo[2], phi[2] = (zeta_lo - 0.5) * dz + poff_z, (zeta_hi + 0.5) * dz + poff_z
+    if not (phi[0] > plo[0] and phi[1] > plo[1] and phi[2] > plo[2]):
+        raise ValueError("Laser box must have positive volume")
+    dxl, dyl = (phi[0] - plo[0]) / nxl, (phi[1] - plo[1]) / nyl
+    xoffl = 0.5 * (plo[0] + phi[0] - dxl * (nxl - 1))
+    yoffl = 0.5 * (plo[1] + phi[1] - dyl * (nyl - 1))
+    if deck.get("laser_solver", 0) == 2 and deck.get("dt", 0.0) != 0.0 and (nxl % 2 or nyl % 2):
+        raise ValueError("the multigrid envelope solver needs even lasers.n_cell (cell-centred hpmg box)")
+    return nxl, nyl, zeta_lo, zeta_hi, tuple(plo), tuple(phi), dxl, dyl, xoffl, yoffl
 
 
 def _ne_SI(kp_inv=10.0e-6):

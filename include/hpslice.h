@@ -417,6 +417,33 @@ int hps_engine_import_laser_slice (void* handle, int islice, const double* msg_d
 /* the same hand-off inside one process (several steps in flight on one device): straight from the engine that ran the
  * previous step, on the receiving engine's stream (make it wait for the sender's slice event first) */
 int hps_engine_import_laser_from (void* handle, int islice, void* src_engine);
+/* The laser envelope on a grid of its own (MultiLaser::MakeLaserGeometry, laser/MultiLaser.cpp:58-115):
+ * lasers.n_cell / patch_lo / patch_hi / interp_order; before the first hps_engine_begin_step.  NULL = the field grid's
+ * cells / the field box.  zeta is snapped to whole field cells -- zeta_lo = max(0, round((patch_lo_z - poff_z)/dz)),
+ * zeta_hi = min(nz - 1, round((patch_hi_z - poff_z)/dz)) -- so laser slice k sits at the z of field slice k; the envelope
+ * arrays are [zeta_hi - zeta_lo + 1][nyl][nxl], |a|^2 reaches the field slab and chi the laser grid through B-spline
+ * interpolation of interp_order 0 .. 3 (UpdateLaserAabs, InterpolateChi), chi outside the field box is that of the
+ * unperturbed plasma (SetInitialChi).  Field slices outside zeta_lo .. zeta_hi have aabs = 0 and no envelope advance.
+ * Refused: an empty zeta range, a box without volume, interp_order outside 0 .. 3 (HPS_ERR_ARG); odd n_cell with the
+ * multigrid envelope solver (HPS_ERR_UNSUPPORTED).  Without this call nothing changes. */
+int hps_engine_set_laser_grid (void* handle, const int* n_cell /*[2] or NULL*/, const double* patch_lo /*[3] or NULL*/,
+                               const double* patch_hi /*[3] or NULL*/, int interp_order);
+int hps_engine_laser_grid (void* handle, int* nxl, int* nyl, int* zeta_lo, int* zeta_hi);    /* as the engine holds it */
+int hps_engine_laser_chi (void* handle, double* out_host);    /* [nyl][nxl]: chi on the laser grid as the last envelope advance read it */
+/* With a laser grid hps_engine_laser_envelope returns [zeta_hi - zeta_lo + 1][nyl][nxl], the hand-off messages are
+ * [2][nyl][nxl] complex = 4 nxl nyl doubles, export / import of a slice outside zeta_lo .. zeta_hi do nothing and return
+ * HPS_OK, and hps_engine_import_laser_from needs equal laser grids.
+ *
+ * The two interpolations as operators of their own.  The laser grid: nxl x nyl cells of dxl x dyl, cell 0 at (xoffl, yoffl);
+ * geom: the slab's geometry; order = lasers.interp_order.
+ * hps_laser_interp_aabs: a_plane [nyl][nxl] complex on the device -> slab component c_aabs, guard cells included; laser cells
+ * outside the grid contribute nothing.
+ * hps_laser_interp_chi: slab component c_chi -> chi_out [nyl][nxl] for the laser cells on the field box shrunk by `shrink`
+ * cells (the engine: its guard width), chi_initial [nyl][nxl] elsewhere. */
+int hps_laser_interp_aabs (hps_slab slab, int c_aabs, const double* a_plane, int nxl, int nyl, double dxl, double dyl,
+                           double xoffl, double yoffl, hps_geom geom, int order, void* stream);
+int hps_laser_interp_chi (hps_slab slab, int c_chi, const double* chi_initial, double* chi_out, int nxl, int nyl, double dxl,
+                          double dyl, double xoffl, double yoffl, hps_geom geom, int shrink, int order, void* stream);
 /* accumulate the per-slice checksums (costs one reduction pass per slice; off by default) */
 int hps_engine_set_diagnostics (void* handle, int on);
 /* Field diagnostics (Fields::Copy, fields/Fields.cpp:413-533; geometry of Diagnostic::ResizeFDiagFAB,
