@@ -47,6 +47,11 @@ class Geom(C.Structure):
                [("plo", C.c_double * 2), ("phi", C.c_double * 2), ("bc", C.c_int), ("normalized", C.c_int)]
 
 
+class LaserPulse(C.Structure):      # hps_laser_pulse
+    _fields_ = [("a0", C.c_double), ("w0", C.c_double), ("L0", C.c_double), ("pos", C.c_double * 3), ("zfoc", C.c_double),
+                ("cep", C.c_double), ("propagation_angle_yz", C.c_double), ("pft_yz", C.c_double)]
+
+
 class Deck(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3),
@@ -195,6 +200,11 @@ _SIGS = {
     "hps_engine_set_laser_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int]),
     "hps_engine_laser_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hps_engine_laser_chi": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hps_engine_set_laser_pulses": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LaserPulse)]),
+    "hps_engine_add_laser_samples": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.c_double]),
+    "hps_engine_set_insitu_laser": (C.c_int, [C.c_void_p, C.c_int]),
+    "hps_engine_insitu_laser": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hps_laser_interp_aabs": (C.c_int, [Slab, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
                                         Geom, C.c_int, C.c_void_p]),
     "hps_laser_interp_chi": (C.c_int, [Slab, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,

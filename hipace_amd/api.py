@@ -532,6 +532,13 @@ class SliceEngine:
         if _decks.has_laser_grid(deck):
             self.set_laser_grid(deck.get("laser_n_cell"), deck.get("laser_patch_lo"), deck.get("laser_patch_hi"),
                                 deck.get("laser_interp_order", 1))
+        # several pulses, parser profiles, in-situ laser reductions (decks.LASER_PULSE_DEFAULT): a deck without these keys makes no call
+        if deck.get("lasers") is not None:
+            self.set_laser_pulses(deck["lasers"])
+        for fn in deck.get("laser_profiles", ()):
+            self.add_laser_profile(fn)
+        if deck.get("laser_insitu", 0):
+            self.set_insitu_laser(True)
         if fine_patch is None:
             fine_patch = deck.get("fine_patch")
         if fine_patch is not None:
@@ -621,6 +628,11 @@ class SliceEngine:
         lo = (C.c_double * 3)(*[float(v) for v in patch_lo]) if patch_lo is not None else None
         hi = (C.c_double * 3)(*[float(v) for v in patch_hi]) if patch_hi is not None else None
         check(_lib.lib().hps_engine_set_laser_grid(self._h, n, lo, hi, int(1 if interp_order is None else interp_order)))
+        # self.deck describes the grid the engine holds: laser_cell_centres and add_laser_profile go by it
+        self.deck.update(laser_n_cell=None if n_cell is None else tuple(int(v) for v in n_cell),
+                         laser_patch_lo=None if patch_lo is None else tuple(float(v) for v in patch_lo),
+                         laser_patch_hi=None if patch_hi is None else tuple(float(v) for v in patch_hi),
+                         laser_interp_order=int(1 if interp_order is None else interp_order))
 
     def laser_grid(self):
         """(nxl, nyl, zeta_lo, zeta_hi) as the engine holds them; without set_laser_grid (nx, ny, 0, nz - 1)"""
@@ -633,6 +645,86 @@ class SliceEngine:
         nxl, nyl, _, _ = self.laser_grid()
         out = np.empty((nyl, nxl), dtype=np.float64)
         check(_lib.lib().hps_engine_laser_chi(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_laser_pulses(self, pulses):
+        """lasers.names with init_type = gaussian: a list of dicts with the reference's keys a0, w0, L0 | tau, position_mean,
+        focal_distance, CEP, propagation_angle_yz, PFT_yz (decks.LASER_PULSE_DEFAULT) replaces the deck's own pulse; an empty
+        list leaves only the envelopes of add_laser_profile / add_laser_samples.  At most 8; before the first begin_step.  CEP
+        scales the pulse by e^CEP, as in the reference (MultiLaser.cpp:912)."""
+        c = _decks.SI["c"] if self.deck.get("si_units", 0) else 1.0
+        arr = (_lib.LaserPulse * max(len(pulses), 1))()
+        for q, pulse in enumerate(pulses):
+            a0, w0, L0, pos, zfoc, cep, angle, pft = _decks.laser_pulse(pulse, c)
+            arr[q] = _lib.LaserPulse(a0, w0, L0, (C.c_double * 3)(*pos), zfoc, cep, angle, pft)
+        check(_lib.lib().hps_engine_set_laser_pulses(self._h, len(pulses), arr))
+
+    def laser_cell_centres(self):
+        """x (nxl), y (nyl), z (nzl) of the laser grid's cells: decks.laser_cell_centres of self.deck, in which set_laser_grid
+        records the grid it gave the engine"""
+        x, y, z = _decks.laser_cell_centres(self.deck)
+        nxl, nyl, zlo, zhi = self.laser_grid()
+        if (x.size, y.size, z.size) != (nxl, nyl, zhi - zlo + 1):
+            raise RuntimeError(f"the engine's laser grid {(nxl, nyl, zhi - zlo + 1)} is not the deck's {(x.size, y.size, z.size)}")
+        return x, y, z
+
+    def add_laser_profile(self, fn):
+        """init_type = parser: fn(x, y, z) -> complex over numpy arrays, evaluated on the laser grid's cell centres on the host and
+        added to the envelope cell by cell (geometry 0)."""
+        x, y, z = self.laser_cell_centres()
+        X, Y, Z = np.broadcast_arrays(x[None, None, :], y[None, :, None], z[:, None, None])
+        data = np.empty(X.shape, dtype=np.complex128)
+        data[...] = fn(X, Y, Z)
+        self.add_laser_samples(0, data, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
+
+    def add_laser_samples(self, geometry, data, offset, spacing, unit=1.0):
+        """init_type = from_file: complex samples [extent0][extent1][extent2] in the geometry 0 (the laser grid itself), 1 | "xyt",
+        2 | "xyz" or 3 | "rt" ([modes][nt][nr]); offset, spacing per axis in the file's order (two values for rt); unit = unitSI.
+        Added to the envelope by the first begin_step, after the pulses, in the order given (hps_engine_add_laser_samples)."""
+        geometry = {"grid": 0, "xyt": 1, "xyz": 2, "rt": 3}.get(geometry, geometry)
+        if geometry not in (0, 1, 2, 3):
+            raise ValueError("laser samples: geometry must be 0, 'xyt', 'xyz' or 'rt'")
+        a = np.ascontiguousarray(data, dtype=np.complex128)
+        if a.ndim != 3:
+            raise ValueError("laser samples: data must have three axes")
+        off, sp = [float(v) for v in offset], [float(v) for v in spacing]
+        need = 2 if geometry == 3 else 3
+        if len(off) < need or len(sp) < need or len(off) > 3 or len(sp) > 3:
+            raise ValueError(f"laser samples: offset and spacing need {need} values")
+        off, sp = off + [0.0] * (3 - len(off)), sp + [1.0] * (3 - len(sp))
+        check(_lib.lib().hps_engine_add_laser_samples(self._h, int(geometry), a.ctypes.data_as(C.c_void_p), (C.c_long * 3)(*a.shape),
+                                                      (C.c_double * 3)(*off), (C.c_double * 3)(*sp), float(unit)))
+
+    def add_laser_file(self, path, iteration=0, name="laserEnvelope"):
+        """init_type = from_file: a lasy-layout openPMD file (openpmd_writer.read_laser); its wavelength must be the deck's."""
+        from . import openpmd_writer
+        geometry, data, offset, spacing, unit, lambda0 = openpmd_writer.read_laser(path, iteration, name)
+        mine = float(self.deck["laser_lambda0"])
+        if not abs(lambda0 - mine) <= 1.0e-12 * abs(mine):
+            raise ValueError(f"{path}: the file's wavelength {lambda0!r} is not the deck's laser_lambda0 {mine!r}, which all "
+                             "envelopes of an engine share")
+        self.add_laser_samples(geometry, data, offset, spacing, unit)
+
+    def set_insitu_laser(self, on=True):
+        """lasers.insitu_period: per-slice reductions of MultiLaser::InSituComputeDiags."""
+        check(_lib.lib().hps_engine_set_insitu_laser(self._h, int(on)))
+
+    INSITU_LASER_NAMES = ("max(|a|^2)", "[|a|^2]", "[|a|^2*x]", "[|a|^2*x*x]", "[|a|^2*y]", "[|a|^2*y*y]")
+
+    def insitu_laser_rows(self):
+        """the raw (8, nzl) rows of hps_engine_insitu_laser"""
+        _, _, zlo, zhi = self.laser_grid()
+        out = np.empty((8, zhi - zlo + 1), dtype=np.float64)
+        check(_lib.lib().hps_engine_insitu_laser(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def insitu_laser(self):
+        """-> dict under the reference's names (MultiLaser.cpp:1039-1052), one value per laser slice, "axis(a)" complex; "sum": the
+        per-step totals the reference writes as "integrated" (the maximum of max(|a|^2), the sums of the others)."""
+        rows = self.insitu_laser_rows()
+        out = {name: rows[q].copy() for q, name in enumerate(self.INSITU_LASER_NAMES)}
+        out["axis(a)"] = rows[6] + 1j * rows[7]
+        out["sum"] = {name: (rows[q].max() if q == 0 else rows[q].sum()) for q, name in enumerate(self.INSITU_LASER_NAMES)}
         return out
 
     def add_collision(self, species_a=0, species_b=0, coulomb_log=-1.0, seed=0):

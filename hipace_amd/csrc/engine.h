@@ -183,6 +183,12 @@ struct Engine {
     struct LaserGrid { bool set = false; int nx = 0, ny = 0, zlo = 0, zhi = -1, order = 1;
                        double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, dx = 0.0, dy = 0.0, xoff = 0.0, yoff = 0.0; } lgrid;
     int set_laser_grid (const int* n_cell, const double* patch_lo, const double* patch_hi, int interp_order);
+    // the initial envelope: hps_engine_set_laser_pulses (pulses_set: the list replaces the deck's pulse) and
+    // hps_engine_add_laser_samples (host copies, uploaded, added and freed by the first begin_step)
+    struct LaserSamples { int geometry = 0; long extent[3] = {0, 0, 0}; double offset[3] = {0, 0, 0}, spacing[3] = {0, 0, 0}, unit = 1.0;
+                          std::vector<double> data; };
+    bool laser_pulses_set = false; std::vector<hps_laser_pulse> laser_pulses; std::vector<LaserSamples> laser_samples;
+    bool insitu_laser = false;       // hps_engine_set_insitu_laser; the buffer lives with the laser grid (LaserState)
     bool laser_has_slice (int islice) const { return !lgrid.set || (islice >= lgrid.zlo && islice <= lgrid.zhi); }      // UseLaser(islice)
     // The envelope's advance of a slice needs chi of the slice and the envelope of the slices before it -- nothing else
     // of the slice needs its result.  It runs on a stream of its own beside the explicit deposition, the Bx/By multigrid
@@ -267,6 +273,10 @@ int laser_set_import (Engine& E, int on, int step);
 int laser_export_slice (Engine& E, int islice, double* msg_dev);
 int laser_import_slice (Engine& E, int islice, const double* msg_dev);
 int laser_import_from (Engine& E, int islice, Engine& src);
+int laser_check_samples (Engine& E, const Engine::LaserSamples& S);          // what hps_engine_add_laser_samples refuses
+int laser_set_insitu (Engine& E, int on);                                    // the [8][nzl] in-situ buffer and its scratch
+int laser_clear_insitu (Engine& E);
+int laser_copy_insitu (Engine& E, double* out_host);
 int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz);      // beam.hip
 int beam_push_moving (Engine& E, int islice);
 int beam_push_slice (Engine& E, int islice, int p, long bound);

@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <new>
 
 // the engines' stream pool (see create_engine_stream)
 namespace {
@@ -900,6 +901,11 @@ int Engine::begin_step ()
     // (PlasmaParticleContainer.cpp:167-169)
     HPS_REQUIRE(fine_patch_set == (fine_ppc[0] > 0 || ion_fine_ppc[0] > 0),
                 "hps_engine_begin_step: both fine_ppc (hps_engine_set_plasma_init) and the fine patch (hps_engine_set_fine_patch) must be given to use the fine plasma patch");
+    HPS_REQUIRE(!(laser && laser_pulses_set && laser_pulses.empty() && laser_samples.empty() && !step_begun),
+                "hps_engine_begin_step: hps_engine_set_laser_pulses with n = 0 needs at least one hps_engine_add_laser_samples");
+    // hps_engine_set_laser_grid may have come after hps_engine_add_laser_samples: checked against the grid as it is now, while
+    // a refusal still leaves the engine as it was
+    if (laser && !step_begun) { for (const LaserSamples& S : laser_samples) { if (int e = laser_check_samples(*this, S)) return e; } }
     if (int e = setup_tiling()) return e;
     step_begun = true;
     if (moving && steps_begun > 0) {
@@ -942,6 +948,7 @@ int Engine::begin_step ()
     if (d_insitu_pl) HPS_HIP_CHECK(hipMemsetAsync(d_insitu_pl, 0, (size_t)15*d.nz*sizeof(double), st));
     if (d_insitu_bm) HPS_HIP_CHECK(hipMemsetAsync(d_insitu_bm, 0, (size_t)23*d.nz*sizeof(double), st));
     if (d_insitu) HPS_HIP_CHECK(hipMemsetAsync(d_insitu, 0, (size_t)10*d.nz*sizeof(double), st));
+    if (insitu_laser && laser) { if (int e = laser_clear_insitu(*this)) return e; }
     if (d_fd) HPS_HIP_CHECK(hipMemsetAsync(d_fd, 0, fd_comps.size()*fd_cells()*sizeof(double), st));
     step_index = (next_step >= 0) ? next_step : step_index + 1;      // Hipace::m_physical_time (PlasmaParticleContainerInit.cpp:90)
     next_step = -1;
@@ -2616,6 +2623,66 @@ extern "C" int hps_engine_laser_grid (void* h, int* nxl, int* nyl, int* zeta_lo,
     if (zeta_lo) *zeta_lo = E->lgrid.set ? E->lgrid.zlo : 0;
     if (zeta_hi) *zeta_hi = E->lgrid.set ? E->lgrid.zhi : E->d.nz - 1;
     return HPS_OK;
+}
+// several Gaussian pulses, envelopes from samples, in-situ reductions
+extern "C" int hps_engine_set_laser_pulses (void* h, int n, const hps_laser_pulse* pulses)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_set_laser_pulses: the deck has no laser (laser_on)");
+    HPS_REQUIRE(!E->step_begun, "hps_engine_set_laser_pulses: must be called before the first hps_engine_begin_step");
+    HPS_REQUIRE(n >= 0 && n <= 8, "hps_engine_set_laser_pulses: 0 to 8 pulses");
+    HPS_REQUIRE(n == 0 || pulses, "hps_engine_set_laser_pulses: null pulse list");
+    for (int q = 0; q < n; ++q) {
+        const hps_laser_pulse& P = pulses[q];
+        HPS_REQUIRE(P.w0 > 0.0 && P.L0 > 0.0, "hps_engine_set_laser_pulses: w0 and L0 must be positive");
+        const double v[10] = {P.a0, P.w0, P.L0, P.pos[0], P.pos[1], P.pos[2], P.zfoc, P.cep, P.propagation_angle_yz, P.pft_yz};
+        for (double x : v) HPS_REQUIRE(std::isfinite(x), "hps_engine_set_laser_pulses: the pulse parameters must be finite");
+    }
+    E->laser_pulses.assign(pulses, pulses + n);
+    E->laser_pulses_set = true;
+    return HPS_OK;
+}
+extern "C" int hps_engine_add_laser_samples (void* h, int geometry, const double* data_host, const long extent[3], const double offset[3],
+                                             const double spacing[3], double unit)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_add_laser_samples: the deck has no laser (laser_on)");
+    HPS_REQUIRE(!E->step_begun, "hps_engine_add_laser_samples: must be called before the first hps_engine_begin_step");
+    HPS_REQUIRE(geometry >= 0 && geometry <= 3, "hps_engine_add_laser_samples: geometry must be 0 (laser grid), 1 (xyt), 2 (xyz) or 3 (rt)");
+    HPS_REQUIRE(extent && offset && spacing, "hps_engine_add_laser_samples: null argument");
+    HPS_REQUIRE(E->laser_samples.size() < 4, "hps_engine_add_laser_samples: at most 4 sets of samples");
+    HPS_REQUIRE(std::isfinite(unit), "hps_engine_add_laser_samples: unit must be finite");
+    Engine::LaserSamples S;
+    S.geometry = geometry; S.unit = unit;
+    for (int q = 0; q < 3; ++q) {
+        HPS_REQUIRE(extent[q] > 0 && extent[q] < (1L << 30), "hps_engine_add_laser_samples: the extents must be positive");
+        S.extent[q] = extent[q]; S.offset[q] = offset[q]; S.spacing[q] = spacing[q];
+    }
+    // each extent is below 2^30, so the product of two fits a long; the product of all three is held below 2^31
+    HPS_REQUIRE(extent[0]*extent[1] <= ((1L << 31) - 1)/extent[2], "hps_engine_add_laser_samples: more than 2^31 - 1 samples in a set");
+    HPS_REQUIRE(data_host, "hps_engine_add_laser_samples: null argument");
+    if (int e = laser_check_samples(*E, S)) return e;
+    const size_t n = (size_t)extent[0]*extent[1]*extent[2];
+    // no host memory for the copy is no fault of the arguments: the code of a failed device allocation
+    try { S.data.assign(data_host, data_host + 2*n); E->laser_samples.push_back(std::move(S)); }
+    catch (const std::exception&) { set_error("hps_engine_add_laser_samples: no host memory for the copy of the samples"); return HPS_ERR_HIP; }
+    return HPS_OK;
+}
+extern "C" int hps_engine_set_insitu_laser (void* h, int on)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_set_insitu_laser: the deck has no laser (laser_on)");
+    if ((on != 0) == E->insitu_laser) return HPS_OK;      // on -> on keeps the rows collected so far
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    if (int e = laser_set_insitu(*E, on)) return e;       // (a failed allocation leaves it off)
+    E->insitu_laser = (on != 0);
+    return HPS_OK;
+}
+extern "C" int hps_engine_insitu_laser (void* h, double* out)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser && E->insitu_laser && out, "hps_engine_insitu_laser: not switched on");
+    return laser_copy_insitu(*E, out);
 }
 extern "C" int hps_engine_laser_chi (void* h, double* out_host)
 {

@@ -5,6 +5,8 @@
 // carrier-envelope phase, no propagation angle, no pulse-front tilt), UpdateLaserAabs :214-291, AdvanceSliceFFT
 // :609-801 (Benedetti et al. 2017 scheme with the on-axis phase terms of lasers.use_phase), and the hand-over of the
 // time levels between two steps, utils/MultiBuffer.cpp:840-852, 913-925.
+// Several pulses with CEP, propagation angle and pulse-front tilt, envelopes from samples (Laser.cpp:117-341) and the in-situ
+// reductions (InSituComputeDiags :923-1003) are DESIGN 8k: k_laser_init_pulses, k_laser_add, k_laser_resample, k_insitu_laser.
 //
 // Layout: three complex arrays [nz][ny][nx] (a at time steps n-1, n, n+1), 16 B per cell, resident in HBM for the whole
 // run -- 1024^2 x 2048 slices are 3 x 34 GB, which is what 288 GB per GPU are for; the reference streams them through
@@ -41,6 +43,7 @@ struct LaserState {
     // lasers.solver_type = multigrid (multigrid2.hip): planar [2][ny][nx] solution (kept from slice to slice: the next
     // solve's initial guess, as np1j00 in the reference) and right-hand side, Re of the coefficient, its Im (one double)
     void* mg = nullptr; double *mg_sol = nullptr, *mg_rhs = nullptr, *mg_acf_real = nullptr, *mg_acf_imag = nullptr; long mg_vcycles = 0;
+    double *insitu = nullptr, *insitu_part = nullptr;              // hps_engine_set_insitu_laser: [8][nz] rows, [INSITU_GROUPS][8] partial rows
     int steps = 0; bool initialised = false;
     bool import_mode = false;        // ring pipeline: a_n, a_{n-1} of the coming step arrive through laser_import_slice
     ~LaserState () {
@@ -51,6 +54,7 @@ struct LaserState {
         if (mg) mg2_destroy_internal(mg);
         (void)hipFree(mg_sol); (void)hipFree(mg_rhs); (void)hipFree(mg_acf_real); (void)hipFree(mg_acf_imag);
         (void)hipFree(chi); (void)hipFree(chi_initial);
+        (void)hipFree(insitu); (void)hipFree(insitu_part);
     }
 };
 
@@ -80,6 +84,175 @@ void k_laser_init (double2* a, int nx, int ny, int nz, LaserPars L, double dx, d
     double sn, cs; sincos(ei, &sn, &cs);
     const double ar = L.a0*dr, ai = L.a0*di;                     // prefactor a0/D
     a[((long)k*ny + j)*nx + i] = make_double2(m*(ar*cs - ai*sn), m*(ar*sn + ai*cs));
+}
+
+// The same for a list of pulses (hps_engine_set_laser_pulses), each with carrier-envelope phase, propagation angle and pulse-front
+// tilt, literally InitLaserSlice :876-915: rotation of (y, z) by rot = propagation_angle_yz + (PFT_yz - pi/2), z0 cos(angle) in
+// the diffraction factor and the factor exp(i yp k0 angle + CEP) -- CEP is added to the exponent as a real number there, so it
+// scales the pulse by e^CEP; restated, not corrected.  One exp and one sincos per pulse and cell; the list is a kernel argument.
+struct LaserPulse { double a0, w0, L0, x0, y0, z0, zfoc, cep, angle, cos_angle, cos_rot, sin_rot; };
+struct LaserPulseList { int n; LaserPulse p[8]; };
+
+__global__ __launch_bounds__(256)
+void k_laser_init_pulses (double2* a, int nx, int ny, int nz, LaserPulseList P, double k0, double dx, double dy, double dz, double xoff, double yoff,
+                          double zoff)
+{
+    const int i = blockIdx.x*blockDim.x + threadIdx.x;
+    const int j = blockIdx.y, k = blockIdx.z;
+    if (i >= nx) return;
+    double sr = 0.0, si = 0.0;
+    for (int q = 0; q < P.n; ++q) {
+        const LaserPulse& L = P.p[q];
+        const double x = i*dx + xoff - L.x0, y = j*dy + yoff - L.y0, z = k*dz + zoff - L.z0;
+        const double yp = L.cos_rot*y - L.sin_rot*z, zp = L.sin_rot*y + L.cos_rot*z;
+        const double qd = (zp - L.zfoc + L.z0*L.cos_angle)*2.0/(k0*L.w0*L.w0);       // diffract_factor D = 1 + i qd
+        const double den = 1.0 + qd*qd;
+        const double dr = 1.0/den, di = -qd/den;                     // 1/D
+        const double wr = dr/(L.w0*L.w0), wi = di/(L.w0*L.w0);       // 1/(w0^2 D)
+        const double r2 = x*x + yp*yp;
+        const double er = -r2*wr - zp*zp/(L.L0*L.L0) + L.cep, ei = -r2*wi + yp*k0*L.angle;   // exponent
+        const double m = exp(er);
+        double sn, cs; sincos(ei, &sn, &cs);
+        const double ar = L.a0*dr, ai = L.a0*di;                     // prefactor a0/D
+        sr += m*(ar*cs - ai*sn); si += m*(ar*sn + ai*cs);
+    }
+    a[((long)k*ny + j)*nx + i] = make_double2(sr, si);
+}
+
+// samples on the laser grid itself (geometry 0, the reference's parser type :856-874): a plain add
+__global__ __launch_bounds__(256)
+void k_laser_add (double2* __restrict__ a, const double2* __restrict__ s, long n)
+{
+    const long o = (long)blockIdx.x*blockDim.x + threadIdx.x;
+    if (o < n) { const double2 v = a[o], w = s[o]; a[o] = make_double2(v.x + w.x, v.y + w.y); }
+}
+
+// order-1 shape factor of a sample axis with n samples (compute_shape_factor<1>): false = the stencil lies wholly outside
+// 0 .. n-1 (also keeps floor() in int range)
+__device__ __forceinline__ bool sample_stencil (double mid, long n, int* cell, double* s)
+{
+    if (!(mid > -2.0 && mid < (double)n + 1.0)) return false;
+    *cell = shape_weights<1>(mid, s);
+    return true;
+}
+
+// Envelope from a file's samples (Laser::GetEnvelopeFromFile, Laser.cpp:177-336), one thread per laser cell, added to a.
+// geometry 1 "xyt": data [nt][ny][nx], 2 "xyz": [nz][ny][nx], 3 "rt": [modes][nt][nr]; off = position of sample 0 per axis in
+// the file's order (t of xyt and rt starts at the laser's last slice: tmid = (zmax - z)/c/spacing[0]); samples outside the
+// extent count as zero.  The sums run in the reference's order: t or z outermost, then y, then x; per (t, r) mode 0, then cos
+// and sin part of m = 1 .. modes/2.
+struct LaserFile { int geometry; int e0, e1, e2; double off0, off1, off2, sp0, sp1, sp2, unit; };
+
+__global__ __launch_bounds__(256)
+void k_laser_resample (double2* __restrict__ a, int nx, int ny, int nz, const double2* __restrict__ data, LaserFile F, double clight,
+                       double dx, double dy, double dz, double xoff, double yoff, double zoff)
+{
+    const int i = blockIdx.x*blockDim.x + threadIdx.x;
+    const int j = blockIdx.y, k = blockIdx.z;
+    if (i >= nx) return;
+    const double x = i*dx + xoff, y = j*dy + yoff, z = k*dz + zoff, zmax = (nz - 1)*dz + zoff;
+    double vr = 0.0, vi = 0.0;
+    if (F.geometry == 3) {
+        const double r = sqrt(x*x + y*y), theta = atan2(y, x);
+        double sr[2], st[2]; int ic, kc;
+        if (sample_stencil((r - F.off1)/F.sp1, F.e2, &ic, sr) && sample_stencil((zmax - z)/clight/F.sp0, F.e1, &kc, st)) {
+            for (int it = 0; it <= 1; ++it)
+                for (int ir = 0; ir <= 1; ++ir) {
+                    const int cr = ic + ir, ct = kc + it;
+                    if (cr < 0 || cr >= F.e2 || ct < 0 || ct >= F.e1) continue;       // (cr < 0 is refused on the host)
+                    const long o = (long)ct*F.e2 + cr, mode = (long)F.e1*F.e2;
+                    const double w = sr[ir]*st[it];
+                    const double2 d0 = data[o];
+                    vr += w*(d0.x*F.unit); vi += w*(d0.y*F.unit);
+                    for (int im = 1; im <= F.e0/2; ++im) {
+                        double sn, cs; sincos(im*theta, &sn, &cs);
+                        const double2 dc = data[(2*im - 1)*mode + o], ds = data[2*im*mode + o];
+                        vr += w*cs*(dc.x*F.unit); vi += w*cs*(dc.y*F.unit);
+                        vr += w*sn*(ds.x*F.unit); vi += w*sn*(ds.y*F.unit);
+                    }
+                }
+        }
+    } else {
+        const double zmid = (F.geometry == 1) ? (zmax - z)/clight/F.sp0 : (z - F.off0)/F.sp0;
+        double sx[2], sy[2], sz[2]; int ic, jc, kc;
+        if (sample_stencil((x - F.off2)/F.sp2, F.e2, &ic, sx) && sample_stencil((y - F.off1)/F.sp1, F.e1, &jc, sy) &&
+            sample_stencil(zmid, F.e0, &kc, sz)) {
+            for (int iz = 0; iz <= 1; ++iz)
+                for (int iy = 0; iy <= 1; ++iy)
+                    for (int ix = 0; ix <= 1; ++ix) {
+                        const int cx = ic + ix, cy = jc + iy, cz = kc + iz;
+                        if (cx < 0 || cx >= F.e2 || cy < 0 || cy >= F.e1 || cz < 0 || cz >= F.e0) continue;
+                        const double2 d = data[((long)cz*F.e1 + cy)*F.e2 + cx];
+                        const double w = sx[ix]*sy[iy]*sz[iz];
+                        vr += w*(d.x*F.unit); vi += w*(d.y*F.unit);
+                    }
+        }
+    }
+    const long o = ((long)k*ny + j)*nx + i;
+    const double2 v = a[o];
+    a[o] = make_double2(v.x + vr, v.y + vi);
+}
+
+// In-situ reductions of one laser plane (InSituComputeDiags :923-1003): max |a|^2, the sums of |a|^2 {1, x, x^2, y, y^2} and of a
+// over the middle cells.  Eight values per lane over a grid-stride loop, through the wave with __shfl_xor, through LDS, one
+// partial row per workgroup; k_insitu_laser_fold adds the rows in index order.  No floating-point atomics: the launch shape
+// depends on the plane's size alone, so the result is a function of the plane, bit for bit.
+constexpr int INSITU_GROUPS = 32;
+
+__global__ __launch_bounds__(256)
+void k_insitu_laser (const double2* __restrict__ a, int nx, int ny, double dx, double dy, double xoff, double yoff, double* __restrict__ part)
+{
+    const int xmid_lo = (nx - 1)/2, xmid_hi = nx/2, ymid_lo = (ny - 1)/2, ymid_hi = ny/2;
+    const long plane = (long)nx*ny;
+    double v[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // a lane takes the cells o, o + S, o + 2 S, ... in this order, four loads in flight at a time; (i, j) of the next cell by
+    // carry from (S mod nx, S div nx) instead of a division per cell
+    const long S = (long)gridDim.x*blockDim.x;
+    const int di = (int)(S % nx), dj = (int)(S/nx);
+    long o = (long)blockIdx.x*blockDim.x + threadIdx.x;
+    int j = (int)(o/nx), i = (int)(o - (long)j*nx);
+    for (; o < plane; o += 4*S) {
+        double2 e[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) e[u] = (o + u*S < plane) ? a[o + u*S] : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (o + u*S >= plane) break;
+            const double s = e[u].x*e[u].x + e[u].y*e[u].y;
+            const double x = i*dx + xoff, y = j*dy + yoff;
+            const bool on_axis = (i == xmid_lo || i == xmid_hi) && (j == ymid_lo || j == ymid_hi);
+            v[0] = s > v[0] ? s : v[0];
+            v[1] += s; v[2] += s*x; v[3] += s*x*x; v[4] += s*y; v[5] += s*y*y;
+            v[6] += on_axis ? e[u].x : 0.0; v[7] += on_axis ? e[u].y : 0.0;
+            i += di; j += dj;
+            if (i >= nx) { i -= nx; ++j; }
+        }
+    }
+    for (int m = 32; m > 0; m >>= 1) {
+        const double w = __shfl_xor(v[0], m);
+        v[0] = w > v[0] ? w : v[0];
+        for (int q = 1; q < 8; ++q) v[q] += __shfl_xor(v[q], m);
+    }
+    __shared__ double wave[4][8];
+    if ((threadIdx.x & 63) == 0) for (int q = 0; q < 8; ++q) wave[threadIdx.x >> 6][q] = v[q];
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const int q = threadIdx.x;
+        double r = wave[0][q];
+        for (int w = 1; w < 4; ++w) r = (q == 0) ? (wave[w][q] > r ? wave[w][q] : r) : r + wave[w][q];
+        part[(long)blockIdx.x*8 + q] = r;
+    }
+}
+
+// one wave: lane q < 8 folds row q of the partials in index order and writes column `col` of out[8][ncol]
+__global__ __launch_bounds__(64)
+void k_insitu_laser_fold (const double* __restrict__ part, int groups, double dxdydz, double mid_factor, double* __restrict__ out, int ncol, int col)
+{
+    const int q = threadIdx.x;
+    if (q >= 8) return;
+    double r = part[q];
+    for (int g = 1; g < groups; ++g) { const double w = part[(long)g*8 + q]; r = (q == 0) ? (w > r ? w : r) : r + w; }
+    out[(long)q*ncol + col] = (q == 0) ? r : (q < 6 ? r*dxdydz : r*mid_factor);
 }
 
 // UpdateLaserAabs (:214-291): aabs = |a_n|^2 on the valid cells, 0 in the guard cells; optionally sum |a_n|
@@ -386,12 +559,80 @@ int laser_create (Engine& E)
         }
         rocfft_execution_info_set_stream(L->info, E.laser_stream());
     }
+    if (E.insitu_laser) {                                      // (the grid was set after the switch)
+        if (int e = laser_set_insitu(E, 1)) { E.insitu_laser = false; return e; }
+    }
     return HPS_OK;
 }
 
 void laser_destroy (Engine& E) { delete E.laser; E.laser = nullptr; }
 
 void laser_sizes (Engine& E, int* nx, int* ny, int* nz) { *nx = E.laser->nx; *ny = E.laser->ny; *nz = E.laser->nz; }
+
+// what hps_engine_add_laser_samples refuses beyond its own argument checks (needs the laser grid: checked again at the top of
+// the first begin_step, since hps_engine_set_laser_grid may have come in between)
+int laser_check_samples (Engine& E, const Engine::LaserSamples& S)
+{
+    LaserState* L = E.laser;
+    for (int q = 0; q < (S.geometry == 3 ? 2 : 3); ++q)
+        HPS_REQUIRE(S.geometry == 0 || (S.spacing[q] > 0.0 && std::isfinite(S.spacing[q]) && std::isfinite(S.offset[q])),
+                    "hps_engine_add_laser_samples: the spacings must be positive and the offsets finite");
+    if (S.geometry == 0)
+        HPS_REQUIRE(S.extent[0] == L->nz && S.extent[1] == L->ny && S.extent[2] == L->nx,
+                    "hps_engine_add_laser_samples: geometry 0 needs the extents of the laser grid, [nzl][nyl][nxl]");
+    if (S.geometry == 3) {
+        HPS_REQUIRE(S.extent[0] % 2 == 1, "hps_engine_add_laser_samples: rt needs an odd extent[0] (mode 0 and a cos and a sin part per further mode)");
+        // the grid's smallest r: the cell nearest the axis in x and in y (Laser.cpp:303 asserts i_cell + ir >= 0)
+        double ax = INFINITY, ay = INFINITY;
+        for (int i = 0; i < L->nx; ++i) ax = std::min(ax, std::fabs(i*L->dx + L->xoff));
+        for (int j = 0; j < L->ny; ++j) ay = std::min(ay, std::fabs(j*L->dy + L->yoff));
+        const double rmid = (std::sqrt(ax*ax + ay*ay) - S.offset[1])/S.spacing[1];
+        HPS_REQUIRE(std::floor(rmid) >= 0.0, "hps_engine_add_laser_samples: rt: a laser cell would reach a sample index < 0 in r (r < 0: offset[1] lies beyond the grid's smallest r)");
+    }
+    return HPS_OK;
+}
+
+// the initial envelope from the pulse list (or the deck's pulse) and the sample sets, in that order (InitLaserSlice :828-918)
+static int laser_init_from_lists (Engine& E, double zoff)
+{
+    LaserState* L = E.laser;
+    const hps_deck& d = E.d;
+    const double pi = 3.14159265358979323846, k0 = 2.0*pi/d.laser_lambda0;
+    const size_t tot = (size_t)L->nx*L->ny*L->nz;
+    const dim3 grid(ceil_div(L->nx, 256), L->ny, L->nz), block(256);
+    LaserPulseList P; P.n = 0;
+    auto push = [&] (const hps_laser_pulse& p) {
+        const double rot = p.propagation_angle_yz + (p.pft_yz - pi/2.0);
+        P.p[P.n++] = LaserPulse{p.a0, p.w0, p.L0, p.pos[0], p.pos[1], p.pos[2], p.zfoc, p.cep, p.propagation_angle_yz,
+                                std::cos(p.propagation_angle_yz), std::cos(rot), std::sin(rot)};
+    };
+    if (E.laser_pulses_set) { for (const hps_laser_pulse& p : E.laser_pulses) push(p); }
+    else push(hps_laser_pulse{d.laser_a0, d.laser_w0, d.laser_L0, {d.laser_pos[0], d.laser_pos[1], d.laser_pos[2]}, d.laser_zfoc, 0.0, 0.0, pi/2.0});
+    hipLaunchKernelGGL(k_laser_init_pulses, grid, block, 0, E.st, L->n00, L->nx, L->ny, L->nz, P, k0, L->dx, L->dy, E.gm.dz, L->xoff, L->yoff, zoff);
+    HPS_HIP_CHECK(hipGetLastError());
+    for (const Engine::LaserSamples& S : E.laser_samples) {        // (checked against this grid by Engine::begin_step)
+        const size_t n = (size_t)S.extent[0]*S.extent[1]*S.extent[2];
+        double2* dev = nullptr;
+        HPS_HIP_CHECK(hipMalloc(&dev, n*sizeof(double2)));
+        hipError_t err = hipMemcpy(dev, S.data.data(), n*sizeof(double2), hipMemcpyHostToDevice);
+        if (err == hipSuccess) {
+            if (S.geometry == 0) {
+                hipLaunchKernelGGL(k_laser_add, dim3((unsigned)ceil_div((long)tot, 256)), block, 0, E.st, L->n00, dev, (long)tot);
+            } else {
+                const LaserFile F{S.geometry, (int)S.extent[0], (int)S.extent[1], (int)S.extent[2], S.offset[0], S.offset[1], S.offset[2],
+                                  S.spacing[0], S.spacing[1], S.spacing[2], S.unit};
+                hipLaunchKernelGGL(k_laser_resample, grid, block, 0, E.st, L->n00, L->nx, L->ny, L->nz, dev, F, E.gm.c, L->dx, L->dy, E.gm.dz,
+                                   L->xoff, L->yoff, zoff);
+            }
+            err = hipGetLastError();
+            if (err == hipSuccess) err = hipStreamSynchronize(E.st);
+        }
+        (void)hipFree(dev);
+        HPS_HIP_CHECK(err);
+    }
+    E.laser_samples.clear(); E.laser_samples.shrink_to_fit();
+    return HPS_OK;
+}
 
 // start of a time step: the first one evaluates the Gaussian on every slice, later ones hand the time levels on
 // (a_{n+1} -> a_n -> a_{n-1}; MultiBuffer.cpp:840-852, 913-925)
@@ -401,11 +642,14 @@ int laser_begin_step (Engine& E)
     const hps_deck& d = E.d;
     if (L->import_mode) {
         L->initialised = true;       // levels are filled slice by slice; the driver has set the step index
+        E.laser_samples.clear();     // (the initial envelope is the first stage's business)
     } else if (!L->initialised) {
         // a laser slice with global index k sits at the z of field slice k (the patch's z limits are snapped to whole field cells)
         const double zoff = 0.5*(d.lo[2] + d.hi[2] - E.gm.dz*(d.nz - 1)) + L->zlo*E.gm.dz;
-        hipLaunchKernelGGL(k_laser_init, dim3(ceil_div(L->nx, 256), L->ny, L->nz), dim3(256), 0, E.st, L->n00, L->nx, L->ny, L->nz, laser_pars(d),
-                           L->dx, L->dy, E.gm.dz, L->xoff, L->yoff, zoff);
+        if (!E.laser_pulses_set && E.laser_samples.empty()) {
+            hipLaunchKernelGGL(k_laser_init, dim3(ceil_div(L->nx, 256), L->ny, L->nz), dim3(256), 0, E.st, L->n00, L->nx, L->ny, L->nz, laser_pars(d),
+                               L->dx, L->dy, E.gm.dz, L->xoff, L->yoff, zoff);
+        } else if (int e = laser_init_from_lists(E, zoff)) return e;
         L->initialised = true; L->steps = 0;
     } else if (L->np1) {
         double2* old = L->nm1; L->nm1 = L->n00; L->n00 = L->np1; L->np1 = old;
@@ -471,10 +715,26 @@ static int launch_interp_chi (SlabView f, int c_chi, const double* chi_initial, 
     return HPS_OK;
 }
 
+// InSituComputeDiags of the plane a_n of a slice (column k of the [8][nz] rows), on the engine's stream
+static int launch_insitu (Engine& E, const double2* a, int k)
+{
+    LaserState* L = E.laser;
+    const long plane = (long)L->nx*L->ny;
+    const int groups = (int)std::min<long>(ceil_div(plane, 256), INSITU_GROUPS);
+    const double mid_factor = (L->nx % 2 ? 1.0 : 0.5)*(L->ny % 2 ? 1.0 : 0.5);
+    hipLaunchKernelGGL(k_insitu_laser, dim3(groups), dim3(256), 0, E.st, a, L->nx, L->ny, L->dx, L->dy, L->xoff, L->yoff, L->insitu_part);
+    hipLaunchKernelGGL(k_insitu_laser_fold, dim3(1), dim3(64), 0, E.st, L->insitu_part, groups, L->dx*L->dy*E.gm.dz, mid_factor, L->insitu, L->nz, k);
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
 int laser_update_aabs (Engine& E, int islice, double* sum_abs)
 {
     LaserState* L = E.laser;
     SlabView f(E.slab);
+    if (L->insitu && E.laser_has_slice(islice)) {
+        if (int e = launch_insitu(E, L->n00 + (size_t)(islice - L->zlo)*L->nx*L->ny, islice - L->zlo)) return e;
+    }
     if (!L->grid) {
         hipLaunchKernelGGL(k_laser_aabs, dim3(ceil_div(E.slab.jstride, 256), E.d.ny + 2*E.g), dim3(256), 0, E.st, f, E.c_aabs,
                            L->n00 + (size_t)islice*L->nx*L->ny, sum_abs);
@@ -576,6 +836,36 @@ int laser_import_from (Engine& E, int islice, Engine& src)
     // a_n -> a_{n-1} first: with one stage in flight source and destination are the same engine
     if (L->nm1) HPS_HIP_CHECK(hipMemcpyAsync(L->nm1 + k*plane, P->n00 + k*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
     if (newest != L->n00) HPS_HIP_CHECK(hipMemcpyAsync(L->n00 + k*plane, newest + k*plane, plane*sizeof(double2), hipMemcpyDeviceToDevice, E.st));
+    return HPS_OK;
+}
+
+int laser_set_insitu (Engine& E, int on)
+{
+    LaserState* L = E.laser;
+    (void)hipFree(L->insitu); (void)hipFree(L->insitu_part); L->insitu = L->insitu_part = nullptr;
+    if (!on) return HPS_OK;
+    hipError_t err = hipMalloc(&L->insitu, (size_t)8*L->nz*sizeof(double));
+    if (err == hipSuccess) err = hipMemset(L->insitu, 0, (size_t)8*L->nz*sizeof(double));
+    if (err == hipSuccess) err = hipMalloc(&L->insitu_part, (size_t)8*INSITU_GROUPS*sizeof(double));
+    if (err == hipSuccess) err = hipMemset(L->insitu_part, 0, (size_t)8*INSITU_GROUPS*sizeof(double));
+    if (err != hipSuccess) {       // both or neither: launch_insitu goes by L->insitu
+        (void)hipFree(L->insitu); (void)hipFree(L->insitu_part); L->insitu = L->insitu_part = nullptr;
+    }
+    HPS_HIP_CHECK(err);
+    return HPS_OK;
+}
+int laser_clear_insitu (Engine& E)
+{
+    LaserState* L = E.laser;
+    if (L->insitu) HPS_HIP_CHECK(hipMemsetAsync(L->insitu, 0, (size_t)8*L->nz*sizeof(double), E.st));
+    return HPS_OK;
+}
+int laser_copy_insitu (Engine& E, double* out_host)
+{
+    LaserState* L = E.laser;
+    HPS_REQUIRE(L->insitu, "hps_engine_insitu_laser: not switched on");
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));
+    HPS_HIP_CHECK(hipMemcpy(out_host, L->insitu, (size_t)8*L->nz*sizeof(double), hipMemcpyDeviceToHost));
     return HPS_OK;
 }
 

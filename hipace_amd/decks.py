@@ -328,6 +328,57 @@ def has_laser_grid(deck):
     return any(deck.get(k) is not None for k in ("laser_n_cell", "laser_patch_lo", "laser_patch_hi")) or "laser_interp_order" in deck
 
 
+# One Gaussian pulse of the deck key "lasers" (a list of such dicts; Laser.H:32-45, Laser.cpp:33-47): the reference's names and
+# defaults.  Exactly one of L0 and tau is given (L0 = tau c); PFT_yz = pi/2 is no pulse-front tilt.  CEP enters the reference's
+# exponent as a real number (MultiLaser.cpp:912): it scales the pulse by e^CEP, and so it does here.  "lasers" replaces the
+# deck's own pulse (laser_a0 ...; laser_lambda0 stays shared); "laser_profiles" is a list of callables f(x, y, z) -> complex
+# (init_type = parser) added on top; "laser_insitu" switches the in-situ reductions on.  A deck without these keys makes no call.
+LASER_PULSE_DEFAULT = dict(a0=0.0, w0=0.0, L0=None, tau=None, position_mean=(0.0, 0.0, 0.0), focal_distance=0.0, CEP=0.0,
+                           propagation_angle_yz=0.0, PFT_yz=math.pi / 2.0)
+
+
+def laser_pulse(pulse, c=1.0):
+    """A pulse dict with the defaults filled in and tau turned into L0 -> (a0, w0, L0, position_mean, focal_distance, CEP,
+    propagation_angle_yz, PFT_yz).  ValueError: an unknown key, both or neither of L0 and tau, w0 or L0 not positive."""
+    unknown = set(pulse) - set(LASER_PULSE_DEFAULT)
+    if unknown:
+        raise ValueError(f"unknown laser pulse keys {sorted(unknown)}")
+    p = dict(LASER_PULSE_DEFAULT, **pulse)
+    if (p["L0"] is None) == (p["tau"] is None):
+        raise ValueError("a laser pulse needs one of L0 (its length) and tau (its duration), not both and not neither")
+    L0 = float(p["L0"]) if p["L0"] is not None else float(p["tau"]) * c
+    pos = tuple(float(v) for v in p["position_mean"])
+    if len(pos) != 3:
+        raise ValueError("position_mean needs three values")
+    if not (float(p["w0"]) > 0.0 and L0 > 0.0):
+        raise ValueError("laser w0 and L0 must be positive")
+    return (float(p["a0"]), float(p["w0"]), L0, pos, float(p["focal_distance"]), float(p["CEP"]), float(p["propagation_angle_yz"]),
+            float(p["PFT_yz"]))
+
+
+def laser_cell_centres(deck):
+    """x (nxl), y (nyl), z (nzl) of the laser grid's cells, as the kernels compute them (i dx + xoff; slice k at the z of field slice k)"""
+    import numpy as np
+    nxl, nyl, zlo, zhi, lo3, hi3, dxl, dyl, xoffl, yoffl = laser_geometry(deck)
+    nz, lo, hi = deck["nz"], deck["lo"], deck["hi"]
+    dz = (hi[2] - lo[2]) / nz
+    zoff = 0.5 * (lo[2] + hi[2] - dz * (nz - 1)) + zlo * dz
+    return np.arange(nxl) * dxl + xoffl, np.arange(nyl) * dyl + yoffl, np.arange(zhi - zlo + 1) * dz + zoff
+
+
+def laser_two_pulses(n=64, nz=40):
+    """laser_evolution's box with the envelope on a patch of its own, a driver pulse and a weaker, tilted, off-axis second pulse
+    behind it (two entries of lasers.names), in-situ reductions on."""
+    d = laser_evolution()
+    d.update(nx=n, ny=n, nz=nz, n_steps=2,
+             laser_n_cell=(3 * n // 4, 3 * n // 4), laser_patch_lo=(-4.5, -4.5, -7.0), laser_patch_hi=(4.5, 4.5, 5.0), laser_interp_order=1,
+             lasers=[dict(a0=1.0, w0=1.5, L0=1.5, position_mean=(0.0, 0.0, 1.5), focal_distance=100.0),
+                     dict(a0=0.4, w0=1.2, L0=1.0, position_mean=(0.0, 0.8, -3.5), focal_distance=50.0, CEP=0.2,
+                          propagation_angle_yz=0.01, PFT_yz=math.pi / 2.0 + 0.05)],
+             laser_insitu=1)
+    return d
+
+
 def _round_half_away(v):
     return math.copysign(math.floor(abs(v) + 0.5), v)        # std::round
 

@@ -1,5 +1,6 @@
 """A few calls of the HDF5 C library through ctypes: enough to write and read back the openPMD files of
-`hipace_amd/openpmd_writer.py` (groups, contiguous datasets of doubles / 64-bit unsigned integers, attributes of the types
+`hipace_amd/openpmd_writer.py` (groups, contiguous datasets of doubles / 64-bit unsigned integers -- and of the two-member
+float compound {r, i} that holds a laser file's complex envelope --, attributes of the types
 openPMD-api's HDF5 backend uses).  The image has the HDF5 C library (libhdf5.so 1.10, no h5py, no openPMD-api); where the
 library cannot be loaded `available()` is False and the writer keeps to its npz / JSON containers.
 
@@ -24,7 +25,7 @@ H5F_ACC_RDONLY, H5F_ACC_TRUNC = 0, 2
 H5P_DEFAULT = 0
 H5S_ALL = 0
 H5S_SCALAR = 0
-H5T_INTEGER, H5T_FLOAT, H5T_STRING, H5T_ENUM = 0, 1, 3, 8
+H5T_INTEGER, H5T_FLOAT, H5T_STRING, H5T_COMPOUND, H5T_ENUM = 0, 1, 3, 6, 8
 H5_INDEX_NAME, H5_ITER_INC = 0, 0
 
 
@@ -79,6 +80,9 @@ def _declare(L):
         "H5Aget_num_attrs": (C.c_int, [hid_t]),
         "H5Tcopy": (hid_t, [hid_t]), "H5Tset_size": (herr_t, [hid_t, C.c_size_t]), "H5Tclose": (herr_t, [hid_t]),
         "H5Tget_class": (C.c_int, [hid_t]), "H5Tget_size": (C.c_size_t, [hid_t]), "H5Tget_sign": (C.c_int, [hid_t]),
+        "H5Tcreate": (hid_t, [C.c_int, C.c_size_t]), "H5Tinsert": (herr_t, [hid_t, C.c_char_p, C.c_size_t, hid_t]),
+        "H5Tget_nmembers": (C.c_int, [hid_t]), "H5Tget_member_class": (C.c_int, [hid_t, C.c_uint]),
+        "H5Tget_member_offset": (C.c_size_t, [hid_t, C.c_uint]), "H5Tget_native_type": (hid_t, [hid_t, C.c_int]),
         "H5Tenum_create": (hid_t, [hid_t]), "H5Tenum_insert": (herr_t, [hid_t, C.c_char_p, C.c_void_p]),
         "H5Gget_info": (herr_t, [hid_t, C.c_void_p]),
         "H5Lget_name_by_idx": (C.c_ssize_t, [hid_t, C.c_char_p, C.c_int, C.c_int, hsize_t, C.c_char_p, C.c_size_t, hid_t]),
@@ -198,8 +202,26 @@ class File:
         for i in range(1, len(parts) + 1):
             self._groups.add("/" + "/".join(parts[:i]))
 
+    def _complex_type(self, dtype):
+        """the compound {r, i} of two floats / doubles that openPMD-api stores CFLOAT / CDOUBLE as (the caller closes it)"""
+        L, half = self.L, np.dtype(dtype).itemsize // 2
+        member = _G["H5T_NATIVE_FLOAT_g" if half == 4 else "H5T_NATIVE_DOUBLE_g"]
+        t = _chk(L.H5Tcreate(H5T_COMPOUND, 2 * half), "H5Tcreate")
+        _chk(L.H5Tinsert(t, b"r", 0, member), "H5Tinsert")
+        _chk(L.H5Tinsert(t, b"i", half, member), "H5Tinsert")
+        return t
+
     def dataset(self, path, array):
         a = np.ascontiguousarray(array)
+        if a.dtype in (np.dtype(np.complex64), np.dtype(np.complex128)):
+            L = self.L
+            t = self._complex_type(a.dtype)
+            sp = _chk(L.H5Screate_simple(a.ndim, _dims(a.shape), None), "H5Screate_simple")
+            d = _chk(L.H5Dcreate2(self.id, path.encode(), t, sp, self.lcpl, H5P_DEFAULT, H5P_DEFAULT), f"H5Dcreate2({path})")
+            if a.size:
+                _chk(L.H5Dwrite(d, t, H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data_as(C.c_void_p)), f"H5Dwrite({path})")
+            L.H5Dclose(d); L.H5Sclose(sp); L.H5Tclose(t)
+            return
         t = {np.dtype(np.float64): "H5T_NATIVE_DOUBLE_g", np.dtype(np.uint64): "H5T_NATIVE_UINT64_g", np.dtype(np.float32): "H5T_NATIVE_FLOAT_g",
              np.dtype(np.int32): "H5T_NATIVE_INT32_g", np.dtype(np.int64): "H5T_NATIVE_INT64_g", np.dtype(np.uint32): "H5T_NATIVE_UINT32_g"}[a.dtype]
         L = self.L
@@ -269,6 +291,19 @@ class File:
         L = self.L
         d = _chk(L.H5Dopen2(self.id, path.encode(), H5P_DEFAULT), f"H5Dopen2({path})")
         t, sp = L.H5Dget_type(d), L.H5Dget_space(d)
+        if L.H5Tget_class(t) == H5T_COMPOUND:       # {r, i} of two floats / doubles: complex
+            size = L.H5Tget_size(t)
+            if not (L.H5Tget_nmembers(t) == 2 and size in (8, 16) and L.H5Tget_member_class(t, 0) == H5T_FLOAT and
+                    L.H5Tget_member_class(t, 1) == H5T_FLOAT and L.H5Tget_member_offset(t, 0) == 0 and
+                    L.H5Tget_member_offset(t, 1) == size // 2):
+                L.H5Tclose(t); L.H5Sclose(sp); L.H5Dclose(d)
+                raise IOError("HDF5: the only compound read is {r, i} of two floats or doubles")
+            mt = _chk(L.H5Tget_native_type(t, 1), "H5Tget_native_type")       # H5T_DIR_ASCEND, the file's member names
+            a = np.empty(self._shape(sp), dtype=np.complex64 if size == 8 else np.complex128)
+            if a.size:
+                _chk(L.H5Dread(d, mt, H5S_ALL, H5S_ALL, H5P_DEFAULT, a.ctypes.data_as(C.c_void_p)), f"H5Dread({path})")
+            L.H5Tclose(mt); L.H5Tclose(t); L.H5Sclose(sp); L.H5Dclose(d)
+            return a
         dt, g = self._np_type(t)
         a = np.empty(self._shape(sp), dtype=dt)
         if a.size:

@@ -347,3 +347,42 @@ def read_beam(container, deck, iteration=0, species=None, plasma_density=0.0):
                     scaled(name_u, "x", to_mom) * c_sim, scaled(name_u, "y", to_mom) * c_sim, scaled(name_u, "z", to_mom) * c_sim,
                     np.abs(scaled(name_w, None, to_w))])
     return out
+
+
+def read_laser(path, iteration=0, name="laserEnvelope"):
+    """A laser envelope from a lasy-layout openPMD HDF5 file, as Laser::GetEnvelopeFromFile reads it (laser/Laser.cpp:63-175):
+    -> (geometry, data, offset, spacing, unit, lambda0) for SliceEngine.add_laser_samples.  geometry "xyt" | "xyz" | "rt" from
+    axisLabels t,y,x | z,y,x | t,r; data complex128 in the file's C order (the scalar record, stored as CFLOAT or CDOUBLE);
+    offset = gridGlobalOffset + position * gridSpacing and spacing per axis, in the file's order; unit = unitSI; lambda0 =
+    2 pi c / angularFrequency (c in SI)."""
+    from . import decks
+    if not h5lite.available():
+        raise IOError("read_laser: no HDF5 library on this machine (h5lite.available() is false)")
+    with h5lite.File(path, "r") as f:
+        root = f.attrs("/")
+        base = root.get("basePath", "/data/%T/").replace("%T", str(int(iteration)))
+        mesh = "/" + base.strip("/") + "/" + root.get("meshesPath", "meshes/").strip("/") + "/" + name
+        try:
+            a = f.attrs(mesh)
+        except IOError:
+            raise IOError(f"{path}: iteration {iteration} holds no mesh named {name!r}") from None
+        if not f.is_dataset(mesh):
+            raise IOError(f"{path}: the mesh {name!r} is a group, not the one scalar record of an envelope")
+        if "angularFrequency" not in a:
+            raise IOError(f"{path}: the mesh {name!r} of iteration {iteration} lacks the attribute angularFrequency")
+        data = f.read(mesh)
+    if data.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128)):
+        raise IOError(f"{path}: the envelope is stored as {data.dtype}, not as complex floats or doubles (CFLOAT, CDOUBLE)")
+    labels = list(a["axisLabels"])
+    geometry = {("t", "y", "x"): "xyt", ("z", "y", "x"): "xyz", ("t", "r"): "rt"}.get(tuple(labels))
+    if geometry is None:
+        raise IOError(f"{path}: axisLabels {labels} are none of t,y,x / z,y,x / t,r")
+    if data.ndim != 3:
+        raise IOError("the laser envelope must have three axes (rt: modes, t, r)")
+    off, sp = np.atleast_1d(a["gridGlobalOffset"]).astype(float), np.atleast_1d(a["gridSpacing"]).astype(float)
+    pos = np.atleast_1d(a.get("position", [0.0] * len(labels))).astype(float)
+    if geometry != "xyz" and np.any(pos[:len(labels)] != 0.0):
+        raise IOError("a laser file with a t axis must have position 0 (Laser.cpp:181, 280)")
+    offset = tuple(float(v) for v in off + pos * sp)
+    lambda0 = 2.0 * np.pi * decks.SI["c"] / float(a["angularFrequency"])
+    return geometry, data.astype(np.complex128), offset, tuple(float(v) for v in sp), float(a.get("unitSI", 1.0)), lambda0

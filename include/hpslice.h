@@ -256,7 +256,8 @@ typedef struct {
      * fields/Fields.cpp:678-735: Psi, Ez, Bz -- and Bx, By of the predictor-corrector loop -- solved with the free-space potential
      * of the sources, expanded to order 18 about x = y = 0, as Dirichlet values; x = y = 0 must lie inside the box). */
     int bxby_solver; double predcorr_tol; int predcorr_max_iter; double predcorr_mix; int field_bc;
-    /* a Gaussian laser envelope (laser/Laser.H:32-45; CEP 0, no propagation angle) drives the wake:
+    /* a Gaussian laser envelope (laser/Laser.H:32-45; CEP 0, no propagation angle -- several pulses, CEP, angle,
+     * pulse-front tilt and envelopes from samples: hps_engine_set_laser_pulses / hps_engine_add_laser_samples) drives the wake:
      * |a|^2 goes into the slab component "aabs" (appended last) and enters the deposition, the explicit source and the
      * pusher.  laser_solver = 1 ("fft", MultiLaser::AdvanceSliceFFT) advances the envelope by hipace.dt every step
      * (laser_use_phase = lasers.use_phase); 2 ("multigrid", MultiLaser::AdvanceSliceMG, hpmg system type 2) likewise;
@@ -444,6 +445,46 @@ int hps_laser_interp_aabs (hps_slab slab, int c_aabs, const double* a_plane, int
                            double xoffl, double yoffl, hps_geom geom, int order, void* stream);
 int hps_laser_interp_chi (hps_slab slab, int c_chi, const double* chi_initial, double* chi_out, int nxl, int nyl, double dxl,
                           double dyl, double xoffl, double yoffl, hps_geom geom, int shrink, int order, void* stream);
+/* The initial envelope from several Gaussian pulses and from samples (MultiLaser::InitLaserSlice, laser/MultiLaser.cpp:804-920;
+ * Laser.cpp:18-60, 117-341).  Both before the first hps_engine_begin_step, on a deck with laser_on; without either
+ * call the deck's own pulse is evaluated by the kernel that has always done so.
+ *
+ * hps_engine_set_laser_pulses: n >= 1 pulses replace the deck's own (lambda0 stays the deck's, shared by all, as in the
+ * reference); n = 0: no Gaussian at all, only the sample envelopes below (refused by the first begin_step if there are none);
+ * n > 8: HPS_ERR_ARG.  The envelope of a cell is the sum over the pulses, in order, of InitLaserSlice :876-915: with
+ * (x, y, z) the cell's position minus pos, angle = propagation_angle_yz and rot = angle + (pft_yz - pi/2) (pft_yz is the
+ * reference's PFT_yz, default pi/2),
+ *     yp = cos(rot) y - sin(rot) z,   zp = sin(rot) y + cos(rot) z,
+ *     D  = 1 + i (zp - zfoc + pos[2] cos(angle)) 2/(k0 w0^2),
+ *     a  = a0/D exp(-zp^2/L0^2) exp(-(x^2 + yp^2)/(w0^2 D)) exp(i yp k0 angle + cep).
+ * The last factor is literal: the reference adds CEP to the exponent as a real number, so it scales the pulse by e^cep and
+ * does not turn its phase.  That is restated here, not corrected. */
+typedef struct { double a0, w0, L0, pos[3], zfoc, cep, propagation_angle_yz, pft_yz; } hps_laser_pulse;
+int hps_engine_set_laser_pulses (void* handle, int n, const hps_laser_pulse* pulses);
+/* geometry: 0 = on the laser grid itself ([nzl][nyl][nxl]; the reference's parser type, evaluated by the host),
+ *           1 = "xyt", 2 = "xyz", 3 = "rt" (Laser.cpp:177-336); data: complex doubles, C order [extent0][extent1][extent2];
+ *           offset = gridGlobalOffset + position*gridSpacing per axis, in the file's axis order; unit = unitSI
+ * (xyt: axes t, y, x; xyz: z, y, x; rt: extent = {modes, nt, nr}, offset and spacing = {t, r, unused}.)  The call copies the
+ * samples; up to 4 sets.  At the first begin_step they are uploaded, added to the envelope after the Gaussians in the order
+ * given -- geometry 0 cell by cell, 1 .. 3 through order-1 shape factors in x, y and z or t (t = (z of the last laser slice
+ * - z)/c/spacing[0]; samples outside the file's extent count as zero; rt: mode 0 plus cos(m theta), sin(m theta) parts, m <=
+ * extent[0]/2, theta = atan2(y, x)) -- and freed.  HPS_ERR_ARG: after the first begin_step, without a laser, a fifth set,
+ * extent or spacing not positive, geometry 0 with extents other than the laser grid's, rt with an even extent[0] or with a
+ * laser cell that would reach a sample index < 0 in r (the reference asserts there), more than 2^31 - 1 samples in a set.
+ * Geometry 0 is checked against the laser grid once more at the top of the first begin_step (hps_engine_set_laser_grid may
+ * have come in between); a refusal there leaves the engine as it was.  No host memory for the copy: HPS_ERR_HIP, as a
+ * failed device allocation. */
+int hps_engine_add_laser_samples (void* handle, int geometry, const double* data_host, const long extent[3],
+                                  const double offset[3], const double spacing[3], double unit);
+/* In-situ laser reductions (MultiLaser::InSituComputeDiags, laser/MultiLaser.cpp:923-1003; lasers.insitu_period): per slice
+ * of the laser's zeta range, of the plane a_n that the |a|^2 interpolation of the slice is about to read, out_host[q*nzl +
+ * islice - zeta_lo]: q = 0 max(|a|^2) (raw); 1 .. 5 [|a|^2], [|a|^2*x], [|a|^2*x*x], [|a|^2*y], [|a|^2*y*y] (sums times the
+ * laser grid's dx dy dz, x = i dx + xoff, y = j dy + yoff on the laser grid); 6, 7 Re, Im of axis(a) (the sum over the one, two
+ * or four middle cells times 1, 1/2 or 1/4).  No floating-point atomics: the values are a function of the plane alone, bit for
+ * bit.  Cleared by hps_engine_begin_step; a slice outside the zeta range keeps zeros; reading synchronises the stream.  Off: no
+ * launch and no allocation.  Switching it on while it is on changes nothing: the rows collected so far stay. */
+int hps_engine_set_insitu_laser (void* handle, int on);
+int hps_engine_insitu_laser (void* handle, double* out_host /* [8][nzl], nzl = zeta_hi - zeta_lo + 1; nz without a laser grid */);
 /* accumulate the per-slice checksums (costs one reduction pass per slice; off by default) */
 int hps_engine_set_diagnostics (void* handle, int on);
 /* Field diagnostics (Fields::Copy, fields/Fields.cpp:413-533; geometry of Diagnostic::ResizeFDiagFAB,
