@@ -52,6 +52,14 @@ class LaserPulse(C.Structure):      # hps_laser_pulse
                 ("cep", C.c_double), ("propagation_angle_yz", C.c_double), ("pft_yz", C.c_double)]
 
 
+class ExprIns(C.Structure):         # hps_expr_ins
+    _fields_ = [("op", C.c_int), ("arg", C.c_int)]
+
+
+class Expr(C.Structure):            # hps_expr
+    _fields_ = [("n_ins", C.c_int), ("n_const", C.c_int), ("ins", C.POINTER(ExprIns)), ("consts", C.POINTER(C.c_double))]
+
+
 class Deck(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3),
@@ -274,6 +282,10 @@ _SIGS = {
                                           C.c_int, C.c_double, C.c_double, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_double,
                                           C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_void_p]),
     "hps_engine_add_beam_collision": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_ulonglong]),
+    "hps_expr_check": (C.c_int, [C.POINTER(Expr), C.c_int, C.POINTER(C.c_int)]),
+    "hps_expr_eval_host": (C.c_int, [C.POINTER(Expr), C.c_int, C.c_long, C.POINTER(C.c_void_p), C.c_void_p]),
+    "hps_expr_eval": (C.c_int, [C.POINTER(Expr), C.c_int, C.c_long, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
+    "hps_engine_set_beam_external_fields": (C.c_int, [C.c_void_p, C.POINTER(Expr), C.POINTER(Expr)]),
     "hps_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_device_count": (C.c_int, [C.POINTER(C.c_int)]),

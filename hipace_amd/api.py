@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, decks as _decks
+from . import _lib, decks as _decks, expr as _expr
 from ._lib import CIDX, COMPS, ID_VALID, PL_REAL, check
 
 
@@ -442,6 +442,46 @@ class MultiGrid:
             self._h = None
 
 
+class Expression:
+    """A parsed function of the input file as a device operator (hps_expr_eval): Expression("if(x > 0, sin(x), y^2)",
+    variables=("x", "y"))(x, y) evaluates the compiled program (hipace_amd/expr.py) with one lane per element on float64
+    device tensors of one shape.  evaluate_host runs the same routine on the CPU over numpy arrays (hps_expr_eval_host, no
+    device); .program.evaluate is the numpy restatement."""
+
+    def __init__(self, text, variables=("x", "y", "z", "t"), constants=None):
+        self.program = text if isinstance(text, _expr.Program) else _expr.compile_expr(text, variables, constants)
+        self._c, self._keep = self.program.c_struct()
+        depth = C.c_int()
+        check(_lib.lib().hps_expr_check(C.byref(self._c), len(self.program.variables), C.byref(depth)))
+        self.depth = depth.value
+
+    def __call__(self, *tensors, out=None):
+        nv = len(self.program.variables)
+        if len(tensors) != nv:
+            raise ValueError(f"Expression: {nv} tensors expected ({', '.join(self.program.variables)}), got {len(tensors)}")
+        if out is None and not tensors:
+            raise ValueError("Expression: a program without variables needs out=")
+        for t in tensors:
+            assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.shape == tensors[0].shape
+        if out is None:
+            out = torch.empty_like(tensors[0])
+        assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and (not tensors or out.shape == tensors[0].shape)
+        ptrs = (C.c_void_p * max(nv, 1))(*[t.data_ptr() if t.numel() else None for t in tensors])
+        check(_lib.lib().hps_expr_eval(C.byref(self._c), nv, out.numel(), ptrs, C.c_void_p(out.data_ptr() if out.numel() else None),
+                                       _stream()))
+        return out
+
+    def evaluate_host(self, *arrays):
+        nv = len(self.program.variables)
+        if len(arrays) != nv:
+            raise ValueError(f"Expression: {nv} arrays expected ({', '.join(self.program.variables)}), got {len(arrays)}")
+        a = [np.ascontiguousarray(v, dtype=np.float64) for v in np.broadcast_arrays(*arrays)] if arrays else []
+        out = np.empty(a[0].shape if a else (1,), dtype=np.float64)
+        ptrs = (C.c_void_p * max(nv, 1))(*[v.ctypes.data for v in a])
+        check(_lib.lib().hps_expr_eval_host(C.byref(self._c), nv, out.size, ptrs, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+
 class AdaptiveTimeStep:
     """hipace.dt = adaptive: the reference's controller (utils/AdaptiveTimeStep.cpp) over hps_adaptive_* -- host code, no
     device.  One per rank / pipeline stage, all initialised alike."""
@@ -550,6 +590,12 @@ class SliceEngine:
                 self.add_beam_collision(b, coulomb_log, seed)
             else:
                 self.add_collision(a, b, coulomb_log, seed)
+        ext = deck.get("beam_external_fields")      # beams.external_E / external_B: dict(E=(...), B=(...), constants={...})
+        if ext is not None:
+            unknown = set(ext) - {"E", "B", "constants"}
+            if unknown:
+                raise ValueError(f"beam_external_fields: unknown entries {sorted(unknown)}")
+            self.set_beam_external_fields(ext.get("E"), ext.get("B"), ext.get("constants"))
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -737,6 +783,26 @@ class SliceEngine:
         0 (plasma) / 1 (ion), in the same ordered list as add_collision (hps_engine_add_beam_collision).  With a static beam
         (hipace.dt = 0) it is accepted and does nothing: every pair's scattering parameter is 0 there."""
         check(_lib.lib().hps_engine_add_beam_collision(self._h, plasma_species, coulomb_log, seed))
+
+    def set_beam_external_fields(self, E=None, B=None, constants=None):
+        """beams.external_E(x,y,z,t) / beams.external_B(x,y,z,t): three expressions (strings in the input file's syntax, or
+        numbers) each, or None; constants: my_constants.  Compiled by hipace_amd/expr.py and handed to
+        hps_engine_set_beam_external_fields before the first begin_step; components that fold to the constant 0 are skipped.
+        The moving beam's push adds them at every sub-step's position and the step's time, on top of the deck's ext_E_slope /
+        ext_Ez_slope; a static beam (hipace.dt = 0) is not changed by them."""
+        progs = [_expr.compile_components(E, "beams.external_E", constants), _expr.compile_components(B, "beams.external_B", constants)]
+        keep, arrs = [], []
+        for three in progs:
+            if three is None:
+                arrs.append(None)
+                continue
+            a = (_lib.Expr * 3)()
+            for q, prog in enumerate(three):
+                a[q], k = prog.c_struct()
+                keep.append(k)
+            arrs.append(a)
+        check(_lib.lib().hps_engine_set_beam_external_fields(self._h, arrs[0], arrs[1]))
+        self.beam_external_fields = progs
 
     def collision_stats(self):
         a, b = C.c_long(), C.c_long()

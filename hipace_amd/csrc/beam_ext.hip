@@ -1,0 +1,65 @@
+// beam_ext.hip -- beams.external_E(x,y,z,t) / beams.external_B(x,y,z,t) as expression programs: the setter that
+// checks the programs and packs them into one device image, and the launch of k_beam_push<ORDER, true> (beam_push.h).
+// Built with -mllvm -disable-machine-licm (Makefile): left on, the pass hoists the literal constants of every inlined
+// transcendental function out of the interpreter's loop and holds them in registers across it (k_expr_eval: 244 VGPRs
+// against 36; the order-3 push beyond 512 registers, into scratch).
+#include "common.h"
+#include "engine.h"
+#include "beam_push.h"
+
+namespace hps {
+
+int beam_push_launch_ext (Engine& E, const SlabView& f, int p, int cPsi, int cEz, int cBx, int cBy, int cBz, const BeamPushConsts& k, dim3 grid)
+{
+    const BeamExtArgs<true> x{E.bext.d_ins, E.bext.d_consts, E.step_time};
+    const dim3 block(256);
+    const size_t lds = (size_t)std::max(E.bext.depth - 1, 0)*256*sizeof(double);
+#define CALL(O) hipLaunchKernelGGL((k_beam_push<O, true>), grid, block, lds, E.st, f, E.bm, E.d_B, p, cPsi, cEz, cBx, cBy, cBz, k, x)
+    HPS_BEAM_ORDER(E.d.order, CALL)
+#undef CALL
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
+// hps_engine_set_beam_external_fields: every component is checked before anything changes
+int Engine::set_beam_external_fields (const hps_expr* E3, const hps_expr* B3)
+{
+    static const char* const fn = "hps_engine_set_beam_external_fields";
+    static const char* const name[6] = {"E[0]: ", "E[1]: ", "E[2]: ", "B[0]: ", "B[1]: ", "B[2]: "};
+    HPS_REQUIRE(!step_begun, std::string(fn) + ": call before the first hps_engine_begin_step");
+    const hps_expr* comp[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int depth = 0; bool any = false;
+    for (int q = 0; q < 6; ++q) {
+        const hps_expr* src = q < 3 ? E3 : B3;
+        if (!src || src[q % 3].n_ins == 0) continue;
+        int dq = 0;
+        if (int e = expr_check_named(fn, name[q], &src[q % 3], 4, &dq)) return e;
+        if (expr_is_zero(src[q % 3])) continue;
+        comp[q] = &src[q % 3]; depth = std::max(depth, dq); any = true;
+    }
+    (void)hipFree(bext.d_ins); (void)hipFree(bext.d_consts);
+    bext = BeamExt{};
+    if (!any || !moving) return HPS_OK;      // hipace.dt = 0: the beam is never pushed, the programs have no effect
+    std::vector<hps_expr_ins> ins(6, hps_expr_ins{0, 0});
+    std::vector<double> consts;
+    for (int q = 0; q < 6; ++q) {
+        if (!comp[q]) continue;
+        const int off = expr_append(*comp[q], ins, consts);
+        ins[q] = hps_expr_ins{off, comp[q]->n_ins};
+    }
+    if (consts.empty()) consts.push_back(0.0);
+    HPS_HIP_CHECK(hipMalloc(&bext.d_ins, ins.size()*sizeof(hps_expr_ins)));
+    HPS_HIP_CHECK(hipMalloc(&bext.d_consts, consts.size()*sizeof(double)));
+    HPS_HIP_CHECK(hipMemcpy(bext.d_ins, ins.data(), ins.size()*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
+    HPS_HIP_CHECK(hipMemcpy(bext.d_consts, consts.data(), consts.size()*sizeof(double), hipMemcpyHostToDevice));
+    bext.depth = depth; bext.on = true;
+    return HPS_OK;
+}
+
+} // namespace hps
+
+extern "C" int hps_engine_set_beam_external_fields (void* h, const hps_expr* E3, const hps_expr* B3)
+{
+    HPS_REQUIRE(h, "hps_engine_set_beam_external_fields: null engine");
+    return static_cast<hps::Engine*>(h)->set_beam_external_fields(E3, B3);
+}

@@ -104,6 +104,13 @@ struct Engine {
     // hps_engine_set_time (hipace.dt = adaptive): time and dt of the step the next begin_step starts; step_dt is what the
     // beam push of the step that has begun uses (the deck's dt unless set)
     bool time_set = false; double next_t = 0.0, next_dt = 0.0, step_dt = 0.0;
+    // physical time of the step that has begun (Hipace::m_physical_time): d.dt*step_index, or the t of hps_engine_set_time
+    double step_time = 0.0;
+    // beams.external_E / external_B as expression programs (hps_engine_set_beam_external_fields, expr.hip): one
+    // device image -- six {offset, count} header slots (Ex Ey Ez Bx By Bz; count 0: absent), then the instructions -- and
+    // the pooled constants; depth = the deepest stack of the six.  on = false: k_beam_push<ORDER, false>, the push as it was.
+    struct BeamExt { bool on = false; hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; int depth = 0; } bext;
+    int set_beam_external_fields (const hps_expr* E3, const hps_expr* B3);
     bool host_beam = false;        // hps_engine_set_beam_particles has given the beam
     double* d_mom = nullptr;       // hipace.dt = adaptive: beam moments [nz + 1][4] (beam.hip: k_beam_partition<true>)
     IonArgs ion_args (int islice);             // ionization.hip: kernel arguments of this slice's ionisation
@@ -277,6 +284,10 @@ int laser_check_samples (Engine& E, const Engine::LaserSamples& S);          // 
 int laser_set_insitu (Engine& E, int on);                                    // the [8][nzl] in-situ buffer and its scratch
 int laser_clear_insitu (Engine& E);
 int laser_copy_insitu (Engine& E, double* out_host);
+// expr.hip: hps_expr_check in the words of fn; "is absent" (no instructions, or the single constant 0); packing into one image
+int expr_check_named (const char* fn, const char* what, const hps_expr* p, int n_vars, int* depth);
+bool expr_is_zero (const hps_expr& p);
+int expr_append (const hps_expr& p, std::vector<hps_expr_ins>& ins, std::vector<double>& consts);
 int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz);      // beam.hip
 int beam_push_moving (Engine& E, int islice);
 int beam_push_slice (Engine& E, int islice, int p, long bound);

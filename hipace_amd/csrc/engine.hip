@@ -346,7 +346,7 @@ Engine::~Engine ()
     (void)hipFree(pl_real_alt); (void)hipFree(pl_alt.idcpu); (void)hipFree(pl_alt.ion_lev); 
     (void)hipFree(staging); (void)hipFree(d_open_mom); (void)hipFree(beam_data); (void)hipFree(beam_init);
     (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr); (void)hipFree(d_B); (void)hipFree(d_nfront);
-    (void)hipFree(d_mom); (void)hipFree(d_sal);
+    (void)hipFree(d_mom); (void)hipFree(d_sal); (void)hipFree(bext.d_ins); (void)hipFree(bext.d_consts);
     (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow); (void)hipFree(d_nqsa); (void)hipFree(d_checksum);
     (void)hipFree(d_pc); (void)hipFree(d_pc_aux); (void)hipFree(d_pc_go); if (h_pc) (void)hipHostFree(h_pc);
     (void)hipFree(d_laser_sum);
@@ -957,11 +957,11 @@ int Engine::begin_step ()
     if (d_mom) { if (int e = beam_moments_reset(*this)) return e; }
     // time factor of the density profile at z = c t of this step (UpdateDensityFunction, PlasmaParticleContainer.cpp:211-217)
     if (time_set) {          // hps_engine_set_time
-        step_dt = next_dt;
+        step_dt = next_dt; step_time = next_t;
         prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*next_t);
         time_set = false;
     } else {
-        step_dt = d.dt;
+        step_dt = d.dt; step_time = d.dt*step_index;
         prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*d.dt*step_index);
     }
     if (laser && lgrid.set) { if (int e = laser_chi_initial(*this)) return e; }      // SetInitialChi: density(x, y, c t) of this step

@@ -222,6 +222,15 @@ def beam_evolution():
     return d
 
 
+def beam_evolution_parsed():
+    """tests/beam_evolution.1Rank.sh as the script writes it: beams.external_E(x,y,z,t) = .5*x .5*y 0. as parsed expressions
+    (the optional entry "beam_external_fields", applied by SliceEngine through hps_engine_set_beam_external_fields -- not a
+    member of hps_deck) in place of beam_evolution()'s slopes."""
+    d = beam_evolution()
+    d.update(ext_E_slope=(0.0, 0.0), beam_external_fields=dict(E=(".5*x", ".5*y", "0.")))
+    return d
+
+
 def adaptive_time_step(sign=1):
     """tests/adaptive_time_step.1Rank.sh: the beam_in_vacuum deck on 32 x 32 x 32 cells in [-2, 2]^3, a flattop beam of
     u_z = 1000 (ppc 4 4 1, four sub-cycles) in beams.external_E = (0, 0, sign * 0.5 z), no plasma, hipace.dt = adaptive with

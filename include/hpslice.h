@@ -877,6 +877,58 @@ int hps_engine_add_beam_collision (void* handle, int plasma_species, double coul
 /* pairs collided and overfull cells since hps_engine_create; synchronises the stream */
 int hps_engine_collision_stats (void* handle, long* pairs_collided, long* overfull_cells);
 
+/* ---- expression programs (parsed functions of the input file) --------------------------------------
+ * The reference's parsed functions (beams.external_E(x,y,z,t), ...) reach the C ABI compiled: a postfix program over
+ * n_vars input variables with one double result.  An instruction is {opcode, operand}; HPS_EX_CONST pushes
+ * consts[operand], HPS_EX_VAR pushes variable operand, HPS_EX_POWI raises the top to the literal integer power operand
+ * (|operand| <= 8) by repeated multiplication (r = x; r = r*x ...; 1/r for a negative power; 1 for power 0); every other
+ * opcode ignores its operand, pops its arguments and pushes its result.  Comparisons, and / or / not give 1.0 / 0.0 (and,
+ * or, not and select test "!= 0"); HPS_EX_SELECT pops b, a, c and pushes c != 0 ? a : b (both arms have been evaluated);
+ * HPS_EX_MIN / HPS_EX_MAX are (a < b ? a : b) / (a > b ? a : b); HPS_EX_HEAVISIDE(x1, x2) is 0 for x1 < 0, x2 for
+ * x1 == 0 and 1 for x1 > 0.  Every arithmetic operation rounds once (no fused multiply-add), on the host and on the device.
+ * hipace_amd/expr.py compiles the input syntax to such programs; there is no text parser in the C ABI. */
+enum { HPS_EX_CONST = 0, HPS_EX_VAR, HPS_EX_ADD, HPS_EX_SUB, HPS_EX_MUL, HPS_EX_DIV, HPS_EX_NEG, HPS_EX_POW, HPS_EX_POWI,
+       HPS_EX_LT, HPS_EX_LE, HPS_EX_GT, HPS_EX_GE, HPS_EX_EQ, HPS_EX_NE, HPS_EX_AND, HPS_EX_OR, HPS_EX_NOT, HPS_EX_SELECT,
+       HPS_EX_SQRT, HPS_EX_EXP, HPS_EX_LOG, HPS_EX_LOG10, HPS_EX_SIN, HPS_EX_COS, HPS_EX_TAN, HPS_EX_ASIN, HPS_EX_ACOS,
+       HPS_EX_ATAN, HPS_EX_ATAN2, HPS_EX_SINH, HPS_EX_COSH, HPS_EX_TANH, HPS_EX_ABS, HPS_EX_FLOOR, HPS_EX_CEIL, HPS_EX_FMOD,
+       HPS_EX_MIN, HPS_EX_MAX, HPS_EX_HEAVISIDE, HPS_EX_ERF, HPS_EX_NOPS };
+#define HPS_EXPR_MAX_INS 256     /* instructions of a program */
+#define HPS_EXPR_MAX_DEPTH 16    /* values on its stack */
+#define HPS_EXPR_MAX_CONST 64    /* entries of its constant pool */
+#define HPS_EXPR_MAX_POWI 8      /* |operand| of HPS_EX_POWI */
+#define HPS_EXPR_MAX_VARS 8      /* input variables */
+typedef struct { int op, arg; } hps_expr_ins;
+typedef struct {
+    int n_ins, n_const;
+    const hps_expr_ins* ins;     /* host memory; read during the call only */
+    const double* consts;
+} hps_expr;
+/* Walks the program once; *depth_host (may be NULL) = the deepest its stack gets.  HPS_ERR_ARG, with hps_last_error naming
+ * which: a bad opcode; an operand out of range (variable >= n_vars, constant index outside the pool, integer power beyond
+ * HPS_EXPR_MAX_POWI); stack underflow; stack overflow (deeper than HPS_EXPR_MAX_DEPTH); a program that does not end with
+ * exactly one value; a program beyond HPS_EXPR_MAX_INS / HPS_EXPR_MAX_CONST, n_vars beyond HPS_EXPR_MAX_VARS, an empty
+ * program.  Every entry point below checks its programs this way first: nothing is evaluated from an unchecked program. */
+int hps_expr_check (const hps_expr* prog, int n_vars, int* depth_host);
+/* out_host[i] = prog(vars_host[0][i], ..., vars_host[n_vars - 1][i]), i < n, on the CPU: the routine the kernels run
+ * (csrc/expr.h), compiled for the host.  Needs no device. */
+int hps_expr_eval_host (const hps_expr* prog, int n_vars, long n, const double* const* vars_host, double* out_host);
+/* The same on the device, one lane per element (grid-stride), on `stream`; vars_dev: a host array of n_vars device
+ * pointers.  Copies the program to the device for the call (allocates and frees) and returns when the kernel has finished
+ * (synchronises the stream).  n = 0: no launch. */
+int hps_expr_eval (const hps_expr* prog, int n_vars, long n, const double* const* vars_dev, double* out_dev, hps_stream stream);
+/* Engine: beams.external_E(x,y,z,t) / beams.external_B(x,y,z,t) -- E, B: three programs each over (x, y, z, t), or NULL for
+ * "none"; a component with n_ins = 0, or one that is the single constant 0, is absent and costs nothing.  The programs are
+ * checked, copied to the device once and kept for the engine's life.  The moving beam's push then evaluates the components
+ * present at every sub-step's (x, y, z) and the step's physical time -- dt * step for a fixed step, the t of
+ * hps_engine_set_time otherwise: one value per step, the same for every sub-cycle and every slice a slipped particle is
+ * pushed on (Hipace::m_physical_time) -- and adds them behind the gather as ApplyExternalField does
+ * (particles/pusher/ExternalFields.H:50-55): ExmBy += Ex - c By, EypBx += Ey + c Bx, Ez += Ez, B += B.  The deck's
+ * ext_E_slope / ext_Ez_slope are added as before; radiation reaction and spin tracking see the sum.  An engine without
+ * programs launches the push it launched before.  A static beam (hipace.dt = 0) accepts the programs and is not changed by
+ * them, as in the reference; the plasma never sees them.  HPS_ERR_ARG: a null handle, a call after the first
+ * hps_engine_begin_step, a program hps_expr_check refuses (with its message). */
+int hps_engine_set_beam_external_fields (void* handle, const hps_expr* E3, const hps_expr* B3);
+
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);
 int hps_memcpy_h2d (void* dst_dev, const void* src_host, long bytes);
