@@ -80,6 +80,11 @@ __device__ __forceinline__ double lds_get (const double* p)
     return *(const lds_double*)p;
 }
 
+// s_waitcnt vmcnt(0): every vector-memory operation of the wave so far has completed (expcnt and lgkmcnt left alone).  The
+// compiler's own wait insertion takes it into account, so a loop that starts behind it carries no wait for what was
+// requested ahead of it.
+__device__ __forceinline__ void vm_wait_all () { __builtin_amdgcn_s_waitcnt(0x0F70); }
+
 // |a|^2 of the laser envelope from one more plane of the tile's LDS image (the LASER variants of the three kernels): the
 // plain-shape gather of doLaserGatherShapeN (FieldGather.H:236-331) with the same weights and summation order as
 // laser_gather / laser_gather_grad (particle_math.h), so the result does not depend on which path a particle takes.
@@ -358,15 +363,16 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
     const int ox = tail ? TAIL_ORIGIN : (tile % ntx)*TS - TILE_HALO, oy = tail ? TAIL_ORIGIN : (tile / ntx)*TS - TILE_HALO;
     const int tid = threadIdx.x;
     const int cc[4] = {cBz, cEz, cExmBy, cEypBx};
-    // software pipeline over the tile's particles: the next particle's record is in flight while the
-    // current one is deposited; the first one is requested ahead of the field-image load
+    // software pipeline over the tile's particles: the next particle's record is in flight while the current one is
+    // deposited; the first one is requested ahead of the field-image load.  fetch() only issues loads: anything that READS a
+    // loaded value there (until round 8 the VBW validity, w != 0) makes the wave wait for the record it has just requested.
     const int pend = lrec.z;
     struct Rec { double x, y, w, ux, uy, psi; uint64_t id; int ion; };
     auto fetch = [&] (int ip) {
         Rec r;
         r.x = pl.x[ip]; r.y = pl.y[ip]; r.w = pl.w[ip];
         r.ux = pl.ux[ip]; r.uy = pl.uy[ip]; r.psi = pl.psi[ip];
-        if constexpr (VBW) r.id = (r.w != 0.0) ? HPS_ID_VALID : 0ULL;      // (PartConsts::valid_by_w: idcpu is not read)
+        if constexpr (VBW) r.id = 0ULL;      // (PartConsts::valid_by_w: idcpu is not read, one() looks at the weight)
         else r.id = pl.idcpu[ip];
         r.ion = k.can_ionize ? pl.ion_lev[ip] : 1;
         return r;
@@ -394,7 +400,7 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
     bool slow = false;
     auto one = [&] (const Rec& cur, auto LC) __attribute__((always_inline)) -> bool {
         constexpr bool LOCAL = decltype(LC)::value;
-        if (!(cur.id & HPS_ID_VALID)) return true;
+        if (VBW ? !(cur.w != 0.0) : !(cur.id & HPS_ID_VALID)) return true;
         if (k.can_ionize && cur.ion == 0) return true;      // a neutral atom deposits nothing (every term carries its level)
         const double xmid = (cur.x - k.xoff)*k.dx_inv;
         const double ymid = (cur.y - k.yoff)*k.dy_inv;
@@ -480,6 +486,10 @@ void k_explicit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offset
         }
         return true;
     };
+    // The first record has arrived with the field image: say so, or the loop body keeps the waits of its first trip -- the
+    // compiler loads that record straight into the registers of `cur`, and a wait for them in the body is, from the second
+    // trip on, a wait for the record requested a few instructions earlier.  The one wait of the loop is at the copy nxt -> cur.
+    vm_wait_all();
     for (int ip = ipb; ip < pend; ip += 256) {
         const Rec cur = nxt;
         if (ip + 256 < pend) nxt = fetch(ip + 256);
@@ -582,7 +592,7 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
         if constexpr (!VBP) q.id = ldo(pl.idcpu, o);
         q.xp = ldo(pl.x_prev, o); q.yp = ldo(pl.y_prev, o);
         q.uxh = ldo_nt(pl.ux_half, o); q.uyh = ldo_nt(pl.uy_half, o); q.psih = ldo_nt(pl.psi_half, o);
-        if constexpr (VBP) q.id = (q.psih != 0.0) ? HPS_ID_VALID : 0ULL;
+        if constexpr (VBP) q.id = 0ULL;      // (the validity is read off psih where the record is used: fetch() only issues loads)
         return q;
     };
     // the thread's first particle is requested ahead of the field image: its six values arrive with the image's
@@ -602,24 +612,49 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
     // The thread's particles are ip = first + 256 m.  Per particle the kernel needs idcpu, x_prev, y_prev and the three
     // half-step momenta: read one after the other where they are used (the validity bit first), that was three dependent
     // trips to memory per particle against ~1 us of arithmetic, with three waves per SIMD to hide them: the waves of
-    // the round-2 kernel lived 29 us for 4-5 particles and issued VALU instructions a fifth of that time.  Now all six
+    // the round-2 kernel lived 29 us for 4-5 particles and issued VALU instructions a fifth of that time.  All six
     // values of particle m + 1 are requested before particle m is worked on (14 VGPRs), and every array is addressed
     // as uniform base + one 32-bit byte offset (the file is compiled with -disable-lsr: the loop-strength-reduction
     // pass otherwise keeps a 64-bit pointer per array and iteration in VGPRs, 24 registers here).
-    for (; ip < pend; ip += 256) {
-        __builtin_assume(ip < (1u << 28));
-        const PIn cur = nxt;
-        if (ip + 256 < pend) nxt = fetch(ip + 256);
+    // Until round 8 that request was waited for at once all the same: the first sub-cycle took its inputs from a
+    // merge "prefetched register or conditional load", behind which the compiler waits for every load in flight, and the copy
+    // nxt -> cur stood behind the particle's stores, which share the loads' counter, on a join with paths that store
+    // nothing -- so it waited for all of them.  An iteration now is
+    //   request record m + 1;  all of particle m's arithmetic, on registers (process);  wait for record m + 1 (the one
+    //   wait: the request is a particle old);  particle m's stores (commit), which have the whole of particle m + 1 to retire.
+    // The wait stands where every lane passes: inside a divergent branch the compiler has to assume that the branch may be
+    // skipped, and waits again at the join.
+    // Sub-cycles after the first re-read what the one before has committed, as the reference does: those loads are issued
+    // and waited for at the end of a sub-cycle that is not the last, off the path of n_subcycles = 1.
+    struct POut { int kind; uint64_t id; double xp, yp, uxh, uyh, psih, ux, uy, psi; };      // kind: 0 nothing to store, 1 absorbed, 2 pushed
+    auto commit = [&] (const POut& r, unsigned o8) __attribute__((always_inline)) {
+        // (the offset is made opaque here: the 11 addresses base + o8 are otherwise formed once per particle, ahead of the
+        // gather, and held in 22 VGPRs across it instead of going into the stores as SGPR base + offset register)
+        asm volatile("" : "+v"(o8));
+        if (r.kind == 1) {
+            sto(pl.w, o8, 0.0);
+            sto(pl.idcpu, o8, (uint64_t)((VBP ? ldo(pl.idcpu, o8) : r.id) & ~HPS_ID_VALID));
+            sto(pl.psi_half, o8, 0.0);      // (Tiling::valid_by_psi)
+        } else if (r.kind == 2) {
+            sto(pl.x, o8, r.xp); sto(pl.y, o8, r.yp);
+            if (!k.temp_slice) {
+                sto_nt(pl.ux_half, o8, r.uxh); sto_nt(pl.uy_half, o8, r.uyh); sto_nt(pl.psi_half, o8, r.psih);
+                if (pl.x_prev != pl.x) sto(pl.x_prev, o8, r.xp);      // (aliased by the engine: already stored)
+                if (pl.y_prev != pl.y) sto(pl.y_prev, o8, r.yp);
+            }
+            sto(pl.ux, o8, r.ux); sto(pl.uy, o8, r.uy); sto(pl.psi, o8, r.psi);
+        }
+    };
+    auto process = [&] (const PIn& cur, unsigned ip) __attribute__((always_inline)) -> POut {
+        POut r{};
         const unsigned o8 = ip*8u;
-        const uint64_t id = cur.id;
-        if (!(id & HPS_ID_VALID)) continue;
+        const uint64_t id = VBP ? ((cur.psih != 0.0) ? HPS_ID_VALID : 0ULL) : cur.id;
+        r.id = id;
+        if (!(id & HPS_ID_VALID)) return r;
         double qmc = k.a;
         if (k.can_ionize) qmc *= (double)pl.ion_lev[ip];
-        bool dead = false;
-        for (int isc = 0; isc < k.n_subcycles && !dead; ++isc) {
-            // (sub-cycles after the first re-read what the one before has committed, as the reference does)
-            double xp = isc == 0 ? cur.xp : ldo(pl.x_prev, o8);
-            double yp = isc == 0 ? cur.yp : ldo(pl.y_prev, o8);
+        double xp = cur.xp, yp = cur.yp, ux = cur.uxh, uy = cur.uyh, psi = cur.psih;
+        for (int isc = 0; isc < k.n_subcycles; ++isc) {
             double sx[NS], dsx[NS], sy[NS], dsy[NS];
             constexpr bool W3 = ORDER == 2;
             double pxw[3] = {0.0, 0.0, 0.0}, pyw[3] = {0.0, 0.0, 0.0}; bool xhw = false, yhw = false;
@@ -718,7 +753,7 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
                     if (ionize) { ++lev; pl.ion_lev[ip] = lev; qmc = k.a*(double)lev; }
                     adk_emit(ia, ionize, pl.x[ip], pl.y[ip], xp, yp, pl.w[ip]);
                     charged |= (lev > 0);
-                    if (lev == 0 && uxh == 0.0 && uyh == 0.0) break;
+                    if (lev == 0 && uxh == 0.0 && uyh == 0.0) return r;
                 }
             }
             LaserFld Lf{0.0, 0.0, 0.0};
@@ -735,7 +770,6 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
                 Lf.A *= 0.5*ln; Lf.ADx *= 0.25*k.c*ln; Lf.ADy *= 0.25*k.c*ln;
             }
             const double dz = k.dz, sdz = dz*0.25;
-            double ux = isc == 0 ? cur.uxh : ldo(pl.ux_half, o8), uy = isc == 0 ? cur.uyh : ldo(pl.uy_half, o8), psi = isc == 0 ? cur.psih : ldo(pl.psi_half, o8);
             const PushForce PFc = push_force(F, Lf, k.c_inv, qmc);
             const double h2 = 0.5*sdz*sdz;
 #pragma unroll 1
@@ -743,23 +777,33 @@ void k_advance_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
             const double pinv = fast_rcp(psi);
             xp += dz*k.c_inv*(ux*pinv);
             yp += dz*k.c_inv*(uy*pinv);
-            if (apply_particle_bc(k, xp, yp, ux, uy)) {
-                sto(pl.w, o8, 0.0);
-                sto(pl.idcpu, o8, (uint64_t)((VBP ? ldo(pl.idcpu, o8) : id) & ~HPS_ID_VALID));
-                sto(pl.psi_half, o8, 0.0);      // (Tiling::valid_by_psi)
-                dead = true;
-                break;
-            }
-            sto(pl.x, o8, xp); sto(pl.y, o8, yp);
-            if (!k.temp_slice) {
-                sto_nt(pl.ux_half, o8, ux); sto_nt(pl.uy_half, o8, uy); sto_nt(pl.psi_half, o8, psi);
-                if (pl.x_prev != pl.x) sto(pl.x_prev, o8, xp);      // (aliased by the engine: already stored)
-                if (pl.y_prev != pl.y) sto(pl.y_prev, o8, yp);
-            }
+            if (apply_particle_bc(k, xp, yp, ux, uy)) { r.kind = 1; return r; }
+            r.xp = xp; r.yp = yp; r.uxh = ux; r.uyh = uy; r.psih = psi;
 #pragma unroll 1
             for (int s = 0; s < 2; ++s) taylor2_substep_pre<LASER>(ux, uy, psi, PFc, sdz, h2);
-            sto(pl.ux, o8, ux); sto(pl.uy, o8, uy); sto(pl.psi, o8, psi);
+            r.ux = ux; r.uy = uy; r.psi = psi;
+            r.kind = 2;
+            if (isc + 1 < k.n_subcycles) {
+                commit(r, o8);
+                r.kind = 0;
+                unsigned o = o8;
+                asm volatile("" : "+v"(o));
+                xp = ldo(pl.x_prev, o); yp = ldo(pl.y_prev, o);
+                ux = ldo(pl.ux_half, o); uy = ldo(pl.uy_half, o); psi = ldo(pl.psi_half, o);
+                vm_wait_all();
+            }
         }
+        return r;
+    };
+    vm_wait_all();      // the thread's first record has arrived with the field image (see k_explicit_tiled)
+    for (; ip < pend; ip += 256) {
+        __builtin_assume(ip < (1u << 28));
+        const PIn cur = nxt;
+        if (ip + 256 < pend) nxt = fetch(ip + 256);
+        const POut r = process(cur, ip);
+        // the one wait of the iteration, ahead of the particle's stores: record m + 1 has to be in its registers here
+        asm volatile("" : "+v"(nxt.id), "+v"(nxt.xp), "+v"(nxt.yp), "+v"(nxt.uxh), "+v"(nxt.uyh), "+v"(nxt.psih) :: "memory");
+        commit(r, ip*8u);
     }
     if constexpr (DEP != 0) {
         // ---- DepositCurrent of the tile's pushed particles into the next slice ----
