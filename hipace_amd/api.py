@@ -486,18 +486,40 @@ class AdaptiveTimeStep:
     """hipace.dt = adaptive: the reference's controller (utils/AdaptiveTimeStep.cpp) over hps_adaptive_* -- host code, no
     device.  One per rank / pipeline stage, all initialised alike."""
 
-    def __init__(self, deck, density_profile=None):
+    def __init__(self, deck, density_profile=None, density_exprs=None):
+        """density_exprs: {species: (text_or_table, constants)} of parsed densities; default: the deck's own
+        (decks.DENSITY_EXPR_DEFAULT), as SliceEngine applies them"""
         self.deck = dict(deck)
         self._dk = _lib.fill_struct(_lib.Deck(), deck)
         self._h = C.c_void_p()
         check(_lib.lib().hps_adaptive_create(C.byref(self._dk), C.byref(self._h)))
         if density_profile is not None:
             self.set_density_profile(*density_profile)
+        if density_exprs is None:
+            density_exprs = {sp: spec[:2] for sp, spec in _decks.density_exprs(deck).items()}
+        for sp, spec in density_exprs.items():
+            self.set_density_expr(sp, *spec)
 
     @classmethod
     def for_engine(cls, engine):
-        """a controller for `engine`'s deck and density profile"""
-        return cls(engine.deck, getattr(engine, "density_profile", None))
+        """a controller for `engine`'s deck, density profile and density programs"""
+        exprs = {sp: ((progs[0] if pos is None else list(zip(pos, progs))), None)
+                 for sp, (progs, pos, _) in getattr(engine, "density_exprs", {}).items()}
+        return cls(engine.deck, getattr(engine, "density_profile", None), exprs)
+
+    def set_density_expr(self, species, text_or_table, constants=None):
+        """the species' parsed density (SliceEngine.set_density_expr): rho_max(z) takes |charge * density(0, 0, z)|"""
+        sp = {"plasma": 0, "ion": 1}.get(species, species)
+        progs, pos = _expr.compile_density(text_or_table, constants)
+        arr, keep = _expr.c_programs(progs)
+        z = (C.c_double * len(pos))(*pos) if pos is not None else None
+        check(_lib.lib().hps_adaptive_set_density_expr(self._h, sp, len(progs), arr, z))
+
+    def rho_max(self, z):
+        """MultiPlasma::maxChargeDensity(z) as the controller takes it (hps_adaptive_rho_max)"""
+        out = C.c_double()
+        check(_lib.lib().hps_adaptive_rho_max(self._h, float(z), C.byref(out)))
+        return out.value
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -596,6 +618,9 @@ class SliceEngine:
             if unknown:
                 raise ValueError(f"beam_external_fields: unknown entries {sorted(unknown)}")
             self.set_beam_external_fields(ext.get("E"), ext.get("B"), ext.get("constants"))
+        # <plasma>.density(x,y,z), min_density, density_table_file (decks.DENSITY_EXPR_DEFAULT): a deck without these keys makes no call
+        for sp, spec in _decks.density_exprs(deck).items():
+            self.set_density_expr(sp, *spec)
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -902,6 +927,23 @@ class SliceEngine:
         assert len(a[0]) == len(a[1]) and len(a[2]) == len(a[3])
         p = [x.ctypes.data_as(C.c_void_p) if len(x) else None for x in a]
         check(_lib.lib().hps_engine_set_density_profile(self._h, len(a[0]), p[0], p[1], len(a[2]), p[2], p[3]))
+
+    def set_density_expr(self, species, text_or_table, constants=None, min_density=0.0):
+        """<plasma>.density(x,y,z) of species 0 / "plasma" or 1 / "ion" as a parsed function: a string in the input file's
+        syntax (or a number), or the density table as a list of (position, string) pairs in ascending order of position
+        (decks.read_density_table reads density_table_file); constants: my_constants; min_density: <plasma>.min_density.
+        Compiled by hipace_amd/expr.py over (x, y, z) and handed to hps_engine_set_density_expr before the first begin_step.
+        The value is the density itself: for this species it replaces <species>_density f_r f_t of set_density_profile."""
+        sp = {"plasma": 0, "ion": 1}.get(species, species)
+        if sp not in (0, 1):
+            raise ValueError(f"set_density_expr: species must be 0, 1, 'plasma' or 'ion', got {species!r}")
+        progs, pos = _expr.compile_density(text_or_table, constants)
+        arr, keep = _expr.c_programs(progs)
+        z = (C.c_double * len(pos))(*pos) if pos is not None else None
+        check(_lib.lib().hps_engine_set_density_expr(self._h, sp, len(progs), arr, z, float(min_density)))
+        if not hasattr(self, "density_exprs"):
+            self.density_exprs = {}
+        self.density_exprs[sp] = (progs, pos, float(min_density))
 
     def set_fusion(self, on=True):
         """Push of slice k and deposition of slice k-1 in one pass over the sheet (include/hpslice.h: hps_engine_set_fusion)."""

@@ -2,11 +2,15 @@
 // Hipace.cpp:270-282, 400-490).  Pure host code: the beam moments it needs come from the engine's partition kernel
 // (beam.hip, k_beam_partition<true>) through hps_engine_beam_moments, so the controller runs, and is tested, without a GPU.
 #include "common.h"
+#include "expr.h"
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <vector>
 
 namespace hps {
+
+int expr_check_named (const char* fn, const char* what, const hps_expr* p, int n_vars, int* depth);      // expr.hip
 
 struct Adaptive {
     double nt = 20.0, dt_max = std::numeric_limits<double>::infinity(), thr = 2.0, tol = 4.0e-4;
@@ -15,8 +19,11 @@ struct Adaptive {
     double c = 1.0, ep0 = 1.0, q_e = 1.0;
     double mq = 1.0; bool zero_charge = false;            // beam mass / charge; charge 0: the beam does not set dt
     double adaptive_density = 0.0;
-    // species on the axis: |charge| * density, times f_r(0) f_t(z) of the profile
-    std::vector<double> species_qn;
+    // species on the axis: |charge| * density, times f_r(0) f_t(z) of the profile -- or |charge * program(0, 0, z)|
+    // hps_adaptive_set_density_expr: per species (0 plasma, 1 ion) its charge, whether the deck has it, and its density
+    // programs with their positions (z_pos empty: one program); none: the species keeps |charge density| f_r(0) f_t(z)
+    struct Species { bool present = false; double charge = 0.0, qn = 0.0; std::vector<std::vector<hps_expr_ins>> ins;
+                     std::vector<std::vector<double>> consts; std::vector<double> z_pos; } species[2];
     std::vector<double> prof_r, prof_fr, prof_t, prof_ft;
     double dt = 0.0;                                       // Hipace::m_dt of this rank
     double min_uz_mq = std::numeric_limits<double>::max();
@@ -28,7 +35,16 @@ struct Adaptive {
         double r = std::fabs(adaptive_density*q_e);
         const double f = table_value(prof_r.data(), prof_fr.data(), (int)prof_r.size(), 0.0)*
                          table_value(prof_t.data(), prof_ft.data(), (int)prof_t.size(), z);
-        for (double qn : species_qn) r = std::max(r, std::fabs(qn*f));
+        for (const Species& S : species) {
+            if (!S.present) continue;
+            if (S.ins.empty()) { r = std::max(r, std::fabs(S.qn*f)); continue; }
+            // UpdateDensityFunction(z): the first entry with z_pos >= z, the last one beyond the table
+            size_t k = 0;
+            if (!S.z_pos.empty()) k = std::min<size_t>(std::lower_bound(S.z_pos.begin(), S.z_pos.end(), z) - S.z_pos.begin(), S.z_pos.size() - 1);
+            ExprHostStack st;
+            const ExprXyz v{0.0, 0.0, z};
+            r = std::max(r, std::fabs(S.charge*expr_run(S.ins[k].data(), (int)S.ins[k].size(), S.consts[k].data(), v, st)));
+        }
         return r;
     }
     void reset_moments () { acc[0] = acc[1] = acc[2] = 0.0; acc[3] = 1e30; }
@@ -98,8 +114,8 @@ extern "C" int hps_adaptive_create (const hps_deck* d, void** handle)
     A->zero_charge = (d->beam_charge == 0.0);
     A->mq = A->zero_charge ? 0.0 : mass/d->beam_charge;
     A->adaptive_density = d->adaptive_density;
-    if (d->plasma_ppc[0]*d->plasma_ppc[1] > 0) A->species_qn.push_back(d->plasma_charge*d->plasma_density);
-    if (d->ion_on) A->species_qn.push_back(d->ion_charge*d->ion_density);
+    if (d->plasma_ppc[0]*d->plasma_ppc[1] > 0) { A->species[0].present = true; A->species[0].charge = d->plasma_charge; A->species[0].qn = d->plasma_charge*d->plasma_density; }
+    if (d->ion_on) { A->species[1].present = true; A->species[1].charge = d->ion_charge; A->species[1].qn = d->ion_charge*d->ion_density; }
     *handle = A;
     return HPS_OK;
 }
@@ -114,6 +130,40 @@ extern "C" int hps_adaptive_set_density_profile (void* h, int nr, const double* 
     for (int k = 1; k < nt; ++k) HPS_REQUIRE(ct_host[k] > ct_host[k - 1], "hps_adaptive_set_density_profile: ct must increase");
     A->prof_r.assign(r_host, r_host + nr); A->prof_fr.assign(fr_host, fr_host + nr);
     A->prof_t.assign(ct_host, ct_host + nt); A->prof_ft.assign(ft_host, ft_host + nt);
+    return HPS_OK;
+}
+
+extern "C" int hps_adaptive_set_density_expr (void* h, int species, int n_progs, const hps_expr* progs, const double* z_pos)
+{
+    static const char* const fn = "hps_adaptive_set_density_expr";
+    Adaptive* A = static_cast<Adaptive*>(h);
+    HPS_REQUIRE(A, std::string(fn) + ": null handle");
+    HPS_REQUIRE(species == 0 || species == 1, std::string(fn) + ": species must be 0 (plasma) or 1 (ion)");
+    HPS_REQUIRE(A->species[species].present, std::string(fn) + ": the deck does not have this species (no plasma, or no ion species)");
+    HPS_REQUIRE(n_progs >= 1 && progs, std::string(fn) + ": n_progs must be >= 1 (at least one program)");
+    HPS_REQUIRE(n_progs == 1 || z_pos, std::string(fn) + ": several programs need their positions (z_pos)");
+    for (int k = 0; z_pos && k < n_progs; ++k)
+        HPS_REQUIRE(std::isfinite(z_pos[k]) && (k == 0 || z_pos[k] > z_pos[k - 1]), std::string(fn) + ": the positions of the density table must be finite and strictly ascending");
+    for (int k = 0; k < n_progs; ++k) {
+        const std::string what = n_progs > 1 ? "entry " + std::to_string(k) + ": " : std::string();
+        if (int e = expr_check_named(fn, what.c_str(), &progs[k], 3, nullptr)) return e;
+    }
+    Adaptive::Species& S = A->species[species];
+    S.ins.clear(); S.consts.clear(); S.z_pos.clear();
+    for (int k = 0; k < n_progs; ++k) {
+        S.ins.emplace_back(progs[k].ins, progs[k].ins + progs[k].n_ins);
+        S.consts.emplace_back(progs[k].consts, progs[k].consts + progs[k].n_const);
+        if (S.consts.back().empty()) S.consts.back().push_back(0.0);
+    }
+    if (z_pos) S.z_pos.assign(z_pos, z_pos + n_progs);
+    return HPS_OK;
+}
+
+extern "C" int hps_adaptive_rho_max (void* h, double z, double* out)
+{
+    Adaptive* A = static_cast<Adaptive*>(h);
+    HPS_REQUIRE(A && out, "hps_adaptive_rho_max: null argument");
+    *out = A->rho_max(z);
     return HPS_OK;
 }
 

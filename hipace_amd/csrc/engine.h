@@ -3,6 +3,7 @@
 #define HPS_ENGINE_H_
 
 #include "common.h"
+#include <algorithm>
 #include <vector>
 #include "tiling.h"
 #include "mg_gate.h"
@@ -38,6 +39,10 @@ int mg_solve1_finish (void* mg_handle, int* iters_out, double* resnorm_out, int*
 namespace hps {
 
 struct LaserState;      // laser.hip
+
+// a density program as a kernel argument: the instructions of the table entry in force and the pooled constants,
+// both on the device, z = c t of the step and <plasma>.min_density.  n_ins = 0: no program
+struct DensityProgram { const hps_expr_ins* ins; int n_ins; const double* consts; double z, min_density; };
 
 struct BeamSoA { double *x, *y, *z, *ux, *uy, *uz, *w; int* nsub;      // moving beam (beam.hip); nsub < 0: absorbed
                  double *sx, *sy, *sz; };                              // spin (do_spin_tracking), null otherwise
@@ -111,6 +116,17 @@ struct Engine {
     // the pooled constants; depth = the deepest stack of the six.  on = false: k_beam_push<ORDER, false>, the push as it was.
     struct BeamExt { bool on = false; hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; int depth = 0; } bext;
     int set_beam_external_fields (const hps_expr* E3, const hps_expr* B3);
+    // <plasma>.density(x,y,z) / density_table_file as expression programs (hps_engine_set_density_expr, plasma_init.hip, DESIGN
+    // 8m), species 0 = plasma, 1 = ion: the species' programs as given (z_pos empty: the one program of density(x,y,z)), the
+    // offset of each in the engine's one device image (both species' instructions, the pooled constants), the deepest stack
+    // of the species' programs, and the entry in force in the step that has begun.  on = false: the tables, the kernels as they were.
+    struct DensityExpr { bool on = false; std::vector<std::vector<hps_expr_ins>> ins; std::vector<std::vector<double>> consts;
+                         std::vector<double> z_pos; std::vector<int> off; int depth = 0; double min_density = 0.0; int cur = 0; } dens[2];
+    hps_expr_ins* d_dens_ins = nullptr; double* d_dens_consts = nullptr; double dens_z = 0.0;      // dens_z: c t of the step that has begun
+    int set_density_expr (int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density);
+    void density_begin_step (double ct);                  // UpdateDensityFunction(c t): the table entry in force
+    DensityProgram density_program (int species) const;   // n_ins = 0: this species keeps the tables
+    size_t density_lds (int species) const { return dens[species].on ? (size_t)std::max(dens[species].depth - 1, 0)*256*sizeof(double) : 0; }
     bool host_beam = false;        // hps_engine_set_beam_particles has given the beam
     double* d_mom = nullptr;       // hipace.dt = adaptive: beam moments [nz + 1][4] (beam.hip: k_beam_partition<true>)
     IonArgs ion_args (int islice);             // ionization.hip: kernel arguments of this slice's ionisation
@@ -261,8 +277,9 @@ int ion_create (Engine& E);                                                  // 
 void ion_destroy (Engine& E);
 unsigned event_flags (bool timing);                                           // engine.hip
 // plasma_init.hip: InitParticles with the fine patch and / or the hollow core for one species' sheet
+// (and, with a density program, for the plain lattice: init_slot's rule of the weight, one place)
 int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
-                      double radius_sq);
+                      double radius_sq, int species);
 // ...: the same sheet with Gaussian momenta, its mirror copies and / or the lattice shifted off the axis (Engine::warm_init)
 int init_plasma_warm (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
                       double radius_sq, int species);

@@ -352,7 +352,7 @@ Engine::~Engine ()
     (void)hipFree(d_laser_sum);
     if (laser) laser_destroy(*this);
     ion_destroy(*this);
-    (void)hipFree(d_prof_r); (void)hipFree(d_fine_level); (void)hipFree(d_fine_cells);
+    (void)hipFree(d_prof_r); (void)hipFree(d_fine_level); (void)hipFree(d_fine_cells); (void)hipFree(d_dens_ins); (void)hipFree(d_dens_consts);
     (void)hipFree(d_fd); (void)hipFree(d_fd_comps); (void)hipFree(d_insitu); (void)hipFree(d_insitu_pl); (void)hipFree(d_insitu_bm);
     for (auto e : ev) (void)hipEventDestroy(e);
     for (auto e : hand_ev) if (e) (void)hipEventDestroy(e);
@@ -959,10 +959,12 @@ int Engine::begin_step ()
     if (time_set) {          // hps_engine_set_time
         step_dt = next_dt; step_time = next_t;
         prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*next_t);
+        density_begin_step(gm.c*next_t);
         time_set = false;
     } else {
         step_dt = d.dt; step_time = d.dt*step_index;
         prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*d.dt*step_index);
+        density_begin_step(gm.c*d.dt*step_index);
     }
     if (laser && lgrid.set) { if (int e = laser_chi_initial(*this)) return e; }      // SetInitialChi: density(x, y, c t) of this step
     if (int e = ionize_collect()) return e;
@@ -970,8 +972,8 @@ int Engine::begin_step ()
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : std::numeric_limits<double>::infinity();
     if (np > 0 && warm_init(0)) {
         if (int e = init_plasma_warm(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq, 0)) return e;
-    } else if (np > 0 && (hollow_core_radius > 0.0 || (fine_patch_set && fine_ppc[0] > 0))) {
-        if (int e = init_plasma_fine(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq)) return e;
+    } else if (np > 0 && (hollow_core_radius > 0.0 || (fine_patch_set && fine_ppc[0] > 0) || dens[0].on)) {      // (a density program: init_slot's kernels)
+        if (int e = init_plasma_fine(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq, 0)) return e;
     } else if (np > 0) {
         const int nppc = d.plasma_ppc[0]*d.plasma_ppc[1];
         hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(np, 256)), dim3(256), 0, st, pl, np, d.nx, d.ny,
@@ -995,8 +997,8 @@ int Engine::begin_step ()
         const int inppc = d.ion_ppc[0]*d.ion_ppc[1];
         if (warm_init(1)) {
             if (int e = init_plasma_warm(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq, 1)) return e;
-        } else if (hollow_core_radius > 0.0 || (fine_patch_set && ion_fine_ppc[0] > 0)) {
-            if (int e = init_plasma_fine(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq)) return e;
+        } else if (hollow_core_radius > 0.0 || (fine_patch_set && ion_fine_ppc[0] > 0) || dens[1].on) {
+            if (int e = init_plasma_fine(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq, 1)) return e;
         } else {
             hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(ion.n, 256)), dim3(256), 0, st, ion.pl, ion.n, d.nx, d.ny,
                                d.ion_ppc[0], d.ion_ppc[1], d.lo[0], d.lo[1], gm.dx, gm.dy,

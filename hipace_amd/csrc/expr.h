@@ -83,6 +83,11 @@ struct ExprXyzt {
     double x, y, z, t;
     __device__ __forceinline__ double get (int k) const { return k == 0 ? x : k == 1 ? y : k == 2 ? z : t; }
 };
+// the three variables of a density program, density(x, y, z), likewise; on the host too (adaptive.hip)
+struct ExprXyz {
+    double x, y, z;
+    __host__ __device__ __forceinline__ double get (int k) const { return k == 0 ? x : k == 1 ? y : z; }
+};
 #endif
 
 // The routine.  ins / consts: a checked program (expr_validate); the caller's Stack holds depth - 1 levels.

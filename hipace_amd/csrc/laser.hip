@@ -16,6 +16,7 @@
 // (UpdateLaserAabs :253-284) and chi to the laser grid (SetInitialChi :293-332, InterpolateChi :334-407).
 #include "common.h"
 #include "engine.h"
+#include "expr.h"
 
 #include <rocfft/rocfft.h>
 #include <algorithm>
@@ -342,6 +343,30 @@ void k_laser_chi_initial (double* __restrict__ out, int nxl, int nyl, double dxl
     out[(long)j*nxl + i] = fac*f0 + fac*f1;
 }
 
+// ... where a species' density is its program (hps_engine_set_density_expr): that species contributes
+// prog(x, y, c t) f with f = q^2 mu0 / m (times init_level^2) alone, inside the radius and outside the hollow core; min_density
+// is not applied (SetInitialChi does not).  A species whose p.n_ins is 0 contributes fac f as above.  Dynamic LDS: the
+// programs' stack, [level][lane], the deeper of the two.
+__global__ __launch_bounds__(256)
+void k_laser_chi_initial_prog (double* __restrict__ out, int nxl, int nyl, double dxl, double dyl, double xoffl, double yoffl, double f0, double f1,
+                               DensityProgram p0, DensityProgram p1, const double* __restrict__ prof, int nr, double ft, double radius_sq,
+                               double hollow_sq)
+{
+    extern __shared__ double s_chi_stack[];
+    const int i = blockIdx.x*blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
+    if (i >= nxl) return;
+    const double x = i*dxl + xoffl, y = j*dyl + yoffl;
+    const double rsq = x*x + y*y;
+    const bool in = !(rsq > radius_sq || rsq < hollow_sq);
+    const double fac = in ? ft*table_value(prof, prof + nr, nr, sqrt(rsq)) : 0.0;
+    ExprLdsStack st{s_chi_stack + threadIdx.x, (int)blockDim.x};
+    double n0 = fac, n1 = fac;
+    if (p0.n_ins > 0) { const ExprXyz v{x, y, p0.z}; const double val = expr_run(p0.ins, p0.n_ins, p0.consts, v, st); n0 = in ? val : 0.0; }
+    if (p1.n_ins > 0) { const ExprXyz v{x, y, p1.z}; const double val = expr_run(p1.ins, p1.n_ins, p1.consts, v, st); n1 = in ? val : 0.0; }
+    out[(long)j*nxl + i] = n0*f0 + n1*f1;
+}
+
 // InterpolateChi (:334-407): one thread per laser cell.  Inside x_lo .. x_hi, y_lo .. y_hi (the laser cells on the field box
 // shrunk by the guard width, :358-372) chi of the slab, interpolated; outside, chi of the unperturbed plasma.
 template <int ORDER>
@@ -665,9 +690,18 @@ int laser_chi_initial (Engine& E)
     LaserState* L = E.laser;
     if (!L->chi_initial) return HPS_OK;
     const hps_deck& d = E.d;
-    const double f0 = d.plasma_density > 0.0 ? d.plasma_density*d.plasma_charge*d.plasma_charge*E.gm.mu0/d.plasma_mass : 0.0;
-    const double f1 = d.ion_on ? d.ion_density*d.ion_charge*d.ion_charge*E.gm.mu0/d.ion_mass*(double)d.ion_init_level*(double)d.ion_init_level : 0.0;
+    const DensityProgram p0 = E.density_program(0), p1 = E.density_program(1);
+    const double n0 = p0.n_ins > 0 ? 1.0 : d.plasma_density, n1 = p1.n_ins > 0 ? 1.0 : d.ion_density;      // a program's value is the density itself
+    const double f0 = d.plasma_density > 0.0 ? n0*d.plasma_charge*d.plasma_charge*E.gm.mu0/d.plasma_mass : 0.0;
+    const double f1 = d.ion_on ? n1*d.ion_charge*d.ion_charge*E.gm.mu0/d.ion_mass*(double)d.ion_init_level*(double)d.ion_init_level : 0.0;
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : INFINITY;
+    if (p0.n_ins > 0 || p1.n_ins > 0) {
+        hipLaunchKernelGGL(k_laser_chi_initial_prog, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), std::max(E.density_lds(0), E.density_lds(1)), E.st,
+                           L->chi_initial, L->nx, L->ny, L->dx, L->dy, L->xoff, L->yoff, f0, f1, p0, p1, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft,
+                           radius_sq, E.hollow_core_radius*E.hollow_core_radius);
+        HPS_HIP_CHECK(hipGetLastError());
+        return HPS_OK;
+    }
     hipLaunchKernelGGL(k_laser_chi_initial, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), 0, E.st, L->chi_initial, L->nx, L->ny, L->dx, L->dy,
                        L->xoff, L->yoff, f0, f1, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, radius_sq, E.hollow_core_radius*E.hollow_core_radius);
     HPS_HIP_CHECK(hipGetLastError());

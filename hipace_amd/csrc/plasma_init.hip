@@ -14,6 +14,7 @@
 // DESIGN 8i) go through k_init_plasma_warm: the same slots with a Gaussian momentum from a counter-based draw, three mirror
 // copies of the whole sheet behind it, and the lattice moved by half a cell where the cell count and ppc are both odd.
 #include "engine.h"
+#include "expr.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,9 +33,16 @@ struct FineInit {
 
 // Slot k of the sheet: its position, its weight and whether it holds a particle.  xoff, yoff: 0, or -0.5 in a direction
 // that prevent_centered_particle shifts (:52-64) -- there the cells are the nodes 1 .. n - 1, and index 0 owns no particle
+//
+// PROG: the density is the species' program at (x, y, c t) instead of density f_r f_t -- a.w_coarse, a.w_fine then
+// hold scale_fac alone (density 1), the weight is value * scale_fac, and the slot holds a particle iff value > min_density
+// (:280).  The program's stack: this lane's column of the workgroup's dynamic LDS, [level][lane], depth - 1 levels.  Every
+// lane of the wave runs the program (the opcode is uniform); the tests of the radius and the core only gate the result.
 struct SlotInit { double x, y, w; bool live; };
+template <bool PROG>
 __device__ __forceinline__ SlotInit init_slot (long k, int nx, int ny, const FineInit& a, double lox, double loy, double dx, double dy,
-                                               const double* __restrict__ prof, int nr, double ft, double xoff = 0.0, double yoff = 0.0)
+                                               const double* __restrict__ prof, int nr, double ft, const DensityProgram& dp,
+                                               double xoff = 0.0, double yoff = 0.0)
 {
     const long cells = (long)nx*ny;
     int ip, L = 0;
@@ -68,19 +76,30 @@ __device__ __forceinline__ SlotInit init_slot (long k, int nx, int ny, const Fin
     const double y = loy + (j + ry + yoff)*dy;
     // <plasma>.radius, hollow_core_radius and the density (PlasmaParticleContainerInit.cpp:274-279)
     const double rsq = x*x + y*y;
-    double fac = (rsq > a.radius_sq || rsq < a.hollow_sq) ? 0.0 : ft*table_value(prof, prof + nr, nr, sqrt(rsq));
-    if ((xoff != 0.0 && i == 0) || (yoff != 0.0 && j == 0)) fac = 0.0;
     const double weight = L == 0 ? a.w_coarse : a.w_fine;      // (:289-294)
-    return {x, y, fac > 0.0 ? weight*fac : 0.0, fac > 0.0};
+    if constexpr (PROG) {
+        extern __shared__ double s_density_stack[];
+        ExprLdsStack st{s_density_stack + threadIdx.x, (int)blockDim.x};
+        const ExprXyz v{x, y, dp.z};
+        const double value = expr_run(dp.ins, dp.n_ins, dp.consts, v, st);
+        const bool out = rsq > a.radius_sq || rsq < a.hollow_sq || (xoff != 0.0 && i == 0) || (yoff != 0.0 && j == 0);
+        const bool live = !out && value > dp.min_density;
+        return {x, y, live ? value*weight : 0.0, live};
+    } else {
+        double fac = (rsq > a.radius_sq || rsq < a.hollow_sq) ? 0.0 : ft*table_value(prof, prof + nr, nr, sqrt(rsq));
+        if ((xoff != 0.0 && i == 0) || (yoff != 0.0 && j == 0)) fac = 0.0;
+        return {x, y, fac > 0.0 ? weight*fac : 0.0, fac > 0.0};
+    }
 }
 
+template <bool PROG>
 __global__ __launch_bounds__(256)
 void k_init_plasma_fine (hps_plasma pl, long n, int nx, int ny, FineInit a, double lox, double loy, double dx, double dy,
-                         int level, int keyed, const double* __restrict__ prof, int nr, double ft)
+                         int level, int keyed, const double* __restrict__ prof, int nr, double ft, DensityProgram dp)
 {
     const long k = (long)blockIdx.x*blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const SlotInit s = init_slot(k, nx, ny, a, lox, loy, dx, dy, prof, nr, ft);
+    const SlotInit s = init_slot<PROG>(k, nx, ny, a, lox, loy, dx, dy, prof, nr, ft, dp);
     const double x = s.x, y = s.y;
     const bool live = s.live;
     pl.x[k] = x; pl.y[k] = y; pl.w[k] = s.w;
@@ -110,14 +129,14 @@ __device__ __forceinline__ void normal_pair (unsigned long long zk, unsigned dra
     nc *= r; ns *= r;
 }
 
-template <bool SYM>
+template <bool SYM, bool PROG>
 __global__ __launch_bounds__(256)
 void k_init_plasma_warm (hps_plasma pl, long nq, int nx, int ny, FineInit a, WarmInit t, double lox, double loy, double dx, double dy,
-                         int level, int keyed, const double* __restrict__ prof, int nr, double ft)
+                         int level, int keyed, const double* __restrict__ prof, int nr, double ft, DensityProgram dp)
 {
     const long k = (long)blockIdx.x*blockDim.x + threadIdx.x;
     if (k >= nq) return;
-    const SlotInit s = init_slot(k, nx, ny, a, lox, loy, dx, dy, prof, nr, ft, t.xoff, t.yoff);
+    const SlotInit s = init_slot<PROG>(k, nx, ny, a, lox, loy, dx, dy, prof, nr, ft, dp, t.xoff, t.yoff);
     const bool live = s.live;
     const unsigned long long zk = coll_hash(t.key, (unsigned long long)k);
     double u[3] = {t.u_mean[0], t.u_mean[1], t.u_mean[2]};
@@ -170,13 +189,19 @@ static FineInit fine_args (const Engine& E, const int ppc[2], const int fine[2],
 }
 
 int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
-                      double radius_sq)
+                      double radius_sq, int species)
 {
     const hps_deck& d = E.d;
-    const FineInit a = fine_args(E, ppc, fine, density, radius_sq, 1.0);
+    const DensityProgram dp = E.density_program(species);
+    const bool prog = dp.n_ins > 0;
+    const FineInit a = fine_args(E, ppc, fine, prog ? 1.0 : density, radius_sq, 1.0);
     if (n != a.ncoarse + (long)(a.fx*a.fy - a.cx*a.cy)*a.ncells) { set_error("init_plasma_fine: the sheet does not have the patch's slot count"); return HPS_ERR_ARG; }
-    hipLaunchKernelGGL(k_init_plasma_fine, dim3(ceil_div(n, 256)), dim3(256), 0, E.st, p, n, d.nx, d.ny, a, d.lo[0], d.lo[1],
-                       E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft);
+    if (prog)
+        hipLaunchKernelGGL(k_init_plasma_fine<true>, dim3(ceil_div(n, 256)), dim3(256), E.density_lds(species), E.st, p, n, d.nx, d.ny, a,
+                           d.lo[0], d.lo[1], E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp);
+    else
+        hipLaunchKernelGGL(k_init_plasma_fine<false>, dim3(ceil_div(n, 256)), dim3(256), 0, E.st, p, n, d.nx, d.ny, a, d.lo[0], d.lo[1],
+                           E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp);
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
@@ -186,7 +211,9 @@ int init_plasma_warm (Engine& E, const hps_plasma& p, long n, const int ppc[2], 
 {
     const hps_deck& d = E.d;
     const bool sym = E.do_symmetrize;
-    const FineInit a = fine_args(E, ppc, fine, density, radius_sq, sym ? 4.0 : 1.0);
+    const DensityProgram dp = E.density_program(species);
+    const bool prog = dp.n_ins > 0;
+    const FineInit a = fine_args(E, ppc, fine, prog ? 1.0 : density, radius_sq, sym ? 4.0 : 1.0);
     const long nq = a.ncoarse + (long)(a.fx*a.fy - a.cx*a.cy)*a.ncells;
     if (n != (sym ? 4 : 1)*nq) { set_error("init_plasma_warm: the sheet does not have the slot count of its keys"); return HPS_ERR_ARG; }
     const Engine::Thermal& th = E.thermal[species];
@@ -198,12 +225,11 @@ int init_plasma_warm (Engine& E, const hps_plasma& p, long n, const int ppc[2], 
     t.yoff = E.shifted(ppc, 1) ? -0.5 : 0.0;
     t.x_mid2 = d.lo[0] + d.hi[0]; t.y_mid2 = d.lo[1] + d.hi[1];       // of the particle boundary box (:319-320)
     const dim3 grid(ceil_div(nq, 256)), block(256);
-    if (sym)
-        hipLaunchKernelGGL(k_init_plasma_warm<true>, grid, block, 0, E.st, p, nq, d.nx, d.ny, a, t, d.lo[0], d.lo[1], E.gm.dx, E.gm.dy,
-                           level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft);
-    else
-        hipLaunchKernelGGL(k_init_plasma_warm<false>, grid, block, 0, E.st, p, nq, d.nx, d.ny, a, t, d.lo[0], d.lo[1], E.gm.dx, E.gm.dy,
-                           level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft);
+#define CALL(SYM, PROG, LDS) hipLaunchKernelGGL((k_init_plasma_warm<SYM, PROG>), grid, block, LDS, E.st, p, nq, d.nx, d.ny, a, t, d.lo[0], d.lo[1], \
+                                                E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp)
+    if (prog) { if (sym) CALL(true, true, E.density_lds(species)); else CALL(false, true, E.density_lds(species)); }
+    else      { if (sym) CALL(true, false, 0); else CALL(false, false, 0); }
+#undef CALL
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
@@ -307,4 +333,76 @@ int Engine::set_fine_patch (const unsigned char* mask_host, int transition_cells
     return alloc_sheets();
 }
 
+// hps_engine_set_density_expr: every program is checked before anything changes; then the engine's one image is
+// rebuilt from both species' programs
+int Engine::set_density_expr (int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density)
+{
+    static const char* const fn = "hps_engine_set_density_expr";
+    HPS_REQUIRE(!step_begun, std::string(fn) + ": call before the first hps_engine_begin_step");
+    HPS_REQUIRE(species == 0 || species == 1, std::string(fn) + ": species must be 0 (plasma) or 1 (ion)");
+    HPS_REQUIRE(species == 0 ? d.plasma_density > 0.0 : d.ion_on != 0, std::string(fn) + ": the deck does not have this species (no plasma, or no ion species)");
+    HPS_REQUIRE(n_progs >= 1 && progs, std::string(fn) + ": n_progs must be >= 1 (at least one program)");
+    HPS_REQUIRE(n_progs == 1 || z_pos, std::string(fn) + ": several programs need their positions (z_pos)");
+    HPS_REQUIRE(!std::isnan(min_density), std::string(fn) + ": min_density is NaN");
+    for (int k = 0; z_pos && k < n_progs; ++k)
+        HPS_REQUIRE(std::isfinite(z_pos[k]) && (k == 0 || z_pos[k] > z_pos[k - 1]), std::string(fn) + ": the positions of the density table must be finite and strictly ascending");
+    int depth = 0;
+    for (int k = 0; k < n_progs; ++k) {
+        int dk = 0;
+        const std::string what = n_progs > 1 ? "entry " + std::to_string(k) + ": " : std::string();
+        if (int e = expr_check_named(fn, what.c_str(), &progs[k], 3, &dk)) return e;
+        depth = std::max(depth, dk);
+    }
+    DensityExpr& D = dens[species];
+    D = DensityExpr{};
+    for (int k = 0; k < n_progs; ++k) {
+        D.ins.emplace_back(progs[k].ins, progs[k].ins + progs[k].n_ins);
+        D.consts.emplace_back(progs[k].consts, progs[k].consts + progs[k].n_const);
+    }
+    if (z_pos) D.z_pos.assign(z_pos, z_pos + n_progs);
+    D.depth = depth; D.min_density = min_density; D.on = true;
+    std::vector<hps_expr_ins> ins;
+    std::vector<double> consts;
+    for (DensityExpr& S : dens) {
+        S.off.clear();
+        for (size_t k = 0; k < S.ins.size(); ++k) {
+            const hps_expr p{(int)S.ins[k].size(), (int)S.consts[k].size(), S.ins[k].data(), S.consts[k].data()};
+            S.off.push_back(expr_append(p, ins, consts));
+        }
+    }
+    if (consts.empty()) consts.push_back(0.0);
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    (void)hipFree(d_dens_ins); (void)hipFree(d_dens_consts); d_dens_ins = nullptr; d_dens_consts = nullptr;
+    HPS_HIP_CHECK(hipMalloc(&d_dens_ins, ins.size()*sizeof(hps_expr_ins)));
+    HPS_HIP_CHECK(hipMalloc(&d_dens_consts, consts.size()*sizeof(double)));
+    HPS_HIP_CHECK(hipMemcpy(d_dens_ins, ins.data(), ins.size()*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
+    HPS_HIP_CHECK(hipMemcpy(d_dens_consts, consts.data(), consts.size()*sizeof(double), hipMemcpyHostToDevice));
+    return HPS_OK;
+}
+
+// UpdateDensityFunction (PlasmaParticleContainer.cpp:211-217): std::map::lower_bound -- the first entry with z_pos >= z, the
+// last one beyond the table
+void Engine::density_begin_step (double ct)
+{
+    dens_z = ct;
+    for (DensityExpr& S : dens) {
+        if (!S.on || S.z_pos.empty()) { S.cur = 0; continue; }
+        const size_t k = std::lower_bound(S.z_pos.begin(), S.z_pos.end(), ct) - S.z_pos.begin();
+        S.cur = (int)std::min(k, S.z_pos.size() - 1);
+    }
+}
+
+DensityProgram Engine::density_program (int species) const
+{
+    const DensityExpr& S = dens[species];
+    if (!S.on) return DensityProgram{nullptr, 0, nullptr, 0.0, 0.0};
+    return DensityProgram{d_dens_ins + S.off[S.cur], (int)S.ins[S.cur].size(), d_dens_consts, dens_z, S.min_density};
+}
+
 } // namespace hps
+
+extern "C" int hps_engine_set_density_expr (void* h, int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density)
+{
+    HPS_REQUIRE(h, "hps_engine_set_density_expr: null engine");
+    return static_cast<hps::Engine*>(h)->set_density_expr(species, n_progs, progs, z_pos, min_density);
+}

@@ -95,6 +95,65 @@ PLASMA_THERMAL_DEFAULT = dict(plasma_u_mean=(0.0, 0.0, 0.0), plasma_u_std=None, 
                               plasmas_do_symmetrize=0, plasmas_prevent_centered_particle=0)
 
 
+# Parsed plasma densities: <plasma>.density(x,y,z), min_density and density_table_file of the species "plasma" and "ion", and
+# plasmas.density(x,y,z) for both (PlasmaParticleContainer.cpp:90-119).  Kept apart from _DEFAULT like
+# PLASMA_INIT_DEFAULT and applied by SliceEngine through hps_engine_set_density_expr; None = not given.  An expression is a string
+# in the input file's syntax (or a number) over x, y, z whose value is the density itself; a species' own key wins over the
+# shared one; a table is a path (read_density_table) or a list of (position, expression) pairs; density_constants is
+# my_constants.  A species with an expression or a table does not use the tables of set_density_profile.
+DENSITY_EXPR_DEFAULT = dict(plasma_density_expr=None, ion_density_expr=None, plasmas_density_expr=None,
+                            plasma_min_density=None, ion_min_density=None, plasma_density_table=None, ion_density_table=None,
+                            density_constants=None)
+
+
+def read_density_table(path):
+    """<plasma>.density_table_file: one `position expression` per line, the expression being the rest of the line
+    (PlasmaParticleContainer.cpp:107-116); a line that does not start with a number, or has nothing behind it, is skipped.
+    -> [(position, expression)] in ascending order of position; of two lines with one position the first stays (std::map)."""
+    table = {}
+    with open(path) as f:
+        for line in f:
+            parts = line.split(None, 1)
+            if len(parts) < 2 or not parts[1].strip():
+                continue
+            try:
+                pos = float(parts[0])
+            except ValueError:
+                continue
+            table.setdefault(pos, parts[1].strip())
+    if not table:
+        raise ValueError(f"unable to get any data out of the density table file {path!r}")
+    return sorted(table.items())
+
+
+def density_exprs(deck):
+    """{species index: (expression or table, constants, min_density)} of the deck's DENSITY_EXPR_DEFAULT keys; a species without
+    them is absent.  ValueError: an expression and a table for one species (the reference asserts "Can only use one plasma
+    density from either 'density(x,y,z)' or 'density_table_file', not both"), a min_density without either, or keys for the
+    ion species of a deck without one."""
+    out = {}
+    for sp, name in enumerate(("plasma", "ion")):
+        own, table, mind = deck.get(name + "_density_expr"), deck.get(name + "_density_table"), deck.get(name + "_min_density")
+        if sp == 1 and not deck.get("ion_on", 0):
+            if own is not None or table is not None or mind is not None:
+                raise ValueError("ion_density_expr / ion_density_table / ion_min_density: the deck has no ion species")
+            continue
+        text = own if own is not None else deck.get("plasmas_density_expr")
+        if sp == 0 and not deck.get("plasma_density", 0.0) > 0.0 and own is None and table is None:
+            continue      # (plasmas.density(x,y,z) of a deck without the species "plasma" is for the ions alone)
+        if text is not None and table is not None:
+            raise ValueError(f"{name}: can only use one plasma density from either '{name}_density_expr' (or plasmas_density_expr) "
+                             f"or '{name}_density_table', not both")
+        if table is not None:
+            text = read_density_table(table) if isinstance(table, (str, bytes)) or hasattr(table, "__fspath__") else list(table)
+        if text is None:
+            if mind is not None:
+                raise ValueError(f"{name}_min_density needs {name}_density_expr, plasmas_density_expr or {name}_density_table")
+            continue
+        out[sp] = (text, deck.get("density_constants"), 0.0 if mind is None else float(mind))
+    return out
+
+
 def thermal_u_std(deck, species="plasma"):
     """u_std of species "plasma" / "ion" from the deck's <species>_u_std or <species>_temperature_in_ev:
     u_std = sqrt(T q_e / (M c^2)) in every direction with the species' mass M in kg (PlasmaParticleContainer.cpp:138-145; a
@@ -800,6 +859,25 @@ def production_lwfa(n=64, nz=100, max_step=10):
     ct = np.array([SI["c"] * d["dt"] * k for k in range(max_step + 2)])
     ft = np.where(ct > 0.0, np.where(ct > Lramp, 1.0, 0.5 * (1.0 - np.cos(np.pi * ct / Lramp))), 0.0)
     return d, (r_tab, fr, ct, ft)
+
+
+# examples/get_started/inputs_lwfa: my_constants as the file writes them (they resolve through one another), and
+# plasma.density(x,y,z) with the line breaks of the file's quoted value
+LWFA_CONSTANTS = dict(kp_inv="clight/wp", kp="wp/clight", wp="sqrt( ne * q_e^2/(m_e *epsilon0) )", ne=1.0505e23, Rm="3*kp_inv",
+                      Lramp=6.e-3)
+LWFA_DENSITY = ("ne*(1+4*(x^2+y^2)/(kp^2 * Rm^4 ) ) *\n"
+                "                         if (z > Lramp, 1, .5*(1-cos(pi*z/Lramp))) *\n"
+                "                         if (z>0,1,0)")
+
+
+def production_lwfa_parsed(n=64, nz=100, max_step=10):
+    """production_lwfa() with the density as examples/get_started/inputs_lwfa writes it: plasma.density(x,y,z) as one parsed
+    function with the file's my_constants (DENSITY_EXPR_DEFAULT), evaluated on the device per lattice point; no tables.
+    -> deck"""
+    d, _ = production_lwfa(n, nz, max_step)
+    d.update(DENSITY_EXPR_DEFAULT)
+    d.update(plasma_density_expr=LWFA_DENSITY, density_constants=dict(LWFA_CONSTANTS))
+    return d
 
 
 def gaussian_weight_SI():

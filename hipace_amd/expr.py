@@ -140,8 +140,9 @@ _CMP = {ast.Lt: "lt", ast.LtE: "le", ast.Gt: "gt", ast.GtE: "ge", ast.Eq: "eq", 
 
 
 def _to_python(text):
-    """the reference's syntax as a Python expression: ^ is **, if( is a call"""
-    return re.sub(r"\bif\s*\(", "_if_(", text.replace("^", "**")).strip()
+    """the reference's syntax as a Python expression: ^ is **, if( and if ( are a call, a line break inside a quoted
+    multi-line value of the input file is white space"""
+    return re.sub(r"\bif\s*\(", "_if_(", re.sub(r"\s+", " ", text).replace("^", "**")).strip()
 
 
 def _token(text, node):
@@ -310,6 +311,30 @@ def compile_expr(text, variables=("x", "y", "z", "t"), constants=None, fold=True
     if len(variables) > MAX_VARS:
         raise ValueError(f"expression {text!r}: more than {MAX_VARS} variables")
     return _Compiler(text, variables, constants, fold, ()).compile()
+
+
+def compile_density(text_or_table, constants=None):
+    """<plasma>.density(x,y,z) -- a string, a number or a Program -- or a density table -- a list of (position, string) pairs
+    in the order given -- over ("x", "y", "z").  -> (Programs, positions or None)"""
+    def one(v):
+        if isinstance(v, Program):
+            return v
+        return compile_expr(v, ("x", "y", "z"), constants)
+    if isinstance(text_or_table, (str, int, float, Program)):
+        return [one(text_or_table)], None
+    pairs = list(text_or_table)
+    if not pairs or any(not hasattr(p, "__len__") or isinstance(p, (str, bytes)) or len(p) != 2 for p in pairs):
+        raise ValueError("density table: a non-empty list of (position, expression) pairs is expected")
+    return [one(e) for _, e in pairs], [float(z) for z, _ in pairs]
+
+
+def c_programs(programs):
+    """-> (ctypes array of hps_expr, keep-alive)"""
+    arr, keep = (Expr * len(programs))(), []
+    for q, p in enumerate(programs):
+        arr[q], k = p.c_struct()
+        keep.append(k)
+    return arr, keep
 
 
 def compile_components(comps, what, constants=None, variables=("x", "y", "z", "t")):

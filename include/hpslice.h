@@ -539,10 +539,11 @@ int hps_engine_set_tiling (void* handle, int tile_size, int sort_period);
 int hps_engine_fallbacks (void* handle, long* n_fallback_host);
 /* Plasma density profile (InitParticles evaluates <plasma>.density(x,y,z) per particle with z = c t,
  * PlasmaParticleContainerInit.cpp:246-313; UpdateDensityFunction / density_table_file, PlasmaParticleContainer.cpp:98-117,
- * 211-217).  The input parser is out of scope; the profile is tabulated: n(x, y, ct) = <species>.density * f_r(sqrt(x^2 +
- * y^2)) * f_t(c t), both piecewise linear (constant beyond the ends of a table; n = 0 entries: factor 1), t = hipace.dt *
- * step.  Plasma channels and density ramps are of this form.  A lattice point whose density is <= 0 carries no particle
- * (min_density = 0).  Applies to every plasma species from the next hps_engine_begin_step on. */
+ * 211-217).  The tabulated form of the density: n(x, y, ct) = <species>.density * f_r(sqrt(x^2 + y^2)) * f_t(c t), both
+ * piecewise linear (constant beyond the ends of a table; n = 0 entries: factor 1), t = hipace.dt * step.  Plasma channels and
+ * density ramps are of this form.  A lattice point whose density is <= 0 carries no particle (min_density = 0).  Applies to
+ * every plasma species from the next hps_engine_begin_step on, except a species whose density is a parsed function
+ * (hps_engine_set_density_expr below: the general form, per species). */
 int hps_engine_set_density_profile (void* handle, int nr, const double* r_host, const double* fr_host, int nt,
                                     const double* ct_host, const double* ft_host);
 /* The plasma fine patch and the hollow core (InitParticles, PlasmaParticleContainerInit.cpp:36-313; get_position_unit_cell_fine,
@@ -711,7 +712,8 @@ int hps_salame_scale_beam_slice (double* w_dev, long n, double W, hps_stream str
  * One controller per rank (or pipeline stage), created from the deck (dt_adaptive and the fields behind it; beam charge
  * and mass, beam_charge = 0: the beam does not set dt; units; the plasma species' densities and charges).  Its dt starts
  * at 0.  rho_max(z) = max(|adaptive_density q_e|, |plasma_charge n(0,0,z)|, |ion_charge n_ion(0,0,z)|) with n(0,0,z) the
- * species' density on the axis, n0 f_r(0) f_t(z) (MultiPlasma::maxChargeDensity). */
+ * species' density on the axis, n0 f_r(0) f_t(z) (MultiPlasma::maxChargeDensity), or the species' parsed density at (0, 0, z)
+ * (hps_adaptive_set_density_expr below). */
 int hps_adaptive_create (const hps_deck* deck, void** handle);
 /* the tables of hps_engine_set_density_profile (pass the engine's); replaces the profile, none = factor 1 */
 int hps_adaptive_set_density_profile (void* handle, int nr, const double* r_host, const double* fr_host, int nt,
@@ -928,6 +930,28 @@ int hps_expr_eval (const hps_expr* prog, int n_vars, long n, const double* const
  * them, as in the reference; the plasma never sees them.  HPS_ERR_ARG: a null handle, a call after the first
  * hps_engine_begin_step, a program hps_expr_check refuses (with its message). */
 int hps_engine_set_beam_external_fields (void* handle, const hps_expr* E3, const hps_expr* B3);
+/* Engine: <plasma>.density(x,y,z), min_density and density_table_file (PlasmaParticleContainer.cpp:90-119, 211-217;
+ * InitParticles, PlasmaParticleContainerInit.cpp:246-313) for species 0 (plasma) or 1 (ion): progs are n_progs >= 1
+ * programs over exactly (x, y, z).  z_pos = NULL with n_progs = 1 is density(x,y,z); otherwise z_pos holds n_progs strictly
+ * ascending positions and the call is the density table: on a step with z = c t the program in force is the first entry with
+ * z_pos >= z, the last one beyond the table (std::map::lower_bound, UpdateDensityFunction).  The program's value at a lattice
+ * point (x, y, c t) is the density itself, in the deck's units: for this species it replaces <species>_density f_r f_t of
+ * hps_engine_set_density_profile, in the sheet's weights (w = value * scale_fac, one multiplication; scale_fac = the cell
+ * volume in SI units / ppc or fine ppc, / 4 with do_symmetrize) and in the laser's initial chi (there without min_density, as
+ * SetInitialChi).  A slot holds a particle iff it passes the radius, hollow-core and prevent_centered_particle tests and
+ * value > min_density; the slot count stays static.  The deck's plasma_density / ion_density keep every other role (they
+ * switch the species on).  The other species, and an engine without programs, keep the tables and launch the kernels they
+ * launched before.  The programs are checked, packed into one device image per engine and kept for its life.  HPS_ERR_ARG: a
+ * null handle, a call after the first hps_engine_begin_step, species 1 without ion_on, species 0 with plasma_density <= 0,
+ * n_progs < 1, positions that are not strictly ascending, a program hps_expr_check refuses for three variables (with its
+ * message). */
+int hps_engine_set_density_expr (void* handle, int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density);
+/* The same programs for the adaptive time step's controller (host only): rho_max(z) takes |charge * prog(0, 0, z)| for that
+ * species (0 plasma, 1 ion) with the program in force at z, evaluated by the routine of hps_expr_eval_host, in place of
+ * |charge density f_r(0) f_t(z)|. */
+int hps_adaptive_set_density_expr (void* handle, int species, int n_progs, const hps_expr* progs, const double* z_pos);
+/* *out_host = rho_max(z) (MultiPlasma::maxChargeDensity, see hps_adaptive_create); changes nothing */
+int hps_adaptive_rho_max (void* handle, double z, double* out_host);
 
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);
