@@ -582,8 +582,7 @@ int Engine::collide_slice (int islice)
 {
     for (size_t i = 0; i < coll.size(); ++i) {
         const Collision& c = coll[i];
-        const hps_plasma* sp[2] = {&pl, &ion.pl};
-        const double q[2] = {d.plasma_charge, d.ion_charge}, m[2] = {d.plasma_mass, d.ion_mass};
+        const Species &A = sp[c.a], &B = sp[c.b];
         if (c.beam) {
             // Species 1 is the beam's slice behind its push and the slipped-particle shift (Hipace.cpp:704-712).  A static beam
             // (hipace.dt = 0) sits in the per-slice blocks, and every pair's s is 0 there: nothing is launched.  No beam: nothing.
@@ -594,11 +593,11 @@ int Engine::collide_slice (int islice)
             const double wp = std::sqrt(d.background_density_SI*SI_QE*SI_QE/(SI_EP0*SI_ME));
             const double dt = gm.normalized ? step_dt/wp : step_dt;      // m_dt, the time step of the run (not dz)
             const CollBeam bs{bm, d_B, p, 0, nbeam, 0};
-            if (int e = collide_beam_plasma(coll_scratch, bs, bound, *sp[c.b], gm, d.nx, d.ny, d.beam_charge, d.beam_mass != 0.0 ? d.beam_mass : 1.0,
-                                            q[c.b], m[c.b], c.b, c.coulomb_log, d.background_density_SI, dt, c.seed, (int)i, step_index, islice, st)) return e;
+            if (int e = collide_beam_plasma(coll_scratch, bs, bound, B.pl, gm, d.nx, d.ny, d.beam_charge, d.beam_mass != 0.0 ? d.beam_mass : 1.0,
+                                            B.charge, B.mass, B.can_ionize, c.coulomb_log, d.background_density_SI, dt, c.seed, (int)i, step_index, islice, st)) return e;
             continue;
         }
-        if (int e = collide_plasma(coll_scratch, *sp[c.a], *sp[c.b], c.a == c.b, gm, d.nx, d.ny, q[c.a], m[c.a], c.a, q[c.b], m[c.b], c.b,
+        if (int e = collide_plasma(coll_scratch, A.pl, B.pl, c.a == c.b, gm, d.nx, d.ny, A.charge, A.mass, A.can_ionize, B.charge, B.mass, B.can_ionize,
                                    c.coulomb_log, d.background_density_SI, c.seed, (int)i, step_index, islice, st)) return e;
     }
     return HPS_OK;

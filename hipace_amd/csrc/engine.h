@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include <algorithm>
+#include <array>
 #include <vector>
 #include "tiling.h"
 #include "mg_gate.h"
@@ -63,16 +64,11 @@ struct Engine {
     hipStream_t st = nullptr;
     bool st_pooled = false; int st_device = 0;       // the stream came from the per-device pool (engine.hip: create_engine_stream)
     hps_slab slab{};
-    hps_plasma pl{};
-    double* pl_real = nullptr;
-    long np = 0;                   // particles of the first species NOW (grows when the species "ion" releases electrons)
-    long np_cap = 0, np_init = 0;  // capacity of its arrays; particles InitParticles creates
-    // species "ion" with ADK field ionisation (ionization.hip): tile-sorted once per step (ions hardly move); released
-    // electrons are appended to `pl` behind the tile-sorted body and run through the per-particle kernels until the next
-    // re-sort.  Counters on the device {electrons, overflow, blocks done, ionised}, the count comes back through mapped
+    // ADK field ionisation of the species "ion" (ionization.hip): it is tile-sorted once per step (ions hardly move); released
+    // electrons are appended to the plasma's sheet behind the tile-sorted body and run through the per-particle kernels until
+    // the next re-sort.  Counters on the device {electrons, overflow, blocks done, ionised}, the count comes back through mapped
     // host memory (no stream synchronisation).
-    struct Ions { hps_plasma pl{}, pl_alt{}; double *real = nullptr, *real_alt = nullptr; Tiling* tiling = nullptr; long n = 0;
-                  double* d_adk = nullptr; unsigned long long* d_cnt = nullptr; long long* h_cnt = nullptr; long long* h_cnt_dev = nullptr;
+    struct Ions { double* d_adk = nullptr; unsigned long long* d_cnt = nullptr; long long* h_cnt = nullptr; long long* h_cnt_dev = nullptr;
                   long long seq = 0; long n_ionized = 0; bool pending = false; int* d_tile_flag = nullptr;
                   double* d_fbound = nullptr;       // [5][tiles] field maxima of the slice (k_ion_field_bounds; HPS_ION_TILE_SKIP=0: off)
                 } ion;
@@ -80,29 +76,23 @@ struct Engine {
     std::vector<double> prof_r, prof_t, prof_f_t; double* d_prof_r = nullptr; double prof_ft = 1.0;
     // <plasma>.fine_patch / fine_ppc / fine_transition_cells / hollow_core_radius (plasma_init.hip): the level map
     // [ny][nx] (0 coarse, 1..T transition, T + 1 fine) and the x-fastest list of the cells with level > 0, shared by the species
-    int fine_ppc[2] = {0, 0}, ion_fine_ppc[2] = {0, 0}; double hollow_core_radius = 0.0;
+    double hollow_core_radius = 0.0;
     bool fine_patch_set = false; int fine_T = 0; long fine_ncells = 0; int* d_fine_level = nullptr; int* d_fine_cells = nullptr;
     // <plasma>.u_mean / u_std (temperature_in_ev), plasmas.do_symmetrize, prevent_centered_particle (plasma_init.hip):
-    // species 0 = plasma, 1 = ion; the two switches hold for both species
+    // the momenta per species (Species::thermal); the two switches hold for both species
     struct Thermal { double u_mean[3] = {0.0, 0.0, 0.0}, u_std[3] = {0.0, 0.0, 0.0}; unsigned long long seed = 0;
                      bool warm () const { for (int q = 0; q < 3; ++q) if (u_mean[q] != 0.0 || u_std[q] != 0.0) return true; return false; }
-                   } thermal[2];
+                   };
     bool do_symmetrize = false, prevent_centered = false;
     bool shifted (const int ppc[2], int dir) const { return prevent_centered && (dir == 0 ? d.nx : d.ny) % 2 == 1 && ppc[dir] % 2 == 1; }
-    // does this species' sheet come from k_init_plasma_warm?  (false: the kernels and arguments of a deck without these keys)
-    bool warm_init (int species) const {
-        const int* ppc = species == 0 ? d.plasma_ppc : d.ion_ppc;
-        return thermal[species].warm() || do_symmetrize || shifted(ppc, 0) || shifted(ppc, 1);
-    }
     int set_plasma_momentum (int species, const double* u_mean, const double* u_std, unsigned long long seed);
     int set_plasma_symmetry (int symmetrize, int prevent_centered_particle);
-    long sheet_slots (const int ppc[2], const int fine[2]) const;
     int alloc_sheets ();
     int set_plasma_init (const int* plasma_fine, const int* ion_fine, double hollow_core);
     int set_fine_patch (const unsigned char* mask_host, int transition_cells);
     // fused push(k) + deposit(k-1) (k_advance_deposit_tiled): ahead_for = slice whose plasma currents are already deposited
     bool fuse_push_deposit = false; int ahead_for = -2;
-    long fallback_div = 256;                    // re-sort once more than np / fallback_div particle visits since the last sort left their tile's halo (HPS_SORT_FALLBACK_DIV)
+    long fallback_div = 256;                    // re-sort once more than el.pl.n / fallback_div particle visits since the last sort left their tile's halo (HPS_SORT_FALLBACK_DIV)
     bool gate_push = true;                      // push enqueued behind the multigrid's V-cycles, gated on its stopping rule (HPS_GATED_PUSH=0: off)
     int step_index = -1;           // physical time step that has begun (density profile's time factor, ionisation draws)
     int next_step = -1;            // hps_engine_set_step: the step the next begin_step starts (-1: the one after step_index)
@@ -117,36 +107,60 @@ struct Engine {
     struct BeamExt { bool on = false; hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; int depth = 0; } bext;
     int set_beam_external_fields (const hps_expr* E3, const hps_expr* B3);
     // <plasma>.density(x,y,z) / density_table_file as expression programs (hps_engine_set_density_expr, plasma_init.hip, DESIGN
-    // 8m), species 0 = plasma, 1 = ion: the species' programs as given (z_pos empty: the one program of density(x,y,z)), the
+    // 8m), per species (Species::dens): the species' programs as given (z_pos empty: the one program of density(x,y,z)), the
     // offset of each in the engine's one device image (both species' instructions, the pooled constants), the deepest stack
     // of the species' programs, and the entry in force in the step that has begun.  on = false: the tables, the kernels as they were.
     struct DensityExpr { bool on = false; std::vector<std::vector<hps_expr_ins>> ins; std::vector<std::vector<double>> consts;
-                         std::vector<double> z_pos; std::vector<int> off; int depth = 0; double min_density = 0.0; int cur = 0; } dens[2];
+                         std::vector<double> z_pos; std::vector<int> off; int depth = 0; double min_density = 0.0; int cur = 0; };
     hps_expr_ins* d_dens_ins = nullptr; double* d_dens_consts = nullptr; double dens_z = 0.0;      // dens_z: c t of the step that has begun
     int set_density_expr (int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density);
     void density_begin_step (double ct);                  // UpdateDensityFunction(c t): the table entry in force
     DensityProgram density_program (int species) const;   // n_ins = 0: this species keeps the tables
-    size_t density_lds (int species) const { return dens[species].on ? (size_t)std::max(dens[species].depth - 1, 0)*256*sizeof(double) : 0; }
+    size_t density_lds (int species) const { const DensityExpr& D = sp[species].dens; return D.on ? (size_t)std::max(D.depth - 1, 0)*256*sizeof(double) : 0; }
+    // One plasma species of the slice: sp[0] the plasma (the electrons), sp[1] the species "ion".  The parameters are the deck's
+    // plasma_* / ion_* fields, read once (Engine::create; keyed: the first begin_step); fine_ppc, thermal and dens are what
+    // hps_engine_set_plasma_init / _momentum / _density_expr have given.
+    struct Species {
+        int index = 0;                                  // 0 or 1: the species' number in the C ABI and in the key of its random draws
+        // the sheet and the second buffer of the tile sort (sort.hip), each one block of 11 arrays + idcpu, ion_lev (soa_arrays);
+        // the particles NOW are pl.n (the plasma's grows when the species "ion" releases electrons)
+        hps_plasma pl{}, pl_alt{}; double *real = nullptr, *real_alt = nullptr; Tiling* tiling = nullptr;
+        long cap = 0, n_init = 0;                       // capacity of the arrays; particles InitParticles creates
+        int ppc[2] = {0, 0}, fine_ppc[2] = {0, 0}; double density = 0.0, charge = 0.0, mass = 0.0;
+        int init_level = 0, can_ionize = 0, keyed = 0;  // keyed: the lattice index in the id bits (the ions; electrons that collide)
+        bool temp_push = false;                         // pushed to temporary slices from x_prev: predictor-corrector; the plasma under SALAME
+        Thermal thermal; DensityExpr dens;
+        bool present () const { return density > 0.0; } // is the species in the deck
+        // Without pushes to a temporary slice every push commits its state, so x_prev == x and y_prev == y at all times
+        // (PlasmaParticleAdvance.cpp:176-188): alias them -- two arrays less to write per push and to move per re-sort.
+        // The C ABI keeps 11 pointers; the kernels skip the second store when two coincide.
+        bool alias_prev () const { return !temp_push; }
+    } sp[2];
+    Species &el = sp[0], &ions = sp[1];
+    // does this species' sheet come from k_init_plasma_warm?  (false: the kernels and arguments of a deck without these keys)
+    bool warm_init (const Species& s) const { return s.thermal.warm() || do_symmetrize || shifted(s.ppc, 0) || shifted(s.ppc, 1); }
+    long sheet_slots (const Species& s) const;
+    int init_sheet (Species& s);               // InitParticles of one species' sheet: the warm, the fine or the plain kernel
+    int sort_sheet (Species& s);               // tile sort into the second buffer, then the two change places
     bool host_beam = false;        // hps_engine_set_beam_particles has given the beam
     double* d_mom = nullptr;       // hipace.dt = adaptive: beam moments [nz + 1][4] (beam.hip: k_beam_partition<true>)
     IonArgs ion_args (int islice);             // ionization.hip: kernel arguments of this slice's ionisation
     int ionize_slice (int islice);             // ...: launch of the per-particle form
     int ionize_collect ();                     // ...: wait for the electron count of the slice
     int ion_field_bounds ();                   // ...: per-tile field maxima for the tile skip of the ions' push
-    hps_plasma tail_of (const hps_plasma& p, long first, long n) const;
     bool fold_tail = true;                     // the particles behind the tile-sorted body ride in the tile kernels' launches (HPS_FOLD_TAIL=0: off)
-    TailWork fold_tail_of (const hps_plasma& p, const Tiling* T, long margin, long* covered) const;
-    int species_deposit (const hps_plasma& p, Tiling* T, const int comp[6], double charge, double mass, int can_ionize, const BeamPairWork* beam = nullptr);
+    TailWork fold_tail_of (const Species& s, long margin, long* covered) const;
+    // (go: the gate word of an iteration of the predictor-corrector loop's device-side control, null otherwise)
+    int species_deposit (const Species& s, const int comp[6], const BeamPairWork* beam = nullptr, const int* go = nullptr);
     bool valid_by_w = true;                    // HPS_VALID_BY_W=0: off.  The depositions take "weight != 0" for the valid bit of idcpu and do not read it (PartConsts::valid_by_w:
                                                // 33.5 MB less per kernel at 1024^2 x 4 ppc -- no time gained with one stage on the GPU, +1 % with three in flight: r04g_ab_inflight_byte_cuts.txt)
     bool post_in_push = true;                  // the gated plasma push posts the Bx/By solve's norms to the host (HPS_POST_IN_PUSH=0: k_post_norms, a launch of its own)
     bool fold_hierarchy = true;                // the multigrid's coefficient hierarchy in the -grad Psi / Sx, Sy launch (HPS_FOLD_HIERARCHY=0: in mg_solve1_begin)
     bool fold_beam = true;                     // the static beam's two deposits of a slice as extra workgroups of the plasma's deposition (HPS_FOLD_BEAM=0: a launch of their own)
-    int species_explicit (const hps_plasma& p, Tiling* T, const int cache[4], const int depos[2], double charge, double mass, int can_ionize);
-    int species_advance (const hps_plasma& p, Tiling* T, const int comp[5], double charge, double mass, int temp_slice, int can_ionize);
-    // tile-sorted sheet (sort.hip): second SoA buffer + tiling state
-    Tiling* tiling = nullptr; int tile_size = 16, sort_period = 128, since_sort = 0;
-    hps_plasma pl_alt{}; double* pl_real_alt = nullptr;
+    int species_explicit (const Species& s, const int cache[4], const int depos[2]);
+    int species_advance (const Species& s, const int comp[5], int temp_slice, const int* go = nullptr);
+    // the tile sort (sort.hip) and the plasma's re-sort rule
+    int tile_size = 16, sort_period = 128, since_sort = 0;
     int* d_nfallback = nullptr;                 // word 0 of the multigrid norm buffer's header slot (mg_rider)
     const int* h_nfallback = nullptr;           // its pinned image, refreshed by every multigrid solve
     long fb_at_sort = 0; int n_sorts = 0;       // adaptive re-sort: fallbacks at the last sort, number of sorts
@@ -276,13 +290,16 @@ struct Engine {
 int ion_create (Engine& E);                                                  // ionization.hip
 void ion_destroy (Engine& E);
 unsigned event_flags (bool timing);                                           // engine.hip
+// The 11 double arrays of a sheet in the order of its block, and what is built on it (engine.hip): a block of cap slots with
+// idcpu and ion_lev (alias: x_prev, y_prev are x, y -- Species::alias_prev) and its release
+std::array<double**, 11> soa_arrays (hps_plasma& p);
+int alloc_soa (hps_plasma& p, double*& real, long cap, bool alias);
+void free_soa (hps_plasma& p, double*& real);
 // plasma_init.hip: InitParticles with the fine patch and / or the hollow core for one species' sheet
 // (and, with a density program, for the plain lattice: init_slot's rule of the weight, one place)
-int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
-                      double radius_sq, int species);
+int init_plasma_fine (Engine& E, const Engine::Species& s, double radius_sq);
 // ...: the same sheet with Gaussian momenta, its mirror copies and / or the lattice shifted off the axis (Engine::warm_init)
-int init_plasma_warm (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
-                      double radius_sq, int species);
+int init_plasma_warm (Engine& E, const Engine::Species& s, double radius_sq);
 int laser_create (Engine& E);                                                // laser.hip
 void laser_destroy (Engine& E);
 int laser_begin_step (Engine& E);

@@ -341,9 +341,8 @@ Engine::~Engine ()
 {
     if (ps) hps_poisson_destroy(ps);
     if (mg) hps_mg_destroy(mg);
-    (void)hipFree(slab.p); (void)hipFree(pl_real); (void)hipFree(pl.idcpu); (void)hipFree(pl.ion_lev);
-    delete tiling;
-    (void)hipFree(pl_real_alt); (void)hipFree(pl_alt.idcpu); (void)hipFree(pl_alt.ion_lev); 
+    (void)hipFree(slab.p); free_soa(el.pl, el.real); free_soa(el.pl_alt, el.real_alt);      // (the ions' sheets: ion_destroy)
+    delete el.tiling;
     (void)hipFree(staging); (void)hipFree(d_open_mom); (void)hipFree(beam_data); (void)hipFree(beam_init);
     (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr); (void)hipFree(d_B); (void)hipFree(d_nfront);
     (void)hipFree(d_mom); (void)hipFree(d_sal); (void)hipFree(bext.d_ins); (void)hipFree(bext.d_consts);
@@ -646,46 +645,53 @@ static hipError_t create_engine_stream (hipStream_t* s, int device, bool* pooled
 }
 
 // Slots of a species' sheet: ppc per cell, and fine_ppc in the cells of the fine patch and its transition
-long Engine::sheet_slots (const int ppc[2], const int fine[2]) const
+long Engine::sheet_slots (const Species& s) const
 {
-    const long cells = (long)d.nx*d.ny, nc = (long)ppc[0]*ppc[1];
+    if (!s.present()) return 0;
+    const long cells = (long)d.nx*d.ny, nc = (long)s.ppc[0]*s.ppc[1];
     const long copies = do_symmetrize ? 4 : 1;       // do_symmetrize: the sheet and its three mirror copies
-    if (!(fine_patch_set && fine[0] > 0)) return copies*nc*cells;
-    return copies*(nc*cells + ((long)fine[0]*fine[1] - nc)*fine_ncells);
+    if (!(fine_patch_set && s.fine_ppc[0] > 0)) return copies*nc*cells;
+    return copies*(nc*cells + ((long)s.fine_ppc[0]*s.fine_ppc[1] - nc)*fine_ncells);
+}
+
+std::array<double**, 11> soa_arrays (hps_plasma& p)
+{
+    return {&p.x, &p.y, &p.w, &p.ux, &p.uy, &p.psi, &p.x_prev, &p.y_prev, &p.ux_half, &p.uy_half, &p.psi_half};
+}
+int alloc_soa (hps_plasma& p, double*& real, long cap, bool alias)
+{
+    HPS_HIP_CHECK(hipMalloc(&real, (size_t)cap*11*sizeof(double)));
+    const auto arr = soa_arrays(p);
+    for (int k = 0; k < 11; ++k) *arr[k] = real + (size_t)k*cap;
+    if (alias) { p.x_prev = p.x; p.y_prev = p.y; }
+    HPS_HIP_CHECK(hipMalloc(&p.idcpu, (size_t)cap*sizeof(uint64_t)));
+    HPS_HIP_CHECK(hipMalloc(&p.ion_lev, (size_t)cap*sizeof(int32_t)));
+    return HPS_OK;
+}
+void free_soa (hps_plasma& p, double*& real)
+{
+    (void)hipFree(real); (void)hipFree(p.idcpu); (void)hipFree(p.ion_lev);
+    real = nullptr; p = hps_plasma{};
+}
+static hps_plasma tail_of (const hps_plasma& p, long first, long n)
+{
+    hps_plasma t = p;
+    for (double** a : soa_arrays(t)) *a += first;      // (x_prev / y_prev stay aliased to x / y where they were)
+    t.idcpu += first; t.ion_lev += first; t.n = n;
+    return t;
 }
 
 // The sheets of both species, sized by what InitParticles creates; hps_engine_set_plasma_init / hps_engine_set_fine_patch
 // call it again (before the first step: nothing else holds a pointer into them yet)
 int Engine::alloc_sheets ()
 {
-    (void)hipFree(pl_real); (void)hipFree(pl.idcpu); (void)hipFree(pl.ion_lev); pl_real = nullptr;
-    (void)hipFree(ion.real); (void)hipFree(ion.pl.idcpu); (void)hipFree(ion.pl.ion_lev); ion.real = nullptr;
-    std::memset(&ion.pl, 0, sizeof(ion.pl));
-    np = (d.plasma_density > 0.0) ? sheet_slots(d.plasma_ppc, fine_ppc) : 0;
-    np_init = np; np_cap = np;
-    if (d.ion_on) {
-        ion.n = sheet_slots(d.ion_ppc, ion_fine_ppc);
-        // every ion can release Z - initial level electrons into the first species
-        np_cap = np_init + ion.n*(long)(d.ion_Z - d.ion_init_level);
+    for (Species& s : sp) { free_soa(s.pl, s.real); s.n_init = s.cap = sheet_slots(s); }
+    // every ion can release Z - initial level electrons into the first species
+    if (ions.present()) el.cap = el.n_init + ions.n_init*(long)(d.ion_Z - d.ion_init_level);
+    for (Species& s : sp) {
+        s.pl.n = s.n_init;
+        if (s.cap > 0) { if (int e = alloc_soa(s.pl, s.real, s.cap, s.alias_prev())) return e; }
     }
-    std::memset(&pl, 0, sizeof(pl));
-    pl.n = np;
-    auto alloc_sheet = [&] (hps_plasma& p, double*& real, long cap, bool alias) -> int {
-        HPS_HIP_CHECK(hipMalloc(&real, (size_t)cap*11*sizeof(double)));
-        double** arr[11] = {&p.x, &p.y, &p.w, &p.ux, &p.uy, &p.psi, &p.x_prev, &p.y_prev, &p.ux_half, &p.uy_half, &p.psi_half};
-        for (int k = 0; k < 11; ++k) *arr[k] = real + (size_t)k*cap;
-        // explicit solver: every push commits its state (temp_slice = false), so x_prev == x and y_prev == y at
-        // all times (PlasmaParticleAdvance.cpp:176-188): alias them -- two arrays less to write per push and to
-        // move per re-sort.  The C ABI keeps 11 pointers; the kernels skip the second store when two coincide.
-        // (the predictor-corrector pushes to temporary slices from x_prev: separate arrays there)
-        if (alias) { p.x_prev = p.x; p.y_prev = p.y; }
-        HPS_HIP_CHECK(hipMalloc(&p.idcpu, (size_t)cap*sizeof(uint64_t)));
-        HPS_HIP_CHECK(hipMalloc(&p.ion_lev, (size_t)cap*sizeof(int32_t)));
-        return HPS_OK;
-    };
-    // (SALAME pushes to the temporary slice from x_prev, as the predictor-corrector does: separate arrays there too)
-    if (np_cap > 0) { if (int e = alloc_sheet(pl, pl_real, np_cap, !pc && c_sal < 0)) return e; }
-    if (ion.n > 0) { ion.pl.n = ion.n; if (int e = alloc_sheet(ion.pl, ion.real, ion.n, !pc)) return e; }
     return HPS_OK;
 }
 
@@ -788,6 +794,11 @@ int Engine::create (const hps_deck& deck, int device)
                     "hps_engine_create: the ion species needs ppc, density, mass and charge");
         if (int e = ion_create(*this)) return e;
     }
+    // the species' records: the one place that reads the deck's plasma_* / ion_* spellings.  An absent species keeps density 0
+    // (the plasma's charge and mass also hold for the electrons the species "ion" releases into a deck without plasma)
+    for (int k = 0; k < 2; ++k) { sp[k].index = k; sp[k].can_ionize = k; sp[k].keyed = k; sp[k].temp_push = pc || (k == 0 && c_sal >= 0); }
+    std::copy(d.plasma_ppc, d.plasma_ppc + 2, el.ppc); el.density = d.plasma_density; el.charge = d.plasma_charge; el.mass = d.plasma_mass;
+    if (d.ion_on) { std::copy(d.ion_ppc, d.ion_ppc + 2, ions.ppc); ions.density = d.ion_density; ions.charge = d.ion_charge; ions.mass = d.ion_mass; ions.init_level = d.ion_init_level; }
     if (int e = alloc_sheets()) return e;
     HPS_HIP_CHECK(hipMalloc(&d_laser_sum, sizeof(double)));
     HPS_HIP_CHECK(hipMemset(d_laser_sum, 0, sizeof(double)));
@@ -849,48 +860,57 @@ int Engine::create (const hps_deck& deck, int device)
 
 int Engine::setup_tiling ()
 {
-    if (tile_size == 0 || np_cap == 0 || tiling) return HPS_OK;
-    auto second = [&] (hps_plasma& alt, double*& real, long cap, bool alias) -> int {
-        std::memset(&alt, 0, sizeof(alt));
-        HPS_HIP_CHECK(hipMalloc(&real, (size_t)cap*11*sizeof(double)));
-        double** arr[11] = {&alt.x, &alt.y, &alt.w, &alt.ux, &alt.uy, &alt.psi, &alt.x_prev, &alt.y_prev,
-                            &alt.ux_half, &alt.uy_half, &alt.psi_half};
-        for (int k = 0; k < 11; ++k) *arr[k] = real + (size_t)k*cap;
-        if (alias) { alt.x_prev = alt.x; alt.y_prev = alt.y; }
-        HPS_HIP_CHECK(hipMalloc(&alt.idcpu, (size_t)cap*sizeof(uint64_t)));
-        HPS_HIP_CHECK(hipMalloc(&alt.ion_lev, (size_t)cap*sizeof(int32_t)));
-        return HPS_OK;
-    };
-    if (int e = tiling_create(d.nx, d.ny, tile_size, np_cap, &tiling)) return e;
+    if (tile_size == 0 || el.cap == 0 || el.tiling) return HPS_OK;
+    if (int e = tiling_create(d.nx, d.ny, tile_size, el.cap, &el.tiling)) return e;
     {   const char* v = std::getenv("HPS_VALID_BY_PSI");       // the electrons' push without its idcpu read (tiling.h)
-        tiling->valid_by_psi = (v && std::atoi(v) != 0); }       // (measured: the push takes the same time with and without, off)
-    if (int e = second(pl_alt, pl_real_alt, np_cap, !pc && c_sal < 0)) return e;
-    pl_alt.n = np;
-    if (ion.n > 0) {
+        el.tiling->valid_by_psi = (v && std::atoi(v) != 0); }    // (measured: the push takes the same time with and without, off)
+    if (int e = alloc_soa(el.pl_alt, el.real_alt, el.cap, el.alias_prev())) return e;      // (its n: sort_sheet)
+    if (ions.present()) {
         // the ionisable species on the engine's tile size.  (Round 2 gave a species with at most one particle per cell 32 x 32-cell
         // tiles -- 256 particles in a 16 x 16 tile, one per thread, against the tile's fixed cost.  With the tile skip most of
         // its tiles cost nothing, and its kernels last as long as the few workgroups around the laser's axis that do have
         // charged ions: four times as many of them, a quarter as long -- config 5 989 -> 1004 slices/s.  HPS_ION_TILE=32)
         int ion_ts = tile_size;
         if (const char* v = std::getenv("HPS_ION_TILE")) { const int t = std::atoi(v); if (t == 16 || t == 32) ion_ts = t; }
-        if (int e = tiling_create(d.nx, d.ny, ion_ts, ion.n, &ion.tiling)) return e;
-        if (int e = second(ion.pl_alt, ion.real_alt, ion.n, !pc)) return e;
-        ion.pl_alt.n = ion.n;
-        HPS_HIP_CHECK(hipMalloc(&ion.d_tile_flag, (size_t)ion.tiling->g.ntiles*sizeof(int)));
+        if (int e = tiling_create(d.nx, d.ny, ion_ts, ions.cap, &ions.tiling)) return e;
+        if (int e = alloc_soa(ions.pl_alt, ions.real_alt, ions.cap, ions.alias_prev())) return e;
+        HPS_HIP_CHECK(hipMalloc(&ion.d_tile_flag, (size_t)ions.tiling->g.ntiles*sizeof(int)));
         {   const char* v = std::getenv("HPS_ION_TILE_SKIP");
-            if (!(v && std::atoi(v) == 0)) HPS_HIP_CHECK(hipMalloc(&ion.d_fbound, (size_t)5*ion.tiling->g.ntiles*sizeof(double))); }
+            if (!(v && std::atoi(v) == 0)) HPS_HIP_CHECK(hipMalloc(&ion.d_fbound, (size_t)5*ions.tiling->g.ntiles*sizeof(double))); }
     }
+    return HPS_OK;
+}
+
+int Engine::sort_sheet (Species& s)
+{
+    s.pl_alt.n = s.pl.n;
+    if (int e = tiling_sort(s.tiling, s.pl, s.pl_alt, gm, st)) return e;
+    std::swap(s.pl, s.pl_alt);
+    std::swap(s.real, s.real_alt);
     return HPS_OK;
 }
 
 int Engine::resort ()
 {
-    pl_alt.n = pl.n;
-    if (int e = tiling_sort(tiling, pl, pl_alt, gm, st)) return e;
-    std::swap(pl, pl_alt);
-    std::swap(pl_real, pl_real_alt);
+    if (int e = sort_sheet(el)) return e;
     since_sort = 0; ++n_sorts;
     fb_at_sort = h_nfallback ? *h_nfallback : 0;
+    return HPS_OK;
+}
+
+// InitParticles of one species: every slot of the sheet back on its lattice point, at rest or with its thermal momentum
+int Engine::init_sheet (Species& s)
+{
+    const long n = s.pl.n;
+    if (n == 0) return HPS_OK;
+    const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : std::numeric_limits<double>::infinity();
+    if (warm_init(s)) return init_plasma_warm(*this, s, radius_sq);
+    if (hollow_core_radius > 0.0 || (fine_patch_set && s.fine_ppc[0] > 0) || s.dens.on)      // (a density program: init_slot's kernels)
+        return init_plasma_fine(*this, s, radius_sq);
+    const int nppc = s.ppc[0]*s.ppc[1];
+    hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(n, 256)), dim3(256), 0, st, s.pl, n, d.nx, d.ny, s.ppc[0], s.ppc[1], d.lo[0], d.lo[1],
+                       gm.dx, gm.dy, s.density*(d.si_units ? gm.dx*gm.dy*gm.dz/nppc : 1.0/nppc),      // scale_fac, PlasmaParticleContainerInit.cpp:40-41
+                       s.init_level, s.keyed, d_prof_r, (int)prof_r.size(), prof_ft, radius_sq);
     return HPS_OK;
 }
 
@@ -899,7 +919,7 @@ int Engine::begin_step ()
     HPS_REQUIRE(!(d.dt_adaptive && steps_begun == 0 && d.beam_profile < 0 && !host_beam),
                 "hps_engine_begin_step: hipace.dt = adaptive needs a beam (beam_profile = -1 and no hps_engine_set_beam_particles: the sum of weights is 0)");
     // (PlasmaParticleContainer.cpp:167-169)
-    HPS_REQUIRE(fine_patch_set == (fine_ppc[0] > 0 || ion_fine_ppc[0] > 0),
+    HPS_REQUIRE(fine_patch_set == (el.fine_ppc[0] > 0 || ions.fine_ppc[0] > 0),
                 "hps_engine_begin_step: both fine_ppc (hps_engine_set_plasma_init) and the fine patch (hps_engine_set_fine_patch) must be given to use the fine plasma patch");
     HPS_REQUIRE(!(laser && laser_pulses_set && laser_pulses.empty() && laser_samples.empty() && !step_begun),
                 "hps_engine_begin_step: hps_engine_set_laser_pulses with n = 0 needs at least one hps_engine_add_laser_samples");
@@ -907,6 +927,7 @@ int Engine::begin_step ()
     // a refusal still leaves the engine as it was
     if (laser && !step_begun) { for (const LaserSamples& S : laser_samples) { if (int e = laser_check_samples(*this, S)) return e; } }
     if (int e = setup_tiling()) return e;
+    el.keyed = coll.empty() ? 0 : 1;      // collisions (all added before the first step): the lattice index in the id bits
     step_begun = true;
     if (moving && steps_begun > 0) {
         // a slice that outgrew the hand-off capacity during the previous step lost particles: refuse to go on
@@ -940,7 +961,7 @@ int Engine::begin_step ()
     // charges cancel to rounding only, it iterates on that residue itself, and the literal rule on the engine's residue is its
     // match (any non-zero byte pattern reads as "disturbed")
     // A warm plasma deposits real jx, jy from the first slice on.
-    if (d_pc_dist) HPS_HIP_CHECK(hipMemsetAsync(d_pc_dist, (d.grid_current_on || d.ion_on || d.plasma_no_neutralize || thermal[0].warm() || thermal[1].warm()) ? 1 : 0, sizeof(int), st));
+    if (d_pc_dist) HPS_HIP_CHECK(hipMemsetAsync(d_pc_dist, (d.grid_current_on || d.ion_on || d.plasma_no_neutralize || el.thermal.warm() || ions.thermal.warm()) ? 1 : 0, sizeof(int), st));
     HPS_HIP_CHECK(hipMemsetAsync(d_checksum, 0, HPS_PC_NCOMP_MAX*sizeof(double), st));
     HPS_HIP_CHECK(hipMemsetAsync(d_laser_sum, 0, sizeof(double), st));
     if (int e = join_laser()) return e;        // the time levels rotate: the last slice's envelope must be in
@@ -968,51 +989,28 @@ int Engine::begin_step ()
     }
     if (laser && lgrid.set) { if (int e = laser_chi_initial(*this)) return e; }      // SetInitialChi: density(x, y, c t) of this step
     if (int e = ionize_collect()) return e;
-    np = np_init; pl.n = np; pl_alt.n = np;
-    const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : std::numeric_limits<double>::infinity();
-    if (np > 0 && warm_init(0)) {
-        if (int e = init_plasma_warm(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq, 0)) return e;
-    } else if (np > 0 && (hollow_core_radius > 0.0 || (fine_patch_set && fine_ppc[0] > 0) || dens[0].on)) {      // (a density program: init_slot's kernels)
-        if (int e = init_plasma_fine(*this, pl, np, d.plasma_ppc, fine_ppc, d.plasma_density, 0, coll.empty() ? 0 : 1, radius_sq, 0)) return e;
-    } else if (np > 0) {
-        const int nppc = d.plasma_ppc[0]*d.plasma_ppc[1];
-        hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(np, 256)), dim3(256), 0, st, pl, np, d.nx, d.ny,
-                           d.plasma_ppc[0], d.plasma_ppc[1], d.lo[0], d.lo[1], gm.dx, gm.dy,
-                           d.plasma_density*(d.si_units ? gm.dx*gm.dy*gm.dz/nppc : 1.0/nppc), 0, coll.empty() ? 0 : 1,     // scale_fac, PlasmaParticleContainerInit.cpp:40-41; collisions: lattice index in the id bits
-                           d_prof_r, (int)prof_r.size(), prof_ft, radius_sq);
-    }
-    if (tiling) { if (int e = resort()) return e; }
-    if (np > 0 && !d.plasma_no_neutralize) {
+    el.pl.n = el.n_init;
+    if (int e = init_sheet(el)) return e;
+    if (el.tiling) { if (int e = resort()) return e; }
+    if (el.pl.n > 0 && !d.plasma_no_neutralize) {
         // neutralising ion background, deposited once per step with charge -q (MultiPlasma.cpp:106-118)
         const int comp[6] = {-1, -1, -1, -1, -1, pc ? (int)HPS_PC_ION_RHOMJZ : (int)HPS_C_ION_RHOMJZ};
-        if (tiling) {
-            if (int e = deposit_current_tiled(slab, pl, gm, comp, -d.plasma_charge, d.plasma_mass, d.order, d.max_qsa, 0, d_nqsa, tiling, d_nfallback, st)) return e;
+        if (el.tiling) {
+            if (int e = deposit_current_tiled(slab, el.pl, gm, comp, -el.charge, el.mass, d.order, d.max_qsa, 0, d_nqsa, el.tiling, d_nfallback, st)) return e;
         } else {
-            if (int e = hps_deposit_current(slab, pl, gm, comp, -d.plasma_charge, d.plasma_mass, d.order, d.max_qsa, 0, d_nqsa, st)) return e;
+            if (int e = hps_deposit_current(slab, el.pl, gm, comp, -el.charge, el.mass, d.order, d.max_qsa, 0, d_nqsa, st)) return e;
         }
     }
-    if (ion.n > 0) {
+    if (ions.present()) {
         // the species "ion": every macro-ion back on its lattice point at its initial level; the product species is back
         // to its own InitParticles count
-        const int inppc = d.ion_ppc[0]*d.ion_ppc[1];
-        if (warm_init(1)) {
-            if (int e = init_plasma_warm(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq, 1)) return e;
-        } else if (hollow_core_radius > 0.0 || (fine_patch_set && ion_fine_ppc[0] > 0) || dens[1].on) {
-            if (int e = init_plasma_fine(*this, ion.pl, ion.n, d.ion_ppc, ion_fine_ppc, d.ion_density, d.ion_init_level, 1, radius_sq, 1)) return e;
-        } else {
-            hipLaunchKernelGGL(k_init_plasma, dim3(ceil_div(ion.n, 256)), dim3(256), 0, st, ion.pl, ion.n, d.nx, d.ny,
-                               d.ion_ppc[0], d.ion_ppc[1], d.lo[0], d.lo[1], gm.dx, gm.dy,
-                               d.ion_density*(d.si_units ? gm.dx*gm.dy*gm.dz/inppc : 1.0/inppc), d.ion_init_level, 1,
-                               d_prof_r, (int)prof_r.size(), prof_ft, radius_sq);
-        }
-        if (ion.tiling) {
-            ion.pl_alt.n = ion.n;
-            if (int e = tiling_sort(ion.tiling, ion.pl, ion.pl_alt, gm, st)) return e;
-            std::swap(ion.pl, ion.pl_alt); std::swap(ion.real, ion.real_alt);
+        if (int e = init_sheet(ions)) return e;
+        if (ions.tiling) {
+            if (int e = sort_sheet(ions)) return e;
             // every tile may hold charged ions if the species starts ionised; else none does until the push says so
-            HPS_HIP_CHECK(hipMemsetAsync(ion.d_tile_flag, d.ion_init_level > 0 ? 0x01 : 0, (size_t)ion.tiling->g.ntiles*sizeof(int), st));
+            HPS_HIP_CHECK(hipMemsetAsync(ion.d_tile_flag, ions.init_level > 0 ? 0x01 : 0, (size_t)ions.tiling->g.ntiles*sizeof(int), st));
         }
-        const unsigned long long c0[4] = {(unsigned long long)np_init, 0ULL, 0ULL, (unsigned long long)ion.n_ionized};
+        const unsigned long long c0[4] = {(unsigned long long)el.n_init, 0ULL, 0ULL, (unsigned long long)ion.n_ionized};
         HPS_HIP_CHECK(hipMemcpyAsync(ion.d_cnt, c0, sizeof(c0), hipMemcpyHostToDevice, st));
         HPS_HIP_CHECK(hipStreamSynchronize(st));      // c0 is on the stack
     }
@@ -1052,55 +1050,51 @@ int Engine::deposit_beam_slice (int islice, int cjx, int cjy, int cjz, const int
     return HPS_OK;
 }
 
-hps_plasma Engine::tail_of (const hps_plasma& p, long first, long n) const
-{
-    hps_plasma t = p;
-    double** arr[11] = {&t.x, &t.y, &t.w, &t.ux, &t.uy, &t.psi, &t.x_prev, &t.y_prev, &t.ux_half, &t.uy_half, &t.psi_half};
-    for (int k = 0; k < 11; ++k) *arr[k] += first;      // (x_prev / y_prev stay aliased to x / y where they were)
-    t.idcpu += first; t.ion_lev += first; t.n = n;
-    return t;
-}
-
 // The three particle operators over one species: LDS-tile kernels over the tile-sorted body of the sheet; what has been
 // appended behind it since the last sort (electrons released by the species "ion": some hundred particles) rides in the same
 // launch on up to 64 extra workgroups (TailWork; HPS_FOLD_TAIL=0: per-particle kernels of their own, 10-40 us of latency
 // chains per launch), anything beyond those goes through the per-particle kernels.
-TailWork Engine::fold_tail_of (const hps_plasma& p, const Tiling* T, long margin, long* covered) const
+TailWork Engine::fold_tail_of (const Species& s, long margin, long* covered) const
 {
+    const Tiling* T = s.tiling;
     TailWork tw;
     *covered = T->sorted_n;
-    if (!fold_tail || T != tiling || T->sorted_n <= 0) return tw;
-    const long nt = p.n - T->sorted_n + margin;
+    if (!fold_tail || &s != &el || T->sorted_n <= 0) return tw;      // (only the plasma's sheet grows a tail)
+    const long nt = s.pl.n - T->sorted_n + margin;
     if (nt <= 0) return tw;
     tw.first = (int)T->sorted_n; tw.nwg = (int)std::min<long>(ceil_div(nt, 256), 64);
     *covered = T->sorted_n + 256L*tw.nwg;
     return tw;
 }
-int Engine::species_deposit (const hps_plasma& p, Tiling* T, const int comp[6], double charge, double mass, int can_ionize, const BeamPairWork* beam)
+// (`go` gates the tile kernels only: the device-side loop control that passes it has neither a tail nor a sheet without tiles)
+int Engine::species_deposit (const Species& s, const int comp[6], const BeamPairWork* beam, const int* go)
 {
+    const hps_plasma& p = s.pl; Tiling* T = s.tiling;
     if (p.n == 0) return HPS_OK;
-    if (!T) return hps_deposit_current_laser(slab, p, gm, comp, c_aabs, charge, mass, d.order, d.max_qsa, can_ionize, d_nqsa, st);
-    long covered; const TailWork tw = fold_tail_of(p, T, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = deposit_current_tiled(slab, p, gm, comp, charge, mass, d.order, d.max_qsa, can_ionize, d_nqsa, T, d_nfallback, st, c_aabs, T == ion.tiling ? ion.d_tile_flag : nullptr, tw, beam, nullptr, valid_by_w && !can_ionize)) return e; }
-    if (p.n > covered) return hps_deposit_current_laser(slab, tail_of(p, covered, p.n - covered), gm, comp, c_aabs, charge, mass, d.order, d.max_qsa, can_ionize, d_nqsa, st);
+    if (!T) return hps_deposit_current_laser(slab, p, gm, comp, c_aabs, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, st);
+    long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
+    if (T->sorted_n > 0) { if (int e = deposit_current_tiled(slab, p, gm, comp, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, beam, go, valid_by_w && !s.can_ionize)) return e; }
+    if (p.n > covered) return hps_deposit_current_laser(slab, tail_of(p, covered, p.n - covered), gm, comp, c_aabs, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, st);
     return HPS_OK;
 }
-int Engine::species_explicit (const hps_plasma& p, Tiling* T, const int cache[4], const int depos[2], double charge, double mass, int can_ionize)
+int Engine::species_explicit (const Species& s, const int cache[4], const int depos[2])
 {
+    const hps_plasma& p = s.pl; Tiling* T = s.tiling;
     if (p.n == 0) return HPS_OK;
-    if (!T) return hps_explicit_deposit_laser(slab, p, gm, cache, c_aabs, depos, charge, mass, d.order, d.deriv_type, can_ionize, st);
-    long covered; const TailWork tw = fold_tail_of(p, T, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = explicit_deposit_tiled(slab, p, gm, cache, depos, charge, mass, d.order, d.deriv_type, can_ionize, T, d_nfallback, st, c_aabs, T == ion.tiling ? ion.d_tile_flag : nullptr, tw, valid_by_w && !can_ionize)) return e; }
-    if (p.n > covered) return hps_explicit_deposit_laser(slab, tail_of(p, covered, p.n - covered), gm, cache, c_aabs, depos, charge, mass, d.order, d.deriv_type, can_ionize, st);
+    if (!T) return hps_explicit_deposit_laser(slab, p, gm, cache, c_aabs, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, st);
+    long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
+    if (T->sorted_n > 0) { if (int e = explicit_deposit_tiled(slab, p, gm, cache, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, valid_by_w && !s.can_ionize)) return e; }
+    if (p.n > covered) return hps_explicit_deposit_laser(slab, tail_of(p, covered, p.n - covered), gm, cache, c_aabs, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, st);
     return HPS_OK;
 }
-int Engine::species_advance (const hps_plasma& p, Tiling* T, const int comp[5], double charge, double mass, int temp_slice, int can_ionize)
+int Engine::species_advance (const Species& s, const int comp[5], int temp_slice, const int* go)
 {
+    const hps_plasma& p = s.pl; Tiling* T = s.tiling;
     if (p.n == 0) return HPS_OK;
-    if (!T) return hps_advance_plasma_laser(slab, p, gm, comp, c_aabs, charge, mass, d.order, temp_slice, d.n_subcycles, can_ionize, st);
-    long covered; const TailWork tw = fold_tail_of(p, T, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = advance_plasma_tiled(slab, p, gm, comp, charge, mass, d.order, temp_slice, d.n_subcycles, can_ionize, T, d_nfallback, st, c_aabs, nullptr, nullptr, tw)) return e; }
-    if (p.n > covered) return hps_advance_plasma_laser(slab, tail_of(p, covered, p.n - covered), gm, comp, c_aabs, charge, mass, d.order, temp_slice, d.n_subcycles, can_ionize, st);
+    if (!T) return hps_advance_plasma_laser(slab, p, gm, comp, c_aabs, s.charge, s.mass, d.order, temp_slice, d.n_subcycles, s.can_ionize, st);
+    long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
+    if (T->sorted_n > 0) { if (int e = advance_plasma_tiled(slab, p, gm, comp, s.charge, s.mass, d.order, temp_slice, d.n_subcycles, s.can_ionize, T, d_nfallback, st, c_aabs, nullptr, go, tw)) return e; }
+    if (p.n > covered) return hps_advance_plasma_laser(slab, tail_of(p, covered, p.n - covered), gm, comp, c_aabs, s.charge, s.mass, d.order, temp_slice, d.n_subcycles, s.can_ionize, st);
     return HPS_OK;
 }
 
@@ -1592,8 +1586,8 @@ int Engine::solve_slice_pc_begin (int islice)
 
     prof_now = profiling && (slices_done % prof_stride == 0);
     mark();   // b0
-    if (d_insitu_pl && np > 0)
-        hipLaunchKernelGGL(k_insitu_plasma, dim3(256), b256, 0, st, pl, 1.0/gm.c, insitu_pl_radius*insitu_pl_radius, d_insitu_pl, d.nz, islice);
+    if (d_insitu_pl && el.pl.n > 0)
+        hipLaunchKernelGGL(k_insitu_plasma, dim3(256), b256, 0, st, el.pl, 1.0/gm.c, insitu_pl_radius*insitu_pl_radius, d_insitu_pl, d.nz, islice);
     // InitializeSlices (fields/Fields.cpp:565-570); ExmBy, EypBx are rewritten by k_grad_psi up to the outermost
     // guard ring, which stays zero from begin_step
     {   CompList z{0, {}}, zb{0, {}};
@@ -1601,18 +1595,14 @@ int Engine::solve_slice_pc_begin (int islice)
         if (d.deposit_rho) z.c[z.n++] = HPS_PC_RHO;
         hipLaunchKernelGGL(k_zero_comps, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, z, zb, CellBox{0, -1, 0, -1}); }
     mark();   // b1
-    if (tiling && (since_sort >= sort_period || (since_sort >= 2 && *h_nfallback - fb_at_sort > np/fallback_div) ||
-                   (since_sort >= 1 && np - tiling->sorted_n > std::max(np/32, 16384L)))) { if ((e = resort())) return e; }
+    if (el.tiling && (since_sort >= sort_period || (since_sort >= 2 && *h_nfallback - fb_at_sort > el.pl.n/fallback_div) ||
+                      (since_sort >= 1 && el.pl.n - el.tiling->sorted_n > std::max(el.pl.n/32, 16384L)))) { if ((e = resort())) return e; }
     ++since_sort;
     mark();   // b1b
     // plasma: jx jy jz [rho] rhomjz (Hipace.cpp:616-618); beams deposit into the same jx jy jz (:620-623)
     {   const int comp[6] = {HPS_PC_JX, HPS_PC_JY, HPS_PC_JZ, d.deposit_rho ? HPS_PC_RHO : -1, -1, HPS_PC_RHOMJZ};
-        // (with an ionisable species the sheet has electrons behind its tile-sorted body: the helper that also covers that tail)
-        if (ion.n > 0) { if ((e = species_deposit(pl, tiling, comp, d.plasma_charge, d.plasma_mass, 0))) return e; }
-        else if (tiling) { if ((e = deposit_current_tiled(slab, pl, gm, comp, d.plasma_charge, d.plasma_mass, d.order, d.max_qsa, 0, d_nqsa, tiling, d_nfallback, st, -1, nullptr, TailWork{}, nullptr, nullptr, valid_by_w))) return e; }
-        else        { if ((e = hps_deposit_current(slab, pl, gm, comp, d.plasma_charge, d.plasma_mass, d.order, d.max_qsa, 0, d_nqsa, st))) return e; }
         // MultiPlasma::DepositCurrent: every species in turn (MultiPlasma.cpp:78-87)
-        if (ion.n > 0) { if ((e = species_deposit(ion.pl, ion.tiling, comp, d.ion_charge, d.ion_mass, 1))) return e; } }
+        for (const Species& s : sp) { if ((e = species_deposit(s, comp))) return e; } }
     mark();   // b2
     if ((e = deposit_beam_slice(islice, HPS_PC_JX, HPS_PC_JY, HPS_PC_JZ))) return e;
     deposit_grid_current(islice, HPS_PC_JZ);
@@ -1632,7 +1622,7 @@ int Engine::solve_slice_pc_begin (int islice)
     // the loop (Hipace.cpp:935-1031)
     HPS_HIP_CHECK(hipMemsetAsync(d_pc, 0, 2*sizeof(double), st));
     hipLaunchKernelGGL(k_rel_b_error, dim3(128), b256, 0, st, f, HPS_PC_P_BX, HPS_PC_PIT_BX, d_pc, (volatile double*)nullptr, 0.0);
-    const bool spec = pc_speculate && tiling && !moving && ion.n == 0;      // (a second species: the host-controlled loop)
+    const bool spec = pc_speculate && el.tiling && !moving && !ions.present();      // (a second species: the host-controlled loop)
     hipLaunchKernelGGL(k_pc_guess, gplane, b256, 0, st, slab.p, slab.nstride, plane, d_pc, pc_tol, spec ? d_pc_go : (int*)nullptr, pc_floor);
     pc_islice = islice;
     if (spec) {
@@ -1679,20 +1669,14 @@ int Engine::pc_enqueue_iteration (int it)
     const dim3 gplane(ceil_div(plane, 256));
     const long nval = (long)d.nx*d.ny;
     const int islice = pc_islice;
-    const bool spec = pc_speculate && tiling && !moving && ion.n == 0;
+    const bool spec = pc_speculate && el.tiling && !moving && !ions.present();
     int* go = spec ? d_pc_go + it : nullptr;
     const int comp_push[5] = {HPS_PC_PSI, HPS_PC_EZ, HPS_PC_BX, HPS_PC_BY, HPS_PC_BZ};
     int e;
-    // plasma to the temporary next slice, its jx jy (+ the beam's) there
-    if (ion.n > 0) { if ((e = species_advance(pl, tiling, comp_push, d.plasma_charge, d.plasma_mass, 1, 0))) return e; }
-    else if (tiling) { if ((e = advance_plasma_tiled(slab, pl, gm, comp_push, d.plasma_charge, d.plasma_mass, d.order, 1, d.n_subcycles, 0, tiling, d_nfallback, st, -1, nullptr, go))) return e; }
-    else        { if ((e = hps_advance_plasma(slab, pl, gm, comp_push, d.plasma_charge, d.plasma_mass, d.order, 1, d.n_subcycles, 0, st))) return e; }
-    if (ion.n > 0) { if ((e = species_advance(ion.pl, ion.tiling, comp_push, d.ion_charge, d.ion_mass, 1, 1))) return e; }      // (go == nullptr with a second species)
+    // every species to the temporary next slice, its jx jy (+ the beam's) there      (go == nullptr with a second species)
+    for (const Species& s : sp) { if ((e = species_advance(s, comp_push, 1, go))) return e; }
     {   const int comp[6] = {HPS_PC_N_JX, HPS_PC_N_JY, -1, -1, -1, -1};
-        if (ion.n > 0) { if ((e = species_deposit(pl, tiling, comp, d.plasma_charge, d.plasma_mass, 0))) return e; }
-        else if (tiling) { if ((e = deposit_current_tiled(slab, pl, gm, comp, d.plasma_charge, d.plasma_mass, d.order, d.max_qsa, 0, d_nqsa, tiling, d_nfallback, st, -1, nullptr, TailWork{}, nullptr, go, valid_by_w))) return e; }
-        else        { if ((e = hps_deposit_current(slab, pl, gm, comp, d.plasma_charge, d.plasma_mass, d.order, d.max_qsa, 0, d_nqsa, st))) return e; }
-        if (ion.n > 0) { if ((e = species_deposit(ion.pl, ion.tiling, comp, d.ion_charge, d.ion_mass, 1))) return e; } }
+        for (const Species& s : sp) { if ((e = species_deposit(s, comp, nullptr, go))) return e; } }
     if ((e = deposit_beam_slice(islice - 1, HPS_PC_N_JX, HPS_PC_N_JY, -1, go))) return e;
     hipLaunchKernelGGL(k_rhs_bxby, dim3(ceil_div(d.nx, 256), d.ny), b256, 0, st, f, gm.mu0, 0.5*(1.0/gm.dx), 0.5*(1.0/gm.dy),
                        0.5*(1.0/gm.dz), staging, nval, d_pc, (const int*)go);
@@ -1739,7 +1723,7 @@ int Engine::solve_slice_pc_finish (int islice)
     const int comp_push[5] = {HPS_PC_PSI, HPS_PC_EZ, HPS_PC_BX, HPS_PC_BY, HPS_PC_BZ};
     int e;
     double err = pc_last_err;
-    if (pc_speculate && tiling && !moving && ion.n == 0) {
+    if (pc_speculate && el.tiling && !moving && !ions.present()) {
         int it = 0;
         err = 1.0;
         while (err > pc_tol && it < pc_max_iter) {
@@ -1760,23 +1744,21 @@ int Engine::solve_slice_pc_finish (int islice)
         hipLaunchKernelGGL(k_checksum, dim3(64, ncomp), b256, 0, st, f, ncomp, d_checksum);
     if ((e = fill_field_diagnostic(islice))) return e;
     mark();   // b7
-    if (ion.n > 0) {
+    if (ions.present()) {
         // DoFieldIonization (Hipace.cpp:693-696) and the committing pushes of both species (:699-701): the decisions on the tiles'
         // gathered fields inside the ions' push (or k_ionize ahead of the per-particle push), the electron count back on the host,
         // then every electron -- the ones this slice has released included
-        if (ion.tiling) {
+        if (ions.tiling) {
             if ((e = ion_field_bounds())) return e;
             const IonArgs ia = ion_args(islice);
-            if ((e = advance_plasma_tiled(slab, ion.pl, gm, comp_push, d.ion_charge, d.ion_mass, d.order, 0, d.n_subcycles, 1, ion.tiling, d_nfallback, st, -1, &ia))) return e;
+            if ((e = advance_plasma_tiled(slab, ions.pl, gm, comp_push, ions.charge, ions.mass, d.order, 0, d.n_subcycles, 1, ions.tiling, d_nfallback, st, -1, &ia))) return e;
         } else {
             if ((e = ionize_slice(islice))) return e;
-            if ((e = species_advance(ion.pl, ion.tiling, comp_push, d.ion_charge, d.ion_mass, 0, 1))) return e;
+            if ((e = species_advance(ions, comp_push, 0))) return e;
         }
         if ((e = ionize_collect())) return e;
-        if ((e = species_advance(pl, tiling, comp_push, d.plasma_charge, d.plasma_mass, 0, 0))) return e;
     }
-    else if (tiling) { if ((e = advance_plasma_tiled(slab, pl, gm, comp_push, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, tiling, d_nfallback, st))) return e; }
-    else        { if ((e = hps_advance_plasma(slab, pl, gm, comp_push, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
+    if ((e = species_advance(el, comp_push, 0))) return e;
     insitu_beam(islice);
     if (moving && nbeam > 0) { if ((e = beam_push_moving(*this, islice))) return e; }
     if (!coll.empty()) { if ((e = collide_slice(islice))) return e; }      // doCoulombCollision (Hipace.cpp:711-712)
@@ -1824,8 +1806,8 @@ int Engine::solve_slice_begin (int islice)
     mg_solve1_forget_hierarchy(mg);            // (left set only if the previous slice failed between prepare and begin)
     if ((e = join_laser())) return e;          // the envelope solver of the previous slice has read its chi
     mark();   // b0
-    if (d_insitu_pl && np > 0)        // m_multi_plasma.InSituComputeDiags (Hipace.cpp:590)
-        hipLaunchKernelGGL(k_insitu_plasma, dim3(256), b256, 0, st, pl, 1.0/gm.c, insitu_pl_radius*insitu_pl_radius, d_insitu_pl, d.nz, islice);
+    if (d_insitu_pl && el.pl.n > 0)        // m_multi_plasma.InSituComputeDiags (Hipace.cpp:590)
+        hipLaunchKernelGGL(k_insitu_plasma, dim3(256), b256, 0, st, el.pl, 1.0/gm.c, insitu_pl_radius*insitu_pl_radius, d_insitu_pl, d.nz, islice);
     // InitializeSlices (fields/Fields.cpp:535-586)
     const CellBox bb{beam_box.ilo, beam_box.ihi, beam_box.jlo, beam_box.jhi};
     // the previous slice's fused push + deposition has already shifted / zeroed the slab and deposited this slice's
@@ -1867,8 +1849,8 @@ int Engine::solve_slice_begin (int islice)
     // the halo of its tile (h_nfallback is as of the previous slice's multigrid sync)
     // (with a species "ion": also once the electrons appended behind the sorted body since the last sort -- they run
     // through the per-particle kernels -- are more than 1/32 of the sheet)
-    if (tiling && (since_sort >= sort_period || (since_sort >= 2 && *h_nfallback - fb_at_sort > np/fallback_div) ||
-                   (since_sort >= 1 && np - tiling->sorted_n > std::max(np/32, 16384L)))) { if ((e = resort())) return e; }
+    if (el.tiling && (since_sort >= sort_period || (since_sort >= 2 && *h_nfallback - fb_at_sort > el.pl.n/fallback_div) ||
+                      (since_sort >= 1 && el.pl.n - el.tiling->sorted_n > std::max(el.pl.n/32, 16384L)))) { if ((e = resort())) return e; }
     ++since_sort;
     mark();   // b1b
     // static beam: jz of this slice and jx, jy of the next one in one go (Hipace.cpp:613-614, 656-657), as extra workgroups of
@@ -1886,12 +1868,12 @@ int Engine::solve_slice_begin (int islice)
         bw.cjz = HPS_C_JZB; bw.cjxn = HPS_C_N_JXB; bw.cjyn = HPS_C_N_JYB;
         bw.q_invvol = d.beam_charge*(d.si_units ? 1.0/(gm.dx*gm.dy*gm.dz) : 1.0); bw.csq_inv = 1.0/(gm.c*gm.c);
     }
-    const bool beam_folded = pair && fold_beam && bw.nwg > 0 && !ahead && np > 0 && tiling && tiling->sorted_n > 0;
+    const bool beam_folded = pair && fold_beam && bw.nwg > 0 && !ahead && el.pl.n > 0 && el.tiling && el.tiling->sorted_n > 0;
     if (!ahead)
     {   const int comp[6] = {HPS_C_JX, HPS_C_JY, -1, d.deposit_rho ? HPS_C_RHO : -1, HPS_C_CHI, HPS_C_RHOMJZ};
-        if ((e = species_deposit(pl, tiling, comp, d.plasma_charge, d.plasma_mass, 0, beam_folded ? &bw : nullptr))) return e;
+        if ((e = species_deposit(el, comp, beam_folded ? &bw : nullptr))) return e;
         // MultiPlasma::DepositCurrent: every species in turn (MultiPlasma.cpp:78-87); an ion weighs in with its level
-        if (ion.n > 0) { if ((e = species_deposit(ion.pl, ion.tiling, comp, d.ion_charge, d.ion_mass, 1))) return e; } }
+        if ((e = species_deposit(ions, comp))) return e; }
     mark();   // b2
     if (pair) {
         if (!beam_folded && bw.nwg > 0) {
@@ -1972,19 +1954,18 @@ int Engine::solve_slice_begin (int islice)
     mark();   // b4
     {   const int cache[4] = {HPS_C_BZ, HPS_C_EZ, HPS_C_EXMBY, HPS_C_EYPBX};
         const int depos[2] = {HPS_C_SY, HPS_C_SX};
-        if ((e = species_explicit(pl, tiling, cache, depos, d.plasma_charge, d.plasma_mass, 0))) return e;
-        if (ion.n > 0) { if ((e = species_explicit(ion.pl, ion.tiling, cache, depos, d.ion_charge, d.ion_mass, 1))) return e; } }
+        for (const Species& s : sp) { if ((e = species_explicit(s, cache, depos))) return e; } }
 
     mark();   // b5
     // Bx, By: Helmholtz multigrid from the previous slice's field (Hipace.cpp:793-933).  The plain case (one tile-sorted
     // species, nothing that reads the fields between the solve and the push) enqueues the push BEHIND the speculated
     // V-cycles, gated on the solve's own stopping rule, and only then waits for the norms: the device goes from the last
     // V-cycle straight into the push instead of idling until the host has seen the norms and launched it.
-    const bool fuse = fuse_push_deposit && coll.empty() && tiling && islice > 0 && !moving && c_aabs < 0 && ion.n == 0 && np > 0 && tiling->sorted_n == np && !sal;
-    const bool gated = gate_push && tiling && !fuse && ion.n == 0 && np > 0 && tiling->sorted_n == np && !diagnostics && !d_fd && !d_insitu && !sal;
+    const bool fuse = fuse_push_deposit && coll.empty() && el.tiling && islice > 0 && !moving && c_aabs < 0 && !ions.present() && el.pl.n > 0 && el.tiling->sorted_n == el.pl.n && !sal;
+    const bool gated = gate_push && el.tiling && !fuse && !ions.present() && el.pl.n > 0 && el.tiling->sorted_n == el.pl.n && !diagnostics && !d_fd && !d_insitu && !sal;
     // ... and with an ionisable species on tiles: its field bounds, its push (which takes the ADK decisions and appends the
     // electrons) and the electrons' push, all behind the speculated V-cycles; the two pushes are gated (HPS_GATED_ION_PUSH=0: off)
-    const bool gated_ion = gate_push && gate_ion_push && tiling && !fuse && ion.n > 0 && ion.tiling && np > 0 && tiling->sorted_n > 0 && fold_tail
+    const bool gated_ion = gate_push && gate_ion_push && el.tiling && !fuse && ions.present() && ions.tiling && el.pl.n > 0 && el.tiling->sorted_n > 0 && fold_tail
                            && !diagnostics && !d_fd && !d_insitu && !sal;
     const int comp_push[5] = {HPS_C_PSI, HPS_C_EZ, HPS_C_BX, HPS_C_BY, HPS_C_BZ};
     {
@@ -2002,7 +1983,7 @@ int Engine::solve_slice_begin (int islice)
             mark();   // b7
             MgPost mp{};
             const bool posting = mg_take_deferred_post(mg, &mp);
-            if ((e = advance_plasma_tiled(slab, pl, gm, comp_push, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, tiling, d_nfallback, st, c_aabs, nullptr,
+            if ((e = advance_plasma_tiled(slab, el.pl, gm, comp_push, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, el.tiling, d_nfallback, st, c_aabs, nullptr,
                                           posting ? nullptr : mg_gate_after_enqueued(mg), TailWork{}, posting ? &mp : nullptr))) return e;
         }
         if (laser_split && d.laser_solver == 2) { if ((e = laser_advance_slice(*this, islice)) || (e = laser_done())) return e; }
@@ -2022,10 +2003,10 @@ int Engine::push_with_ionization (int islice, const int comp[5], const int* go, 
     int e;
     if ((e = ion_field_bounds())) return e;
     if (first) pend_ia = ion_args(islice);
-    if ((e = advance_plasma_tiled(slab, ion.pl, gm, comp, d.ion_charge, d.ion_mass, d.order, 0, d.n_subcycles, 1, ion.tiling, d_nfallback, st, c_aabs, &pend_ia, go))) return e;
-    TailWork tw = fold_tail_of(pl, tiling, 256, &pend_covered);
+    if ((e = advance_plasma_tiled(slab, ions.pl, gm, comp, ions.charge, ions.mass, d.order, 0, d.n_subcycles, 1, ions.tiling, d_nfallback, st, c_aabs, &pend_ia, go))) return e;
+    TailWork tw = fold_tail_of(el, 256, &pend_covered);
     if (tw.nwg) tw.live_n = ion.d_cnt;
-    return advance_plasma_tiled(slab, pl, gm, comp, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, tiling, d_nfallback, st, c_aabs, nullptr, go, tw);
+    return advance_plasma_tiled(slab, el.pl, gm, comp, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, el.tiling, d_nfallback, st, c_aabs, nullptr, go, tw);
 }
 
 int Engine::solve_slice_finish (int islice)
@@ -2045,12 +2026,12 @@ int Engine::solve_slice_finish (int islice)
         if ((e = mg_solve1_finish(mg, &iters, nullptr, &extra, st))) return e;
         total_vcycles += iters;
         // the speculated V-cycles were not enough (the gated push has not run): the host has added the rest, push now
-        if (gated && extra) { if ((e = species_advance(pl, tiling, comp_push, d.plasma_charge, d.plasma_mass, 0, 0))) return e; }
+        if (gated && extra) { if ((e = species_advance(el, comp_push, 0))) return e; }
         if (gated_ion) {
             if (extra) { if ((e = push_with_ionization(islice, comp_push, nullptr, false))) return e; }
             // the electrons the slice has released beyond the room the body's launch had for them
             if ((e = ionize_collect())) return e;
-            if (pl.n > pend_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(pl, pend_covered, pl.n - pend_covered), gm, comp_push, c_aabs, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
+            if (el.pl.n > pend_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(el.pl, pend_covered, el.pl.n - pend_covered), gm, comp_push, c_aabs, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
         } }
 
     // SalameModule (Hipace.cpp:673-678): behind the Bx/By solve, ahead of the diagnostics and the push, on a slice whose beam
@@ -2071,25 +2052,25 @@ int Engine::solve_slice_finish (int islice)
     // gather + push (Hipace.cpp:699-701)
     {   const int* comp = comp_push;
         bool body_done = false; long body_covered = 0;
-        if (ion.n > 0) {
+        if (ions.present()) {
             // DoFieldIonization (Hipace.cpp:693-696), then the ions' own push; the host learns how many electrons the
             // slice has released while that push runs
-            if (ion.tiling) {       // decided inside the ions' LDS-tile push, on the fields it gathers anyway
+            if (ions.tiling) {       // decided inside the ions' LDS-tile push, on the fields it gathers anyway
                 if ((e = ion_field_bounds())) return e;
                 const IonArgs ia = ion_args(islice);
-                if ((e = advance_plasma_tiled(slab, ion.pl, gm, comp, d.ion_charge, d.ion_mass, d.order, 0, d.n_subcycles, 1, ion.tiling, d_nfallback, st, c_aabs, &ia))) return e;
+                if ((e = advance_plasma_tiled(slab, ions.pl, gm, comp, ions.charge, ions.mass, d.order, 0, d.n_subcycles, 1, ions.tiling, d_nfallback, st, c_aabs, &ia))) return e;
             } else {
                 if ((e = ionize_slice(islice))) return e;
-                if ((e = species_advance(ion.pl, ion.tiling, comp, d.ion_charge, d.ion_mass, 0, 1))) return e;
+                if ((e = species_advance(ions, comp, 0))) return e;
             }
             // the electrons' tile-sorted body does not depend on how many electrons the slice has released: push it while the
             // count travels to the host, then the tail with the new count
             // (the tail's workgroups in that launch read the count on the device -- the ions' push is ahead of them on the
             //  stream --, with room for 256 electrons more than the host knows of; whoever is beyond that is pushed below)
-            if (tiling && tiling->sorted_n > 0 && !fuse) {
-                TailWork tw = fold_tail_of(pl, tiling, 256, &body_covered);
+            if (el.tiling && el.tiling->sorted_n > 0 && !fuse) {
+                TailWork tw = fold_tail_of(el, 256, &body_covered);
                 if (tw.nwg) tw.live_n = ion.d_cnt;
-                if ((e = advance_plasma_tiled(slab, pl, gm, comp, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, tiling, d_nfallback, st, c_aabs, nullptr, nullptr, tw))) return e;
+                if ((e = advance_plasma_tiled(slab, el.pl, gm, comp, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, el.tiling, d_nfallback, st, c_aabs, nullptr, nullptr, tw))) return e;
                 body_done = true;
             }
             if ((e = ionize_collect())) return e;
@@ -2099,12 +2080,12 @@ int Engine::solve_slice_finish (int islice)
         if (fuse) {
             hipLaunchKernelGGL(k_shift_zero, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb, d.deposit_rho ? (int)HPS_C_RHO : -1, (int)HPS_C_ION_RHOMJZ);
             const int dep[6] = {HPS_C_JX, HPS_C_JY, -1, d.deposit_rho ? HPS_C_RHO : -1, HPS_C_CHI, HPS_C_RHOMJZ};
-            if ((e = advance_deposit_tiled(slab, pl, gm, comp, dep, d.plasma_charge, d.plasma_mass, d.order, d.n_subcycles, d.max_qsa, d_nqsa, tiling, d_nfallback, st))) return e;
+            if ((e = advance_deposit_tiled(slab, el.pl, gm, comp, dep, el.charge, el.mass, d.order, d.n_subcycles, d.max_qsa, d_nqsa, el.tiling, d_nfallback, st))) return e;
             ahead_for = islice - 1;
         } else if (body_done) {
-            if (pl.n > body_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(pl, body_covered, pl.n - body_covered), gm, comp, c_aabs, d.plasma_charge, d.plasma_mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
+            if (el.pl.n > body_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(el.pl, body_covered, el.pl.n - body_covered), gm, comp, c_aabs, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
         } else {
-            if ((e = species_advance(pl, tiling, comp, d.plasma_charge, d.plasma_mass, 0, 0))) return e;
+            if ((e = species_advance(el, comp, 0))) return e;
         } }
     }
 
@@ -2177,7 +2158,7 @@ int Engine::salame_module (int islice)
     zero({HPS_C_SY, HPS_C_SX});
     {   const int cache[4] = {HPS_C_BZ, HPS_C_EZ, HPS_C_EXMBY, HPS_C_EYPBX};
         const int depos[2] = {HPS_C_SY, HPS_C_SX};
-        if ((e = species_explicit(pl, tiling, cache, depos, d.plasma_charge, d.plasma_mass, 0))) return e; }
+        if ((e = species_explicit(el, cache, depos))) return e; }
     copy({S + HPS_SAL_SY_BACK, S + HPS_SAL_SX_BACK}, {HPS_C_SY, HPS_C_SX});
 
     const long first0 = beam_off[d.nz - 1 - islice], count = beam_off[d.nz - islice] - first0;
@@ -2185,9 +2166,9 @@ int Engine::salame_module (int islice)
     int iter = 0, used = 0; bool converged = false, undetermined = false;
     for (; iter < d.salame_n_iter; ++iter) {
         // STEP 1: Ez of the next slice with the beam at its present weight (:43-73)
-        if ((e = species_advance(pl, tiling, comp_push, d.plasma_charge, d.plasma_mass, 1, 0))) return e;
+        if ((e = species_advance(el, comp_push, 1))) return e;
         copy({S + HPS_SAL_JX, S + HPS_SAL_JY}, {HPS_C_N_JXB, HPS_C_N_JYB});
-        if ((e = species_deposit(pl, tiling, dep_jxjy, d.plasma_charge, d.plasma_mass, 0))) return e;
+        if ((e = species_deposit(el, dep_jxjy))) return e;
         zero({S + HPS_SAL_EZ, S + HPS_SAL_JZB, S + HPS_SAL_SY, S + HPS_SAL_SX, S + HPS_SAL_BX, S + HPS_SAL_BY});
         if ((e = salame_solve_ez())) return e;
         copy({S + HPS_SAL_EZ_NO_SALAME}, {S + HPS_SAL_EZ});
@@ -2198,8 +2179,8 @@ int Engine::salame_module (int islice)
         if ((e = solve_bxby(S + HPS_SAL_BX, S + HPS_SAL_SY))) return e;       // zero guess, This chi
         zero({S + HPS_SAL_EZ, S + HPS_SAL_JX, S + HPS_SAL_JY});
         if (!d.salame_no_advance) {
-            if (pl.n > 0) { if ((e = hps_salame_only_advance(slab, pl, gm, S + HPS_SAL_BX, S + HPS_SAL_BY, d.plasma_charge, d.plasma_mass, d.order, 0, st))) return e; }
-            if ((e = species_deposit(pl, tiling, dep_jxjy, d.plasma_charge, d.plasma_mass, 0))) return e;
+            if (el.pl.n > 0) { if ((e = hps_salame_only_advance(slab, el.pl, gm, S + HPS_SAL_BX, S + HPS_SAL_BY, el.charge, el.mass, d.order, 0, st))) return e; }
+            if ((e = species_deposit(el, dep_jxjy))) return e;
         } else {
             if ((e = hps_salame_jxjy_from_bxby(slab, gm, S + HPS_SAL_BX, S + HPS_SAL_BY, HPS_C_CHI, S + HPS_SAL_JX, S + HPS_SAL_JY, st))) return e;
         }
@@ -2283,7 +2264,7 @@ extern "C" int hps_engine_slice_ready (void* h)
     if (E->pc) {
         // device-controlled loop: ready when the host's walk over the posted errors (solve_slice_pc_finish) would not wait --
         // an iteration that met the tolerance has been posted, or every iteration enqueued so far has
-        if (!(E->pc_speculate && E->tiling && !E->moving && E->ion.n == 0) || E->pc_islice < 0 || E->pc_enqueued <= 0) return 1;
+        if (!(E->pc_speculate && E->el.tiling && !E->moving && !E->ions.present()) || E->pc_islice < 0 || E->pc_enqueued <= 0) return 1;
         for (int it = 1; it <= E->pc_enqueued; ++it) {
             const volatile double* hp = E->h_pc + 8*it;
             const double seq = E->pc_base_seq + it;
@@ -2318,24 +2299,22 @@ extern "C" int hps_engine_info (void* h, int* ncomp, int* ng, long* np)
     Engine* E = static_cast<Engine*>(h);
     if (ncomp) *ncomp = E->ncomp;
     if (ng) *ng = E->g;
-    if (np) *np = E->np;
+    if (np) *np = E->el.pl.n;
     return HPS_OK;
 }
 extern "C" hps_slab hps_engine_slab (void* h) { Engine* E = static_cast<Engine*>(h); E->flush_shift(); return E->slab; }
-extern "C" hps_plasma hps_engine_plasma (void* h) { return static_cast<Engine*>(h)->pl; }
+extern "C" hps_plasma hps_engine_plasma (void* h) { return static_cast<Engine*>(h)->el.pl; }
 extern "C" int hps_engine_tiling (void* h, void** tiling)
 {
     HPS_REQUIRE(h && tiling, "hps_engine_tiling: null argument");
-    *tiling = static_cast<Engine*>(h)->tiling;
+    *tiling = static_cast<Engine*>(h)->el.tiling;
     return HPS_OK;
 }
 extern "C" hps_plasma hps_engine_ions (void* h)
 {
     Engine* E = static_cast<Engine*>(h);
     (void)hipStreamSynchronize(E->st);
-    hps_plasma p = E->ion.pl;
-    p.n = E->ion.n;
-    return p;
+    return E->ions.pl;
 }
 extern "C" int hps_engine_ion_stats (void* h, long* n_ionized, long* n_product)
 {
@@ -2343,7 +2322,7 @@ extern "C" int hps_engine_ion_stats (void* h, long* n_ionized, long* n_product)
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     if (int e = E->ionize_collect()) return e;
     if (n_ionized) *n_ionized = E->ion.n_ionized;
-    if (n_product) *n_product = E->np;
+    if (n_product) *n_product = E->el.pl.n;
     return HPS_OK;
 }
 extern "C" hps_stream hps_engine_stream (void* h) { return static_cast<Engine*>(h)->st; }
@@ -2884,7 +2863,7 @@ extern "C" int hps_engine_set_tiling (void* h, int tile_size, int sort_period)
     Engine* E = static_cast<Engine*>(h);
     HPS_REQUIRE(tile_size == 0 || tile_size == 16 || tile_size == 32, "hps_engine_set_tiling: tile_size must be 0, 16 or 32");
     HPS_REQUIRE(sort_period >= 1, "hps_engine_set_tiling: sort_period must be >= 1");
-    HPS_REQUIRE(E->tiling == nullptr, "hps_engine_set_tiling: call before the first hps_engine_begin_step");
+    HPS_REQUIRE(E->el.tiling == nullptr, "hps_engine_set_tiling: call before the first hps_engine_begin_step");
     E->tile_size = tile_size; E->sort_period = sort_period;
     return HPS_OK;
 }
@@ -2912,10 +2891,10 @@ extern "C" int hps_engine_set_fusion (void* h, int on)
     static_cast<Engine*>(h)->fuse_push_deposit = (on != 0);
     return HPS_OK;
 }
-extern "C" int hps_engine_set_plasma_init (void* h, const int* plasma_fine_ppc, const int* ion_fine_ppc, double hollow_core_radius)
+extern "C" int hps_engine_set_plasma_init (void* h, const int* plasma_fine, const int* ion_fine, double hollow_core_radius)
 {
     HPS_REQUIRE(h, "hps_engine_set_plasma_init: null engine");
-    return static_cast<Engine*>(h)->set_plasma_init(plasma_fine_ppc, ion_fine_ppc, hollow_core_radius);
+    return static_cast<Engine*>(h)->set_plasma_init(plasma_fine, ion_fine, hollow_core_radius);
 }
 extern "C" int hps_engine_set_plasma_momentum (void* h, int species, const double* u_mean, const double* u_std, unsigned long long seed)
 {

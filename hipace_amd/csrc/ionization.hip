@@ -104,8 +104,8 @@ void k_ion_field_bounds (SlabView f, int cPsi, int cEz, int cBx, int cBy, int ts
 
 int Engine::ion_field_bounds ()
 {
-    if (!ion.tiling || !ion.d_fbound || thermal[1].warm()) return HPS_OK;
-    const TileGeom& g = ion.tiling->g;
+    if (!ions.tiling || !ion.d_fbound || ions.thermal.warm()) return HPS_OK;
+    const TileGeom& g = ions.tiling->g;
     const int cP = pc ? (int)HPS_PC_PSI : (int)HPS_C_PSI, cE = pc ? (int)HPS_PC_EZ : (int)HPS_C_EZ, cX = pc ? (int)HPS_PC_BX : (int)HPS_C_BX, cY = pc ? (int)HPS_PC_BY : (int)HPS_C_BY;
     hipLaunchKernelGGL(k_ion_field_bounds, dim3(g.ntiles), dim3(256), 0, st, SlabView(slab), cP, cE, cX, cY, g.ts, g.ntx, g.nty,
                        ion.d_fbound);
@@ -164,9 +164,8 @@ void ion_destroy (Engine& E)
 {
     (void)hipFree(E.ion.d_adk); (void)hipFree(E.ion.d_cnt);
     if (E.ion.h_cnt) (void)hipHostFree(E.ion.h_cnt);
-    (void)hipFree(E.ion.real); (void)hipFree(E.ion.pl.idcpu); (void)hipFree(E.ion.pl.ion_lev);
-    (void)hipFree(E.ion.real_alt); (void)hipFree(E.ion.pl_alt.idcpu); (void)hipFree(E.ion.pl_alt.ion_lev);
-    delete E.ion.tiling; (void)hipFree(E.ion.d_tile_flag); (void)hipFree(E.ion.d_fbound);
+    free_soa(E.ions.pl, E.ions.real); free_soa(E.ions.pl_alt, E.ions.real_alt);
+    delete E.ions.tiling; (void)hipFree(E.ion.d_tile_flag); (void)hipFree(E.ion.d_fbound);
 }
 
 IonArgs Engine::ion_args (int islice)
@@ -174,15 +173,15 @@ IonArgs Engine::ion_args (int islice)
     IonArgs a{};
     const double cSI = 299792458.0, qeSI = 1.602176634e-19, meSI = 9.1093837015e-31, ep0SI = 8.8541878128e-12;
     const double wp = std::sqrt(d.background_density_SI*qeSI*qeSI/(ep0SI*meSI));
-    a.el = pl; a.adk = ion.d_adk; a.cnt = ion.d_cnt; a.host = (volatile long long*)ion.h_cnt_dev;
+    a.el = el.pl; a.adk = ion.d_adk; a.cnt = ion.d_cnt; a.host = (volatile long long*)ion.h_cnt_dev;
     a.E0 = d.si_units ? 1.0 : wp*meSI*cSI/qeSI;
     a.clightsq_inv = 1.0/(gm.c*gm.c);
     a.Z = d.ion_Z; a.seed = d.ion_seed; a.step = (unsigned long long)step_index; a.islice = (unsigned long long)islice;
-    a.cap = np_cap; a.tile_flag = ion.d_tile_flag;
+    a.cap = el.cap; a.tile_flag = ion.d_tile_flag;
     a.product_init_lev = 0;       // the product species is the first (electron) species: not ionisable here, its particles carry level 0
     // (the tile skip is a bound for atoms at rest: neutral atoms with momentum move, their tiles are pushed -- DESIGN 8i)
-    a.fbound = (ion.tiling && ion.d_fbound && !thermal[1].warm()) ? ion.d_fbound : nullptr;
-    if (ion.tiling) { a.fb_ntx = ion.tiling->g.ntx; a.fb_nty = ion.tiling->g.nty; }
+    a.fbound = (ions.tiling && ion.d_fbound && !ions.thermal.warm()) ? ion.d_fbound : nullptr;
+    if (ions.tiling) { a.fb_ntx = ions.tiling->g.ntx; a.fb_nty = ions.tiling->g.nty; }
     a.fb_dx_inv = 1.0/gm.dx; a.fb_dy_inv = 1.0/gm.dy; a.fb_c = gm.c;
     a.seq = ++ion.seq;
     ion.pending = true;
@@ -191,13 +190,13 @@ IonArgs Engine::ion_args (int islice)
 
 int Engine::ionize_slice (int islice)
 {
-    if (!d.ion_on || ion.n == 0) return HPS_OK;
+    if (!ions.present()) return HPS_OK;
     const IonArgs a = ion_args(islice);
     const PartConsts k = base_consts(gm);
     const SlabView f(slab);
-    const dim3 grid(ceil_div(ion.n, 256)), block(256);
+    const dim3 grid(ceil_div(ions.pl.n, 256)), block(256);
     const int cP = pc ? (int)HPS_PC_PSI : (int)HPS_C_PSI, cE = pc ? (int)HPS_PC_EZ : (int)HPS_C_EZ, cX = pc ? (int)HPS_PC_BX : (int)HPS_C_BX, cY = pc ? (int)HPS_PC_BY : (int)HPS_C_BY;
-#define CALL(O) hipLaunchKernelGGL(k_ionize<O>, grid, block, 0, st, f, ion.pl, cP, cE, cX, cY, k, a)
+#define CALL(O) hipLaunchKernelGGL(k_ionize<O>, grid, block, 0, st, f, ions.pl, cP, cE, cX, cY, k, a)
     switch (d.order) { case 0: CALL(0); break; case 1: CALL(1); break; case 2: CALL(2); break; default: CALL(3); break; }
 #undef CALL
     HPS_HIP_CHECK(hipGetLastError());
@@ -221,7 +220,7 @@ int Engine::ionize_collect ()
     }
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     if (hp[1] != 0) { set_error("ionisation: the product species' arrays are full"); return HPS_ERR_ARG; }
-    np = (long)hp[0]; pl.n = np; pl_alt.n = np;
+    el.pl.n = (long)hp[0];
     ion.n_ionized = (long)hp[2];
     return HPS_OK;
 }

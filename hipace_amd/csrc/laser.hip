@@ -690,20 +690,23 @@ int laser_chi_initial (Engine& E)
     LaserState* L = E.laser;
     if (!L->chi_initial) return HPS_OK;
     const hps_deck& d = E.d;
-    const DensityProgram p0 = E.density_program(0), p1 = E.density_program(1);
-    const double n0 = p0.n_ins > 0 ? 1.0 : d.plasma_density, n1 = p1.n_ins > 0 ? 1.0 : d.ion_density;      // a program's value is the density itself
-    const double f0 = d.plasma_density > 0.0 ? n0*d.plasma_charge*d.plasma_charge*E.gm.mu0/d.plasma_mass : 0.0;
-    const double f1 = d.ion_on ? n1*d.ion_charge*d.ion_charge*E.gm.mu0/d.ion_mass*(double)d.ion_init_level*(double)d.ion_init_level : 0.0;
+    // per species: n q^2 mu0 / m, an ionisable one at its initial level; a program's value is the density itself
+    const DensityProgram p[2] = {E.density_program(0), E.density_program(1)};
+    double fac[2] = {0.0, 0.0};
+    for (const Engine::Species& s : E.sp) if (s.present()) {
+        const double n = p[s.index].n_ins > 0 ? 1.0 : s.density, lev = s.can_ionize ? (double)s.init_level : 1.0;
+        fac[s.index] = n*s.charge*s.charge*E.gm.mu0/s.mass*lev*lev;
+    }
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : INFINITY;
-    if (p0.n_ins > 0 || p1.n_ins > 0) {
+    if (p[0].n_ins > 0 || p[1].n_ins > 0) {
         hipLaunchKernelGGL(k_laser_chi_initial_prog, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), std::max(E.density_lds(0), E.density_lds(1)), E.st,
-                           L->chi_initial, L->nx, L->ny, L->dx, L->dy, L->xoff, L->yoff, f0, f1, p0, p1, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft,
+                           L->chi_initial, L->nx, L->ny, L->dx, L->dy, L->xoff, L->yoff, fac[0], fac[1], p[0], p[1], E.d_prof_r, (int)E.prof_r.size(), E.prof_ft,
                            radius_sq, E.hollow_core_radius*E.hollow_core_radius);
         HPS_HIP_CHECK(hipGetLastError());
         return HPS_OK;
     }
     hipLaunchKernelGGL(k_laser_chi_initial, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), 0, E.st, L->chi_initial, L->nx, L->ny, L->dx, L->dy,
-                       L->xoff, L->yoff, f0, f1, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, radius_sq, E.hollow_core_radius*E.hollow_core_radius);
+                       L->xoff, L->yoff, fac[0], fac[1], E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, radius_sq, E.hollow_core_radius*E.hollow_core_radius);
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
@@ -805,7 +808,7 @@ int laser_advance_slice (Engine& E, int islice)
     }
     hipLaunchKernelGGL(k_laser_phase, dim3(1), dim3(1), 0, ls, S.n00j00, S.n00jp1, S.n00jp2, nx, ny, d.laser_use_phase, E.gm.dz, L->phase);
     const dim3 grid(ceil_div(nx, 256), ny), block(256);
-    const double chi0 = d.plasma_density > 0.0 ? d.plasma_density*d.plasma_charge*d.plasma_charge*E.gm.mu0/d.plasma_mass : 0.0;
+    const double chi0 = E.el.present() ? E.el.density*E.el.charge*E.el.charge*E.gm.mu0/E.el.mass : 0.0;
     hipLaunchKernelGGL(k_laser_rhs, grid, block, 0, ls, S, SlabView(E.slab), (int)HPS_C_CHI, chi0, E.g, L->chi, nx, ny, L->phase, L->steps,
                        L->dx, L->dy, E.gm.dz, E.gm.c, d.dt, k0, L->work, L->mg_rhs, L->mg_acf_real, L->mg_acf_imag);
     if (L->mg) {

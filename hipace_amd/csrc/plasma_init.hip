@@ -168,9 +168,10 @@ void k_init_plasma_warm (hps_plasma pl, long nq, int nx, int ny, FineInit a, War
 }
 
 // the kernels' view of one species' patch and weights; wdiv = 4 with do_symmetrize (:173-177)
-static FineInit fine_args (const Engine& E, const int ppc[2], const int fine[2], double density, double radius_sq, double wdiv)
+static FineInit fine_args (const Engine& E, const Engine::Species& s, double density, double radius_sq, double wdiv)
 {
     const hps_deck& d = E.d;
+    const int *ppc = s.ppc, *fine = s.fine_ppc;
     const bool patch = E.fine_patch_set && fine[0] > 0;
     FineInit a{};
     a.level = patch ? E.d_fine_level : nullptr;
@@ -188,46 +189,45 @@ static FineInit fine_args (const Engine& E, const int ppc[2], const int fine[2],
     return a;
 }
 
-int init_plasma_fine (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
-                      double radius_sq, int species)
+int init_plasma_fine (Engine& E, const Engine::Species& s, double radius_sq)
 {
     const hps_deck& d = E.d;
-    const DensityProgram dp = E.density_program(species);
+    const DensityProgram dp = E.density_program(s.index);
     const bool prog = dp.n_ins > 0;
-    const FineInit a = fine_args(E, ppc, fine, prog ? 1.0 : density, radius_sq, 1.0);
+    const FineInit a = fine_args(E, s, prog ? 1.0 : s.density, radius_sq, 1.0);
+    const long n = s.pl.n;
     if (n != a.ncoarse + (long)(a.fx*a.fy - a.cx*a.cy)*a.ncells) { set_error("init_plasma_fine: the sheet does not have the patch's slot count"); return HPS_ERR_ARG; }
     if (prog)
-        hipLaunchKernelGGL(k_init_plasma_fine<true>, dim3(ceil_div(n, 256)), dim3(256), E.density_lds(species), E.st, p, n, d.nx, d.ny, a,
-                           d.lo[0], d.lo[1], E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp);
+        hipLaunchKernelGGL(k_init_plasma_fine<true>, dim3(ceil_div(n, 256)), dim3(256), E.density_lds(s.index), E.st, s.pl, n, d.nx, d.ny, a,
+                           d.lo[0], d.lo[1], E.gm.dx, E.gm.dy, s.init_level, s.keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp);
     else
-        hipLaunchKernelGGL(k_init_plasma_fine<false>, dim3(ceil_div(n, 256)), dim3(256), 0, E.st, p, n, d.nx, d.ny, a, d.lo[0], d.lo[1],
-                           E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp);
+        hipLaunchKernelGGL(k_init_plasma_fine<false>, dim3(ceil_div(n, 256)), dim3(256), 0, E.st, s.pl, n, d.nx, d.ny, a, d.lo[0], d.lo[1],
+                           E.gm.dx, E.gm.dy, s.init_level, s.keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp);
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }
 
-int init_plasma_warm (Engine& E, const hps_plasma& p, long n, const int ppc[2], const int fine[2], double density, int level, int keyed,
-                      double radius_sq, int species)
+int init_plasma_warm (Engine& E, const Engine::Species& s, double radius_sq)
 {
     const hps_deck& d = E.d;
     const bool sym = E.do_symmetrize;
-    const DensityProgram dp = E.density_program(species);
+    const DensityProgram dp = E.density_program(s.index);
     const bool prog = dp.n_ins > 0;
-    const FineInit a = fine_args(E, ppc, fine, prog ? 1.0 : density, radius_sq, sym ? 4.0 : 1.0);
+    const FineInit a = fine_args(E, s, prog ? 1.0 : s.density, radius_sq, sym ? 4.0 : 1.0);
     const long nq = a.ncoarse + (long)(a.fx*a.fy - a.cx*a.cy)*a.ncells;
-    if (n != (sym ? 4 : 1)*nq) { set_error("init_plasma_warm: the sheet does not have the slot count of its keys"); return HPS_ERR_ARG; }
-    const Engine::Thermal& th = E.thermal[species];
+    if (s.pl.n != (sym ? 4 : 1)*nq) { set_error("init_plasma_warm: the sheet does not have the slot count of its keys"); return HPS_ERR_ARG; }
+    const Engine::Thermal& th = s.thermal;
     WarmInit t{};
     for (int q = 0; q < 3; ++q) { t.u_mean[q] = th.u_mean[q]; t.u_std[q] = th.u_std[q]; }
     t.c = E.gm.c;
-    t.key = coll_hash(coll_hash(th.seed, (unsigned long long)species), (unsigned long long)E.step_index);
-    t.xoff = E.shifted(ppc, 0) ? -0.5 : 0.0;
-    t.yoff = E.shifted(ppc, 1) ? -0.5 : 0.0;
+    t.key = coll_hash(coll_hash(th.seed, (unsigned long long)s.index), (unsigned long long)E.step_index);
+    t.xoff = E.shifted(s.ppc, 0) ? -0.5 : 0.0;
+    t.yoff = E.shifted(s.ppc, 1) ? -0.5 : 0.0;
     t.x_mid2 = d.lo[0] + d.hi[0]; t.y_mid2 = d.lo[1] + d.hi[1];       // of the particle boundary box (:319-320)
     const dim3 grid(ceil_div(nq, 256)), block(256);
-#define CALL(SYM, PROG, LDS) hipLaunchKernelGGL((k_init_plasma_warm<SYM, PROG>), grid, block, LDS, E.st, p, nq, d.nx, d.ny, a, t, d.lo[0], d.lo[1], \
-                                                E.gm.dx, E.gm.dy, level, keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp)
-    if (prog) { if (sym) CALL(true, true, E.density_lds(species)); else CALL(false, true, E.density_lds(species)); }
+#define CALL(SYM, PROG, LDS) hipLaunchKernelGGL((k_init_plasma_warm<SYM, PROG>), grid, block, LDS, E.st, s.pl, nq, d.nx, d.ny, a, t, d.lo[0], d.lo[1], \
+                                                E.gm.dx, E.gm.dy, s.init_level, s.keyed, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, dp)
+    if (prog) { if (sym) CALL(true, true, E.density_lds(s.index)); else CALL(false, true, E.density_lds(s.index)); }
     else      { if (sym) CALL(true, false, 0); else CALL(false, false, 0); }
 #undef CALL
     HPS_HIP_CHECK(hipGetLastError());
@@ -244,19 +244,19 @@ static bool divisible (const int* fine, const int* ppc)
 
 int Engine::set_plasma_init (const int* plasma_fine, const int* ion_fine, double hollow_core)
 {
-    HPS_REQUIRE(!step_begun && !tiling, "hps_engine_set_plasma_init: call before the first hps_engine_begin_step");
+    HPS_REQUIRE(!step_begun && !el.tiling, "hps_engine_set_plasma_init: call before the first hps_engine_begin_step");
     const int none[2] = {0, 0};
     const int* pf = plasma_fine ? plasma_fine : none;
     const int* jf = ion_fine ? ion_fine : none;
     const bool p_on = pf[0] != 0 || pf[1] != 0, i_on = jf[0] != 0 || jf[1] != 0;
     // (PlasmaParticleContainer.cpp:158-163)
-    HPS_REQUIRE(!p_on || (d.plasma_density > 0.0 && divisible(pf, d.plasma_ppc)), "hps_engine_set_plasma_init: plasma fine_ppc must be positive and divisible by ppc, component by component");
-    HPS_REQUIRE(!i_on || (d.ion_on && divisible(jf, d.ion_ppc)), "hps_engine_set_plasma_init: ion fine_ppc needs the ion species and must be positive and divisible by its ppc, component by component");
+    HPS_REQUIRE(!p_on || (el.present() && divisible(pf, el.ppc)), "hps_engine_set_plasma_init: plasma fine_ppc must be positive and divisible by ppc, component by component");
+    HPS_REQUIRE(!i_on || (ions.present() && divisible(jf, ions.ppc)), "hps_engine_set_plasma_init: ion fine_ppc needs the ion species and must be positive and divisible by its ppc, component by component");
     HPS_REQUIRE(!(prevent_centered && (p_on || i_on)), PREVENT_VS_PATCH);
     // (:126-128; radius 0 = infinite)
     HPS_REQUIRE(hollow_core >= 0.0 && (d.plasma_radius <= 0.0 || hollow_core < d.plasma_radius),
                 "hps_engine_set_plasma_init: the hollow core radius must not be negative and must be smaller than the plasma radius");
-    fine_ppc[0] = pf[0]; fine_ppc[1] = pf[1]; ion_fine_ppc[0] = jf[0]; ion_fine_ppc[1] = jf[1];
+    el.fine_ppc[0] = pf[0]; el.fine_ppc[1] = pf[1]; ions.fine_ppc[0] = jf[0]; ions.fine_ppc[1] = jf[1];
     hollow_core_radius = hollow_core;
     HPS_HIP_CHECK(hipStreamSynchronize(st));
     return alloc_sheets();
@@ -264,13 +264,13 @@ int Engine::set_plasma_init (const int* plasma_fine, const int* ion_fine, double
 
 int Engine::set_plasma_momentum (int species, const double* u_mean, const double* u_std, unsigned long long seed)
 {
-    HPS_REQUIRE(!step_begun && !tiling, "hps_engine_set_plasma_momentum: call before the first hps_engine_begin_step");
+    HPS_REQUIRE(!step_begun && !el.tiling, "hps_engine_set_plasma_momentum: call before the first hps_engine_begin_step");
     HPS_REQUIRE(species == 0 || species == 1, "hps_engine_set_plasma_momentum: species must be 0 (plasma) or 1 (ion)");
-    HPS_REQUIRE(species == 0 ? d.plasma_density > 0.0 : d.ion_on != 0, "hps_engine_set_plasma_momentum: the deck does not have this species (no plasma, or no ion species)");
+    HPS_REQUIRE(sp[species].present(), "hps_engine_set_plasma_momentum: the deck does not have this species (no plasma, or no ion species)");
     HPS_REQUIRE(u_mean && u_std, "hps_engine_set_plasma_momentum: null argument");
     for (int q = 0; q < 3; ++q)
         HPS_REQUIRE(std::isfinite(u_mean[q]) && std::isfinite(u_std[q]) && u_std[q] >= 0.0, "hps_engine_set_plasma_momentum: u_std must not be negative (and u_mean, u_std finite)");
-    Thermal& th = thermal[species];
+    Thermal& th = sp[species].thermal;
     for (int q = 0; q < 3; ++q) { th.u_mean[q] = u_mean[q]; th.u_std[q] = u_std[q]; }
     th.seed = seed;
     return HPS_OK;
@@ -278,8 +278,8 @@ int Engine::set_plasma_momentum (int species, const double* u_mean, const double
 
 int Engine::set_plasma_symmetry (int symmetrize, int prevent_centered_particle)
 {
-    HPS_REQUIRE(!step_begun && !tiling, "hps_engine_set_plasma_symmetry: call before the first hps_engine_begin_step");
-    HPS_REQUIRE(!(prevent_centered_particle && (fine_patch_set || fine_ppc[0] > 0 || ion_fine_ppc[0] > 0)), PREVENT_VS_PATCH);
+    HPS_REQUIRE(!step_begun && !el.tiling, "hps_engine_set_plasma_symmetry: call before the first hps_engine_begin_step");
+    HPS_REQUIRE(!(prevent_centered_particle && (fine_patch_set || el.fine_ppc[0] > 0 || ions.fine_ppc[0] > 0)), PREVENT_VS_PATCH);
     do_symmetrize = symmetrize != 0; prevent_centered = prevent_centered_particle != 0;
     HPS_HIP_CHECK(hipStreamSynchronize(st));
     return alloc_sheets();
@@ -287,7 +287,7 @@ int Engine::set_plasma_symmetry (int symmetrize, int prevent_centered_particle)
 
 int Engine::set_fine_patch (const unsigned char* mask_host, int transition_cells)
 {
-    HPS_REQUIRE(!step_begun && !tiling, "hps_engine_set_fine_patch: call before the first hps_engine_begin_step");
+    HPS_REQUIRE(!step_begun && !el.tiling, "hps_engine_set_fine_patch: call before the first hps_engine_begin_step");
     HPS_REQUIRE(mask_host, "hps_engine_set_fine_patch: null mask");
     HPS_REQUIRE(!prevent_centered, PREVENT_VS_PATCH);
     HPS_REQUIRE(transition_cells >= 0, "hps_engine_set_fine_patch: fine_transition_cells must not be negative");
@@ -340,7 +340,7 @@ int Engine::set_density_expr (int species, int n_progs, const hps_expr* progs, c
     static const char* const fn = "hps_engine_set_density_expr";
     HPS_REQUIRE(!step_begun, std::string(fn) + ": call before the first hps_engine_begin_step");
     HPS_REQUIRE(species == 0 || species == 1, std::string(fn) + ": species must be 0 (plasma) or 1 (ion)");
-    HPS_REQUIRE(species == 0 ? d.plasma_density > 0.0 : d.ion_on != 0, std::string(fn) + ": the deck does not have this species (no plasma, or no ion species)");
+    HPS_REQUIRE(sp[species].present(), std::string(fn) + ": the deck does not have this species (no plasma, or no ion species)");
     HPS_REQUIRE(n_progs >= 1 && progs, std::string(fn) + ": n_progs must be >= 1 (at least one program)");
     HPS_REQUIRE(n_progs == 1 || z_pos, std::string(fn) + ": several programs need their positions (z_pos)");
     HPS_REQUIRE(!std::isnan(min_density), std::string(fn) + ": min_density is NaN");
@@ -353,7 +353,7 @@ int Engine::set_density_expr (int species, int n_progs, const hps_expr* progs, c
         if (int e = expr_check_named(fn, what.c_str(), &progs[k], 3, &dk)) return e;
         depth = std::max(depth, dk);
     }
-    DensityExpr& D = dens[species];
+    DensityExpr& D = sp[species].dens;
     D = DensityExpr{};
     for (int k = 0; k < n_progs; ++k) {
         D.ins.emplace_back(progs[k].ins, progs[k].ins + progs[k].n_ins);
@@ -363,7 +363,8 @@ int Engine::set_density_expr (int species, int n_progs, const hps_expr* progs, c
     D.depth = depth; D.min_density = min_density; D.on = true;
     std::vector<hps_expr_ins> ins;
     std::vector<double> consts;
-    for (DensityExpr& S : dens) {
+    for (Species& q : sp) {
+        DensityExpr& S = q.dens;
         S.off.clear();
         for (size_t k = 0; k < S.ins.size(); ++k) {
             const hps_expr p{(int)S.ins[k].size(), (int)S.consts[k].size(), S.ins[k].data(), S.consts[k].data()};
@@ -385,7 +386,8 @@ int Engine::set_density_expr (int species, int n_progs, const hps_expr* progs, c
 void Engine::density_begin_step (double ct)
 {
     dens_z = ct;
-    for (DensityExpr& S : dens) {
+    for (Species& q : sp) {
+        DensityExpr& S = q.dens;
         if (!S.on || S.z_pos.empty()) { S.cur = 0; continue; }
         const size_t k = std::lower_bound(S.z_pos.begin(), S.z_pos.end(), ct) - S.z_pos.begin();
         S.cur = (int)std::min(k, S.z_pos.size() - 1);
@@ -394,7 +396,7 @@ void Engine::density_begin_step (double ct)
 
 DensityProgram Engine::density_program (int species) const
 {
-    const DensityExpr& S = dens[species];
+    const DensityExpr& S = sp[species].dens;
     if (!S.on) return DensityProgram{nullptr, 0, nullptr, 0.0, 0.0};
     return DensityProgram{d_dens_ins + S.off[S.cur], (int)S.ins[S.cur].size(), d_dens_consts, dens_z, S.min_density};
 }
