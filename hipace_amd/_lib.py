@@ -287,6 +287,7 @@ _SIGS = {
     "hps_expr_eval": (C.c_int, [C.POINTER(Expr), C.c_int, C.c_long, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     "hps_engine_set_beam_external_fields": (C.c_int, [C.c_void_p, C.POINTER(Expr), C.POINTER(Expr)]),
     "hps_engine_set_density_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Expr), C.c_void_p, C.c_double]),
+    "hps_engine_set_beam_fixed_ppc": (C.c_int, [C.c_void_p, C.POINTER(Expr), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_ulonglong]),
     "hps_adaptive_set_density_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Expr), C.c_void_p]),
     "hps_adaptive_rho_max": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
     "hps_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

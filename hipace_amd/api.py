@@ -537,6 +537,8 @@ class AdaptiveTimeStep:
         default: the deck's u_mean[2] and beam_uz_std.  -> dt"""
         um = self.deck["beam_umean"][2] if uz_mean is None else uz_mean
         us = self.deck.get("beam_uz_std", 0.0) if uz_std is None else uz_std
+        if uz_std is None and us == 0.0 and self.deck.get("beam_density_expr") is not None:
+            us = (self.deck.get("beam_u_std") or (0, 0, 0))[2]      # decks.BEAM_INIT_DEFAULT: the fixed_ppc beam's own u_std[2]
         dt = C.c_double()
         check(_lib.lib().hps_adaptive_initial_dt(self._h, float(um), float(us), int(nstages), C.byref(dt)))
         return dt.value
@@ -572,6 +574,11 @@ class SliceEngine:
         self.deck = dict(deck)
         self.step_times = []            # hipace.dt = adaptive in a pipeline: (step, t, dt) of every step this engine began
         self._dk = _lib.fill_struct(_lib.Deck(), deck)
+        # <beam>.density(x,y,z), min_density, u_std, random_ppc (decks.BEAM_INIT_DEFAULT): the device generator replaces the beam
+        # of beam_profile, so the library is not asked to build that one first.  A deck without these keys changes nothing here.
+        beam = _decks.beam_init(deck)
+        if beam is not None:
+            self._dk.beam_profile = -1
         self._h = C.c_void_p()
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
         if tile_size is not None:
@@ -621,6 +628,8 @@ class SliceEngine:
         # <plasma>.density(x,y,z), min_density, density_table_file (decks.DENSITY_EXPR_DEFAULT): a deck without these keys makes no call
         for sp, spec in _decks.density_exprs(deck).items():
             self.set_density_expr(sp, *spec)
+        if beam is not None:      # (a deck without the keys makes no call)
+            self.set_beam_fixed_ppc(**beam)
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -984,6 +993,30 @@ class SliceEngine:
         check(_lib.lib().hps_engine_set_beam_particles(self._h, soa.shape[1], soa.ctypes.data_as(C.c_void_p),
                                                        C.byref(out) if allow_outside else None))
         return out.value
+
+    def set_beam_fixed_ppc(self, expr, constants=None, min_density=0.0, u_std=None, random_ppc=None, seed=1):
+        """The general fixed_ppc beam in place of the deck's, generated on the device (hps_engine_set_beam_fixed_ppc):
+        <beam>.density(x,y,z) as a string in the input file's syntax (or a number, or a Program over x, y, z), constants:
+        my_constants, <beam>.min_density, u_std (3, units of c), random_ppc (3 flags) and the seed of the draws.  The deck gives
+        beam_ppc, the window beam_zmin / beam_zmax / beam_radius around beam_pos_mean, beam_umean, charge and mass.  Before the
+        first begin_step; whichever of this and set_beam_particles is called last holds."""
+        if isinstance(expr, _expr.Program):
+            prog = expr
+            if len(prog.variables) > 3 and any(o == "var" and a >= 3 for o, a in prog.ins):
+                raise ValueError("set_beam_fixed_ppc: the beam's density is a function of x, y, z and cannot read t")
+            if len(prog.variables) != 3:
+                prog = _expr.Program(prog.ins, prog.consts, ("x", "y", "z"), prog.text)
+        else:
+            try:
+                prog = _expr.compile_expr(expr, ("x", "y", "z"), constants)
+            except ValueError as e:
+                if "unknown name: 't'" in str(e):
+                    raise ValueError(f"set_beam_fixed_ppc: the beam's density is a function of x, y, z and cannot read t ({e})") from None
+                raise
+        c, keep = prog.c_struct()
+        us = (C.c_double * 3)(*[float(v) for v in u_std]) if u_std is not None else None
+        rp = (C.c_int * 3)(*[int(bool(v)) for v in random_ppc]) if random_ppc is not None else None
+        check(_lib.lib().hps_engine_set_beam_fixed_ppc(self._h, C.byref(c), float(min_density), us, rp, int(seed)))
 
     def set_beam_storage(self, tensor, injected_beam_support=False):
         """Use `tensor` (float64, 7*nbeam, on this device) as the engine's beam blocks; None = own.

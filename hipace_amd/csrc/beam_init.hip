@@ -1,0 +1,324 @@
+// beam_init.hip -- the general fixed_ppc beam on the device: <beam>.density(x,y,z) as an expression program, min_density, u_std
+// and random_ppc (InitBeamFixedPPC3D / InitBeamFixedPPCSlice, particles/beam/BeamParticleContainerInit.cpp:119-346;
+// get_position_unit_cell, particles/particles_utils/ParticleUtil.H:30-64) for the whole box.
+//
+// A lattice point is (cell i, j, k; i_part < ppc_x ppc_y ppc_z).  The beam's order is Engine::init_beam's and the reference's
+// exclusive scan: slices head first (k descending), inside a slice j, then i, then i_part.  One workgroup owns one row
+// (k, j) of the window that zmin, zmax and the radius leave, and walks the row's points (i, i_part) in that order, 256 at a time:
+//     k_beam_fixed_ppc<false>   counts the row's particles                    -> count[row j][slice k]
+//     k_beam_row_offsets        running sums along j, one lane per slice      -> the row's first index in its slice, slice totals
+//     (host)                    running sum of the nz slice totals            -> beam_off[nz + 1]
+//     k_beam_fixed_ppc<true>    the same walk; a ballot ranks the particles of a chunk, the row's running index carries over
+//                               the chunks, and every particle goes straight into the engine's block of its slice
+// Both walks compute the same points from the same numbers -- every random draw is a function of (seed, tag, the point's global
+// slot, component), never of a lane or of the packed index -- so the count and the fill agree, and the beam does not depend on
+// the launch.  No atomics.  The program's stack is the lane's column of the workgroup's dynamic LDS ([level][lane], expr.h).
+#include "engine.h"
+#include "expr.h"
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+namespace hps {
+
+constexpr int BI_THREADS = 256;
+constexpr unsigned long long BI_TAG_POSITION = 0, BI_TAG_MOMENTUM = 1;      // second link of the draws' key
+
+struct BeamInit {
+    int nx, ny, nz, ppc[3], nppc;
+    int i_lo, ni, j_lo, nj, k_lo, nk;             // the window of cells that can hold a particle
+    double lo[3], h[3];
+    double x_mean, y_mean, zmin, zmax, radius_sq, min_density, scale_fac, c;
+    double u_mean[3], u_std[3];
+    int rnd[3];                                   // random_ppc
+    unsigned long long key_pos, key_mom;          // hash(seed, tag)
+    const hps_expr_ins* ins; int n_ins; const double* consts;
+};
+
+struct BeamPoint { double x, y, z, density; bool keep; unsigned long long slot; };
+
+// point q = (i - i_lo) nppc + i_part of row (k, j): position, selection and density.  Every operation rounds once (no
+// contraction), in the order of Engine::init_beam, so that numpy reproduces the positions bit for bit.
+__device__ __forceinline__ BeamPoint beam_point (const BeamInit& a, int k, int j, int q, ExprLdsStack& st)
+{
+#pragma clang fp contract(off)
+    const int ci = q/a.nppc, ip = q - ci*a.nppc, i = a.i_lo + ci;
+    const int nyz = a.ppc[1]*a.ppc[2];
+    const int ixp = ip/nyz, iyp = (ip % nyz) % a.ppc[1], izp = (ip % nyz)/a.ppc[1];      // get_position_unit_cell
+    BeamPoint p;
+    p.slot = (((unsigned long long)k*a.ny + j)*a.nx + i)*a.nppc + ip;
+    double r[3] = {(0.5 + ixp)/a.ppc[0], (0.5 + iyp)/a.ppc[1], (0.5 + izp)/a.ppc[2]};
+    const bool random = (a.rnd[0] | a.rnd[1] | a.rnd[2]) != 0;
+    if (random) {
+        const unsigned long long zk = coll_hash(a.key_pos, p.slot);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) if (a.rnd[d]) r[d] = coll_unit(coll_hash(zk, (unsigned long long)d));
+    }
+    p.x = a.lo[0] + (i + r[0])*a.h[0];
+    p.y = a.lo[1] + (j + r[1])*a.h[1];
+    p.z = a.lo[2] + (k + r[2])*a.h[2];
+    // evenly spaced: the point itself is tested; randomly placed: the lower corner of its cell (:166-183)
+    const double tx = random ? a.lo[0] + i*a.h[0] : p.x, ty = random ? a.lo[1] + j*a.h[1] : p.y, tz = random ? a.lo[2] + k*a.h[2] : p.z;
+    const double rx = tx - a.x_mean, ry = ty - a.y_mean;
+    const bool out = tz >= a.zmax || tz < a.zmin || (rx*rx + ry*ry) > a.radius_sq;
+    const ExprXyz v{p.x, p.y, p.z};
+    p.density = expr_run(a.ins, a.n_ins, a.consts, v, st);
+    p.keep = !out && !(p.density <= a.min_density);
+    return p;
+}
+
+// FILL = false: count[jj*nk + kk] = particles of row (k_lo + kk, j_lo + jj).
+// FILL = true: the particles, into block p = nz - 1 - k of `blocks` ([7][count_p] at 7 off[p]) from index first[jj*nk + kk] on.
+template <bool FILL>
+__global__ __launch_bounds__(BI_THREADS)
+void k_beam_fixed_ppc (BeamInit a, int* __restrict__ count, const long* __restrict__ first, const long* __restrict__ off,
+                       double* __restrict__ blocks)
+{
+    extern __shared__ double s_beam_stack[];
+    __shared__ int s_wave[BI_THREADS/64];
+    const int jj = blockIdx.x, kk = blockIdx.y, j = a.j_lo + jj, k = a.k_lo + kk;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    ExprLdsStack st{s_beam_stack + threadIdx.x, BI_THREADS};
+    const int nitems = a.ni*a.nppc;
+    long run = 0, cnt_p = 0;
+    double* blk = nullptr;
+    if constexpr (FILL) {
+        const int p = a.nz - 1 - k;
+        cnt_p = off[p + 1] - off[p];
+        blk = blocks + 7*off[p];
+        run = first[(long)jj*a.nk + kk];
+    }
+    for (int base = 0; base < nitems; base += BI_THREADS) {
+        const int q = base + (int)threadIdx.x;
+        const bool valid = q < nitems;
+        const BeamPoint pt = beam_point(a, k, j, valid ? q : nitems - 1, st);      // (every lane runs the program: uniform opcodes)
+        const bool keep = valid && pt.keep;
+        const unsigned long long mask = __ballot(keep);
+        if constexpr (!FILL) {
+            run += __popcll(mask);                // per wave
+        } else {
+            if (lane == 0) s_wave[wave] = __popcll(mask);
+            __syncthreads();
+            int before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < BI_THREADS/64; ++w) { const int n = s_wave[w]; before += w < wave ? n : 0; total += n; }
+            __syncthreads();
+            if (keep) {
+                const long o = run + before + __popcll(mask & ((1ULL << lane) - 1ULL));
+                double u[3] = {a.u_mean[0], a.u_mean[1], a.u_mean[2]};
+                if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0 || a.u_std[2] != 0.0) {
+                    const unsigned long long zk = coll_hash(a.key_mom, pt.slot);
+                    if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0) {
+                        double n0, n1;
+                        normal_pair(zk, 0u, n0, n1);
+                        if (a.u_std[0] != 0.0) u[0] += a.u_std[0]*n0;
+                        if (a.u_std[1] != 0.0) u[1] += a.u_std[1]*n1;
+                    }
+                    if (a.u_std[2] != 0.0) {
+                        double n2, unused;
+                        normal_pair(zk, 2u, n2, unused);
+                        u[2] += a.u_std[2]*n2;
+                    }
+                }
+                blk[o] = pt.x; blk[cnt_p + o] = pt.y; blk[2*cnt_p + o] = pt.z;
+                blk[3*cnt_p + o] = u[0]*a.c; blk[4*cnt_p + o] = u[1]*a.c; blk[5*cnt_p + o] = u[2]*a.c;
+                blk[6*cnt_p + o] = fabs(pt.density*a.scale_fac);
+            }
+            run += total;
+        }
+    }
+    if constexpr (!FILL) {
+        if (lane == 0) s_wave[wave] = (int)run;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int n = 0;
+#pragma unroll
+            for (int w = 0; w < BI_THREADS/64; ++w) n += s_wave[w];
+            count[(long)jj*a.nk + kk] = n;
+        }
+    }
+}
+
+// one lane per slice of the window: the running sum of its rows' counts (consecutive lanes read consecutive words)
+__global__ __launch_bounds__(BI_THREADS)
+void k_beam_row_offsets (const int* __restrict__ count, long* __restrict__ first, long* __restrict__ total, int nj, int nk)
+{
+    const int kk = blockIdx.x*blockDim.x + threadIdx.x;
+    if (kk >= nk) return;
+    long run = 0;
+    for (int jj = 0; jj < nj; ++jj) {
+        first[(long)jj*nk + kk] = run;
+        run += count[(long)jj*nk + kk];
+    }
+    total[kk] = run;
+}
+
+// min and max of x and y of slice p's block: mm[p] = {xlo, xhi, ylo, yhi} (an empty block: +inf, -inf)
+__global__ __launch_bounds__(BI_THREADS)
+void k_beam_extent (const double* __restrict__ blocks, const long* __restrict__ off, double* __restrict__ mm)
+{
+    __shared__ double s[4][BI_THREADS];
+    const int p = blockIdx.x;
+    const long cnt = off[p + 1] - off[p];
+    const double* x = blocks + 7*off[p];
+    const double* y = x + cnt;
+    const double inf = __longlong_as_double(0x7FF0000000000000LL);
+    double v[4] = {inf, -inf, inf, -inf};
+    for (long i = threadIdx.x; i < cnt; i += BI_THREADS) {
+        v[0] = fmin(v[0], x[i]); v[1] = fmax(v[1], x[i]); v[2] = fmin(v[2], y[i]); v[3] = fmax(v[3], y[i]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q][threadIdx.x] = v[q];
+    __syncthreads();
+    for (int n = BI_THREADS/2; n > 0; n >>= 1) {
+        if ((int)threadIdx.x < n) {
+            s[0][threadIdx.x] = fmin(s[0][threadIdx.x], s[0][threadIdx.x + n]); s[1][threadIdx.x] = fmax(s[1][threadIdx.x], s[1][threadIdx.x + n]);
+            s[2][threadIdx.x] = fmin(s[2][threadIdx.x], s[2][threadIdx.x + n]); s[3][threadIdx.x] = fmax(s[3][threadIdx.x], s[3][threadIdx.x + n]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) mm[4*p + threadIdx.x] = s[threadIdx.x][0];
+}
+
+// the moving beam's global SoA (row k at soa + k nb, particles head slice first) from the slice-major blocks
+__global__ __launch_bounds__(BI_THREADS)
+void k_beam_blocks_to_soa (const double* __restrict__ blocks, const long* __restrict__ off, double* __restrict__ soa, long nb)
+{
+    const int p = blockIdx.x, k = blockIdx.y;
+    const long first = off[p], cnt = off[p + 1] - first;
+    const double* src = blocks + 7*first + k*cnt;
+    double* dst = soa + k*nb + first;
+    for (long i = threadIdx.x; i < cnt; i += BI_THREADS) dst[i] = src[i];
+}
+
+int beam_blocks_to_soa (Engine& E, const double* blocks, double* soa, long nb)
+{
+    long* d_off = nullptr;
+    HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(E.d.nz + 1)*sizeof(long)));
+    HPS_HIP_CHECK(hipMemcpy(d_off, E.beam_off.data(), (size_t)(E.d.nz + 1)*sizeof(long), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_beam_blocks_to_soa, dim3(E.d.nz, 7), dim3(BI_THREADS), 0, E.st, blocks, d_off, soa, nb);
+    HPS_HIP_CHECK(hipGetLastError());
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));
+    HPS_HIP_CHECK(hipFree(d_off));
+    return HPS_OK;
+}
+
+// first and last cell index (clamped to 0 .. n - 1; an empty range has first > last) a coordinate range [a, b] can touch,
+// one cell of margin for the rounding of the positions; NaN or infinite ends open the range
+static void cell_window (double a, double b, double lo, double h, int n, int* first, int* count)
+{
+    const double fa = std::floor((a - lo)/h) - 1.0, fb = std::floor((b - lo)/h) + 1.0;
+    const int ia = fa > 0.0 ? (int)std::min<double>(fa, n) : 0;
+    const int ib = fb < n - 1 ? (int)std::max<double>(fb, -1.0) : n - 1;
+    *first = ia; *count = std::max(ib - ia + 1, 0);
+}
+
+// hps_engine_set_beam_fixed_ppc: everything is checked before anything of the engine changes
+int Engine::set_beam_fixed_ppc (const hps_expr* density, double min_density, const double* u_std, const int* random_ppc, unsigned long long seed)
+{
+    static const char* const fn = "hps_engine_set_beam_fixed_ppc";
+    HPS_REQUIRE(density, std::string(fn) + ": null program");
+    HPS_REQUIRE(steps_begun == 0 && step_index < 0, std::string(fn) + ": call before the first hps_engine_begin_step");
+    HPS_REQUIRE(d.beam_ppc[0] >= 1 && d.beam_ppc[1] >= 1 && d.beam_ppc[2] >= 1, std::string(fn) + ": every entry of beam_ppc must be at least 1");
+    HPS_REQUIRE(!std::isnan(min_density) && min_density != std::numeric_limits<double>::infinity(), std::string(fn) + ": min_density must be a number below +infinity");
+    for (int q = 0; u_std && q < 3; ++q)
+        HPS_REQUIRE(std::isfinite(u_std[q]) && u_std[q] >= 0.0, std::string(fn) + ": u_std must be finite and must not be negative");
+    int depth = 0;
+    if (int e = expr_check_named(fn, "density: ", density, 3, &depth)) return e;
+    const long nppc = (long)d.beam_ppc[0]*d.beam_ppc[1]*d.beam_ppc[2];
+    HPS_REQUIRE(nppc*d.nx < (1L << 30), std::string(fn) + ": beam_ppc is too large (more than 2^30 lattice points in a row of cells)");
+
+    BeamInit a{};
+    a.nx = d.nx; a.ny = d.ny; a.nz = d.nz; a.nppc = (int)nppc;
+    for (int q = 0; q < 3; ++q) {
+        a.ppc[q] = d.beam_ppc[q]; a.lo[q] = d.lo[q];
+        a.u_mean[q] = d.beam_umean[q]; a.u_std[q] = u_std ? u_std[q] : 0.0; a.rnd[q] = random_ppc ? (random_ppc[q] != 0) : 0;
+    }
+    a.h[0] = gm.dx; a.h[1] = gm.dy; a.h[2] = gm.dz;
+    a.x_mean = d.beam_pos_mean[0]; a.y_mean = d.beam_pos_mean[1]; a.zmin = d.beam_zmin; a.zmax = d.beam_zmax;
+    a.radius_sq = d.beam_radius*d.beam_radius; a.min_density = min_density; a.c = gm.c;
+    a.scale_fac = d.si_units ? gm.dx*gm.dy*gm.dz/(int)nppc : 1.0/(int)nppc;      // BeamParticleContainerInit.cpp:215-216, as Engine::init_beam
+    a.key_pos = coll_hash(seed, BI_TAG_POSITION); a.key_mom = coll_hash(seed, BI_TAG_MOMENTUM);
+    a.n_ins = density->n_ins;
+    const double R = std::fabs(d.beam_radius);
+    cell_window(a.x_mean - R, a.x_mean + R, d.lo[0], gm.dx, d.nx, &a.i_lo, &a.ni);
+    cell_window(a.y_mean - R, a.y_mean + R, d.lo[1], gm.dy, d.ny, &a.j_lo, &a.nj);
+    cell_window(a.zmin, a.zmax, d.lo[2], gm.dz, d.nz, &a.k_lo, &a.nk);
+    const bool window = a.ni > 0 && a.nj > 0 && a.nk > 0;
+    HPS_REQUIRE(a.nk <= 65535, std::string(fn) + ": more than 65535 slices");
+
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    release_beam();
+    host_beam = true;
+    beam_off.assign(d.nz + 1, 0);
+    double box[4] = {0.0, 0.0, 0.0, 0.0};
+    double* blocks = nullptr;
+    long n = 0;
+    if (window) {
+        hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; int* d_count = nullptr; long *d_first = nullptr, *d_total = nullptr, *d_off = nullptr;
+        double* d_mm = nullptr;
+        const size_t rows = (size_t)a.nj*a.nk, lds = (size_t)std::max(depth - 1, 0)*BI_THREADS*sizeof(double);
+        auto release = [&] { (void)hipFree(d_ins); (void)hipFree(d_consts); (void)hipFree(d_count); (void)hipFree(d_first); (void)hipFree(d_total);
+                             (void)hipFree(d_off); (void)hipFree(d_mm); };
+        auto run = [&] () -> int {
+            HPS_HIP_CHECK(hipMalloc(&d_ins, (size_t)density->n_ins*sizeof(hps_expr_ins)));
+            HPS_HIP_CHECK(hipMalloc(&d_consts, (size_t)std::max(density->n_const, 1)*sizeof(double)));
+            HPS_HIP_CHECK(hipMemcpy(d_ins, density->ins, (size_t)density->n_ins*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
+            if (density->n_const > 0) HPS_HIP_CHECK(hipMemcpy(d_consts, density->consts, (size_t)density->n_const*sizeof(double), hipMemcpyHostToDevice));
+            a.ins = d_ins; a.consts = d_consts;
+            HPS_HIP_CHECK(hipMalloc(&d_count, rows*sizeof(int)));
+            HPS_HIP_CHECK(hipMalloc(&d_first, rows*sizeof(long)));
+            HPS_HIP_CHECK(hipMalloc(&d_total, (size_t)a.nk*sizeof(long)));
+            HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(d.nz + 1)*sizeof(long)));
+            HPS_HIP_CHECK(hipMalloc(&d_mm, (size_t)4*d.nz*sizeof(double)));
+            const dim3 grid(a.nj, a.nk), block(BI_THREADS);
+            hipLaunchKernelGGL(k_beam_fixed_ppc<false>, grid, block, lds, st, a, d_count, nullptr, nullptr, nullptr);
+            HPS_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_beam_row_offsets, dim3(ceil_div(a.nk, BI_THREADS)), block, 0, st, d_count, d_first, d_total, a.nj, a.nk);
+            HPS_HIP_CHECK(hipGetLastError());
+            std::vector<long> total((size_t)a.nk);
+            HPS_HIP_CHECK(hipMemcpyAsync(total.data(), d_total, total.size()*sizeof(long), hipMemcpyDeviceToHost, st));
+            HPS_HIP_CHECK(hipStreamSynchronize(st));
+            for (int p = 0; p < d.nz; ++p) {              // head slice first
+                const int kk = d.nz - 1 - p - a.k_lo;
+                beam_off[p + 1] = beam_off[p] + ((kk >= 0 && kk < a.nk) ? total[(size_t)kk] : 0);
+            }
+            n = beam_off[d.nz];
+            if (n == 0) return HPS_OK;
+            HPS_HIP_CHECK(hipMemcpyAsync(d_off, beam_off.data(), (size_t)(d.nz + 1)*sizeof(long), hipMemcpyHostToDevice, st));
+            HPS_HIP_CHECK(hipMalloc(&blocks, (size_t)7*n*sizeof(double)));
+            hipLaunchKernelGGL(k_beam_fixed_ppc<true>, grid, block, lds, st, a, nullptr, d_first, d_off, blocks);
+            HPS_HIP_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(k_beam_extent, dim3(d.nz), block, 0, st, blocks, d_off, d_mm);
+            HPS_HIP_CHECK(hipGetLastError());
+            std::vector<double> mm((size_t)4*d.nz);
+            HPS_HIP_CHECK(hipMemcpyAsync(mm.data(), d_mm, mm.size()*sizeof(double), hipMemcpyDeviceToHost, st));
+            HPS_HIP_CHECK(hipStreamSynchronize(st));
+            box[0] = box[2] = std::numeric_limits<double>::infinity(); box[1] = box[3] = -std::numeric_limits<double>::infinity();
+            for (int p = 0; p < d.nz; ++p) {
+                box[0] = std::min(box[0], mm[(size_t)4*p]);     box[1] = std::max(box[1], mm[(size_t)4*p + 1]);
+                box[2] = std::min(box[2], mm[(size_t)4*p + 2]); box[3] = std::max(box[3], mm[(size_t)4*p + 3]);
+            }
+            return HPS_OK;
+        };
+        const int e = run();
+        release();
+        if (e) {                                   // the engine is left without a beam
+            (void)hipFree(blocks); beam_off.assign(d.nz + 1, 0);
+            (void)install_beam_device(nullptr, 0, box);
+            return e;
+        }
+    }
+    return install_beam_device(blocks, n, box);
+}
+
+} // namespace hps
+
+extern "C" int hps_engine_set_beam_fixed_ppc (void* h, const hps_expr* density, double min_density, const double u_std[3], const int random_ppc[3],
+                                              unsigned long long seed)
+{
+    HPS_REQUIRE(h, "hps_engine_set_beam_fixed_ppc: null engine");
+    return static_cast<hps::Engine*>(h)->set_beam_fixed_ppc(density, min_density, u_std, random_ppc, seed);
+}

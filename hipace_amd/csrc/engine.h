@@ -258,6 +258,13 @@ struct Engine {
     int init_beam ();
     int install_beam (std::vector<double> (&h)[7]);
     int set_beam_particles (long n, const double* soa_host, long* n_outside);
+    // beam_init.hip: the general fixed_ppc beam, generated on the device; install_beam_device takes its blocks
+    // (ownership too: they become beam_init) with beam_off filled in and box = {xlo, xhi, ylo, yhi} of the particles
+    int set_beam_fixed_ppc (const hps_expr* density, double min_density, const double* u_std, const int* random_ppc, unsigned long long seed);
+    int install_beam_device (double* blocks_dev, long n, const double box[4]);
+    void release_beam ();                                               // the beam's device storage, ahead of another beam
+    void set_beam_box (double xlo, double xhi, double ylo, double yhi);  // beam_box_init from the particles' extent
+    int install_moving_beam (const std::vector<double> (*h)[7]);        // the moving beam's storage; h null: filled from beam_init on the device
     int begin_step ();
     int deposit_beam_slice (int islice, int cjx, int cjy, int cjz, const int* go = nullptr);
     void deposit_grid_current (int islice, int cjz);
@@ -322,6 +329,7 @@ int laser_copy_insitu (Engine& E, double* out_host);
 int expr_check_named (const char* fn, const char* what, const hps_expr* p, int n_vars, int* depth);
 bool expr_is_zero (const hps_expr& p);
 int expr_append (const hps_expr& p, std::vector<hps_expr_ins>& ins, std::vector<double>& consts);
+int beam_blocks_to_soa (Engine& E, const double* blocks, double* soa, long nb);      // beam_init.hip: slice-major blocks -> global SoA (beam_off)
 int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz);      // beam.hip
 int beam_push_moving (Engine& E, int islice);
 int beam_push_slice (Engine& E, int islice, int p, long bound);

@@ -444,11 +444,48 @@ int Engine::set_beam_particles (long n, const double* soa, long* n_outside)
     }
     host_beam = true;
     HPS_HIP_CHECK(hipStreamSynchronize(st));
+    release_beam();
+    return install_beam(h);
+}
+
+void Engine::release_beam ()
+{
     (void)hipFree(beam_data); (void)hipFree(beam_init); (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr);
     (void)hipFree(d_B); (void)hipFree(d_nfront); (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow);
     beam_data = beam_init = beam_cur = nullptr; bm_store = nullptr; bm_nsub = bm_nsub_scr = nullptr;
     d_B = nullptr; d_nfront = nullptr; d_Bimp = nullptr; d_beam_overflow = nullptr;
-    return install_beam(h);
+}
+
+// support of the beam's currents from the extent of its nbeam particles
+void Engine::set_beam_box (double xlo, double xhi, double ylo, double yhi)
+{
+    const int js = d.nx + 2*g, jn = d.ny + 2*g;
+    full_box = Box{0, js - 1, 0, jn - 1};
+    beam_box_init = Box{0, -1, 0, -1};          // empty
+    if (nbeam > 0) {
+        // nearest cell -+ (deposit footprint 2 + one cell for the centred differences + 1 spare)
+        const int m = 4;
+        beam_box_init.ilo = std::max(0,      (int)std::floor((xlo - gm.xoff)/gm.dx + 0.5) - m + g);
+        beam_box_init.ihi = std::min(js - 1, (int)std::floor((xhi - gm.xoff)/gm.dx + 0.5) + m + g);
+        beam_box_init.jlo = std::max(0,      (int)std::floor((ylo - gm.yoff)/gm.dy + 0.5) - m + g);
+        beam_box_init.jhi = std::min(jn - 1, (int)std::floor((yhi - gm.yoff)/gm.dy + 0.5) + m + g);
+    }
+    if (d.grid_current_on) beam_box_init = full_box;      // the grid current fills jz_beam of every cell
+    beam_box = beam_box_init;
+}
+
+// the beam's device storage from blocks the device has filled (beam_init.hip; beam_off filled in): no particle crosses to the host
+int Engine::install_beam_device (double* blocks_dev, long n, const double box[4])
+{
+    nbeam = n;
+    set_beam_box(box[0], box[1], box[2], box[3]);
+    if (nbeam > 0) {
+        beam_init = blocks_dev;
+        HPS_HIP_CHECK(hipMalloc(&beam_data, 7*nbeam*sizeof(double)));
+        HPS_HIP_CHECK(hipMemcpy(beam_data, beam_init, 7*nbeam*sizeof(double), hipMemcpyDeviceToDevice));
+        beam_cur = beam_data;
+    }
+    return install_moving_beam(nullptr);
 }
 
 // the beam's device storage from the host arrays h[7] (head slice first, beam_off filled in)
@@ -456,21 +493,12 @@ int Engine::install_beam (std::vector<double> (&h)[7])
 {
     nbeam = (long)h[0].size();
     {
-        const int js = d.nx + 2*g, jn = d.ny + 2*g;
-        full_box = Box{0, js - 1, 0, jn - 1};
-        beam_box_init = Box{0, -1, 0, -1};          // empty
+        double xlo = 0.0, xhi = 0.0, ylo = 0.0, yhi = 0.0;
         if (nbeam > 0) {
-            double xlo = h[0][0], xhi = h[0][0], ylo = h[1][0], yhi = h[1][0];
+            xlo = xhi = h[0][0]; ylo = yhi = h[1][0];
             for (long k = 1; k < nbeam; ++k) { xlo = std::min(xlo, h[0][k]); xhi = std::max(xhi, h[0][k]); ylo = std::min(ylo, h[1][k]); yhi = std::max(yhi, h[1][k]); }
-            // nearest cell -+ (deposit footprint 2 + one cell for the centred differences + 1 spare)
-            const int m = 4;
-            beam_box_init.ilo = std::max(0,      (int)std::floor((xlo - gm.xoff)/gm.dx + 0.5) - m + g);
-            beam_box_init.ihi = std::min(js - 1, (int)std::floor((xhi - gm.xoff)/gm.dx + 0.5) + m + g);
-            beam_box_init.jlo = std::max(0,      (int)std::floor((ylo - gm.yoff)/gm.dy + 0.5) - m + g);
-            beam_box_init.jhi = std::min(jn - 1, (int)std::floor((yhi - gm.yoff)/gm.dy + 0.5) + m + g);
         }
-        if (d.grid_current_on) beam_box_init = full_box;      // the grid current fills jz_beam of every cell
-        beam_box = beam_box_init;
+        set_beam_box(xlo, xhi, ylo, yhi);
     }
     if (nbeam > 0) {
         // slice-major blocks: block p (p-th slice from the head) = [7][count_p] at 7*beam_off[p]
@@ -486,6 +514,11 @@ int Engine::install_beam (std::vector<double> (&h)[7])
         HPS_HIP_CHECK(hipMemcpy(beam_data, beam_init, 7*nbeam*sizeof(double), hipMemcpyDeviceToDevice));
         beam_cur = beam_data;
     }
+    return install_moving_beam(&h);
+}
+
+int Engine::install_moving_beam (const std::vector<double> (*h)[7])
+{
     moving = (d.dt != 0.0 || d.dt_adaptive);
     if (moving) {
         // global SoA in head-first order + device boundaries (beam.hip)
@@ -510,8 +543,10 @@ int Engine::install_beam (std::vector<double> (&h)[7])
                 HPS_HIP_CHECK(hipMemcpy(bm_store + (size_t)(7 + q)*nb, v.data(), nbeam*sizeof(double), hipMemcpyHostToDevice));
             }
         }
-        for (int k = 0; k < 7 && nbeam > 0; ++k)
-            HPS_HIP_CHECK(hipMemcpy(bm_store + (size_t)k*nb, h[k].data(), nbeam*sizeof(double), hipMemcpyHostToDevice));
+        for (int k = 0; h && k < 7 && nbeam > 0; ++k)
+            HPS_HIP_CHECK(hipMemcpy(bm_store + (size_t)k*nb, (*h)[k].data(), nbeam*sizeof(double), hipMemcpyHostToDevice));
+        if (!h && nbeam > 0)
+            if (int e = beam_blocks_to_soa(*this, beam_init, bm_store, nb)) return e;
         HPS_HIP_CHECK(hipMemset(bm_nsub, 0, (size_t)nb*sizeof(int)));
         h_B.assign(beam_off.begin(), beam_off.end());
         HPS_HIP_CHECK(hipMalloc(&d_B, (size_t)(d.nz + 1)*sizeof(long)));

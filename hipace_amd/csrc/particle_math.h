@@ -226,6 +226,14 @@ __host__ __device__ inline unsigned long long coll_hash (unsigned long long h, u
     return z;
 }
 __device__ __forceinline__ double coll_unit (unsigned long long z) { return (double)(z >> 11)*(1.0/9007199254740992.0); }
+// two standard normal deviates from the draws (draw, draw + 1) of the key zk: Box-Muller (the warm plasma's and the beam's momenta)
+__device__ __forceinline__ void normal_pair (unsigned long long zk, unsigned draw, double& nc, double& ns)
+{
+    const double u1 = 1.0 - coll_unit(coll_hash(zk, draw)), u2 = coll_unit(coll_hash(zk, draw + 1));      // u1 in (0, 1]
+    const double r = sqrt(-2.0*log(u1));
+    sincos(2.0*M_PI*u2, &ns, &nc);
+    nc *= r; ns *= r;
+}
 
 struct IonArgs {
     hps_plasma el;                       // product species: electrons are appended behind cnt[0] particles

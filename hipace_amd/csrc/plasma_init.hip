@@ -121,14 +121,6 @@ struct WarmInit {
     double xoff, yoff, x_mid2, y_mid2;
 };
 
-__device__ __forceinline__ void normal_pair (unsigned long long zk, unsigned draw, double& nc, double& ns)
-{
-    const double u1 = 1.0 - coll_unit(coll_hash(zk, draw)), u2 = coll_unit(coll_hash(zk, draw + 1));      // u1 in (0, 1]
-    const double r = sqrt(-2.0*log(u1));
-    sincos(2.0*M_PI*u2, &ns, &nc);
-    nc *= r; ns *= r;
-}
-
 template <bool SYM, bool PROG>
 __global__ __launch_bounds__(256)
 void k_init_plasma_warm (hps_plasma pl, long nq, int nx, int ny, FineInit a, WarmInit t, double lox, double loy, double dx, double dy,

@@ -106,6 +106,51 @@ DENSITY_EXPR_DEFAULT = dict(plasma_density_expr=None, ion_density_expr=None, pla
                             density_constants=None)
 
 
+# The general fixed_ppc beam: <beam>.density(x,y,z), min_density, u_std, random_ppc (BeamParticleContainer.cpp; InitBeamFixedPPCSlice,
+# BeamParticleContainerInit.cpp:198-346).  Kept apart from _DEFAULT like PLASMA_INIT_DEFAULT and applied by SliceEngine
+# through hps_engine_set_beam_fixed_ppc, which generates the beam on the device; a deck without beam_density_expr keeps the beam
+# of its beam_profile.  The expression is a string in the input file's syntax (or a number) over x, y, z whose value is the density
+# itself (beam_profile, beam_density and beam_pos_std are then ignored; the window beam_zmin / beam_zmax / beam_radius around
+# beam_pos_mean holds); beam_u_std in units of c; beam_random_ppc per direction; beam_seed keys the position and momentum draws;
+# beam_density_constants is my_constants.  beam_profile_expr(deck) writes the deck's own profile as such an expression.
+BEAM_INIT_DEFAULT = dict(beam_density_expr=None, beam_min_density=0.0, beam_u_std=(0, 0, 0), beam_random_ppc=(0, 0, 0), beam_seed=1,
+                         beam_density_constants=None)
+
+
+def beam_profile_expr(deck):
+    """(expression, constants) of the deck's own beam_profile -- 0 gaussian, 1 flattop -- in the operation order of the engine's
+    host generator, for a deck that only wants beam_u_std or beam_random_ppc: dict(deck, beam_density_expr=..., beam_density_constants=...)."""
+    prof = deck.get("beam_profile", 0)
+    if prof == 1:
+        return "n0", dict(n0=float(deck["beam_density"]))
+    if prof != 0:
+        raise ValueError(f"beam_profile_expr: the deck has no beam profile to write as an expression (beam_profile = {prof})")
+    m, s = deck["beam_pos_mean"], deck["beam_pos_std"]
+    consts = dict(n0=float(deck["beam_density"]), x0=float(m[0]), y0=float(m[1]), z0=float(m[2]), sx=float(s[0]), sy=float(s[1]), sz=float(s[2]))
+    return ("n0*exp(-0.5*((x-x0)/sx)*((x-x0)/sx))*exp(-0.5*((y-y0)/sy)*((y-y0)/sy))*exp(-0.5*((z-z0)/sz)*((z-z0)/sz))", consts)
+
+
+def beam_init(deck):
+    """The deck's BEAM_INIT_DEFAULT keys as the arguments of SliceEngine.set_beam_fixed_ppc -- dict(expr, constants, min_density,
+    u_std, random_ppc, seed) -- or None for a deck without beam_density_expr.  ValueError: beam_min_density, beam_u_std or
+    beam_random_ppc without beam_density_expr (they belong to the device generator; beam_profile_expr gives the expression of
+    the deck's own profile)."""
+    text = deck.get("beam_density_expr")
+    mind = float(deck.get("beam_min_density", 0.0) or 0.0)
+    u_std = tuple(float(v) for v in (deck.get("beam_u_std") or (0, 0, 0)))
+    rnd = tuple(int(bool(v)) for v in (deck.get("beam_random_ppc") or (0, 0, 0)))
+    if len(u_std) != 3 or len(rnd) != 3:
+        raise ValueError("beam_u_std and beam_random_ppc have three entries each")
+    if text is None:
+        given = [k for k, on in (("beam_min_density", mind != 0.0), ("beam_u_std", any(u_std)), ("beam_random_ppc", any(rnd))) if on]
+        if given:
+            raise ValueError(f"{', '.join(given)}: needs beam_density_expr (decks.beam_profile_expr(deck) writes the deck's own "
+                             "beam_profile as one)")
+        return None
+    return dict(expr=text, constants=deck.get("beam_density_constants"), min_density=mind, u_std=u_std, random_ppc=rnd,
+                seed=int(deck.get("beam_seed", 1)))
+
+
 def read_density_table(path):
     """<plasma>.density_table_file: one `position expression` per line, the expression being the rest of the line
     (PlasmaParticleContainer.cpp:107-116); a line that does not start with a number, or has nothing behind it, is skipped.
@@ -199,6 +244,20 @@ def with_ion_species(d, element, density, ppc=(1, 1), mass_Da=None, initial_leve
 def blowout_wake():
     d = copy.deepcopy(_DEFAULT)
     d["n_steps"] = 2
+    return d
+
+
+HOLLOW_BEAM_DENSITY = "if(sqrt(x^2+y^2) >= r_in and sqrt(x^2+y^2) < r_out, n_ring*exp(-0.5*(z/sigma_z)^2), 0)"
+
+
+def blowout_wake_hollow_beam(r_in=0.6, r_out=1.0, density=1.0, sigma_z=1.41):
+    """The 64 x 64 blowout deck driven by a ring-shaped (hollow) driver: <beam>.density(x,y,z) as a parsed function with the
+    file's my_constants (BEAM_INIT_DEFAULT), evaluated on the device per lattice point; nothing of it on the axis."""
+    d = blowout_wake()
+    d.update(BEAM_INIT_DEFAULT)
+    d.update(beam_density_expr=HOLLOW_BEAM_DENSITY,
+             beam_density_constants=dict(r_in=float(r_in), r_out=float(r_out), n_ring=float(density), sigma_z=float(sigma_z)),
+             beam_radius=max(float(r_out), d["beam_radius"]))
     return d
 
 

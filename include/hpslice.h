@@ -952,6 +952,25 @@ int hps_engine_set_density_expr (void* handle, int species, int n_progs, const h
 int hps_adaptive_set_density_expr (void* handle, int species, int n_progs, const hps_expr* progs, const double* z_pos);
 /* *out_host = rho_max(z) (MultiPlasma::maxChargeDensity, see hps_adaptive_create); changes nothing */
 int hps_adaptive_rho_max (void* handle, double z, double* out_host);
+/* Engine: the general fixed_ppc beam -- <beam>.density(x,y,z), min_density, u_std and random_ppc of injection_type = fixed_ppc
+ * (InitBeamFixedPPC3D / InitBeamFixedPPCSlice, particles/beam/BeamParticleContainerInit.cpp:119-346; get_position_unit_cell,
+ * particles/particles_utils/ParticleUtil.H:30-64) -- generated on the device in place of the deck's beam, as
+ * hps_engine_set_beam_particles replaces it; whichever of the two is called last holds.  `density` is one program over exactly
+ * (x, y, z).  From the deck come beam_ppc, beam_zmin, beam_zmax, beam_radius, beam_pos_mean (x, y), beam_umean, beam_charge and
+ * beam_mass; beam_profile, beam_density and beam_pos_std are ignored.  Lattice point i_part of cell (i, j, k) sits at
+ * lo_d + (cell_d + r_d) cell_size_d with r_d = (0.5 + i_d)/ppc_d, or a uniform draw in [0, 1) where random_ppc[d] != 0.  It is
+ * dropped if z >= zmax, z < zmin or (x - x_mean)^2 + (y - y_mean)^2 > radius^2 -- tested on the point itself, with any
+ * random_ppc on the lower corner of its cell instead (:166-183) -- or if density(x, y, z) <= min_density.  A particle has
+ * w = |density * scale_fac| (scale_fac = 1/num_ppc, in SI units dx dy dz/num_ppc, :215-216) and u_d = (u_mean_d + u_std_d N_d) c
+ * with N_d a standard normal deviate (none is drawn where u_std_d = 0).  Every draw is a function of (seed, position | momentum,
+ * the point's global index ((k ny + j) nx + i) num_ppc + i_part, the component): the same deck, program and seed give the same
+ * beam bit for bit.  The order is the deck beam's: slices head first, then j, i, i_part.  u_std and random_ppc may be NULL
+ * (all zero).  A beam of zero particles is legal and behaves like beam_profile = -1.  Everything downstream sees an ordinary
+ * beam.  HPS_ERR_ARG, with the cause in the message: a null handle or program, a call after the first hps_engine_begin_step, a
+ * beam_ppc entry below 1, a negative or non-finite u_std, a min_density that is NaN or +infinity (-infinity: no lattice
+ * point is dropped for its density), a program hps_expr_check refuses for three variables (one that reads t). */
+int hps_engine_set_beam_fixed_ppc (void* handle, const hps_expr* density, double min_density, const double u_std[3],
+                                   const int random_ppc[3], unsigned long long seed);
 
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);
