@@ -60,6 +60,14 @@ class Expr(C.Structure):            # hps_expr
     _fields_ = [("n_ins", C.c_int), ("n_const", C.c_int), ("ins", C.POINTER(ExprIns)), ("consts", C.POINTER(C.c_double))]
 
 
+class BeamFixedWeight(C.Structure):     # hps_beam_fixed_weight
+    _fields_ = [("num_particles", C.c_long), ("profile", C.c_int), ("do_symmetrize", C.c_int), ("pos_mean_z", C.c_double),
+                ("pos_std", C.c_double * 3), ("u_mean", C.c_double * 3), ("u_std", C.c_double * 3),
+                ("zmin", C.c_double), ("zmax", C.c_double), ("radius", C.c_double), ("z_foc", C.c_double),
+                ("duz_per_uz0_dzeta", C.c_double), ("density", C.c_double), ("total_charge", C.c_double),
+                ("charge_is_specified", C.c_int)]
+
+
 class Deck(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3),
@@ -288,6 +296,8 @@ _SIGS = {
     "hps_engine_set_beam_external_fields": (C.c_int, [C.c_void_p, C.POINTER(Expr), C.POINTER(Expr)]),
     "hps_engine_set_density_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Expr), C.c_void_p, C.c_double]),
     "hps_engine_set_beam_fixed_ppc": (C.c_int, [C.c_void_p, C.POINTER(Expr), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_ulonglong]),
+    "hps_engine_set_beam_fixed_weight": (C.c_int, [C.c_void_p, C.POINTER(BeamFixedWeight), C.POINTER(Expr), C.POINTER(Expr), C.c_ulonglong,
+                                                   C.POINTER(C.c_long)]),
     "hps_adaptive_set_density_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Expr), C.c_void_p]),
     "hps_adaptive_rho_max": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
     "hps_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -579,6 +579,10 @@ class SliceEngine:
         beam = _decks.beam_init(deck)
         if beam is not None:
             self._dk.beam_profile = -1
+        # the fixed_weight beam (the deck's optional entry beam_fixed_weight, decks.BEAM_FIXED_WEIGHT_DEFAULT): likewise
+        beam_fw = _decks.beam_fixed_weight(deck)
+        if beam_fw is not None:
+            self._dk.beam_profile = -1
         self._h = C.c_void_p()
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
         if tile_size is not None:
@@ -630,6 +634,8 @@ class SliceEngine:
             self.set_density_expr(sp, *spec)
         if beam is not None:      # (a deck without the keys makes no call)
             self.set_beam_fixed_ppc(**beam)
+        if beam_fw is not None:
+            self.beam_left_out = self.set_beam_fixed_weight(**beam_fw)
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -1017,6 +1023,48 @@ class SliceEngine:
         us = (C.c_double * 3)(*[float(v) for v in u_std]) if u_std is not None else None
         rp = (C.c_int * 3)(*[int(bool(v)) for v in random_ppc]) if random_ppc is not None else None
         check(_lib.lib().hps_engine_set_beam_fixed_ppc(self._h, C.byref(c), float(min_density), us, rp, int(seed)))
+
+    def set_beam_fixed_weight(self, num_particles, position_mean, position_std, u_mean=(0.0, 0.0, 0.0), u_std=(0.0, 0.0, 0.0),
+                              density=None, total_charge=None, profile="gaussian", zmin=-np.inf, zmax=np.inf, radius=np.inf,
+                              do_symmetrize=False, z_foc=0.0, duz_per_uz0_dzeta=0.0, seed=1, constants=None):
+        """The fixed_weight beam (injection_type = fixed_weight, profile "gaussian" or "can") in place of the deck's, generated on
+        the device (hps_engine_set_beam_fixed_weight): num_particles draws -- a quarter of them with do_symmetrize --
+        with z normal about position_mean[2] with position_std[2] (gaussian) or uniform in [zmin, zmax] (can), x and y normal
+        about position_mean[0](z), position_mean[1](z): numbers, strings in the input file's syntax over z (constants:
+        my_constants) or Programs over ("z",).  Exactly one of density (the peak density) and total_charge (SI units only).
+        u_mean, u_std in units of c.  The deck gives the grid, the units, beam_charge and beam_mass.  Before the first
+        begin_step; whichever beam setter is called last holds.
+        -> (particles of invalid draws, particles of valid draws outside the box in z): both left out."""
+        if (density is None) == (total_charge is None):
+            raise ValueError("set_beam_fixed_weight: specify exclusively either total_charge or density of the beam")
+        prof = {"gaussian": 0, "can": 1}.get(profile)
+        if prof is None:
+            raise ValueError(f"set_beam_fixed_weight: only gaussian and can are supported with fixed_weight beam injection, got {profile!r}")
+        if len(position_mean) != 3 or len(position_std) != 3 or len(u_mean) != 3 or len(u_std) != 3:
+            raise ValueError("set_beam_fixed_weight: position_mean, position_std, u_mean and u_std have three entries each")
+        progs = []
+        for q in range(2):
+            m = position_mean[q]
+            if isinstance(m, _expr.Program):
+                if tuple(m.variables) != ("z",):
+                    raise ValueError(f"set_beam_fixed_weight: position_mean[{q}] is a function of z alone")
+                progs.append(m)
+                continue
+            try:
+                progs.append(_expr.compile_expr(m, ("z",), constants))
+            except ValueError as e:
+                raise ValueError(f"set_beam_fixed_weight: position_mean[{q}] is a function of z alone ({e})") from None
+        spec = _lib.BeamFixedWeight(
+            num_particles=int(num_particles), profile=prof, do_symmetrize=int(bool(do_symmetrize)), pos_mean_z=float(position_mean[2]),
+            pos_std=(C.c_double * 3)(*[float(v) for v in position_std]), u_mean=(C.c_double * 3)(*[float(v) for v in u_mean]),
+            u_std=(C.c_double * 3)(*[float(v) for v in u_std]), zmin=float(zmin), zmax=float(zmax), radius=float(radius),
+            z_foc=float(z_foc), duz_per_uz0_dzeta=float(duz_per_uz0_dzeta), density=0.0 if density is None else float(density),
+            total_charge=0.0 if total_charge is None else float(total_charge), charge_is_specified=int(total_charge is not None))
+        (cx, keep_x), (cy, keep_y) = progs[0].c_struct(), progs[1].c_struct()
+        out = (C.c_long * 2)(0, 0)
+        check(_lib.lib().hps_engine_set_beam_fixed_weight(self._h, C.byref(spec), C.byref(cx), C.byref(cy), int(seed), out))
+        self.beam_mean_programs = (progs[0], progs[1])
+        return out[0], out[1]
 
     def set_beam_storage(self, tensor, injected_beam_support=False):
         """Use `tensor` (float64, 7*nbeam, on this device) as the engine's beam blocks; None = own.

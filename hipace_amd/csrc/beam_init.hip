@@ -13,6 +13,7 @@
 // Both walks compute the same points from the same numbers -- every random draw is a function of (seed, tag, the point's global
 // slot, component), never of a lane or of the packed index -- so the count and the fill agree, and the beam does not depend on
 // the launch.  No atomics.  The program's stack is the lane's column of the workgroup's dynamic LDS ([level][lane], expr.h).
+// Below it, the fixed_weight beam (gaussian and can profiles) by the same rule for its draws.
 #include "engine.h"
 #include "expr.h"
 
@@ -314,7 +315,262 @@ int Engine::set_beam_fixed_ppc (const hps_expr* density, double min_density, con
     return install_beam_device(blocks, n, box);
 }
 
+// ---- the fixed_weight beam (InitBeamFixedWeight3D / InitBeamFixedWeightSlice, BeamParticleContainerInit.cpp:348-475) ----
+// Draw i of nd is a function of (seed, tag, i, component) alone, so nothing but a key and the index i is ever stored per draw:
+//     k_fw_keys     one lane per draw: z, x, y, validity -> key = slice from the head | nz (invalid) | nz + 1 (outside the box), i
+//     (sort.hip)    stable radix sort of (key, i): slices head first, ascending i inside a slice -- the reference's box sort
+//     k_fw_starts   first sorted position of every key -> the slices' counts and the two left-out counts
+//     k_fw_fill     one lane per kept position o: i = perm[o], the draws of i again, X(z) and Y(z), the particle (or its four
+//                   mirror copies at 4o + q) straight into the block of its slice
+// The z draw is a stage of its own (fw_draw_z) behind which everything else only reads z.  No atomics.
+constexpr unsigned long long BI_TAG_FW_Z = 2, BI_TAG_FW_XY = 3;      // beside BI_TAG_POSITION / BI_TAG_MOMENTUM
+
+struct BeamFixedWeight {
+    long nd; int can, sym, nz;
+    double lo_z, inv_dz, pos_mean_z, z_mean, std[3], u_mean[3], u_std[3], zmin, zmax, radius_sq, z_foc, duz, c, weight;
+    unsigned long long key_z, key_xy, key_mom;        // hash(seed, tag)
+    const hps_expr_ins *ins_x, *ins_y; int n_ins_x, n_ins_y; const double *consts_x, *consts_y;
+};
+
+struct ExprZ {      // the one variable of position_mean[0], position_mean[1]
+    double z;
+    __device__ __forceinline__ double get (int) const { return z; }
+};
+
+struct FwDraw { double z, x, y; bool valid; };
+
+// stage 1: z of draw i
+__device__ __forceinline__ double fw_draw_z (const BeamFixedWeight& a, unsigned long long i)
+{
+#pragma clang fp contract(off)
+    const unsigned long long zk = coll_hash(a.key_z, i);
+    if (a.can) return coll_unit(coll_hash(zk, 0ULL))*(a.zmax - a.zmin) + a.zmin;
+    double n, unused;
+    normal_pair(zk, 0u, n, unused);
+    return a.pos_mean_z + a.std[2]*n;
+}
+
+// z, the transverse offsets about the mean and the validity of draw i (:433-443); every operation rounds once
+__device__ __forceinline__ FwDraw fw_draw (const BeamFixedWeight& a, unsigned long long i)
+{
+#pragma clang fp contract(off)
+    FwDraw d;
+    d.z = fw_draw_z(a, i);
+    double n0, n1;
+    normal_pair(coll_hash(a.key_xy, i), 0u, n0, n1);
+    d.x = a.std[0]*n0; d.y = a.std[1]*n1;
+    d.valid = !(d.z < a.zmin || d.z > a.zmax || d.x*d.x + d.y*d.y > a.radius_sq);
+    return d;
+}
+
+// Engine::set_beam_particles' rule: slice from the head, -1 outside the box
+__device__ __forceinline__ int fw_slice (const BeamFixedWeight& a, double z)
+{
+#pragma clang fp contract(off)
+    const double t = (z - a.lo_z)*a.inv_dz;
+    const int q = (t > -1.0e9 && t < 1.0e9) ? static_cast<int>(t) : -1;
+    return (q < 0 || q >= a.nz) ? -1 : a.nz - 1 - q;
+}
+
+__global__ __launch_bounds__(BI_THREADS)
+void k_fw_keys (BeamFixedWeight a, unsigned int* __restrict__ keys, unsigned int* __restrict__ idx)
+{
+    const long i = (long)blockIdx.x*BI_THREADS + threadIdx.x;
+    if (i >= a.nd) return;
+    const FwDraw d = fw_draw(a, (unsigned long long)i);
+    const int p = fw_slice(a, d.z);
+    keys[i] = (unsigned int)(!d.valid ? a.nz : p < 0 ? a.nz + 1 : p);
+    idx[i] = (unsigned int)i;
+}
+
+// first[k] = first sorted position with key >= k, k = 0 .. nkeys (keys ascending, < nkeys)
+__global__ __launch_bounds__(BI_THREADS)
+void k_fw_starts (const unsigned int* __restrict__ keys, long n, int nkeys, long* __restrict__ first)
+{
+    const long p = (long)blockIdx.x*BI_THREADS + threadIdx.x;
+    if (p > n) return;
+    const int prev = (p == 0) ? -1 : (int)keys[p - 1];
+    const int cur = (p == n) ? nkeys : (int)keys[p];
+    for (int k = prev + 1; k <= cur; ++k) first[k] = p;
+}
+
+// kept position o (sorted order, o < nkept = first[nz]) -> block keys[o] of `blocks`: [7][count_p] at 7 m first[p], m = 4 copies or 1
+__global__ __launch_bounds__(BI_THREADS)
+void k_fw_fill (BeamFixedWeight a, const unsigned int* __restrict__ keys, const unsigned int* __restrict__ perm,
+                const long* __restrict__ first, long nkept, double* __restrict__ blocks)
+{
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) double s_fw_stack[];
+    const long o = (long)blockIdx.x*BI_THREADS + threadIdx.x;
+    const bool live = o < nkept;
+    const long oo = live ? o : nkept - 1;             // (every lane runs the programs: uniform opcodes)
+    const unsigned long long i = perm[oo];
+    const int p = (int)keys[oo];
+    const FwDraw d = fw_draw(a, i);
+    double u[3] = {a.u_mean[0], a.u_mean[1], a.u_mean[2]};
+    if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0 || a.u_std[2] != 0.0) {      // the momentum draws of the fixed_ppc beam
+        const unsigned long long zk = coll_hash(a.key_mom, i);
+        if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0) {
+            double n0, n1;
+            normal_pair(zk, 0u, n0, n1);
+            if (a.u_std[0] != 0.0) u[0] = a.u_mean[0] + a.u_std[0]*n0;
+            if (a.u_std[1] != 0.0) u[1] = a.u_mean[1] + a.u_std[1]*n1;
+        }
+        if (a.u_std[2] != 0.0) {
+            double n2, unused;
+            normal_pair(zk, 2u, n2, unused);
+            u[2] = a.u_mean[2] + a.u_std[2]*n2;
+        }
+    }
+    u[2] = u[2] + (d.z - a.z_mean)*a.duz*a.u_mean[2];      // GetInitialMomentum.H:47
+    double x = d.x, y = d.y;
+    if (a.z_foc != 0.0) { x = x - a.z_foc*u[0]/u[2]; y = y - a.z_foc*u[1]/u[2]; }      // (:446-447)
+    ExprLdsStack st{s_fw_stack + threadIdx.x, BI_THREADS};
+    const ExprZ v{d.z};
+    const double X = expr_run(a.ins_x, a.n_ins_x, a.consts_x, v, st);
+    const double Y = expr_run(a.ins_y, a.n_ins_y, a.consts_y, v, st);
+    if (!live) return;
+    const int m = a.sym ? 4 : 1;
+    const long f = first[p], cnt = m*(first[p + 1] - f);
+    double* blk = blocks + 7*m*f + m*(o - f);
+    for (int q = 0; q < m; ++q) {                    // (+,+), (-,+), (+,-), (-,-) (:459-470)
+        const bool nx = (q & 1) != 0, ny = (q & 2) != 0;
+        blk[q] = nx ? X - x : X + x; blk[cnt + q] = ny ? Y - y : Y + y; blk[2*cnt + q] = d.z;
+        blk[3*cnt + q] = (nx ? -u[0] : u[0])*a.c; blk[4*cnt + q] = (ny ? -u[1] : u[1])*a.c; blk[5*cnt + q] = u[2]*a.c;
+        blk[6*cnt + q] = a.weight;
+    }
+}
+
+// hps_engine_set_beam_fixed_weight: everything is checked before anything of the engine changes
+int Engine::set_beam_fixed_weight (const hps_beam_fixed_weight* s, const hps_expr* mean_x, const hps_expr* mean_y, unsigned long long seed,
+                                   long* n_left_out)
+{
+    static const char* const name = "hps_engine_set_beam_fixed_weight";
+    const std::string fn = std::string(name) + ": ";
+    const double inf = std::numeric_limits<double>::infinity();
+    HPS_REQUIRE(s && mean_x && mean_y, fn + "null argument");
+    HPS_REQUIRE(steps_begun == 0 && step_index < 0, fn + "call before the first hps_engine_begin_step");
+    HPS_REQUIRE(s->num_particles > 0, fn + "num_particles must be positive");
+    HPS_REQUIRE(!s->do_symmetrize || s->num_particles % 4 == 0, fn + "num_particles must be divisible by 4 with do_symmetrize");
+    const long nd = s->do_symmetrize ? s->num_particles/4 : s->num_particles;
+    HPS_REQUIRE(nd < (1L << 32), fn + "num_particles: 2^32 draws or more");
+    HPS_REQUIRE(s->profile == 0 || s->profile == 1, fn + "profile must be 0 (gaussian) or 1 (can)");
+    HPS_REQUIRE(std::isfinite(s->pos_mean_z), fn + "pos_mean_z must be finite");
+    for (int q = 0; q < 3; ++q) {
+        HPS_REQUIRE(std::isfinite(s->pos_std[q]) && s->pos_std[q] > 0.0, fn + "pos_std must be positive and finite");
+        HPS_REQUIRE(std::isfinite(s->u_std[q]) && s->u_std[q] >= 0.0, fn + "u_std must be finite and must not be negative");
+        HPS_REQUIRE(std::isfinite(s->u_mean[q]), fn + "u_mean must be finite");
+    }
+    HPS_REQUIRE(!std::isnan(s->zmin) && !std::isnan(s->zmax) && !std::isnan(s->radius), fn + "zmin, zmax and radius must be numbers");
+    HPS_REQUIRE(s->profile != 1 || (std::isfinite(s->zmin) && std::isfinite(s->zmax) && s->zmin < s->zmax),
+                fn + "the can profile needs finite zmin < zmax");
+    HPS_REQUIRE(!s->charge_is_specified || d.si_units, fn + "total_charge is only valid in SI units: give the density (BeamParticleContainer.cpp:169)");
+    HPS_REQUIRE(std::isfinite(s->charge_is_specified ? s->total_charge : s->density), fn + (s->charge_is_specified ? "total_charge" : "density") + " must be finite");
+    HPS_REQUIRE(std::isfinite(s->z_foc) && std::isfinite(s->duz_per_uz0_dzeta), fn + "z_foc and duz_per_uz0_dzeta must be finite");
+    HPS_REQUIRE(s->z_foc == 0.0 || s->u_mean[2] != 0.0, fn + "z_foc needs u_mean[2] != 0");
+    HPS_REQUIRE(d.beam_charge != 0.0, fn + "the deck's beam_charge must not be 0");
+    HPS_REQUIRE(!(d.beam_do_salame && s->profile == 0 && (std::isinf(s->zmin) || std::isinf(s->zmax))),
+                fn + "a beam_do_salame deck needs the can profile, or zmin and zmax with the gaussian profile (BeamParticleContainer.cpp:149)");
+    int depth_x = 0, depth_y = 0;
+    if (int e = expr_check_named(name, "position_mean[0]: ", mean_x, 1, &depth_x)) return e;
+    if (int e = expr_check_named(name, "position_mean[1]: ", mean_y, 1, &depth_y)) return e;
+
+    BeamFixedWeight a{};
+    a.nd = nd; a.can = s->profile == 1; a.sym = s->do_symmetrize != 0; a.nz = d.nz;
+    a.lo_z = d.lo[2]; a.inv_dz = 1.0/gm.dz; a.pos_mean_z = s->pos_mean_z;
+    a.z_mean = a.can ? 0.5*(s->zmin + s->zmax) : s->pos_mean_z;      // (:419)
+    for (int q = 0; q < 3; ++q) { a.std[q] = s->pos_std[q]; a.u_mean[q] = s->u_mean[q]; a.u_std[q] = s->u_std[q]; }
+    a.zmin = s->zmin; a.zmax = s->zmax; a.radius_sq = s->radius*s->radius; a.z_foc = s->z_foc; a.duz = s->duz_per_uz0_dzeta; a.c = gm.c;
+    {   // BeamParticleContainer.cpp:179-190, BeamParticleContainerInit.cpp:425; tests/beam_fixed_weight_reference.weight follows this chain
+        double total_charge = s->total_charge;
+        if (!s->charge_is_specified) {
+            total_charge = s->density*d.beam_charge;
+            for (int q = 0; q < 3; ++q) total_charge *= s->pos_std[q]*std::sqrt(2.0*M_PI);
+        }
+        if (!d.si_units) total_charge *= (1.0/gm.dx)*(1.0/gm.dy)*(1.0/gm.dz);
+        a.weight = std::fabs(total_charge/((double)s->num_particles*d.beam_charge));
+    }
+    a.key_z = coll_hash(seed, BI_TAG_FW_Z); a.key_xy = coll_hash(seed, BI_TAG_FW_XY); a.key_mom = coll_hash(seed, BI_TAG_MOMENTUM);
+    a.n_ins_x = mean_x->n_ins; a.n_ins_y = mean_y->n_ins;
+    const int m = a.sym ? 4 : 1, nkeys = d.nz + 2;
+    int bits = 1; while ((1L << bits) < (long)nkeys) ++bits;
+
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    release_beam();
+    host_beam = true;
+    beam_off.assign(d.nz + 1, 0);
+    if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
+    double box[4] = {0.0, 0.0, 0.0, 0.0};
+    double* blocks = nullptr;
+    long n = 0;
+    hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; unsigned int* d_keys = nullptr; long *d_first = nullptr, *d_off = nullptr;
+    double* d_mm = nullptr;
+    auto release = [&] { (void)hipFree(d_ins); (void)hipFree(d_consts); (void)hipFree(d_keys); (void)hipFree(d_first); (void)hipFree(d_off);
+                         (void)hipFree(d_mm); };
+    auto run = [&] () -> int {
+        const size_t ni = (size_t)mean_x->n_ins + mean_y->n_ins, nc = (size_t)mean_x->n_const + mean_y->n_const;
+        HPS_HIP_CHECK(hipMalloc(&d_ins, ni*sizeof(hps_expr_ins)));
+        HPS_HIP_CHECK(hipMalloc(&d_consts, std::max<size_t>(nc, 1)*sizeof(double)));
+        HPS_HIP_CHECK(hipMemcpy(d_ins, mean_x->ins, (size_t)mean_x->n_ins*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
+        HPS_HIP_CHECK(hipMemcpy(d_ins + mean_x->n_ins, mean_y->ins, (size_t)mean_y->n_ins*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
+        if (mean_x->n_const > 0) HPS_HIP_CHECK(hipMemcpy(d_consts, mean_x->consts, (size_t)mean_x->n_const*sizeof(double), hipMemcpyHostToDevice));
+        if (mean_y->n_const > 0) HPS_HIP_CHECK(hipMemcpy(d_consts + mean_x->n_const, mean_y->consts, (size_t)mean_y->n_const*sizeof(double), hipMemcpyHostToDevice));
+        a.ins_x = d_ins; a.ins_y = d_ins + mean_x->n_ins; a.consts_x = d_consts; a.consts_y = d_consts + mean_x->n_const;
+        HPS_HIP_CHECK(hipMalloc(&d_keys, (size_t)4*nd*sizeof(unsigned int)));      // keys, indices; sorted keys, sorted indices
+        unsigned int *ka = d_keys, *ia = ka + nd, *kb = ia + nd, *ib = kb + nd;
+        HPS_HIP_CHECK(hipMalloc(&d_first, (size_t)(nkeys + 1)*sizeof(long)));
+        const dim3 block(BI_THREADS);
+        hipLaunchKernelGGL(k_fw_keys, dim3(ceil_div(nd, BI_THREADS)), block, 0, st, a, ka, ia);
+        HPS_HIP_CHECK(hipGetLastError());
+        if (int e = sort_pairs_u32(ka, kb, ia, ib, nd, bits, st)) return e;
+        hipLaunchKernelGGL(k_fw_starts, dim3(ceil_div(nd + 1, BI_THREADS)), block, 0, st, kb, nd, nkeys, d_first);
+        HPS_HIP_CHECK(hipGetLastError());
+        std::vector<long> first((size_t)nkeys + 1);
+        HPS_HIP_CHECK(hipMemcpyAsync(first.data(), d_first, first.size()*sizeof(long), hipMemcpyDeviceToHost, st));
+        HPS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int p = 0; p <= d.nz; ++p) beam_off[p] = m*first[(size_t)p];
+        if (n_left_out) { n_left_out[0] = m*(first[(size_t)d.nz + 1] - first[(size_t)d.nz]); n_left_out[1] = m*(nd - first[(size_t)d.nz + 1]); }
+        const long nkept = first[(size_t)d.nz];
+        n = m*nkept;
+        if (n == 0) return HPS_OK;
+        HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(d.nz + 1)*sizeof(long)));
+        HPS_HIP_CHECK(hipMalloc(&d_mm, (size_t)4*d.nz*sizeof(double)));
+        HPS_HIP_CHECK(hipMemcpyAsync(d_off, beam_off.data(), (size_t)(d.nz + 1)*sizeof(long), hipMemcpyHostToDevice, st));
+        HPS_HIP_CHECK(hipMalloc(&blocks, (size_t)7*n*sizeof(double)));
+        const size_t lds = (size_t)std::max(std::max(depth_x, depth_y) - 1, 0)*BI_THREADS*sizeof(double);
+        hipLaunchKernelGGL(k_fw_fill, dim3(ceil_div(nkept, BI_THREADS)), block, lds, st, a, kb, ib, d_first, nkept, blocks);
+        HPS_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_beam_extent, dim3(d.nz), block, 0, st, blocks, d_off, d_mm);
+        HPS_HIP_CHECK(hipGetLastError());
+        std::vector<double> mm((size_t)4*d.nz);
+        HPS_HIP_CHECK(hipMemcpyAsync(mm.data(), d_mm, mm.size()*sizeof(double), hipMemcpyDeviceToHost, st));
+        HPS_HIP_CHECK(hipStreamSynchronize(st));
+        box[0] = box[2] = inf; box[1] = box[3] = -inf;
+        for (int p = 0; p < d.nz; ++p) {
+            box[0] = std::min(box[0], mm[(size_t)4*p]);     box[1] = std::max(box[1], mm[(size_t)4*p + 1]);
+            box[2] = std::min(box[2], mm[(size_t)4*p + 2]); box[3] = std::max(box[3], mm[(size_t)4*p + 3]);
+        }
+        return HPS_OK;
+    };
+    const int e = run();
+    release();
+    if (e) {                                   // the engine is left without a beam
+        (void)hipFree(blocks); beam_off.assign(d.nz + 1, 0);
+        if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
+        (void)install_beam_device(nullptr, 0, box);
+        return e;
+    }
+    return install_beam_device(blocks, n, box);
+}
+
 } // namespace hps
+
+extern "C" int hps_engine_set_beam_fixed_weight (void* h, const hps_beam_fixed_weight* spec, const hps_expr* mean_x_of_z,
+                                                 const hps_expr* mean_y_of_z, unsigned long long seed, long n_left_out[2])
+{
+    HPS_REQUIRE(h, "hps_engine_set_beam_fixed_weight: null engine");
+    return static_cast<hps::Engine*>(h)->set_beam_fixed_weight(spec, mean_x_of_z, mean_y_of_z, seed, n_left_out);
+}
 
 extern "C" int hps_engine_set_beam_fixed_ppc (void* h, const hps_expr* density, double min_density, const double u_std[3], const int random_ppc[3],
                                               unsigned long long seed)

@@ -210,6 +210,11 @@ __device__ __forceinline__ void atomic_add_f64 (double* addr, double v)
 
 inline int ceil_div (long a, long b) { return (int)((a + b - 1)/b); }
 
+// sort.hip: stable radix sort of n < 2^32 (key, value) pairs of 32-bit words by the low `bits` bits of the keys, all four
+// arrays on the device; allocates and frees its own scratch, and returns with the stream drained
+int sort_pairs_u32 (const unsigned int* keys_in, unsigned int* keys_out, const unsigned int* vals_in, unsigned int* vals_out,
+                    long n, int bits, hipStream_t st);
+
 } // namespace hps
 
 

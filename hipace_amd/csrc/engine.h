@@ -261,6 +261,9 @@ struct Engine {
     // beam_init.hip: the general fixed_ppc beam, generated on the device; install_beam_device takes its blocks
     // (ownership too: they become beam_init) with beam_off filled in and box = {xlo, xhi, ylo, yhi} of the particles
     int set_beam_fixed_ppc (const hps_expr* density, double min_density, const double* u_std, const int* random_ppc, unsigned long long seed);
+    // ... and the fixed_weight beam (gaussian | can): num_particles draws sorted into the slices on the device
+    int set_beam_fixed_weight (const hps_beam_fixed_weight* spec, const hps_expr* mean_x, const hps_expr* mean_y, unsigned long long seed,
+                               long* n_left_out);
     int install_beam_device (double* blocks_dev, long n, const double box[4]);
     void release_beam ();                                               // the beam's device storage, ahead of another beam
     void set_beam_box (double xlo, double xhi, double ylo, double yhi);  // beam_box_init from the particles' extent

@@ -353,6 +353,20 @@ void k_box_counts (long n, int num_boxes, const unsigned int* idx, unsigned long
     if (p <= num_boxes) counts[p] = (p == num_boxes ? (unsigned long long)n : offsets[p + 1]) - offsets[p];
 }
 
+// the sort of the beam's box sort and of the fixed_weight generator (beam_init.hip): stable, so that equal keys keep their order
+int sort_pairs_u32 (const unsigned int* keys_in, unsigned int* keys_out, const unsigned int* vals_in, unsigned int* vals_out,
+                    long n, int bits, hipStream_t st)
+{
+    void* temp = nullptr; size_t tb = 0;
+    HPS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, bits, st));
+    HPS_HIP_CHECK(hipMalloc(&temp, std::max<size_t>(tb, 1)));
+    hipError_t e = rocprim::radix_sort_pairs(temp, tb, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, bits, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(temp);
+    HPS_HIP_CHECK(e);
+    return HPS_OK;
+}
+
 } // namespace hps
 
 using namespace hps;
@@ -371,24 +385,27 @@ extern "C" int hps_beam_sort_by_box (const double* z_dev, long n, double plo_z, 
         HPS_HIP_CHECK(hipMemsetAsync(offsets_dev, 0, nb1*sizeof(unsigned long long), st));
         return HPS_OK;
     }
-    unsigned int *ka = nullptr, *kb = nullptr, *ia = nullptr, *ib = nullptr; void* temp = nullptr; size_t tb = 0;
+    unsigned int *ka = nullptr, *kb = nullptr, *ia = nullptr, *ib = nullptr;
     int bits = 1; while ((1L << bits) < (long)nb1) ++bits;
     HPS_HIP_CHECK(hipMalloc(&ka, 4*(size_t)n*sizeof(unsigned int)));
     kb = ka + n; ia = kb + n; ib = ia + n;
-    HPS_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, tb, ka, kb, ia, ib, (size_t)n, 0, bits, st));
-    HPS_HIP_CHECK(hipMalloc(&temp, tb));
     const dim3 b256(256);
-    // the reference takes 1/dz from the geometry (InvCellSize)
-    hipLaunchKernelGGL(k_box_keys, dim3(ceil_div(n, 256)), b256, 0, st, z_dev, n, plo_z, 1.0/dz, num_boxes, ka, ia);
-    // stable: particles keep their order inside a box, which is what the reference's serial CPU build produces
-    HPS_HIP_CHECK(rocprim::radix_sort_pairs(temp, tb, ka, kb, ia, ib, (size_t)n, 0, bits, st));
-    const long span = std::max<long>(n + 1, (long)nb1);
-    hipLaunchKernelGGL(k_box_offsets, dim3(ceil_div(n + 1, 256)), b256, 0, st, kb, n, num_boxes, counts_dev, offsets_dev);
-    hipLaunchKernelGGL(k_box_counts, dim3(ceil_div(span, 256)), b256, 0, st, n, num_boxes, ib, counts_dev, offsets_dev, perm_dev);
-    HPS_HIP_CHECK(hipGetLastError());
-    HPS_HIP_CHECK(hipStreamSynchronize(st));        // the reference synchronises too (:66-69); frees the scratch
-    (void)hipFree(ka); (void)hipFree(temp);
-    return HPS_OK;
+    auto run = [&] () -> int {
+        // the reference takes 1/dz from the geometry (InvCellSize)
+        hipLaunchKernelGGL(k_box_keys, dim3(ceil_div(n, 256)), b256, 0, st, z_dev, n, plo_z, 1.0/dz, num_boxes, ka, ia);
+        HPS_HIP_CHECK(hipGetLastError());
+        // stable: particles keep their order inside a box, which is what the reference's serial CPU build produces
+        if (int e = sort_pairs_u32(ka, kb, ia, ib, n, bits, st)) return e;
+        const long span = std::max<long>(n + 1, (long)nb1);
+        hipLaunchKernelGGL(k_box_offsets, dim3(ceil_div(n + 1, 256)), b256, 0, st, kb, n, num_boxes, counts_dev, offsets_dev);
+        hipLaunchKernelGGL(k_box_counts, dim3(ceil_div(span, 256)), b256, 0, st, n, num_boxes, ib, counts_dev, offsets_dev, perm_dev);
+        HPS_HIP_CHECK(hipGetLastError());
+        HPS_HIP_CHECK(hipStreamSynchronize(st));        // the reference synchronises too (:66-69); frees the scratch
+        return HPS_OK;
+    };
+    const int e = run();
+    (void)hipFree(ka);
+    return e;
 }
 
 extern "C" int hps_tiling_create (int nx, int ny, int tile_size, long max_particles, void** handle)

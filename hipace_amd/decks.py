@@ -151,6 +151,54 @@ def beam_init(deck):
                 seed=int(deck.get("beam_seed", 1)))
 
 
+# The fixed_weight beam on the device: injection_type = fixed_weight, profile = gaussian | can (BeamParticleContainer.cpp:137-198;
+# InitBeamFixedWeight3D / InitBeamFixedWeightSlice, BeamParticleContainerInit.cpp:348-475).  A deck's optional entry
+# "beam_fixed_weight" is a dict of these keys -- the arguments of SliceEngine.set_beam_fixed_weight, which SliceEngine applies
+# through hps_engine_set_beam_fixed_weight in place of the beam of beam_profile; the deck itself gives the grid, the units,
+# beam_charge and beam_mass.  No deck function sets the entry, and it is no member of _DEFAULT, BEAM_INIT_DEFAULT or hps_deck.
+# position_mean = (X(z), Y(z), z mean): X and Y numbers or strings in the input file's syntax over z with `constants`
+# (my_constants); exactly one of density and total_charge (SI units only); u_mean, u_std in units of c.
+BEAM_FIXED_WEIGHT_DEFAULT = dict(num_particles=0, position_mean=(0.0, 0.0, 0.0), position_std=None, u_mean=(0.0, 0.0, 0.0),
+                                 u_std=(0.0, 0.0, 0.0), density=None, total_charge=None, profile="gaussian", zmin=-math.inf,
+                                 zmax=math.inf, radius=math.inf, do_symmetrize=False, z_foc=0.0, duz_per_uz0_dzeta=0.0, seed=1,
+                                 constants=None)
+
+
+def beam_fixed_weight(deck):
+    """The deck's entry beam_fixed_weight over BEAM_FIXED_WEIGHT_DEFAULT as the arguments of SliceEngine.set_beam_fixed_weight, or
+    None for a deck without the entry.  ValueError: unknown keys, or the entry beside beam_density_expr (two beams for one deck)."""
+    entry = deck.get("beam_fixed_weight")
+    if entry is None:
+        return None
+    unknown = set(entry) - set(BEAM_FIXED_WEIGHT_DEFAULT)
+    if unknown:
+        raise ValueError(f"beam_fixed_weight: unknown entries {sorted(unknown)}")
+    if deck.get("beam_density_expr") is not None:
+        raise ValueError("beam_fixed_weight and beam_density_expr: a deck has one beam, from fixed_weight or from fixed_ppc")
+    return dict(BEAM_FIXED_WEIGHT_DEFAULT, **entry)
+
+
+def with_fixed_weight_beam(deck, beam=None, **more):
+    """A copy of deck with the entry beam_fixed_weight, from the keyword names of fixed_weight_beam (num_particles, density,
+    total_charge, pos_mean, pos_std, u_mean, u_std, zmin, zmax, radius, seed, do_symmetrize, duz_per_uz0_dzeta): the (deck, beam)
+    pairs of gaussian_weight_SI(), radiation_reaction_SI(), ... pass as with_fixed_weight_beam(*gaussian_weight_SI()), and
+    single parameters as keywords, which win over the dict's.  The names of BEAM_FIXED_WEIGHT_DEFAULT pass as they are.
+    A mean that is a Python callable cannot run on the device: write it as a string over z."""
+    rename = dict(pos_mean="position_mean", pos_std="position_std")
+    entry = {}
+    for k, v in dict(beam or {}, **more).items():
+        k = rename.get(k, k)
+        if k not in BEAM_FIXED_WEIGHT_DEFAULT:
+            raise ValueError(f"with_fixed_weight_beam: unknown beam parameter {k!r}")
+        entry[k] = v
+    if any(callable(m) for m in entry.get("position_mean", ())):
+        raise ValueError("with_fixed_weight_beam: a position mean that is a Python callable cannot run on the device; "
+                         "write it as a string over z, such as '0.2*z'")
+    d = copy.deepcopy(deck)
+    d["beam_fixed_weight"] = entry
+    return d
+
+
 def read_density_table(path):
     """<plasma>.density_table_file: one `position expression` per line, the expression being the rest of the line
     (PlasmaParticleContainer.cpp:107-116); a line that does not start with a number, or has nothing behind it, is skipped.

@@ -971,6 +971,41 @@ int hps_adaptive_rho_max (void* handle, double z, double* out_host);
  * point is dropped for its density), a program hps_expr_check refuses for three variables (one that reads t). */
 int hps_engine_set_beam_fixed_ppc (void* handle, const hps_expr* density, double min_density, const double u_std[3],
                                    const int random_ppc[3], unsigned long long seed);
+/* Engine: the fixed_weight beam -- injection_type = fixed_weight, profile = gaussian | can (InitBeamFixedWeight3D /
+ * InitBeamFixedWeightSlice, particles/beam/BeamParticleContainerInit.cpp:348-475; the parameters of particles/beam/
+ * BeamParticleContainer.cpp:137-198; GetInitialMomentum, particles/profiles/GetInitialMomentum.H:36-48) -- generated
+ * on the device in place of the deck's beam; whichever beam setter is called last holds.  The struct holds the beam; the deck
+ * gives the grid, the units, beam_charge and beam_mass only.  num_particles = N; nd = N/4 draws with do_symmetrize, else N.
+ * Draw i < nd: z = pos_mean_z + pos_std[2] n_z (gaussian) or u (zmax - zmin) + zmin (can); x = pos_std[0] n_x, y = pos_std[1] n_y;
+ * u_d = u_mean[d] + u_std[d] m_d (u_mean[d] itself where u_std[d] = 0), then u_z += (z - z_mean) duz_per_uz0_dzeta u_mean[2] with
+ * z_mean = pos_mean_z (gaussian) or (zmin + zmax)/2 (can).  The draw is valid iff zmin <= z <= zmax and x^2 + y^2 <= radius^2;
+ * then x -= z_foc u_x/u_z, y -= z_foc u_y/u_z (not applied where z_foc = 0) and the particle is (X(z) + x, Y(z) + y, z, u c) with
+ * X = mean_x_of_z, Y = mean_y_of_z: programs over exactly one variable, z (position_mean[0], position_mean[1]).  With
+ * do_symmetrize a draw gives the four particles (X +- x, Y +- y, z, +-u_x, +-u_y, u_z) in the order (+,+), (-,+), (+,-), (-,-),
+ * next to each other.  Every particle has w = |total_charge/(N beam_charge)|; with charge_is_specified = 0, total_charge =
+ * density beam_charge prod_d(pos_std[d] sqrt(2 pi)) (for the can profile too), times 1/(dx dy dz) in normalised units.  Every
+ * deviate is a function of (seed, tag, i, component) -- tags and draws in DESIGN 8o -- never of the launch.  Valid draws are
+ * binned as hps_engine_set_beam_particles bins particles (slice = int((z - lo_z)(1/dz)), head slice first), ascending i inside a
+ * slice.  n_left_out (may be NULL) receives the particles left out: {of invalid draws, of valid draws outside the box in z}.
+ * A beam of zero particles is legal.  On an error past the checks the engine is left without a beam.  HPS_ERR_ARG, with the
+ * parameter in the message: a null handle, struct or program; a call after the first hps_engine_begin_step; num_particles <= 0,
+ * or not divisible by 4 with do_symmetrize, or 2^32 draws or more; a profile other than 0 and 1; a pos_std that is not positive and
+ * finite; a u_std that is negative or not finite; the can profile without finite zmin < zmax; total_charge (charge_is_specified)
+ * in normalised units; z_foc != 0 with u_mean[2] = 0; a mean program hps_expr_check refuses for one variable; a beam_do_salame
+ * deck with the gaussian profile and an infinite zmin or zmax (BeamParticleContainer.cpp:149-153). */
+typedef struct {
+    long num_particles;
+    int profile;            /* 0 gaussian, 1 can */
+    int do_symmetrize;
+    double pos_mean_z;
+    double pos_std[3], u_mean[3], u_std[3];
+    double zmin, zmax, radius;      /* +-infinity allowed */
+    double z_foc, duz_per_uz0_dzeta;
+    double density, total_charge;
+    int charge_is_specified;
+} hps_beam_fixed_weight;
+int hps_engine_set_beam_fixed_weight (void* handle, const hps_beam_fixed_weight* spec, const hps_expr* mean_x_of_z,
+                                      const hps_expr* mean_y_of_z, unsigned long long seed, long n_left_out[2]);
 
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);

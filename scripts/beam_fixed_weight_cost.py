@@ -1,0 +1,48 @@
+"""A fixed_weight beam of N particles into an engine that exists: the device generator, SliceEngine.set_beam_fixed_weight (DESIGN
+8o), against the host path, decks.fixed_weight_beam (numpy's generator) + SliceEngine.set_beam_particles (a serial host loop and
+an upload), with the same parameters -- the blow-out deck's Gaussian driver -- on 64^3 cells and on 1024^2 x 1024, N = 10^6 and
+10^7.  Host clock around the calls, ending in a device synchronise; median of 3, the two paths alternating in one session.
+(profiles/beam_fixed_weight.txt).  Usage: python scripts/beam_fixed_weight_cost.py [file to write the lines to]"""
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch                                                        # noqa: E402
+
+from hipace_amd import api, decks                                   # noqa: E402
+
+lines = []
+for n, nz in ((64, 64), (1024, 1024)):
+    deck = dict(decks.synthetic(n, nz, 2), beam_profile=-1)
+    eng = api.SliceEngine(deck, tile_size=16, sort_period=128)
+    mean, std, um = deck["beam_pos_mean"], deck["beam_pos_std"], deck["beam_umean"]
+    for N in (10 ** 6, 10 ** 7):
+        dev, host, gen, kept = [], [], [], {}
+        for rep in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            left = eng.set_beam_fixed_weight(N, mean, std, u_mean=um, u_std=(1.0, 1.0, 10.0), density=deck["beam_density"],
+                                             zmin=deck["beam_zmin"], zmax=deck["beam_zmax"], radius=deck["beam_radius"], seed=1)
+            eng.sync()
+            dev.append(time.perf_counter() - t0)
+            kept["device"] = (eng.beam_layout()[0], left)
+            t0 = time.perf_counter()
+            soa = decks.fixed_weight_beam(deck, N, deck["beam_density"], mean, std, u_mean=um, u_std=(1.0, 1.0, 10.0),
+                                          zmin=deck["beam_zmin"], zmax=deck["beam_zmax"], radius=deck["beam_radius"], seed=1)
+            gen.append(time.perf_counter() - t0)
+            out = eng.set_beam_particles(soa, allow_outside=True)
+            eng.sync()
+            host.append(time.perf_counter() - t0)
+            kept["host"] = (eng.beam_layout()[0], (N - soa.shape[1], out))
+        lines.append(f"{n} x {n} x {nz}, N = {N:>8d}: device {statistics.median(dev) * 1e3:9.2f} ms (min {min(dev) * 1e3:.2f}, max {max(dev) * 1e3:.2f}; "
+                     f"{kept['device'][0]} kept, left out {kept['device'][1]});  host {statistics.median(host) * 1e3:9.1f} ms, of it numpy's draws "
+                     f"{statistics.median(gen) * 1e3:.1f} ms ({kept['host'][0]} kept, left out {kept['host'][1]})")
+    del eng
+print("\n".join(lines))
+if len(sys.argv) > 1:      # a file to keep the lines in
+    with open(sys.argv[1], "w") as f:
+        f.write("\n".join(lines) + "\n")
