@@ -68,6 +68,11 @@ class BeamFixedWeight(C.Structure):     # hps_beam_fixed_weight
                 ("charge_is_specified", C.c_int)]
 
 
+class BeamFixedWeightPdf(C.Structure):  # hps_beam_fixed_weight_pdf
+    _fields_ = [("num_particles", C.c_long), ("do_symmetrize", C.c_int), ("pdf_ref_ratio", C.c_int), ("radius", C.c_double),
+                ("z_foc", C.c_double), ("density", C.c_double), ("total_charge", C.c_double), ("charge_is_specified", C.c_int)]
+
+
 class Deck(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3),
@@ -298,6 +303,8 @@ _SIGS = {
     "hps_engine_set_beam_fixed_ppc": (C.c_int, [C.c_void_p, C.POINTER(Expr), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_ulonglong]),
     "hps_engine_set_beam_fixed_weight": (C.c_int, [C.c_void_p, C.POINTER(BeamFixedWeight), C.POINTER(Expr), C.POINTER(Expr), C.c_ulonglong,
                                                    C.POINTER(C.c_long)]),
+    "hps_engine_set_beam_fixed_weight_pdf": (C.c_int, [C.c_void_p, C.POINTER(BeamFixedWeightPdf), C.POINTER(Expr), C.POINTER(Expr),
+                                                       C.c_ulonglong, C.POINTER(C.c_long), C.POINTER(C.c_double)]),
     "hps_adaptive_set_density_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Expr), C.c_void_p]),
     "hps_adaptive_rho_max": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
     "hps_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),

@@ -583,6 +583,10 @@ class SliceEngine:
         beam_fw = _decks.beam_fixed_weight(deck)
         if beam_fw is not None:
             self._dk.beam_profile = -1
+        # ... and the fixed_weight_pdf beam (beam_fixed_weight_pdf, decks.BEAM_FIXED_WEIGHT_PDF_DEFAULT)
+        beam_fwp = _decks.beam_fixed_weight_pdf(deck)
+        if beam_fwp is not None:
+            self._dk.beam_profile = -1
         self._h = C.c_void_p()
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
         if tile_size is not None:
@@ -636,6 +640,8 @@ class SliceEngine:
             self.set_beam_fixed_ppc(**beam)
         if beam_fw is not None:
             self.beam_left_out = self.set_beam_fixed_weight(**beam_fw)
+        if beam_fwp is not None:
+            self.beam_left_out = self.set_beam_fixed_weight_pdf(**beam_fwp)
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -1064,6 +1070,60 @@ class SliceEngine:
         out = (C.c_long * 2)(0, 0)
         check(_lib.lib().hps_engine_set_beam_fixed_weight(self._h, C.byref(spec), C.byref(cx), C.byref(cy), int(seed), out))
         self.beam_mean_programs = (progs[0], progs[1])
+        return out[0], out[1]
+
+    def set_beam_fixed_weight_pdf(self, num_particles, pdf, position_mean, position_std, u_mean=(0.0, 0.0, 0.0), u_std=(0.0, 0.0, 0.0),
+                                  density=None, total_charge=None, radius=np.inf, z_foc=0.0, do_symmetrize=False, pdf_ref_ratio=4,
+                                  seed=1, constants=None):
+        """The fixed_weight_pdf beam (injection_type = fixed_weight_pdf) in place of the deck's, generated on the device
+        (hps_engine_set_beam_fixed_weight_pdf): num_particles particles of one weight -- a quarter as many draws with
+        do_symmetrize -- with the longitudinal profile pdf(z), tabulated on nz pdf_ref_ratio sub-slices, x and y normal about
+        position_mean[0 | 1](z) with position_std[0 | 1](z), u normal about u_mean[d](z) with u_std[d](z), in units of c.  pdf and
+        the ten functions: numbers, strings in the input file's syntax over z (constants: my_constants) or Programs over ("z",).
+        Exactly one of density (the peak density) and total_charge (SI units only): numbers, or strings over the constants.
+        The deck gives the grid, the units, beam_charge and beam_mass.  Before the first begin_step; whichever beam setter is
+        called last holds.  beam_uz_moments keeps the pdf-weighted (mean, standard deviation) of u_z: the arguments of
+        adaptive_initial_dt.
+        -> (particles of invalid draws, particles of valid draws outside the box in z): both left out."""
+        name = "set_beam_fixed_weight_pdf"
+        if (density is None) == (total_charge is None):
+            raise ValueError(f"{name}: specify exclusively either total_charge or density of the beam")
+        if len(position_mean) != 2 or len(position_std) != 2 or len(u_mean) != 3 or len(u_std) != 3:
+            raise ValueError(f"{name}: position_mean and position_std have two entries each, u_mean and u_std three")
+
+        def function(what, f):
+            if isinstance(f, _expr.Program):
+                if tuple(f.variables) != ("z",):
+                    raise ValueError(f"{name}: {what} is a function of z alone")
+                return f
+            try:
+                return _expr.compile_expr(f, ("z",), constants)
+            except ValueError as e:
+                raise ValueError(f"{name}: {what} is a function of z alone ({e})") from None
+
+        def number(what, v):
+            if not isinstance(v, str):
+                return float(v)
+            try:
+                p = _expr.compile_expr(v, (), constants)
+            except ValueError as e:
+                raise ValueError(f"{name}: {what} is a number ({e})") from None
+            return float(p.evaluate())
+
+        prog_pdf = function("pdf", pdf)
+        progs = [function(f"{k}[{q}]", v) for k, vals in (("position_mean", position_mean), ("position_std", position_std),
+                                                          ("u_mean", u_mean), ("u_std", u_std)) for q, v in enumerate(vals)]
+        spec = _lib.BeamFixedWeightPdf(
+            num_particles=int(num_particles), do_symmetrize=int(bool(do_symmetrize)), pdf_ref_ratio=int(pdf_ref_ratio),
+            radius=number("radius", radius), z_foc=number("z_foc", z_foc), density=0.0 if density is None else number("density", density),
+            total_charge=0.0 if total_charge is None else number("total_charge", total_charge),
+            charge_is_specified=int(total_charge is not None))
+        cpdf, keep_pdf = prog_pdf.c_struct()
+        arr, keep = _expr.c_programs(progs)
+        out, mom = (C.c_long * 2)(0, 0), (C.c_double * 2)(0.0, 0.0)
+        check(_lib.lib().hps_engine_set_beam_fixed_weight_pdf(self._h, C.byref(spec), C.byref(cpdf), arr, int(seed), out, mom))
+        self.beam_pdf_programs = (prog_pdf, tuple(progs))
+        self.beam_uz_moments = (mom[0], mom[1])
         return out[0], out[1]
 
     def set_beam_storage(self, tensor, injected_beam_support=False):

@@ -13,7 +13,8 @@
 // Both walks compute the same points from the same numbers -- every random draw is a function of (seed, tag, the point's global
 // slot, component), never of a lane or of the packed index -- so the count and the fill agree, and the beam does not depend on
 // the launch.  No atomics.  The program's stack is the lane's column of the workgroup's dynamic LDS ([level][lane], expr.h).
-// Below it, the fixed_weight beam (gaussian and can profiles) by the same rule for its draws.
+// Below it, the fixed_weight beam (gaussian and can profiles) and the fixed_weight_pdf beam by the same
+// rule for their draws.
 #include "engine.h"
 #include "expr.h"
 
@@ -363,8 +364,9 @@ __device__ __forceinline__ FwDraw fw_draw (const BeamFixedWeight& a, unsigned lo
     return d;
 }
 
-// Engine::set_beam_particles' rule: slice from the head, -1 outside the box
-__device__ __forceinline__ int fw_slice (const BeamFixedWeight& a, double z)
+// Engine::set_beam_particles' rule: slice from the head, -1 outside the box (Args: BeamFixedWeight, BeamFwPdf)
+template <class Args>
+__device__ __forceinline__ int fw_slice (const Args& a, double z)
 {
 #pragma clang fp contract(off)
     const double t = (z - a.lo_z)*a.inv_dz;
@@ -563,7 +565,295 @@ int Engine::set_beam_fixed_weight (const hps_beam_fixed_weight* s, const hps_exp
     return install_beam_device(blocks, n, box);
 }
 
+// ---- the fixed_weight_pdf beam (InitBeamFixedWeightPDF3D / InitBeamFixedWeightPDFSlice, BeamParticleContainerInit.cpp:477-695;
+// DESIGN 8p) ----
+// The fixed_weight beam's scheme with a table-driven z draw and every mean and width a program over z:
+//     (host)         pe[s] = pdf(edge s), lw, integral, max_density, the u_z moments, cum[] -- once, in the reference's order
+//     k_fwp_keys     one lane per draw: s by binary search in cum, z, std_x(z), std_y(z), the rejection loop -> key, i
+//     (sort.hip), k_fw_starts                                              as above
+//     k_fwp_fill     one lane per kept position: the draw of i again, all ten programs at z, the particle or its four copies
+// cum and pe (at most 2 x 8193 doubles for 2048 slices of 4 sub-slices) are read through L2: every lane's search starts on the same
+// few lines, and an image in LDS would cost a workgroup of 256 draws 128 KiB of loads and the CU all but one workgroup.
+constexpr unsigned long long BI_TAG_FW_PDF_Z = 4;
+constexpr int FWP_MAX_ATTEMPTS = 4096;              // of the (x, y) pair of a total_charge beam inside the radius (:662-666)
+constexpr int FWP_MEAN_X = 0, FWP_MEAN_Y = 1, FWP_STD_X = 2, FWP_STD_Y = 3, FWP_U_MEAN = 4, FWP_U_STD = 7, FWP_NPROG = 10;
+
+struct BeamFwPdf {
+    long nd; int sym, nz, ns, last, retry;          // last: the last sub-slice with lw > 0; retry: total_charge was given
+    double lo_z, inv_dz, zs, radius_sq, z_foc, c, weight;
+    unsigned long long key_z, key_xy, key_mom;      // hash(seed, tag)
+    const double *cum, *pe;                         // [ns + 1] each
+    const hps_expr_ins* ins; const double* consts; int off[FWP_NPROG + 1];      // the ten programs in one image
+};
+
+struct FwpDraw { double z, x, y; int s, attempt; bool valid; };
+
+template <class Stack>
+__device__ __forceinline__ double fwp_prog (const BeamFwPdf& a, int k, const ExprZ& v, Stack& st)
+{
+    return expr_run(a.ins + a.off[k], a.off[k + 1] - a.off[k], a.consts, v, st);
+}
+
+// stage 1: sub-slice and z of draw i (:631-652); every operation rounds once
+__device__ __forceinline__ double fwp_draw_z (const BeamFwPdf& a, unsigned long long i, int& s)
+{
+#pragma clang fp contract(off)
+    const unsigned long long zk = coll_hash(a.key_z, i);
+    const double t = coll_unit(coll_hash(zk, 0ULL))*a.cum[a.ns];
+    int lo = 0, hi = a.last;                        // the last index with cum[.] <= t, at most `last` (cum[0] = 0 <= t)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.cum[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    s = lo;
+    const double w = coll_unit(coll_hash(zk, 1ULL));
+    const double lo_w = a.pe[lo], hi_w = a.pe[lo + 1];
+    const bool taylor = fmin(lo_w, hi_w)*1.1 > fmax(lo_w, hi_w);
+    double f;
+    if (taylor) {
+        const double inv = 1.0/(hi_w + lo_w);
+        f = w - w*(w - 1.0)*(hi_w - lo_w)*inv;
+    } else {
+        const double inv = 1.0/(hi_w - lo_w);
+        f = (sqrt(lo_w*lo_w + w*(hi_w*hi_w - lo_w*lo_w)) - lo_w)*inv;
+    }
+    return (a.lo_z + lo*a.zs) + a.zs*f;
+}
+
+// z, the widths at z, the transverse offsets and the validity of draw i (:654-666)
+template <class Stack>
+__device__ __forceinline__ FwpDraw fwp_draw (const BeamFwPdf& a, unsigned long long i, Stack& st)
+{
+#pragma clang fp contract(off)
+    FwpDraw d;
+    d.z = fwp_draw_z(a, i, d.s);
+    const ExprZ v{d.z};
+    const double sx = fwp_prog(a, FWP_STD_X, v, st), sy = fwp_prog(a, FWP_STD_Y, v, st);
+    const unsigned long long xk = coll_hash(a.key_xy, i);
+    const int cap = a.retry ? FWP_MAX_ATTEMPTS : 1;
+    d.valid = false; d.attempt = 0; d.x = 0.0; d.y = 0.0;
+    for (int k = 0; k < cap; ++k) {
+        double n0, n1;
+        normal_pair(xk, 2u*(unsigned)k, n0, n1);
+        d.x = sx*n0; d.y = sy*n1; d.attempt = k;
+        if (d.x*d.x + d.y*d.y <= a.radius_sq) { d.valid = true; break; }
+    }
+    return d;
+}
+
+__global__ __launch_bounds__(BI_THREADS)
+void k_fwp_keys (BeamFwPdf a, unsigned int* __restrict__ keys, unsigned int* __restrict__ idx)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_fwp_key_stack[];
+    const long i = (long)blockIdx.x*BI_THREADS + threadIdx.x;
+    const bool live = i < a.nd;
+    ExprLdsStack st{s_fwp_key_stack + threadIdx.x, BI_THREADS};
+    const FwpDraw d = fwp_draw(a, (unsigned long long)(live ? i : a.nd - 1), st);      // (every lane runs the programs: uniform opcodes)
+    if (!live) return;
+    const int p = fw_slice(a, d.z);
+    keys[i] = (unsigned int)(!d.valid ? a.nz : p < 0 ? a.nz + 1 : p);
+    idx[i] = (unsigned int)i;
+}
+
+// kept position o (sorted order, o < nkept = first[nz]) -> block keys[o] of `blocks`, as k_fw_fill
+__global__ __launch_bounds__(BI_THREADS)
+void k_fwp_fill (BeamFwPdf a, const unsigned int* __restrict__ keys, const unsigned int* __restrict__ perm,
+                 const long* __restrict__ first, long nkept, double* __restrict__ blocks)
+{
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) double s_fwp_stack[];
+    const long o = (long)blockIdx.x*BI_THREADS + threadIdx.x;
+    const bool live = o < nkept;
+    const long oo = live ? o : nkept - 1;             // (every lane runs the programs: uniform opcodes)
+    const unsigned long long i = perm[oo];
+    const int p = (int)keys[oo];
+    ExprLdsStack st{s_fwp_stack + threadIdx.x, BI_THREADS};
+    const FwpDraw d = fwp_draw(a, i, st);
+    const ExprZ v{d.z};
+    const double X = fwp_prog(a, FWP_MEAN_X, v, st), Y = fwp_prog(a, FWP_MEAN_Y, v, st);
+    double m[3], unused, u[3];
+    const unsigned long long zk = coll_hash(a.key_mom, i);      // the momentum deviates of the fixed_ppc beam
+    normal_pair(zk, 0u, m[0], m[1]);
+    normal_pair(zk, 2u, m[2], unused);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const double um = fwp_prog(a, FWP_U_MEAN + q, v, st), us = fwp_prog(a, FWP_U_STD + q, v, st);
+        u[q] = um + us*m[q];
+    }
+    double x = d.x, y = d.y;
+    if (a.z_foc != 0.0) { x = x - a.z_foc*u[0]/u[2]; y = y - a.z_foc*u[1]/u[2]; }      // (:673-674)
+    if (!live) return;
+    const int n = a.sym ? 4 : 1;
+    const long f = first[p], cnt = n*(first[p + 1] - f);
+    double* blk = blocks + 7*n*f + n*(o - f);
+    for (int q = 0; q < n; ++q) {                    // (+,+), (-,+), (+,-), (-,-) (:676-690)
+        const bool nx = (q & 1) != 0, ny = (q & 2) != 0;
+        blk[q] = nx ? X - x : X + x; blk[cnt + q] = ny ? Y - y : Y + y; blk[2*cnt + q] = d.z;
+        blk[3*cnt + q] = (nx ? -u[0] : u[0])*a.c; blk[4*cnt + q] = (ny ? -u[1] : u[1])*a.c; blk[5*cnt + q] = u[2]*a.c;
+        blk[6*cnt + q] = a.weight;
+    }
+}
+
+// hps_engine_set_beam_fixed_weight_pdf: everything is checked before anything of the engine changes
+int Engine::set_beam_fixed_weight_pdf (const hps_beam_fixed_weight_pdf* s, const hps_expr* pdf, const hps_expr* progs, unsigned long long seed,
+                                       long* n_left_out, double* uz_moments)
+{
+    static const char* const name = "hps_engine_set_beam_fixed_weight_pdf";
+    static const char* const prog_name[FWP_NPROG] = {"position_mean[0]: ", "position_mean[1]: ", "position_std[0]: ", "position_std[1]: ",
+                                                     "u_mean[0]: ", "u_mean[1]: ", "u_mean[2]: ", "u_std[0]: ", "u_std[1]: ", "u_std[2]: "};
+    const std::string fn = std::string(name) + ": ";
+    const double inf = std::numeric_limits<double>::infinity();
+    HPS_REQUIRE(s && pdf && progs, fn + "null argument");
+    HPS_REQUIRE(steps_begun == 0 && step_index < 0, fn + "call before the first hps_engine_begin_step");
+    HPS_REQUIRE(s->num_particles > 0, fn + "num_particles must be positive");
+    HPS_REQUIRE(!s->do_symmetrize || s->num_particles % 4 == 0, fn + "num_particles must be divisible by 4 with do_symmetrize");
+    const long nd = s->do_symmetrize ? s->num_particles/4 : s->num_particles;
+    HPS_REQUIRE(nd < (1L << 32), fn + "num_particles: 2^32 draws or more");
+    HPS_REQUIRE(s->pdf_ref_ratio >= 1, fn + "pdf_ref_ratio must be at least 1");
+    HPS_REQUIRE((long)d.nz*s->pdf_ref_ratio < (long)std::numeric_limits<int>::max(), fn + "pdf_ref_ratio: nz pdf_ref_ratio overflows an int");
+    int depth_pdf = 0, depth[FWP_NPROG] = {};
+    if (int e = expr_check_named(name, "pdf: ", pdf, 1, &depth_pdf)) return e;
+    for (int k = 0; k < FWP_NPROG; ++k)
+        if (int e = expr_check_named(name, prog_name[k], &progs[k], 1, &depth[k])) return e;
+    HPS_REQUIRE(!s->charge_is_specified || d.si_units, fn + "total_charge is only valid in SI units: give the density (BeamParticleContainer.cpp:242)");
+    HPS_REQUIRE(std::isfinite(s->charge_is_specified ? s->total_charge : s->density), fn + (s->charge_is_specified ? "total_charge" : "density") + " must be finite");
+    HPS_REQUIRE(d.beam_charge != 0.0, fn + "the deck's beam_charge must not be 0");
+    HPS_REQUIRE(s->radius > 0.0, fn + "radius must be positive");
+    HPS_REQUIRE(std::isfinite(s->z_foc), fn + "z_foc must be finite");
+
+    // the host part (:489-542), with the routine of hps_expr_eval_host
+    const int ns = d.nz*s->pdf_ref_ratio;
+    const double lo_z = d.lo[2], zs = gm.dz/s->pdf_ref_ratio;
+    auto value = [] (const hps_expr& p, double z) {
+        ExprHostStack hs;
+        const double* const vp[1] = {&z};
+        const ExprArrayVars v{vp, 0};
+        return expr_run(p.ins, p.n_ins, p.consts, v, hs);
+    };
+    std::vector<double> tab((size_t)2*(ns + 1));      // cum[ns + 1], pe[ns + 1]
+    double* const cum = tab.data(); double* const pe = cum + (ns + 1);
+    for (int q = 0; q <= ns; ++q) {
+        pe[q] = value(*pdf, lo_z + q*zs);
+        HPS_REQUIRE(std::isfinite(pe[q]) && pe[q] >= 0.0, fn + "pdf: PDF must be >= 0 everywhere (and finite), at z = " + std::to_string(lo_z + q*zs));
+    }
+    double integral = 0.0, max_density = 0.0, avg_uz = 0.0, avg_uz_sq = 0.0, weight = 0.0, uz_mean = 0.0, uz_std = 0.0;
+    int last = -1;
+    {
+#pragma clang fp contract(off)
+        for (int q = ns - 1; q >= 0; --q) {
+            const double zmin = lo_z + q*zs, zmax = lo_z + (q + 1)*zs, zmid = 0.5*(zmin + zmax);
+            const double lw = 0.5*(pe[q] + pe[q + 1]);
+            if (lw > 0.0) {
+                if (last < 0) last = q;
+                const double sx = value(progs[FWP_STD_X], zmid), sy = value(progs[FWP_STD_Y], zmid);
+                HPS_REQUIRE(std::isfinite(sx) && sx > 0.0 && std::isfinite(sy) && sy > 0.0,
+                            fn + "position_std must be positive and finite wherever the pdf is positive, at z = " + std::to_string(zmid));
+                if (!s->charge_is_specified) max_density = std::max(max_density, lw/(zs*sx*sy*2.0*M_PI));
+            }
+            const double um = value(progs[FWP_U_MEAN + 2], zmid), us = value(progs[FWP_U_STD + 2], zmid);
+            avg_uz += lw*um;
+            avg_uz_sq += lw*(um*um + us*us);
+            integral += lw;
+        }
+        HPS_REQUIRE(integral > 0.0 && std::isfinite(integral), fn + "pdf: the integral over the box must be positive and finite");
+        double total_weight = s->charge_is_specified ? s->total_charge/d.beam_charge : s->density*integral/max_density;
+        if (!d.si_units) total_weight *= (1.0/gm.dx)*(1.0/gm.dy)*(1.0/gm.dz);
+        weight = std::fabs(total_weight/(double)s->num_particles);
+        uz_mean = avg_uz/integral;
+        uz_std = std::sqrt(std::max(avg_uz_sq/integral - (avg_uz/integral)*(avg_uz/integral), 0.0));      // (a rounding below 0 is 0)
+        cum[0] = 0.0;
+        for (int q = 0; q < ns; ++q) cum[q + 1] = cum[q] + 0.5*(pe[q] + pe[q + 1]);
+    }
+    HPS_REQUIRE(std::isfinite(weight), fn + "the weight density integral / (max_density num_particles) is not finite");
+
+    BeamFwPdf a{};
+    a.nd = nd; a.sym = s->do_symmetrize != 0; a.nz = d.nz; a.ns = ns; a.last = last; a.retry = s->charge_is_specified != 0;
+    a.lo_z = lo_z; a.inv_dz = 1.0/gm.dz; a.zs = zs; a.radius_sq = s->radius*s->radius; a.z_foc = s->z_foc; a.c = gm.c; a.weight = weight;
+    a.key_z = coll_hash(seed, BI_TAG_FW_PDF_Z); a.key_xy = coll_hash(seed, BI_TAG_FW_XY); a.key_mom = coll_hash(seed, BI_TAG_MOMENTUM);
+    std::vector<hps_expr_ins> ins; std::vector<double> consts;
+    for (int k = 0; k < FWP_NPROG; ++k) a.off[k] = expr_append(progs[k], ins, consts);
+    a.off[FWP_NPROG] = (int)ins.size();
+    const int depth_keys = std::max(depth[FWP_STD_X], depth[FWP_STD_Y]), depth_fill = *std::max_element(depth, depth + FWP_NPROG);
+    const int m = a.sym ? 4 : 1, nkeys = d.nz + 2;
+    int bits = 1; while ((1L << bits) < (long)nkeys) ++bits;
+
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    release_beam();
+    host_beam = true;
+    beam_off.assign(d.nz + 1, 0);
+    if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
+    if (uz_moments) { uz_moments[0] = uz_mean; uz_moments[1] = uz_std; }
+    double box[4] = {0.0, 0.0, 0.0, 0.0};
+    double* blocks = nullptr;
+    long n = 0;
+    hps_expr_ins* d_ins = nullptr; double *d_consts = nullptr, *d_tab = nullptr, *d_mm = nullptr; unsigned int* d_keys = nullptr;
+    long *d_first = nullptr, *d_off = nullptr;
+    auto release = [&] { (void)hipFree(d_ins); (void)hipFree(d_consts); (void)hipFree(d_tab); (void)hipFree(d_keys); (void)hipFree(d_first);
+                         (void)hipFree(d_off); (void)hipFree(d_mm); };
+    auto run = [&] () -> int {
+        HPS_HIP_CHECK(hipMalloc(&d_ins, std::max<size_t>(ins.size(), 1)*sizeof(hps_expr_ins)));
+        HPS_HIP_CHECK(hipMalloc(&d_consts, std::max<size_t>(consts.size(), 1)*sizeof(double)));
+        HPS_HIP_CHECK(hipMalloc(&d_tab, tab.size()*sizeof(double)));
+        if (!ins.empty()) HPS_HIP_CHECK(hipMemcpy(d_ins, ins.data(), ins.size()*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
+        if (!consts.empty()) HPS_HIP_CHECK(hipMemcpy(d_consts, consts.data(), consts.size()*sizeof(double), hipMemcpyHostToDevice));
+        HPS_HIP_CHECK(hipMemcpy(d_tab, tab.data(), tab.size()*sizeof(double), hipMemcpyHostToDevice));
+        a.ins = d_ins; a.consts = d_consts; a.cum = d_tab; a.pe = d_tab + (ns + 1);
+        HPS_HIP_CHECK(hipMalloc(&d_keys, (size_t)4*nd*sizeof(unsigned int)));      // keys, indices; sorted keys, sorted indices
+        unsigned int *ka = d_keys, *ia = ka + nd, *kb = ia + nd, *ib = kb + nd;
+        HPS_HIP_CHECK(hipMalloc(&d_first, (size_t)(nkeys + 1)*sizeof(long)));
+        const dim3 block(BI_THREADS);
+        const size_t lds_keys = (size_t)std::max(depth_keys - 1, 0)*BI_THREADS*sizeof(double);
+        hipLaunchKernelGGL(k_fwp_keys, dim3(ceil_div(nd, BI_THREADS)), block, lds_keys, st, a, ka, ia);
+        HPS_HIP_CHECK(hipGetLastError());
+        if (int e = sort_pairs_u32(ka, kb, ia, ib, nd, bits, st)) return e;
+        hipLaunchKernelGGL(k_fw_starts, dim3(ceil_div(nd + 1, BI_THREADS)), block, 0, st, kb, nd, nkeys, d_first);
+        HPS_HIP_CHECK(hipGetLastError());
+        std::vector<long> first((size_t)nkeys + 1);
+        HPS_HIP_CHECK(hipMemcpyAsync(first.data(), d_first, first.size()*sizeof(long), hipMemcpyDeviceToHost, st));
+        HPS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int p = 0; p <= d.nz; ++p) beam_off[p] = m*first[(size_t)p];
+        if (n_left_out) { n_left_out[0] = m*(first[(size_t)d.nz + 1] - first[(size_t)d.nz]); n_left_out[1] = m*(nd - first[(size_t)d.nz + 1]); }
+        const long nkept = first[(size_t)d.nz];
+        n = m*nkept;
+        if (n == 0) return HPS_OK;
+        HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(d.nz + 1)*sizeof(long)));
+        HPS_HIP_CHECK(hipMalloc(&d_mm, (size_t)4*d.nz*sizeof(double)));
+        HPS_HIP_CHECK(hipMemcpyAsync(d_off, beam_off.data(), (size_t)(d.nz + 1)*sizeof(long), hipMemcpyHostToDevice, st));
+        HPS_HIP_CHECK(hipMalloc(&blocks, (size_t)7*n*sizeof(double)));
+        const size_t lds = (size_t)std::max(depth_fill - 1, 0)*BI_THREADS*sizeof(double);
+        hipLaunchKernelGGL(k_fwp_fill, dim3(ceil_div(nkept, BI_THREADS)), block, lds, st, a, kb, ib, d_first, nkept, blocks);
+        HPS_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_beam_extent, dim3(d.nz), block, 0, st, blocks, d_off, d_mm);
+        HPS_HIP_CHECK(hipGetLastError());
+        std::vector<double> mm((size_t)4*d.nz);
+        HPS_HIP_CHECK(hipMemcpyAsync(mm.data(), d_mm, mm.size()*sizeof(double), hipMemcpyDeviceToHost, st));
+        HPS_HIP_CHECK(hipStreamSynchronize(st));
+        box[0] = box[2] = inf; box[1] = box[3] = -inf;
+        for (int p = 0; p < d.nz; ++p) {
+            box[0] = std::min(box[0], mm[(size_t)4*p]);     box[1] = std::max(box[1], mm[(size_t)4*p + 1]);
+            box[2] = std::min(box[2], mm[(size_t)4*p + 2]); box[3] = std::max(box[3], mm[(size_t)4*p + 3]);
+        }
+        return HPS_OK;
+    };
+    const int e = run();
+    release();
+    if (e) {                                   // the engine is left without a beam
+        (void)hipFree(blocks); beam_off.assign(d.nz + 1, 0);
+        if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
+        (void)install_beam_device(nullptr, 0, box);
+        return e;
+    }
+    return install_beam_device(blocks, n, box);
+}
+
 } // namespace hps
+
+extern "C" int hps_engine_set_beam_fixed_weight_pdf (void* h, const hps_beam_fixed_weight_pdf* spec, const hps_expr* pdf, const hps_expr progs[10],
+                                                     unsigned long long seed, long n_left_out[2], double uz_moments[2])
+{
+    HPS_REQUIRE(h, "hps_engine_set_beam_fixed_weight_pdf: null engine");
+    return static_cast<hps::Engine*>(h)->set_beam_fixed_weight_pdf(spec, pdf, progs, seed, n_left_out, uz_moments);
+}
 
 extern "C" int hps_engine_set_beam_fixed_weight (void* h, const hps_beam_fixed_weight* spec, const hps_expr* mean_x_of_z,
                                                  const hps_expr* mean_y_of_z, unsigned long long seed, long n_left_out[2])

@@ -264,6 +264,9 @@ struct Engine {
     // ... and the fixed_weight beam (gaussian | can): num_particles draws sorted into the slices on the device
     int set_beam_fixed_weight (const hps_beam_fixed_weight* spec, const hps_expr* mean_x, const hps_expr* mean_y, unsigned long long seed,
                                long* n_left_out);
+    // ... and the fixed_weight_pdf beam: z from the table of pdf(z), means and widths as programs over z
+    int set_beam_fixed_weight_pdf (const hps_beam_fixed_weight_pdf* spec, const hps_expr* pdf, const hps_expr* progs, unsigned long long seed,
+                                   long* n_left_out, double* uz_moments);
     int install_beam_device (double* blocks_dev, long n, const double box[4]);
     void release_beam ();                                               // the beam's device storage, ahead of another beam
     void set_beam_box (double xlo, double xhi, double ylo, double yhi);  // beam_box_init from the particles' extent

@@ -199,6 +199,55 @@ def with_fixed_weight_beam(deck, beam=None, **more):
     return d
 
 
+# The fixed_weight_pdf beam on the device: injection_type = fixed_weight_pdf (BeamParticleContainer.cpp:200-240;
+# InitBeamFixedWeightPDF3D / InitBeamFixedWeightPDFSlice, BeamParticleContainerInit.cpp:477-695).  A deck's optional
+# entry "beam_fixed_weight_pdf" is a dict of these keys -- the arguments of SliceEngine.set_beam_fixed_weight_pdf, which
+# SliceEngine applies through hps_engine_set_beam_fixed_weight_pdf in place of the beam of beam_profile; the deck itself gives the
+# grid, the units, beam_charge and beam_mass.  No deck function sets the entry, and it is no member of _DEFAULT,
+# BEAM_INIT_DEFAULT, BEAM_FIXED_WEIGHT_DEFAULT or hps_deck.  pdf, position_mean (2), position_std (2), u_mean (3), u_std (3):
+# numbers or strings in the input file's syntax over z with `constants` (my_constants); exactly one of density (the peak
+# density) and total_charge (SI units only); u_mean, u_std in units of c.
+BEAM_FIXED_WEIGHT_PDF_DEFAULT = dict(num_particles=0, pdf=None, position_mean=(0.0, 0.0), position_std=None, u_mean=(0.0, 0.0, 0.0),
+                                     u_std=(0.0, 0.0, 0.0), density=None, total_charge=None, radius=math.inf, z_foc=0.0,
+                                     do_symmetrize=False, pdf_ref_ratio=4, seed=1, constants=None)
+
+
+def beam_fixed_weight_pdf(deck):
+    """The deck's entry beam_fixed_weight_pdf over BEAM_FIXED_WEIGHT_PDF_DEFAULT as the arguments of
+    SliceEngine.set_beam_fixed_weight_pdf, or None for a deck without the entry.  ValueError: unknown keys, or the entry beside
+    beam_fixed_weight or beam_density_expr (two beams for one deck)."""
+    entry = deck.get("beam_fixed_weight_pdf")
+    if entry is None:
+        return None
+    unknown = set(entry) - set(BEAM_FIXED_WEIGHT_PDF_DEFAULT)
+    if unknown:
+        raise ValueError(f"beam_fixed_weight_pdf: unknown entries {sorted(unknown)}")
+    for other in ("beam_fixed_weight", "beam_density_expr"):
+        if deck.get(other) is not None:
+            raise ValueError(f"beam_fixed_weight_pdf and {other}: a deck has one beam")
+    return dict(BEAM_FIXED_WEIGHT_PDF_DEFAULT, **entry)
+
+
+def with_fixed_weight_pdf_beam(deck, **beam):
+    """A copy of deck with the entry beam_fixed_weight_pdf from the names of BEAM_FIXED_WEIGHT_PDF_DEFAULT; pos_mean and pos_std,
+    the names of fixed_weight_pdf_beam, pass too.  A function that is a Python callable cannot run on the device: write it as
+    a string over z."""
+    rename = dict(pos_mean="position_mean", pos_std="position_std")
+    entry = {}
+    for k, v in beam.items():
+        k = rename.get(k, k)
+        if k not in BEAM_FIXED_WEIGHT_PDF_DEFAULT:
+            raise ValueError(f"with_fixed_weight_pdf_beam: unknown beam parameter {k!r}")
+        entry[k] = v
+    funcs = [entry.get("pdf")] + [m for k in ("position_mean", "position_std", "u_mean", "u_std") for m in entry.get(k) or ()]
+    if any(callable(f) for f in funcs):
+        raise ValueError("with_fixed_weight_pdf_beam: a Python callable cannot run on the device; write it as a string over z, "
+                         "such as 'exp(-0.5*(z/1.41)^2)'")
+    d = copy.deepcopy(deck)
+    d["beam_fixed_weight_pdf"] = entry
+    return d
+
+
 def read_density_table(path):
     """<plasma>.density_table_file: one `position expression` per line, the expression being the rest of the line
     (PlasmaParticleContainer.cpp:107-116); a line that does not start with a number, or has nothing behind it, is skipped.
@@ -833,6 +882,28 @@ def TRANSVERSE_BENCHMARK_BEAM(nxy=1023):
     import numpy as np
     return dict(num_particles=nxy * nxy * 10, density=2.0, pdf=lambda z: np.exp(-0.5 * (z / 1.41) ** 2), pos_std=(0.3, 0.3),
                 u_mean=(0.0, 0.0, 2000.0))
+
+
+def TRANSVERSE_BENCHMARK_BEAM_PARSED(nxy=1023):
+    """The same driver as the file writes it, for the device: with_fixed_weight_pdf_beam(transverse_benchmark(nxy),
+    **TRANSVERSE_BENCHMARK_BEAM_PARSED(nxy)) or SliceEngine.set_beam_fixed_weight_pdf(**...)."""
+    return dict(num_particles=nxy * nxy * 10, density=2.0, pdf="exp(-0.5*(z/1.41)^2)", position_mean=(0.0, 0.0), position_std=(0.3, 0.3),
+                u_mean=(0.0, 0.0, 2000.0), u_std=(0.0, 0.0, 0.0))
+
+
+def timestep_benchmark_beam(num_particles=268_000_000_000):
+    """examples/benchmarks/inputs_timestep_benchmark's proton driver (normalised units, beam1.element = proton: the deck's
+    beam_charge and beam_mass) as the arguments of SliceEngine.set_beam_fixed_weight_pdf: the Gaussian current profile cut at
+    4 sigma_z by two comparisons, widths and momentum spreads from my_constants.  The file's 268e9 particles are more draws than
+    one engine takes (2^32): a run gives its own num_particles.  The file's box in z ends where the window does, at
+    -+4 sigma_z kp, so both end edges carry no weight."""
+    constants = dict(n0=9.38e20, wp="sqrt( n0 * q_e^2 / (m_e *epsilon0) )", kp="wp/clight",
+                     nb="43e-9 /q_e / ( (2*pi)^(3/2) *sigma_x * sigma_y * sigma_z * n0 )", sigma_x=0.45e-3, sigma_y=0.54e-3,
+                     sigma_z=0.049, emittance=2.5e-6)
+    return dict(num_particles=int(num_particles), density="nb",
+                pdf="exp(-0.5*(z/(sigma_z*kp))^2)*(z > -4*sigma_z*kp)*(z < 4*sigma_z*kp)", position_mean=(0.0, 0.0),
+                position_std=("sigma_x*kp", "sigma_y*kp"), u_mean=(0.0, 0.0, "400/0.938+1"),
+                u_std=("emittance/sigma_x", "emittance/sigma_y", 0.003499), constants=constants)
 
 
 def fixed_weight_pdf_beam(deck, num_particles, density, pdf, pos_mean=(0.0, 0.0), pos_std=(1.0, 1.0), u_mean=(0.0, 0.0, 0.0),

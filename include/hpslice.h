@@ -1006,6 +1006,44 @@ typedef struct {
 } hps_beam_fixed_weight;
 int hps_engine_set_beam_fixed_weight (void* handle, const hps_beam_fixed_weight* spec, const hps_expr* mean_x_of_z,
                                       const hps_expr* mean_y_of_z, unsigned long long seed, long n_left_out[2]);
+/* Engine: the fixed_weight_pdf beam -- injection_type = fixed_weight_pdf (InitBeamFixedWeightPDF3D / InitBeamFixedWeightPDFSlice,
+ * particles/beam/BeamParticleContainerInit.cpp:477-695; the parameters of particles/beam/BeamParticleContainer.cpp:200-240;
+ * DESIGN 8p) -- generated on the device in place of the deck's beam; whichever beam setter is called last holds.  The deck gives
+ * the grid, the units, beam_charge and beam_mass only.  pdf is the longitudinal profile pdf(z); progs[10] are, in this order,
+ * position_mean x, position_mean y, position_std x, position_std y, u_mean x y z, u_std x y z: eleven programs over exactly one
+ * variable, z; a number is a constant program.  Once, on the host, with the routine of hps_expr_eval_host and in the reference's
+ * order: ns = nz pdf_ref_ratio sub-slices of width zs = dz/pdf_ref_ratio, pe[s] = pdf(lo_z + s zs) for s = 0 .. ns,
+ * lw[s] = 0.5 (pe[s] + pe[s + 1]); integral = sum of lw and max_density = max of lw[s]/(zs std_x std_y 2 pi) at the sub-slice's
+ * mid-point, both from s = ns - 1 down; total_weight = density integral/max_density, or total_charge/beam_charge with
+ * charge_is_specified, times 1/(dx dy dz) in normalised units; every particle has w = |total_weight/N|.  uz_moments (may be NULL)
+ * receives the pdf-weighted mean and standard deviation of u_z (:520-538), the pair hps_adaptive_initial_dt takes.  The table
+ * cum[0] = 0, cum[s + 1] = cum[s] + lw[s].  num_particles = N; nd = N/4 draws with do_symmetrize, else N.  Draw i < nd:
+ * t = unit(0) cum[ns]; s = the last index with cum[s] <= t; w = unit(1); z = (lo_z + s zs) + zs f with the reference's f
+ * (:631-652): w - w (w - 1)(hi - lo)/(hi + lo) where min(lo, hi) 1.1 > max(lo, hi), (sqrt(lo^2 + w (hi^2 - lo^2)) - lo)/(hi - lo)
+ * otherwise, lo = pe[s], hi = pe[s + 1]; x = std_x(z) n_x, y = std_y(z) n_y; with density the draw is invalid where x^2 + y^2 >
+ * radius^2, with total_charge further pairs are drawn until one is valid (:662-666; at most 4096, then invalid); u_d =
+ * u_mean_d(z) + u_std_d(z) m_d; x -= z_foc u_x/u_z, y -= z_foc u_y/u_z (not applied where z_foc = 0); the particle is
+ * (X(z) + x, Y(z) + y, z, u c), with do_symmetrize its four copies as hps_engine_set_beam_fixed_weight places them.  The counts per
+ * sub-slice are multinomial, where the reference iterates Poisson draws (:546-579): the beam is the reference's in distribution.
+ * Every deviate is a function of (seed, tag, i, component) -- DESIGN 8p.  Binning, order and n_left_out (may be NULL) as
+ * hps_engine_set_beam_fixed_weight.  On an error past the checks the engine is left without a beam.  HPS_ERR_ARG, with the
+ * parameter in the message and nothing of the engine changed: a null argument; a call after the first hps_engine_begin_step;
+ * num_particles <= 0, or not divisible by 4 with do_symmetrize, or 2^32 draws or more; pdf_ref_ratio < 1, or nz pdf_ref_ratio
+ * beyond an int; a program hps_expr_check refuses for one variable; a pdf that is negative or not finite at an edge; integral
+ * <= 0; a position_std that is not positive and finite at the mid-point of a sub-slice of positive weight; total_charge in
+ * normalised units; a radius that is not positive (infinity allowed); a z_foc that is not finite. */
+typedef struct {
+    long num_particles;
+    int do_symmetrize;
+    int pdf_ref_ratio;      /* the reference's default: 4 */
+    double radius;          /* +infinity allowed */
+    double z_foc;
+    double density, total_charge;
+    int charge_is_specified;
+} hps_beam_fixed_weight_pdf;
+int hps_engine_set_beam_fixed_weight_pdf (void* handle, const hps_beam_fixed_weight_pdf* spec, const hps_expr* pdf,
+                                          const hps_expr progs[10], unsigned long long seed, long n_left_out[2],
+                                          double uz_moments[2]);
 
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);
