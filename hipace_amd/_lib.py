@@ -286,6 +286,8 @@ _SIGS = {
     "hps_salame_sxsy_from_jz": (C.c_int, [Slab, Geom, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hps_salame_get_w": (C.c_int, [Slab, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hps_salame_scale_beam_slice": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p]),
+    "hps_open_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint,
+                                    C.c_void_p]),
     "hps_collide_plasma": (C.c_int, [Plasma, C.c_void_p, Plasma, C.c_void_p, Geom, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
                                      C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_ulonglong, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(C.c_long), C.POINTER(C.c_long), C.c_void_p]),

@@ -323,6 +323,19 @@ class LaserInterp:
         return out
 
 
+def open_boundary(planes, lo, hi, no_monopole_mask=0):
+    """boundary.field = Open on source planes of the caller's (hps_open_boundary, the engine's own two kernels): planes is a
+    CUDA float64 tensor (nbatch, ny, nx) on the box lo .. hi (x, y), updated in place -- the outermost rows and columns get the
+    Dirichlet corrections of the sources' free-space potential; bit b of no_monopole_mask drops the monopole of plane b."""
+    if not (isinstance(planes, torch.Tensor) and planes.is_cuda and planes.dtype == torch.float64 and planes.dim() == 3
+            and planes.is_contiguous()):
+        raise ValueError("open_boundary: planes must be a contiguous CUDA float64 tensor (nbatch, ny, nx)")
+    nbatch, ny, nx = planes.shape
+    check(_lib.lib().hps_open_boundary(C.c_void_p(planes.data_ptr()), nbatch, nx, ny, (C.c_double * 2)(lo[0], lo[1]),
+                                       (C.c_double * 2)(hi[0], hi[1]), int(no_monopole_mask), _stream()))
+    return planes
+
+
 class FFTPoissonSolver:
     """Lap(F) = S, F = 0 one cell outside the box; S lives in the staging area."""
 

@@ -1592,18 +1592,32 @@ void k_open_boundary_apply (double* staging, long nval, int nx, int ny, double d
     atomic_add_f64(staging + (long)b*nval + target, -(pref*v)/hh);
 }
 
+constexpr size_t OPEN_MOM_DOUBLES = (size_t)4*OPEN_PARTS*2*(OPEN_ORDER + 1);      // mom: [source][OPEN_PARTS][2 (OPEN_ORDER + 1)]
+
+// The two launches on nbatch (1..4) contiguous planes [ny][nx] of the box lo .. hi (x, y), with the geometry derived as
+// Engine::create derives gm (GetPosOffset); bit b of no_monopole_mask drops M_0 of plane b.  mom: OPEN_MOM_DOUBLES doubles on
+// the device.  The engine's path and hps_open_boundary's.
+static void open_boundary_planes (double* planes, int nbatch, int nx, int ny, const double* lo, const double* hi,
+                                  unsigned no_monopole_mask, double* mom, hipStream_t st)
+{
+    const long nval = (long)nx*ny;
+    const double dx = (hi[0] - lo[0])/nx, dy = (hi[1] - lo[1])/ny;
+    const double xoff = 0.5*(lo[0] + hi[0] - dx*(nx - 1));
+    const double yoff = 0.5*(lo[1] + hi[1] - dy*(ny - 1));
+    const double Lx = hi[0] - lo[0], Ly = hi[1] - lo[1];
+    const double scale = 3.0/std::sqrt(Lx*Lx + Ly*Ly);
+    const double radius = std::min(std::min(std::fabs(lo[0]), std::fabs(hi[0])), std::min(std::fabs(lo[1]), std::fabs(hi[1])));
+    const double cutoff_sq = (0.95*radius*scale)*(0.95*radius*scale);
+    hipLaunchKernelGGL(k_multipole_moments, dim3(OPEN_PARTS, nbatch), dim3(256), 0, st, planes, nval, nx, dx, dy, xoff, yoff,
+                       scale, cutoff_sq, mom);
+    hipLaunchKernelGGL(k_open_boundary_apply, dim3(ceil_div(2*nx + 2*ny, 256), nbatch), dim3(256), 0, st, planes, nval, nx, ny,
+                       dx, dy, xoff, yoff, scale, dx*dy/(4.0*3.14159265358979323846), mom, OPEN_PARTS, no_monopole_mask);
+}
+
 int Engine::open_boundary (int nbatch, unsigned no_monopole_mask)
 {
     if (d.field_bc != 1) return HPS_OK;
-    const long nval = (long)d.nx*d.ny;
-    const double Lx = d.hi[0] - d.lo[0], Ly = d.hi[1] - d.lo[1];
-    const double scale = 3.0/std::sqrt(Lx*Lx + Ly*Ly);
-    const double radius = std::min(std::min(std::fabs(d.lo[0]), std::fabs(d.hi[0])), std::min(std::fabs(d.lo[1]), std::fabs(d.hi[1])));
-    const double cutoff_sq = (0.95*radius*scale)*(0.95*radius*scale);
-    hipLaunchKernelGGL(k_multipole_moments, dim3(OPEN_PARTS, nbatch), dim3(256), 0, st, staging, nval, d.nx, gm.dx, gm.dy, gm.xoff, gm.yoff,
-                       scale, cutoff_sq, d_open_mom);
-    hipLaunchKernelGGL(k_open_boundary_apply, dim3(ceil_div(2*d.nx + 2*d.ny, 256), nbatch), dim3(256), 0, st, staging, nval, d.nx, d.ny,
-                       gm.dx, gm.dy, gm.xoff, gm.yoff, scale, gm.dx*gm.dy/(4.0*3.14159265358979323846), d_open_mom, OPEN_PARTS, no_monopole_mask);
+    open_boundary_planes(staging, nbatch, d.nx, d.ny, d.lo, d.hi, no_monopole_mask, d_open_mom, st);
     return HPS_OK;
 }
 
@@ -2874,6 +2888,24 @@ extern "C" int hps_engine_salame_stats (void* h, double* out)
     HPS_REQUIRE(E->c_sal >= 0, "hps_engine_salame_stats: the deck has no beam_do_salame");
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     std::memcpy(out, E->sal_stats.data(), E->sal_stats.size()*sizeof(double));
+    return HPS_OK;
+}
+extern "C" int hps_open_boundary (double* staging_dev, int nbatch, int nx, int ny, const double lo[2], const double hi[2],
+                                  unsigned no_monopole_mask, void* stream)
+{
+    HPS_REQUIRE(staging_dev && lo && hi, "hps_open_boundary: null argument");
+    HPS_REQUIRE(nbatch >= 1 && nbatch <= 4, "hps_open_boundary: nbatch must be 1..4");
+    HPS_REQUIRE(nx >= 2 && ny >= 2, "hps_open_boundary: nx and ny must be at least 2");
+    HPS_REQUIRE(hi[0] > lo[0] && hi[1] > lo[1], "hps_open_boundary: the box needs hi > lo in x and y");
+    HPS_REQUIRE(lo[0] < 0.0 && hi[0] > 0.0 && lo[1] < 0.0 && hi[1] > 0.0, "hps_open_boundary: boundary.field = Open needs x = y = 0 inside the box");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* mom = nullptr;
+    HPS_HIP_CHECK(hipMalloc(&mom, OPEN_MOM_DOUBLES*sizeof(double)));
+    open_boundary_planes(staging_dev, nbatch, nx, ny, lo, hi, no_monopole_mask, mom, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(mom);
+    HPS_HIP_CHECK(e);
     return HPS_OK;
 }
 extern "C" int hps_engine_assume_initial_beam_support (void* h)

@@ -683,6 +683,18 @@ int hps_stream_pool_shared_pairs (int device);
 int hps_engine_wait_event (void* handle, void* event);
 int hps_engine_copy_async (void* handle, void* dst_dev, const void* src_dev, long bytes);
 
+/* ---- boundary.field = Open as an operator (Fields::SetBoundaryCondition, fields/Fields.cpp:678-735) -----------------------
+ * What the engine runs ahead of every Poisson solve of an open-wall deck, on planes of the caller's: staging_dev holds
+ * nbatch (1..4) contiguous source planes [ny][nx] on the box lo .. hi (x, y), cell centres at i dx + GetPosOffset.  Per
+ * plane: the 19 complex multipole moments M_n = sum s z'^n (coordinates scaled by 3/|diagonal|) of the cells within 95 % of
+ * the distance from x = y = 0 to the nearest wall, then -dx dy/(4 pi) [M_0 ln|z|^2 - sum_n (2/n) Re(M_n z^-n)] / h^2 added
+ * to the outermost rows (h = dy) and columns (h = dx), z one cell outside the box; corners get both.  Bit b of
+ * no_monopole_mask drops M_0 of plane b (Ez, Bz).  Every other cell is left as it is.  Deterministic (fixed order of
+ * summation).  The moment scratch is allocated and freed per call; synchronises the stream.  HPS_ERR_ARG for a null
+ * pointer, nbatch outside 1..4, nx or ny < 2, hi <= lo, or x = y = 0 not strictly inside the box. */
+int hps_open_boundary (double* staging_dev, int nbatch, int nx, int ny, const double lo[2], const double hi[2],
+                       unsigned no_monopole_mask, void* stream);
+
 /* ---- SALAME (salame/Salame.cpp): the engine's module and its operators ------------------------------------------------
  * Per slice of step 0 on which the module ran: out_host[4*islice + {0, 1, 2, 3}] = the last weight factor W, W_total =
  * W * sum(jz) of that iteration (SalameGetW), the iterations used, and flags (bit 0: converged, bit 1: overloaded), the

@@ -1,0 +1,253 @@
+"""boundary.field = Open restated in numpy (Fields::SetBoundaryCondition + SetDirichletBoundaries, fields/Fields.cpp:617-741):
+what k_multipole_moments + k_open_boundary_apply (hipace_amd/csrc/engine.hip) do to a batch of source planes.
+
+    expansion   the operation itself -- moments to order 18, their potential one cell outside each wall -- in float64 or longdouble
+    direct      what the operation approximates: the free-space potential summed source cell by source cell, no multipoles
+    magnitude   the size S of the terms the correction is a sum of: tolerances are stated in units of eps * S
+    terms       S, and how much the correction moves per unit shift of the source cells (T) and of the wall points (U)
+
+The geometry (dx, dy, GetPosOffset, scale, cutoff, prefactor) is computed in float64 by the expressions of the engine's host
+code: these are the kernels' arguments, every dtype starts from the same values.  Planes are (nbatch, ny, nx); bit b of `mask`
+drops the monopole of plane b."""
+import math
+from types import SimpleNamespace
+
+import numpy as np
+
+ORDER = 18
+_CPLX = {np.float64: np.complex128, np.longdouble: np.clongdouble}
+
+
+def geometry(nx, ny, lo, hi):
+    lo, hi = [float(v) for v in lo[:2]], [float(v) for v in hi[:2]]
+    dx, dy = (hi[0] - lo[0]) / nx, (hi[1] - lo[1]) / ny
+    xoff = 0.5 * (lo[0] + hi[0] - dx * (nx - 1))
+    yoff = 0.5 * (lo[1] + hi[1] - dy * (ny - 1))
+    Lx, Ly = hi[0] - lo[0], hi[1] - lo[1]
+    scale = 3.0 / math.sqrt(Lx * Lx + Ly * Ly)
+    radius = min(abs(lo[0]), abs(hi[0]), abs(lo[1]), abs(hi[1]))
+    cutoff_sq = (0.95 * radius * scale) * (0.95 * radius * scale)
+    return SimpleNamespace(nx=nx, ny=ny, dx=dx, dy=dy, xoff=xoff, yoff=yoff, scale=scale, radius=radius, cutoff_sq=cutoff_sq,
+                           pref=dx * dy / (4.0 * math.pi))
+
+
+def cell_positions(g, dtype):
+    """unscaled cell centres x[nx], y[ny] by the engine's expression i*dx + xoff"""
+    x = np.arange(g.nx).astype(dtype) * dtype(g.dx) + dtype(g.xoff)
+    y = np.arange(g.ny).astype(dtype) * dtype(g.dy) + dtype(g.yoff)
+    return x, y
+
+
+def cutoff_r2(g, dtype=np.float64):
+    """(r^2 [ny][nx] of the scaled cell centres, cutoff_sq): a cell counts unless r^2 > cutoff_sq"""
+    x, y = cell_positions(g, dtype)
+    xs, ys = x * dtype(g.scale), y * dtype(g.scale)
+    return xs[None, :] * xs[None, :] + ys[:, None] * ys[:, None], dtype(g.cutoff_sq)
+
+
+def _inside(g, dtype):
+    r2, c = cutoff_r2(g, dtype)
+    return ~(r2 > c)
+
+
+def edge_points(g, dtype):
+    """The 2 nx + 2 ny points one cell outside the box, wall by wall (low y, high y, low x, high x): unscaled position, the
+    edge cell (tj, ti) each corrects, and h^2 of the spacing normal to that wall."""
+    x, y = cell_positions(g, dtype)
+    dx, dy, xoff, yoff = dtype(g.dx), dtype(g.dy), dtype(g.xoff), dtype(g.yoff)
+    ii, jj = np.arange(g.nx), np.arange(g.ny)
+    one = np.ones
+    px = np.concatenate([x, x, one(g.ny, dtype) * (-dx + xoff), one(g.ny, dtype) * (g.nx * dx + xoff)])
+    py = np.concatenate([one(g.nx, dtype) * (-dy + yoff), one(g.nx, dtype) * (g.ny * dy + yoff), y, y])
+    tj = np.concatenate([0 * ii, 0 * ii + g.ny - 1, jj, jj])
+    ti = np.concatenate([ii, ii, 0 * jj, 0 * jj + g.nx - 1])
+    hh = np.concatenate([one(2 * g.nx, dtype) * (dy * dy), one(2 * g.ny, dtype) * (dx * dx)])
+    return px, py, tj, ti, hh
+
+
+def correction(planes, nx, ny, lo, hi, mask=0, dtype=np.longdouble):
+    """what the operation adds: (nbatch, ny, nx), zero off the outermost rows and columns"""
+    g = geometry(nx, ny, lo, hi)
+    ctype = _CPLX[dtype]
+    planes = np.asarray(planes)
+    x, y = cell_positions(g, dtype)
+    inside = _inside(g, dtype)
+    zsrc = ((x * dtype(g.scale))[None, :] + 1j * (y * dtype(g.scale))[:, None]).astype(ctype)[inside]
+    px, py, tj, ti, hh = edge_points(g, dtype)
+    z = ((px * dtype(g.scale)) + 1j * (py * dtype(g.scale))).astype(ctype)
+    zinv = 1 / z
+    out = np.zeros(planes.shape, dtype)
+    for b in range(planes.shape[0]):
+        s = planes[b][inside].astype(dtype)
+        M, zn = [], np.ones(zsrc.shape, ctype)
+        for n in range(ORDER + 1):
+            M.append((s * zn).sum())
+            zn = zn * zsrc
+        v = np.zeros(z.shape, dtype) if (mask >> b) & 1 else M[0].real * np.log(z.real * z.real + z.imag * z.imag)
+        zin = zinv
+        for n in range(1, ORDER + 1):
+            v = v - (dtype(2) / n) * (M[n] * zin).real
+            zin = zin * zinv
+        np.add.at(out[b], (tj, ti), -(dtype(g.pref) * v) / hh)
+    return out
+
+
+def expansion(planes, nx, ny, lo, hi, mask=0, dtype=np.longdouble):
+    """the planes after the operation, in dtype"""
+    return np.asarray(planes).astype(dtype) + correction(planes, nx, ny, lo, hi, mask, dtype)
+
+
+def direct(planes, nx, ny, lo, hi):
+    """The planes after the boundary rule applied to the potential itself, in longdouble: phi(r) = dx dy/(4 pi) sum_src s
+    ln(|r - r'|^2 scale^2) over the source cells inside the cutoff, -phi/h^2 onto the edge cells.  The scale^2: the reference
+    hands its expansion the coordinates times scale = 3/|diagonal| (Fields.cpp:700-703, :720-721, :739), whose monopole term is
+    ln of the scaled radius squared (OpenBoundary.H:115-120); the series it truncates is that of ln|z - z'|^2 in those scaled
+    coordinates, |z - z'|^2 = |r - r'|^2 scale^2."""
+    ld = np.longdouble
+    g = geometry(nx, ny, lo, hi)
+    planes = np.asarray(planes)
+    x, y = cell_positions(g, ld)
+    inside = _inside(g, ld)
+    px, py, tj, ti, hh = edge_points(g, ld)
+    out = planes.astype(ld)
+    for b in range(planes.shape[0]):
+        jj, ii = np.nonzero(inside & (planes[b] != 0.0))
+        phi = np.zeros(px.shape, ld)
+        for j, i in zip(jj, ii):
+            d2 = (px - x[i]) * (px - x[i]) + (py - y[j]) * (py - y[j])
+            phi += ld(planes[b, j, i]) * np.log(d2 * (ld(g.scale) * ld(g.scale)))
+        np.add.at(out[b], (tj, ti), -(ld(g.pref) * phi) / hh)
+    return out
+
+
+def _abs_moments(g, plane, nmax):
+    """A_n = sum |s| |z'|^n over the cells inside the cutoff, n = 0 .. nmax"""
+    ld = np.longdouble
+    r2, c = cutoff_r2(g, ld)
+    live = ~(r2 > c) & (plane != 0.0)
+    r, a = np.sqrt(r2[live]), np.abs(plane[live]).astype(ld)
+    A, rn = [], np.ones(r.shape, ld)
+    for n in range(nmax + 1):
+        A.append((a * rn).sum())
+        rn = rn * r
+    return A
+
+
+def terms(planes, nx, ny, lo, hi, mask=0):
+    """(S, T, U), each (nbatch, ny, nx), zero off the edge cells, a corner holding the sum of its two.  With A_n = sum |s| |z'|^n:
+    S = pref/h^2 [A_0 |ln|z|^2| + sum_n (2/n) A_n |z|^-n], the size of the terms the correction is a sum of (a masked plane's has no
+    A_0 term, nor has its S);
+    T = pref/h^2 sum_n 2 A_(n-1) |z|^-n and U = pref/h^2 [2 A_0/|z| + sum_n 2 A_n |z|^-(n+1)], the correction's first-order change
+    per unit shift, in scaled coordinates, of every source cell (d z'^n = n z'^(n-1) d z') and of the wall point.  Positions are
+    rounded absolutely -- i dx + xoff cancels -- so that part of the error is no multiple of S: where ln|z|^2 crosses 0, S loses
+    its A_0 term and U does not."""
+    ld = np.longdouble
+    g = geometry(nx, ny, lo, hi)
+    planes = np.asarray(planes)
+    px, py, tj, ti, hh = edge_points(g, ld)
+    rz = np.sqrt((px * ld(g.scale)) ** 2 + (py * ld(g.scale)) ** 2)
+    S, T, U = (np.zeros(planes.shape, ld) for _ in range(3))
+    for b in range(planes.shape[0]):
+        A = _abs_moments(g, planes[b], ORDER)
+        masked = (mask >> b) & 1
+        s = np.zeros(rz.shape, ld) if masked else A[0] * np.abs(np.log(rz * rz))
+        t = np.zeros(rz.shape, ld)
+        u = np.zeros(rz.shape, ld) if masked else 2 * A[0] / rz
+        rn = np.ones(rz.shape, ld)
+        for n in range(1, ORDER + 1):
+            rn = rn / rz
+            s = s + (ld(2) / n) * A[n] * rn
+            t = t + 2 * A[n - 1] * rn
+            u = u + 2 * A[n] * rn / rz
+        for out, v in ((S, s), (T, t), (U, u)):
+            np.add.at(out[b], (tj, ti), ld(g.pref) * v / hh)
+    return S, T, U
+
+
+def magnitude(planes, nx, ny, lo, hi, mask=0):
+    return terms(planes, nx, ny, lo, hi, mask)[0]
+
+
+# The rounding bound of one evaluation in a format of machine epsilon eps (unit roundoff u = eps/2), counted from the kernels'
+# longest chain -- the order-18 term -- with every product and sum rounded separately (a fused multiply-add only removes one):
+#   moments   z'^18 by 18 complex products, 2 sqrt2 u each on the modulus ............................................  51 u
+#             per component: s * z'^n (1), the thread's sum of up to 16 cells at 1024^2 (15), 43 LDS entries per thread
+#             (43), the six-way tree (3), 43 of the 256 parts per thread (43), its tree (3): 108 u, on the modulus x sqrt2  153 u
+#   series    1/z: |z|^2 (2), the division (1), x sqrt2, to the 18th power (77); 17 complex products (48); M_n z^-n (2), 2/n and
+#             its product (2); the 19 sums of the series (19); the logarithm and its product (3); pref, h^2, the division
+#             (3); the atomic add, two at a corner (2) ........................................................... 156 u
+# 360 u = 180 eps, each relative to a term of S.  The positions come on top (terms(): T, U), in scaled coordinates, where the box
+# is at most 3/sqrt2 wide, the cutoff disc has radius <= 1.01 and a wall point lies within 3.2 of the origin: a source cell's
+# (i dx + xoff) scale is off by u (Lx scale + 2 |x|) <= 5.02 u per coordinate, 7.1 u = 3.6 eps in the plane -> DSRC = 4; a wall
+# point's by u (3 + 2 * 3.2) = 9.4 u per coordinate, 13.3 u in the plane, and the rounding of |z|^2 under the logarithm moves |z|
+# by another u |z| <= 3.2 u: 16.5 u = 8.3 eps -> DEDGE = 9.
+K, DSRC, DEDGE = 180, 4, 9
+
+
+def rounding_bound(planes, nx, ny, lo, hi, mask=0, eps=np.finfo(np.float64).eps):
+    """(bound, S): eps (K S + DSRC T + DEDGE U) per edge cell"""
+    S, T, U = terms(planes, nx, ny, lo, hi, mask)
+    return eps * (K * S + DSRC * T + DEDGE * U), S
+
+
+def cutoff_border(nx, ny, lo, hi, rel=1e-9):
+    """[ny][nx] bool: the cells whose membership in the cutoff disc a fused multiply-add in i dx + xoff, or in x x + y y, could
+    decide: |r^2 - cutoff_sq| <= rel cutoff_sq"""
+    g = geometry(nx, ny, lo, hi)
+    r2, c = cutoff_r2(g, np.float64)
+    return np.abs(r2 - c) <= rel * c
+
+
+def dense_source(nx, ny, lo, hi, nbatch=1, seed=0, ring="zero"):
+    """Standard normal in every cell, times 1e6 beyond the cutoff (a cell that leaks into the moments is unmistakable), zero on
+    the cutoff's border cells; the outermost ring zeroed (the correction reads without cancellation) or left random."""
+    g = geometry(nx, ny, lo, hi)
+    rng = np.random.default_rng(seed)
+    p = rng.standard_normal((nbatch, ny, nx))
+    r2, c = cutoff_r2(g, np.float64)
+    beyond = r2 > c
+    beyond[0, :] = beyond[-1, :] = beyond[:, 0] = beyond[:, -1] = False      # (the ring keeps its size: the add onto it rounds to it)
+    p[:, beyond] *= 1.0e6
+    p[:, cutoff_border(nx, ny, lo, hi)] = 0.0
+    if ring == "zero":
+        p[:, 0, :] = p[:, -1, :] = 0.0
+        p[:, :, 0] = p[:, :, -1] = 0.0
+    return p
+
+
+def compact_source(nx, ny, lo, hi, nbatch=1, seed=0, rho=0.25, ncell=36):
+    """Up to ncell cells per plane, magnitudes 0.5 .. 1.5 of either sign, drawn from a disc centred off the origin, on neither
+    axis, that lies within |z'| <= rho min|z_edge|: nothing in it is symmetric about an axis."""
+    g = geometry(nx, ny, lo, hi)
+    px, py, *_ = edge_points(g, np.float64)
+    rmin = np.sqrt(px * px + py * py).min()                       # unscaled: the ratio rho does not see the scale
+    x, y = cell_positions(g, np.float64)
+    cx, cy = 0.38 * rho * rmin * math.cos(2.2), 0.38 * rho * rmin * math.sin(2.2)
+    cand = np.argwhere((x[None, :] - cx) ** 2 + (y[:, None] - cy) ** 2 <= (0.6 * rho * rmin) ** 2)
+    rng = np.random.default_rng(seed)
+    p = np.zeros((nbatch, ny, nx))
+    for b in range(nbatch):
+        pick = cand[rng.choice(len(cand), size=min(ncell, len(cand)), replace=False)]
+        val = rng.uniform(0.5, 1.5, len(pick)) * np.where(np.arange(len(pick)) % 3 == 0, -1.0, 1.0)
+        p[b, pick[:, 0], pick[:, 1]] = val
+    p[:, cutoff_border(nx, ny, lo, hi)] = 0.0
+    return p
+
+
+def truncation_bound(planes, nx, ny, lo, hi):
+    """(rho, bound): rho = max|z'| / min|z_edge| over the nonzero source cells inside the cutoff of all planes, and, laid out as
+    magnitude(), the remainder of the series behind order 18: sum|s| sum_(n>18) (2/n) rho^n <= sum|s| (2/19) rho^19/(1 - rho),
+    times pref/h^2 of the wall (a corner holds the sum of its two)."""
+    ld = np.longdouble
+    g = geometry(nx, ny, lo, hi)
+    planes = np.asarray(planes)
+    r2, c = cutoff_r2(g, ld)
+    inside = ~(r2 > c)
+    live = inside & np.any(planes != 0.0, axis=0)
+    px, py, tj, ti, hh = edge_points(g, ld)
+    rho = np.sqrt(r2[live].max()) / np.sqrt(((px * ld(g.scale)) ** 2 + (py * ld(g.scale)) ** 2).min())
+    out = np.zeros(planes.shape, ld)
+    for b in range(planes.shape[0]):
+        a0 = np.abs(planes[b][inside]).astype(ld).sum()
+        np.add.at(out[b], (tj, ti), ld(g.pref) / hh * a0 * (ld(2) / 19) * rho ** 19 / (1 - rho))
+    return rho, out
