@@ -11,9 +11,9 @@ namespace hps {
 
 int beam_push_launch_ext (Engine& E, const SlabView& f, int p, int cPsi, int cEz, int cBx, int cBy, int cBz, const BeamPushConsts& k, dim3 grid)
 {
-    const BeamExtArgs<true> x{E.bext.d_ins, E.bext.d_consts, E.step_time};
+    const BeamExtArgs<true> x{E.bext.image.ins(), E.bext.image.consts(), E.step_time};
     const dim3 block(256);
-    const size_t lds = (size_t)std::max(E.bext.depth - 1, 0)*256*sizeof(double);
+    const size_t lds = expr_lds_bytes(E.bext.depth, 256);
 #define CALL(O) hipLaunchKernelGGL((k_beam_push<O, true>), grid, block, lds, E.st, f, E.bm, E.d_B, p, cPsi, cEz, cBx, cBy, cBz, k, x)
     HPS_BEAM_ORDER(E.d.order, CALL)
 #undef CALL
@@ -37,21 +37,13 @@ int Engine::set_beam_external_fields (const hps_expr* E3, const hps_expr* B3)
         if (expr_is_zero(src[q % 3])) continue;
         comp[q] = &src[q % 3]; depth = std::max(depth, dq); any = true;
     }
-    (void)hipFree(bext.d_ins); (void)hipFree(bext.d_consts);
     bext = BeamExt{};
     if (!any || !moving) return HPS_OK;      // hipace.dt = 0: the beam is never pushed, the programs have no effect
-    std::vector<hps_expr_ins> ins(6, hps_expr_ins{0, 0});
-    std::vector<double> consts;
-    for (int q = 0; q < 6; ++q) {
-        if (!comp[q]) continue;
-        const int off = expr_append(*comp[q], ins, consts);
-        ins[q] = hps_expr_ins{off, comp[q]->n_ins};
-    }
-    if (consts.empty()) consts.push_back(0.0);
-    HPS_HIP_CHECK(hipMalloc(&bext.d_ins, ins.size()*sizeof(hps_expr_ins)));
-    HPS_HIP_CHECK(hipMalloc(&bext.d_consts, consts.size()*sizeof(double)));
-    HPS_HIP_CHECK(hipMemcpy(bext.d_ins, ins.data(), ins.size()*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
-    HPS_HIP_CHECK(hipMemcpy(bext.d_consts, consts.data(), consts.size()*sizeof(double), hipMemcpyHostToDevice));
+    ExprImage image(6);
+    for (int q = 0; q < 6; ++q)
+        if (comp[q]) image.slot(q) = hps_expr_ins{image.add(*comp[q]), comp[q]->n_ins};
+    if (int e = image.upload()) return e;
+    bext.image = std::move(image);
     bext.depth = depth; bext.on = true;
     return HPS_OK;
 }

@@ -1,22 +1,35 @@
-// beam_init.hip -- the general fixed_ppc beam on the device: <beam>.density(x,y,z) as an expression program, min_density, u_std
-// and random_ppc (InitBeamFixedPPC3D / InitBeamFixedPPCSlice, particles/beam/BeamParticleContainerInit.cpp:119-346;
-// get_position_unit_cell, particles/particles_utils/ParticleUtil.H:30-64) for the whole box.
+// beam_init.hip -- the beams the device generates: fixed_ppc, fixed_weight (8o) and fixed_weight_pdf (8p).
 //
-// A lattice point is (cell i, j, k; i_part < ppc_x ppc_y ppc_z).  The beam's order is Engine::init_beam's and the reference's
-// exclusive scan: slices head first (k descending), inside a slice j, then i, then i_part.  One workgroup owns one row
-// (k, j) of the window that zmin, zmax and the radius leave, and walks the row's points (i, i_part) in that order, 256 at a time:
+// Every setter checks all its arguments, fills the argument struct of its kernels, and then goes through the same three steps:
+//     begin_device_beam     the stream drained, the old beam released, beam_off and n_left_out zeroed
+//     (the generator)       its programs in one ExprImage, its scratch in DevBufs -> the slices' blocks [7][count_p], beam_off
+//     finish_device_beam    k_beam_extent and the box of the particles, install_beam_device (the blocks become the engine's)
+// A generator that fails leaves the engine without a beam (drop_device_beam).  Every random draw is a function of (seed, tag, the
+// point's or the draw's index, component), never of a lane or of the packed index: a generator computes a point twice -- to count
+// or to sort, then to fill -- from the same numbers, and the beam does not depend on the launch.  No atomics.  A program's stack
+// is the lane's column of the workgroup's dynamic LDS ([level][lane], expr.h).
+//
+// fixed_ppc (InitBeamFixedPPC3D / InitBeamFixedPPCSlice, particles/beam/BeamParticleContainerInit.cpp:119-346;
+// get_position_unit_cell, particles/particles_utils/ParticleUtil.H:30-64): a lattice point is (cell i, j, k; i_part < ppc_x ppc_y
+// ppc_z), the order Engine::init_beam's and the reference's exclusive scan: slices head first (k descending), inside a slice j,
+// then i, then i_part.  One workgroup owns one row (k, j) of the window that zmin, zmax and the radius leave, and walks the row's
+// points (i, i_part) in that order, 256 at a time:
 //     k_beam_fixed_ppc<false>   counts the row's particles                    -> count[row j][slice k]
 //     k_beam_row_offsets        running sums along j, one lane per slice      -> the row's first index in its slice, slice totals
 //     (host)                    running sum of the nz slice totals            -> beam_off[nz + 1]
 //     k_beam_fixed_ppc<true>    the same walk; a ballot ranks the particles of a chunk, the row's running index carries over
 //                               the chunks, and every particle goes straight into the engine's block of its slice
-// Both walks compute the same points from the same numbers -- every random draw is a function of (seed, tag, the point's global
-// slot, component), never of a lane or of the packed index -- so the count and the fill agree, and the beam does not depend on
-// the launch.  No atomics.  The program's stack is the lane's column of the workgroup's dynamic LDS ([level][lane], expr.h).
-// Below it, the fixed_weight beam (gaussian and can profiles) and the fixed_weight_pdf beam by the same
-// rule for their draws.
+//
+// fixed_weight and fixed_weight_pdf (InitBeamFixedWeight3D / ..Slice, :348-475; InitBeamFixedWeightPDF3D / ..Slice, :477-695):
+// nothing but a key and the index i is ever stored per draw, and the two beams share one stage (fw_generate):
+//     k_fw_keys | k_fwp_keys   one lane per draw: z, x, y, validity -> key = slice from the head | nz (invalid) | nz + 1 (outside
+//                              the box), i
+//     (sort.hip)               stable radix sort of (key, i): slices head first, ascending i inside a slice -- the reference's box sort
+//     k_fw_starts              first sorted position of every key -> the slices' counts and the two left-out counts
+//     k_fw_fill | k_fwp_fill   one lane per kept position o: i = perm[o], the draws of i again, the means at z, the particle (or its
+//                              four mirror copies at 4o + q) straight into the block of its slice
+// The z draw is a stage of its own (fw_draw_z, fwp_draw_z) behind which everything else only reads z.
 #include "engine.h"
-#include "expr.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,6 +53,16 @@ struct BeamInit {
 };
 
 struct BeamPoint { double x, y, z, density; bool keep; unsigned long long slot; };
+
+// the three momentum deviates of particle i (a lattice slot, a draw) of every generated beam -- the pair n[0], n[1] and n[2] each
+// only if wanted (a Box-Muller pair nobody reads is not drawn); u_mean + u_std n is the caller's
+__device__ __forceinline__ void beam_deviates (unsigned long long key_mom, unsigned long long i, bool want_xy, bool want_z, double n[3])
+{
+    const unsigned long long zk = coll_hash(key_mom, i);
+    n[0] = n[1] = n[2] = 0.0;
+    if (want_xy) normal_pair(zk, 0u, n[0], n[1]);
+    if (want_z) { double unused; normal_pair(zk, 2u, n[2], unused); }
+}
 
 // point q = (i - i_lo) nppc + i_part of row (k, j): position, selection and density.  Every operation rounds once (no
 // contraction), in the order of Engine::init_beam, so that numpy reproduces the positions bit for bit.
@@ -111,18 +134,10 @@ void k_beam_fixed_ppc (BeamInit a, int* __restrict__ count, const long* __restri
                 const long o = run + before + __popcll(mask & ((1ULL << lane) - 1ULL));
                 double u[3] = {a.u_mean[0], a.u_mean[1], a.u_mean[2]};
                 if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0 || a.u_std[2] != 0.0) {
-                    const unsigned long long zk = coll_hash(a.key_mom, pt.slot);
-                    if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0) {
-                        double n0, n1;
-                        normal_pair(zk, 0u, n0, n1);
-                        if (a.u_std[0] != 0.0) u[0] += a.u_std[0]*n0;
-                        if (a.u_std[1] != 0.0) u[1] += a.u_std[1]*n1;
-                    }
-                    if (a.u_std[2] != 0.0) {
-                        double n2, unused;
-                        normal_pair(zk, 2u, n2, unused);
-                        u[2] += a.u_std[2]*n2;
-                    }
+                    double n[3];
+                    beam_deviates(a.key_mom, pt.slot, a.u_std[0] != 0.0 || a.u_std[1] != 0.0, a.u_std[2] != 0.0, n);
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) if (a.u_std[q] != 0.0) u[q] += a.u_std[q]*n[q];
                 }
                 blk[o] = pt.x; blk[cnt_p + o] = pt.y; blk[2*cnt_p + o] = pt.z;
                 blk[3*cnt_p + o] = u[0]*a.c; blk[4*cnt_p + o] = u[1]*a.c; blk[5*cnt_p + o] = u[2]*a.c;
@@ -195,16 +210,69 @@ void k_beam_blocks_to_soa (const double* __restrict__ blocks, const long* __rest
     for (long i = threadIdx.x; i < cnt; i += BI_THREADS) dst[i] = src[i];
 }
 
+// beam_off[nz + 1] for the kernels above
+static int beam_off_to_device (Engine& E, DevBuf<long>& off)
+{
+    const size_t n = (size_t)E.d.nz + 1;
+    if (int e = off.alloc(n)) return e;
+    HPS_HIP_CHECK(hipMemcpyAsync(off.get(), E.beam_off.data(), n*sizeof(long), hipMemcpyHostToDevice, E.st));
+    return HPS_OK;
+}
+
 int beam_blocks_to_soa (Engine& E, const double* blocks, double* soa, long nb)
 {
-    long* d_off = nullptr;
-    HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(E.d.nz + 1)*sizeof(long)));
-    HPS_HIP_CHECK(hipMemcpy(d_off, E.beam_off.data(), (size_t)(E.d.nz + 1)*sizeof(long), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_beam_blocks_to_soa, dim3(E.d.nz, 7), dim3(BI_THREADS), 0, E.st, blocks, d_off, soa, nb);
+    DevBuf<long> off;
+    if (int e = beam_off_to_device(E, off)) return e;
+    hipLaunchKernelGGL(k_beam_blocks_to_soa, dim3(E.d.nz, 7), dim3(BI_THREADS), 0, E.st, blocks, off.get(), soa, nb);
     HPS_HIP_CHECK(hipGetLastError());
     HPS_HIP_CHECK(hipStreamSynchronize(E.st));
-    HPS_HIP_CHECK(hipFree(d_off));
     return HPS_OK;
+}
+
+// box = {xlo, xhi, ylo, yhi} of the particles of `blocks` (beam_off filled in, at least one particle)
+static int beam_extent (Engine& E, const double* blocks, double box[4])
+{
+    const int nz = E.d.nz;
+    DevBuf<long> off; DevBuf<double> d_mm;
+    if (int e = beam_off_to_device(E, off)) return e;
+    if (int e = d_mm.alloc((size_t)4*nz)) return e;
+    hipLaunchKernelGGL(k_beam_extent, dim3(nz), dim3(BI_THREADS), 0, E.st, blocks, off.get(), d_mm.get());
+    HPS_HIP_CHECK(hipGetLastError());
+    std::vector<double> mm((size_t)4*nz);
+    HPS_HIP_CHECK(hipMemcpyAsync(mm.data(), d_mm.get(), mm.size()*sizeof(double), hipMemcpyDeviceToHost, E.st));
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));
+    box[0] = box[2] = std::numeric_limits<double>::infinity(); box[1] = box[3] = -std::numeric_limits<double>::infinity();
+    for (int p = 0; p < nz; ++p) {
+        box[0] = std::min(box[0], mm[(size_t)4*p]);     box[1] = std::max(box[1], mm[(size_t)4*p + 1]);
+        box[2] = std::min(box[2], mm[(size_t)4*p + 2]); box[3] = std::max(box[3], mm[(size_t)4*p + 3]);
+    }
+    return HPS_OK;
+}
+
+int Engine::begin_device_beam (long* n_left_out)
+{
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    release_beam();
+    host_beam = true;
+    beam_off.assign(d.nz + 1, 0);
+    if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
+    return HPS_OK;
+}
+
+int Engine::drop_device_beam (int e, long* n_left_out)
+{
+    const double box[4] = {0.0, 0.0, 0.0, 0.0};
+    beam_off.assign(d.nz + 1, 0);
+    if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
+    (void)install_beam_device(nullptr, 0, box);
+    return e;
+}
+
+int Engine::finish_device_beam (DevBuf<double>& blocks, long n, long* n_left_out)
+{
+    double box[4] = {0.0, 0.0, 0.0, 0.0};
+    if (int e = n > 0 ? beam_extent(*this, blocks.get(), box) : HPS_OK) return drop_device_beam(e, n_left_out);
+    return install_beam_device(blocks.release(), n, box);
 }
 
 // first and last cell index (clamped to 0 .. n - 1; an empty range has first > last) a coordinate range [a, b] can touch,
@@ -215,6 +283,41 @@ static void cell_window (double a, double b, double lo, double h, int n, int* fi
     const int ia = fa > 0.0 ? (int)std::min<double>(fa, n) : 0;
     const int ib = fb < n - 1 ? (int)std::max<double>(fb, -1.0) : n - 1;
     *first = ia; *count = std::max(ib - ia + 1, 0);
+}
+
+// the two walks over the rows of a's window: beam_off, and the n > 0 particles in `blocks`
+static int fixed_ppc_generate (Engine& E, BeamInit a, const hps_expr& density, size_t lds, DevBuf<double>& blocks, long& n)
+{
+    const int nz = E.d.nz;
+    ExprImage image;
+    image.add(density);
+    if (int e = image.upload()) return e;
+    a.ins = image.ins(); a.consts = image.consts();
+    const size_t rows = (size_t)a.nj*a.nk;
+    DevBuf<int> count; DevBuf<long> first, total, off;
+    if (int e = count.alloc(rows)) return e;
+    if (int e = first.alloc(rows)) return e;
+    if (int e = total.alloc((size_t)a.nk)) return e;
+    const dim3 grid(a.nj, a.nk), block(BI_THREADS);
+    hipLaunchKernelGGL(k_beam_fixed_ppc<false>, grid, block, lds, E.st, a, count.get(), nullptr, nullptr, nullptr);
+    HPS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_beam_row_offsets, dim3(ceil_div(a.nk, BI_THREADS)), block, 0, E.st, count.get(), first.get(), total.get(), a.nj, a.nk);
+    HPS_HIP_CHECK(hipGetLastError());
+    std::vector<long> h_total((size_t)a.nk);
+    HPS_HIP_CHECK(hipMemcpyAsync(h_total.data(), total.get(), h_total.size()*sizeof(long), hipMemcpyDeviceToHost, E.st));
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));
+    for (int p = 0; p < nz; ++p) {              // head slice first
+        const int kk = nz - 1 - p - a.k_lo;
+        E.beam_off[p + 1] = E.beam_off[p] + ((kk >= 0 && kk < a.nk) ? h_total[(size_t)kk] : 0);
+    }
+    n = E.beam_off[nz];
+    if (n == 0) return HPS_OK;
+    if (int e = beam_off_to_device(E, off)) return e;
+    if (int e = blocks.alloc((size_t)7*n)) return e;
+    hipLaunchKernelGGL(k_beam_fixed_ppc<true>, grid, block, lds, E.st, a, nullptr, first.get(), off.get(), blocks.get());
+    HPS_HIP_CHECK(hipGetLastError());
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));      // (the image and the scratch go out of scope)
+    return HPS_OK;
 }
 
 // hps_engine_set_beam_fixed_ppc: everything is checked before anything of the engine changes
@@ -251,79 +354,14 @@ int Engine::set_beam_fixed_ppc (const hps_expr* density, double min_density, con
     const bool window = a.ni > 0 && a.nj > 0 && a.nk > 0;
     HPS_REQUIRE(a.nk <= 65535, std::string(fn) + ": more than 65535 slices");
 
-    HPS_HIP_CHECK(hipStreamSynchronize(st));
-    release_beam();
-    host_beam = true;
-    beam_off.assign(d.nz + 1, 0);
-    double box[4] = {0.0, 0.0, 0.0, 0.0};
-    double* blocks = nullptr;
-    long n = 0;
-    if (window) {
-        hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; int* d_count = nullptr; long *d_first = nullptr, *d_total = nullptr, *d_off = nullptr;
-        double* d_mm = nullptr;
-        const size_t rows = (size_t)a.nj*a.nk, lds = (size_t)std::max(depth - 1, 0)*BI_THREADS*sizeof(double);
-        auto release = [&] { (void)hipFree(d_ins); (void)hipFree(d_consts); (void)hipFree(d_count); (void)hipFree(d_first); (void)hipFree(d_total);
-                             (void)hipFree(d_off); (void)hipFree(d_mm); };
-        auto run = [&] () -> int {
-            HPS_HIP_CHECK(hipMalloc(&d_ins, (size_t)density->n_ins*sizeof(hps_expr_ins)));
-            HPS_HIP_CHECK(hipMalloc(&d_consts, (size_t)std::max(density->n_const, 1)*sizeof(double)));
-            HPS_HIP_CHECK(hipMemcpy(d_ins, density->ins, (size_t)density->n_ins*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
-            if (density->n_const > 0) HPS_HIP_CHECK(hipMemcpy(d_consts, density->consts, (size_t)density->n_const*sizeof(double), hipMemcpyHostToDevice));
-            a.ins = d_ins; a.consts = d_consts;
-            HPS_HIP_CHECK(hipMalloc(&d_count, rows*sizeof(int)));
-            HPS_HIP_CHECK(hipMalloc(&d_first, rows*sizeof(long)));
-            HPS_HIP_CHECK(hipMalloc(&d_total, (size_t)a.nk*sizeof(long)));
-            HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(d.nz + 1)*sizeof(long)));
-            HPS_HIP_CHECK(hipMalloc(&d_mm, (size_t)4*d.nz*sizeof(double)));
-            const dim3 grid(a.nj, a.nk), block(BI_THREADS);
-            hipLaunchKernelGGL(k_beam_fixed_ppc<false>, grid, block, lds, st, a, d_count, nullptr, nullptr, nullptr);
-            HPS_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_beam_row_offsets, dim3(ceil_div(a.nk, BI_THREADS)), block, 0, st, d_count, d_first, d_total, a.nj, a.nk);
-            HPS_HIP_CHECK(hipGetLastError());
-            std::vector<long> total((size_t)a.nk);
-            HPS_HIP_CHECK(hipMemcpyAsync(total.data(), d_total, total.size()*sizeof(long), hipMemcpyDeviceToHost, st));
-            HPS_HIP_CHECK(hipStreamSynchronize(st));
-            for (int p = 0; p < d.nz; ++p) {              // head slice first
-                const int kk = d.nz - 1 - p - a.k_lo;
-                beam_off[p + 1] = beam_off[p] + ((kk >= 0 && kk < a.nk) ? total[(size_t)kk] : 0);
-            }
-            n = beam_off[d.nz];
-            if (n == 0) return HPS_OK;
-            HPS_HIP_CHECK(hipMemcpyAsync(d_off, beam_off.data(), (size_t)(d.nz + 1)*sizeof(long), hipMemcpyHostToDevice, st));
-            HPS_HIP_CHECK(hipMalloc(&blocks, (size_t)7*n*sizeof(double)));
-            hipLaunchKernelGGL(k_beam_fixed_ppc<true>, grid, block, lds, st, a, nullptr, d_first, d_off, blocks);
-            HPS_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_beam_extent, dim3(d.nz), block, 0, st, blocks, d_off, d_mm);
-            HPS_HIP_CHECK(hipGetLastError());
-            std::vector<double> mm((size_t)4*d.nz);
-            HPS_HIP_CHECK(hipMemcpyAsync(mm.data(), d_mm, mm.size()*sizeof(double), hipMemcpyDeviceToHost, st));
-            HPS_HIP_CHECK(hipStreamSynchronize(st));
-            box[0] = box[2] = std::numeric_limits<double>::infinity(); box[1] = box[3] = -std::numeric_limits<double>::infinity();
-            for (int p = 0; p < d.nz; ++p) {
-                box[0] = std::min(box[0], mm[(size_t)4*p]);     box[1] = std::max(box[1], mm[(size_t)4*p + 1]);
-                box[2] = std::min(box[2], mm[(size_t)4*p + 2]); box[3] = std::max(box[3], mm[(size_t)4*p + 3]);
-            }
-            return HPS_OK;
-        };
-        const int e = run();
-        release();
-        if (e) {                                   // the engine is left without a beam
-            (void)hipFree(blocks); beam_off.assign(d.nz + 1, 0);
-            (void)install_beam_device(nullptr, 0, box);
-            return e;
-        }
-    }
-    return install_beam_device(blocks, n, box);
+    if (int e = begin_device_beam()) return e;
+    DevBuf<double> blocks; long n = 0;
+    if (window)
+        if (int e = fixed_ppc_generate(*this, a, *density, expr_lds_bytes(depth, BI_THREADS), blocks, n)) return drop_device_beam(e, nullptr);
+    return finish_device_beam(blocks, n);
 }
 
-// ---- the fixed_weight beam (InitBeamFixedWeight3D / InitBeamFixedWeightSlice, BeamParticleContainerInit.cpp:348-475) ----
-// Draw i of nd is a function of (seed, tag, i, component) alone, so nothing but a key and the index i is ever stored per draw:
-//     k_fw_keys     one lane per draw: z, x, y, validity -> key = slice from the head | nz (invalid) | nz + 1 (outside the box), i
-//     (sort.hip)    stable radix sort of (key, i): slices head first, ascending i inside a slice -- the reference's box sort
-//     k_fw_starts   first sorted position of every key -> the slices' counts and the two left-out counts
-//     k_fw_fill     one lane per kept position o: i = perm[o], the draws of i again, X(z) and Y(z), the particle (or its four
-//                   mirror copies at 4o + q) straight into the block of its slice
-// The z draw is a stage of its own (fw_draw_z) behind which everything else only reads z.  No atomics.
+// ---- the fixed_weight beam ----
 constexpr unsigned long long BI_TAG_FW_Z = 2, BI_TAG_FW_XY = 3;      // beside BI_TAG_POSITION / BI_TAG_MOMENTUM
 
 struct BeamFixedWeight {
@@ -374,14 +412,35 @@ __device__ __forceinline__ int fw_slice (const Args& a, double z)
     return (q < 0 || q >= a.nz) ? -1 : a.nz - 1 - q;
 }
 
+// the sort key of a draw: its slice from the head | nz (invalid) | nz + 1 (valid, outside the box)
+template <class Args>
+__device__ __forceinline__ unsigned int fw_key (const Args& a, bool valid, double z)
+{
+    const int p = fw_slice(a, z);
+    return (unsigned int)(!valid ? a.nz : p < 0 ? a.nz + 1 : p);
+}
+
+// the particle at (X + x, Y + y, z) with momentum u, or its m = 4 mirror copies about (X, Y): (+,+), (-,+), (+,-), (-,-)
+// (:459-470, :676-690), into rows of cnt slots from blk on
+__device__ __forceinline__ void fw_store_copies (double* blk, long cnt, int m, double X, double x, double Y, double y, double z,
+                                                 const double u[3], double c, double weight)
+{
+#pragma clang fp contract(off)
+    for (int q = 0; q < m; ++q) {
+        const bool nx = (q & 1) != 0, ny = (q & 2) != 0;
+        blk[q] = nx ? X - x : X + x; blk[cnt + q] = ny ? Y - y : Y + y; blk[2*cnt + q] = z;
+        blk[3*cnt + q] = (nx ? -u[0] : u[0])*c; blk[4*cnt + q] = (ny ? -u[1] : u[1])*c; blk[5*cnt + q] = u[2]*c;
+        blk[6*cnt + q] = weight;
+    }
+}
+
 __global__ __launch_bounds__(BI_THREADS)
 void k_fw_keys (BeamFixedWeight a, unsigned int* __restrict__ keys, unsigned int* __restrict__ idx)
 {
     const long i = (long)blockIdx.x*BI_THREADS + threadIdx.x;
     if (i >= a.nd) return;
     const FwDraw d = fw_draw(a, (unsigned long long)i);
-    const int p = fw_slice(a, d.z);
-    keys[i] = (unsigned int)(!d.valid ? a.nz : p < 0 ? a.nz + 1 : p);
+    keys[i] = fw_key(a, d.valid, d.z);
     idx[i] = (unsigned int)i;
 }
 
@@ -410,19 +469,11 @@ void k_fw_fill (BeamFixedWeight a, const unsigned int* __restrict__ keys, const 
     const int p = (int)keys[oo];
     const FwDraw d = fw_draw(a, i);
     double u[3] = {a.u_mean[0], a.u_mean[1], a.u_mean[2]};
-    if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0 || a.u_std[2] != 0.0) {      // the momentum draws of the fixed_ppc beam
-        const unsigned long long zk = coll_hash(a.key_mom, i);
-        if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0) {
-            double n0, n1;
-            normal_pair(zk, 0u, n0, n1);
-            if (a.u_std[0] != 0.0) u[0] = a.u_mean[0] + a.u_std[0]*n0;
-            if (a.u_std[1] != 0.0) u[1] = a.u_mean[1] + a.u_std[1]*n1;
-        }
-        if (a.u_std[2] != 0.0) {
-            double n2, unused;
-            normal_pair(zk, 2u, n2, unused);
-            u[2] = a.u_mean[2] + a.u_std[2]*n2;
-        }
+    if (a.u_std[0] != 0.0 || a.u_std[1] != 0.0 || a.u_std[2] != 0.0) {
+        double n[3];
+        beam_deviates(a.key_mom, i, a.u_std[0] != 0.0 || a.u_std[1] != 0.0, a.u_std[2] != 0.0, n);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) if (a.u_std[q] != 0.0) u[q] = a.u_mean[q] + a.u_std[q]*n[q];
     }
     u[2] = u[2] + (d.z - a.z_mean)*a.duz*a.u_mean[2];      // GetInitialMomentum.H:47
     double x = d.x, y = d.y;
@@ -434,13 +485,51 @@ void k_fw_fill (BeamFixedWeight a, const unsigned int* __restrict__ keys, const 
     if (!live) return;
     const int m = a.sym ? 4 : 1;
     const long f = first[p], cnt = m*(first[p + 1] - f);
-    double* blk = blocks + 7*m*f + m*(o - f);
-    for (int q = 0; q < m; ++q) {                    // (+,+), (-,+), (+,-), (-,-) (:459-470)
-        const bool nx = (q & 1) != 0, ny = (q & 2) != 0;
-        blk[q] = nx ? X - x : X + x; blk[cnt + q] = ny ? Y - y : Y + y; blk[2*cnt + q] = d.z;
-        blk[3*cnt + q] = (nx ? -u[0] : u[0])*a.c; blk[4*cnt + q] = (ny ? -u[1] : u[1])*a.c; blk[5*cnt + q] = u[2]*a.c;
-        blk[6*cnt + q] = a.weight;
-    }
+    fw_store_copies(blocks + 7*m*f + m*(o - f), cnt, m, X, x, Y, y, d.z, u, a.c, a.weight);
+}
+
+// The stage both fixed-weight beams share (Args: BeamFixedWeight, BeamFwPdf, filled in, their programs on the device): the keys of
+// the nd draws, the sort, the first position of every key -> beam_off, n_left_out and the n = m nkept particles (m = 4 mirror
+// copies or 1 per draw) that `fill` writes into `blocks`
+template <class Args>
+static int fw_generate (Engine& E, const Args& a, long nd, int m, void (*keys) (Args, unsigned int*, unsigned int*), size_t lds_keys,
+                        void (*fill) (Args, const unsigned int*, const unsigned int*, const long*, long, double*), size_t lds_fill,
+                        long* n_left_out, DevBuf<double>& blocks, long& n)
+{
+    const int nz = E.d.nz, nkeys = nz + 2;
+    int bits = 1; while ((1L << bits) < (long)nkeys) ++bits;
+    DevBuf<unsigned int> pairs; DevBuf<long> d_first;
+    if (int e = pairs.alloc((size_t)4*nd)) return e;      // keys, indices; sorted keys, sorted indices
+    unsigned int *ka = pairs.get(), *ia = ka + nd, *kb = ia + nd, *ib = kb + nd;
+    if (int e = d_first.alloc((size_t)nkeys + 1)) return e;
+    const dim3 block(BI_THREADS);
+    hipLaunchKernelGGL(keys, dim3(ceil_div(nd, BI_THREADS)), block, lds_keys, E.st, a, ka, ia);
+    HPS_HIP_CHECK(hipGetLastError());
+    if (int e = sort_pairs_u32(ka, kb, ia, ib, nd, bits, E.st)) return e;
+    hipLaunchKernelGGL(k_fw_starts, dim3(ceil_div(nd + 1, BI_THREADS)), block, 0, E.st, kb, nd, nkeys, d_first.get());
+    HPS_HIP_CHECK(hipGetLastError());
+    std::vector<long> first((size_t)nkeys + 1);
+    HPS_HIP_CHECK(hipMemcpyAsync(first.data(), d_first.get(), first.size()*sizeof(long), hipMemcpyDeviceToHost, E.st));
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));
+    for (int p = 0; p <= nz; ++p) E.beam_off[p] = m*first[(size_t)p];
+    if (n_left_out) { n_left_out[0] = m*(first[(size_t)nz + 1] - first[(size_t)nz]); n_left_out[1] = m*(nd - first[(size_t)nz + 1]); }
+    const long nkept = first[(size_t)nz];
+    n = m*nkept;
+    if (n == 0) return HPS_OK;
+    if (int e = blocks.alloc((size_t)7*n)) return e;
+    hipLaunchKernelGGL(fill, dim3(ceil_div(nkept, BI_THREADS)), block, lds_fill, E.st, a, kb, ib, d_first.get(), nkept, blocks.get());
+    HPS_HIP_CHECK(hipGetLastError());
+    HPS_HIP_CHECK(hipStreamSynchronize(E.st));      // (the scratch goes out of scope)
+    return HPS_OK;
+}
+
+// ... and the beam becomes the engine's
+template <class Args, class Keys, class Fill>
+static int fixed_weight_beam (Engine& E, const Args& a, long nd, int m, Keys keys, size_t lds_keys, Fill fill, size_t lds_fill, long* n_left_out)
+{
+    DevBuf<double> blocks; long n = 0;
+    if (int e = fw_generate<Args>(E, a, nd, m, keys, lds_keys, fill, lds_fill, n_left_out, blocks, n)) return E.drop_device_beam(e, n_left_out);
+    return E.finish_device_beam(blocks, n, n_left_out);
 }
 
 // hps_engine_set_beam_fixed_weight: everything is checked before anything of the engine changes
@@ -449,7 +538,6 @@ int Engine::set_beam_fixed_weight (const hps_beam_fixed_weight* s, const hps_exp
 {
     static const char* const name = "hps_engine_set_beam_fixed_weight";
     const std::string fn = std::string(name) + ": ";
-    const double inf = std::numeric_limits<double>::infinity();
     HPS_REQUIRE(s && mean_x && mean_y, fn + "null argument");
     HPS_REQUIRE(steps_begun == 0 && step_index < 0, fn + "call before the first hps_engine_begin_step");
     HPS_REQUIRE(s->num_particles > 0, fn + "num_particles must be positive");
@@ -494,84 +582,19 @@ int Engine::set_beam_fixed_weight (const hps_beam_fixed_weight* s, const hps_exp
     }
     a.key_z = coll_hash(seed, BI_TAG_FW_Z); a.key_xy = coll_hash(seed, BI_TAG_FW_XY); a.key_mom = coll_hash(seed, BI_TAG_MOMENTUM);
     a.n_ins_x = mean_x->n_ins; a.n_ins_y = mean_y->n_ins;
-    const int m = a.sym ? 4 : 1, nkeys = d.nz + 2;
-    int bits = 1; while ((1L << bits) < (long)nkeys) ++bits;
 
-    HPS_HIP_CHECK(hipStreamSynchronize(st));
-    release_beam();
-    host_beam = true;
-    beam_off.assign(d.nz + 1, 0);
-    if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
-    double box[4] = {0.0, 0.0, 0.0, 0.0};
-    double* blocks = nullptr;
-    long n = 0;
-    hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; unsigned int* d_keys = nullptr; long *d_first = nullptr, *d_off = nullptr;
-    double* d_mm = nullptr;
-    auto release = [&] { (void)hipFree(d_ins); (void)hipFree(d_consts); (void)hipFree(d_keys); (void)hipFree(d_first); (void)hipFree(d_off);
-                         (void)hipFree(d_mm); };
-    auto run = [&] () -> int {
-        const size_t ni = (size_t)mean_x->n_ins + mean_y->n_ins, nc = (size_t)mean_x->n_const + mean_y->n_const;
-        HPS_HIP_CHECK(hipMalloc(&d_ins, ni*sizeof(hps_expr_ins)));
-        HPS_HIP_CHECK(hipMalloc(&d_consts, std::max<size_t>(nc, 1)*sizeof(double)));
-        HPS_HIP_CHECK(hipMemcpy(d_ins, mean_x->ins, (size_t)mean_x->n_ins*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
-        HPS_HIP_CHECK(hipMemcpy(d_ins + mean_x->n_ins, mean_y->ins, (size_t)mean_y->n_ins*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
-        if (mean_x->n_const > 0) HPS_HIP_CHECK(hipMemcpy(d_consts, mean_x->consts, (size_t)mean_x->n_const*sizeof(double), hipMemcpyHostToDevice));
-        if (mean_y->n_const > 0) HPS_HIP_CHECK(hipMemcpy(d_consts + mean_x->n_const, mean_y->consts, (size_t)mean_y->n_const*sizeof(double), hipMemcpyHostToDevice));
-        a.ins_x = d_ins; a.ins_y = d_ins + mean_x->n_ins; a.consts_x = d_consts; a.consts_y = d_consts + mean_x->n_const;
-        HPS_HIP_CHECK(hipMalloc(&d_keys, (size_t)4*nd*sizeof(unsigned int)));      // keys, indices; sorted keys, sorted indices
-        unsigned int *ka = d_keys, *ia = ka + nd, *kb = ia + nd, *ib = kb + nd;
-        HPS_HIP_CHECK(hipMalloc(&d_first, (size_t)(nkeys + 1)*sizeof(long)));
-        const dim3 block(BI_THREADS);
-        hipLaunchKernelGGL(k_fw_keys, dim3(ceil_div(nd, BI_THREADS)), block, 0, st, a, ka, ia);
-        HPS_HIP_CHECK(hipGetLastError());
-        if (int e = sort_pairs_u32(ka, kb, ia, ib, nd, bits, st)) return e;
-        hipLaunchKernelGGL(k_fw_starts, dim3(ceil_div(nd + 1, BI_THREADS)), block, 0, st, kb, nd, nkeys, d_first);
-        HPS_HIP_CHECK(hipGetLastError());
-        std::vector<long> first((size_t)nkeys + 1);
-        HPS_HIP_CHECK(hipMemcpyAsync(first.data(), d_first, first.size()*sizeof(long), hipMemcpyDeviceToHost, st));
-        HPS_HIP_CHECK(hipStreamSynchronize(st));
-        for (int p = 0; p <= d.nz; ++p) beam_off[p] = m*first[(size_t)p];
-        if (n_left_out) { n_left_out[0] = m*(first[(size_t)d.nz + 1] - first[(size_t)d.nz]); n_left_out[1] = m*(nd - first[(size_t)d.nz + 1]); }
-        const long nkept = first[(size_t)d.nz];
-        n = m*nkept;
-        if (n == 0) return HPS_OK;
-        HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(d.nz + 1)*sizeof(long)));
-        HPS_HIP_CHECK(hipMalloc(&d_mm, (size_t)4*d.nz*sizeof(double)));
-        HPS_HIP_CHECK(hipMemcpyAsync(d_off, beam_off.data(), (size_t)(d.nz + 1)*sizeof(long), hipMemcpyHostToDevice, st));
-        HPS_HIP_CHECK(hipMalloc(&blocks, (size_t)7*n*sizeof(double)));
-        const size_t lds = (size_t)std::max(std::max(depth_x, depth_y) - 1, 0)*BI_THREADS*sizeof(double);
-        hipLaunchKernelGGL(k_fw_fill, dim3(ceil_div(nkept, BI_THREADS)), block, lds, st, a, kb, ib, d_first, nkept, blocks);
-        HPS_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_beam_extent, dim3(d.nz), block, 0, st, blocks, d_off, d_mm);
-        HPS_HIP_CHECK(hipGetLastError());
-        std::vector<double> mm((size_t)4*d.nz);
-        HPS_HIP_CHECK(hipMemcpyAsync(mm.data(), d_mm, mm.size()*sizeof(double), hipMemcpyDeviceToHost, st));
-        HPS_HIP_CHECK(hipStreamSynchronize(st));
-        box[0] = box[2] = inf; box[1] = box[3] = -inf;
-        for (int p = 0; p < d.nz; ++p) {
-            box[0] = std::min(box[0], mm[(size_t)4*p]);     box[1] = std::max(box[1], mm[(size_t)4*p + 1]);
-            box[2] = std::min(box[2], mm[(size_t)4*p + 2]); box[3] = std::max(box[3], mm[(size_t)4*p + 3]);
-        }
-        return HPS_OK;
-    };
-    const int e = run();
-    release();
-    if (e) {                                   // the engine is left without a beam
-        (void)hipFree(blocks); beam_off.assign(d.nz + 1, 0);
-        if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
-        (void)install_beam_device(nullptr, 0, box);
-        return e;
-    }
-    return install_beam_device(blocks, n, box);
+    if (int e = begin_device_beam(n_left_out)) return e;
+    ExprImage image;
+    const int off_x = image.add(*mean_x), off_y = image.add(*mean_y);
+    if (int e = image.upload()) return drop_device_beam(e, n_left_out);
+    a.ins_x = image.ins() + off_x; a.ins_y = image.ins() + off_y; a.consts_x = a.consts_y = image.consts();
+    return fixed_weight_beam(*this, a, nd, a.sym ? 4 : 1, k_fw_keys, 0, k_fw_fill, expr_lds_bytes(std::max(depth_x, depth_y), BI_THREADS), n_left_out);
 }
 
-// ---- the fixed_weight_pdf beam (InitBeamFixedWeightPDF3D / InitBeamFixedWeightPDFSlice, BeamParticleContainerInit.cpp:477-695;
-// DESIGN 8p) ----
-// The fixed_weight beam's scheme with a table-driven z draw and every mean and width a program over z:
+// ---- the fixed_weight_pdf beam: a table-driven z draw, every mean and width a program over z ----
 //     (host)         pe[s] = pdf(edge s), lw, integral, max_density, the u_z moments, cum[] -- once, in the reference's order
-//     k_fwp_keys     one lane per draw: s by binary search in cum, z, std_x(z), std_y(z), the rejection loop -> key, i
-//     (sort.hip), k_fw_starts                                              as above
-//     k_fwp_fill     one lane per kept position: the draw of i again, all ten programs at z, the particle or its four copies
+//     k_fwp_keys     the draw: s by binary search in cum, z, std_x(z), std_y(z), the rejection loop
+//     k_fwp_fill     the draw of i again, all ten programs at z
 // cum and pe (at most 2 x 8193 doubles for 2048 slices of 4 sub-slices) are read through L2: every lane's search starts on the same
 // few lines, and an image in LDS would cost a workgroup of 256 draws 128 KiB of loads and the CU all but one workgroup.
 constexpr unsigned long long BI_TAG_FW_PDF_Z = 4;
@@ -650,8 +673,7 @@ void k_fwp_keys (BeamFwPdf a, unsigned int* __restrict__ keys, unsigned int* __r
     ExprLdsStack st{s_fwp_key_stack + threadIdx.x, BI_THREADS};
     const FwpDraw d = fwp_draw(a, (unsigned long long)(live ? i : a.nd - 1), st);      // (every lane runs the programs: uniform opcodes)
     if (!live) return;
-    const int p = fw_slice(a, d.z);
-    keys[i] = (unsigned int)(!d.valid ? a.nz : p < 0 ? a.nz + 1 : p);
+    keys[i] = fw_key(a, d.valid, d.z);
     idx[i] = (unsigned int)i;
 }
 
@@ -671,10 +693,8 @@ void k_fwp_fill (BeamFwPdf a, const unsigned int* __restrict__ keys, const unsig
     const FwpDraw d = fwp_draw(a, i, st);
     const ExprZ v{d.z};
     const double X = fwp_prog(a, FWP_MEAN_X, v, st), Y = fwp_prog(a, FWP_MEAN_Y, v, st);
-    double m[3], unused, u[3];
-    const unsigned long long zk = coll_hash(a.key_mom, i);      // the momentum deviates of the fixed_ppc beam
-    normal_pair(zk, 0u, m[0], m[1]);
-    normal_pair(zk, 2u, m[2], unused);
+    double m[3], u[3];
+    beam_deviates(a.key_mom, i, true, true, m);
 #pragma unroll
     for (int q = 0; q < 3; ++q) {
         const double um = fwp_prog(a, FWP_U_MEAN + q, v, st), us = fwp_prog(a, FWP_U_STD + q, v, st);
@@ -685,13 +705,16 @@ void k_fwp_fill (BeamFwPdf a, const unsigned int* __restrict__ keys, const unsig
     if (!live) return;
     const int n = a.sym ? 4 : 1;
     const long f = first[p], cnt = n*(first[p + 1] - f);
-    double* blk = blocks + 7*n*f + n*(o - f);
-    for (int q = 0; q < n; ++q) {                    // (+,+), (-,+), (+,-), (-,-) (:676-690)
-        const bool nx = (q & 1) != 0, ny = (q & 2) != 0;
-        blk[q] = nx ? X - x : X + x; blk[cnt + q] = ny ? Y - y : Y + y; blk[2*cnt + q] = d.z;
-        blk[3*cnt + q] = (nx ? -u[0] : u[0])*a.c; blk[4*cnt + q] = (ny ? -u[1] : u[1])*a.c; blk[5*cnt + q] = u[2]*a.c;
-        blk[6*cnt + q] = a.weight;
-    }
+    fw_store_copies(blocks + 7*n*f + n*(o - f), cnt, n, X, x, Y, y, d.z, u, a.c, a.weight);
+}
+
+// the ten programs and the table cum | pe on the device
+static int fwp_upload (ExprImage& image, const std::vector<double>& tab, DevBuf<double>& d_tab)
+{
+    if (int e = image.upload()) return e;
+    if (int e = d_tab.alloc(tab.size())) return e;
+    HPS_HIP_CHECK(hipMemcpy(d_tab.get(), tab.data(), tab.size()*sizeof(double), hipMemcpyHostToDevice));
+    return HPS_OK;
 }
 
 // hps_engine_set_beam_fixed_weight_pdf: everything is checked before anything of the engine changes
@@ -702,7 +725,6 @@ int Engine::set_beam_fixed_weight_pdf (const hps_beam_fixed_weight_pdf* s, const
     static const char* const prog_name[FWP_NPROG] = {"position_mean[0]: ", "position_mean[1]: ", "position_std[0]: ", "position_std[1]: ",
                                                      "u_mean[0]: ", "u_mean[1]: ", "u_mean[2]: ", "u_std[0]: ", "u_std[1]: ", "u_std[2]: "};
     const std::string fn = std::string(name) + ": ";
-    const double inf = std::numeric_limits<double>::infinity();
     HPS_REQUIRE(s && pdf && progs, fn + "null argument");
     HPS_REQUIRE(steps_begun == 0 && step_index < 0, fn + "call before the first hps_engine_begin_step");
     HPS_REQUIRE(s->num_particles > 0, fn + "num_particles must be positive");
@@ -770,80 +792,18 @@ int Engine::set_beam_fixed_weight_pdf (const hps_beam_fixed_weight_pdf* s, const
     a.nd = nd; a.sym = s->do_symmetrize != 0; a.nz = d.nz; a.ns = ns; a.last = last; a.retry = s->charge_is_specified != 0;
     a.lo_z = lo_z; a.inv_dz = 1.0/gm.dz; a.zs = zs; a.radius_sq = s->radius*s->radius; a.z_foc = s->z_foc; a.c = gm.c; a.weight = weight;
     a.key_z = coll_hash(seed, BI_TAG_FW_PDF_Z); a.key_xy = coll_hash(seed, BI_TAG_FW_XY); a.key_mom = coll_hash(seed, BI_TAG_MOMENTUM);
-    std::vector<hps_expr_ins> ins; std::vector<double> consts;
-    for (int k = 0; k < FWP_NPROG; ++k) a.off[k] = expr_append(progs[k], ins, consts);
-    a.off[FWP_NPROG] = (int)ins.size();
+    ExprImage image;
+    for (int k = 0; k < FWP_NPROG; ++k) a.off[k] = image.add(progs[k]);
+    a.off[FWP_NPROG] = image.n_ins();
     const int depth_keys = std::max(depth[FWP_STD_X], depth[FWP_STD_Y]), depth_fill = *std::max_element(depth, depth + FWP_NPROG);
-    const int m = a.sym ? 4 : 1, nkeys = d.nz + 2;
-    int bits = 1; while ((1L << bits) < (long)nkeys) ++bits;
 
-    HPS_HIP_CHECK(hipStreamSynchronize(st));
-    release_beam();
-    host_beam = true;
-    beam_off.assign(d.nz + 1, 0);
-    if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
+    if (int e = begin_device_beam(n_left_out)) return e;
     if (uz_moments) { uz_moments[0] = uz_mean; uz_moments[1] = uz_std; }
-    double box[4] = {0.0, 0.0, 0.0, 0.0};
-    double* blocks = nullptr;
-    long n = 0;
-    hps_expr_ins* d_ins = nullptr; double *d_consts = nullptr, *d_tab = nullptr, *d_mm = nullptr; unsigned int* d_keys = nullptr;
-    long *d_first = nullptr, *d_off = nullptr;
-    auto release = [&] { (void)hipFree(d_ins); (void)hipFree(d_consts); (void)hipFree(d_tab); (void)hipFree(d_keys); (void)hipFree(d_first);
-                         (void)hipFree(d_off); (void)hipFree(d_mm); };
-    auto run = [&] () -> int {
-        HPS_HIP_CHECK(hipMalloc(&d_ins, std::max<size_t>(ins.size(), 1)*sizeof(hps_expr_ins)));
-        HPS_HIP_CHECK(hipMalloc(&d_consts, std::max<size_t>(consts.size(), 1)*sizeof(double)));
-        HPS_HIP_CHECK(hipMalloc(&d_tab, tab.size()*sizeof(double)));
-        if (!ins.empty()) HPS_HIP_CHECK(hipMemcpy(d_ins, ins.data(), ins.size()*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
-        if (!consts.empty()) HPS_HIP_CHECK(hipMemcpy(d_consts, consts.data(), consts.size()*sizeof(double), hipMemcpyHostToDevice));
-        HPS_HIP_CHECK(hipMemcpy(d_tab, tab.data(), tab.size()*sizeof(double), hipMemcpyHostToDevice));
-        a.ins = d_ins; a.consts = d_consts; a.cum = d_tab; a.pe = d_tab + (ns + 1);
-        HPS_HIP_CHECK(hipMalloc(&d_keys, (size_t)4*nd*sizeof(unsigned int)));      // keys, indices; sorted keys, sorted indices
-        unsigned int *ka = d_keys, *ia = ka + nd, *kb = ia + nd, *ib = kb + nd;
-        HPS_HIP_CHECK(hipMalloc(&d_first, (size_t)(nkeys + 1)*sizeof(long)));
-        const dim3 block(BI_THREADS);
-        const size_t lds_keys = (size_t)std::max(depth_keys - 1, 0)*BI_THREADS*sizeof(double);
-        hipLaunchKernelGGL(k_fwp_keys, dim3(ceil_div(nd, BI_THREADS)), block, lds_keys, st, a, ka, ia);
-        HPS_HIP_CHECK(hipGetLastError());
-        if (int e = sort_pairs_u32(ka, kb, ia, ib, nd, bits, st)) return e;
-        hipLaunchKernelGGL(k_fw_starts, dim3(ceil_div(nd + 1, BI_THREADS)), block, 0, st, kb, nd, nkeys, d_first);
-        HPS_HIP_CHECK(hipGetLastError());
-        std::vector<long> first((size_t)nkeys + 1);
-        HPS_HIP_CHECK(hipMemcpyAsync(first.data(), d_first, first.size()*sizeof(long), hipMemcpyDeviceToHost, st));
-        HPS_HIP_CHECK(hipStreamSynchronize(st));
-        for (int p = 0; p <= d.nz; ++p) beam_off[p] = m*first[(size_t)p];
-        if (n_left_out) { n_left_out[0] = m*(first[(size_t)d.nz + 1] - first[(size_t)d.nz]); n_left_out[1] = m*(nd - first[(size_t)d.nz + 1]); }
-        const long nkept = first[(size_t)d.nz];
-        n = m*nkept;
-        if (n == 0) return HPS_OK;
-        HPS_HIP_CHECK(hipMalloc(&d_off, (size_t)(d.nz + 1)*sizeof(long)));
-        HPS_HIP_CHECK(hipMalloc(&d_mm, (size_t)4*d.nz*sizeof(double)));
-        HPS_HIP_CHECK(hipMemcpyAsync(d_off, beam_off.data(), (size_t)(d.nz + 1)*sizeof(long), hipMemcpyHostToDevice, st));
-        HPS_HIP_CHECK(hipMalloc(&blocks, (size_t)7*n*sizeof(double)));
-        const size_t lds = (size_t)std::max(depth_fill - 1, 0)*BI_THREADS*sizeof(double);
-        hipLaunchKernelGGL(k_fwp_fill, dim3(ceil_div(nkept, BI_THREADS)), block, lds, st, a, kb, ib, d_first, nkept, blocks);
-        HPS_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_beam_extent, dim3(d.nz), block, 0, st, blocks, d_off, d_mm);
-        HPS_HIP_CHECK(hipGetLastError());
-        std::vector<double> mm((size_t)4*d.nz);
-        HPS_HIP_CHECK(hipMemcpyAsync(mm.data(), d_mm, mm.size()*sizeof(double), hipMemcpyDeviceToHost, st));
-        HPS_HIP_CHECK(hipStreamSynchronize(st));
-        box[0] = box[2] = inf; box[1] = box[3] = -inf;
-        for (int p = 0; p < d.nz; ++p) {
-            box[0] = std::min(box[0], mm[(size_t)4*p]);     box[1] = std::max(box[1], mm[(size_t)4*p + 1]);
-            box[2] = std::min(box[2], mm[(size_t)4*p + 2]); box[3] = std::max(box[3], mm[(size_t)4*p + 3]);
-        }
-        return HPS_OK;
-    };
-    const int e = run();
-    release();
-    if (e) {                                   // the engine is left without a beam
-        (void)hipFree(blocks); beam_off.assign(d.nz + 1, 0);
-        if (n_left_out) n_left_out[0] = n_left_out[1] = 0;
-        (void)install_beam_device(nullptr, 0, box);
-        return e;
-    }
-    return install_beam_device(blocks, n, box);
+    DevBuf<double> d_tab;
+    if (int e = fwp_upload(image, tab, d_tab)) return drop_device_beam(e, n_left_out);
+    a.ins = image.ins(); a.consts = image.consts(); a.cum = d_tab.get(); a.pe = d_tab.get() + (ns + 1);
+    return fixed_weight_beam(*this, a, nd, a.sym ? 4 : 1, k_fwp_keys, expr_lds_bytes(depth_keys, BI_THREADS), k_fwp_fill,
+                             expr_lds_bytes(depth_fill, BI_THREADS), n_left_out);
 }
 
 } // namespace hps

@@ -37,6 +37,20 @@ __host__ __device__ inline double table_value (const double* x, const double* f,
 #define HPS_REQUIRE(cond, msg)                                                           \
     do { if (!(cond)) { hps::set_error(msg); return HPS_ERR_ARG; } } while (0)
 
+// n elements of device memory for one scope (move-only: the moves delete the copies); release() hands the block to another owner
+template <class T>
+struct DevBuf {
+    DevBuf () = default;
+    DevBuf (DevBuf&& o) noexcept : p(o.release()) {}
+    DevBuf& operator= (DevBuf&& o) noexcept { if (this != &o) { (void)hipFree(p); p = o.release(); } return *this; }
+    ~DevBuf () { (void)hipFree(p); }
+    int alloc (size_t n) { (void)hipFree(p); p = nullptr; HPS_HIP_CHECK(hipMalloc(&p, n*sizeof(T))); return HPS_OK; }
+    T* get () const { return p; }
+    T* release () { T* q = p; p = nullptr; return q; }
+private:
+    T* p = nullptr;
+};
+
 // Slab view usable in device code.  (i,j) are cell indices, guards at negative indices.
 struct SlabView {
     double* p; int nx, ny, ng; long js, ns;

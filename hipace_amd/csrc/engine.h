@@ -3,6 +3,7 @@
 #define HPS_ENGINE_H_
 
 #include "common.h"
+#include "expr.h"
 #include <algorithm>
 #include <array>
 #include <vector>
@@ -44,6 +45,23 @@ struct LaserState;      // laser.hip
 // a density program as a kernel argument: the instructions of the table entry in force and the pooled constants,
 // both on the device, z = c t of the step and <plasma>.min_density.  n_ins = 0: no program
 struct DensityProgram { const hps_expr_ins* ins; int n_ins; const double* consts; double z, min_density; };
+
+// Expression programs packed into one image (expr.hip): on the host the instruction stream -- behind `header_slots` words the
+// owner fills in itself, slot() -- and the pooled constants; after upload() the same two arrays on the device, freed with the
+// image (move-only).
+struct ExprImage {
+    ExprImage () = default;
+    explicit ExprImage (int header_slots) : h_ins((size_t)header_slots, hps_expr_ins{0, 0}) {}
+    int add (const hps_expr& checked);                   // appends a CHECKED program -> offset of its first instruction
+    hps_expr_ins& slot (int q) { return h_ins[(size_t)q]; }
+    int n_ins () const { return (int)h_ins.size(); }
+    int upload ();
+    const hps_expr_ins* ins () const { return d_ins.get(); }
+    const double* consts () const { return d_consts.get(); }
+private:
+    std::vector<hps_expr_ins> h_ins; std::vector<double> h_consts;
+    DevBuf<hps_expr_ins> d_ins; DevBuf<double> d_consts;
+};
 
 struct BeamSoA { double *x, *y, *z, *ux, *uy, *uz, *w; int* nsub;      // moving beam (beam.hip); nsub < 0: absorbed
                  double *sx, *sy, *sz; };                              // spin (do_spin_tracking), null otherwise
@@ -101,10 +119,10 @@ struct Engine {
     bool time_set = false; double next_t = 0.0, next_dt = 0.0, step_dt = 0.0;
     // physical time of the step that has begun (Hipace::m_physical_time): d.dt*step_index, or the t of hps_engine_set_time
     double step_time = 0.0;
-    // beams.external_E / external_B as expression programs (hps_engine_set_beam_external_fields, expr.hip): one
+    // beams.external_E / external_B as expression programs (hps_engine_set_beam_external_fields, beam_ext.hip): one
     // device image -- six {offset, count} header slots (Ex Ey Ez Bx By Bz; count 0: absent), then the instructions -- and
     // the pooled constants; depth = the deepest stack of the six.  on = false: k_beam_push<ORDER, false>, the push as it was.
-    struct BeamExt { bool on = false; hps_expr_ins* d_ins = nullptr; double* d_consts = nullptr; int depth = 0; } bext;
+    struct BeamExt { bool on = false; ExprImage image; int depth = 0; } bext;
     int set_beam_external_fields (const hps_expr* E3, const hps_expr* B3);
     // <plasma>.density(x,y,z) / density_table_file as expression programs (hps_engine_set_density_expr, plasma_init.hip, DESIGN
     // 8m), per species (Species::dens): the species' programs as given (z_pos empty: the one program of density(x,y,z)), the
@@ -112,11 +130,11 @@ struct Engine {
     // of the species' programs, and the entry in force in the step that has begun.  on = false: the tables, the kernels as they were.
     struct DensityExpr { bool on = false; std::vector<std::vector<hps_expr_ins>> ins; std::vector<std::vector<double>> consts;
                          std::vector<double> z_pos; std::vector<int> off; int depth = 0; double min_density = 0.0; int cur = 0; };
-    hps_expr_ins* d_dens_ins = nullptr; double* d_dens_consts = nullptr; double dens_z = 0.0;      // dens_z: c t of the step that has begun
+    ExprImage dens_image; double dens_z = 0.0;      // dens_z: c t of the step that has begun
     int set_density_expr (int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density);
     void density_begin_step (double ct);                  // UpdateDensityFunction(c t): the table entry in force
     DensityProgram density_program (int species) const;   // n_ins = 0: this species keeps the tables
-    size_t density_lds (int species) const { const DensityExpr& D = sp[species].dens; return D.on ? (size_t)std::max(D.depth - 1, 0)*256*sizeof(double) : 0; }
+    size_t density_lds (int species) const { const DensityExpr& D = sp[species].dens; return D.on ? expr_lds_bytes(D.depth, 256) : 0; }
     // One plasma species of the slice: sp[0] the plasma (the electrons), sp[1] the species "ion".  The parameters are the deck's
     // plasma_* / ion_* fields, read once (Engine::create; keyed: the first begin_step); fine_ppc, thermal and dens are what
     // hps_engine_set_plasma_init / _momentum / _density_expr have given.
@@ -268,6 +286,11 @@ struct Engine {
     int set_beam_fixed_weight_pdf (const hps_beam_fixed_weight_pdf* spec, const hps_expr* pdf, const hps_expr* progs, unsigned long long seed,
                                    long* n_left_out, double* uz_moments);
     int install_beam_device (double* blocks_dev, long n, const double box[4]);
+    // ... the three share: everything between "all arguments are checked" and the first allocation; the extent of the n particles
+    // of `blocks` (beam_off filled in) and install_beam_device; the one failure path: the engine is left without a beam, -> e
+    int begin_device_beam (long* n_left_out = nullptr);
+    int finish_device_beam (DevBuf<double>& blocks, long n, long* n_left_out = nullptr);
+    int drop_device_beam (int e, long* n_left_out);
     void release_beam ();                                               // the beam's device storage, ahead of another beam
     void set_beam_box (double xlo, double xhi, double ylo, double yhi);  // beam_box_init from the particles' extent
     int install_moving_beam (const std::vector<double> (*h)[7]);        // the moving beam's storage; h null: filled from beam_init on the device
@@ -331,10 +354,9 @@ int laser_check_samples (Engine& E, const Engine::LaserSamples& S);          // 
 int laser_set_insitu (Engine& E, int on);                                    // the [8][nzl] in-situ buffer and its scratch
 int laser_clear_insitu (Engine& E);
 int laser_copy_insitu (Engine& E, double* out_host);
-// expr.hip: hps_expr_check in the words of fn; "is absent" (no instructions, or the single constant 0); packing into one image
+// expr.hip: hps_expr_check in the words of fn; "is absent" (no instructions, or the single constant 0); packing: ExprImage
 int expr_check_named (const char* fn, const char* what, const hps_expr* p, int n_vars, int* depth);
 bool expr_is_zero (const hps_expr& p);
-int expr_append (const hps_expr& p, std::vector<hps_expr_ins>& ins, std::vector<double>& consts);
 int beam_blocks_to_soa (Engine& E, const double* blocks, double* soa, long nb);      // beam_init.hip: slice-major blocks -> global SoA (beam_off)
 int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz);      // beam.hip
 int beam_push_moving (Engine& E, int islice);

@@ -345,13 +345,13 @@ Engine::~Engine ()
     delete el.tiling;
     (void)hipFree(staging); (void)hipFree(d_open_mom); (void)hipFree(beam_data); (void)hipFree(beam_init);
     (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr); (void)hipFree(d_B); (void)hipFree(d_nfront);
-    (void)hipFree(d_mom); (void)hipFree(d_sal); (void)hipFree(bext.d_ins); (void)hipFree(bext.d_consts);
+    (void)hipFree(d_mom); (void)hipFree(d_sal);
     (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow); (void)hipFree(d_nqsa); (void)hipFree(d_checksum);
     (void)hipFree(d_pc); (void)hipFree(d_pc_aux); (void)hipFree(d_pc_go); if (h_pc) (void)hipHostFree(h_pc);
     (void)hipFree(d_laser_sum);
     if (laser) laser_destroy(*this);
     ion_destroy(*this);
-    (void)hipFree(d_prof_r); (void)hipFree(d_fine_level); (void)hipFree(d_fine_cells); (void)hipFree(d_dens_ins); (void)hipFree(d_dens_consts);
+    (void)hipFree(d_prof_r); (void)hipFree(d_fine_level); (void)hipFree(d_fine_cells);
     (void)hipFree(d_fd); (void)hipFree(d_fd_comps); (void)hipFree(d_insitu); (void)hipFree(d_insitu_pl); (void)hipFree(d_insitu_bm);
     for (auto e : ev) (void)hipEventDestroy(e);
     for (auto e : hand_ev) if (e) (void)hipEventDestroy(e);

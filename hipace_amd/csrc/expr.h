@@ -71,6 +71,8 @@ struct ExprArrayVars {
     const double* const* p; long i;
     __host__ __device__ double get (int k) const { return p[k][i]; }
 };
+// dynamic LDS of a workgroup of `threads` lanes running programs of at most `depth` levels: the levels below the top (ExprLdsStack)
+inline size_t expr_lds_bytes (int depth, int threads) { return (size_t)(depth > 1 ? depth - 1 : 0)*threads*sizeof(double); }
 #ifdef __HIPCC__
 // device stack: base = this lane's slot of level 0, stride = lanes of the workgroup
 struct ExprLdsStack {

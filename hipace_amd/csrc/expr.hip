@@ -1,8 +1,6 @@
 // expr.hip -- the C entry points of the expression programs (include/hpslice.h): the check, the host evaluation,
-// the stand-alone device operator, and the packing of several programs into the one device image the beam push reads.
-#include "common.h"
-#include "expr.h"
-#include <vector>
+// the stand-alone device operator, and ExprImage: the packing of several programs into one image and its upload.
+#include "engine.h"
 
 namespace hps {
 
@@ -35,18 +33,27 @@ bool expr_is_zero (const hps_expr& p)
                             p.ins[0].arg < p.n_const && p.consts[p.ins[0].arg] == 0.0);
 }
 
-// appends a CHECKED program to one image: its constants behind the pool's, its instructions (constant indices rebased)
-// behind the stream's; -> offset of its first instruction
-int expr_append (const hps_expr& p, std::vector<hps_expr_ins>& ins, std::vector<double>& consts)
+// its constants behind the pool's, its instructions (constant indices rebased) behind the stream's
+int ExprImage::add (const hps_expr& p)
 {
-    const int off = (int)ins.size(), base = (int)consts.size();
-    consts.insert(consts.end(), p.consts, p.consts + p.n_const);
+    const int off = (int)h_ins.size(), base = (int)h_consts.size();
+    h_consts.insert(h_consts.end(), p.consts, p.consts + p.n_const);
     for (int i = 0; i < p.n_ins; ++i) {
         hps_expr_ins q = p.ins[i];
         if (q.op == HPS_EX_CONST) q.arg += base;
-        ins.push_back(q);
+        h_ins.push_back(q);
     }
     return off;
+}
+
+// (neither device array is ever empty: a program without constants still gets a pool to point at)
+int ExprImage::upload ()
+{
+    if (int e = d_ins.alloc(std::max<size_t>(h_ins.size(), 1))) return e;
+    if (int e = d_consts.alloc(std::max<size_t>(h_consts.size(), 1))) return e;
+    if (!h_ins.empty()) HPS_HIP_CHECK(hipMemcpy(d_ins.get(), h_ins.data(), h_ins.size()*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
+    if (!h_consts.empty()) HPS_HIP_CHECK(hipMemcpy(d_consts.get(), h_consts.data(), h_consts.size()*sizeof(double), hipMemcpyHostToDevice));
+    return HPS_OK;
 }
 
 } // namespace hps
@@ -91,7 +98,7 @@ extern "C" int hps_expr_eval (const hps_expr* prog, int n_vars, long n, const do
     if (err == hipSuccess) err = hipMemcpy(image + const_bytes + ins_bytes, ptrs, sizeof(ptrs), hipMemcpyHostToDevice);
     if (err == hipSuccess) {
         const unsigned blocks = (unsigned)std::min<long>(ceil_div(n, 256), 2048);
-        const size_t lds = (size_t)std::max(depth - 1, 0)*256*sizeof(double);
+        const size_t lds = expr_lds_bytes(depth, 256);
         hipLaunchKernelGGL(k_expr_eval, dim3(blocks), dim3(256), lds, st, (const hps_expr_ins*)(image + const_bytes), prog->n_ins,
                            (const double*)image, (const double* const*)(image + const_bytes + ins_bytes), out_dev, n);
         err = hipGetLastError();

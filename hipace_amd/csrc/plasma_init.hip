@@ -353,23 +353,17 @@ int Engine::set_density_expr (int species, int n_progs, const hps_expr* progs, c
     }
     if (z_pos) D.z_pos.assign(z_pos, z_pos + n_progs);
     D.depth = depth; D.min_density = min_density; D.on = true;
-    std::vector<hps_expr_ins> ins;
-    std::vector<double> consts;
+    ExprImage image;
     for (Species& q : sp) {
         DensityExpr& S = q.dens;
         S.off.clear();
-        for (size_t k = 0; k < S.ins.size(); ++k) {
-            const hps_expr p{(int)S.ins[k].size(), (int)S.consts[k].size(), S.ins[k].data(), S.consts[k].data()};
-            S.off.push_back(expr_append(p, ins, consts));
-        }
+        for (size_t k = 0; k < S.ins.size(); ++k)
+            S.off.push_back(image.add(hps_expr{(int)S.ins[k].size(), (int)S.consts[k].size(), S.ins[k].data(), S.consts[k].data()}));
     }
-    if (consts.empty()) consts.push_back(0.0);
     HPS_HIP_CHECK(hipStreamSynchronize(st));
-    (void)hipFree(d_dens_ins); (void)hipFree(d_dens_consts); d_dens_ins = nullptr; d_dens_consts = nullptr;
-    HPS_HIP_CHECK(hipMalloc(&d_dens_ins, ins.size()*sizeof(hps_expr_ins)));
-    HPS_HIP_CHECK(hipMalloc(&d_dens_consts, consts.size()*sizeof(double)));
-    HPS_HIP_CHECK(hipMemcpy(d_dens_ins, ins.data(), ins.size()*sizeof(hps_expr_ins), hipMemcpyHostToDevice));
-    HPS_HIP_CHECK(hipMemcpy(d_dens_consts, consts.data(), consts.size()*sizeof(double), hipMemcpyHostToDevice));
+    dens_image = ExprImage{};
+    if (int e = image.upload()) return e;
+    dens_image = std::move(image);
     return HPS_OK;
 }
 
@@ -390,7 +384,7 @@ DensityProgram Engine::density_program (int species) const
 {
     const DensityExpr& S = sp[species].dens;
     if (!S.on) return DensityProgram{nullptr, 0, nullptr, 0.0, 0.0};
-    return DensityProgram{d_dens_ins + S.off[S.cur], (int)S.ins[S.cur].size(), d_dens_consts, dens_z, S.min_density};
+    return DensityProgram{dens_image.ins() + S.off[S.cur], (int)S.ins[S.cur].size(), dens_image.consts(), dens_z, S.min_density};
 }
 
 } // namespace hps

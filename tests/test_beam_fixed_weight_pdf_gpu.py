@@ -323,3 +323,59 @@ def test_transverse_benchmark_with_the_parsed_beam(api):
     bnda, soaa = a.beam_state()
     bndb, soab = b.beam_state()
     _slices_as_sets(bnda, soaa, bndb, soab, deck["nz"])
+
+
+# ---- 7. the prologue and the tail that the three device generators share --------------------------------------------------------
+
+def _installed(eng):
+    """what the engine holds of its beam: count, offsets, the beam as it is now (the moving beam's storage with hipace.dt != 0)
+    and the injected blocks"""
+    import torch
+    n, off = eng.beam_layout()
+    bnd, soa = eng.beam_state()
+    blocks = torch.zeros(7 * max(n, 1), dtype=torch.float64, device="cuda")
+    if n:
+        eng.initial_beam_into(blocks)
+    return n, off, bnd, soa, blocks.cpu().numpy()[:7 * n]
+
+
+@pytest.mark.parametrize("dt", [0.0, 0.5])
+def test_one_engine_takes_every_generator_in_turn(api, dt):
+    """fixed_ppc, fixed_weight (257), fixed_weight_pdf (65), a fixed_weight beam whose zmin / zmax cut every draw away (n = 0) and
+    fixed_ppc again on ONE engine: after every call the engine holds exactly what a fresh engine holds after the same call alone
+    -- nothing of the beam before it is left in the offsets, the blocks, the moving beam's storage or the left-out counts.  The C
+    ABI does not show the beam's box; for the static beam the step at the end deposits inside it on both engines (the deposited
+    currents agree to 1e-9, the order of the atomic additions; a box of another beam would cut the current off)."""
+    from tests import beam_fixed_weight_reference as F
+    deck = dict(R.small_deck(), dt=dt, beam_ppc=(2, 2, 1), beam_radius=0.9, beam_pos_mean=(0.1, -0.1, 0.0), beam_zmin=-0.5,
+                beam_zmax=0.7, beam_umean=(0.0, 0.0, 100.0))
+    fw = dict(F.cases()["size_257"][1])
+    steps = [("fixed_ppc", lambda e: e.set_beam_fixed_ppc("1 + 0.5*x", u_std=(0.2, 0.0, 1.0), random_ppc=(1, 0, 0), seed=3)),
+             ("fixed_weight", lambda e: e.set_beam_fixed_weight(**fw)),
+             ("fixed_weight_pdf", lambda e: e.set_beam_fixed_weight_pdf(**CASES["size_65"][1])),
+             ("nothing", lambda e: e.set_beam_fixed_weight(**dict(fw, zmin=5.0, zmax=6.0)))]
+    steps.append(steps[0])
+    fresh = {}
+    eng = api.SliceEngine(deck, tile_size=0)
+    for name, call in steps:
+        if name not in fresh:
+            other = api.SliceEngine(deck, tile_size=0)
+            fresh[name] = (call(other), _installed(other), other)
+        left = call(eng)
+        want_left, want, _ = fresh[name]
+        got = _installed(eng)
+        assert left == want_left, (name, left, want_left)
+        assert got[0] == want[0], (name, got[0], want[0])
+        for a, b in zip(got[1:], want[1:]):
+            assert np.array_equal(a, b), name
+    assert fresh["fixed_ppc"][1][0] > 100 and fresh["fixed_weight"][0] != (0, 0) and 0 < fresh["fixed_weight"][1][0] < 257
+    assert fresh["fixed_weight_pdf"][1][0] == 65 and fresh["nothing"][0] == (257, 0) and fresh["nothing"][1][0] == 0
+    if dt == 0.0:
+        other = fresh["fixed_ppc"][2]
+        for e in (eng, other):
+            e.set_diagnostics(True)
+            e.run_step()
+        ca, cb = eng.checksums(), other.checksums()
+        assert cb["jz_beam"] != 0.0
+        for k in ("jx_beam", "jy_beam", "jz_beam"):
+            assert abs(ca[k] - cb[k]) <= 1e-9 * max(abs(cb[k]), 1e-300), (k, ca[k], cb[k])
