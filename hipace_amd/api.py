@@ -1329,7 +1329,9 @@ class SliceEngine:
     def stats(self):
         vc, sl = C.c_long(), C.c_long()
         check(_lib.lib().hps_engine_stats(self._h, C.byref(vc), C.byref(sl)))
-        return dict(vcycles=vc.value, slices=sl.value)
+        ei = C.c_long()      # slices whose shift / zero pass rode in the Bx/By solve's lower V (HPS_EARLY_INIT)
+        check(_lib.lib().hps_engine_early_init_slices(self._h, C.byref(ei)))
+        return dict(vcycles=vc.value, slices=sl.value, early_init=ei.value)
 
     def slab(self):
         self.sync()

@@ -31,6 +31,9 @@ int mg_solve1_prepare (void* mg_handle, hps_slab s, int sol_comp, int rhs_comp, 
 // hierarchy needs more than that launch (then nothing has been enqueued)
 int mg_solve1_prepare_with (void* mg_handle, hps_slab s, int sol_comp, int rhs_comp, int acf_comp, int max_iters, SlabView f, GradPsiSxSy ga,
                             hipStream_t st, bool* done);
+// the slab's shift / zero pass for the next slice as guest workgroups of the next mg_solve1_begin's first lower V; false: this
+// grid's lower V takes no guests (nothing will be done)
+bool mg_ride_shift_init (void* mg_handle, const ShiftInit& pass);
 const int* mg_gate_after_enqueued (void* mg_handle);
 void mg_defer_post (void* mg_handle);
 bool mg_take_deferred_post (void* mg_handle, MgPost* out);
@@ -305,7 +308,15 @@ struct Engine {
     int push_with_ionization (int islice, const int comp[5], const int* go, bool first);
     bool lazy_shift = true, shift_pending = false;      // ShiftSlices deferred to the next slice's InitializeSlices pass (HPS_LAZY_SHIFT=0: off)
     void flush_shift ();
-    bool fuse_sources = true;       // the Poisson sources formed inside the first transform pass (HPS_FUSE_SOURCES=0: k_rhs_all + staging planes)
+    // HPS_EARLY_INIT (=0: off): on the plain path the next slice's shift / zero pass rides in the launch of the Bx/By solve's first
+    // lower V (mg_ride_shift_init).  The planes it re-initialises have an alternate behind the slab's own (n_alt of them, not
+    // counted by hps_engine_slab) and the slices take turns: `live` = the set this slice deposits into.  init_done: the live set
+    // holds the next slice's zeros and the shift is done, the slice just solved is in the other set.
+    bool early_init = true; int n_alt = 0; InitSet set_canon{}, set_alt{};
+    bool alt_live = false, init_done = false, pend_rode = false; long slices_rode = 0;
+    const InitSet& live () const { return alt_live ? set_alt : set_canon; }
+    const InitSet& other () const { return alt_live ? set_canon : set_alt; }
+    bool fuse_sources = true;      // the Poisson sources formed inside the first transform pass (HPS_FUSE_SOURCES=0: k_rhs_all + staging planes)
     // <beam>.do_salame (salame/Salame.cpp): c_sal = first of the HPS_SAL_NCOMP planes behind the engine's own (-1: none);
     // state of the run of consecutive slices (Hipace::m_salame_last_slice, m_salame_overloaded, m_salame_zeta_initial);
     // d_sal = scratch of the W reduction; sal_stats = [nz][4] {W, W_total, iterations, flags}

@@ -76,7 +76,7 @@ void k_copy_comps (double* p, long ns, long plane, CompList dst, CompList src)
 // ShiftSlices (fields/Fields.cpp:588-604): Previous <- This <- Next for the beam currents, jx, jy <- Next.
 // The beam planes are zero outside the box: there only jx = jy = 0 is written.
 __global__ __launch_bounds__(256)
-void k_shift_slices (double* p, long ns, long plane, int js, CellBox bb)
+void k_shift_slices (double* p, long ns, long plane, int js, CellBox bb, int c_njxb, int c_njyb)
 {
     const long s = (long)blockIdx.x*blockDim.x + threadIdx.x;
     if (s >= plane) return;
@@ -84,7 +84,7 @@ void k_shift_slices (double* p, long ns, long plane, int js, CellBox bb)
     double njx = 0.0, njy = 0.0;
     if (i >= bb.ilo && i <= bb.ihi && j >= bb.jlo && j <= bb.jhi) {
         const double tjx = p[HPS_C_JXB*ns + s], tjy = p[HPS_C_JYB*ns + s];
-        njx = p[HPS_C_N_JXB*ns + s]; njy = p[HPS_C_N_JYB*ns + s];
+        njx = p[c_njxb*ns + s]; njy = p[c_njyb*ns + s];
         p[HPS_C_P_JXB*ns + s] = tjx; p[HPS_C_P_JYB*ns + s] = tjy;
         p[HPS_C_JXB*ns + s] = njx;   p[HPS_C_JYB*ns + s] = njy;
     }
@@ -93,25 +93,14 @@ void k_shift_slices (double* p, long ns, long plane, int js, CellBox bb)
 
 // ShiftSlices (fields/Fields.cpp:588-604) of this slice AND InitializeSlices (:535-586) of the next one in one pass: what
 // the fused push + deposition (k_advance_deposit_tiled) needs done before it deposits into the next slice's jx jy chi
-// rhomjz [rho].  Inside the beam's box also jz_beam and the Next beam currents are cleared.
+// rhomjz [rho].  Inside the beam's box also jz_beam and the Next beam currents are cleared.  (shift_init_cell, slab_ops.h: the
+// same pass rides in the multigrid's lower V where the slice allows it, HPS_EARLY_INIT)
 __global__ __launch_bounds__(256)
-void k_shift_zero (double* p, long ns, long plane, int js, CellBox bb, int c_rho, int c_ion = -1)
+void k_shift_zero (ShiftInit a)
 {
     const long s = (long)blockIdx.x*blockDim.x + threadIdx.x;
-    if (s >= plane) return;
-    const int j = (int)(s / js), i = (int)(s - (long)j*js);
-    double njx = 0.0, njy = 0.0;
-    if (i >= bb.ilo && i <= bb.ihi && j >= bb.jlo && j <= bb.jhi) {
-        const double tjx = p[HPS_C_JXB*ns + s], tjy = p[HPS_C_JYB*ns + s];
-        njx = p[HPS_C_N_JXB*ns + s]; njy = p[HPS_C_N_JYB*ns + s];
-        p[HPS_C_P_JXB*ns + s] = tjx; p[HPS_C_P_JYB*ns + s] = tjy;
-        p[HPS_C_JXB*ns + s] = njx;   p[HPS_C_JYB*ns + s] = njy;
-        p[HPS_C_N_JXB*ns + s] = 0.0; p[HPS_C_N_JYB*ns + s] = 0.0; p[HPS_C_JZB*ns + s] = 0.0;
-    }
-    p[HPS_C_JX*ns + s] = njx; p[HPS_C_JY*ns + s] = njy;
-    const double ion = c_ion >= 0 ? p[c_ion*ns + s] : 0.0;      // AddRhoIons ahead of the deposition (see k_zero_comps)
-    p[HPS_C_CHI*ns + s] = 0.0; p[HPS_C_RHOMJZ*ns + s] = ion;
-    if (c_rho >= 0) p[c_rho*ns + s] = ion;
+    if (s >= a.plane) return;
+    shift_init_cell(a, s);
 }
 
 // AddRhoIons (fields/Fields.cpp:606-615) fused with the Psi source  -rhomjz/ep0  (:887-888)
@@ -759,6 +748,7 @@ int Engine::create (const hps_deck& deck, int device)
     if (const char* v = std::getenv("HPS_GATED_ION_PUSH")) gate_ion_push = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_LAZY_SHIFT")) lazy_shift = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_FUSE_SOURCES")) fuse_sources = std::atoi(v) != 0;
+    if (const char* v = std::getenv("HPS_EARLY_INIT")) early_init = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_SORT_FALLBACK_DIV")) { const long q = std::atol(v); if (q >= 1) fallback_div = q; }
     HPS_REQUIRE(!(d.beam_spin_tracking && d.dt == 0.0 && !d.dt_adaptive), "hps_engine_create: spin tracking needs a moving beam (hipace.dt != 0)");
     HPS_REQUIRE(!(d.dt_adaptive && d.laser_on), "hps_engine_create: hipace.dt = adaptive cannot be used with a laser (Hipace.cpp:408)");
@@ -817,6 +807,15 @@ int Engine::create (const hps_deck& deck, int device)
         sal_stats.assign((size_t)4*d.nz, 0.0);
     }
     slab.nx = d.nx; slab.ny = d.ny; slab.ng = g; slab.ncomp = ncomp + (c_sal >= 0 ? (int)HPS_SAL_NCOMP : 0);
+    // the alternates of the re-initialised planes (HPS_EARLY_INIT), behind everything else; only decks whose slices can take the
+    // plain path have them (the multigrid's lower V is known further down: a grid it does not suit keeps them unused)
+    set_canon = set_alt = InitSet{HPS_C_CHI, HPS_C_RHOMJZ, d.deposit_rho ? (int)HPS_C_RHO : -1, HPS_C_JZB, HPS_C_N_JXB, HPS_C_N_JYB};
+    if (early_init && !pc && !d.laser_on && !d.ion_on && d.dt == 0.0 && !d.dt_adaptive && d.nx % 2 == 0 && d.ny % 2 == 0) {
+        int c = slab.ncomp;
+        set_alt.chi = c++; set_alt.rhomjz = c++; if (d.deposit_rho) set_alt.rho = c++;
+        set_alt.jzb = c++; set_alt.njxb = c++; set_alt.njyb = c++;
+        n_alt = c - slab.ncomp; slab.ncomp = c;
+    }
     slab.jstride = d.nx + 2*g; slab.nstride = slab.jstride*(d.ny + 2*g);
     HPS_HIP_CHECK(hipMalloc(&slab.p, (size_t)slab.nstride*slab.ncomp*sizeof(double)));
     HPS_HIP_CHECK(hipMemset(slab.p, 0, (size_t)slab.nstride*slab.ncomp*sizeof(double)));
@@ -989,6 +988,7 @@ int Engine::begin_step ()
         ++steps_begun;
     }
     shift_pending = false;      // (the slab is cleared whole below)
+    alt_live = false; init_done = false; pend_rode = false;      // (... the alternate planes too: the step starts on the slab's own)
     // ResetAllQuantities (Hipace.cpp:730-742)
     HPS_HIP_CHECK(hipMemsetAsync(slab.p, 0, (size_t)slab.nstride*slab.ncomp*sizeof(double), st));
     // predictor-corrector: nothing but the cold plasma has been deposited in this sweep yet.  Not so from the first slice on
@@ -1826,12 +1826,29 @@ int Engine::solve_slice_pc_finish (int islice)
 // device, hps_engine_solve_slice_begin / _finish): begin enqueues everything up to and including the speculated V-cycles of
 // the Bx/By solve (and the gated push behind them) and returns without waiting for the device; finish waits for the
 // solve's norms -- the one host wait of a slice -- and enqueues the rest.  solve_slice = begin + finish.
+// Makes the slab what an observer expects: the pending shift done, the slice just solved on the slab's own planes.
+// (HPS_EARLY_INIT: that slice is in the alternate planes if it ran on them and its pass did not ride, or if it ran on the slab's
+//  own and its pass rode -- then those hold the next slice's zeros.  Either way the two sets change places, the zeros with
+//  them: the next slice finds them where `live` then points, and a run that goes on is not disturbed.)
 void Engine::flush_shift ()
 {
-    if (!shift_pending) return;
-    shift_pending = false;
-    const CellBox bb{beam_box.ilo, beam_box.ihi, beam_box.jlo, beam_box.jhi};
-    hipLaunchKernelGGL(k_shift_slices, dim3(ceil_div(slab.nstride, 256)), dim3(256), 0, st, slab.p, slab.nstride, slab.nstride, (int)slab.jstride, bb);
+    const dim3 gplane(ceil_div(slab.nstride, 256)), b256(256);
+    if (shift_pending) {
+        shift_pending = false;
+        const CellBox bb{beam_box.ilo, beam_box.ihi, beam_box.jlo, beam_box.jhi};
+        hipLaunchKernelGGL(k_shift_slices, gplane, b256, 0, st, slab.p, slab.nstride, slab.nstride, (int)slab.jstride, bb, live().njxb, live().njyb);
+    }
+    if (alt_live != init_done) {
+        CompList a{0, {}}, b{0, {}};
+        for (int k = 0; k < 2; ++k) {
+            const InitSet& x = k ? set_alt : set_canon; CompList& l = k ? b : a;
+            for (int c : {x.chi, x.rhomjz, x.rho, x.jzb, x.njxb, x.njyb}) if (c >= 0) l.c[l.n++] = c;
+        }
+        CompList dst = a, src = b;       // dst = own | alternate, src = alternate | own
+        for (int k = 0; k < b.n; ++k) { dst.c[dst.n++] = b.c[k]; src.c[src.n++] = a.c[k]; }
+        hipLaunchKernelGGL(k_copy_comps, gplane, b256, 0, st, slab.p, slab.nstride, slab.nstride, dst, src);
+        alt_live = !alt_live;
+    }
 }
 
 int Engine::solve_slice (int islice)
@@ -1863,23 +1880,34 @@ int Engine::solve_slice_begin (int islice)
     // plasma currents (k_shift_zero + k_advance_deposit_tiled)
     const bool ahead = (ahead_for == islice);
     ahead_for = -2;
+    // HPS_EARLY_INIT: a slice of the plain path -- nothing but the kernels below and the push touches the re-initialised planes --
+    // runs on whichever set of them is live; any other slice runs on the slab's own, with the zeroing pass of its own
+    const bool plain = n_alt > 0 && !moving && coll.empty() && c_aabs < 0 && !ions.present() && !salame_now() && !fuse_push_deposit && !ahead
+                       && lazy_shift && !aux_on && !diagnostics && !d_fd && !d_insitu;
+    if (!plain && (alt_live || init_done)) {
+        flush_shift();
+        alt_live = false; init_done = false;      // (zeros left in the alternate planes are dropped)
+    }
+    const InitSet L = live();
     // ShiftSlices of the slice before, left pending at its end (lazy_shift), and this slice's InitializeSlices in one pass
-    bool zeroed = false;
+    // (init_done: both have ridden in the previous slice's Bx/By solve)
+    bool zeroed = init_done;
+    init_done = false;
     if (shift_pending) {
         shift_pending = false;
-        if (!ahead) { hipLaunchKernelGGL(k_shift_zero, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb, d.deposit_rho ? (int)HPS_C_RHO : -1, (int)HPS_C_ION_RHOMJZ); zeroed = true; }
-        else hipLaunchKernelGGL(k_shift_slices, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb);
+        if (!ahead) { hipLaunchKernelGGL(k_shift_zero, gplane, b256, 0, st, ShiftInit{slab.p, slab.nstride, plane, (int)slab.jstride, bb, L, L, (int)HPS_C_ION_RHOMJZ}); zeroed = true; }
+        else hipLaunchKernelGGL(k_shift_slices, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb, L.njxb, L.njyb);
     }
     if (!ahead && !zeroed)
     {   CompList z{0, {}}, zb{0, {}};
         // Sx, Sy are written as whole planes by k_sxsy_beam; ExmBy, EypBx by k_grad_psi up to the outermost
         // guard ring, which nothing ever writes (it keeps the zeros of begin_step); the beam planes only
         // ever hold values inside the beam's box
-        for (int c : {HPS_C_CHI, HPS_C_RHOMJZ}) z.c[z.n++] = c;
-        if (d.deposit_rho) z.c[z.n++] = HPS_C_RHO;
-        for (int c : {HPS_C_JZB, HPS_C_N_JXB, HPS_C_N_JYB}) zb.c[zb.n++] = c;
+        for (int c : {L.chi, L.rhomjz}) z.c[z.n++] = c;
+        if (d.deposit_rho) z.c[z.n++] = L.rho;
+        for (int c : {L.jzb, L.njxb, L.njyb}) zb.c[zb.n++] = c;
         CompList fi{0, {}};
-        fi.c[fi.n++] = HPS_C_RHOMJZ; if (d.deposit_rho) fi.c[fi.n++] = HPS_C_RHO;
+        fi.c[fi.n++] = L.rhomjz; if (d.deposit_rho) fi.c[fi.n++] = L.rho;
         hipLaunchKernelGGL(k_zero_comps, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, z, zb, bb, fi, (int)HPS_C_ION_RHOMJZ); }
     if (c_aabs >= 0) {
         // UpdateLaserAabs (Hipace.cpp:603)
@@ -1914,12 +1942,12 @@ int Engine::solve_slice_begin (int islice)
         bw.a = BeamView{pa, pa + cA, pa + 2*cA, pa + 3*cA, pa + 4*cA, pa + 5*cA, pa + 6*cA};
         bw.b = BeamView{pb, pb + cB, pb + 2*cB, pb + 3*cB, pb + 4*cB, pb + 5*cB, pb + 6*cB};
         bw.ca = cA; bw.cb = cB; bw.nba = (int)ceil_div(cA, 256); bw.nwg = bw.nba + (int)ceil_div(cB, 256);
-        bw.cjz = HPS_C_JZB; bw.cjxn = HPS_C_N_JXB; bw.cjyn = HPS_C_N_JYB;
+        bw.cjz = L.jzb; bw.cjxn = L.njxb; bw.cjyn = L.njyb;
         bw.q_invvol = d.beam_charge*(d.si_units ? 1.0/(gm.dx*gm.dy*gm.dz) : 1.0); bw.csq_inv = 1.0/(gm.c*gm.c);
     }
     const bool beam_folded = pair && fold_beam && bw.nwg > 0 && !ahead && el.pl.n > 0 && el.tiling && el.tiling->sorted_n > 0;
     if (!ahead)
-    {   const int comp[6] = {HPS_C_JX, HPS_C_JY, -1, d.deposit_rho ? HPS_C_RHO : -1, HPS_C_CHI, HPS_C_RHOMJZ};
+    {   const int comp[6] = {HPS_C_JX, HPS_C_JY, -1, L.rho, L.chi, L.rhomjz};
         if ((e = species_deposit(el, comp, beam_folded ? &bw : nullptr))) return e;
         // MultiPlasma::DepositCurrent: every species in turn (MultiPlasma.cpp:78-87); an ion weighs in with its level
         if ((e = species_deposit(ions, comp))) return e; }
@@ -1932,12 +1960,12 @@ int Engine::solve_slice_begin (int islice)
             switch (d.order) { case 0: HPS_PAIR(0); break; case 1: HPS_PAIR(1); break; case 2: HPS_PAIR(2); break; default: HPS_PAIR(3); break; }
 #undef HPS_PAIR
         }
-    } else if ((e = deposit_beam_slice(islice, -1, -1, HPS_C_JZB))) return e;
-    deposit_grid_current(islice, HPS_C_JZB);
+    } else if ((e = deposit_beam_slice(islice, -1, -1, L.jzb))) return e;
+    deposit_grid_current(islice, L.jzb);
     if (aux) {
         // chi is final: the multigrid's coefficient hierarchy on the auxiliary stream, joined ahead of the Sx/Sy initialisation
         HPS_HIP_CHECK(hipEventRecord(ev_aux[1], st)); HPS_HIP_CHECK(hipStreamWaitEvent(st_aux, ev_aux[1], 0));
-        if ((e = mg_solve1_prepare(mg, slab, HPS_C_BX, HPS_C_SY, HPS_C_CHI, 200, st_aux))) return e;
+        if ((e = mg_solve1_prepare(mg, slab, HPS_C_BX, HPS_C_SY, L.chi, 200, st_aux))) return e;
         HPS_HIP_CHECK(hipEventRecord(ev_aux[2], st_aux));
         aux_pending = true;
     }
@@ -1950,7 +1978,7 @@ int Engine::solve_slice_begin (int islice)
             // the three sources (fields/Fields.cpp:887-912) are formed by the first transform pass while it loads its rows:
             // -rhomjz/ep0;  (d_x jx + d_y jy)/(ep0 c);  mu0 (d_y jx - d_x jy) -- centred differences, guard cells read as they are
             const long js = slab.jstride;
-            const double* R = slab.p + (long)HPS_C_RHOMJZ*slab.nstride + g + (long)g*js;       // cell (0, 0) of the planes
+            const double* R = slab.p + (long)L.rhomjz*slab.nstride + g + (long)g*js;       // cell (0, 0) of the planes
             const double* X = slab.p + (long)HPS_C_JX*slab.nstride + g + (long)g*js;
             const double* Y = slab.p + (long)HPS_C_JY*slab.nstride + g + (long)g*js;
             const PoissonSrc spec[3] = {
@@ -1959,8 +1987,8 @@ int Engine::solve_slice_begin (int islice)
                 {2, {X + js, Y + 1}, {X - js, Y - 1}, {fbz_y, fbz_x}}};
             if ((e = poisson_solve_batch_src(ps, 3, spec, js, slab, comps, st))) return e;
         } else {
-            hipLaunchKernelGGL(k_rhs_all, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, HPS_C_RHOMJZ,
-                               -1 /* AddRhoIons: done by the slice's zeroing pass */, d.deposit_rho ? HPS_C_RHO : -1, HPS_C_JX, HPS_C_JY, 1.0/gm.ep0,
+            hipLaunchKernelGGL(k_rhs_all, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, L.rhomjz,
+                               -1 /* AddRhoIons: done by the slice's zeroing pass */, L.rho, HPS_C_JX, HPS_C_JY, 1.0/gm.ep0,
                                fez_x, fez_y, fbz_y, fbz_x, staging, (long)d.nx*d.ny);
             if ((e = open_boundary(3, 0x6u))) return e;
             if ((e = hps_poisson_solve_batch(ps, 3, staging, slab, comps, st))) return e;
@@ -1980,13 +2008,13 @@ int Engine::solve_slice_begin (int islice)
     if (aux_pending) { HPS_HIP_CHECK(hipStreamWaitEvent(st, ev_aux[2], 0)); aux_pending = false; }
     if (pair || nbeam == 0) {
         // -grad Psi and the beam part of Sx, Sy (Hipace.cpp:659-660) in one pass (without a beam there is no deposition between them either)
-        const GradPsiSxSy ga{HPS_C_PSI, HPS_C_EXMBY, HPS_C_EYPBX, 0.5*(1.0/gm.dx), 0.5*(1.0/gm.dy), HPS_C_SX, HPS_C_SY, HPS_C_JZB, HPS_C_N_JXB, HPS_C_N_JYB,
+        const GradPsiSxSy ga{HPS_C_PSI, HPS_C_EXMBY, HPS_C_EYPBX, 0.5*(1.0/gm.dx), 0.5*(1.0/gm.dy), HPS_C_SX, HPS_C_SY, L.jzb, L.njxb, L.njyb,
                              HPS_C_P_JXB, HPS_C_P_JYB, gm.mu0, 2.0*gm.dx, 2.0*gm.dy, 2.0*gm.dz, bb};
         // ... and, in the same launch, the coefficient hierarchy of the Bx/By multigrid solve (it needs chi only): one launch less
         // on the chain between the explicit deposition and the first smoothing pass
         bool with_hierarchy = false;
         if (fold_hierarchy && !pc && !aux) {
-            if ((e = mg_solve1_prepare_with(mg, slab, HPS_C_BX, HPS_C_SY, HPS_C_CHI, 200, f, ga, st, &with_hierarchy))) return e;
+            if ((e = mg_solve1_prepare_with(mg, slab, HPS_C_BX, HPS_C_SY, L.chi, 200, f, ga, st, &with_hierarchy))) return e;
         }
         if (!with_hierarchy)
             hipLaunchKernelGGL(k_gradpsi_sxsy, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, ga);
@@ -1996,8 +2024,8 @@ int Engine::solve_slice_begin (int islice)
                            HPS_C_EXMBY, HPS_C_EYPBX, 0.5*(1.0/gm.dx), 0.5*(1.0/gm.dy));
         mark();   // b3
         // beam jx, jy of the next slice; beam part of Sx, Sy (Hipace.cpp:656-660)
-        if (!sal) { if ((e = deposit_beam_slice(islice - 1, HPS_C_N_JXB, HPS_C_N_JYB, -1))) return e; }
-        hipLaunchKernelGGL(k_sxsy_beam, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, HPS_C_SX, HPS_C_SY, HPS_C_JZB, HPS_C_N_JXB, HPS_C_N_JYB,
+        if (!sal) { if ((e = deposit_beam_slice(islice - 1, L.njxb, L.njyb, -1))) return e; }
+        hipLaunchKernelGGL(k_sxsy_beam, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, HPS_C_SX, HPS_C_SY, L.jzb, L.njxb, L.njyb,
                            HPS_C_P_JXB, HPS_C_P_JYB, gm.mu0, 2.0*gm.dx, 2.0*gm.dy, 2.0*gm.dz, bb);
     }
     mark();   // b4
@@ -2021,7 +2049,11 @@ int Engine::solve_slice_begin (int islice)
         // the plain gated push also posts the solve's norms to the host (k_advance_tiled's MgPost): no k_post_norms launch between
         // the last V-cycle and the push (HPS_POST_IN_PUSH=0: the launch of its own)
         if (gated && post_in_push) mg_defer_post(mg);
-        if ((e = mg_solve1_begin(mg, slab, HPS_C_BX, HPS_C_SY, HPS_C_CHI, d.mg_tol_rel, d.mg_tol_abs, 200, st))) return e;
+        // the plain gated slice: nothing from here to its end reads what the next slice's shift / zero pass overwrites -- it rides
+        // in the first lower V of the solve, writing the zeros to the set of planes that is not live (HPS_EARLY_INIT)
+        pend_rode = plain && gated && islice > 0
+                    && mg_ride_shift_init(mg, ShiftInit{slab.p, slab.nstride, plane, (int)slab.jstride, bb, L, other(), (int)HPS_C_ION_RHOMJZ});
+        if ((e = mg_solve1_begin(mg, slab, HPS_C_BX, HPS_C_SY, L.chi, d.mg_tol_rel, d.mg_tol_abs, 200, st))) return e;
         if (gated_ion) {
             mark();   // b6
             mark();   // b7
@@ -2127,7 +2159,7 @@ int Engine::solve_slice_finish (int islice)
         // push of this slice and deposition of the next one in one pass over the sheet (static beam, no laser, one
         // plasma species, the whole sheet inside the tile-sorted body)
         if (fuse) {
-            hipLaunchKernelGGL(k_shift_zero, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb, d.deposit_rho ? (int)HPS_C_RHO : -1, (int)HPS_C_ION_RHOMJZ);
+            hipLaunchKernelGGL(k_shift_zero, gplane, b256, 0, st, ShiftInit{slab.p, slab.nstride, plane, (int)slab.jstride, bb, set_canon, set_canon, (int)HPS_C_ION_RHOMJZ});
             const int dep[6] = {HPS_C_JX, HPS_C_JY, -1, d.deposit_rho ? HPS_C_RHO : -1, HPS_C_CHI, HPS_C_RHOMJZ};
             if ((e = advance_deposit_tiled(slab, el.pl, gm, comp, dep, el.charge, el.mass, d.order, d.n_subcycles, d.max_qsa, d_nqsa, el.tiling, d_nfallback, st))) return e;
             ahead_for = islice - 1;
@@ -2146,9 +2178,11 @@ int Engine::solve_slice_finish (int islice)
     // ShiftSlices (fields/Fields.cpp:588-604)
     // (lazy_shift: left to the start of the next slice, where it shares a pass with InitializeSlices; anything that looks at
     //  the slab in between -- hps_engine_slab, _sync, the diagnostics' accessors -- runs it first: flush_shift)
-    if (ahead_for != islice - 1) {
+    // (HPS_EARLY_INIT: the shift and the next slice's zeros have ridden in this slice's Bx/By solve -- the sets change roles)
+    if (pend_rode) { pend_rode = false; alt_live = !alt_live; init_done = true; ++slices_rode; }
+    else if (ahead_for != islice - 1) {
         if (lazy_shift && islice > 0 && !salame_now()) shift_pending = true;
-        else hipLaunchKernelGGL(k_shift_slices, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb);
+        else hipLaunchKernelGGL(k_shift_slices, gplane, b256, 0, st, slab.p, slab.nstride, plane, (int)slab.jstride, bb, live().njxb, live().njyb);
     }
     mark();   // b9
     HPS_HIP_CHECK(hipGetLastError());
@@ -2351,7 +2385,19 @@ extern "C" int hps_engine_info (void* h, int* ncomp, int* ng, long* np)
     if (np) *np = E->el.pl.n;
     return HPS_OK;
 }
-extern "C" hps_slab hps_engine_slab (void* h) { Engine* E = static_cast<Engine*>(h); E->flush_shift(); return E->slab; }
+extern "C" hps_slab hps_engine_slab (void* h)
+{
+    Engine* E = static_cast<Engine*>(h);
+    E->flush_shift();
+    hps_slab s = E->slab; s.ncomp -= E->n_alt;      // (the alternate planes of HPS_EARLY_INIT are the engine's own business)
+    return s;
+}
+extern "C" int hps_engine_early_init_slices (void* h, long* n)
+{
+    HPS_REQUIRE(h && n, "hps_engine_early_init_slices: null argument");
+    *n = static_cast<Engine*>(h)->slices_rode;
+    return HPS_OK;
+}
 extern "C" hps_plasma hps_engine_plasma (void* h) { return static_cast<Engine*>(h)->el.pl; }
 extern "C" int hps_engine_tiling (void* h, void** tiling)
 {

@@ -1120,11 +1120,20 @@ __device__ __forceinline__ void tiny_up_s (lds_double* base, const Low2& d, int 
     }
 }
 
+// Guests of the lower V (the engine's HPS_EARLY_INIT): workgroups 2 .. of the first V-cycle's launch run the slab's shift /
+// zero pass for the next slice on the compute units the two solver workgroups leave idle.  They share nothing with the
+// solver workgroups and do not read the stop rule.
+__device__ __forceinline__ void lower_v_guest (const ShiftInit& a, int guest, int nguests)
+{
+    for (long s = (long)guest*1024 + threadIdx.x; s < a.plane; s += (long)nguests*1024) shift_init_cell(a, s);
+}
+
 __global__ __launch_bounds__(1024)
 void k_lower_v3 (const Low2* __restrict__ dp, const double* __restrict__ acf_g, const double* __restrict__ cinv_g,
                  const double* __restrict__ res_g, double* __restrict__ cor_g, double* __restrict__ coef_g, int nxA, int nyA, int ctot,
-                 double facx0, double facy0, int nsweeps_bottom, StopRule sr)
+                 double facx0, double facy0, int nsweeps_bottom, StopRule sr, ShiftInit guest)
 {
+    if (blockIdx.x >= 2) { lower_v_guest(guest, (int)blockIdx.x - 2, (int)gridDim.x - 2); return; }
     extern __shared__ __attribute__((aligned(16))) double lds_raw[];
     lds_double* base = (lds_double*)lds_raw;
     const int t = threadIdx.x;
@@ -1482,6 +1491,7 @@ struct Multigrid {
     SolveRun run{};                             // the solve between mg_solve1_begin and mg_solve1_finish
     bool defer_post = false; bool deferred_valid = false; MgPost deferred{};      // mg_defer_post / mg_take_deferred_post
     bool use_low3 = false; Low2 low3{}; Low2* d_low3 = nullptr; size_t low3_lds = 0;   // cell-centred register/LDS lower V (k_lower_v3)
+    bool ride_on = false; ShiftInit ride{}; int ride_guests = 0;      // mg_ride_shift_init: guests of the next solve's first k_lower_v3 launch
     double* cinvA = nullptr;                    // inverse diagonals of level lowv_begin (written with the coefficient pyramid)
     double* coef_img = nullptr;                 // [acf | 1/diag] planes of the levels below it (left by the first V-cycle of a solve)
     double* tmp0 = nullptr;                     // level-0 scratch: smoothed solution before the last GSRB^4
@@ -1585,6 +1595,11 @@ int mg_create (int nx, int ny, double dx, double dy, Multigrid** out)
             HPS_HIP_CHECK(hipMalloc(&M->d_low3, sizeof(Low2)));
             HPS_HIP_CHECK(hipMemcpy(M->d_low3, &e, sizeof(Low2), hipMemcpyHostToDevice));
             HPS_HIP_CHECK(hipMalloc(&M->cinvA, (size_t)e.nx[0]*e.ny[0]*sizeof(double)));
+            // guests: one per compute unit that the two solver workgroups leave free
+            int dev = 0, ncu = 0;
+            HPS_HIP_CHECK(hipGetDevice(&dev));
+            HPS_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+            M->ride_guests = std::max(ncu - 2, 1);
             break;
         }
     }
@@ -1702,10 +1717,13 @@ static void vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStre
             const dim3 grid(ceil_div(bb.vhx - bb.vlx + 1, 64), bb.vhy - bb.vly + 1);
             for (int is = -1; is < nsweeps; ++is)
                 hipLaunchKernelGGL(k_bottom_sweep<CC>, grid, dim3(64), 0, st, bb, cor, rhs, acf, 1.0/(ldx*ldx), 1.0/(ldy*ldy), is, sr);
-        } else if (M->use_low3)
-            hipLaunchKernelGGL(k_lower_v3, dim3(2), dim3(1024), M->low3_lds, st, M->d_low3, M->L[lb].acf, M->cinvA, M->L[lb].res, M->L[lb].cor,
-                               M->coef_img, M->low3.nx[0], M->low3.ny[0], M->low3.ctot, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr);
-        else      // (node-centred: one field component per workgroup)
+        } else if (M->use_low3) {
+            // one field component per workgroup; behind them the guests of this solve (mg_ride_shift_init), in V-cycle 0 only
+            const int guests = (k == 0 && M->ride_on) ? M->ride_guests : 0;
+            M->ride_on = false;
+            hipLaunchKernelGGL(k_lower_v3, dim3(2 + guests), dim3(1024), M->low3_lds, st, M->d_low3, M->L[lb].acf, M->cinvA, M->L[lb].res, M->L[lb].cor,
+                               M->coef_img, M->low3.nx[0], M->low3.ny[0], M->low3.ctot, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, M->ride);
+        } else      // (node-centred: one field component per workgroup)
             hipLaunchKernelGGL(k_lower_v<CC>, dim3(CC ? 1 : 2), dim3(1024), M->low_lds, st, M->d_low, nl - lb, M->L[lb].acf, M->L[lb].res,
                                M->L[lb].cor, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, M->pulls(lb) ? M->lv(lb-1, M->L[lb-1].rescor) : FView{});
     }
@@ -1965,7 +1983,13 @@ int mg_solve1_prepare_with (void* handle, hps_slab s, int sol_comp, int rhs_comp
     return HPS_OK;
 }
 // a hierarchy enqueued by mg_solve1_prepare* that no mg_solve1_begin followed (the caller failed in between) is dropped
-void mg_solve1_forget_hierarchy (void* handle) { if (handle) static_cast<Multigrid*>(handle)->hierarchy_ready = false; }
+// (and so is a pass handed to mg_ride_shift_init)
+void mg_solve1_forget_hierarchy (void* handle)
+{
+    if (!handle) return;
+    Multigrid* M = static_cast<Multigrid*>(handle);
+    M->hierarchy_ready = false; M->ride_on = false;
+}
 // mg_defer_post ahead of mg_solve1_begin: the post of the first batch's norms is not launched but handed out by
 // mg_take_deferred_post -- the caller MUST then enqueue, next on the same stream, a kernel that performs it (k_advance_tiled's
 // MgPost argument), or the solve's finish never sees its norms.  (Without mg_defer_post k_post_norms has posted already:
@@ -1977,6 +2001,16 @@ bool mg_take_deferred_post (void* handle, MgPost* out)
     M->defer_post = false;
     if (!M->deferred_valid) return false;
     M->deferred_valid = false; *out = M->deferred;
+    return true;
+}
+// mg_ride_shift_init ahead of mg_solve1_begin: the slab's shift / zero pass for the next slice rides in the launch of that
+// solve's first lower V (k_lower_v3's guests; V-cycle 0 is always enqueued).  false: this grid's lower V is another kernel and
+// nothing will be done -- the caller keeps its own launch.
+bool mg_ride_shift_init (void* handle, const ShiftInit& pass)
+{
+    Multigrid* M = static_cast<Multigrid*>(handle);
+    if (!M->cc || !M->use_low3 || M->bottom) return false;
+    M->ride = pass; M->ride_on = true;
     return true;
 }
 const int* mg_gate_after_enqueued (void* handle)

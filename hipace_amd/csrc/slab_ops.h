@@ -37,5 +37,31 @@ __device__ __forceinline__ void gradpsi_sxsy_cell (const SlabView& f, const Grad
     f.p[a.cSx*f.ns + o] = -a.mu0*(-dx_jzb + dz_jxb);
 }
 
+// ShiftSlices (fields/Fields.cpp:588-604) of a slice AND InitializeSlices (:535-586) of the next one, cell s of the padded
+// plane: jx, jy <- Next beam currents, Previous <- This <- Next inside the beam's box; chi = 0, rhomjz [rho] = the ion
+// background (AddRhoIons ahead of the deposition), and inside the box jz_beam = Next = 0.  The planes that are re-initialised
+// come in two sets: the slice's values are read from `live`, the next slice's zeros and backgrounds go to `next` (the same
+// set: in place, the Next currents are read before they are cleared).  Planes hold fewer than 2^31 cells (mg_create).
+struct InitSet { int chi, rhomjz, rho, jzb, njxb, njyb; };      // rho = -1: the deck deposits none
+struct ShiftInit { double* p; long ns, plane; int js; CellBox bb; InitSet live, next; int c_ion; };
+
+__device__ __forceinline__ void shift_init_cell (const ShiftInit& a, long s)
+{
+    double* p = a.p; const long ns = a.ns;
+    const int j = (int)((unsigned)s / (unsigned)a.js), i = (int)s - j*a.js;
+    double njx = 0.0, njy = 0.0;
+    if (i >= a.bb.ilo && i <= a.bb.ihi && j >= a.bb.jlo && j <= a.bb.jhi) {
+        const double tjx = p[HPS_C_JXB*ns + s], tjy = p[HPS_C_JYB*ns + s];
+        njx = p[a.live.njxb*ns + s]; njy = p[a.live.njyb*ns + s];
+        p[HPS_C_P_JXB*ns + s] = tjx; p[HPS_C_P_JYB*ns + s] = tjy;
+        p[HPS_C_JXB*ns + s] = njx;   p[HPS_C_JYB*ns + s] = njy;
+        p[a.next.njxb*ns + s] = 0.0; p[a.next.njyb*ns + s] = 0.0; p[a.next.jzb*ns + s] = 0.0;
+    }
+    p[HPS_C_JX*ns + s] = njx; p[HPS_C_JY*ns + s] = njy;
+    const double ion = a.c_ion >= 0 ? p[a.c_ion*ns + s] : 0.0;
+    p[a.next.chi*ns + s] = 0.0; p[a.next.rhomjz*ns + s] = ion;
+    if (a.next.rho >= 0) p[a.next.rho*ns + s] = ion;
+}
+
 } // namespace hps
 #endif

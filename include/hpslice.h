@@ -371,7 +371,10 @@ int hps_engine_info (void* handle, int* ncomp, int* nguards, long* nparticles);
  * in the next slice's InitializeSlices pass); hps_engine_slab and hps_engine_sync enqueue the pending shift before they
  * return, hps_engine_record_event / hps_engine_copy_async / the export calls do NOT.  A host that keeps the hps_slab
  * pointer and reads the Previous / Next planes stream-ordered between two slices without one of those two calls sees
- * them as they were before the shift; HPS_LAZY_SHIFT=0 in the environment restores the shift at the end of every slice. */
+ * them as they were before the shift; HPS_LAZY_SHIFT=0 in the environment restores the shift at the end of every slice.
+ * Likewise chi, rhomjz, rho, jz_beam and the Next beam currents of the slice just solved: on the plain explicit-solver slice
+ * they may sit in alternate planes the engine keeps behind the slab's own (hps_engine_early_init_slices below) until one of
+ * those two calls has put them back; HPS_EARLY_INIT=0 in the environment keeps every slice on the slab's own planes. */
 hps_slab hps_engine_slab (void* handle);
 /* The engine's sheet: raw device pointers.  CONTRACT for a host that invalidates particles itself: clearing the valid bit of
  * idcpu is not enough -- also store 0 to the particle's w AND psi_half.  The engine's tiled depositions take "w != 0" for
@@ -390,6 +393,10 @@ hps_stream hps_engine_stream (void* handle);
 /* sum |Q| per component over valid cells and all slices of the current step (host array[ncomp]) */
 int hps_engine_checksums (void* handle, double* out_host);
 int hps_engine_stats (void* handle, long* total_vcycles, long* slices_done);
+/* slices so far whose ShiftSlices + the next slice's InitializeSlices rode in the launch of their Bx/By solve's first lower V
+ * instead of a launch of their own at the head of the next slice (the plain explicit-solver slice on a grid whose lower V is
+ * k_lower_v3; HPS_EARLY_INIT=0 in the environment: never).  hps_engine_slab and hps_engine_sync show the slab as without it. */
+int hps_engine_early_init_slices (void* handle, long* n_slices);
 /* predictor-corrector: iterations so far and the sum over slices of the final relative B-field error
  * (m_predcorr_avg_iterations / m_predcorr_avg_B_error of Hipace.cpp:964,1028 before the division by nz) */
 int hps_engine_pc_stats (void* handle, long* iterations, double* error_sum);
