@@ -73,6 +73,12 @@ class BeamFixedWeightPdf(C.Structure):  # hps_beam_fixed_weight_pdf
                 ("z_foc", C.c_double), ("density", C.c_double), ("total_charge", C.c_double), ("charge_is_specified", C.c_int)]
 
 
+class BeamSpecies(C.Structure):         # hps_beam_species
+    _fields_ = [("charge", C.c_double), ("mass", C.c_double), ("n_subcycles", C.c_int), ("no_z_push", C.c_int),
+                ("radiation_reaction", C.c_int), ("do_spin_tracking", C.c_int), ("spin_anom", C.c_double),
+                ("uz_mean", C.c_double), ("uz_std", C.c_double)]
+
+
 class Deck(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3),
@@ -310,6 +316,18 @@ _SIGS = {
                                                        C.c_ulonglong, C.POINTER(C.c_long), C.POINTER(C.c_double)]),
     "hps_adaptive_set_density_expr": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Expr), C.c_void_p]),
     "hps_adaptive_rho_max": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(C.c_double)]),
+    "hps_engine_add_beam_species": (C.c_int, [C.c_void_p, C.POINTER(BeamSpecies), C.POINTER(C.c_int)]),
+    "hps_engine_select_beam_species": (C.c_int, [C.c_void_p, C.c_int]),
+    "hps_engine_beam_species_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_long)]),
+    "hps_engine_beam_state_species": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_long), C.c_void_p, C.c_void_p]),
+    "hps_engine_insitu_beam_species": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hps_engine_beam_tags": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hps_engine_beam_moments_species": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hps_engine_beam_kernels": (C.c_int, [C.c_void_p, C.c_char_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    "hps_adaptive_initial_dt_beams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.POINTER(C.c_double)]),
+    "hps_adaptive_after_step_beams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
+                                                C.POINTER(C.c_double)]),
     "hps_memcpy_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long]),
     "hps_device_count": (C.c_int, [C.POINTER(C.c_int)]),

@@ -499,10 +499,16 @@ class AdaptiveTimeStep:
     """hipace.dt = adaptive: the reference's controller (utils/AdaptiveTimeStep.cpp) over hps_adaptive_* -- host code, no
     device.  One per rank / pipeline stage, all initialised alike."""
 
-    def __init__(self, deck, density_profile=None, density_exprs=None):
+    def __init__(self, deck, density_profile=None, density_exprs=None, beams=None):
         """density_exprs: {species: (text_or_table, constants)} of parsed densities; default: the deck's own
-        (decks.DENSITY_EXPR_DEFAULT), as SliceEngine applies them"""
+        (decks.DENSITY_EXPR_DEFAULT), as SliceEngine applies them.  beams: [dict(charge, mass, uz_mean, uz_std)], one per beam
+        species (default: the deck's entry beam_species behind the deck's own beam); with more than one the controller runs per
+        beam (hps_adaptive_*_beams): CalculateFromMinUz takes the moments [n][4] of SliceEngine.beam_moments(species=all)"""
         self.deck = dict(deck)
+        if beams is None:
+            more = [s["record"] for s in _decks.beam_species(deck)]
+            beams = ([dict(charge=deck.get("beam_charge", -1.0), mass=deck.get("beam_mass", 1.0))] + more) if more else None
+        self.beams = None if beams is None or len(beams) < 2 else [dict(b) for b in beams]
         self._dk = _lib.fill_struct(_lib.Deck(), deck)
         self._h = C.c_void_p()
         check(_lib.lib().hps_adaptive_create(C.byref(self._dk), C.byref(self._h)))
@@ -518,7 +524,14 @@ class AdaptiveTimeStep:
         """a controller for `engine`'s deck, density profile and density programs"""
         exprs = {sp: ((progs[0] if pos is None else list(zip(pos, progs))), None)
                  for sp, (progs, pos, _) in getattr(engine, "density_exprs", {}).items()}
-        return cls(engine.deck, getattr(engine, "density_profile", None), exprs)
+        names, _ = engine.beam_species()
+        beams = [r for r in engine.beam_species_records] if len(names) > 1 else None
+        return cls(engine.deck, getattr(engine, "density_profile", None), exprs, beams)
+
+    def _beam_arrays(self):
+        q = np.array([b["charge"] for b in self.beams], dtype=np.float64)
+        m = np.array([b["mass"] for b in self.beams], dtype=np.float64)
+        return q, m
 
     def set_density_expr(self, species, text_or_table, constants=None):
         """the species' parsed density (SliceEngine.set_density_expr): rho_max(z) takes |charge * density(0, 0, z)|"""
@@ -553,6 +566,14 @@ class AdaptiveTimeStep:
         if uz_std is None and us == 0.0 and self.deck.get("beam_density_expr") is not None:
             us = (self.deck.get("beam_u_std") or (0, 0, 0))[2]      # decks.BEAM_INIT_DEFAULT: the fixed_ppc beam's own u_std[2]
         dt = C.c_double()
+        if self.beams is not None:      # per beam: species 0 as above, the others from their own uz_mean / uz_std
+            ums = np.array([um] + [b.get("uz_mean", 0.0) for b in self.beams[1:]], dtype=np.float64)
+            uss = np.array([us] + [b.get("uz_std", 0.0) for b in self.beams[1:]], dtype=np.float64)
+            q, m = self._beam_arrays()
+            check(_lib.lib().hps_adaptive_initial_dt_beams(self._h, len(self.beams), ums.ctypes.data_as(C.c_void_p),
+                                                           uss.ctypes.data_as(C.c_void_p), q.ctypes.data_as(C.c_void_p),
+                                                           m.ctypes.data_as(C.c_void_p), int(nstages), C.byref(dt)))
+            return dt.value
         check(_lib.lib().hps_adaptive_initial_dt(self._h, float(um), float(us), int(nstages), C.byref(dt)))
         return dt.value
 
@@ -571,8 +592,15 @@ class AdaptiveTimeStep:
     def CalculateFromMinUz(self, moments, t, nstages=1):
         """end of the step that started at t, from its moments (SliceEngine.beam_moments).  -> this controller's next dt"""
         m = np.ascontiguousarray(moments, dtype=np.float64)
-        assert m.shape == (4,)
         dt = C.c_double()
+        if self.beams is not None:
+            assert m.shape == (len(self.beams), 4)
+            q, ms = self._beam_arrays()
+            check(_lib.lib().hps_adaptive_after_step_beams(self._h, len(self.beams), m.ctypes.data_as(C.c_void_p),
+                                                           q.ctypes.data_as(C.c_void_p), ms.ctypes.data_as(C.c_void_p), float(t),
+                                                           int(nstages), C.byref(dt)))
+            return dt.value
+        assert m.shape == (4,)
         check(_lib.lib().hps_adaptive_after_step(self._h, m.ctypes.data_as(C.c_void_p), float(t), int(nstages), C.byref(dt)))
         return dt.value
 
@@ -602,6 +630,11 @@ class SliceEngine:
             self._dk.beam_profile = -1
         self._h = C.c_void_p()
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
+        # the beam species: species 0 is the deck's beam; the deck's entry beam_species is applied further down
+        self.beam_species_names = [deck.get("beam_name", "beam")]
+        self.beam_species_records = [dict(charge=deck.get("beam_charge", -1.0), mass=deck.get("beam_mass", 1.0),
+                                          uz_mean=deck["beam_umean"][2] if "beam_umean" in deck else 0.0,
+                                          uz_std=deck.get("beam_uz_std", 0.0))]
         if tile_size is not None:
             check(_lib.lib().hps_engine_set_tiling(self._h, tile_size, sort_period or 128))
         # not members of hps_deck: applied through the setters, fine_ppc ahead of the patch
@@ -655,6 +688,9 @@ class SliceEngine:
             self.beam_left_out = self.set_beam_fixed_weight(**beam_fw)
         if beam_fwp is not None:
             self.beam_left_out = self.set_beam_fixed_weight_pdf(**beam_fwp)
+        # further beam species (decks.BEAM_SPECIES_DEFAULT): a deck without the entry makes no call
+        for spec in _decks.beam_species(deck):
+            self._add_beam_species(spec)
         nc, ng, npart = C.c_int(), C.c_int(), C.c_long()
         check(_lib.lib().hps_engine_info(self._h, C.byref(nc), C.byref(ng), C.byref(npart)))
         self.ncomp, self.ng, self.nparticles = nc.value, ng.value, npart.value
@@ -882,11 +918,92 @@ class SliceEngine:
         """physical time and dt of the step the next begin_step starts (hps_engine_set_time)"""
         check(_lib.lib().hps_engine_set_time(self._h, float(t), float(dt)))
 
-    def beam_moments(self):
-        """{sum w, sum w uz/c, sum w (uz/c)^2, min uz/c} of the step last solved, as a float64 array (synchronises)"""
-        out = np.zeros(4, dtype=np.float64)
-        check(_lib.lib().hps_engine_beam_moments(self._h, out.ctypes.data_as(C.c_void_p)))
-        return out
+    def beam_moments(self, species=None):
+        """{sum w, sum w uz/c, sum w (uz/c)^2, min uz/c} of the step last solved, as a float64 array (synchronises).
+        species: None -- the one beam's (refused by an engine with several species: their moments are never summed);
+        "all" -- every species', [n][4]; k -- species k's."""
+        if species is None:
+            out = np.zeros(4, dtype=np.float64)
+            check(_lib.lib().hps_engine_beam_moments(self._h, out.ctypes.data_as(C.c_void_p)))
+            return out
+        n = len(self.beam_species_names)
+        out = np.zeros((n, 4), dtype=np.float64)
+        check(_lib.lib().hps_engine_beam_moments_species(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out if isinstance(species, str) and species == "all" else out[self._species_index(species)]
+
+    # ---- several beam species in one engine (DESIGN 8q) ---------------------------------------------
+    def _species_index(self, species):
+        if isinstance(species, str):
+            if species not in self.beam_species_names:
+                raise ValueError(f"no beam species named {species!r} (have {self.beam_species_names})")
+            return self.beam_species_names.index(species)
+        k = int(species)
+        if not 0 <= k < len(self.beam_species_names):
+            raise ValueError(f"no beam species {k} (the engine holds {len(self.beam_species_names)})")
+        return k
+
+    def _select_species(self, species):
+        check(_lib.lib().hps_engine_select_beam_species(self._h, self._species_index(species or 0)))
+
+    def _add_beam_species(self, spec):
+        rec = _lib.fill_struct(_lib.BeamSpecies(), spec["record"])
+        k = C.c_int(-1)
+        check(_lib.lib().hps_engine_add_beam_species(self._h, C.byref(rec), C.byref(k)))
+        name = spec["name"] if spec["name"] is not None else f"beam{k.value}"
+        self.beam_species_names.append(name)
+        self.beam_species_records.append(dict(spec["record"]))
+        setter = dict(fixed_weight=self.set_beam_fixed_weight, fixed_weight_pdf=self.set_beam_fixed_weight_pdf,
+                      density_expr=self.set_beam_fixed_ppc, particles=self.set_beam_particles)[spec["source"]]
+        args = dict(spec["args"])
+        if spec["source"] == "particles":
+            args["allow_outside"] = True
+        if not hasattr(self, "beam_species_left_out"):
+            self.beam_species_left_out = {}
+        self.beam_species_left_out[k.value] = setter(species=k.value, **args)
+        if spec["source"] == "fixed_weight_pdf" and not (spec["record"]["uz_mean"] or spec["record"]["uz_std"]):
+            self.beam_species_records[-1].update(uz_mean=self.beam_uz_moments[0], uz_std=self.beam_uz_moments[1])
+        return k.value
+
+    def add_beam_species(self, **spec):
+        """One more beam species in this moving-beam engine (hps_engine_add_beam_species + the source's setter with species=):
+        name, charge, mass, n_subcycles, do_z_push, radiation_reaction, spin_anom, do_spin_tracking, uz_mean, uz_std (defaults:
+        the deck's beam's) and exactly one source -- fixed_weight=dict(...), fixed_weight_pdf=dict(...), density_expr=... (with
+        constants, min_density, u_std, random_ppc, seed) or particles=(7, n) array (decks.BEAM_SPECIES_DEFAULT).  Before the
+        first begin_step.  -> the species' index; what the source left out of the box: beam_species_left_out[index]."""
+        return self._add_beam_species(_decks.beam_species_spec(self.deck, spec, "add_beam_species"))
+
+    def beam_species(self):
+        """-> (names, counts) of the engine's beam species, species 0 = the deck's beam"""
+        n = C.c_int()
+        counts = (C.c_long * _decks.MAX_BEAM_SPECIES)()
+        check(_lib.lib().hps_engine_beam_species_info(self._h, C.byref(n), counts))
+        return list(self.beam_species_names[:n.value]), [counts[k] for k in range(n.value)]
+
+    def beam_container(self):
+        """-> (boundaries int64 [nz+1], soa float64 [7, nbeam], tags uint8 [nbeam]) of the whole container, every species"""
+        names, _ = self.beam_species()
+        nz = self.deck["nz"]
+        if len(names) == 1:
+            bnd, soa = self.beam_state()
+            return bnd, soa, np.zeros(soa.shape[1], dtype=np.uint8)
+        n = C.c_long()
+        check(_lib.lib().hps_engine_beam_state_species(self._h, -1, C.byref(n), None, None))
+        bnd = np.zeros(nz + 1, dtype=np.int64)
+        soa = np.zeros((7, max(n.value, 1)), dtype=np.float64)
+        tags = np.zeros(max(n.value, 1), dtype=np.uint8)
+        check(_lib.lib().hps_engine_beam_state_species(self._h, -1, C.byref(n), bnd.ctypes.data_as(C.c_void_p),
+                                                       soa.ctypes.data_as(C.c_void_p) if n.value else None))
+        check(_lib.lib().hps_engine_beam_tags(self._h, tags.ctypes.data_as(C.c_void_p)))
+        return bnd, soa[:, :n.value], tags[:n.value]
+
+    def beam_kernels(self):
+        """-> (set of the beam kernel instances launched so far, e.g. "k_beam_push<2,0,0>" = ORDER, EXT, MULTI; does the
+        container hold a species tag row)"""
+        n, tagged = C.c_long(), C.c_int()
+        check(_lib.lib().hps_engine_beam_kernels(self._h, None, 0, C.byref(n), C.byref(tagged)))
+        buf = C.create_string_buffer(n.value + 1)
+        check(_lib.lib().hps_engine_beam_kernels(self._h, buf, n.value + 1, C.byref(n), C.byref(tagged)))
+        return set(buf.value.decode().split()), bool(tagged.value)
 
     def run_adaptive(self, n_steps=None, controller=None, on_step_end=None):
         """hipace.dt = adaptive on this one engine (Hipace::Evolve with one rank, Hipace.cpp:400-490): the head rank's
@@ -905,7 +1022,7 @@ class SliceEngine:
             log.append((step, t, dt))
             self.set_time(t, dt)
             self.run_step()
-            ats.CalculateFromMinUz(self.beam_moments(), t, 1)
+            ats.CalculateFromMinUz(self.beam_moments("all" if ats.beams is not None else None), t, 1)
             if on_step_end is not None:
                 on_step_end(step, t, dt)
             t = ats.next_time()
@@ -943,12 +1060,22 @@ class SliceEngine:
     def import_beam_slice(self, islice, msg):
         check(_lib.lib().hps_engine_import_beam_slice(self._h, islice, C.c_void_p(msg.data_ptr())))
 
-    def beam_state(self):
+    def beam_state(self, species=None):
         """(boundaries int64 [nz+1], soa float64 [7, nbeam]) of the beam as it is now; slice p from the head is
         soa[:, boundaries[p]:boundaries[p+1]] (rows x y z ux uy uz w).  A static beam (hipace.dt = 0) comes in the same
-        layout, with the weights SALAME has left."""
-        nbeam, _ = self.beam_layout()
+        layout, with the weights SALAME has left.  species=k (index or name): that species' particles alone, in container
+        order (an engine with several species refuses species=None)."""
         nz = self.deck["nz"]
+        if species is not None:
+            k = self._species_index(species)
+            n = C.c_long()
+            check(_lib.lib().hps_engine_beam_state_species(self._h, k, C.byref(n), None, None))
+            bnd = np.zeros(nz + 1, dtype=np.int64)
+            soa = np.zeros((7, max(n.value, 1)), dtype=np.float64)
+            check(_lib.lib().hps_engine_beam_state_species(self._h, k, C.byref(n), bnd.ctypes.data_as(C.c_void_p),
+                                                           soa.ctypes.data_as(C.c_void_p) if n.value else None))
+            return bnd, soa[:, :n.value]
+        nbeam, _ = self.beam_layout()
         bnd = np.zeros(nz + 1, dtype=np.int64)
         soa = np.zeros((7, max(nbeam, 1)), dtype=np.float64)
         check(_lib.lib().hps_engine_beam_state(self._h, bnd.ctypes.data_as(C.c_void_p), soa.ctypes.data_as(C.c_void_p) if nbeam else None))
@@ -1009,17 +1136,19 @@ class SliceEngine:
         check(_lib.lib().hps_engine_beam_info(self._h, C.byref(nb), off))
         return nb.value, np.array(off[:], dtype=np.int64)
 
-    def set_beam_particles(self, soa, allow_outside=False):
+    def set_beam_particles(self, soa, allow_outside=False, species=None):
         """A host-initialised beam in place of the deck's (any of the reference's injection types): soa = (7, n) array
-        x y z ux uy uz w.  Before the first begin_step.  -> number of particles outside the box in z (left out)."""
+        x y z ux uy uz w.  Before the first begin_step.  -> number of particles outside the box in z (left out).
+        species=k: the particles fill beam species k (add_beam_species) instead of replacing the beam."""
         soa = np.ascontiguousarray(soa, dtype=np.float64)
         assert soa.ndim == 2 and soa.shape[0] == 7
+        self._select_species(species)
         out = C.c_long(0)
         check(_lib.lib().hps_engine_set_beam_particles(self._h, soa.shape[1], soa.ctypes.data_as(C.c_void_p),
                                                        C.byref(out) if allow_outside else None))
         return out.value
 
-    def set_beam_fixed_ppc(self, expr, constants=None, min_density=0.0, u_std=None, random_ppc=None, seed=1):
+    def set_beam_fixed_ppc(self, expr, constants=None, min_density=0.0, u_std=None, random_ppc=None, seed=1, species=None):
         """The general fixed_ppc beam in place of the deck's, generated on the device (hps_engine_set_beam_fixed_ppc):
         <beam>.density(x,y,z) as a string in the input file's syntax (or a number, or a Program over x, y, z), constants:
         my_constants, <beam>.min_density, u_std (3, units of c), random_ppc (3 flags) and the seed of the draws.  The deck gives
@@ -1041,11 +1170,12 @@ class SliceEngine:
         c, keep = prog.c_struct()
         us = (C.c_double * 3)(*[float(v) for v in u_std]) if u_std is not None else None
         rp = (C.c_int * 3)(*[int(bool(v)) for v in random_ppc]) if random_ppc is not None else None
+        self._select_species(species)      # (species=k: fills beam species k, add_beam_species)
         check(_lib.lib().hps_engine_set_beam_fixed_ppc(self._h, C.byref(c), float(min_density), us, rp, int(seed)))
 
     def set_beam_fixed_weight(self, num_particles, position_mean, position_std, u_mean=(0.0, 0.0, 0.0), u_std=(0.0, 0.0, 0.0),
                               density=None, total_charge=None, profile="gaussian", zmin=-np.inf, zmax=np.inf, radius=np.inf,
-                              do_symmetrize=False, z_foc=0.0, duz_per_uz0_dzeta=0.0, seed=1, constants=None):
+                              do_symmetrize=False, z_foc=0.0, duz_per_uz0_dzeta=0.0, seed=1, constants=None, species=None):
         """The fixed_weight beam (injection_type = fixed_weight, profile "gaussian" or "can") in place of the deck's, generated on
         the device (hps_engine_set_beam_fixed_weight): num_particles draws -- a quarter of them with do_symmetrize --
         with z normal about position_mean[2] with position_std[2] (gaussian) or uniform in [zmin, zmax] (can), x and y normal
@@ -1081,13 +1211,14 @@ class SliceEngine:
             total_charge=0.0 if total_charge is None else float(total_charge), charge_is_specified=int(total_charge is not None))
         (cx, keep_x), (cy, keep_y) = progs[0].c_struct(), progs[1].c_struct()
         out = (C.c_long * 2)(0, 0)
+        self._select_species(species)      # (species=k: fills beam species k, add_beam_species)
         check(_lib.lib().hps_engine_set_beam_fixed_weight(self._h, C.byref(spec), C.byref(cx), C.byref(cy), int(seed), out))
         self.beam_mean_programs = (progs[0], progs[1])
         return out[0], out[1]
 
     def set_beam_fixed_weight_pdf(self, num_particles, pdf, position_mean, position_std, u_mean=(0.0, 0.0, 0.0), u_std=(0.0, 0.0, 0.0),
                                   density=None, total_charge=None, radius=np.inf, z_foc=0.0, do_symmetrize=False, pdf_ref_ratio=4,
-                                  seed=1, constants=None):
+                                  seed=1, constants=None, species=None):
         """The fixed_weight_pdf beam (injection_type = fixed_weight_pdf) in place of the deck's, generated on the device
         (hps_engine_set_beam_fixed_weight_pdf): num_particles particles of one weight -- a quarter as many draws with
         do_symmetrize -- with the longitudinal profile pdf(z), tabulated on nz pdf_ref_ratio sub-slices, x and y normal about
@@ -1134,6 +1265,7 @@ class SliceEngine:
         cpdf, keep_pdf = prog_pdf.c_struct()
         arr, keep = _expr.c_programs(progs)
         out, mom = (C.c_long * 2)(0, 0), (C.c_double * 2)(0.0, 0.0)
+        self._select_species(species)      # (species=k: fills beam species k, add_beam_species)
         check(_lib.lib().hps_engine_set_beam_fixed_weight_pdf(self._h, C.byref(spec), C.byref(cpdf), arr, int(seed), out, mom))
         self.beam_pdf_programs = (prog_pdf, tuple(progs))
         self.beam_uz_moments = (mom[0], mom[1])
@@ -1196,10 +1328,14 @@ class SliceEngine:
         """<beam>.insitu_period / insitu_radius: per-slice moments of BeamParticleContainer::InSituComputeDiags."""
         check(_lib.lib().hps_engine_set_insitu_beam(self._h, min(float(radius), 1.0e300)))
 
-    def insitu_beam(self):
-        """-> dict name -> array[nz] (index = islice), names as the reference's in-situ file (BeamParticleContainer.cpp:625-650)."""
+    def insitu_beam(self, species=None):
+        """-> dict name -> array[nz] (index = islice), names as the reference's in-situ file (BeamParticleContainer.cpp:625-650).
+        species=k (index or name): that beam species' moments (an engine with several species refuses species=None)."""
         out = np.empty((23, self.deck["nz"]))
-        check(_lib.lib().hps_engine_insitu_beam(self._h, out.ctypes.data_as(C.c_void_p)))
+        if species is None:
+            check(_lib.lib().hps_engine_insitu_beam(self._h, out.ctypes.data_as(C.c_void_p)))
+        else:
+            check(_lib.lib().hps_engine_insitu_beam_species(self._h, self._species_index(species), out.ctypes.data_as(C.c_void_p)))
         return {n: out[i] for i, n in enumerate(self.INSITU_BEAM)}
 
     def set_insitu_plasma(self, radius=float("inf")):

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "expr.h"
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <limits>
 #include <vector>
@@ -28,6 +29,7 @@ struct Adaptive {
     double dt = 0.0;                                       // Hipace::m_dt of this rank
     double min_uz_mq = std::numeric_limits<double>::max();
     double acc[4] = {0.0, 0.0, 0.0, 1e30};                 // sum w, sum w uz, sum w uz^2, min uz (uz/c)
+    std::vector<std::array<double, 4>> accs;               // ... per beam, of the calls with several beams (m_timestep_data[ibeam])
     double next_time = 0.0;
 
     // MultiPlasma::maxChargeDensity(z)
@@ -47,7 +49,43 @@ struct Adaptive {
         }
         return r;
     }
-    void reset_moments () { acc[0] = acc[1] = acc[2] = 0.0; acc[3] = 1e30; }
+    void reset_moments () { acc[0] = acc[1] = acc[2] = 0.0; acc[3] = 1e30; for (auto& a : accs) a = {0.0, 0.0, 0.0, 1e30}; }
+    void size_beams (int n) { if ((int)accs.size() != n) accs.assign((size_t)n, std::array<double, 4>{0.0, 0.0, 0.0, 1e30}); }
+
+    // CalculateFromMinUz over several beams (AdaptiveTimeStep.cpp:177-258): every beam's dt from its own moments and m/q, a
+    // beam of charge 0 skipped; dt = the smallest, then dt_max; min_uz_mq = the smallest over the beams.  One beam with the
+    // deck's m/q: from_min_uz, statement by statement.
+    int from_min_uz_beams (int n, const double* charge, const double* mass, double t, int nstages) {
+        double dt_min = std::numeric_limits<double>::max(), mq_min = std::numeric_limits<double>::max();
+        for (int b = 0; b < n; ++b) {
+            double out = dt;
+            if (charge[b] != 0.0) {
+                const double* a = accs[(size_t)b].data();
+                const double mq_b = (mass[b] != 0.0 ? mass[b] : 1.0)/charge[b];
+                HPS_REQUIRE(a[0] != 0.0, "hps_adaptive: the sum of all weights is 0 (no beam particles)");
+                const double mean = a[1]/a[0];
+                const double sigma = std::sqrt(std::fabs(a[2]/a[0] - mean*mean));
+                double chosen = std::min(std::max(mean - 4.0*sigma, a[3]), 1.0e30);
+                chosen = std::max(chosen, thr);
+                mq_min = std::min(mq_min, std::fabs(chosen*mq_b));
+                double new_dt = dt, time = t, min_uz = chosen;
+                const int niter = predict ? std::max(nstages, 1) : 1;
+                for (int i = 0; i < niter; ++i) {
+                    const double rho = rho_max(c*time);
+                    HPS_REQUIRE(rho > 0.0, "hps_adaptive: the adaptive time step needs a plasma density > 0 (plasmas.adaptive_density)");
+                    min_uz = std::max(min_uz, 0.001*thr);
+                    const double omega_b = std::sqrt(rho/(2.0*std::fabs(min_uz*mq_b)*ep0));
+                    new_dt = 2.0*M_PI/omega_b/nt;
+                    time += new_dt;
+                    if (min_uz > thr) out = new_dt;
+                }
+            }
+            dt_min = std::min(dt_min, out);
+        }
+        min_uz_mq = mq_min;
+        dt = std::min(dt_min, dt_max);
+        return HPS_OK;
+    }
 
     // CalculateFromMinUz
     int from_min_uz (double t, int nstages) {
@@ -218,6 +256,43 @@ extern "C" int hps_adaptive_after_step (void* h, const double* m, double t, int 
     // the slices' GatherMinUzSlice(beams, false) on top of what CalculateFromDensity reset
     A->acc[0] += m[0]; A->acc[1] += m[1]; A->acc[2] += m[2]; A->acc[3] = std::min(A->acc[3], m[3]);
     if (int e = A->from_min_uz(t, nstages)) return e;
+    *dt = A->dt;
+    return HPS_OK;
+}
+
+static int beams_args_ok (const char* fn, const Adaptive* A, int n, const void* a, const void* b, const double* charge, const double* mass, const double* dt, int nstages)
+{
+    HPS_REQUIRE(A && a && b && charge && mass && dt, std::string(fn) + ": null argument");
+    HPS_REQUIRE(n >= 1 && nstages >= 1, std::string(fn) + ": n and nstages must be >= 1");
+    for (int k = 0; k < n; ++k) HPS_REQUIRE(std::isfinite(charge[k]) && std::isfinite(mass[k]), std::string(fn) + ": charge and mass must be finite");
+    return HPS_OK;
+}
+
+extern "C" int hps_adaptive_initial_dt_beams (void* h, int n, const double* uz_mean, const double* uz_std, const double* charge,
+                                              const double* mass, int nstages, double* dt)
+{
+    Adaptive* A = static_cast<Adaptive*>(h);
+    if (int e = beams_args_ok("hps_adaptive_initial_dt_beams", A, n, uz_mean, uz_std, charge, mass, dt, nstages)) return e;
+    A->size_beams(n);
+    for (int b = 0; b < n; ++b)      // GatherMinUzSlice(beams, true), per beam
+        A->accs[(size_t)b] = {1.0, uz_mean[b], uz_mean[b]*uz_mean[b] + uz_std[b]*uz_std[b], uz_mean[b] - 4.0*uz_std[b]};
+    if (int e = A->from_min_uz_beams(n, charge, mass, 0.0, nstages)) return e;
+    A->from_density(0.0);
+    *dt = A->dt;
+    return HPS_OK;
+}
+
+extern "C" int hps_adaptive_after_step_beams (void* h, int n, const double* m, const double* charge, const double* mass, double t,
+                                              int nstages, double* dt)
+{
+    Adaptive* A = static_cast<Adaptive*>(h);
+    if (int e = beams_args_ok("hps_adaptive_after_step_beams", A, n, m, m, charge, mass, dt, nstages)) return e;
+    A->size_beams(n);
+    for (int b = 0; b < n; ++b) {
+        std::array<double, 4>& a = A->accs[(size_t)b];
+        a[0] += m[4*b]; a[1] += m[4*b + 1]; a[2] += m[4*b + 2]; a[3] = std::min(a[3], m[4*b + 3]);
+    }
+    if (int e = A->from_min_uz_beams(n, charge, mass, t, nstages)) return e;
     *dt = A->dt;
     return HPS_OK;
 }

@@ -1,5 +1,5 @@
 // beam_ext.hip -- beams.external_E(x,y,z,t) / beams.external_B(x,y,z,t) as expression programs: the setter that
-// checks the programs and packs them into one device image, and the launch of k_beam_push<ORDER, true> (beam_push.h).
+// checks the programs and packs them into one device image, and the launch of k_beam_push<ORDER, true, MULTI> (beam_push.h).
 // Built with -mllvm -disable-machine-licm (Makefile): left on, the pass hoists the literal constants of every inlined
 // transcendental function out of the interpreter's loop and holds them in registers across it (k_expr_eval: 244 VGPRs
 // against 36; the order-3 push beyond 512 registers, into scratch).
@@ -14,9 +14,17 @@ int beam_push_launch_ext (Engine& E, const SlabView& f, int p, int cPsi, int cEz
     const BeamExtArgs<true> x{E.bext.image.ins(), E.bext.image.consts(), E.step_time};
     const dim3 block(256);
     const size_t lds = expr_lds_bytes(E.bext.depth, 256);
-#define CALL(O) hipLaunchKernelGGL((k_beam_push<O, true>), grid, block, lds, E.st, f, E.bm, E.d_B, p, cPsi, cEz, cBx, cBy, cBz, k, x)
-    HPS_BEAM_ORDER(E.d.order, CALL)
+    if (E.multi_beam()) {
+        const BeamMultiArgs<true> m{E.d_bsp_tab, E.n_beam_species()};
+#define CALL(O) hipLaunchKernelGGL((k_beam_push<O, true, true>), grid, block, lds, E.st, f, E.bm, E.d_B, p, cPsi, cEz, cBx, cBy, cBz, k, x, m)
+        HPS_BEAM_ORDER(E.d.order, CALL)
 #undef CALL
+    } else {
+#define CALL(O) hipLaunchKernelGGL((k_beam_push<O, true, false>), grid, block, lds, E.st, f, E.bm, E.d_B, p, cPsi, cEz, cBx, cBy, cBz, k, x, BeamMultiArgs<false>{})
+        HPS_BEAM_ORDER(E.d.order, CALL)
+#undef CALL
+    }
+    E.beam_launched |= beam_push_bit(std::min(std::max(E.d.order, 0), 3), true, E.multi_beam());
     HPS_HIP_CHECK(hipGetLastError());
     return HPS_OK;
 }

@@ -812,19 +812,22 @@ extern "C" int hps_engine_set_beam_fixed_weight_pdf (void* h, const hps_beam_fix
                                                      unsigned long long seed, long n_left_out[2], double uz_moments[2])
 {
     HPS_REQUIRE(h, "hps_engine_set_beam_fixed_weight_pdf: null engine");
-    return static_cast<hps::Engine*>(h)->set_beam_fixed_weight_pdf(spec, pdf, progs, seed, n_left_out, uz_moments);
+    hps::Engine* E = static_cast<hps::Engine*>(h);
+    return E->fill_selected_species("hps_engine_set_beam_fixed_weight_pdf", [&] { return E->set_beam_fixed_weight_pdf(spec, pdf, progs, seed, n_left_out, uz_moments); });
 }
 
 extern "C" int hps_engine_set_beam_fixed_weight (void* h, const hps_beam_fixed_weight* spec, const hps_expr* mean_x_of_z,
                                                  const hps_expr* mean_y_of_z, unsigned long long seed, long n_left_out[2])
 {
     HPS_REQUIRE(h, "hps_engine_set_beam_fixed_weight: null engine");
-    return static_cast<hps::Engine*>(h)->set_beam_fixed_weight(spec, mean_x_of_z, mean_y_of_z, seed, n_left_out);
+    hps::Engine* E = static_cast<hps::Engine*>(h);
+    return E->fill_selected_species("hps_engine_set_beam_fixed_weight", [&] { return E->set_beam_fixed_weight(spec, mean_x_of_z, mean_y_of_z, seed, n_left_out); });
 }
 
 extern "C" int hps_engine_set_beam_fixed_ppc (void* h, const hps_expr* density, double min_density, const double u_std[3], const int random_ppc[3],
                                               unsigned long long seed)
 {
     HPS_REQUIRE(h, "hps_engine_set_beam_fixed_ppc: null engine");
-    return static_cast<hps::Engine*>(h)->set_beam_fixed_ppc(density, min_density, u_std, random_ppc, seed);
+    hps::Engine* E = static_cast<hps::Engine*>(h);
+    return E->fill_selected_species("hps_engine_set_beam_fixed_ppc", [&] { return E->set_beam_fixed_ppc(density, min_density, u_std, random_ppc, seed); });
 }

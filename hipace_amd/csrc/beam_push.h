@@ -1,7 +1,9 @@
 // beam_push.h -- the moving beam's slice push (AdvanceBeamParticlesSlice, particles/pusher/BeamParticleAdvance.cpp:20-336) as a
-// kernel template: beam.hip instantiates k_beam_push<ORDER, false>, the push of a deck without parsed external fields;
-// beam_ext.hip instantiates k_beam_push<ORDER, true>, which runs the expression programs of beams.external_E / external_B
-// (expr.h) at every sub-step, in a translation unit with compiler options of its own (Makefile).
+// kernel template: beam.hip instantiates k_beam_push<ORDER, false, MULTI>, the push of a deck without parsed external fields;
+// beam_ext.hip instantiates k_beam_push<ORDER, true, MULTI>, which runs the expression programs of beams.external_E / external_B
+// (expr.h) at every sub-step, in a translation unit with compiler options of its own (Makefile).  MULTI = true is
+// the push of an engine with several beam species: every lane takes charge / mass, the sub-cycle count and length,
+// do_z_push, the radiation reaction and the anomalous moment from its species' record; MULTI = false reads no tag and no table.
 #ifndef HPS_BEAM_PUSH_H_
 #define HPS_BEAM_PUSH_H_
 
@@ -30,12 +32,15 @@ struct BeamPushConsts {
 template <bool EXT> struct BeamExtArgs {};
 template <> struct BeamExtArgs<true> { const hps_expr_ins* ins; const double* consts; double t; };
 
+// The push's launch bookkeeping (Engine::beam_launched): bit (4*ORDER + 2*EXT + MULTI)
+constexpr unsigned long beam_push_bit (int order, bool ext, bool multi) { return 1UL << (4*order + 2*(ext ? 1 : 0) + (multi ? 1 : 0)); }
+
 // EXT = false is the push of a deck without programs.  EXT = true adds the programs' fields to the gathered ones; its dynamic
 // LDS is the operand stack of expr_run, (depth - 1) levels of blockDim.x doubles (expr.h).
-template <int ORDER, bool EXT>
+template <int ORDER, bool EXT, bool MULTI>
 __global__ __launch_bounds__(256)
 void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int cPsi, int cEz, int cBx, int cBy, int cBz,
-                  BeamPushConsts k, BeamExtArgs<EXT> ext)
+                  BeamPushConsts k, BeamExtArgs<EXT> ext, BeamMultiArgs<MULTI> multi)
 {
     constexpr int NS = ORDER + 2;
     const long first = B[p], count = B[p + 1] - first;       // slipped-in particles included (:131)
@@ -47,11 +52,18 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     if (k.spin) { s0 = b.sx[ip]; s1 = b.sy[ip]; s2 = b.sz[ip]; }
     bool absorbed = false;
-    for (; i < k.nsc; ++i) {
+    // the per-species constants: the launch's (one species), or this lane's record of the species table
+    double dt = k.dt, qm = k.qm, RRcoeff = k.RRcoeff, spin_anom = k.spin_anom;
+    int nsc = k.nsc, rr = k.rr, no_z_push = k.no_z_push;
+    if constexpr (MULTI) {
+        const BeamSpeciesRec& r = multi.tab[b.sp[ip]];
+        dt = r.dt; qm = r.qm; RRcoeff = r.RRcoeff; spin_anom = r.spin_anom; nsc = r.nsc; rr = r.rr; no_z_push = r.no_z_push;
+    }
+    for (; i < nsc; ++i) {
         if (zp < k.min_z) break;                              // not on this slice any more (:150-153)
         const double gi = 1.0/sqrt(1.0 + (ux*ux + uy*uy + uz*uz)*k.inv_c2);
-        xp += k.dt*0.5*ux*gi;
-        yp += k.dt*0.5*uy*gi;
+        xp += dt*0.5*ux*gi;
+        yp += dt*0.5*uy*gi;
         if (apply_particle_bc(k.pc, xp, yp, ux, uy)) { absorbed = true; break; }
         // beams.external_E / external_B as programs: the components that are present, at (xp, yp, zp, time of the step)
         // (ExternalFields.H:43-48).  Evaluated ahead of the gather, whose weights and sums then do not live across the interpreter.
@@ -98,10 +110,10 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
             Ez += e2;
             Bx += b0; By += b1; Bz += b2;
         }
-        double ux_next = ux + k.dt*k.qm*(ExmBy + (k.c - uz*gi)*By + uy*gi*Bz);
-        double uy_next = uy + k.dt*k.qm*(EypBx + (uz*gi - k.c)*Bx - ux*gi*Bz);
+        double ux_next = ux + dt*qm*(ExmBy + (k.c - uz*gi)*By + uy*gi*Bz);
+        double uy_next = uy + dt*qm*(EypBx + (uz*gi - k.c)*Bx - ux*gi*Bz);
         const double ux_i = (ux_next + ux)*0.5, uy_i = (uy_next + uy)*0.5;
-        const double uz_i = uz + k.dt*0.5*k.qm*Ez;
+        const double uz_i = uz + dt*0.5*qm*Ez;
         const double gii = 1.0/sqrt(1.0 + (ux_i*ux_i + uy_i*uy_i + uz_i*uz_i)*k.inv_c2);
         if (k.spin) {      // Thomas-BMT precession as a Boris-type rotation (:218-238)
             const double ic = 1.0/k.c;
@@ -111,10 +123,10 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
             const double gp1 = gii/(1.0 + gii);
             const double x0 = be1*E2_ - be2*E1_, x1 = be2*E0_ - be0*E2_, x2 = be0*E1_ - be1*E0_;      // beta x E
             const double bdB = be0*Bx + be1*By + be2*Bz;
-            const double aq = fabs(k.qm);
-            const double h0 = aq*(Bx*gii - x0*ic*gp1 + k.spin_anom*(Bx - gp1*u0*bdB - x0*ic))*k.dt*0.5;
-            const double h1 = aq*(By*gii - x1*ic*gp1 + k.spin_anom*(By - gp1*u1*bdB - x1*ic))*k.dt*0.5;
-            const double h2 = aq*(Bz*gii - x2*ic*gp1 + k.spin_anom*(Bz - gp1*u2*bdB - x2*ic))*k.dt*0.5;
+            const double aq = fabs(qm);
+            const double h0 = aq*(Bx*gii - x0*ic*gp1 + spin_anom*(Bx - gp1*u0*bdB - x0*ic))*dt*0.5;
+            const double h1 = aq*(By*gii - x1*ic*gp1 + spin_anom*(By - gp1*u1*bdB - x1*ic))*dt*0.5;
+            const double h2 = aq*(Bz*gii - x2*ic*gp1 + spin_anom*(Bz - gp1*u2*bdB - x2*ic))*dt*0.5;
             const double p0 = s0 + (h1*s2 - h2*s1), p1 = s1 + (h2*s0 - h0*s2), p2 = s2 + (h0*s1 - h1*s0);   // s' = s + h x s
             const double o = 1.0/(1.0 + (h0*h0 + h1*h1 + h2*h2));
             const double hd = h0*p0 + h1*p1 + h2*p2;
@@ -122,8 +134,8 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
             s1 = o*(p1 + (hd*h1 + (h2*p0 - h0*p2)));
             s2 = o*(p2 + (hd*h2 + (h0*p1 - h1*p0)));
         }
-        double uz_next = uz + k.dt*k.qm*(Ez + (ux_i*By - uy_i*Bx)*gii);
-        if (k.rr) {      // classical radiation reaction in SI quantities (:244-297)
+        double uz_next = uz + dt*qm*(Ez + (ux_i*By - uy_i*Bx)*gii);
+        if (rr) {      // classical radiation reaction in SI quantities (:244-297)
             const double icSI = 1.0/k.c_SI, ic = 1.0/k.c;
             double Ex = ExmBy + k.c*By, Ey = EypBx - k.c*Bx, Ezs = Ez, Bxs = Bx, Bys = By, Bzs = Bz;
             if (k.normalized) { Ex *= k.E0; Ey *= k.E0; Ezs *= k.E0; Bxs *= k.E0*icSI; Bys *= k.E0*icSI; Bzs *= k.E0*icSI; }
@@ -134,16 +146,16 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
             const double fl2 = flx*flx + fly*fly + flz*flz;
             const double bE = (bx*Ex + by*Ey + bz*Ezs);
             const double coeff = gam*gam*(fl2 - bE*bE);
-            const double frx = k.RRcoeff*(k.c_SI*(fly*Bzs - flz*Bys) + bE*Ex - coeff*bx);
-            const double fry = k.RRcoeff*(k.c_SI*(flz*Bxs - flx*Bzs) + bE*Ey - coeff*by);
-            const double frz = k.RRcoeff*(k.c_SI*(flx*Bys - fly*Bxs) + bE*Ezs - coeff*bz);
-            const double sc = k.dt*k.wp_inv*k.c*icSI;
+            const double frx = RRcoeff*(k.c_SI*(fly*Bzs - flz*Bys) + bE*Ex - coeff*bx);
+            const double fry = RRcoeff*(k.c_SI*(flz*Bxs - flx*Bzs) + bE*Ey - coeff*by);
+            const double frz = RRcoeff*(k.c_SI*(flx*Bys - fly*Bxs) + bE*Ezs - coeff*bz);
+            const double sc = dt*k.wp_inv*k.c*icSI;
             ux_next += frx*sc; uy_next += fry*sc; uz_next += frz*sc;
         }
         const double gni = 1.0/sqrt(1.0 + (ux_next*ux_next + uy_next*uy_next + uz_next*uz_next)*k.inv_c2);
-        xp += k.dt*0.5*ux_next*gni;
-        yp += k.dt*0.5*uy_next*gni;
-        if (!k.no_z_push) zp += k.dt*(uz_next*gni - k.c);     // do_z_push (:316)
+        xp += dt*0.5*ux_next*gni;
+        yp += dt*0.5*uy_next*gni;
+        if (!no_z_push) zp += dt*(uz_next*gni - k.c);     // do_z_push (:316)
         ux = ux_next; uy = uy_next; uz = uz_next;
     }
     if (absorbed || apply_particle_bc(k.pc, xp, yp, ux, uy)) { b.w[ip] = 0.0; b.nsub[ip] = -1; continue; }
@@ -156,7 +168,7 @@ void k_beam_push (SlabView f, BeamSoA b, const long* __restrict__ B, int p, int 
 #define HPS_BEAM_ORDER(order, CALL) switch (order) { case 0: { CALL(0); } break; case 1: { CALL(1); } break; \
                                                      case 2: { CALL(2); } break; default: { CALL(3); } break; }
 
-// beam_ext.hip: the launch of k_beam_push<ORDER, true> for slice p (256 lanes per workgroup, as `grid` was sized)
+// beam_ext.hip: the launch of k_beam_push<ORDER, true, MULTI> for slice p (256 lanes per workgroup, as `grid` was sized)
 int beam_push_launch_ext (Engine& E, const SlabView& f, int p, int cPsi, int cEz, int cBx, int cBy, int cBz, const BeamPushConsts& k, dim3 grid);
 
 } // namespace hps

@@ -672,6 +672,10 @@ extern "C" int hps_engine_add_beam_collision (void* h, int plasma_species, doubl
                                ": the plasma species is 0 (plasma) or 1 (ion)", plasma_species == 1,
                                ": at most HPS_MAX_COLLISIONS collisions, of both kinds together")) return e;
     Engine* E = static_cast<Engine*>(h);
+    if (E->multi_beam()) {
+        set_error("hps_engine_add_beam_collision: the engine holds several beam species (hps_engine_add_beam_species); the collision takes one beam's charge and mass");
+        return HPS_ERR_UNSUPPORTED;
+    }
     if (E->d.dt_adaptive) {
         set_error("hps_engine_add_beam_collision: hipace.dt = adaptive is not supported with a beam collision: the reference gathers the beam's "
                   "moments behind the collisions (GatherMinUzSlice, Hipace.cpp:713-716), the engine reduces them inside k_beam_partition, ahead of them");

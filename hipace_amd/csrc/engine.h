@@ -6,6 +6,7 @@
 #include "expr.h"
 #include <algorithm>
 #include <array>
+#include <string>
 #include <vector>
 #include "tiling.h"
 #include "mg_gate.h"
@@ -67,7 +68,16 @@ private:
 };
 
 struct BeamSoA { double *x, *y, *z, *ux, *uy, *uz, *w; int* nsub;      // moving beam (beam.hip); nsub < 0: absorbed
-                 double *sx, *sy, *sz; };                              // spin (do_spin_tracking), null otherwise
+                 double *sx, *sy, *sz;                                 // spin (do_spin_tracking), null otherwise
+                 unsigned char* sp; };                                 // species tag, null in a one-species engine
+
+// Several beam species in one container (hps_engine_add_beam_species): what the push and the deposit take per species,
+// one record per species in a small device table (Engine::d_bsp_tab) that every lane of a MULTI kernel indexes with its tag.
+struct BeamSpeciesRec { double q_invvol, qm, dt, RRcoeff, spin_anom; int nsc, rr, no_z_push; };
+struct BeamSpeciesTable { BeamSpeciesRec r[HPS_MAX_BEAM_SPECIES]; };
+// the table as a kernel argument: nothing in the kernels of a one-species engine
+template <bool MULTI> struct BeamMultiArgs {};
+template <> struct BeamMultiArgs<true> { const BeamSpeciesRec* tab; int ns; };
 
 // cell lists of the collision kernels (collisions.hip): per species slot the exclusive cell offsets [ncells + 1] and the
 // cell-sorted particle indices; cnt [ncells + 1] is shared (zero between launches); stats = {pairs collided, overfull cells}
@@ -77,6 +87,10 @@ struct CollScratch {
     CollScratch () = default; CollScratch (const CollScratch&) = delete; CollScratch& operator= (const CollScratch&) = delete;
     ~CollScratch ();
 };
+
+// the container's blocks, offsets, tags and particle count set aside while a setter builds the next species' beam
+struct BeamStash { double* blocks = nullptr; unsigned char* tag = nullptr; std::vector<long> off; long n = 0; bool host_beam = false;
+                   double charge = 0.0, mass = 0.0; };
 
 struct Engine {
     hps_deck d{};
@@ -164,7 +178,24 @@ struct Engine {
     int init_sheet (Species& s);               // InitParticles of one species' sheet: the warm, the fine or the plain kernel
     int sort_sheet (Species& s);               // tile sort into the second buffer, then the two change places
     bool host_beam = false;        // hps_engine_set_beam_particles has given the beam
-    double* d_mom = nullptr;       // hipace.dt = adaptive: beam moments [nz + 1][4] (beam.hip: k_beam_partition<true>)
+    double* d_mom = nullptr;       // hipace.dt = adaptive: beam moments [nz + 1][n species][4] (beam.hip: k_beam_partition<true>)
+    // Beam species.  bsp[0] is the deck's beam; hps_engine_add_beam_species appends.  With more than one the container
+    // carries a tag row (bm.sp, its twin for the partition bm_scr.sp) and the beam kernels are the MULTI instantiations, which read
+    // the per-species constants from d_bsp_tab (written once per step: the sub-cycle's dt is the step's).  beam_tag: the tags in the
+    // order of beam_init's blocks (null: all 0); sel_species: whom the beam setters fill (hps_engine_select_beam_species).
+    struct BeamSpecies { hps_beam_species s{}; long count = 0; bool filled = false; };
+    std::vector<BeamSpecies> bsp; int sel_species = 0;
+    unsigned char *bm_sp = nullptr, *bm_sp_scr = nullptr, *beam_tag = nullptr; BeamSpeciesRec* d_bsp_tab = nullptr;
+    unsigned long beam_launched = 0;      // which beam kernel instances this engine has launched (beam.hip: beam_kernel_names)
+    int n_beam_species () const { return std::max<int>(1, (int)bsp.size()); }
+    bool multi_beam () const { return bsp.size() > 1; }
+    int add_beam_species (const hps_beam_species* s, int* index_out);
+    int alloc_beam_tags ();                                             // bm.sp and its twin for the container as it is (zeroed)
+    // a beam setter's work `set` for the selected species: species 0 -> as it was; k > 0 -> the setter builds k's beam with k's
+    // charge and mass through the one install tail, then k_beam_merge puts it behind what the container held (beam.hip)
+    template <class F> int fill_selected_species (const char* fn, F&& set);
+    int stash_beam_for_merge (const char* fn, BeamStash& A);
+    int merge_stashed_beam (BeamStash& A, int e_setter);
     IonArgs ion_args (int islice);             // ionization.hip: kernel arguments of this slice's ionisation
     int ionize_slice (int islice);             // ...: launch of the per-particle form
     int ionize_collect ();                     // ...: wait for the electron count of the slice
@@ -334,6 +365,21 @@ struct Engine {
     int collide_slice (int islice);
 };
 
+template <class F> int Engine::fill_selected_species (const char* fn, F&& set)
+{
+    if (sel_species == 0) {
+        for (size_t k = 1; k < bsp.size(); ++k)
+            HPS_REQUIRE(!bsp[k].filled, std::string(fn) + ": species 0 cannot be replaced once another beam species holds particles");
+        const int e = set();
+        if (!bsp.empty()) { bsp[0].count = nbeam; bsp[0].filled = e == HPS_OK && nbeam > 0; }
+        if (e == HPS_OK && multi_beam()) return alloc_beam_tags();
+        return e;
+    }
+    BeamStash A;
+    if (int e = stash_beam_for_merge(fn, A)) return e;
+    return merge_stashed_beam(A, set());
+}
+
 int ion_create (Engine& E);                                                  // ionization.hip
 void ion_destroy (Engine& E);
 unsigned event_flags (bool timing);                                           // engine.hip
@@ -373,6 +419,8 @@ int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz);      // b
 int beam_push_moving (Engine& E, int islice);
 int beam_push_slice (Engine& E, int islice, int p, long bound);
 int beam_moments_reset (Engine& E);
+int beam_species_table_upload (Engine& E);                                  // the per-species constants of the step that has begun
+std::string beam_kernel_names (const Engine& E);                            // the beam kernel instances launched so far, one per line
 int beam_export_slice (Engine& E, int islice, double* msg_dev, long cap);
 int beam_import_slice (Engine& E, int islice, const double* msg_dev, long cap);
 int salame_get_w_enqueue (const hps_slab& slab, int cT, int cN, int cE, int cJ, double* scratch, hipStream_t st);      // salame.hip

@@ -334,7 +334,7 @@ Engine::~Engine ()
     delete el.tiling;
     (void)hipFree(staging); (void)hipFree(d_open_mom); (void)hipFree(beam_data); (void)hipFree(beam_init);
     (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr); (void)hipFree(d_B); (void)hipFree(d_nfront);
-    (void)hipFree(d_mom); (void)hipFree(d_sal);
+    (void)hipFree(d_mom); (void)hipFree(d_sal); (void)hipFree(bm_sp); (void)hipFree(bm_sp_scr); (void)hipFree(beam_tag); (void)hipFree(d_bsp_tab);
     (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow); (void)hipFree(d_nqsa); (void)hipFree(d_checksum);
     (void)hipFree(d_pc); (void)hipFree(d_pc_aux); (void)hipFree(d_pc_go); if (h_pc) (void)hipHostFree(h_pc);
     (void)hipFree(d_laser_sum);
@@ -443,6 +443,7 @@ void Engine::release_beam ()
     (void)hipFree(d_B); (void)hipFree(d_nfront); (void)hipFree(d_Bimp); (void)hipFree(d_beam_overflow);
     beam_data = beam_init = beam_cur = nullptr; bm_store = nullptr; bm_nsub = bm_nsub_scr = nullptr;
     d_B = nullptr; d_nfront = nullptr; d_Bimp = nullptr; d_beam_overflow = nullptr;
+    (void)hipFree(bm_sp); (void)hipFree(bm_sp_scr); (void)hipFree(beam_tag); bm_sp = bm_sp_scr = beam_tag = nullptr;      // (several species: the tag rows)
 }
 
 // support of the beam's currents from the extent of its nbeam particles
@@ -519,10 +520,10 @@ int Engine::install_moving_beam (const std::vector<double> (*h)[7])
         HPS_HIP_CHECK(hipMalloc(&bm_nsub_scr, (size_t)nb*sizeof(int)));
         double* a = bm_store;
         bm = BeamSoA{a, a + nb, a + 2*nb, a + 3*nb, a + 4*nb, a + 5*nb, a + 6*nb, bm_nsub,
-                     spin ? a + 7*nb : nullptr, spin ? a + 8*nb : nullptr, spin ? a + 9*nb : nullptr};
+                     spin ? a + 7*nb : nullptr, spin ? a + 8*nb : nullptr, spin ? a + 9*nb : nullptr, nullptr};
         a += (size_t)beam_rows*nb;
         bm_scr = BeamSoA{a, a + nb, a + 2*nb, a + 3*nb, a + 4*nb, a + 5*nb, a + 6*nb, bm_nsub_scr,
-                         spin ? a + 7*nb : nullptr, spin ? a + 8*nb : nullptr, spin ? a + 9*nb : nullptr};
+                         spin ? a + 7*nb : nullptr, spin ? a + 8*nb : nullptr, spin ? a + 9*nb : nullptr, nullptr};
         if (spin && nbeam > 0) {       // initial_spin, normalised, for every particle (BeamParticleContainer.cpp:390-402)
             const double* s0 = d.beam_initial_spin;
             const double nrm = std::sqrt(s0[0]*s0[0] + s0[1]*s0[1] + s0[2]*s0[2]);
@@ -550,10 +551,11 @@ int Engine::install_moving_beam (const std::vector<double> (*h)[7])
         for (int p = 0; p < d.nz; ++p) mx = std::max(mx, beam_off[p + 1] - beam_off[p]);
         beam_cap = std::max(2*mx, 1L);                 // particles a slice may hold in a hand-off message
         if (nbeam > 0) beam_box = beam_box_init = full_box;          // a moving beam may go anywhere (no beam at all, e.g. a laser driver: the box stays empty)
-        if (d.dt_adaptive && !d_mom) {
-            HPS_HIP_CHECK(hipMalloc(&d_mom, (size_t)4*(d.nz + 1)*sizeof(double)));
+        if (d.dt_adaptive && !d_mom) {      // (room for HPS_MAX_BEAM_SPECIES; the slots in use are [nz + 1][species][4])
+            HPS_HIP_CHECK(hipMalloc(&d_mom, (size_t)4*HPS_MAX_BEAM_SPECIES*(d.nz + 1)*sizeof(double)));
             if (int e = beam_moments_reset(*this)) return e;
         }
+        if (multi_beam()) { if (int e = alloc_beam_tags()) return e; }      // the tag row: beam_tag's, or species 0 throughout
     }
     return HPS_OK;
 }
@@ -1002,7 +1004,7 @@ int Engine::begin_step ()
     if (int e = join_laser()) return e;        // the time levels rotate: the last slice's envelope must be in
     if (laser) { if (int e = laser_begin_step(*this)) return e; }
     if (d_insitu_pl) HPS_HIP_CHECK(hipMemsetAsync(d_insitu_pl, 0, (size_t)15*d.nz*sizeof(double), st));
-    if (d_insitu_bm) HPS_HIP_CHECK(hipMemsetAsync(d_insitu_bm, 0, (size_t)23*d.nz*sizeof(double), st));
+    if (d_insitu_bm) HPS_HIP_CHECK(hipMemsetAsync(d_insitu_bm, 0, (size_t)23*d.nz*n_beam_species()*sizeof(double), st));
     if (d_insitu) HPS_HIP_CHECK(hipMemsetAsync(d_insitu, 0, (size_t)10*d.nz*sizeof(double), st));
     if (insitu_laser && laser) { if (int e = laser_clear_insitu(*this)) return e; }
     if (d_fd) HPS_HIP_CHECK(hipMemsetAsync(d_fd, 0, fd_comps.size()*fd_cells()*sizeof(double), st));
@@ -1011,6 +1013,11 @@ int Engine::begin_step ()
     ahead_for = -2;
     if (salame_now()) { sal_last_slice = -2; sal_overloaded = false; std::fill(sal_stats.begin(), sal_stats.end(), 0.0); }
     if (d_mom) { if (int e = beam_moments_reset(*this)) return e; }
+    if (multi_beam() && !bsp.empty()) {
+        long filled = 0;
+        for (const BeamSpecies& b : bsp) filled += b.count;
+        HPS_REQUIRE(filled == nbeam || beam_import, "hps_engine_begin_step: the beam species' particle counts do not add up to the container's");
+    }
     // time factor of the density profile at z = c t of this step (UpdateDensityFunction, PlasmaParticleContainer.cpp:211-217)
     if (time_set) {          // hps_engine_set_time
         step_dt = next_dt; step_time = next_t;
@@ -1022,6 +1029,7 @@ int Engine::begin_step ()
         prof_ft = table_value(prof_t.data(), prof_f_t.data(), (int)prof_t.size(), gm.c*d.dt*step_index);
         density_begin_step(gm.c*d.dt*step_index);
     }
+    if (int e = beam_species_table_upload(*this)) return e;      // several beam species: their constants at this step's dt
     if (laser && lgrid.set) { if (int e = laser_chi_initial(*this)) return e; }      // SetInitialChi: density(x, y, c t) of this step
     if (int e = ionize_collect()) return e;
     el.pl.n = el.n_init;
@@ -1270,9 +1278,13 @@ void k_insitu_plasma (hps_plasma pl, double clight_inv, double radius_sq, double
 // BeamParticleContainer::InSituComputeDiags (particles/beam/BeamParticleContainer.cpp:476-556): raw sums over the
 // particles of the slice (slipped-in ones excluded, :494).  Static beam: count_static particles behind b; moving beam:
 // the block [B[p] + nfront[p], B[p+1]) of the SoA, nsub < 0 = absorbed.
+// MULTI (several beam species): the workgroups of blockIdx.y = s reduce the particles tagged s into species s's
+// block of `out` ([species][23][nz]) -- still one launch per slice.
+template <bool MULTI>
 __global__ __launch_bounds__(256)
 void k_insitu_beam (BeamView b, const int* __restrict__ nsub, const long* __restrict__ B, const int* __restrict__ nfront, int p,
-                    long count_static, double clight_inv, double radius_sq, double* out, int nz, int islice, int skip_zero_w = 0)
+                    long count_static, double clight_inv, double radius_sq, double* out, int nz, int islice, int skip_zero_w,
+                    const unsigned char* __restrict__ sp)
 {
     // skip_zero_w (SALAME deck): a particle whose weight SALAME has set to 0 no longer exists (the reference invalidates it)
     long first = 0, count = count_static;
@@ -1284,6 +1296,7 @@ void k_insitu_beam (BeamView b, const int* __restrict__ nsub, const long* __rest
         const long ip = first + t;
         const double x = b.x[ip], y = b.y[ip], z = b.z[ip];
         if ((nsub && nsub[ip] < 0) || x*x + y*y > radius_sq || (skip_zero_w && b.w[ip] == 0.0)) continue;
+        if constexpr (MULTI) { if (sp[ip] != blockIdx.y) continue; }
         const double ux = b.ux[ip]*clight_inv, uy = b.uy[ip]*clight_inv, uz = b.uz[ip]*clight_inv, w = b.w[ip];
         const double uz_inv = uz == 0.0 ? 0.0 : 1.0/uz;
         const double gamma = sqrt(1.0 + ux*ux + uy*uy + uz*uz);
@@ -1302,7 +1315,7 @@ void k_insitu_beam (BeamView b, const int* __restrict__ nsub, const long* __rest
     __syncthreads();
     if (threadIdx.x < 23) {
         const double v = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-        if (v != 0.0) atomic_add_f64(out + (long)threadIdx.x*nz + islice, v);
+        if (v != 0.0) atomic_add_f64(out + (MULTI ? (long)blockIdx.y*23*nz : 0L) + (long)threadIdx.x*nz + islice, v);
     }
 }
 
@@ -1316,15 +1329,21 @@ void Engine::insitu_beam (int islice)
         const long bound = beam_bound(p);
         if (bound <= 0) return;
         const BeamView b{bm.x, bm.y, bm.z, bm.ux, bm.uy, bm.uz, bm.w};
-        hipLaunchKernelGGL(k_insitu_beam, dim3((unsigned)std::min<long>(ceil_div(bound, 256), 64)), dim3(256), 0, st, b, bm.nsub, d_B, d_nfront, p,
-                           0L, 1.0/gm.c, r2, d_insitu_bm, d.nz, islice);
+        const unsigned nwg = (unsigned)std::min<long>(ceil_div(bound, 256), 64);
+        if (multi_beam())
+            hipLaunchKernelGGL(k_insitu_beam<true>, dim3(nwg, (unsigned)n_beam_species()), dim3(256), 0, st, b, bm.nsub, d_B, d_nfront, p,
+                               0L, 1.0/gm.c, r2, d_insitu_bm, d.nz, islice, 0, bm.sp);
+        else
+            hipLaunchKernelGGL(k_insitu_beam<false>, dim3(nwg), dim3(256), 0, st, b, bm.nsub, d_B, d_nfront, p,
+                               0L, 1.0/gm.c, r2, d_insitu_bm, d.nz, islice, 0, (const unsigned char*)nullptr);
     } else {
         const long first0 = beam_off[d.nz - 1 - islice], count = beam_off[d.nz - islice] - first0;
         if (count <= 0) return;
         double* blk = beam_cur + 7*first0;
         const BeamView b{blk, blk + count, blk + 2*count, blk + 3*count, blk + 4*count, blk + 5*count, blk + 6*count};
-        hipLaunchKernelGGL(k_insitu_beam, dim3((unsigned)std::min<long>(ceil_div(count, 256), 64)), dim3(256), 0, st, b, (const int*)nullptr,
-                           (const long*)nullptr, (const int*)nullptr, 0, count, 1.0/gm.c, r2, d_insitu_bm, d.nz, islice, c_sal >= 0 ? 1 : 0);
+        hipLaunchKernelGGL(k_insitu_beam<false>, dim3((unsigned)std::min<long>(ceil_div(count, 256), 64)), dim3(256), 0, st, b, (const int*)nullptr,
+                           (const long*)nullptr, (const int*)nullptr, 0, count, 1.0/gm.c, r2, d_insitu_bm, d.nz, islice, c_sal >= 0 ? 1 : 0,
+                           (const unsigned char*)nullptr);
     }
 }
 
@@ -2451,17 +2470,25 @@ extern "C" int hps_engine_set_insitu_beam (void* h, double radius)
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     (void)hipFree(E->d_insitu_bm); E->d_insitu_bm = nullptr; E->insitu_bm_radius = radius;
     if (!(radius > 0.0)) return HPS_OK;
-    HPS_HIP_CHECK(hipMalloc(&E->d_insitu_bm, (size_t)23*E->d.nz*sizeof(double)));
-    HPS_HIP_CHECK(hipMemset(E->d_insitu_bm, 0, (size_t)23*E->d.nz*sizeof(double)));
+    // (room for HPS_MAX_BEAM_SPECIES blocks [23][nz]: species may still be added)
+    HPS_HIP_CHECK(hipMalloc(&E->d_insitu_bm, (size_t)23*E->d.nz*HPS_MAX_BEAM_SPECIES*sizeof(double)));
+    HPS_HIP_CHECK(hipMemset(E->d_insitu_bm, 0, (size_t)23*E->d.nz*HPS_MAX_BEAM_SPECIES*sizeof(double)));
     return HPS_OK;
 }
 extern "C" int hps_engine_insitu_beam (void* h, double* out)
 {
     Engine* E = static_cast<Engine*>(h);
-    HPS_REQUIRE(E->d_insitu_bm && out, "hps_engine_insitu_beam: not switched on");
+    HPS_REQUIRE(E && !E->multi_beam(), "hps_engine_insitu_beam: the engine holds several beam species: hps_engine_insitu_beam_species returns one of them");
+    return hps_engine_insitu_beam_species(h, 0, out);
+}
+extern "C" int hps_engine_insitu_beam_species (void* h, int species, double* out)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->d_insitu_bm && out, "hps_engine_insitu_beam: not switched on");
+    HPS_REQUIRE(species >= 0 && species < E->n_beam_species(), "hps_engine_insitu_beam_species: no such beam species");
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     const int nz = E->d.nz;
-    HPS_HIP_CHECK(hipMemcpy(out, E->d_insitu_bm, (size_t)23*nz*sizeof(double), hipMemcpyDeviceToHost));
+    HPS_HIP_CHECK(hipMemcpy(out, E->d_insitu_bm + (size_t)species*23*nz, (size_t)23*nz*sizeof(double), hipMemcpyDeviceToHost));
     // averages: everything but sum(w) and the count is divided by sum(w) (BeamParticleContainer.cpp:542-548)
     for (int k = 0; k < nz; ++k) {
         const double sw = out[k], inv = sw <= 0.0 ? 0.0 : 1.0/sw;
@@ -2616,6 +2643,7 @@ extern "C" int hps_engine_beam_moments (void* h, double* out4)
     Engine* E = static_cast<Engine*>(h);
     HPS_REQUIRE(E && out4, "hps_engine_beam_moments: null argument");
     HPS_REQUIRE(E->d_mom, "hps_engine_beam_moments: the deck has no adaptive time step (dt_adaptive)");
+    HPS_REQUIRE(!E->multi_beam(), "hps_engine_beam_moments: the engine holds several beam species, whose moments are never summed: hps_engine_beam_moments_species");
     HPS_HIP_CHECK(hipMemcpyAsync(out4, E->d_mom + 4*E->d.nz, 4*sizeof(double), hipMemcpyDeviceToHost, E->st));
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     return HPS_OK;
@@ -2870,7 +2898,7 @@ extern "C" int hps_engine_set_beam_capacity (void* h, long cap)
 }
 extern "C" int hps_engine_beam_message_rows (void* h, int* rows)
 {
-    *rows = static_cast<Engine*>(h)->beam_rows;
+    *rows = static_cast<Engine*>(h)->beam_rows + (static_cast<Engine*>(h)->multi_beam() ? 1 : 0);      // (several species: one row for the tag)
     return HPS_OK;
 }
 extern "C" int hps_engine_beam_spin (void* h, double* soa_host)
@@ -2905,6 +2933,7 @@ extern "C" int hps_engine_import_beam_slice (void* h, int islice, const double* 
 extern "C" int hps_engine_beam_state (void* h, long* boundaries_host, double* soa_host)
 {
     Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(!E->multi_beam(), "hps_engine_beam_state: the engine holds several beam species: hps_engine_beam_state_species returns one of them");
     if (!E->moving) {
         // static beam: the slice-major blocks [slice p][7][count_p] gathered into the same global layout
         HPS_HIP_CHECK(hipStreamSynchronize(E->st));
@@ -2969,7 +2998,8 @@ extern "C" int hps_engine_initial_beam (void* h, double* dst_dev)
 extern "C" int hps_engine_set_beam_particles (void* h, long n, const double* soa_host, long* n_outside)
 {
     HPS_REQUIRE(h, "hps_engine_set_beam_particles: null engine");
-    return static_cast<Engine*>(h)->set_beam_particles(n, soa_host, n_outside);
+    Engine* E = static_cast<Engine*>(h);
+    return E->fill_selected_species("hps_engine_set_beam_particles", [&] { return E->set_beam_particles(n, soa_host, n_outside); });
 }
 extern "C" int hps_engine_set_tiling (void* h, int tile_size, int sort_period)
 {
@@ -3043,5 +3073,100 @@ extern "C" int hps_device_count (int* n)
     int c = 0;
     if (hipGetDeviceCount(&c) != hipSuccess) c = 0;
     *n = c;
+    return HPS_OK;
+}
+
+// ---- several beam species (the kernels and the merge: beam.hip) ----------------------------------------------------
+extern "C" int hps_engine_add_beam_species (void* h, const hps_beam_species* species, int* index_out)
+{
+    HPS_REQUIRE(h, "hps_engine_add_beam_species: null engine");
+    return static_cast<Engine*>(h)->add_beam_species(species, index_out);
+}
+extern "C" int hps_engine_select_beam_species (void* h, int k)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E, "hps_engine_select_beam_species: null engine");
+    HPS_REQUIRE(k >= 0 && k < E->n_beam_species(), "hps_engine_select_beam_species: no such beam species (hps_engine_add_beam_species gives the numbers)");
+    E->sel_species = k;
+    return HPS_OK;
+}
+extern "C" int hps_engine_beam_species_info (void* h, int* n_host, long* counts_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E, "hps_engine_beam_species_info: null engine");
+    if (n_host) *n_host = E->n_beam_species();
+    if (counts_host) {
+        if (E->bsp.empty()) counts_host[0] = E->nbeam;
+        for (size_t k = 0; k < E->bsp.size(); ++k) counts_host[k] = E->bsp[k].count;
+    }
+    return HPS_OK;
+}
+extern "C" int hps_engine_beam_state_species (void* h, int k, long* count_host, long* boundaries_host, double* soa_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E, "hps_engine_beam_state_species: null engine");
+    HPS_REQUIRE(k >= -1 && k < E->n_beam_species(), "hps_engine_beam_state_species: no such beam species");
+    if (k == -1 && E->multi_beam()) {      // the whole container, whatever the species
+        HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+        if (count_host) *count_host = E->nbeam;
+        if (boundaries_host) HPS_HIP_CHECK(hipMemcpy(boundaries_host, E->d_B, (size_t)(E->d.nz + 1)*sizeof(long), hipMemcpyDeviceToHost));
+        for (int q = 0; soa_host && q < 7 && E->nbeam > 0; ++q)
+            HPS_HIP_CHECK(hipMemcpy(soa_host + (size_t)q*E->nbeam, E->bm_store + (size_t)q*E->nbeam, E->nbeam*sizeof(double), hipMemcpyDeviceToHost));
+        return HPS_OK;
+    }
+    if (!E->multi_beam()) {
+        if (count_host) *count_host = E->nbeam;
+        return hps_engine_beam_state(h, boundaries_host, soa_host);
+    }
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    const int nz = E->d.nz; const long nb = E->nbeam, cnt = E->bsp[(size_t)k].count;
+    if (count_host) *count_host = cnt;
+    if (!boundaries_host && !soa_host) return HPS_OK;
+    std::vector<long> B((size_t)nz + 1, 0); std::vector<unsigned char> tag((size_t)std::max(nb, 1L)); std::vector<double> row;
+    HPS_HIP_CHECK(hipMemcpy(B.data(), E->d_B, B.size()*sizeof(long), hipMemcpyDeviceToHost));
+    if (nb > 0) HPS_HIP_CHECK(hipMemcpy(tag.data(), E->bm_sp, (size_t)nb, hipMemcpyDeviceToHost));
+    if (boundaries_host) {
+        long j = 0; boundaries_host[0] = 0;
+        for (int p = 0; p < nz; ++p) { for (long i = B[(size_t)p]; i < B[(size_t)p + 1]; ++i) j += tag[(size_t)i] == k; boundaries_host[p + 1] = j; }
+        HPS_REQUIRE(j == cnt, "hps_engine_beam_state_species: the container's tags do not hold the species' particle count");
+    }
+    if (soa_host && cnt > 0) {
+        row.resize((size_t)nb);
+        for (int q = 0; q < 7; ++q) {
+            HPS_HIP_CHECK(hipMemcpy(row.data(), E->bm_store + (size_t)q*std::max(nb, 1L), (size_t)nb*sizeof(double), hipMemcpyDeviceToHost));
+            long j = 0;
+            for (long i = B[0]; i < B[(size_t)nz] && j < cnt; ++i) if (tag[(size_t)i] == k) soa_host[(size_t)q*cnt + j++] = row[(size_t)i];
+        }
+    }
+    return HPS_OK;
+}
+extern "C" int hps_engine_beam_moments_species (void* h, double* out_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && out_host, "hps_engine_beam_moments_species: null argument");
+    HPS_REQUIRE(E->d_mom, "hps_engine_beam_moments_species: the deck has no adaptive time step (dt_adaptive)");
+    const int ns = E->n_beam_species();
+    HPS_HIP_CHECK(hipMemcpyAsync(out_host, E->d_mom + (size_t)4*ns*E->d.nz, (size_t)4*ns*sizeof(double), hipMemcpyDeviceToHost, E->st));
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    return HPS_OK;
+}
+extern "C" int hps_engine_beam_tags (void* h, unsigned char* tags_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && tags_host, "hps_engine_beam_tags: null argument");
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    if (E->nbeam == 0) return HPS_OK;
+    if (!E->bm.sp) { std::memset(tags_host, 0, (size_t)E->nbeam); return HPS_OK; }
+    HPS_HIP_CHECK(hipMemcpy(tags_host, E->bm.sp, (size_t)E->nbeam, hipMemcpyDeviceToHost));
+    return HPS_OK;
+}
+extern "C" int hps_engine_beam_kernels (void* h, char* buf, long cap, long* len, int* tagged)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E, "hps_engine_beam_kernels: null engine");
+    const std::string all = beam_kernel_names(*E);
+    if (len) *len = (long)all.size();
+    if (tagged) *tagged = E->bm.sp != nullptr ? 1 : 0;
+    if (buf && cap > 0) { const size_t n = std::min<size_t>(all.size(), (size_t)cap - 1); std::memcpy(buf, all.data(), n); buf[n] = 0; }
     return HPS_OK;
 }

@@ -178,6 +178,88 @@ def beam_fixed_weight(deck):
     return dict(BEAM_FIXED_WEIGHT_DEFAULT, **entry)
 
 
+# Further beam species of a moving-beam engine (beams.names = driver witness).  A deck's optional entry "beam_species"
+# is a list of dicts of these keys -- the arguments of SliceEngine.add_beam_species, which SliceEngine applies, in order, behind the
+# deck's own beam (species 0).  charge and mass default to the deck's beam_charge and beam_mass, the other constants to the
+# deck's.  Exactly one source: fixed_weight (the keys of BEAM_FIXED_WEIGHT_DEFAULT), fixed_weight_pdf (those of
+# BEAM_FIXED_WEIGHT_PDF_DEFAULT), density_expr (with the keys of BEAM_INIT_DEFAULT but the expression: constants, min_density,
+# u_std, random_ppc, seed) or particles (a (7, n) array x y z ux uy uz w).  It is no member of _DEFAULT or hps_deck.
+BEAM_SPECIES_DEFAULT = dict(name=None, charge=None, mass=None, n_subcycles=None, do_z_push=None, radiation_reaction=None,
+                            spin_anom=None, do_spin_tracking=None, uz_mean=0.0, uz_std=0.0)
+BEAM_SPECIES_SOURCES = ("fixed_weight", "fixed_weight_pdf", "density_expr", "particles")
+BEAM_SPECIES_EXPR_KEYS = ("constants", "min_density", "u_std", "random_ppc", "seed")
+MAX_BEAM_SPECIES = 4
+
+
+def beam_species_spec(deck, spec, where="beam_species"):
+    """One beam species over BEAM_SPECIES_DEFAULT and the deck's own beam constants -> dict(name, record, source, args):
+    record = the fields of hps_beam_species, source one of BEAM_SPECIES_SOURCES, args its setter's arguments.  ValueError:
+    unknown keys, no source or several, unknown keys inside the source's dict."""
+    allowed = set(BEAM_SPECIES_DEFAULT) | set(BEAM_SPECIES_SOURCES) | set(BEAM_SPECIES_EXPR_KEYS)
+    unknown = set(spec) - allowed
+    if unknown:
+        raise ValueError(f"{where}: unknown entries {sorted(unknown)}")
+    given = [k for k in BEAM_SPECIES_SOURCES if spec.get(k) is not None]
+    if len(given) != 1:
+        raise ValueError(f"{where}: exactly one source of {', '.join(BEAM_SPECIES_SOURCES)} is needed, got {given or 'none'}")
+    source = given[0]
+    stray = [k for k in BEAM_SPECIES_EXPR_KEYS if k in spec and source != "density_expr"]
+    if stray:
+        raise ValueError(f"{where}: {', '.join(stray)} go with density_expr, not with {source}")
+
+    def pick(key, deck_key, default):
+        v = spec.get(key)
+        return deck.get(deck_key, default) if v is None else v
+    do_z_push = spec.get("do_z_push")
+    record = dict(charge=float(pick("charge", "beam_charge", -1.0)), mass=float(pick("mass", "beam_mass", 1.0)),
+                  n_subcycles=int(pick("n_subcycles", "beam_n_subcycles", 10)),
+                  no_z_push=int(deck.get("beam_no_z_push", 0)) if do_z_push is None else int(not do_z_push),
+                  radiation_reaction=int(bool(pick("radiation_reaction", "beam_radiation_reaction", 0))),
+                  do_spin_tracking=int(bool(pick("do_spin_tracking", "beam_spin_tracking", 0))),
+                  spin_anom=float(pick("spin_anom", "beam_spin_anom", 0.0)),
+                  uz_mean=float(spec.get("uz_mean", 0.0) or 0.0), uz_std=float(spec.get("uz_std", 0.0) or 0.0))
+    if source == "fixed_weight":
+        bad = set(spec[source]) - set(BEAM_FIXED_WEIGHT_DEFAULT)
+        args = dict(BEAM_FIXED_WEIGHT_DEFAULT, **spec[source])
+    elif source == "fixed_weight_pdf":
+        bad = set(spec[source]) - set(BEAM_FIXED_WEIGHT_PDF_DEFAULT)
+        args = dict(BEAM_FIXED_WEIGHT_PDF_DEFAULT, **spec[source])
+    elif source == "density_expr":
+        bad = set()
+        args = dict(expr=spec[source], constants=spec.get("constants"), min_density=float(spec.get("min_density", 0.0) or 0.0),
+                    u_std=tuple(spec.get("u_std") or (0.0, 0.0, 0.0)), random_ppc=tuple(spec.get("random_ppc") or (0, 0, 0)),
+                    seed=int(spec.get("seed", 1)))
+    else:
+        bad = set()
+        shape = getattr(spec[source], "shape", None)
+        if shape is None or len(shape) != 2 or shape[0] != 7:
+            raise ValueError(f"{where}: particles is a (7, n) array x y z ux uy uz w")
+        args = dict(soa=spec[source])
+    if bad:
+        raise ValueError(f"{where}: {source}: unknown entries {sorted(bad)}")
+    if source == "fixed_weight" and "uz_mean" not in spec and "uz_std" not in spec:
+        record["uz_mean"], record["uz_std"] = float(args["u_mean"][2]), float(args["u_std"][2])      # the source's own u_z
+    # (fixed_weight_pdf: u_z may be a function of z; SliceEngine takes the pdf-weighted moments its setter returns)
+    return dict(name=spec.get("name"), record=record, source=source, args=args)
+
+
+def beam_species(deck):
+    """The deck's entry beam_species as a list of beam_species_spec results ([] for a deck without it).  ValueError: what
+    beam_species_spec refuses, more species than the engine holds beside the deck's beam, a name given twice."""
+    entry = deck.get("beam_species")
+    if entry is None:
+        return []
+    if isinstance(entry, dict) or not hasattr(entry, "__len__"):
+        raise ValueError("beam_species: a list of dicts, one per species")
+    if len(entry) > MAX_BEAM_SPECIES - 1:
+        raise ValueError(f"beam_species: at most {MAX_BEAM_SPECIES - 1} species beside the deck's own beam")
+    out = [beam_species_spec(deck, s, f"beam_species[{k}]") for k, s in enumerate(entry)]
+    names = [s["name"] for s in out if s["name"] is not None]
+    if len(set(names)) != len(names):
+        raise ValueError(f"beam_species: a name is given twice ({names})")
+    return out
+
+
 def with_fixed_weight_beam(deck, beam=None, **more):
     """A copy of deck with the entry beam_fixed_weight, from the keyword names of fixed_weight_beam (num_particles, density,
     total_charge, pos_mean, pos_std, u_mean, u_std, zmin, zmax, radius, seed, do_symmetrize, duz_per_uz0_dzeta): the (deck, beam)
@@ -1046,6 +1128,31 @@ LWFA_CONSTANTS = dict(kp_inv="clight/wp", kp="wp/clight", wp="sqrt( ne * q_e^2/(
 LWFA_DENSITY = ("ne*(1+4*(x^2+y^2)/(kp^2 * Rm^4 ) ) *\n"
                 "                         if (z > Lramp, 1, .5*(1-cos(pi*z/Lramp))) *\n"
                 "                         if (z>0,1,0)")
+
+
+def production_pwfa(nxy=64, nz=100, n_steps=11, seed=1):
+    """examples/get_started/inputs_pwfa as tests/production.SI.2Rank.sh runs it (amr.n_cell = 64 64 100, max_step = 10): SI units,
+    electrons and mobile hydrogen ions of 2e22 m^-3 (one particle per cell each, neither with a neutralising background), two
+    fixed_weight electron beams of 10^6 particles with do_symmetrize -- the driver (0.6 nC, sigma 2, 2, 30 um about z = 0) as the
+    deck's beam, the witness (0.2 nC, sigma 2, 2, 5 um about z = -160 um) as the one entry of beam_species --, hipace.dt =
+    adaptive with nt_per_betatron = 30 and max_time = 0.3 / c.  seed: the driver's draws; the witness takes seed + 1000."""
+    um = 1.0e-6
+    d = copy.deepcopy(_DEFAULT)
+    d.update(ADAPTIVE_DEFAULT)
+    ne = 2.0e22
+    d.update(nx=nxy, ny=nxy, nz=nz, lo=(-250.0 * um, -250.0 * um, -250.0 * um), hi=(250.0 * um, 250.0 * um, 110.0 * um), order=2,
+             si_units=1, plasma_ppc=(1, 1), plasma_density=ne, plasma_charge=-SI["q_e"], plasma_mass=SI["m_e"], plasma_no_neutralize=1,
+             beam_profile=-1, beam_charge=-SI["q_e"], beam_mass=SI["m_e"], beam_umean=(0.0, 0.0, 1000.0), beam_uz_std=10.0,
+             bc=1, n_steps=n_steps, dt=0.0, dt_adaptive=1, nt_per_betatron=30.0, max_time=0.3 / SI["c"])
+    with_ion_species(d, "H", ne, ppc=(1, 1), initial_level=1)
+    beam = dict(num_particles=1000000, position_std=(2.0 * um, 2.0 * um, 30.0 * um), position_mean=(0.0, 0.0, 0.0),
+                u_mean=(0.0, 0.0, 1000.0), u_std=(2.0, 2.0, 10.0), total_charge=0.6e-9, do_symmetrize=True, seed=int(seed))
+    d["beam_name"] = "driver"
+    d["beam_fixed_weight"] = beam
+    d["beam_species"] = [dict(name="witness", fixed_weight=dict(beam, position_mean=(0.0, 0.0, -160.0 * um),
+                                                                 position_std=(2.0 * um, 2.0 * um, 5.0 * um), total_charge=0.2e-9,
+                                                                 seed=int(seed) + 1000))]
+    return d
 
 
 def production_lwfa_parsed(n=64, nz=100, max_step=10):

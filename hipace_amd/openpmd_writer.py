@@ -239,13 +239,28 @@ def read_openpmd_json(fn):
     return arrays, attrs
 
 
-def write_engine_output(engine, prefix, iteration, time=0.0, beam_name="beam", beam=None, json_too=False, hdf5=None):
+def write_engine_output(engine, prefix, iteration, time=0.0, beam_name="beam", beam=None, json_too=False, hdf5=None, species=None):
     """diagnostic.output of one step of a SliceEngine: the fields of its field diagnostic (set_field_diagnostic before
-    the step) and, if given, the beam as (7, n) rows x y z ux uy uz w."""
+    the step) and, if given, the beam as (7, n) rows x y z ux uy uz w.  An engine with several beam species writes
+    one particle group per species name: species = {name or index: (7, n) rows}, default with beam=None on such an engine: every
+    species as it is now (beam_state(species=k)); charge and mass are the species' own."""
     d = engine.deck
     fields = engine.field_diagnostic()
     beams = None
-    if beam is not None:
+    names = list(getattr(engine, "beam_species_names", [beam_name]))
+    if species is None and beam is None and len(names) > 1:
+        species = {n: engine.beam_state(species=k)[1] for k, n in enumerate(names)}
+    if species is not None:
+        if beam is not None:
+            raise ValueError("write_engine_output: give the beam of a one-species engine, or the species of one with several, not both")
+        beams = {}
+        inv_c = 1.0 / 299792458.0 if d.get("si_units", 0) else 1.0      # the engine keeps u times c, the file u (momentum / (m c))
+        for key, rows in species.items():
+            k = names.index(key) if isinstance(key, str) else int(key)
+            rec = engine.beam_species_records[k]
+            beams[names[k]] = dict(x=rows[0], y=rows[1], z=rows[2], ux=rows[3] * inv_c, uy=rows[4] * inv_c, uz=rows[5] * inv_c, w=rows[6],
+                                   charge=rec["charge"], mass=rec.get("mass", 1.0) or 1.0)
+    elif beam is not None:
         beams = {beam_name: dict(x=beam[0], y=beam[1], z=beam[2], ux=beam[3], uy=beam[4], uz=beam[5], w=beam[6],
                                  charge=d["beam_charge"], mass=d.get("beam_mass", 1.0) or 1.0)}
     lo, hi = d["lo"], d["hi"]

@@ -754,6 +754,14 @@ int hps_adaptive_next_time (void* handle, double* t_next_host);
  * nstages steps (this dt is used nstages steps later), clamped by dt_max.  *dt: the dt of this controller's next step.
  * HPS_ERR_ARG if the sum of weights is 0 (no beam) or rho_max <= 0. */
 int hps_adaptive_after_step (void* handle, const double* moments4_host, double t, int nstages, double* dt_host);
+/* The same two with several beams (AdaptiveTimeStep.cpp:94-110, 177-258): one set of moments per beam, each beam's dt from its
+ * own mass / charge (a beam of charge 0 is skipped and keeps the dt that was), *dt = the smallest of them, then dt_max; the
+ * smallest |min uz m/q| over the beams feeds the phase-advance control.  charge and mass replace the deck's for these calls
+ * (mass 0 reads as 1); n = 1 with the deck's charge and mass gives the numbers of the one-beam calls.  n >= 1. */
+int hps_adaptive_initial_dt_beams (void* handle, int n, const double* uz_mean, const double* uz_std, const double* charge,
+                                   const double* mass, int nstages, double* dt_host);
+int hps_adaptive_after_step_beams (void* handle, int n, const double* moments_host /* [n][4] */, const double* charge,
+                                   const double* mass, double t, int nstages, double* dt_host);
 int hps_adaptive_destroy (void* handle);
 
 /* ---- ring pipeline over time steps: the transport (utils/MultiBuffer.H:21-34; MultiBuffer.cpp:287-609) --------
@@ -1063,6 +1071,50 @@ typedef struct {
 int hps_engine_set_beam_fixed_weight_pdf (void* handle, const hps_beam_fixed_weight_pdf* spec, const hps_expr* pdf,
                                           const hps_expr progs[10], unsigned long long seed, long n_left_out[2],
                                           double uz_moments[2]);
+
+/* ---- several beam species in one moving-beam engine (driver + witness) -----------------------------------------
+ * The engine keeps ONE beam container, one set of slice boundaries and one launch per phase and slice; a further species is a
+ * per-particle tag (one byte) and a record of a small device table with what the push and the deposit take per species.
+ * Species 0 is the deck's beam (beam_charge, beam_mass, beam_n_subcycles, ...).  hps_engine_add_beam_species appends a record
+ * (*index_out: its number, 1 .. HPS_MAX_BEAM_SPECIES - 1) and switches the engine's beam kernels to their tagged instances; an
+ * engine that never calls it holds no tag row and launches the kernels it always did.  mass 0 reads as 1, n_subcycles <= 0 as
+ * 10, as in the deck.  uz_mean / uz_std (units of c) are kept for the adaptive controller's initial estimate only.
+ * Refused, each with its reason in hps_last_error: a call after the first hps_engine_begin_step or a fifth species
+ * (HPS_ERR_ARG); a static beam (hipace.dt = 0), beam_do_salame, an engine with hps_engine_add_beam_collision, species that
+ * differ in do_spin_tracking (HPS_ERR_UNSUPPORTED each); hps_engine_add_beam_collision refuses an engine with several species
+ * in turn.  The ring hand-off carries the tag as one more row of the message (hps_engine_beam_message_rows: 8, or 11 with
+ * spin), so every engine of a pipeline is given the same species; the in-situ beam moments are kept per species
+ * (hps_engine_insitu_beam_species: hps_engine_insitu_beam for species k; hps_engine_insitu_beam refuses several species).
+ *
+ * hps_engine_select_beam_species(k): the beam setters (hps_engine_set_beam_particles, _fixed_ppc, _fixed_weight,
+ * _fixed_weight_pdf) called afterwards fill species k instead of replacing the beam: they build k's particles as they build a
+ * beam (with k's charge where a weight derives from it), and k_beam_merge (beam.hip) puts them into the container: inside a
+ * slice the particles already there stay in front, in their order, the new species' follow in theirs.  Species 0 is filled
+ * first (replacing it later is refused); a species k > 0 is filled once.
+ *
+ * hps_engine_beam_species_info: *n species and their particle counts [n] (either may be NULL).
+ * hps_engine_beam_state_species: species k's particles in container order -- *count of them, boundaries [nz + 1] of its slices
+ * and [7][*count] x y z ux uy uz w (any of the three may be NULL); synchronises the stream.  k = -1: the whole container
+ * (*count = nbeam of hps_engine_beam_info), whose tags hps_engine_beam_tags copies ([nbeam] bytes, all 0 with one species).
+ * hps_engine_beam_moments_species: hps_engine_beam_moments per species, out [n][4].
+ * hps_engine_beam_state and hps_engine_beam_moments refuse an engine with several species (HPS_ERR_ARG).
+ * hps_engine_beam_kernels: the names of the beam kernel instances the engine has launched so far, one per line, e.g.
+ * "k_beam_push<2,0,0>" (ORDER, EXT, MULTI), "k_beam_deposit_dyn<2,0>", "k_beam_partition<1,0>" (MOM, MULTI); *tagged = does
+ * the container hold a tag row.  buf may be NULL (then *len alone is written). */
+#define HPS_MAX_BEAM_SPECIES 4
+typedef struct {
+    double charge, mass;
+    int n_subcycles, no_z_push, radiation_reaction, do_spin_tracking;
+    double spin_anom, uz_mean, uz_std;
+} hps_beam_species;
+int hps_engine_add_beam_species (void* handle, const hps_beam_species* species, int* index_out);
+int hps_engine_select_beam_species (void* handle, int k);
+int hps_engine_beam_species_info (void* handle, int* n_host, long* counts_host);
+int hps_engine_beam_state_species (void* handle, int k, long* count_host, long* boundaries_host, double* soa_host);
+int hps_engine_beam_tags (void* handle, unsigned char* tags_host /* [nbeam] */);
+int hps_engine_insitu_beam_species (void* handle, int species, double* out_host /* [23][nz] */);
+int hps_engine_beam_moments_species (void* handle, double* out_host /* [n][4] */);
+int hps_engine_beam_kernels (void* handle, char* buf, long cap, long* len, int* tagged);
 
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);
