@@ -167,6 +167,7 @@ _SIGS = {
                                      C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p]),
     "hps_mg_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                               C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hps_mg_info_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "hps_mg_destroy": (C.c_int, [C.c_void_p]),
     "hps_mg2_create": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
     "hps_mg2_solve2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,
@@ -194,6 +195,8 @@ _SIGS = {
                                        C.c_void_p, C.c_void_p]),
     "hps_engine_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "hps_engine_early_init_slices": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
+    "hps_engine_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hps_engine_qsa_drops": (C.c_int, [C.c_void_p, C.POINTER(C.c_long)]),
     "hps_engine_set_insitu_plasma": (C.c_int, [C.c_void_p, C.c_double]),
     "hps_engine_set_insitu_beam": (C.c_int, [C.c_void_p, C.c_double]),
     "hps_engine_insitu_beam": (C.c_int, [C.c_void_p, C.c_void_p]),

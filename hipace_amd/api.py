@@ -419,18 +419,25 @@ class MultiGrid:
     LOWV = ("v3", "v-cc", "v-nodal", "bottom")                      # HPS_MG_LOWV_* of include/hpslice.h
     TILES = ("TileSmall", "TileBig", "TileSmall-pull", "TileMid-pull")    # HPS_MG_TILE_*
 
-    def info(self):
+    def info(self, schedule=False):
         """What the size dispatch chose: {"cc", "nlev", "lowv_begin", "lowv" (one of LOWV), "lowv_lds" (dynamic LDS bytes of the
         lower V, 0 for the bottom), "tiles" (one of TILES for level 0's initial pass and the down-leg of levels 1 ..
         lowv_begin - 1), "nodal_pull1", "pyramid" (levels k_acf_pyramid / k_nodal_acf_pyramid<n> derives), "restricts"
-        (k_restrict launches behind it)}."""
+        (k_restrict launches behind it)}.  schedule=True adds what the schedule switches chose when the solver was created:
+        "coef_guest" (k_lower_v3's coefficient image comes from a guest workgroup of the initial level-0 pass,
+        HPS_MG_COEF_GUEST)."""
         cc, nl, lb, kind, npyr, nres, pull1 = (C.c_int() for _ in range(7))
         lds, t = C.c_long(), (C.c_int * 31)()
         check(_lib.lib().hps_mg_info(self._h, C.byref(cc), C.byref(nl), C.byref(lb), C.byref(kind), C.byref(lds), t,
                                      C.byref(pull1), C.byref(npyr), C.byref(nres)))
-        return {"cc": bool(cc.value), "nlev": nl.value, "lowv_begin": lb.value, "lowv": self.LOWV[kind.value],
-                "lowv_lds": lds.value, "tiles": tuple(self.TILES[v] for v in t if v >= 0), "nodal_pull1": bool(pull1.value),
-                "pyramid": npyr.value, "restricts": nres.value}
+        out = {"cc": bool(cc.value), "nlev": nl.value, "lowv_begin": lb.value, "lowv": self.LOWV[kind.value],
+               "lowv_lds": lds.value, "tiles": tuple(self.TILES[v] for v in t if v >= 0), "nodal_pull1": bool(pull1.value),
+               "pyramid": npyr.value, "restricts": nres.value}
+        if schedule:
+            guest = C.c_int()
+            check(_lib.lib().hps_mg_info_schedule(self._h, C.byref(guest)))
+            out["coef_guest"] = bool(guest.value)
+        return out
 
     def solve1(self, fields, sol_comp, rhs_comp, acoef_comp, tol_rel=1e-4, tol_abs=2.2250738585072014e-308,
                nummaxiter=200):
@@ -1468,6 +1475,19 @@ class SliceEngine:
         ei = C.c_long()      # slices whose shift / zero pass rode in the Bx/By solve's lower V (HPS_EARLY_INIT)
         check(_lib.lib().hps_engine_early_init_slices(self._h, C.byref(ei)))
         return dict(vcycles=vc.value, slices=sl.value, early_init=ei.value)
+
+    def schedule(self):
+        """What the schedule switches read at creation chose: {"mg_coef_guest" (MultiGrid.info(schedule=True)["coef_guest"] of
+        the Bx/By solver), "valid_by_psi" (the electrons' tiled push reads validity off psi_half, HPS_VALID_BY_PSI)}."""
+        g, v = C.c_int(), C.c_int()
+        check(_lib.lib().hps_engine_schedule(self._h, C.byref(g), C.byref(v)))
+        return dict(mg_coef_guest=bool(g.value), valid_by_psi=bool(v.value))
+
+    def qsa_drops(self):
+        """particles dropped by the depositions so far for violating the quasi-static approximation (max_qsa)"""
+        n = C.c_long()
+        check(_lib.lib().hps_engine_qsa_drops(self._h, C.byref(n)))
+        return n.value
 
     def slab(self):
         self.sync()

@@ -206,6 +206,8 @@ struct Engine {
     int species_deposit (const Species& s, const int comp[6], const BeamPairWork* beam = nullptr, const int* go = nullptr);
     bool valid_by_w = true;                    // HPS_VALID_BY_W=0: off.  The depositions take "weight != 0" for the valid bit of idcpu and do not read it (PartConsts::valid_by_w:
                                                // 33.5 MB less per kernel at 1024^2 x 4 ppc -- no time gained with one stage on the GPU, +1 % with three in flight: r04g_ab_inflight_byte_cuts.txt)
+    bool valid_by_psi = true;                  // HPS_VALID_BY_PSI=0: off.  The electrons' tiled push takes "psi_half != 0" for the valid bit of idcpu and does not read it (Tiling::valid_by_psi;
+                                               // 33.5 MB less per launch at 1024^2 x 4 ppc); read when the engine is created, handed to the electrons' tiling when that is set up
     bool post_in_push = true;                  // the gated plasma push posts the Bx/By solve's norms to the host (HPS_POST_IN_PUSH=0: k_post_norms, a launch of its own)
     bool fold_hierarchy = true;                // the multigrid's coefficient hierarchy in the -grad Psi / Sx, Sy launch (HPS_FOLD_HIERARCHY=0: in mg_solve1_begin)
     bool fold_beam = true;                     // the static beam's two deposits of a slice as extra workgroups of the plasma's deposition (HPS_FOLD_BEAM=0: a launch of their own)

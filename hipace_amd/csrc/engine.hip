@@ -747,6 +747,7 @@ int Engine::create (const hps_deck& deck, int device)
     if (const char* v = std::getenv("HPS_FOLD_BEAM")) fold_beam = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_FOLD_HIERARCHY")) fold_hierarchy = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_VALID_BY_W")) valid_by_w = std::atoi(v) != 0;
+    if (const char* v = std::getenv("HPS_VALID_BY_PSI")) valid_by_psi = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_GATED_ION_PUSH")) gate_ion_push = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_LAZY_SHIFT")) lazy_shift = std::atoi(v) != 0;
     if (const char* v = std::getenv("HPS_FUSE_SOURCES")) fuse_sources = std::atoi(v) != 0;
@@ -898,8 +899,9 @@ int Engine::setup_tiling ()
 {
     if (tile_size == 0 || el.cap == 0 || el.tiling) return HPS_OK;
     if (int e = tiling_create(d.nx, d.ny, tile_size, el.cap, &el.tiling)) return e;
-    {   const char* v = std::getenv("HPS_VALID_BY_PSI");       // the electrons' push without its idcpu read (tiling.h)
-        el.tiling->valid_by_psi = (v && std::atoi(v) != 0); }    // (measured: the push takes the same time with and without, off)
+    // the electrons' push without its idcpu read (tiling.h): every path that creates or invalidates an electron keeps
+    // "valid <=> psi_half != 0" (DESIGN section 6 "Round 10")
+    el.tiling->valid_by_psi = valid_by_psi;
     if (int e = alloc_soa(el.pl_alt, el.real_alt, el.cap, el.alias_prev())) return e;      // (its n: sort_sheet)
     if (ions.present()) {
         // the ionisable species on the engine's tile size.  (Round 2 gave a species with at most one particle per cell 32 x 32-cell
@@ -2415,6 +2417,24 @@ extern "C" int hps_engine_early_init_slices (void* h, long* n)
 {
     HPS_REQUIRE(h && n, "hps_engine_early_init_slices: null argument");
     *n = static_cast<Engine*>(h)->slices_rode;
+    return HPS_OK;
+}
+extern "C" int hps_engine_schedule (void* h, int* mg_coef_guest, int* valid_by_psi)
+{
+    HPS_REQUIRE(h, "hps_engine_schedule: null handle");
+    Engine* E = static_cast<Engine*>(h);
+    if (mg_coef_guest) { *mg_coef_guest = 0; if (E->mg) { if (int e = hps_mg_info_schedule(E->mg, mg_coef_guest)) return e; } }
+    if (valid_by_psi) *valid_by_psi = (E->tile_size != 0 && E->valid_by_psi) ? 1 : 0;
+    return HPS_OK;
+}
+extern "C" int hps_engine_qsa_drops (void* h, long* n)
+{
+    HPS_REQUIRE(h && n, "hps_engine_qsa_drops: null argument");
+    Engine* E = static_cast<Engine*>(h);
+    int v = 0;
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    HPS_HIP_CHECK(hipMemcpy(&v, E->d_nqsa, sizeof(int), hipMemcpyDeviceToHost));
+    *n = v;
     return HPS_OK;
 }
 extern "C" hps_plasma hps_engine_plasma (void* h) { return static_cast<Engine*>(h)->el.pl; }

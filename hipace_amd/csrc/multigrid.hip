@@ -92,6 +92,8 @@ using TileHugeNodal = TileShape<64, 32, 512>;
 template <bool CC> struct HugeTileOf { using type = TileHuge; };
 template <> struct HugeTileOf<false> { using type = TileHugeNodal; };
 using TileSmall = TileShape<32, 16, 256>;
+// k_lower_v3's [acf | 1/diag] image of the levels below its top one is at most this long (32^2 .. 2^2 with their rings)
+constexpr int COEF_GUEST_MAX_IMG = 2*(34*34 + 18*18 + 10*10 + 6*6 + 4*4);
 
 // diagonal of the operator at (i,j): -(a + 2(fx+fy)) with the wall modification (gs1 :265-292)
 template <bool CC>
@@ -525,19 +527,32 @@ __device__ __forceinline__ void smooth_tile (double (&s_phi)[2][TS::AY*TS::AX], 
 
 // NSW red-black half-sweeps per launch: 4 (one GSRB^4 of the reference) or 8 (the two consecutive
 // GSRB^4 that end a V-cycle on level 0, fused: one pass over HBM instead of two)
-template <class TS, bool CC, int SRC, bool DO_RES, bool FUSE_R, int NSW = 4, bool RPULL = false>
+// GUEST (none, or one CoefGuest: the instance that makes a solve's initial level-0 pass where the lower V is k_lower_v3):
+// workgroup 0 of that launch is no tile but derives the lower V's coefficient image (coef_guest_derive) in the tile's static
+// LDS: it starts with the first round of tiles and is done long before the pass is; the tiles are workgroups 1 .. .  Instances
+// without a guest have the same arguments and the same code as before the guest existed.
+struct CoefGuest;
+__device__ void coef_guest_derive (double* s_img, const CoefGuest& g, int nt);
+
+template <class TS, bool CC, int SRC, bool DO_RES, bool FUSE_R, int NSW = 4, bool RPULL = false, class... GUEST>
 __global__ __launch_bounds__(TS::NT, (RPULL && TS::GPAIRS > 1) ? 2 : 4)      // at most 128 VGPRs: two 512-thread workgroups per CU (several variants sit at 113-130); the pulling smoother with two pairs per thread (36 + 36 loads in flight) gets 256
 void k_smooth (LevBox b, FView phi_out, FView phi_out2, FView rhs, FView acf, FView phi_in, FView crse, FView res_out,
                FView cres_out, double facx, double facy, int ntx, unsigned long long* resnorm,
-               unsigned long long* rhsnorm, StopRule sr)
+               unsigned long long* rhsnorm, StopRule sr, GUEST... guest)
 {
     static_assert(!FUSE_R || (CC && DO_RES), "fused restriction is cell-centred only");
+    constexpr int HOST = (int)sizeof...(GUEST);       // workgroups ahead of the tiles
+    static_assert(HOST <= 1 && (HOST == 0 || (CC && NSW == 4)), "the guest rides in the cell-centred initial pass");
     // (the 4-sweep kernels read the gate behind their loads, see smooth_tile; the 8-sweep pass first: with the gate behind its
     //  loads all of the tile's operands are live across it, 61 registers spilled under its 128-register cap, round 4)
     if (NSW != 4 && !vcycle_active(sr)) return;
     constexpr int GT_X = TS::TX, GT_Y = TS::TY;
     __shared__ double s_phi[2][TS::AY*TS::AX];
     __shared__ double s_red[TS::NT/64];
+    if constexpr (HOST > 0) {
+        static_assert(2*TS::AY*TS::AX >= COEF_GUEST_MAX_IMG, "the image is staged in the tile's static LDS");
+        if (blockIdx.x == 0) { coef_guest_derive(&s_phi[0][0], guest..., TS::NT); return; }
+    }
     // node-centred prolongation goes through LDS (smooth_tile): the coarse cells under the ringed tile, two components
     constexpr bool PLDS = !CC && SRC == SRC_PROLONG;
     __shared__ double s_crs[PLDS ? 2*(TS::AX/2 + 2)*(TS::AY/2 + 2) : 1];
@@ -545,8 +560,10 @@ void k_smooth (LevBox b, FView phi_out, FView phi_out2, FView rhs, FView acf, FV
     constexpr int FX = GT_X - 2*E, FY = GT_Y - 2*E;   // cells a tile finalises (even numbers)
     // workgroups go round-robin to the 8 XCDs: give each XCD a contiguous run of tiles, so that the
     // rims shared by neighbouring tiles hit in that XCD's L2
-    const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = blockIdx.x & 7;
-    const int tile = xcd*q8 + min(xcd, r8) + (blockIdx.x >> 3);
+    // (behind a guest the runs belong to XCD (xcd + 1) & 7: contiguous all the same)
+    const unsigned wg = blockIdx.x - HOST;
+    const int nb = gridDim.x - HOST, q8 = nb >> 3, r8 = nb & 7, xcd = wg & 7;
+    const int tile = xcd*q8 + min(xcd, r8) + (wg >> 3);
     const int bx = tile % ntx, by = tile / ntx;
     const int gi0 = b.vlx + bx*FX - E;                // global index of swept cell (0,0)
     const int gj0 = b.vly + by*FY - E;
@@ -1128,10 +1145,65 @@ __device__ __forceinline__ void lower_v_guest (const ShiftInit& a, int guest, in
     for (long s = (long)guest*1024 + threadIdx.x; s < a.plane; s += (long)nguests*1024) shift_init_cell(a, s);
 }
 
+// Guest of a solve's initial level-0 pass (k_smooth's GUEST): the [acf | 1/diag] image of the levels below k_lower_v3's top
+// level A, which depends on level A's coefficient plane only (the pyramid's, a whole launch earlier in the stream) -- derived
+// here, beside the pass's tiles, the first lower V of the solve does not derive it on the V-cycle's critical path.  Cell for
+// cell the expressions of k_lower_v3's own derivation (which grids without this guest keep), block by block as there; the
+// image is staged in the host kernel's static LDS (s_img, nt threads) and left in g.img, where every lower V copies it in.
+struct CoefGuest { const Low2* low; const double* acfA; double* img; double facx0, facy0; };
+
+__device__ void coef_guest_derive (double* s_img, const CoefGuest& g, int nt)
+{
+    lds_double* img = (lds_double*)s_img;
+    const Low2& d = *g.low;
+    const int t = threadIdx.x;
+    const int nl = d.nl, ctot = d.ctot, cbase = d.cbase;
+    for (int q = t; q < ctot; q += nt) img[q] = 0.0;       // (the rings: never read, but the image is the same every time)
+    __syncthreads();
+    if (nl > 1) {
+        const int nxA = d.nx[0], nyA = d.ny[0], nbx = (nxA + 1) >> 1, nby = (nyA + 1) >> 1, p1 = d.nx[1] + 2;
+        for (int q = t; q < nbx*nby; q += nt) {
+            const int bj = q / nbx, i = 2*(q - bj*nbx), j = 2*bj;
+            double a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ik = i + (k & 1), jk = j + (k >> 1);
+                const double v = g.acfA[min(ik, nxA - 1) + min(jk, nyA - 1)*nxA];
+                a[k] = (ik < nxA && jk < nyA) ? v : 0.0;
+            }
+            img[d.coff[1] - cbase + ((j >> 1) + 1)*p1 + (i >> 1) + 1] = 0.25*(a[0] + a[1] + a[2] + a[3]);
+        }
+    }
+    __syncthreads();
+    for (int l = 1; l < nl; ++l) {
+        const double fx = lvl_fac(g.facx0, l), fy = lvl_fac(g.facy0, l);
+        const int nx = d.nx[l], ny = d.ny[l], nbx = (nx + 1) >> 1, nby = (ny + 1) >> 1, pitch = nx + 2, ps = pitch*(ny + 2);
+        lds_double* lev = img + (d.coff[l] - cbase);
+        const int ok[4] = {0, 1, pitch, pitch + 1};
+        for (int q = t; q < nbx*nby; q += nt) {
+            const int bj = q / nbx, i = 2*(q - bj*nbx), j = 2*bj;
+            lds_double* acf = lev + (j + 1)*pitch + i + 1;
+            const bool in[4] = {true, i + 1 < nx, j + 1 < ny, i + 1 < nx && j + 1 < ny};
+            double a[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = in[k] ? acf[ok[k]] : 0.0;
+            if (l + 1 < nl) {
+                const int pn = d.nx[l+1] + 2;
+                img[d.coff[l+1] - cbase + ((j >> 1) + 1)*pn + (i >> 1) + 1] = 0.25*(a[0] + a[1] + a[2] + a[3]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (in[k]) acf[ps + ok[k]] = 1.0/diag_c0<true>(i + (k & 1), j + (k >> 1), cc_box(nx, ny), a[k], fx, fy);
+        }
+        __syncthreads();
+    }
+    for (int q = t; q < ctot; q += nt) g.img[q] = img[q];
+}
+
 __global__ __launch_bounds__(1024)
 void k_lower_v3 (const Low2* __restrict__ dp, const double* __restrict__ acf_g, const double* __restrict__ cinv_g,
                  const double* __restrict__ res_g, double* __restrict__ cor_g, double* __restrict__ coef_g, int nxA, int nyA, int ctot,
-                 double facx0, double facy0, int nsweeps_bottom, StopRule sr, ShiftInit guest)
+                 double facx0, double facy0, int nsweeps_bottom, StopRule sr, ShiftInit guest, int derive_first)
 {
     if (blockIdx.x >= 2) { lower_v_guest(guest, (int)blockIdx.x - 2, (int)gridDim.x - 2); return; }
     extern __shared__ __attribute__((aligned(16))) double lds_raw[];
@@ -1154,9 +1226,11 @@ void k_lower_v3 (const Low2* __restrict__ dp, const double* __restrict__ acf_g, 
         rA[k] = A.ok[k] ? v0 : 0.0; aA[k] = A.ok[k] ? v2 : 0.0; A.ci[k] = A.ok[k] ? v3 : 0.0;
         A.r0[k] = rA[k];
     }
-    // The [acf | 1/diag] planes of the levels below A depend on the coefficient only: the first V-cycle of a solve derives
-    // them (average_down_acoef + one division per cell) and leaves the image in coef_g, the later ones copy it in.
-    const bool derive = (sr.k <= 0);
+    // The [acf | 1/diag] planes of the levels below A depend on the coefficient only: the guest of the solve's initial level-0
+    // pass has left their image in coef_g (coef_guest_derive) and every V-cycle copies it in.  derive_first (grids whose
+    // initial pass cannot host the guest, HPS_MG_COEF_GUEST=0): the first V-cycle of a solve derives them here
+    // (average_down_acoef + one division per cell) and leaves the image in coef_g for the later ones.
+    const bool derive = derive_first && (sr.k <= 0);
     constexpr int NIMG = 4;      // image words per thread (LOW2 levels below 64 x 64: 3264 doubles)
     double img[NIMG];
 #pragma unroll
@@ -1493,7 +1567,8 @@ struct Multigrid {
     bool use_low3 = false; Low2 low3{}; Low2* d_low3 = nullptr; size_t low3_lds = 0;   // cell-centred register/LDS lower V (k_lower_v3)
     bool ride_on = false; ShiftInit ride{}; int ride_guests = 0;      // mg_ride_shift_init: guests of the next solve's first k_lower_v3 launch
     double* cinvA = nullptr;                    // inverse diagonals of level lowv_begin (written with the coefficient pyramid)
-    double* coef_img = nullptr;                 // [acf | 1/diag] planes of the levels below it (left by the first V-cycle of a solve)
+    double* coef_img = nullptr;                 // [acf | 1/diag] planes of the levels below it (left by the initial pass's guest, or by the first V-cycle of a solve)
+    bool coef_guest = false;                    // the image is derived by a guest workgroup of the initial level-0 pass (HPS_MG_COEF_GUEST)
     double* tmp0 = nullptr;                     // level-0 scratch: smoothed solution before the last GSRB^4
     bool cor_in_tmp = false;                    // which buffer holds cor[0] (the fused 8-sweep end of the V-cycle is out of place)
     FView sol, rhs, acf0;                       // level-0 user views (set per solve)
@@ -1600,6 +1675,9 @@ int mg_create (int nx, int ny, double dx, double dy, Multigrid** out)
             HPS_HIP_CHECK(hipGetDevice(&dev));
             HPS_HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
             M->ride_guests = std::max(ncu - 2, 1);
+            // the image's guest needs the initial pass on 64 x 32 tiles (its static LDS holds the image; 32 x 16 tiles: too small)
+            const char* sw = getenv("HPS_MG_COEF_GUEST");
+            M->coef_guest = !(sw && atoi(sw) == 0) && M->L[0].cells > SMALL_TILE_CELLS && e.nl > 1 && e.ctot <= COEF_GUEST_MAX_IMG;
             break;
         }
     }
@@ -1722,7 +1800,8 @@ static void vcycle (Multigrid* M, int k, double tol_rel, double tol_abs, hipStre
             const int guests = (k == 0 && M->ride_on) ? M->ride_guests : 0;
             M->ride_on = false;
             hipLaunchKernelGGL(k_lower_v3, dim3(2 + guests), dim3(1024), M->low3_lds, st, M->d_low3, M->L[lb].acf, M->cinvA, M->L[lb].res, M->L[lb].cor,
-                               M->coef_img, M->low3.nx[0], M->low3.ny[0], M->low3.ctot, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, M->ride);
+                               M->coef_img, M->low3.nx[0], M->low3.ny[0], M->low3.ctot, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, M->ride,
+                               M->coef_guest ? 0 : 1);
         } else      // (node-centred: one field component per workgroup)
             hipLaunchKernelGGL(k_lower_v<CC>, dim3(CC ? 1 : 2), dim3(1024), M->low_lds, st, M->d_low, nl - lb, M->L[lb].acf, M->L[lb].res,
                                M->L[lb].cor, 1.0/(ldx*ldx), 1.0/(ldy*ldy), nsweeps, sr, M->pulls(lb) ? M->lv(lb-1, M->L[lb-1].rescor) : FView{});
@@ -1855,6 +1934,23 @@ static int solve1_hierarchy (Multigrid* M, int max_iters, hipStream_t st, const 
     return HPS_OK;
 }
 
+// the initial pass of a cell-centred solve (launch_smooth<true, SRC_DIRECT, true> on level 0's 64 x 32 tiles) with one workgroup
+// more: the guest that derives k_lower_v3's coefficient image (coef_guest_derive).  The hierarchy's launches are ahead of it
+// on this stream, or on the stream the caller has joined (mg_solve1_prepare*); the first lower V is behind it.
+static void launch_initial_with_guest (Multigrid* M, const StopRule& sr, hipStream_t st)
+{
+    using TS = TileBig;
+    const LevBox& b = M->L[0].b;
+    constexpr int FX = TS::TX - 2*4, FY = TS::TY - 2*4;
+    const int ntx = ceil_div(b.vhx - b.vlx + 1, FX), nty = ceil_div(b.vhy - b.vly + 1, FY);
+    const int lb = M->lowv_begin;
+    const double lfac = (double)(1 << lb), ldx = M->dx*lfac, ldy = M->dy*lfac;
+    const CoefGuest g{M->d_low3, M->L[lb].acf, M->coef_img, 1.0/(ldx*ldx), 1.0/(ldy*ldy)};
+    hipLaunchKernelGGL((k_smooth<TS, true, SRC_DIRECT, true, true, 4, false, CoefGuest>), dim3(ntx*nty + 1), dim3(TS::NT), 0, st, b,
+                       M->lv(0, M->L[0].cor), FView{}, M->rhs, M->acf0, M->sol, FView{}, M->lv(0, M->L[0].rescor), M->lv(1, M->L[1].res),
+                       1.0/(M->dx*M->dx), 1.0/(M->dy*M->dy), ntx, M->d_norms, M->d_norms + MG_NSUB, sr, g);
+}
+
 template <bool CC>
 static int solve1_begin (Multigrid* M, double tol_rel, double tol_abs, int max_iters, hipStream_t st)
 {
@@ -1866,6 +1962,9 @@ static int solve1_begin (Multigrid* M, double tol_rel, double tol_abs, int max_i
     if (M->hierarchy_ready) M->hierarchy_ready = false;       // (mg_solve1_prepare has enqueued it; the caller has ordered the streams)
     else if (int e = solve1_hierarchy<CC>(M, max_iters, st)) return e;
     // cor[0] = GSRB^4(sol), residual norm, rhs norm, res[1] = R(residual)  (solve_doit :1319-1346)
+    if (CC && M->coef_guest)
+        launch_initial_with_guest(M, always, st);
+    else
     launch_smooth<CC, SRC_DIRECT, true>(M, 0, M->lv(0, M->L[0].cor), FView{}, M->rhs, M->acf0, M->sol, FView{}, M->lv(0, M->L[0].rescor),
                                         M->lv(1, M->L[1].res), M->d_norms, M->d_norms + MG_NSUB, always, st);
     if (!M->nodal_pull1) restrict_residual_if_nodal<CC>(M, 0, always, st);
@@ -2074,6 +2173,13 @@ extern "C" int hps_mg_info (void* handle, int* cc, int* nlev, int* lowv_begin, i
     if (nodal_pull1) *nodal_pull1 = M->nodal_pull1;
     if (pyr_levels) *pyr_levels = std::min(lb, M->cc ? 5 : NPYR_MAX);
     if (pyr_restricts) *pyr_restricts = lb - std::min(lb, M->cc ? 5 : NPYR_MAX);
+    return HPS_OK;
+}
+
+extern "C" int hps_mg_info_schedule (void* handle, int* coef_guest)
+{
+    HPS_REQUIRE(handle, "hps_mg_info_schedule: null handle");
+    if (coef_guest) *coef_guest = static_cast<const Multigrid*>(handle)->coef_guest ? 1 : 0;
     return HPS_OK;
 }
 

@@ -190,7 +190,9 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
         Rec r;
         r.x = pl.x[ip]; r.y = pl.y[ip]; r.w = pl.w[ip];
         r.ux = pl.ux[ip]; r.uy = pl.uy[ip]; r.psi = pl.psi[ip];
-        if constexpr (VBW) r.id = (r.w != 0.0) ? HPS_ID_VALID : 0ULL;      // (PartConsts::valid_by_w: idcpu is not read)
+        // fetch() only issues loads: a value formed from one here (the VBW validity, w != 0, until round 10) makes the wave wait
+        // for the batch it has just requested, ahead of the zeroing below
+        if constexpr (VBW) r.id = 0ULL;      // (PartConsts::valid_by_w: idcpu is not read, the weight is looked at where the record is used)
         else r.id = pl.idcpu[ip];
         r.ion = k.can_ionize ? pl.ion_lev[ip] : 1;
         return r;
@@ -230,7 +232,7 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
         if (ip >= pend) break;
         const Rec cur = rec[u];
         const uint64_t id = cur.id;
-        if (!(id & HPS_ID_VALID)) continue;
+        if (VBW ? (cur.w == 0.0) : !(id & HPS_ID_VALID)) continue;
         // (IEEE: the QSA test below must see inf for psi = 0.  v_rcp_f64 + one Newton step, as the push's fast_rcp, with
         // psi = 0 mapped to inf by hand was measured: 69.0 against 69.2 us per launch, no gain)
         const double psi_inv = 1.0/cur.psi;

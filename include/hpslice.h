@@ -214,6 +214,10 @@ enum { HPS_MG_TILE_SMALL = 0, HPS_MG_TILE_BIG = 1, HPS_MG_TILE_SMALL_PULL = 2, H
 enum { HPS_MG_MAXLEV = 31 };
 int hps_mg_info (void* handle, int* cc, int* nlev, int* lowv_begin, int* lowv_kind, long* lowv_lds, int* tiles,
                  int* nodal_pull1, int* pyr_levels, int* pyr_restricts);
+/* What the schedule switches read by hps_mg_create chose.  *coef_guest: 1 where k_lower_v3's coefficient image is derived by a
+ * guest workgroup of the solve's initial level-0 pass (HPS_MG_COEF_GUEST, default 1; k_lower_v3 grids whose initial pass runs on
+ * 64 x 32 tiles), 0 where the first lower V of a solve derives it itself. */
+int hps_mg_info_schedule (void* handle, int* coef_guest);
 int hps_mg_destroy (void* handle);
 
 /* hpmg::MultiGrid, system type 2 (mg_solver/HpMultiGrid.H:48,84-87 solve2 with an array Re and a scalar Im coefficient;
@@ -378,7 +382,7 @@ int hps_engine_info (void* handle, int* ncomp, int* nguards, long* nparticles);
 hps_slab hps_engine_slab (void* handle);
 /* The engine's sheet: raw device pointers.  CONTRACT for a host that invalidates particles itself: clearing the valid bit of
  * idcpu is not enough -- also store 0 to the particle's w AND psi_half.  The engine's tiled depositions take "w != 0" for
- * the valid bit and do not read idcpu (HPS_VALID_BY_W, default on; the push under HPS_VALID_BY_PSI reads psi_half the same
+ * the valid bit and do not read idcpu (HPS_VALID_BY_W, default on; the tiled push under HPS_VALID_BY_PSI, default on too, reads psi_half the same
  * way): every path of the engine that invalidates a particle (QSA drop, absorbing boundary) zeroes both.  HPS_VALID_BY_W=0
  * in the environment restores the idcpu read. */
 hps_plasma hps_engine_plasma (void* handle);
@@ -397,6 +401,14 @@ int hps_engine_stats (void* handle, long* total_vcycles, long* slices_done);
  * instead of a launch of their own at the head of the next slice (the plain explicit-solver slice on a grid whose lower V is
  * k_lower_v3; HPS_EARLY_INIT=0 in the environment: never).  hps_engine_slab and hps_engine_sync show the slab as without it. */
 int hps_engine_early_init_slices (void* handle, long* n_slices);
+/* What two schedule switches, read when the engine was created, chose for this engine.  Null outputs are skipped.
+ *   *mg_coef_guest: hps_mg_info_schedule of the Bx/By solver (0 for an engine without one);
+ *   *valid_by_psi: the electrons' tiled push takes "psi_half != 0" for the valid bit of idcpu and does not read it
+ *     (HPS_VALID_BY_PSI, default 1; 0 for an engine whose sheet is not tile-sorted). */
+int hps_engine_schedule (void* handle, int* mg_coef_guest, int* valid_by_psi);
+/* particles the depositions have dropped since the engine was created because they violate the quasi-static approximation
+ * (plasmas.max_qsa_weighting_factor); waits for the engine's stream */
+int hps_engine_qsa_drops (void* handle, long* n);
 /* predictor-corrector: iterations so far and the sum over slices of the final relative B-field error
  * (m_predcorr_avg_iterations / m_predcorr_avg_B_error of Hipace.cpp:964,1028 before the division by nz) */
 int hps_engine_pc_stats (void* handle, long* iterations, double* error_sum);
