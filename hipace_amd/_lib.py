@@ -76,7 +76,7 @@ class BeamFixedWeightPdf(C.Structure):  # hps_beam_fixed_weight_pdf
 class BeamSpecies(C.Structure):         # hps_beam_species
     _fields_ = [("charge", C.c_double), ("mass", C.c_double), ("n_subcycles", C.c_int), ("no_z_push", C.c_int),
                 ("radiation_reaction", C.c_int), ("do_spin_tracking", C.c_int), ("spin_anom", C.c_double),
-                ("uz_mean", C.c_double), ("uz_std", C.c_double)]
+                ("uz_mean", C.c_double), ("uz_std", C.c_double), ("do_salame", C.c_int)]
 
 
 class Deck(C.Structure):
@@ -124,6 +124,7 @@ COMPS_PC = ["N_jx", "N_jy", "ExmBy", "EypBx", "Ez", "Bx", "By", "Bz", "Psi", "jx
             "P_Bx", "P_By", "P_jx", "P_jy", "Ion_rhomjz", "It_Bx", "It_By", "PIt_Bx", "PIt_By", "rho"]
 CIDX_PC = {n: i for i, n in enumerate(COMPS_PC)}
 # the SALAME slice, index = value of the HPS_SAL_* enum; appended behind the engine's own components in a beam_do_salame deck
+# and in a moving-beam engine whose deck carries beam_species_salame (hps_engine_set_beam_species_salame)
 COMPS_SALAME = ["Ez_target", "Ez_no_salame", "Ez", "jx", "jy", "jz_beam", "Bx", "By", "Sy", "Sx", "Sy_back", "Sx_back"]
 ID_VALID = 1 << 63
 
@@ -296,6 +297,9 @@ _SIGS = {
     "hps_salame_sxsy_from_jz": (C.c_int, [Slab, Geom, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hps_salame_get_w": (C.c_int, [Slab, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hps_salame_scale_beam_slice": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p]),
+    "hps_engine_set_beam_species_salame": (C.c_int, [C.c_void_p, C.c_int]),
+    "hps_engine_deposit_beam_species": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int]),
+    "hps_engine_salame_scale_slice": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "hps_open_boundary": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint,
                                     C.c_void_p]),
     "hps_collide_plasma": (C.c_int, [Plasma, C.c_void_p, Plasma, C.c_void_p, Geom, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,

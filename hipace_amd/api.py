@@ -637,6 +637,11 @@ class SliceEngine:
             self._dk.beam_profile = -1
         self._h = C.c_void_p()
         check(_lib.lib().hps_engine_create(C.byref(self._dk), device, C.byref(self._h)))
+        # SALAME on a witness species of a moving-beam engine (decks.SALAME_SPECIES_DEFAULT): announced ahead of every other
+        # setter -- the engine allocates the SALAME slice now; a deck without the key and without a do_salame species makes no call
+        if _decks.beam_species_salame(deck):
+            self.deck["beam_species_salame"] = 1
+            check(_lib.lib().hps_engine_set_beam_species_salame(self._h, 1))
         # the beam species: species 0 is the deck's beam; the deck's entry beam_species is applied further down
         self.beam_species_names = [deck.get("beam_name", "beam")]
         self.beam_species_records = [dict(charge=deck.get("beam_charge", -1.0), mass=deck.get("beam_mass", 1.0),
@@ -974,7 +979,8 @@ class SliceEngine:
     def add_beam_species(self, **spec):
         """One more beam species in this moving-beam engine (hps_engine_add_beam_species + the source's setter with species=):
         name, charge, mass, n_subcycles, do_z_push, radiation_reaction, spin_anom, do_spin_tracking, uz_mean, uz_std (defaults:
-        the deck's beam's) and exactly one source -- fixed_weight=dict(...), fixed_weight_pdf=dict(...), density_expr=... (with
+        the deck's beam's), do_salame (the species takes part in SALAME during step 0: needs a deck with beam_species_salame)
+        and exactly one source -- fixed_weight=dict(...), fixed_weight_pdf=dict(...), density_expr=... (with
         constants, min_density, u_std, random_ppc, seed) or particles=(7, n) array (decks.BEAM_SPECIES_DEFAULT).  Before the
         first begin_step.  -> the species' index; what the source left out of the box: beam_species_left_out[index]."""
         return self._add_beam_species(_decks.beam_species_spec(self.deck, spec, "add_beam_species"))
@@ -1438,12 +1444,13 @@ class SliceEngine:
 
     def comp_names(self):
         """Names of the slab components of this engine (rho and aabs are optional and come last; behind them the twelve
-        planes of the SALAME slice, "Salame_<name>", in a beam_do_salame deck -- slab() holds them, checksums() does not)."""
+        planes of the SALAME slice, "Salame_<name>", in a beam_do_salame or beam_species_salame deck -- slab() holds them,
+        checksums() does not)."""
         if self.deck.get("bxby_solver", 0):
             return list(_lib.COMPS_PC[:22]) + (["rho"] if self.deck.get("deposit_rho", 0) else [])
         return list(COMPS[:21]) + (["rho"] if self.deck.get("deposit_rho", 0) else []) + \
             (["aabs"] if self.deck.get("laser_on", 0) else []) + \
-            (["Salame_" + n for n in _lib.COMPS_SALAME] if self.deck.get("beam_do_salame", 0) else [])
+            (["Salame_" + n for n in _lib.COMPS_SALAME] if self.deck.get("beam_do_salame", 0) or self.deck.get("beam_species_salame", 0) else [])
 
     def salame_stats(self):
         """<beam>.do_salame: dict of arrays [nz] (index = islice) -- "W" the last weight factor, "W_total" = W * sum(jz) of
@@ -1455,6 +1462,22 @@ class SliceEngine:
         flags = out[:, 3].astype(np.int64)
         return {"W": out[:, 0].copy(), "W_total": out[:, 1].copy(), "iterations": out[:, 2].astype(np.int64),
                 "converged": (flags & 1) != 0, "overloaded": (flags & 2) != 0, "ran": out[:, 2] > 0}
+
+    def deposit_beam_species(self, islice, species, jx=None, jy=None, jz=None):
+        """hps_engine_deposit_beam_species: the moving beam's deposit of slice islice restricted to `species` (indices or names),
+        added to the slab components named jx, jy (both or neither) and jz (comp_names(); None: none).  Enqueued on the engine's
+        stream, behind begin_step."""
+        names = self.comp_names()
+        comp = [names.index(c) if c is not None else -1 for c in (jx, jy, jz)]
+        mask = 0
+        for s in species:
+            mask |= 1 << self._species_index(s)
+        check(_lib.lib().hps_engine_deposit_beam_species(self._h, int(islice), mask, *comp))
+
+    def salame_scale_slice(self, islice, W):
+        """hps_engine_salame_scale_slice: SalameMultiplyBeamWeight on slice islice of the moving beam's container (the do_salame
+        species' particles that have not slipped in; W = 0 removes them).  Enqueued on the engine's stream, behind begin_step."""
+        check(_lib.lib().hps_engine_salame_scale_slice(self._h, int(islice), float(W)))
 
     def pc_stats(self):
         """(predictor-corrector iterations so far, sum over slices of the final relative B-field error)."""

@@ -20,16 +20,20 @@
 namespace hps {
 
 // MULTI (several beam species): the charge per cell volume is the lane's species'
-template <int ORDER, bool MULTI>
+// SEL (SALAME's step 0 in a moving-beam engine): only the species whose bit is set in multi.mask deposit -- a do_salame
+// species leaves jx, jy of Next alone, the SALAME slice's jz_beam takes the do_salame species only (MultiBeam.cpp:42-59)
+template <int ORDER, bool MULTI, bool SEL = false>
 __global__ __launch_bounds__(256)
 void k_beam_deposit_dyn (SlabView f, BeamSoA b, const long* __restrict__ B, const int* __restrict__ nfront, int p,
                          int cjx, int cjy, int cjz, double q_invvol, double clightsq_inv, PartConsts k, int* disturbed,
                          BeamMultiArgs<MULTI> multi)
 {
+    static_assert(MULTI || !SEL, "a species selection needs the tag row");
     const long first = B[p] + nfront[p], count = B[p + 1] - first;
     for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
     const long ip = first + t;
     if (b.nsub[ip] < 0) continue;               // absorbed at the boundary
+    if constexpr (SEL) { if (!(multi.mask >> b.sp[ip] & 1u)) continue; }
     const double ux = b.ux[ip], uy = b.uy[ip], uz = b.uz[ip];
     const double gaminv = 1.0/sqrt(1.0 + ux*ux*clightsq_inv + uy*uy*clightsq_inv + uz*uz*clightsq_inv);
     if constexpr (MULTI) q_invvol = multi.tab[b.sp[ip]].q_invvol;
@@ -300,6 +304,26 @@ int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz)
     return HPS_OK;
 }
 
+// the same deposit restricted to the species in mask: launched by step 0 of a SALAME engine only (solve_slice_begin's jx, jy of
+// Next without the do_salame species; Engine::salame_module's jz of the do_salame species alone)
+int beam_deposit_species (Engine& E, int p, unsigned mask, int cjx, int cjy, int cjz)
+{
+    if (p < 0 || p >= E.d.nz || !E.multi_beam() || (mask & E.species_mask_all()) == 0) return HPS_OK;
+    const long bound = E.beam_bound(p);
+    if (bound <= 0) return HPS_OK;
+    const SlabView f(E.slab);
+    const PartConsts k = base_consts(E.gm);
+    const double csq_inv = 1.0/(E.gm.c*E.gm.c);
+    const dim3 grid((unsigned)std::min<long>(ceil_div(bound, 256), 2048)), block(256);
+    const BeamMultiArgs<true> m{E.d_bsp_tab, E.n_beam_species(), mask};
+#define CALL(O) hipLaunchKernelGGL((k_beam_deposit_dyn<O, true, true>), grid, block, 0, E.st, f, E.bm, E.d_B, E.d_nfront, p, cjx, cjy, cjz, 0.0, csq_inv, k, E.d_pc_dist, m)
+    HPS_BEAM_ORDER(E.d.order, CALL)
+#undef CALL
+    E.beam_launched |= 1UL << (28 + std::min(std::max(E.d.order, 0), 3));
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
 int beam_moments_reset (Engine& E)
 {
     hipLaunchKernelGGL(k_beam_moments_reset, dim3(1), dim3(256), 0, E.st, E.d_mom, E.d.nz, E.n_beam_species());
@@ -365,6 +389,8 @@ std::string beam_kernel_names (const Engine& E)
         if (E.beam_launched >> (16 + q) & 1UL) { std::snprintf(b, sizeof b, "k_beam_deposit_dyn<%d,%d>\n", q >> 1, q & 1); out += b; }
     for (int q = 0; q < 4; ++q)
         if (E.beam_launched >> (24 + q) & 1UL) { std::snprintf(b, sizeof b, "k_beam_partition<%d,%d>\n", q >> 1, q & 1); out += b; }
+    for (int q = 0; q < 4; ++q)      // (the species-masked deposit of SALAME's step 0: ORDER, MULTI, SEL)
+        if (E.beam_launched >> (28 + q) & 1UL) { std::snprintf(b, sizeof b, "k_beam_deposit_dyn<%d,1,1>\n", q); out += b; }
     return out;
 }
 
@@ -414,6 +440,7 @@ int Engine::add_beam_species (const hps_beam_species* s, int* index_out)
     HPS_REQUIRE(std::isfinite(s->charge) && std::isfinite(s->mass) && s->mass >= 0.0 && std::isfinite(s->spin_anom), fn + "charge, mass and spin_anom must be finite, the mass not negative");
 #define HPS_REFUSE(cond, msg) do { if (cond) { set_error(fn + msg); return HPS_ERR_UNSUPPORTED; } } while (0)
     HPS_REFUSE(d.beam_do_salame, "several beam species with beam_do_salame are not supported (SALAME acts on the one beam of a static-beam engine)");
+    HPS_REQUIRE(!(s->do_salame && !species_salame), fn + "a do_salame species needs beam_species_salame (hps_engine_set_beam_species_salame, right behind hps_engine_create: it allocates the SALAME slice)");
     HPS_REFUSE(!(d.dt != 0.0 || d.dt_adaptive), "several beam species need a moving beam (hipace.dt != 0 or adaptive): a static beam (dt = 0) has no species tag");
     for (const Collision& c : coll)
         HPS_REFUSE(c.beam, "several beam species with a beam-plasma collision (hps_engine_add_beam_collision) are not supported: the collision takes one beam's charge and mass");
@@ -423,7 +450,7 @@ int Engine::add_beam_species (const hps_beam_species* s, int* index_out)
     if (bsp.empty()) {      // species 0: the deck's beam, as the container holds it
         BeamSpecies b0;
         b0.s = hps_beam_species{d.beam_charge, d.beam_mass, d.beam_n_subcycles, d.beam_no_z_push, d.beam_radiation_reaction, d.beam_spin_tracking,
-                                d.beam_spin_anom, d.beam_umean[2], d.beam_uz_std};
+                                d.beam_spin_anom, d.beam_umean[2], d.beam_uz_std, 0};      // (species 0 is never the SALAME beam of a moving engine)
         b0.count = nbeam; b0.filled = nbeam > 0;
         bsp.push_back(b0);
     }
@@ -488,6 +515,7 @@ int Engine::merge_stashed_beam (BeamStash& A, int e_setter)
     } else (void)hipStreamSynchronize(st);
     release_beam();                                  // the new species' own container
     (void)hipFree(A.blocks); (void)hipFree(A.tag); A.blocks = nullptr; A.tag = nullptr;
+    bsp[(size_t)k].off = beam_off;                   // the species' own slices: what it holds of each when step 0 begins
     beam_off = off_m; host_beam = true;
     beam_tag = tag_m.release();
     bsp[(size_t)k].count = nb; bsp[(size_t)k].filled = true;

@@ -561,6 +561,8 @@ int Engine::set_beam_fixed_weight (const hps_beam_fixed_weight* s, const hps_exp
     HPS_REQUIRE(d.beam_charge != 0.0, fn + "the deck's beam_charge must not be 0");
     HPS_REQUIRE(!(d.beam_do_salame && s->profile == 0 && (std::isinf(s->zmin) || std::isinf(s->zmax))),
                 fn + "a beam_do_salame deck needs the can profile, or zmin and zmax with the gaussian profile (BeamParticleContainer.cpp:149)");
+    HPS_REQUIRE(!(sel_species > 0 && sel_species < (int)bsp.size() && bsp[(size_t)sel_species].s.do_salame && s->profile == 0 && (std::isinf(s->zmin) || std::isinf(s->zmax))),
+                fn + "a do_salame beam species needs the can profile, or zmin and zmax with the gaussian profile (BeamParticleContainer.cpp:149)");
     int depth_x = 0, depth_y = 0;
     if (int e = expr_check_named(name, "position_mean[0]: ", mean_x, 1, &depth_x)) return e;
     if (int e = expr_check_named(name, "position_mean[1]: ", mean_y, 1, &depth_y)) return e;

@@ -77,7 +77,8 @@ struct BeamSpeciesRec { double q_invvol, qm, dt, RRcoeff, spin_anom; int nsc, rr
 struct BeamSpeciesTable { BeamSpeciesRec r[HPS_MAX_BEAM_SPECIES]; };
 // the table as a kernel argument: nothing in the kernels of a one-species engine
 template <bool MULTI> struct BeamMultiArgs {};
-template <> struct BeamMultiArgs<true> { const BeamSpeciesRec* tab; int ns; };
+// (mask: the species a SEL deposit takes, bit k = species k; read by k_beam_deposit_dyn<ORDER, true, true> alone)
+template <> struct BeamMultiArgs<true> { const BeamSpeciesRec* tab; int ns; unsigned mask; };
 
 // cell lists of the collision kernels (collisions.hip): per species slot the exclusive cell offsets [ncells + 1] and the
 // cell-sorted particle indices; cnt [ncells + 1] is shared (zero between launches); stats = {pairs collided, overfull cells}
@@ -183,7 +184,9 @@ struct Engine {
     // carries a tag row (bm.sp, its twin for the partition bm_scr.sp) and the beam kernels are the MULTI instantiations, which read
     // the per-species constants from d_bsp_tab (written once per step: the sub-cycle's dt is the step's).  beam_tag: the tags in the
     // order of beam_init's blocks (null: all 0); sel_species: whom the beam setters fill (hps_engine_select_beam_species).
-    struct BeamSpecies { hps_beam_species s{}; long count = 0; bool filled = false; };
+    // off: the species' own slice offsets [nz + 1] (head first) as its setter left them, kept at merge time: the particles of a
+    // slice that have not slipped in during step 0 (MultiBeam::isSalameNow) without a device read
+    struct BeamSpecies { hps_beam_species s{}; long count = 0; bool filled = false; std::vector<long> off; };
     std::vector<BeamSpecies> bsp; int sel_species = 0;
     unsigned char *bm_sp = nullptr, *bm_sp_scr = nullptr, *beam_tag = nullptr; BeamSpeciesRec* d_bsp_tab = nullptr;
     unsigned long beam_launched = 0;      // which beam kernel instances this engine has launched (beam.hip: beam_kernel_names)
@@ -356,6 +359,16 @@ struct Engine {
     int c_sal = -1; int sal_last_slice = -2; bool sal_overloaded = false; double sal_zeta_initial = 0.0;
     double* d_sal = nullptr; std::vector<double> sal_stats;
     bool salame_now () const { return c_sal >= 0 && step_index == 0; }      // MultiBeam::isSalameNow without the particle count
+    // A moving-beam engine (hps_engine_set_beam_species_salame -> species_salame): the do_salame species as a mask (bit k =
+    // species k; 0: none added), every species, and the SALAME particles slice p (from the head) held when step 0 began
+    unsigned salame_mask () const { unsigned m = 0; for (size_t k = 0; k < bsp.size(); ++k) if (bsp[k].s.do_salame) m |= 1u << k; return m; }
+    unsigned species_mask_all () const { return (1u << n_beam_species()) - 1u; }
+    long salame_count (int p) const {
+        long n = 0;
+        for (const BeamSpecies& b : bsp) if (b.s.do_salame && (long)b.off.size() == d.nz + 1 && p >= 0 && p < d.nz) n += b.off[(size_t)p + 1] - b.off[(size_t)p];
+        return n;
+    }
+    bool species_salame = false; int set_beam_species_salame (int on);
     int salame_module (int islice);
     int salame_solve_ez ();
     int run_step ();
@@ -418,6 +431,8 @@ int expr_check_named (const char* fn, const char* what, const hps_expr* p, int n
 bool expr_is_zero (const hps_expr& p);
 int beam_blocks_to_soa (Engine& E, const double* blocks, double* soa, long nb);      // beam_init.hip: slice-major blocks -> global SoA (beam_off)
 int beam_deposit_moving (Engine& E, int p, int cjx, int cjy, int cjz);      // beam.hip
+int beam_deposit_species (Engine& E, int p, unsigned mask, int cjx, int cjy, int cjz);      // ... of the species in mask (SALAME's step 0)
+int salame_scale_moving (Engine& E, int p, unsigned mask, double W);        // SalameMultiplyBeamWeight on slice p of the container
 int beam_push_moving (Engine& E, int islice);
 int beam_push_slice (Engine& E, int islice, int p, long bound);
 int beam_moments_reset (Engine& E);

@@ -762,7 +762,9 @@ int Engine::create (const hps_deck& deck, int device)
             set_error("hps_engine_create: beam_do_salame with a gaussian beam profile needs finite beam_zmin and beam_zmax (BeamParticleContainer.cpp:149)"); return HPS_ERR_ARG; }
         if (d.ion_on) { set_error("hps_engine_create: beam_do_salame with the ionisable species (ion_on) is not supported"); return HPS_ERR_UNSUPPORTED; }
         if (d.laser_on) { set_error("hps_engine_create: beam_do_salame with a laser is not supported"); return HPS_ERR_UNSUPPORTED; }
-        if (d.dt != 0.0 || d.dt_adaptive) { set_error("hps_engine_create: beam_do_salame needs a static beam (hipace.dt = 0)"); return HPS_ERR_UNSUPPORTED; }
+        if (d.dt != 0.0 || d.dt_adaptive) {
+            set_error("hps_engine_create: beam_do_salame needs a static beam (hipace.dt = 0): the SALAME beam of a moving-beam engine is an added "
+                      "species (hps_engine_set_beam_species_salame: beam_species_salame, do_salame)"); return HPS_ERR_UNSUPPORTED; }
         HPS_REQUIRE(d.salame_n_iter >= 0 && d.salame_relative_tolerance >= 0.0, "hps_engine_create: salame_n_iter and salame_relative_tolerance must not be negative");
         if (d.salame_n_iter == 0) d.salame_n_iter = 5;                                    // hipace.salame_n_iter (Hipace.H)
         if (d.salame_relative_tolerance == 0.0) d.salame_relative_tolerance = 1.0e-4;      // hipace.salame_relative_tolerance
@@ -1936,7 +1938,7 @@ int Engine::solve_slice_begin (int islice)
     }
     // the auxiliary stream may start on the beam's planes (zeroed above)
     // SALAME's step 0 (MultiBeam::isSalameNow): the slice runs through the plain sequence -- no paired / folded beam deposit, no
-    // auxiliary stream, no fused or gated push, no deferred shift -- and the beam deposits no jx, jy on Next (MultiBeam.cpp:50-56)
+    // auxiliary stream, no fused or gated push, no deferred shift -- and the SALAME beam deposits no jx, jy on Next (MultiBeam.cpp:50-56)
     const bool sal = salame_now();
     const bool aux = aux_on && st_aux && !pc && !ahead && !prof_now && !sal;
     if (aux) { HPS_HIP_CHECK(hipEventRecord(ev_aux[0], st)); HPS_HIP_CHECK(hipStreamWaitEvent(st_aux, ev_aux[0], 0)); }
@@ -2045,7 +2047,10 @@ int Engine::solve_slice_begin (int islice)
                            HPS_C_EXMBY, HPS_C_EYPBX, 0.5*(1.0/gm.dx), 0.5*(1.0/gm.dy));
         mark();   // b3
         // beam jx, jy of the next slice; beam part of Sx, Sy (Hipace.cpp:656-660)
-        if (!sal) { if ((e = deposit_beam_slice(islice - 1, L.njxb, L.njyb, -1))) return e; }
+        // (SALAME's step 0: a do_salame beam deposits no jx, jy on Next, every other species does -- MultiBeam.cpp:50-56)
+        const unsigned smask = (sal && moving) ? salame_mask() : 0u;
+        if (!sal || (moving && smask == 0)) { if ((e = deposit_beam_slice(islice - 1, L.njxb, L.njyb, -1))) return e; }
+        else if (moving && nbeam > 0) { if ((e = beam_deposit_species(*this, d.nz - islice, species_mask_all() & ~smask, L.njxb, L.njyb, -1))) return e; }
         hipLaunchKernelGGL(k_sxsy_beam, dim3(ceil_div(slab.jstride, 256), d.ny + 2*g), b256, 0, st, f, HPS_C_SX, HPS_C_SY, L.jzb, L.njxb, L.njyb,
                            HPS_C_P_JXB, HPS_C_P_JYB, gm.mu0, 2.0*gm.dx, 2.0*gm.dy, 2.0*gm.dz, bb);
     }
@@ -2141,6 +2146,11 @@ int Engine::solve_slice_finish (int islice)
     if (salame_now() && !moving && nbeam > 0 && beam_off[d.nz - islice] - beam_off[d.nz - 1 - islice] > 0) {
         if ((e = salame_module(islice))) return e;
     }
+    // ... a moving-beam engine: on a slice that held particles of a do_salame species when the step began (MultiBeam::isSalameNow
+    // counts getNumParticles(This): what has slipped in during this step does not count)
+    if (salame_now() && moving && nbeam > 0 && salame_count(d.nz - 1 - islice) > 0) {
+        if ((e = salame_module(islice))) return e;
+    }
 
     if (!gated && !gated_ion) {
     mark();   // b6
@@ -2212,6 +2222,43 @@ int Engine::solve_slice_finish (int islice)
 }
 
 
+// hps_engine_set_beam_species_salame: a do_salame species will be added to this moving-beam engine.  What Engine::create gives a
+// beam_do_salame deck, allocated now: the SALAME planes behind the engine's own (the slab holds nothing but begin_step's zeros
+// yet), the W reduction's scratch and statistics, the plasma sheet with x_prev, y_prev of their own (alloc_sheets, as the other
+// setters of the sheet call it again).
+int Engine::set_beam_species_salame (int on)
+{
+    static const std::string fn = "hps_engine_set_beam_species_salame: ";
+    if (!on) return HPS_OK;
+    if (species_salame) return HPS_OK;
+#define HPS_REFUSE(cond, msg) do { if (cond) { set_error(fn + msg); return HPS_ERR_UNSUPPORTED; } } while (0)
+    HPS_REFUSE(d.beam_do_salame, "the deck has beam_do_salame: that is the one beam of a static-beam engine, a do_salame species belongs to a moving-beam engine");
+    HPS_REFUSE(!moving, "beam_species_salame needs a moving beam (hipace.dt != 0 or adaptive): a static beam (dt = 0) has no species; its one beam takes beam_do_salame");
+    HPS_REFUSE(pc, "beam_species_salame needs the explicit solver (Hipace.cpp:152), not the predictor-corrector");
+    HPS_REFUSE(d.ion_on, "beam_species_salame with the ionisable species (ion_on) is not supported");
+    HPS_REFUSE(d.laser_on, "beam_species_salame with a laser is not supported");
+#undef HPS_REFUSE
+    HPS_REQUIRE(!step_begun && !el.tiling && steps_begun == 0 && bsp.empty() && coll.empty() && !fine_patch_set,
+                fn + "call behind hps_engine_create, ahead of the other setters, of hps_engine_add_beam_species and of the first hps_engine_begin_step");
+    HPS_REQUIRE(d.salame_n_iter >= 0 && d.salame_relative_tolerance >= 0.0, fn + "salame_n_iter and salame_relative_tolerance must not be negative");
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    double* grown = nullptr;
+    const size_t bytes = (size_t)slab.nstride*(slab.ncomp + (int)HPS_SAL_NCOMP)*sizeof(double);
+    HPS_HIP_CHECK(hipMalloc(&grown, bytes));
+    if (hipMemset(grown, 0, bytes) != hipSuccess || hipMalloc(&d_sal, (size_t)4*257*sizeof(double)) != hipSuccess) {
+        (void)hipFree(grown); set_error(fn + "allocation of the SALAME slice failed"); return HPS_ERR_HIP; }
+    (void)hipFree(slab.p);
+    slab.p = grown;
+    c_sal = slab.ncomp;                      // (= ncomp: a moving-beam engine has no alternates of the re-initialised planes)
+    slab.ncomp += (int)HPS_SAL_NCOMP;
+    sal_stats.assign((size_t)4*d.nz, 0.0);
+    if (d.salame_n_iter == 0) d.salame_n_iter = 5;                                    // hipace.salame_n_iter (Hipace.H)
+    if (d.salame_relative_tolerance == 0.0) d.salame_relative_tolerance = 1.0e-4;      // hipace.salame_relative_tolerance
+    species_salame = true;
+    el.temp_push = true;                     // the plasma is pushed to temporary slices from x_prev (Species::alias_prev)
+    return alloc_sheets();
+}
+
 // SolvePoissonEz(WhichSlice::Salame) (fields/Fields.cpp:960-1006): Ez of the SALAME slice from its jx, jy
 int Engine::salame_solve_ez ()
 {
@@ -2222,7 +2269,8 @@ int Engine::salame_solve_ez ()
     return hps_poisson_solve(ps, staging, slab, c_sal + HPS_SAL_EZ, st);
 }
 
-// SalameModule (salame/Salame.cpp:13-189) on level 0 with one beam species, statement by statement.  The fields of This
+// SalameModule (salame/Salame.cpp:13-189) on level 0, statement by statement: with the one beam of a static-beam engine, or
+// with the do_salame species of a moving-beam engine's container.  The fields of This
 // are solved; the sheet holds the committed state of this slice (x_prev, y_prev, u_half) and is pushed to the temporary
 // slice only.  The host reads W once per iteration, as the reference does.
 int Engine::salame_module (int islice)
@@ -2265,7 +2313,13 @@ int Engine::salame_module (int islice)
         if ((e = species_explicit(el, cache, depos))) return e; }
     copy({S + HPS_SAL_SY_BACK, S + HPS_SAL_SX_BACK}, {HPS_C_SY, HPS_C_SX});
 
-    const long first0 = beam_off[d.nz - 1 - islice], count = beam_off[d.nz - islice] - first0;
+    // static beam: the slice's block; moving beam: the do_salame species of the container's slice (the deposits onto the SALAME
+    // slice take them alone, MultiBeam.cpp:44-47; STEP 4's onto This takes every species)
+    const long first0 = moving ? 0 : beam_off[d.nz - 1 - islice], count = moving ? 0 : beam_off[d.nz - islice] - first0;
+    const unsigned smask = moving ? salame_mask() : 0u;
+    auto deposit_salame = [&] (int cjz) -> int {
+        return moving ? beam_deposit_species(*this, d.nz - 1 - islice, smask, -1, -1, cjz) : deposit_beam_slice(islice, -1, -1, cjz);
+    };
     double W = 1.0, W_total = 0.0;
     int iter = 0, used = 0; bool converged = false, undetermined = false;
     for (; iter < d.salame_n_iter; ++iter) {
@@ -2278,7 +2332,7 @@ int Engine::salame_module (int islice)
         copy({S + HPS_SAL_EZ_NO_SALAME}, {S + HPS_SAL_EZ});
 
         // STEP 2: Ez of the SALAME beam alone (:75-121)
-        if ((e = deposit_beam_slice(islice, -1, -1, S + HPS_SAL_JZB))) return e;
+        if ((e = deposit_salame(S + HPS_SAL_JZB))) return e;
         if ((e = hps_salame_sxsy_from_jz(slab, gm, S + HPS_SAL_JZB, S + HPS_SAL_SY, S + HPS_SAL_SX, st))) return e;
         if ((e = solve_bxby(S + HPS_SAL_BX, S + HPS_SAL_SY))) return e;       // zero guess, This chi
         zero({S + HPS_SAL_EZ, S + HPS_SAL_JX, S + HPS_SAL_JY});
@@ -2292,7 +2346,7 @@ int Engine::salame_module (int islice)
 
         // STEP 3: the weight factor (:123-158)
         zero({S + HPS_SAL_JZB});
-        if ((e = deposit_beam_slice(islice, -1, -1, S + HPS_SAL_JZB))) return e;
+        if ((e = deposit_salame(S + HPS_SAL_JZB))) return e;
         double s4[4];
         if ((e = salame_get_w_enqueue(slab, S + HPS_SAL_EZ_TARGET, S + HPS_SAL_EZ_NO_SALAME, S + HPS_SAL_EZ, S + HPS_SAL_JZB, d_sal, st))) return e;
         HPS_HIP_CHECK(hipMemcpyAsync(s4, salame_get_w_result(d_sal), sizeof(s4), hipMemcpyDeviceToHost, st));
@@ -2316,7 +2370,8 @@ int Engine::salame_module (int islice)
         bool last = undetermined;
         if (!undetermined && (W < 0.0 || sal_overloaded)) { W = 0.0; W_total = 0.0; last = true; sal_overloaded = true; }
         if (!undetermined && !sal_overloaded && iter >= 1 && std::fabs(W - 1.0) < d.salame_relative_tolerance) { last = true; converged = true; }
-        if ((e = hps_salame_scale_beam_slice(beam_cur + 7*first0 + 6*count, count, W, st))) return e;
+        if (moving) { if ((e = salame_scale_moving(*this, d.nz - 1 - islice, smask, W))) return e; }
+        else if ((e = hps_salame_scale_beam_slice(beam_cur + 7*first0 + 6*count, count, W, st))) return e;
 
         // STEP 4: the fields of This with the new weight (:160-182)
         {   CompList zb{0, {}}; zb.c[zb.n++] = HPS_C_JZB;
@@ -2980,10 +3035,38 @@ extern "C" int hps_engine_salame_stats (void* h, double* out)
 {
     HPS_REQUIRE(h && out, "hps_engine_salame_stats: null argument");
     Engine* E = static_cast<Engine*>(h);
-    HPS_REQUIRE(E->c_sal >= 0, "hps_engine_salame_stats: the deck has no beam_do_salame");
+    HPS_REQUIRE(E->c_sal >= 0, "hps_engine_salame_stats: the deck has no beam_do_salame (nor was hps_engine_set_beam_species_salame called)");
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     std::memcpy(out, E->sal_stats.data(), E->sal_stats.size()*sizeof(double));
     return HPS_OK;
+}
+extern "C" int hps_engine_set_beam_species_salame (void* h, int on)
+{
+    HPS_REQUIRE(h, "hps_engine_set_beam_species_salame: null engine");
+    return static_cast<Engine*>(h)->set_beam_species_salame(on);
+}
+extern "C" int hps_engine_deposit_beam_species (void* h, int islice, unsigned species_mask, int cjx, int cjy, int cjz)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E, "hps_engine_deposit_beam_species: null engine");
+    HPS_REQUIRE(E->moving, "hps_engine_deposit_beam_species: needs a moving beam (hipace.dt != 0 or adaptive): a static beam has no species");
+    HPS_REQUIRE(E->steps_begun > 0 && !E->beam_import, "hps_engine_deposit_beam_species: call after hps_engine_begin_step, on an engine that holds its beam");
+    HPS_REQUIRE(islice >= 0 && islice < E->d.nz, "hps_engine_deposit_beam_species: no such slice");
+    HPS_REQUIRE((cjx >= 0) == (cjy >= 0), "hps_engine_deposit_beam_species: cjx and cjy go together");
+    for (int c : {cjx, cjy, cjz}) HPS_REQUIRE(c >= -1 && c < E->slab.ncomp, "hps_engine_deposit_beam_species: bad component");
+    HPS_REQUIRE(E->multi_beam(), "hps_engine_deposit_beam_species: the engine holds one beam species (no tag row to select by)");
+    E->flush_shift();
+    return beam_deposit_species(*E, E->d.nz - 1 - islice, species_mask, cjx, cjy, cjz);
+}
+extern "C" int hps_engine_salame_scale_slice (void* h, int islice, double W)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E, "hps_engine_salame_scale_slice: null engine");
+    HPS_REQUIRE(E->moving, "hps_engine_salame_scale_slice: needs a moving beam (hipace.dt != 0 or adaptive): the one beam of a static-beam engine takes hps_salame_scale_beam_slice");
+    HPS_REQUIRE(E->steps_begun > 0 && !E->beam_import, "hps_engine_salame_scale_slice: call after hps_engine_begin_step, on an engine that holds its beam");
+    HPS_REQUIRE(islice >= 0 && islice < E->d.nz, "hps_engine_salame_scale_slice: no such slice");
+    HPS_REQUIRE(std::isfinite(W), "hps_engine_salame_scale_slice: W must be finite");
+    return salame_scale_moving(*E, E->d.nz - 1 - islice, E->salame_mask(), W);
 }
 extern "C" int hps_open_boundary (double* staging_dev, int nbatch, int nx, int ny, const double lo[2], const double hi[2],
                                   unsigned no_monopole_mask, void* stream)

@@ -108,6 +108,32 @@ void k_salame_scale_w (double* __restrict__ w, long n, double W)
     w[t] = (W == 0.0) ? 0.0 : w[t]*W;
 }
 
+// ... on slice p of a moving-beam engine's container (beam.hip): the particles [B[p] + nfront[p], B[p + 1]) -- those that have
+// not slipped in during this step -- whose species is in mask and that are not absorbed.  Every lane owns its particle: no
+// atomics.  W == 0: gone, as the push's absorbing boundary leaves a particle (beam_push.h: w = 0, nsub = -1).
+__global__ __launch_bounds__(256)
+void k_salame_scale_moving (BeamSoA b, const long* __restrict__ B, const int* __restrict__ nfront, int p, unsigned mask, double W)
+{
+    const long first = B[p] + nfront[p], count = B[p + 1] - first;
+    for (long t = (long)blockIdx.x*blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x*blockDim.x) {
+        const long ip = first + t;
+        if (!(mask >> b.sp[ip] & 1u) || b.nsub[ip] < 0) continue;
+        if (W == 0.0) { b.w[ip] = 0.0; b.nsub[ip] = -1; }
+        else b.w[ip] *= W;
+    }
+}
+
+int salame_scale_moving (Engine& E, int p, unsigned mask, double W)
+{
+    if (p < 0 || p >= E.d.nz || !E.multi_beam() || (mask & E.species_mask_all()) == 0) return HPS_OK;
+    const long bound = E.beam_bound(p);
+    if (bound <= 0) return HPS_OK;
+    const dim3 grid((unsigned)std::min<long>(ceil_div(bound, 256), 2048));
+    hipLaunchKernelGGL(k_salame_scale_moving, grid, dim3(256), 0, E.st, E.bm, E.d_B, E.d_nfront, p, mask, W);
+    HPS_HIP_CHECK(hipGetLastError());
+    return HPS_OK;
+}
+
 static bool comp_ok (const hps_slab& s, int c) { return c >= 0 && c < s.ncomp; }
 
 int salame_get_w_enqueue (const hps_slab& slab, int cT, int cN, int cE, int cJ, double* scratch, hipStream_t st)

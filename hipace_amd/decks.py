@@ -78,6 +78,12 @@ ADAPTIVE_DEFAULT = dict(
 # the linear target Ez_initial + slope (zeta - zeta_initial) that stands in for the parsed hipace.salame_Ez_target
 SALAME_DEFAULT = dict(beam_do_salame=0, salame_n_iter=0, salame_relative_tolerance=0.0, salame_no_advance=0,
                       salame_Ez_target_slope=0.0)
+# SALAME on a witness species of a moving-beam engine: beam_do_salame is the one beam of a static-beam engine; with
+# hipace.dt != 0 the SALAME beam is an entry of beam_species that carries do_salame (BEAM_SPECIES_DEFAULT).  beam_species_salame
+# announces such a species -- the engine then allocates the SALAME slice ahead of every species.  Like "collisions" it is no
+# member of hps_deck (nor of SALAME_DEFAULT, which mirrors the deck's members): SliceEngine applies it through
+# hps_engine_set_beam_species_salame, and sets it itself when an entry of the deck's beam_species carries do_salame.
+SALAME_SPECIES_DEFAULT = dict(beam_species_salame=0)
 
 # <plasma>.fine_ppc, <ion>.fine_ppc and <plasma>.hollow_core_radius (PlasmaParticleContainer.cpp:123-169).  Kept apart from
 # _DEFAULT like ADAPTIVE_DEFAULT; 0 = off.  Like "collisions" they are not members of hps_deck: SliceEngine applies them
@@ -184,8 +190,10 @@ def beam_fixed_weight(deck):
 # deck's.  Exactly one source: fixed_weight (the keys of BEAM_FIXED_WEIGHT_DEFAULT), fixed_weight_pdf (those of
 # BEAM_FIXED_WEIGHT_PDF_DEFAULT), density_expr (with the keys of BEAM_INIT_DEFAULT but the expression: constants, min_density,
 # u_std, random_ppc, seed) or particles (a (7, n) array x y z ux uy uz w).  It is no member of _DEFAULT or hps_deck.
+# do_salame (<beam>.do_salame of that species): it takes part in SALAME during step 0; it enters the species' record only where
+# the entry sets it (hps_beam_species.do_salame stays 0 otherwise), and needs the deck's beam_species_salame (SALAME_SPECIES_DEFAULT).
 BEAM_SPECIES_DEFAULT = dict(name=None, charge=None, mass=None, n_subcycles=None, do_z_push=None, radiation_reaction=None,
-                            spin_anom=None, do_spin_tracking=None, uz_mean=0.0, uz_std=0.0)
+                            spin_anom=None, do_spin_tracking=None, uz_mean=0.0, uz_std=0.0, do_salame=None)
 BEAM_SPECIES_SOURCES = ("fixed_weight", "fixed_weight_pdf", "density_expr", "particles")
 BEAM_SPECIES_EXPR_KEYS = ("constants", "min_density", "u_std", "random_ppc", "seed")
 MAX_BEAM_SPECIES = 4
@@ -218,6 +226,8 @@ def beam_species_spec(deck, spec, where="beam_species"):
                   do_spin_tracking=int(bool(pick("do_spin_tracking", "beam_spin_tracking", 0))),
                   spin_anom=float(pick("spin_anom", "beam_spin_anom", 0.0)),
                   uz_mean=float(spec.get("uz_mean", 0.0) or 0.0), uz_std=float(spec.get("uz_std", 0.0) or 0.0))
+    if spec.get("do_salame") is not None:
+        record["do_salame"] = int(bool(spec["do_salame"]))
     if source == "fixed_weight":
         bad = set(spec[source]) - set(BEAM_FIXED_WEIGHT_DEFAULT)
         args = dict(BEAM_FIXED_WEIGHT_DEFAULT, **spec[source])
@@ -258,6 +268,17 @@ def beam_species(deck):
     if len(set(names)) != len(names):
         raise ValueError(f"beam_species: a name is given twice ({names})")
     return out
+
+
+def beam_species_salame(deck):
+    """-> 1 if the deck announces a do_salame beam species: its own beam_species_salame, or an entry of beam_species that carries
+    do_salame (SALAME_SPECIES_DEFAULT); 0 otherwise"""
+    if deck.get("beam_species_salame", 0):
+        return 1
+    entry = deck.get("beam_species") or ()
+    if isinstance(entry, dict):
+        return 0
+    return int(any(isinstance(s, dict) and s.get("do_salame") for s in entry))
 
 
 def with_fixed_weight_beam(deck, beam=None, **more):
@@ -853,6 +874,52 @@ def salame_grid_current_overload():
     """`salame_grid_current` with the witness reaching to z = -3.0 (slice 36), past the point (z = -2.0) where the unloaded Ez changes
     sign: no positive weight holds the target there, W < 0 must occur and the rest of the witness is dropped."""
     return salame_grid_current(zmin=-3.0)
+
+
+def salame_grid_current_moving(zmin=-1.4, zmax=0.78, density=0.5, dt=0.1):
+    """`salame_grid_current` in a moving-beam engine (hipace.dt = dt != 0): the deck's own beam is empty (beam_profile
+    = -1) behind the same grid current, and the same witness -- the flat top written as <beam>.density(x,y,z) = n0 for the device's
+    fixed_ppc generator, which takes the deck's window beam_zmin / beam_zmax / beam_radius, beam_ppc and beam_umean -- is species 1
+    with do_salame.  beam_do_salame = 0, beam_species_salame = 1 (SALAME_SPECIES_DEFAULT)."""
+    d = salame_grid_current(zmin=zmin, zmax=zmax, density=density)
+    d.update(SALAME_SPECIES_DEFAULT)
+    d.update(beam_profile=-1, beam_do_salame=0, beam_species_salame=1, dt=dt)
+    d["beam_name"] = "driver"
+    d["beam_species"] = [dict(name="witness", do_salame=1, density_expr="n0", constants=dict(n0=float(density)))]
+    return d
+
+
+def salame_grid_current_moving_overload():
+    """the moving twin of `salame_grid_current_overload`"""
+    return salame_grid_current_moving(zmin=-3.0)
+
+
+SALAME_WITNESS_DENSITY = "if(z < zw, 1, 0)*if(x*x + y*y < rw*rw, n0, 0)"
+
+
+def salame_driver_witness(zmin=-1.4, zmax=0.78, density=0.5, dt=0.1, driver_zmax=5.94, driver_radius=2.0):
+    """A particle driver and a do_salame witness in one moving-beam engine, the case SALAME was written for: the box,
+    the plasma and the witness of `salame_grid_current_moving`, the grid current off.  The driver is the deck's own Gaussian beam
+    with the grid current's shape -- electrons, peak density 0.5, centre z = 3, sigma (0.5, 0.5, 1), u = (0, 0, 2000) -- cut at
+    driver_radius = 2 (four sigma) and at z in [zmin, driver_zmax): finite beam_zmin / beam_zmax.  The fixed_ppc generators of both
+    species share the deck's window and beam_ppc, so the window spans both and the witness's flat top (radius 0.3, z in [zmin,
+    zmax)) is written into its density: SALAME_WITNESS_DENSITY with min_density = n0 / 2.  At the witness head (z = 0.78) the
+    driver's own density is 0.5 exp(-2.46) = 0.043, at its tail 3e-5: the driver's tail overlaps the witness, as a grid current's.
+
+    Placement, from the CPU oracle's run of the driver alone (static, no witness; on-axis Ez, mean of the four central cells):
+        z      5.23   3.83   2.43   1.31   0.75   0.47   0.19  -0.37  -0.65  -0.93  -1.35  -1.77  -2.05  -2.61  -3.17
+        Ez    0.003  0.040  0.083  0.008 -0.053 -0.084 -0.113 -0.156 -0.166 -0.165 -0.135 -0.066 -0.005  0.111  0.165
+    The head (slice 62, z = 0.75) sits where Ez = -0.053 < 0; over the witness (down to slice 47, z = -1.35) the unloaded Ez goes
+    to -0.167 (z = -0.79) and back to -0.135 without changing sign -- that happens at z = -2.07, past the witness: the table of
+    `salame_grid_current` to a tenth, so the witness stays where it is.
+    """
+    d = salame_grid_current_moving(zmin=zmin, zmax=zmax, density=density, dt=dt)
+    d.update(grid_current_on=0, grid_current_peak=0.0, beam_profile=0, beam_density=0.5, beam_pos_mean=(0.0, 0.0, 3.0),
+             beam_pos_std=(0.5, 0.5, 1.0), beam_zmin=zmin, beam_zmax=driver_zmax, beam_radius=driver_radius, beam_charge=-1.0,
+             beam_umean=(0.0, 0.0, 2000.0))
+    d["beam_species"] = [dict(name="witness", do_salame=1, density_expr=SALAME_WITNESS_DENSITY, min_density=0.5 * float(density),
+                              constants=dict(n0=float(density), zw=float(zmax), rw=0.3))]
+    return d
 
 
 def salame_grid_current_SI(**kw):

@@ -38,6 +38,8 @@ import ctypes as C
 import torch
 import torch.distributed as dist
 
+from . import decks as _decks
+
 
 def steps_of_rank(rank, world, n_steps):
     return list(range(rank, n_steps, world))
@@ -674,6 +676,10 @@ def _refuse_salame(engines):
         if getattr(e, "deck", None) and e.deck.get("beam_do_salame", 0):
             raise NotImplementedError("beam_do_salame: SALAME runs on one engine (SliceEngine.run_step); the pipeline's hand-off does "
                                       "not carry the weights it changes in step 0")
+        # (a do_salame species of a moving-beam engine: the deck's own key, or an entry of beam_species that carries it)
+        if getattr(e, "deck", None) and _decks.beam_species_salame(e.deck):
+            raise NotImplementedError("beam_species_salame: SALAME on a beam species (do_salame) runs on one engine (SliceEngine.run_step); "
+                                      "the pipeline's hand-off does not carry the weights it changes in step 0")
 
 
 def _refuse_adaptive_ring(world):

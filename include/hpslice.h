@@ -315,13 +315,16 @@ typedef struct {
      * salame_relative_tolerance (0 -> 1e-4), salame_do_advance (the ABI reads the negation, so that 0 keeps the default "on").
      * The reference's parsed salame_Ez_target(zeta, zeta_initial, Ez_initial) is the linear family Ez_initial +
      * salame_Ez_target_slope (zeta - zeta_initial) here (slope 0: the reference's default).  Explicit solver, static beam
-     * (hipace.dt = 0), a grid current as the driver; DESIGN 8e says what is refused. */
+     * (hipace.dt = 0), a grid current as the driver; DESIGN 8e says what is refused.  beam_do_salame is the ONE beam of a
+     * static-beam engine; in a moving-beam engine the SALAME beam is an added species (hps_engine_set_beam_species_salame,
+     * hps_beam_species.do_salame), for which the salame_* parameters here hold as well. */
     int beam_do_salame; int salame_n_iter; double salame_relative_tolerance; int salame_no_advance;
     double salame_Ez_target_slope;
 } hps_deck;
 
 /* The SALAME slice (fields/Fields.cpp:111-114): twelve planes appended behind the engine's own components (and behind
- * "aabs"), only in a deck with beam_do_salame: the first one is component hps_engine_slab().ncomp - HPS_SAL_NCOMP. */
+ * "aabs"), only in a deck with beam_do_salame or behind hps_engine_set_beam_species_salame: the first one is component
+ * hps_engine_slab().ncomp - HPS_SAL_NCOMP. */
 enum { HPS_SAL_EZ_TARGET = 0, HPS_SAL_EZ_NO_SALAME, HPS_SAL_EZ, HPS_SAL_JX, HPS_SAL_JY, HPS_SAL_JZB, HPS_SAL_BX, HPS_SAL_BY,
        HPS_SAL_SY, HPS_SAL_SX, HPS_SAL_SY_BACK, HPS_SAL_SX_BACK, HPS_SAL_NCOMP };
 
@@ -717,8 +720,34 @@ int hps_open_boundary (double* staging_dev, int nbatch, int nx, int ny, const do
 /* ---- SALAME (salame/Salame.cpp): the engine's module and its operators ------------------------------------------------
  * Per slice of step 0 on which the module ran: out_host[4*islice + {0, 1, 2, 3}] = the last weight factor W, W_total =
  * W * sum(jz) of that iteration (SalameGetW), the iterations used, and flags (bit 0: converged, bit 1: overloaded), the
- * last two as doubles.  All zeros where it did not run.  Synchronises the stream; HPS_ERR_ARG without beam_do_salame. */
+ * last two as doubles.  All zeros where it did not run.  Synchronises the stream; HPS_ERR_ARG without beam_do_salame or
+ * hps_engine_set_beam_species_salame. */
 int hps_engine_salame_stats (void* handle, double* out_host /* [4*nz] */);
+/* SALAME for a witness species of a moving-beam engine (hipace.dt != 0 or adaptive).  beam_do_salame is the one
+ * beam of a static-beam engine; here the SALAME beam is a species added with hps_beam_species.do_salame = 1 (species 0, the
+ * deck's beam, is the driver -- or empty, beam_profile = -1, behind a grid current).  hps_engine_set_beam_species_salame(1)
+ * announces that such a species will be added: called once, behind hps_engine_create and ahead of every other setter and of
+ * the first hps_engine_begin_step, it allocates what a beam_do_salame deck gets at creation -- the twelve HPS_SAL_* planes
+ * behind the engine's own components (hps_engine_info keeps the count without them), the scratch and the statistics of the
+ * W reduction, and a plasma sheet whose x_prev, y_prev are arrays of their own -- and applies the defaults of salame_n_iter
+ * and salame_relative_tolerance.  It is a setter and no member of hps_deck, as the collisions and the further beam species
+ * themselves are.  Refused, each with its reason: a static beam (dt = 0: it has no species), a deck with beam_do_salame, the
+ * predictor-corrector, ion_on, a laser (HPS_ERR_UNSUPPORTED each, the reasons are beam_do_salame's); a call after a
+ * species was added or a step begun (HPS_ERR_ARG).  on = 0 is accepted on any engine and changes nothing.
+ * During step 0 the do_salame species deposit jz only, every other species deposits as always, the deposits onto the SALAME
+ * slice take the do_salame species alone (MultiBeam.cpp:42-59); the module runs on every slice that held particles of such a
+ * species when the step began (:128-140), behind the Bx/By solve and ahead of the in-situ beam diagnostic and the push. */
+int hps_engine_set_beam_species_salame (void* handle, int on);
+/* The two operators the module calls on the container of a moving-beam engine (HPS_ERR_ARG on a static-beam engine and
+ * before the first hps_engine_begin_step; both enqueue on the engine's stream):
+ * hps_engine_deposit_beam_species: the moving beam's deposit of slice islice (the particles that have not slipped in during
+ * this step, BeamDepositCurrent.cpp:100) restricted to the species whose bit is set in species_mask, added to the slab
+ * components cjx, cjy (both or neither; -1: none) and cjz (-1: none) -- k_beam_deposit_dyn<ORDER, 1, 1>.
+ * hps_engine_salame_scale_slice: SalameMultiplyBeamWeight (Salame.cpp:407-435) on slice islice of the container: the
+ * particles of the do_salame species that have not slipped in and are not absorbed get w *= W; W = 0 makes them absorbed
+ * particles (w = 0 exactly, sub-cycle counter -1: what the push's absorbing boundary writes). */
+int hps_engine_deposit_beam_species (void* handle, int islice, unsigned species_mask, int cjx, int cjy, int cjz);
+int hps_engine_salame_scale_slice (void* handle, int islice, double W);
 /* SalameOnlyAdvancePlasma (Salame.cpp:262-339): every valid particle gathers Bx, By (components bx_comp, by_comp) at
  * (x_prev, y_prev) with the plain shape of depos_order and stores ux = 1.5 dz (q/m) By, uy = -1.5 dz (q/m) Bx, q times
  * ion_lev with can_ionize.  Nothing else of the sheet is touched. */
@@ -1094,8 +1123,11 @@ int hps_engine_set_beam_fixed_weight_pdf (void* handle, const hps_beam_fixed_wei
  * Refused, each with its reason in hps_last_error: a call after the first hps_engine_begin_step or a fifth species
  * (HPS_ERR_ARG); a static beam (hipace.dt = 0), beam_do_salame, an engine with hps_engine_add_beam_collision, species that
  * differ in do_spin_tracking (HPS_ERR_UNSUPPORTED each); hps_engine_add_beam_collision refuses an engine with several species
- * in turn.  The ring hand-off carries the tag as one more row of the message (hps_engine_beam_message_rows: 8, or 11 with
- * spin), so every engine of a pipeline is given the same species; the in-situ beam moments are kept per species
+ * in turn.  do_salame: the species takes part in SALAME during step 0 (MultiBeam.cpp:42-59, 128-140: it deposits jz only,
+ * the module scales its weights slice by slice; species 0 is then the driver, or empty behind a grid current); HPS_ERR_ARG
+ * unless hps_engine_set_beam_species_salame came first; a gaussian fixed_weight source for it needs finite zmin and zmax.
+ * The ring hand-off carries the tag as one more row of the message (hps_engine_beam_message_rows: 8, or 11 with spin), so every
+ * engine of a pipeline is given the same species; the in-situ beam moments are kept per species
  * (hps_engine_insitu_beam_species: hps_engine_insitu_beam for species k; hps_engine_insitu_beam refuses several species).
  *
  * hps_engine_select_beam_species(k): the beam setters (hps_engine_set_beam_particles, _fixed_ppc, _fixed_weight,
@@ -1111,13 +1143,15 @@ int hps_engine_set_beam_fixed_weight_pdf (void* handle, const hps_beam_fixed_wei
  * hps_engine_beam_moments_species: hps_engine_beam_moments per species, out [n][4].
  * hps_engine_beam_state and hps_engine_beam_moments refuse an engine with several species (HPS_ERR_ARG).
  * hps_engine_beam_kernels: the names of the beam kernel instances the engine has launched so far, one per line, e.g.
- * "k_beam_push<2,0,0>" (ORDER, EXT, MULTI), "k_beam_deposit_dyn<2,0>", "k_beam_partition<1,0>" (MOM, MULTI); *tagged = does
+ * "k_beam_push<2,0,0>" (ORDER, EXT, MULTI), "k_beam_deposit_dyn<2,0>", "k_beam_partition<1,0>" (MOM, MULTI), and
+ * "k_beam_deposit_dyn<2,1,1>" for the species-masked deposit that only step 0 of a SALAME engine launches; *tagged = does
  * the container hold a tag row.  buf may be NULL (then *len alone is written). */
 #define HPS_MAX_BEAM_SPECIES 4
 typedef struct {
     double charge, mass;
     int n_subcycles, no_z_push, radiation_reaction, do_spin_tracking;
     double spin_anom, uz_mean, uz_std;
+    int do_salame;
 } hps_beam_species;
 int hps_engine_add_beam_species (void* handle, const hps_beam_species* species, int* index_out);
 int hps_engine_select_beam_species (void* handle, int k);
