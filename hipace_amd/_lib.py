@@ -169,6 +169,7 @@ _SIGS = {
     "hps_mg_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                               C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hps_mg_info_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "hps_mg_info_upleg": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "hps_mg_destroy": (C.c_int, [C.c_void_p]),
     "hps_mg2_create": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
     "hps_mg2_solve2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int,

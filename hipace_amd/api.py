@@ -439,6 +439,13 @@ class MultiGrid:
             out["coef_guest"] = bool(guest.value)
         return out
 
+    def upleg_fused_levels(self):
+        """n where the mid levels 1 .. n of a V-cycle make their up-leg in one launch (k_up_fused: 2 or 3; HPS_MG_UP_FUSED,
+        read when the solver is created), 0 where every mid level has a launch of its own."""
+        n = C.c_int()
+        check(_lib.lib().hps_mg_info_upleg(self._h, C.byref(n)))
+        return n.value
+
     def solve1(self, fields, sol_comp, rhs_comp, acoef_comp, tol_rel=1e-4, tol_abs=2.2250738585072014e-308,
                nummaxiter=200):
         it = C.c_int()

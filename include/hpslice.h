@@ -218,6 +218,10 @@ int hps_mg_info (void* handle, int* cc, int* nlev, int* lowv_begin, int* lowv_ki
  * guest workgroup of the solve's initial level-0 pass (HPS_MG_COEF_GUEST, default 1; k_lower_v3 grids whose initial pass runs on
  * 64 x 32 tiles), 0 where the first lower V of a solve derives it itself. */
 int hps_mg_info_schedule (void* handle, int* coef_guest);
+/* The up-leg of a V-cycle.  *fused_levels: n where the mid levels 1 .. n (n = 2 or 3) make their up-leg in one launch
+ * (k_up_fused: HPS_MG_UP_FUSED, default 1; cell-centred grids with k_lower_v3 and lowv_begin >= 3, n = min(3, lowv_begin - 1)),
+ * 0 where every mid level has a launch of its own. */
+int hps_mg_info_upleg (void* handle, int* fused_levels);
 int hps_mg_destroy (void* handle);
 
 /* hpmg::MultiGrid, system type 2 (mg_solver/HpMultiGrid.H:48,84-87 solve2 with an array Re and a scalar Im coefficient;
