@@ -14,6 +14,7 @@
 #include "poisson_src.h"
 #include "beam_deposit.h"
 #include "slab_ops.h"
+#include "particles_tiled.h"
 
 void mg_rider (void* mg_handle, int** dev_words, const int** host_words);     // multigrid.hip
 namespace hps {
@@ -98,7 +99,7 @@ struct Engine {
     hps_geom gm{};
     int g = 0, ncomp = 0;
     hipStream_t st = nullptr;
-    bool st_pooled = false; int st_device = 0;       // the stream came from the per-device pool (engine.hip: create_engine_stream)
+    bool st_pooled = false; int st_device = 0;       // the stream came from the per-device pool (stream_pool.hip: create_engine_stream)
     hps_slab slab{};
     // ADK field ionisation of the species "ion" (ionization.hip): it is tile-sorted once per step (ions hardly move); released
     // electrons are appended to the plasma's sheet behind the tile-sorted body and run through the per-particle kernels until
@@ -263,10 +264,11 @@ struct Engine {
     // predictor-corrector Bx/By (hipace.bxby_solver = predictor-corrector): d_pc = {sum |B|, sum |B - B_iter|, halo
     // fallback counter (int), spare}, h_pc its pinned image read back once per iteration
     // device-side control of the loop (HPS_PC_SPECULATE=0: off): per-iteration flags, iterations enqueued ahead of the host
-    int* d_pc_dist = nullptr;  // predictor-corrector: device word "something other than rounding residue has been deposited in this sweep" (Engine::create)
-    double pc_floor = 0.0;     // sum |B| below this is the exact zero of the serial path (Engine::create)
+    int* d_pc_dist = nullptr;  // predictor-corrector: device word "something other than rounding residue has been deposited in this sweep" (Engine::pc_create)
+    double pc_floor = 0.0;     // sum |B| below this is the exact zero of the serial path (Engine::pc_create)
     int* d_pc_go = nullptr; bool pc_speculate = false; int pc_spec_iters = 1, pc_enqueued = 0, pc_islice = -1; double pc_base_seq = 0.0, pc_last_err = 0.0;
     int solve_slice_pc_begin (int islice); int solve_slice_pc_finish (int islice); int pc_enqueue_iteration (int it); int pc_wait_slot (int slot, double seq);
+    int pc_create (); int pc_slice_ready () const;      // (predcorr.hip: Engine::create's part; hps_engine_slice_ready's answer)
     bool pc = false; double* d_pc = nullptr; double* d_pc_aux = nullptr; double* h_pc = nullptr; double* h_pc_dev = nullptr; double pc_seq = 0.0; long pc_iterations = 0; double pc_err_sum = 0.0; long pc_zero_b_slices = 0;
     double pc_tol = 4e-2, pc_mix = 0.05; int pc_max_iter = 30;
     int c_aabs = -1; double* d_laser_sum = nullptr;       // laser: slab component of |a|^2, device sum of |a| (diagnostics)
@@ -309,6 +311,7 @@ struct Engine {
     void insitu_beam (int islice);
     double* d_insitu_pl = nullptr; double insitu_pl_radius = 0.0;     // [15][nz] raw sums of the plasma moments
     double* d_insitu = nullptr;      // [10][nz] in-situ field reductions (Fields::InSituComputeDiags)
+    void insitu_plasma (int islice); void insitu_fields (int islice); void checksum_slice ();      // diagnostics.hip: no-ops unless switched on
 
     ~Engine ();
     int create (const hps_deck& deck, int device);
@@ -398,6 +401,10 @@ template <class F> int Engine::fill_selected_species (const char* fn, F&& set)
 int ion_create (Engine& E);                                                  // ionization.hip
 void ion_destroy (Engine& E);
 unsigned event_flags (bool timing);                                           // engine.hip
+hipError_t create_engine_stream (hipStream_t* s, int device, bool* pooled);   // stream_pool.hip: from the device's pool where there is one
+void return_engine_stream (hipStream_t st, int device);                       // ...: a pooled stream back to it
+__global__ __launch_bounds__(256) void k_beam_new_step (int* nsub, long n);   // beam_host.hip (begin_step launches it)
+void beam_deposit_pair (const hps_slab& slab, const BeamPairWork& bw, const hps_geom& gm, int order, hipStream_t st);      // ...: k_beam_deposit_pair
 // The 11 double arrays of a sheet in the order of its block, and what is built on it (engine.hip): a block of cap slots with
 // idcpu and ion_lev (alias: x_prev, y_prev are x, y -- Species::alias_prev) and its release
 std::array<double**, 11> soa_arrays (hps_plasma& p);

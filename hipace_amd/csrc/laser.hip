@@ -927,6 +927,36 @@ int laser_copy_chi (Engine& E, double* out_host)
     return HPS_OK;
 }
 
+// MultiLaser::MakeLaserGeometry (laser/MultiLaser.cpp:58-115): the field grid and box unless given; zeta snapped to whole field
+// cells, so that laser slice k sits at the z of field slice k
+int Engine::set_laser_grid (const int* n_cell, const double* patch_lo, const double* patch_hi, int interp_order)
+{
+    HPS_REQUIRE(laser, "hps_engine_set_laser_grid: the deck has no laser (laser_on)");
+    HPS_REQUIRE(!step_begun, "hps_engine_set_laser_grid: must be called before the first hps_engine_begin_step");
+    HPS_REQUIRE(interp_order >= 0 && interp_order <= 3, "hps_engine_set_laser_grid: lasers.interp_order must be 0, 1, 2 or 3");
+    LaserGrid G;
+    G.set = true; G.order = interp_order;
+    G.nx = n_cell ? n_cell[0] : d.nx; G.ny = n_cell ? n_cell[1] : d.ny;
+    for (int q = 0; q < 3; ++q) { G.lo[q] = patch_lo ? patch_lo[q] : d.lo[q]; G.hi[q] = patch_hi ? patch_hi[q] : d.hi[q]; }
+    HPS_REQUIRE(G.nx >= 1 && G.ny >= 1, "hps_engine_set_laser_grid: lasers.n_cell must be positive");
+    for (int q = 0; q < 3; ++q) HPS_REQUIRE(std::isfinite(G.lo[q]) && std::isfinite(G.hi[q]), "hps_engine_set_laser_grid: lasers.patch_lo / patch_hi must be finite");
+    const double poff_z = 0.5*(d.lo[2] + d.hi[2] - gm.dz*(d.nz - 1)), dz_inv = 1.0/gm.dz;
+    const double zl = std::max(0.0, std::round((G.lo[2] - poff_z)*dz_inv)), zh = std::min((double)(d.nz - 1), std::round((G.hi[2] - poff_z)*dz_inv));
+    HPS_REQUIRE(zl <= zh, "hps_engine_set_laser_grid: the laser patch holds no field slice (empty zeta range)");
+    G.zlo = (int)zl; G.zhi = (int)zh;
+    G.lo[2] = (G.zlo - 0.5)*gm.dz + poff_z; G.hi[2] = (G.zhi + 0.5)*gm.dz + poff_z;
+    HPS_REQUIRE(G.hi[0] > G.lo[0] && G.hi[1] > G.lo[1] && G.hi[2] > G.lo[2], "hps_engine_set_laser_grid: Laser box must have positive volume");
+    G.dx = (G.hi[0] - G.lo[0])/G.nx; G.dy = (G.hi[1] - G.lo[1])/G.ny;
+    G.xoff = 0.5*(G.lo[0] + G.hi[0] - G.dx*(G.nx - 1));
+    G.yoff = 0.5*(G.lo[1] + G.hi[1] - G.dy*(G.ny - 1));
+    if (d.laser_solver == 2 && d.dt != 0.0 && (G.nx % 2 || G.ny % 2)) {
+        set_error("hps_engine_set_laser_grid: the multigrid envelope solver needs even lasers.n_cell (cell-centred hpmg box)"); return HPS_ERR_UNSUPPORTED; }
+    HPS_HIP_CHECK(hipStreamSynchronize(st));
+    laser_destroy(*this);
+    lgrid = G;
+    return laser_create(*this);
+}
+
 } // namespace hps
 
 // The two grid-to-grid interpolations of the laser grid as operators of their own (the engine's kernels and launch code).
@@ -952,4 +982,142 @@ extern "C" int hps_laser_interp_chi (hps_slab slab, int c_chi, const double* chi
     HPS_REQUIRE(order >= 0 && order <= 3 && shrink >= 0, "hps_laser_interp_chi: lasers.interp_order must be 0, 1, 2 or 3 and shrink must not be negative");
     return launch_interp_chi(SlabView(slab), c_chi, chi_initial, chi_out, nxl, nyl, dxl, dyl, xoffl, yoffl, geom, shrink, order,
                              static_cast<hipStream_t>(stream));
+}
+
+// ---- the engine's laser entry points: arguments checked, then the laser_* functions above --------------------------------------
+using namespace hps;
+
+extern "C" int hps_engine_set_laser_import (void* h, int on, int step)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E->laser, "hps_engine_set_laser_import: no laser");
+    return laser_set_import(*E, on, step);
+}
+extern "C" int hps_engine_export_laser_slice (void* h, int islice, double* msg_dev)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E->laser && msg_dev && islice >= 0 && islice < E->d.nz, "hps_engine_export_laser_slice: bad argument");
+    return laser_export_slice(*E, islice, msg_dev);
+}
+extern "C" int hps_engine_import_laser_slice (void* h, int islice, const double* msg_dev)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E->laser && msg_dev && islice >= 0 && islice < E->d.nz, "hps_engine_import_laser_slice: bad argument");
+    return laser_import_slice(*E, islice, msg_dev);
+}
+extern "C" int hps_engine_import_laser_from (void* h, int islice, void* src)
+{
+    Engine* E = static_cast<Engine*>(h); Engine* S = static_cast<Engine*>(src);
+    HPS_REQUIRE(E->laser && S && S->laser && islice >= 0 && islice < E->d.nz && S->d.nx == E->d.nx && S->d.ny == E->d.ny && S->d.nz == E->d.nz,
+                "hps_engine_import_laser_from: bad argument");
+    {   const Engine::LaserGrid &a = E->lgrid, &b = S->lgrid;
+        HPS_REQUIRE(a.set == b.set && (!a.set || (a.nx == b.nx && a.ny == b.ny && a.zlo == b.zlo && a.zhi == b.zhi)),
+                    "hps_engine_import_laser_from: the two engines' laser grids differ"); }
+    return laser_import_from(*E, islice, *S);
+}
+extern "C" int hps_engine_laser_envelope (void* h, double* out_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E->laser && out_host, "hps_engine_laser_envelope: no laser");
+    return laser_copy_envelope(*E, out_host);
+}
+extern "C" int hps_engine_set_laser_grid (void* h, const int* n_cell, const double* patch_lo, const double* patch_hi, int interp_order)
+{
+    HPS_REQUIRE(h, "hps_engine_set_laser_grid: null handle");
+    return static_cast<Engine*>(h)->set_laser_grid(n_cell, patch_lo, patch_hi, interp_order);
+}
+extern "C" int hps_engine_laser_grid (void* h, int* nxl, int* nyl, int* zeta_lo, int* zeta_hi)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_laser_grid: no laser");
+    int nx = 0, ny = 0, nz = 0;
+    laser_sizes(*E, &nx, &ny, &nz);
+    if (nxl) *nxl = nx;
+    if (nyl) *nyl = ny;
+    if (zeta_lo) *zeta_lo = E->lgrid.set ? E->lgrid.zlo : 0;
+    if (zeta_hi) *zeta_hi = E->lgrid.set ? E->lgrid.zhi : E->d.nz - 1;
+    return HPS_OK;
+}
+// several Gaussian pulses, envelopes from samples, in-situ reductions
+extern "C" int hps_engine_set_laser_pulses (void* h, int n, const hps_laser_pulse* pulses)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_set_laser_pulses: the deck has no laser (laser_on)");
+    HPS_REQUIRE(!E->step_begun, "hps_engine_set_laser_pulses: must be called before the first hps_engine_begin_step");
+    HPS_REQUIRE(n >= 0 && n <= 8, "hps_engine_set_laser_pulses: 0 to 8 pulses");
+    HPS_REQUIRE(n == 0 || pulses, "hps_engine_set_laser_pulses: null pulse list");
+    for (int q = 0; q < n; ++q) {
+        const hps_laser_pulse& P = pulses[q];
+        HPS_REQUIRE(P.w0 > 0.0 && P.L0 > 0.0, "hps_engine_set_laser_pulses: w0 and L0 must be positive");
+        const double v[10] = {P.a0, P.w0, P.L0, P.pos[0], P.pos[1], P.pos[2], P.zfoc, P.cep, P.propagation_angle_yz, P.pft_yz};
+        for (double x : v) HPS_REQUIRE(std::isfinite(x), "hps_engine_set_laser_pulses: the pulse parameters must be finite");
+    }
+    E->laser_pulses.assign(pulses, pulses + n);
+    E->laser_pulses_set = true;
+    return HPS_OK;
+}
+extern "C" int hps_engine_add_laser_samples (void* h, int geometry, const double* data_host, const long extent[3], const double offset[3],
+                                             const double spacing[3], double unit)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_add_laser_samples: the deck has no laser (laser_on)");
+    HPS_REQUIRE(!E->step_begun, "hps_engine_add_laser_samples: must be called before the first hps_engine_begin_step");
+    HPS_REQUIRE(geometry >= 0 && geometry <= 3, "hps_engine_add_laser_samples: geometry must be 0 (laser grid), 1 (xyt), 2 (xyz) or 3 (rt)");
+    HPS_REQUIRE(extent && offset && spacing, "hps_engine_add_laser_samples: null argument");
+    HPS_REQUIRE(E->laser_samples.size() < 4, "hps_engine_add_laser_samples: at most 4 sets of samples");
+    HPS_REQUIRE(std::isfinite(unit), "hps_engine_add_laser_samples: unit must be finite");
+    Engine::LaserSamples S;
+    S.geometry = geometry; S.unit = unit;
+    for (int q = 0; q < 3; ++q) {
+        HPS_REQUIRE(extent[q] > 0 && extent[q] < (1L << 30), "hps_engine_add_laser_samples: the extents must be positive");
+        S.extent[q] = extent[q]; S.offset[q] = offset[q]; S.spacing[q] = spacing[q];
+    }
+    // each extent is below 2^30, so the product of two fits a long; the product of all three is held below 2^31
+    HPS_REQUIRE(extent[0]*extent[1] <= ((1L << 31) - 1)/extent[2], "hps_engine_add_laser_samples: more than 2^31 - 1 samples in a set");
+    HPS_REQUIRE(data_host, "hps_engine_add_laser_samples: null argument");
+    if (int e = laser_check_samples(*E, S)) return e;
+    const size_t n = (size_t)extent[0]*extent[1]*extent[2];
+    // no host memory for the copy is no fault of the arguments: the code of a failed device allocation
+    try { S.data.assign(data_host, data_host + 2*n); E->laser_samples.push_back(std::move(S)); }
+    catch (const std::exception&) { set_error("hps_engine_add_laser_samples: no host memory for the copy of the samples"); return HPS_ERR_HIP; }
+    return HPS_OK;
+}
+extern "C" int hps_engine_set_insitu_laser (void* h, int on)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser, "hps_engine_set_insitu_laser: the deck has no laser (laser_on)");
+    if ((on != 0) == E->insitu_laser) return HPS_OK;      // on -> on keeps the rows collected so far
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    if (int e = laser_set_insitu(*E, on)) return e;       // (a failed allocation leaves it off)
+    E->insitu_laser = (on != 0);
+    return HPS_OK;
+}
+extern "C" int hps_engine_insitu_laser (void* h, double* out)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser && E->insitu_laser && out, "hps_engine_insitu_laser: not switched on");
+    return laser_copy_insitu(*E, out);
+}
+extern "C" int hps_engine_laser_chi (void* h, double* out_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(E && E->laser && out_host, "hps_engine_laser_chi: no laser");
+    return laser_copy_chi(*E, out_host);
+}
+extern "C" int hps_engine_laser_info (void* h, int* aabs_comp, double* sum_host)
+{
+    Engine* E = static_cast<Engine*>(h);
+    if (aabs_comp) *aabs_comp = E->c_aabs;
+    if (sum_host) {
+        HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+        HPS_HIP_CHECK(hipMemcpy(sum_host, E->d_laser_sum, sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return HPS_OK;
+}
+extern "C" int hps_engine_laser_vcycles (void* h, long* vcycles)
+{
+    Engine* E = static_cast<Engine*>(h);
+    HPS_REQUIRE(vcycles, "hps_engine_laser_vcycles: null argument");
+    *vcycles = E->laser ? laser_mg_vcycles(*E) : 0;
+    return HPS_OK;
 }

@@ -16,6 +16,7 @@
 #include "tiling.h"
 #include "mg_gate.h"
 #include "beam_deposit.h"
+#include "particles_tiled.h"
 
 #include <algorithm>
 #include <atomic>
@@ -154,7 +155,7 @@ void k_deposit_tiled (SlabView f, hps_plasma pl, const int* __restrict__ offsets
                       PartConsts k, int* n_qsa, int* n_fallback, const int* __restrict__ tile_flag, TailWork tw, BeamPairWork bw,
                       const int* go)
 {
-    // an iteration of the predictor-corrector loop enqueued past the loop's end (engine.hip: pc_enqueue_iteration)
+    // an iteration of the predictor-corrector loop enqueued past the loop's end (predcorr.hip: pc_enqueue_iteration)
     if (go && *go == 0) return;
     // the first bw.nwg workgroups: the static beam's deposits of this slice (beam_deposit.h) -- a 7.9 us launch of a few
     // thousand particles that nothing ahead of the Sx/Sy initialisation waits for, off the slice's chain of launches.  (At the

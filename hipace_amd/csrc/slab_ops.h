@@ -63,5 +63,22 @@ __device__ __forceinline__ void shift_init_cell (const ShiftInit& a, long s)
     if (a.next.rho >= 0) p[a.next.rho*ns + s] = ion;
 }
 
+// ---- slab kernels of engine.hip that the predictor-corrector (predcorr.hip) and SALAME (salame.hip) schedules launch too.
+// Each is defined once, in engine.hip; a caller in another file calls the kernel's host stub there.
+struct CompList { int n; int c[12]; };
+
+// k_zero_comps / k_copy_comps over the whole padded planes of `slab` on `st`
+void zero_comps (const hps_slab& slab, hipStream_t st, CompList full, CompList boxed, CellBox bb, CompList from_ion = CompList{0, {}}, int c_ion = -1);
+void copy_comps (const hps_slab& slab, hipStream_t st, CompList dst, CompList src);
+
+__global__ __launch_bounds__(256)
+void k_rhs_all (SlabView f, int c_rhomjz, int c_ion, int c_rho, int c_jx, int c_jy, double inv_ep0,
+                double fez_x, double fez_y, double fbz_y, double fbz_x, double* staging, long plane);
+__global__ __launch_bounds__(256)
+void k_grad_psi (SlabView f, int cPsi, int cExmBy, int cEypBx, double hdx_inv, double hdy_inv);
+__global__ __launch_bounds__(256)
+void k_sxsy_beam (SlabView f, int cSx, int cSy, int cJzb, int cNx, int cNy, int cPx, int cPy,
+                  double mu0, double dx2, double dy2, double dz2, CellBox bb, int cBackX = -1, int cBackY = -1);
+
 } // namespace hps
 #endif

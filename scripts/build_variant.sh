@@ -9,7 +9,7 @@ extra=""
 [ "$src" = particles_tiled.hip ] && extra="-mllvm -disable-lsr"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -w $extra $flags -c $src -o ${src%.hip}.$name.vo
 objs=""
-for s in particles.hip particles_tiled.hip sort.hip poisson.hip multigrid.hip multigrid2.hip engine.hip beam.hip laser.hip ring.hip ionization.hip; do
+for s in $(sed -n "s/^SRCS = //p" Makefile); do
   if [ "$s" = "$src" ]; then objs="$objs ${s%.hip}.$name.vo"; else objs="$objs ${s%.hip}.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o libhpslice_$name.so $objs -L/opt/rocm/lib -lrocfft -ldl -Wl,-rpath,/opt/rocm/lib

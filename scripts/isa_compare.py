@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""isa_compare.py <old.o> <new.o> <name-part> [<name-part> ...]: are the gfx950 kernels whose mangled names contain one of
-the parts the same in two HIP objects?  Compares each kernel's instructions (addresses and branch targets stripped) and its
+"""isa_compare.py <old.o>[,<old2.o>...] <new.o>[,<new2.o>...] <name-part> [<name-part> ...]: are the gfx950 kernels whose
+mangled names contain one of the parts the same in two HIP objects?  Either side may be a comma-separated list of objects,
+whose kernels are merged by mangled name (a kernel that has moved to another file is found wherever it lives now).
+Compares each kernel's instructions (addresses, branch targets and the fill behind the last instruction stripped) and its
 metadata note (registers, LDS, scratch), lists the kernels only one object has, and prints registers / LDS / scratch of
 every kernel it looked at.  Exit status 1 if a kernel that both objects have differs."""
 import os
@@ -36,6 +38,11 @@ def kernels(dis, parts):
             text = re.sub(r"//.*$", "", text)                              # objdump's address comments
             text = re.sub(r"<[^>]+>", "<L>", text)                         # branch targets by symbol + offset
             out[name].append(re.sub(r"\s+", " ", text).strip())
+    # what follows a kernel's last instruction up to the next symbol is the assembler's alignment fill, or the padding behind the
+    # last kernel of the section: it depends on the kernel's neighbours in the file, not on the kernel
+    for body in out.values():
+        while body and body[-1] in ("s_nop 0", "s_code_end", "..."):
+            body.pop()
     return out
 
 
@@ -55,10 +62,14 @@ def metadata(notes, parts):
 
 
 def main():
-    old, new, parts = sys.argv[1], sys.argv[2], sys.argv[3:]
+    old, new, parts = sys.argv[1].split(","), sys.argv[2].split(","), sys.argv[3:]
+    (k0, m0), (k1, m1) = ({}, {}), ({}, {})
     with tempfile.TemporaryDirectory() as tmp:
-        (d0, n0), (d1, n1) = device_code(old, tmp, "old"), device_code(new, tmp, "new")
-    k0, k1, m0, m1 = kernels(d0, parts), kernels(d1, parts), metadata(n0, parts), metadata(n1, parts)
+        for objs, tag, k, m in ((old, "old", k0, m0), (new, "new", k1, m1)):
+            for q, obj in enumerate(objs):
+                dis, notes = device_code(obj, tmp, f"{tag}{q}")
+                k.update(kernels(dis, parts))
+                m.update(metadata(notes, parts))
     bad = 0
     for name in sorted(set(k0) | set(k1)):
         m = m1.get(name) or m0.get(name) or {}

@@ -1,5 +1,5 @@
 """boundary.field = Open restated in numpy (Fields::SetBoundaryCondition + SetDirichletBoundaries, fields/Fields.cpp:617-741):
-what k_multipole_moments + k_open_boundary_apply (hipace_amd/csrc/engine.hip) do to a batch of source planes.
+what k_multipole_moments + k_open_boundary_apply (hipace_amd/csrc/open_boundary.hip) do to a batch of source planes.
 
     expansion   the operation itself -- moments to order 18, their potential one cell outside each wall -- in float64 or longdouble
     direct      what the operation approximates: the free-space potential summed source cell by source cell, no multipoles

@@ -1,5 +1,5 @@
 """boundary.field = Open on the GPU, off the 64 x 64 centred box: k_multipole_moments + k_open_boundary_apply through
-hps_open_boundary (the engine's own launches, hipace_amd/csrc/engine.hip) against the numpy restatement in longdouble and against
+hps_open_boundary (the engine's own launches, hipace_amd/csrc/open_boundary.hip) against the numpy restatement in longdouble and against
 the free-space potential itself (tests/open_boundary_reference.py), and the engine on an off-centre rectangular box against the
 oracle.
 
@@ -63,7 +63,7 @@ COMPACT = [(nx, ny, box) for nx, ny in SHAPES for box in BOXES] + [(24, 20, box)
 
 
 def test_shapes_reach_what_they_are_named_for():
-    src = open(os.path.join(os.path.dirname(__file__), "..", "hipace_amd", "csrc", "engine.hip")).read()
+    src = open(os.path.join(os.path.dirname(__file__), "..", "hipace_amd", "csrc", "open_boundary.hip")).read()
     order, parts = map(int, re.search(r"constexpr int OPEN_ORDER = (\d+), OPEN_PARTS = (\d+);", src).groups())
     assert order == R.ORDER
     assert "hipLaunchKernelGGL(k_multipole_moments, dim3(OPEN_PARTS, nbatch), dim3(256)" in src
