@@ -15,35 +15,15 @@
 #include "beam_deposit.h"
 #include "slab_ops.h"
 #include "particles_tiled.h"
+#include "multigrid.h"
 
-void mg_rider (void* mg_handle, int** dev_words, const int** host_words);     // multigrid.hip
 namespace hps {
 
 constexpr int PC_MAX_SPEC = 64;      // flags / host slots of the device-controlled predictor-corrector loop: iterations 1 .. 62
 
-// hps_mg_solve1 in two halves (multigrid.hip): kernels enqueued between them are gated on mg_gate_after_enqueued
-int mg_solve1_begin (void* mg_handle, hps_slab s, int sol_comp, int rhs_comp, int acf_comp, double tol_rel, double tol_abs,
-                     int max_iters, hipStream_t st);
-void mg_solve1_forget_hierarchy (void* mg_handle);
 bool poisson_gateable (void* poisson_handle);
 void poisson_set_gate (void* poisson_handle, const int* gate);
 bool ring_is_ticket (const void* p);      // ring.hip: is p the receive handle of an ipc ring edge (not a hipEvent_t)?
-int mg_solve1_prepare (void* mg_handle, hps_slab s, int sol_comp, int rhs_comp, int acf_comp, int max_iters, hipStream_t st);
-// ... in one launch with the -grad Psi / Sx, Sy pass of the slab (multigrid.hip: k_hierarchy_gradpsi); *done = false if this grid's
-// hierarchy needs more than that launch (then nothing has been enqueued)
-int mg_solve1_prepare_with (void* mg_handle, hps_slab s, int sol_comp, int rhs_comp, int acf_comp, int max_iters, SlabView f, GradPsiSxSy ga,
-                            hipStream_t st, bool* done);
-// the slab's shift / zero pass for the next slice as guest workgroups of the next mg_solve1_begin's first lower V; false: this
-// grid's lower V takes no guests (nothing will be done)
-bool mg_ride_shift_init (void* mg_handle, const ShiftInit& pass);
-const int* mg_gate_after_enqueued (void* mg_handle);
-void mg_defer_post (void* mg_handle);
-bool mg_take_deferred_post (void* mg_handle, MgPost* out);
-bool mg_solve1_ready (void* mg_handle);
-int mg_solve1_finish (void* mg_handle, int* iters_out, double* resnorm_out, int* extra, hipStream_t st);
-}
-
-namespace hps {
 
 struct LaserState;      // laser.hip
 

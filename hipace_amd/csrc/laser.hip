@@ -17,6 +17,7 @@
 #include "common.h"
 #include "engine.h"
 #include "expr.h"
+#include "multigrid.h"
 
 #include <rocfft/rocfft.h>
 #include <algorithm>
@@ -25,11 +26,6 @@
 namespace hps {
 
 struct LaserPhase { double2 exp1, exp2; double djn, pad; };
-
-int mg2_create_internal (int nx, int ny, double dx, double dy, void** h);       // multigrid2.hip
-int mg2_solve_internal (void* h, double* sol, const double* rhs, const double* ar, const double* ai, double tol_rel, double tol_abs,
-                        int maxiter, int* iters, hipStream_t st);
-void mg2_destroy_internal (void* h);
 
 struct LaserState {
     int nx = 0, ny = 0, nz = 0;                                    // cells of the laser grid (the field grid's unless a grid is set)

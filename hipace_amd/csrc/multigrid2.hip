@@ -13,8 +13,10 @@
 // __syncthreads, arrays in L2); larger levels use an LDS-tiled kernel that does the four sweeps, the residual and (up-leg)
 // the prolongation in one pass.  The planes are planar [2][ny][nx] without guard cells.
 #include "common.h"
+#include "multigrid.h"
 
 #include <vector>
+#include <memory>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -396,7 +398,7 @@ static bool smooth4 (const Lev2& l, int src_mode, const double* fin, const doubl
 
 static int mg2_create (int nx, int ny, double dx, double dy, Multigrid2** out)
 {
-    Multigrid2* M = new Multigrid2;
+    std::unique_ptr<Multigrid2> M(new Multigrid2);      // (a failure below frees what has been allocated: ~Multigrid2)
     M->nx = nx; M->ny = ny; M->dx = dx; M->dy = dy;
     int lx = nx, ly = ny;
     for (int il = 0; il < 31; ++il) {           // level build (:1043-1072), cell-centred
@@ -406,12 +408,13 @@ static int mg2_create (int nx, int ny, double dx, double dy, Multigrid2** out)
         if (!ok) break;
         lx /= 2; ly /= 2;
     }
-    if (M->L.size() < 2) { delete M; set_error("hps_mg2_create: grid too small to coarsen"); return HPS_ERR_ARG; }
-    for (const Lev2& l : M->L) {
-        double* p[4];
-        for (int k = 0; k < 4; ++k) { HPS_HIP_CHECK(hipMalloc(&p[k], (size_t)2*l.n*sizeof(double))); HPS_HIP_CHECK(hipMemset(p[k], 0, (size_t)2*l.n*sizeof(double))); }
-        M->acf.push_back(p[0]); M->res.push_back(p[1]); M->cor.push_back(p[2]); M->rescor.push_back(p[3]);
-    }
+    if (M->L.size() < 2) { set_error("hps_mg2_create: grid too small to coarsen"); return HPS_ERR_ARG; }
+    for (const Lev2& l : M->L)
+        for (std::vector<double*>* v : {&M->acf, &M->res, &M->cor, &M->rescor}) {
+            v->push_back(nullptr);
+            HPS_HIP_CHECK(hipMalloc(&v->back(), (size_t)2*l.n*sizeof(double)));
+            HPS_HIP_CHECK(hipMemset(v->back(), 0, (size_t)2*l.n*sizeof(double)));
+        }
     HPS_HIP_CHECK(hipMalloc(&M->d_norm, 2*MG2_NSUB*sizeof(unsigned long long)));
     HPS_HIP_CHECK(hipHostMalloc(&M->h_post, 4*sizeof(unsigned long long), hipHostMallocMapped));
     HPS_HIP_CHECK(hipHostGetDevicePointer((void**)&M->h_post_dev, M->h_post, 0));
@@ -431,7 +434,7 @@ static int mg2_create (int nx, int ny, double dx, double dy, Multigrid2** out)
             HPS_HIP_CHECK(hipMemcpy(M->d_low_acf, ptrs.data(), ptrs.size()*sizeof(double*), hipMemcpyHostToDevice));
         }
     }
-    *out = M;
+    *out = M.release();
     return HPS_OK;
 }
 

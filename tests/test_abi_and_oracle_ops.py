@@ -177,12 +177,14 @@ def test_numpy_helmholtz1_matches_the_oracle_multigrid(oracle, nx, ny, dx, dy):
 
 
 def test_multigrid_dispatch_lists_mirror_the_source():
-    """LOWV / TILES / the thresholds of tests/test_multigrid_dispatch_gpu.py are what multigrid.hip and multigrid2.hip launch and
+    """LOWV / TILES / the thresholds of tests/test_multigrid_dispatch_gpu.py are what multigrid.hip (with its kernels' mg_*.h) and multigrid2.hip launch and
     decide by, and what the C ABI and api.py name: a kernel or threshold changed there without the tests fails here (the GPU
     module's completeness test checks that the grids reach every entry)."""
     from hipace_amd import api as A
     from tests import test_multigrid_dispatch_gpu as T
-    src = open(os.path.join(ROOT, "hipace_amd", "csrc", "multigrid.hip")).read()
+    csrc = os.path.join(ROOT, "hipace_amd", "csrc")
+    families = ("mg_stencil.h", "mg_smooth.h", "mg_up_fused.h", "mg_lower_v.h", "mg_lower_v3.h", "mg_pyramid.h")
+    src = "\n".join(open(os.path.join(csrc, f)).read() for f in ("multigrid.hip",) + families)      # the host side and its kernels
     src2 = open(os.path.join(ROOT, "hipace_amd", "csrc", "multigrid2.hip")).read()
     hdr = open(os.path.join(ROOT, "include", "hpslice.h")).read()
     def const(text, name):
@@ -198,8 +200,14 @@ def test_multigrid_dispatch_lists_mirror_the_source():
     assert launched == {"k_bottom_sweep<CC>", "k_lower_v3", "k_lower_v<CC>"}, launched
     assert len(T.LOWV) == 4 and A.MultiGrid.LOWV == T.LOWV
     assert re.findall(r"HPS_MG_LOWV_(\w+) = (\d)", hdr) == [("V3", "0"), ("CC", "1"), ("NODAL", "2"), ("BOTTOM", "3")]
-    # the smoother tiles of the down-leg: launch_smooth's two, the pulling TileSmall / TileMid of node-centred levels
+    # the smoother tiles of the down-leg: launch_smooth's two, the pulling TileSmall / TileMid of node-centred levels; vcycle
+    # picks among the four by the HPS_MG_TILE_* that mg_create decided and hps_mg_info reports
+    down = dict(re.findall(r"case HPS_MG_TILE_(\w+):\s+(?:if constexpr \(!CC\)\s+)?launch_smooth_ts<(Tile\w+, CC, SRC_ZERO, true(?:, 4, true)?)>", vc))
+    assert down == {"SMALL": "TileSmall, CC, SRC_ZERO, true", "BIG": "TileBig, CC, SRC_ZERO, true",
+                    "SMALL_PULL": "TileSmall, CC, SRC_ZERO, true, 4, true", "MID_PULL": "TileMid, CC, SRC_ZERO, true, 4, true"}, down
+    assert re.findall(r"HPS_MG_TILE_(\w+) = (\d)", hdr) == [("SMALL", "0"), ("BIG", "1"), ("SMALL_PULL", "2"), ("MID_PULL", "3")]
     assert set(re.findall(r"launch_smooth_ts<(Tile\w+), CC, SRC_ZERO, true, 4, true>", vc)) == {"TileSmall", "TileMid"}
+    assert set(re.findall(r"launch_smooth_ts<(Tile\w+), CC, SRC_ZERO, true>", vc)) == {"TileSmall", "TileBig"}
     ls = re.search(r"static void launch_smooth \(.*?\n\}", src, re.S).group(0)
     assert set(re.findall(r"launch_smooth_ts<(Tile\w+)", ls)) == {"TileSmall", "TileBig"}
     assert A.MultiGrid.TILES == T.TILES == ("TileSmall", "TileBig", "TileSmall-pull", "TileMid-pull")
