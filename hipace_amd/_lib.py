@@ -79,6 +79,11 @@ class BeamSpecies(C.Structure):         # hps_beam_species
                 ("uz_mean", C.c_double), ("uz_std", C.c_double), ("do_salame", C.c_int)]
 
 
+class PlasmaSpecies(C.Structure):       # hps_plasma_species
+    _fields_ = [("charge", C.c_double), ("mass", C.c_double), ("density", C.c_double), ("ppc", C.c_int * 2),
+                ("fine_ppc", C.c_int * 2), ("neutralize_background", C.c_int)]
+
+
 class Deck(C.Structure):
     _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int),
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3),
@@ -332,6 +337,11 @@ _SIGS = {
     "hps_engine_beam_tags": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hps_engine_beam_moments_species": (C.c_int, [C.c_void_p, C.c_void_p]),
     "hps_engine_beam_kernels": (C.c_int, [C.c_void_p, C.c_char_p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    "hps_engine_add_plasma_species": (C.c_int, [C.c_void_p, C.POINTER(PlasmaSpecies), C.POINTER(C.c_int)]),
+    "hps_engine_plasma_species_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_long)]),
+    "hps_engine_plasma_species": (Plasma, [C.c_void_p, C.c_int]),
+    "hps_engine_insitu_plasma_species": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "hps_adaptive_add_species": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "hps_adaptive_initial_dt_beams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.POINTER(C.c_double)]),
     "hps_adaptive_after_step_beams": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,

@@ -513,8 +513,9 @@ class AdaptiveTimeStep:
     """hipace.dt = adaptive: the reference's controller (utils/AdaptiveTimeStep.cpp) over hps_adaptive_* -- host code, no
     device.  One per rank / pipeline stage, all initialised alike."""
 
-    def __init__(self, deck, density_profile=None, density_exprs=None, beams=None):
-        """density_exprs: {species: (text_or_table, constants)} of parsed densities; default: the deck's own
+    def __init__(self, deck, density_profile=None, density_exprs=None, beams=None, plasma_species=None):
+        """plasma_species: the further plasma species as decks.plasma_species gives them (default: the deck's own entry), each
+        one more species of rho_max(z) (hps_adaptive_add_species).  density_exprs: {species: (text_or_table, constants)} of parsed densities; default: the deck's own
         (decks.DENSITY_EXPR_DEFAULT), as SliceEngine applies them.  beams: [dict(charge, mass, uz_mean, uz_std)], one per beam
         species (default: the deck's entry beam_species behind the deck's own beam); with more than one the controller runs per
         beam (hps_adaptive_*_beams): CalculateFromMinUz takes the moments [n][4] of SliceEngine.beam_moments(species=all)"""
@@ -528,8 +529,15 @@ class AdaptiveTimeStep:
         check(_lib.lib().hps_adaptive_create(C.byref(self._dk), C.byref(self._h)))
         if density_profile is not None:
             self.set_density_profile(*density_profile)
-        if density_exprs is None:
+        more_sp = _decks.plasma_species(deck) if plasma_species is None else list(plasma_species)
+        self.plasma_species_names = list(_decks.PLASMA_SPECIES_NAMES)
+        own = density_exprs is None
+        if own:
             density_exprs = {sp: spec[:2] for sp, spec in _decks.density_exprs(deck).items()}
+        for spec in more_sp:
+            k = self.add_species(spec["record"]["charge"], spec["record"]["density"], spec.get("name"))
+            if own and spec.get("density") is not None:
+                density_exprs[k] = spec["density"][:2]
         for sp, spec in density_exprs.items():
             self.set_density_expr(sp, *spec)
 
@@ -540,7 +548,15 @@ class AdaptiveTimeStep:
                  for sp, (progs, pos, _) in getattr(engine, "density_exprs", {}).items()}
         names, _ = engine.beam_species()
         beams = [r for r in engine.beam_species_records] if len(names) > 1 else None
-        return cls(engine.deck, getattr(engine, "density_profile", None), exprs, beams)
+        return cls(engine.deck, getattr(engine, "density_profile", None), exprs, beams, getattr(engine, "plasma_species_specs", []))
+
+    def add_species(self, charge, density, name=None):
+        """one more plasma species for rho_max(z) (hps_adaptive_add_species) -> its index (2, 3, ...)"""
+        k = _lib.lib().hps_adaptive_add_species(self._h, float(charge), float(density))
+        if k < 0:
+            raise _lib.HpsError(f"hps_adaptive_add_species: {_lib.lib().hps_last_error().decode()}")
+        self.plasma_species_names.append(name or f"species{k}")
+        return k
 
     def _beam_arrays(self):
         q = np.array([b["charge"] for b in self.beams], dtype=np.float64)
@@ -549,7 +565,7 @@ class AdaptiveTimeStep:
 
     def set_density_expr(self, species, text_or_table, constants=None):
         """the species' parsed density (SliceEngine.set_density_expr): rho_max(z) takes |charge * density(0, 0, z)|"""
-        sp = {"plasma": 0, "ion": 1}.get(species, species)
+        sp = _decks.plasma_species_index(self.plasma_species_names, species) if isinstance(species, str) else int(species)
         progs, pos = _expr.compile_density(text_or_table, constants)
         arr, keep = _expr.c_programs(progs)
         z = (C.c_double * len(pos))(*pos) if pos is not None else None
@@ -654,8 +670,14 @@ class SliceEngine:
         self.beam_species_records = [dict(charge=deck.get("beam_charge", -1.0), mass=deck.get("beam_mass", 1.0),
                                           uz_mean=deck["beam_umean"][2] if "beam_umean" in deck else 0.0,
                                           uz_std=deck.get("beam_uz_std", 0.0))]
+        # the plasma species: 0 = "plasma", 1 = "ion"; the deck's entry plasma_species is appended here, ahead of the
+        # setters that take a species' index or name (a deck without the entry makes no call)
+        self.plasma_species_names = list(_decks.PLASMA_SPECIES_NAMES)
+        self.plasma_species_specs = []
         if tile_size is not None:
             check(_lib.lib().hps_engine_set_tiling(self._h, tile_size, sort_period or 128))
+        for spec in _decks.plasma_species(deck):
+            self._add_plasma_species(spec)
         # not members of hps_deck: applied through the setters, fine_ppc ahead of the patch
         pf, jf = tuple(deck.get("plasma_fine_ppc", (0, 0))), tuple(deck.get("ion_fine_ppc", (0, 0)))
         hollow = float(deck.get("plasma_hollow_core_radius", 0.0))
@@ -769,12 +791,61 @@ class SliceEngine:
         self.nparticles = npart.value
 
     def set_plasma_momentum(self, species=0, u_mean=(0.0, 0.0, 0.0), u_std=(0.0, 0.0, 0.0), seed=0):
-        """<plasma>.u_mean / u_std of species 0 (plasma) / 1 (ion) in units of c and the seed of its momentum draws
+        """<plasma>.u_mean / u_std of species 0 (plasma) / 1 (ion) / a further species (index or name) in units of c and the seed of its momentum draws
         (hps_engine_set_plasma_momentum), before the first begin_step."""
-        check(_lib.lib().hps_engine_set_plasma_momentum(self._h, int(species), (C.c_double * 3)(*u_mean), (C.c_double * 3)(*u_std), int(seed)))
+        check(_lib.lib().hps_engine_set_plasma_momentum(self._h, self._plasma_index(species), (C.c_double * 3)(*u_mean), (C.c_double * 3)(*u_std), int(seed)))
+
+    # ---- further plasma species in one engine (DESIGN 8r) -------------------------------------------
+    def _plasma_index(self, species):
+        """a name -> its index (ValueError: unknown); a number passes as it is: the library refuses one it does not hold"""
+        return _decks.plasma_species_index(self.plasma_species_names, species) if isinstance(species, str) else int(species)
+
+    def _add_plasma_species(self, spec):
+        rec = _lib.fill_struct(_lib.PlasmaSpecies(), spec["record"])
+        k = C.c_int()
+        check(_lib.lib().hps_engine_add_plasma_species(self._h, C.byref(rec), C.byref(k)))
+        self.plasma_species_names.append(spec["name"] or f"species{k.value}")
+        self.plasma_species_specs.append(spec)
+        if any(spec["u_mean"]) or any(spec["u_std"]):
+            self.set_plasma_momentum(k.value, spec["u_mean"], spec["u_std"], spec["seed"])
+        if spec["density"] is not None:
+            self.set_density_expr(k.value, *spec["density"])
+        return k.value
+
+    def add_plasma_species(self, **spec):
+        """One more fixed-charge plasma species behind "plasma" (0) and "ion" (1) (hps_engine_add_plasma_species and the
+        per-species setters), before the first begin_step.  spec: decks.PLASMA_SPECIES_DEFAULT -- name, charge (default: the
+        opposite of the plasma's), mass, density, ppc, fine_ppc, neutralize_background, u_mean, u_std | temperature_in_ev, seed,
+        density_expr | density_table, density_constants, min_density.  -> the species' index"""
+        if spec.get("name") is not None and spec["name"] in self.plasma_species_names:
+            raise ValueError(f"add_plasma_species: a name is given twice ({spec['name']!r})")
+        return self._add_plasma_species(_decks.plasma_species_spec(self.deck, spec, "add_plasma_species"))
+
+    def plasma_species(self):
+        """-> (names, counts) of the engine's plasma species: "plasma", "ion" (count 0 in a deck without it), the further ones"""
+        n = C.c_int()
+        counts = (C.c_long * _decks.MAX_PLASMA_SPECIES)()
+        check(_lib.lib().hps_engine_plasma_species_info(self._h, C.byref(n), counts))
+        return list(self.plasma_species_names[:n.value]), [counts[k] for k in range(n.value)]
+
+    def plasma(self, species=0):
+        """The sheet of plasma species `species` (index or name): (real (11, n), valid (n,), ion_lev (n,), key (n,)) as ions()"""
+        self.sync()
+        p = _lib.lib().hps_engine_plasma_species(self._h, self._plasma_index(species))
+        n = p.n
+        real = np.empty((11, n), dtype=np.float64)
+        idc = np.empty(n, dtype=np.uint64)
+        lev = np.empty(n, dtype=np.int32)
+        if n:
+            for k, name in enumerate(PL_REAL):
+                check(_lib.lib().hps_memcpy_d2h(real[k].ctypes.data_as(C.c_void_p), C.c_void_p(getattr(p, name)), real[k].nbytes))
+            check(_lib.lib().hps_memcpy_d2h(idc.ctypes.data_as(C.c_void_p), C.c_void_p(p.idcpu), idc.nbytes))
+            check(_lib.lib().hps_memcpy_d2h(lev.ctypes.data_as(C.c_void_p), C.c_void_p(p.ion_lev), lev.nbytes))
+        key = ((idc >> np.uint64(24)) & np.uint64((1 << 39) - 1)).astype(np.int64) - 1
+        return real, ((idc >> np.uint64(63)) & np.uint64(1)).astype(np.int32), lev, key
 
     def set_plasma_symmetry(self, do_symmetrize=False, prevent_centered_particle=False):
-        """plasmas.do_symmetrize and prevent_centered_particle, one value for both species (hps_engine_set_plasma_symmetry),
+        """plasmas.do_symmetrize and prevent_centered_particle, one value for every species (hps_engine_set_plasma_symmetry),
         before the first begin_step; the particle count follows the four mirrored copies."""
         check(_lib.lib().hps_engine_set_plasma_symmetry(self._h, int(bool(do_symmetrize)), int(bool(prevent_centered_particle))))
         npart = C.c_long()
@@ -888,15 +959,15 @@ class SliceEngine:
         return out
 
     def add_collision(self, species_a=0, species_b=0, coulomb_log=-1.0, seed=0):
-        """hipace.collisions: one more Coulomb collision between species 0 (plasma) / 1 (ion), before the first begin_step
+        """hipace.collisions: one more Coulomb collision between species 0 (plasma) / 1 (ion) / further ones (indices or names), before the first begin_step
         (hps_engine_add_collision); coulomb_log <= 0 = computed per pair."""
-        check(_lib.lib().hps_engine_add_collision(self._h, species_a, species_b, coulomb_log, seed))
+        check(_lib.lib().hps_engine_add_collision(self._h, self._plasma_index(species_a), self._plasma_index(species_b), coulomb_log, seed))
 
     def add_beam_collision(self, plasma_species=0, coulomb_log=-1.0, seed=0):
         """hipace.collisions with <collision>.species = beam <plasma>: one more collision, between the moving beam and species
         0 (plasma) / 1 (ion), in the same ordered list as add_collision (hps_engine_add_beam_collision).  With a static beam
         (hipace.dt = 0) it is accepted and does nothing: every pair's scattering parameter is 0 there."""
-        check(_lib.lib().hps_engine_add_beam_collision(self._h, plasma_species, coulomb_log, seed))
+        check(_lib.lib().hps_engine_add_beam_collision(self._h, self._plasma_index(plasma_species), coulomb_log, seed))
 
     def set_beam_external_fields(self, E=None, B=None, constants=None):
         """beams.external_E(x,y,z,t) / beams.external_B(x,y,z,t): three expressions (strings in the input file's syntax, or
@@ -1110,14 +1181,15 @@ class SliceEngine:
         check(_lib.lib().hps_engine_set_density_profile(self._h, len(a[0]), p[0], p[1], len(a[2]), p[2], p[3]))
 
     def set_density_expr(self, species, text_or_table, constants=None, min_density=0.0):
-        """<plasma>.density(x,y,z) of species 0 / "plasma" or 1 / "ion" as a parsed function: a string in the input file's
+        """<plasma>.density(x,y,z) of species 0 / "plasma", 1 / "ion" or a further species (index or name) as a parsed function: a string in the input file's
         syntax (or a number), or the density table as a list of (position, string) pairs in ascending order of position
         (decks.read_density_table reads density_table_file); constants: my_constants; min_density: <plasma>.min_density.
         Compiled by hipace_amd/expr.py over (x, y, z) and handed to hps_engine_set_density_expr before the first begin_step.
         The value is the density itself: for this species it replaces <species>_density f_r f_t of set_density_profile."""
-        sp = {"plasma": 0, "ion": 1}.get(species, species)
-        if sp not in (0, 1):
-            raise ValueError(f"set_density_expr: species must be 0, 1, 'plasma' or 'ion', got {species!r}")
+        try:
+            sp = self._plasma_index(species)
+        except (ValueError, TypeError):
+            raise ValueError(f"set_density_expr: species must be 0, 1, 'plasma', 'ion' or a further species' index or name, got {species!r}")
         progs, pos = _expr.compile_density(text_or_table, constants)
         arr, keep = _expr.c_programs(progs)
         z = (C.c_double * len(pos))(*pos) if pos is not None else None
@@ -1362,9 +1434,10 @@ class SliceEngine:
         """plasma.insitu_period / insitu_radius: per-slice moments of PlasmaParticleContainer::InSituComputeDiags."""
         check(_lib.lib().hps_engine_set_insitu_plasma(self._h, min(float(radius), 1.0e300)))
 
-    def insitu_plasma(self):
+    def insitu_plasma(self, species=0):
+        """species: 0 / "plasma", or a further species' index or name (hps_engine_insitu_plasma_species)"""
         out = np.empty((15, self.deck["nz"]))
-        check(_lib.lib().hps_engine_insitu_plasma(self._h, out.ctypes.data_as(C.c_void_p)))
+        check(_lib.lib().hps_engine_insitu_plasma_species(self._h, self._plasma_index(species), out.ctypes.data_as(C.c_void_p)))
         return {n: out[i] for i, n in enumerate(self.INSITU_PLASMA)}
 
     def set_insitu_fields(self, on=True):

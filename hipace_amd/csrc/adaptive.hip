@@ -24,7 +24,8 @@ struct Adaptive {
     // hps_adaptive_set_density_expr: per species (0 plasma, 1 ion) its charge, whether the deck has it, and its density
     // programs with their positions (z_pos empty: one program); none: the species keeps |charge density| f_r(0) f_t(z)
     struct Species { bool present = false; double charge = 0.0, qn = 0.0; std::vector<std::vector<hps_expr_ins>> ins;
-                     std::vector<std::vector<double>> consts; std::vector<double> z_pos; } species[2];
+                     std::vector<std::vector<double>> consts; std::vector<double> z_pos; } species[HPS_MAX_PLASMA_SPECIES];
+    int n_species = 2;                                     // hps_adaptive_add_species appends behind the deck's two
     std::vector<double> prof_r, prof_fr, prof_t, prof_ft;
     double dt = 0.0;                                       // Hipace::m_dt of this rank
     double min_uz_mq = std::numeric_limits<double>::max();
@@ -176,7 +177,7 @@ extern "C" int hps_adaptive_set_density_expr (void* h, int species, int n_progs,
     static const char* const fn = "hps_adaptive_set_density_expr";
     Adaptive* A = static_cast<Adaptive*>(h);
     HPS_REQUIRE(A, std::string(fn) + ": null handle");
-    HPS_REQUIRE(species == 0 || species == 1, std::string(fn) + ": species must be 0 (plasma) or 1 (ion)");
+    HPS_REQUIRE(species >= 0 && species < A->n_species, std::string(fn) + ": species must be 0 (plasma), 1 (ion) or the index of an added species");
     HPS_REQUIRE(A->species[species].present, std::string(fn) + ": the deck does not have this species (no plasma, or no ion species)");
     HPS_REQUIRE(n_progs >= 1 && progs, std::string(fn) + ": n_progs must be >= 1 (at least one program)");
     HPS_REQUIRE(n_progs == 1 || z_pos, std::string(fn) + ": several programs need their positions (z_pos)");
@@ -195,6 +196,18 @@ extern "C" int hps_adaptive_set_density_expr (void* h, int species, int n_progs,
     }
     if (z_pos) S.z_pos.assign(z_pos, z_pos + n_progs);
     return HPS_OK;
+}
+
+extern "C" int hps_adaptive_add_species (void* h, double charge, double density)
+{
+    Adaptive* A = static_cast<Adaptive*>(h);
+    if (!A || A->n_species >= HPS_MAX_PLASMA_SPECIES || !std::isfinite(charge) || !std::isfinite(density)) {
+        set_error("hps_adaptive_add_species: null handle, more than HPS_MAX_PLASMA_SPECIES species, or a charge / density that is not finite");
+        return -1;
+    }
+    Adaptive::Species& S = A->species[A->n_species];
+    S.present = true; S.charge = charge; S.qn = charge*density;
+    return A->n_species++;
 }
 
 extern "C" int hps_adaptive_rho_max (void* h, double z, double* out)

@@ -642,8 +642,9 @@ static int coll_add_check (const void* h, const std::string& fn, bool species_ok
 
 extern "C" int hps_engine_add_collision (void* h, int species_a, int species_b, double coulomb_log, unsigned long long seed)
 {
-    if (int e = coll_add_check(h, "hps_engine_add_collision", (species_a == 0 || species_a == 1) && (species_b == 0 || species_b == 1),
-                               ": species are 0 (plasma) or 1 (ion)", species_a == 1 || species_b == 1,
+    const Engine* E = static_cast<const Engine*>(h);
+    if (int e = coll_add_check(h, "hps_engine_add_collision", E && E->plasma_species_ok(species_a) && E->plasma_species_ok(species_b),
+                               ": species are 0 (plasma), 1 (ion) or the index of an added species", species_a == 1 || species_b == 1,
                                ": at most HPS_MAX_COLLISIONS collisions")) return e;
     static_cast<Engine*>(h)->coll.push_back(Engine::Collision{species_a, species_b, coulomb_log, seed});
     return HPS_OK;
@@ -668,6 +669,10 @@ extern "C" int hps_collide_beam_plasma (hps_beam_slice beam, hps_plasma plasma, 
 
 extern "C" int hps_engine_add_beam_collision (void* h, int plasma_species, double coulomb_log, unsigned long long seed)
 {
+    if (h && plasma_species >= 2 && static_cast<const Engine*>(h)->plasma_species_ok(plasma_species)) {
+        set_error("hps_engine_add_beam_collision: a beam collision with a further plasma species (index >= 2) is not supported");
+        return HPS_ERR_UNSUPPORTED;
+    }
     if (int e = coll_add_check(h, "hps_engine_add_beam_collision", plasma_species == 0 || plasma_species == 1,
                                ": the plasma species is 0 (plasma) or 1 (ion)", plasma_species == 1,
                                ": at most HPS_MAX_COLLISIONS collisions, of both kinds together")) return e;

@@ -238,8 +238,13 @@ void Engine::checksum_slice ()
 // m_multi_plasma.InSituComputeDiags (Hipace.cpp:590): at the start of the slice
 void Engine::insitu_plasma (int islice)
 {
-    if (!d_insitu_pl || el.pl.n <= 0) return;
-    hipLaunchKernelGGL(k_insitu_plasma, dim3(256), dim3(256), 0, st, el.pl, 1.0/gm.c, insitu_pl_radius*insitu_pl_radius, d_insitu_pl, d.nz, islice);
+    if (!d_insitu_pl) return;
+    if (el.pl.n > 0)
+        hipLaunchKernelGGL(k_insitu_plasma, dim3(256), dim3(256), 0, st, el.pl, 1.0/gm.c, insitu_pl_radius*insitu_pl_radius, d_insitu_pl, d.nz, islice);
+    // the further species, each into its own block
+    for (int k = 2; k < n_sp && d_insitu_pl_more; ++k) if (sp[k].pl.n > 0)
+        hipLaunchKernelGGL(k_insitu_plasma, dim3(256), dim3(256), 0, st, sp[k].pl, 1.0/gm.c, insitu_pl_radius*insitu_pl_radius,
+                           d_insitu_pl_more + (size_t)(k - 2)*15*d.nz, d.nz, islice);
 }
 // Fields::InSituComputeDiags (Hipace.cpp:686): behind the field solves
 void Engine::insitu_fields (int islice)
@@ -264,6 +269,7 @@ extern "C" int hps_engine_set_insitu_plasma (void* h, double radius)
     Engine* E = static_cast<Engine*>(h);
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     (void)hipFree(E->d_insitu_pl); E->d_insitu_pl = nullptr; E->insitu_pl_radius = radius;
+    (void)hipFree(E->d_insitu_pl_more); E->d_insitu_pl_more = nullptr;      // (the further species' blocks: the next begin_step)
     if (!(radius > 0.0)) return HPS_OK;
     HPS_HIP_CHECK(hipMalloc(&E->d_insitu_pl, (size_t)15*E->d.nz*sizeof(double)));
     HPS_HIP_CHECK(hipMemset(E->d_insitu_pl, 0, (size_t)15*E->d.nz*sizeof(double)));
@@ -301,13 +307,17 @@ extern "C" int hps_engine_insitu_beam_species (void* h, int species, double* out
     }
     return HPS_OK;
 }
-extern "C" int hps_engine_insitu_plasma (void* h, double* out)
+extern "C" int hps_engine_insitu_plasma (void* h, double* out) { return hps_engine_insitu_plasma_species(h, 0, out); }
+extern "C" int hps_engine_insitu_plasma_species (void* h, int k, double* out)
 {
     Engine* E = static_cast<Engine*>(h);
-    HPS_REQUIRE(E->d_insitu_pl && out, "hps_engine_insitu_plasma: not switched on");
+    HPS_REQUIRE(E && E->d_insitu_pl && out, "hps_engine_insitu_plasma: not switched on");
+    HPS_REQUIRE(k == 0 || (k >= 2 && k < E->n_sp), "hps_engine_insitu_plasma_species: species must be 0 (plasma) or the index of an added species");
+    HPS_REQUIRE(k == 0 || E->d_insitu_pl_more, "hps_engine_insitu_plasma_species: no step has begun since hps_engine_set_insitu_plasma");
     HPS_HIP_CHECK(hipStreamSynchronize(E->st));
     const int nz = E->d.nz;
-    HPS_HIP_CHECK(hipMemcpy(out, E->d_insitu_pl, (size_t)15*nz*sizeof(double), hipMemcpyDeviceToHost));
+    const double* src = k == 0 ? E->d_insitu_pl : E->d_insitu_pl_more + (size_t)(k - 2)*15*nz;
+    HPS_HIP_CHECK(hipMemcpy(out, src, (size_t)15*nz*sizeof(double), hipMemcpyDeviceToHost));
     // averages: everything but sum(w), the energy and the count is divided by sum(w) (:511-516)
     for (int k = 0; k < nz; ++k) {
         const double sw = out[k], inv = sw <= 0.0 ? 0.0 : 1.0/sw;

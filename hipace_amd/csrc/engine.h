@@ -96,7 +96,7 @@ struct Engine {
     double hollow_core_radius = 0.0;
     bool fine_patch_set = false; int fine_T = 0; long fine_ncells = 0; int* d_fine_level = nullptr; int* d_fine_cells = nullptr;
     // <plasma>.u_mean / u_std (temperature_in_ev), plasmas.do_symmetrize, prevent_centered_particle (plasma_init.hip):
-    // the momenta per species (Species::thermal); the two switches hold for both species
+    // the momenta per species (Species::thermal); the two switches hold for every species
     struct Thermal { double u_mean[3] = {0.0, 0.0, 0.0}, u_std[3] = {0.0, 0.0, 0.0}; unsigned long long seed = 0;
                      bool warm () const { for (int q = 0; q < 3; ++q) if (u_mean[q] != 0.0 || u_std[q] != 0.0) return true; return false; }
                    };
@@ -125,7 +125,7 @@ struct Engine {
     int set_beam_external_fields (const hps_expr* E3, const hps_expr* B3);
     // <plasma>.density(x,y,z) / density_table_file as expression programs (hps_engine_set_density_expr, plasma_init.hip, DESIGN
     // 8m), per species (Species::dens): the species' programs as given (z_pos empty: the one program of density(x,y,z)), the
-    // offset of each in the engine's one device image (both species' instructions, the pooled constants), the deepest stack
+    // offset of each in the engine's one device image (every species' instructions, the pooled constants), the deepest stack
     // of the species' programs, and the entry in force in the step that has begun.  on = false: the tables, the kernels as they were.
     struct DensityExpr { bool on = false; std::vector<std::vector<hps_expr_ins>> ins; std::vector<std::vector<double>> consts;
                          std::vector<double> z_pos; std::vector<int> off; int depth = 0; double min_density = 0.0; int cur = 0; };
@@ -134,11 +134,12 @@ struct Engine {
     void density_begin_step (double ct);                  // UpdateDensityFunction(c t): the table entry in force
     DensityProgram density_program (int species) const;   // n_ins = 0: this species keeps the tables
     size_t density_lds (int species) const { const DensityExpr& D = sp[species].dens; return D.on ? expr_lds_bytes(D.depth, 256) : 0; }
-    // One plasma species of the slice: sp[0] the plasma (the electrons), sp[1] the species "ion".  The parameters are the deck's
-    // plasma_* / ion_* fields, read once (Engine::create; keyed: the first begin_step); fine_ppc, thermal and dens are what
+    // One plasma species of the slice: sp[0] the plasma (the electrons), sp[1] the species "ion", sp[2 ..] the fixed-charge species
+    // of hps_engine_add_plasma_species.  The parameters are the deck's plasma_* / ion_* fields, read once
+    // (Engine::create; keyed: the first begin_step) or the added record's; fine_ppc, thermal and dens are what
     // hps_engine_set_plasma_init / _momentum / _density_expr have given.
     struct Species {
-        int index = 0;                                  // 0 or 1: the species' number in the C ABI and in the key of its random draws
+        int index = 0;                                  // the species' number in the C ABI and in the key of its random draws
         // the sheet and the second buffer of the tile sort (sort.hip), each one block of 11 arrays + idcpu, ion_lev (soa_arrays);
         // the particles NOW are pl.n (the plasma's grows when the species "ion" releases electrons)
         hps_plasma pl{}, pl_alt{}; double *real = nullptr, *real_alt = nullptr; Tiling* tiling = nullptr;
@@ -146,14 +147,21 @@ struct Engine {
         int ppc[2] = {0, 0}, fine_ppc[2] = {0, 0}; double density = 0.0, charge = 0.0, mass = 0.0;
         int init_level = 0, can_ionize = 0, keyed = 0;  // keyed: the lattice index in the id bits (the ions; electrons that collide)
         bool temp_push = false;                         // pushed to temporary slices from x_prev: predictor-corrector; the plasma under SALAME
+        bool neutralize = false;                        // a further species: its initial sheet with -charge into the ion rhomjz plane
         Thermal thermal; DensityExpr dens;
         bool present () const { return density > 0.0; } // is the species in the deck
         // Without pushes to a temporary slice every push commits its state, so x_prev == x and y_prev == y at all times
         // (PlasmaParticleAdvance.cpp:176-188): alias them -- two arrays less to write per push and to move per re-sort.
         // The C ABI keeps 11 pointers; the kernels skip the second store when two coincide.
         bool alias_prev () const { return !temp_push; }
-    } sp[2];
+    } sp[HPS_MAX_PLASMA_SPECIES];
     Species &el = sp[0], &ions = sp[1];
+    // Further species: the slots behind the two (absent slots hold no particles and every per-species loop passes them by).
+    // With one the electrons are not alone: the slice takes the general schedule wherever a fast one reads "one species only"
+    int n_sp = 2;
+    bool further () const { return n_sp > 2; }
+    int add_plasma_species (const hps_plasma_species* s, int* index_out);
+    bool plasma_species_ok (int k) const { return k >= 0 && k < n_sp; }      // an index the C ABI takes (present or not)
     // does this species' sheet come from k_init_plasma_warm?  (false: the kernels and arguments of a deck without these keys)
     bool warm_init (const Species& s) const { return s.thermal.warm() || do_symmetrize || shifted(s.ppc, 0) || shifted(s.ppc, 1); }
     long sheet_slots (const Species& s) const;
@@ -290,6 +298,7 @@ struct Engine {
     double* d_insitu_bm = nullptr; double insitu_bm_radius = 0.0;     // [23][nz] raw sums of the beam moments
     void insitu_beam (int islice);
     double* d_insitu_pl = nullptr; double insitu_pl_radius = 0.0;     // [15][nz] raw sums of the plasma moments
+    double* d_insitu_pl_more = nullptr;                               // ... of the further species, [n_sp - 2][15][nz] (begin_step)
     double* d_insitu = nullptr;      // [10][nz] in-situ field reductions (Fields::InSituComputeDiags)
     void insitu_plasma (int islice); void insitu_fields (int islice); void checksum_slice ();      // diagnostics.hip: no-ops unless switched on
 

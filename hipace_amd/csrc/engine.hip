@@ -234,6 +234,8 @@ Engine::~Engine ()
     if (mg) hps_mg_destroy(mg);
     (void)hipFree(slab.p); free_soa(el.pl, el.real); free_soa(el.pl_alt, el.real_alt);      // (the ions' sheets: ion_destroy)
     delete el.tiling;
+    for (int k = 2; k < n_sp; ++k) { free_soa(sp[k].pl, sp[k].real); free_soa(sp[k].pl_alt, sp[k].real_alt); delete sp[k].tiling; }
+    (void)hipFree(d_insitu_pl_more);
     (void)hipFree(staging); (void)hipFree(d_open_mom); (void)hipFree(beam_data); (void)hipFree(beam_init);
     (void)hipFree(bm_store); (void)hipFree(bm_nsub); (void)hipFree(bm_nsub_scr); (void)hipFree(d_B); (void)hipFree(d_nfront);
     (void)hipFree(d_mom); (void)hipFree(d_sal); (void)hipFree(bm_sp); (void)hipFree(bm_sp_scr); (void)hipFree(beam_tag); (void)hipFree(d_bsp_tab);
@@ -292,7 +294,7 @@ static hps_plasma tail_of (const hps_plasma& p, long first, long n)
     return t;
 }
 
-// The sheets of both species, sized by what InitParticles creates; hps_engine_set_plasma_init / hps_engine_set_fine_patch
+// The sheets of every species, sized by what InitParticles creates; hps_engine_set_plasma_init / hps_engine_set_fine_patch
 // call it again (before the first step: nothing else holds a pointer into them yet)
 int Engine::alloc_sheets ()
 {
@@ -442,6 +444,36 @@ int Engine::create (const hps_deck& deck, int device)
     return init_beam();
 }
 
+// hps_engine_add_plasma_species: every check first, then the record and its sheet; nothing else of the engine changes
+int Engine::add_plasma_species (const hps_plasma_species* s, int* index_out)
+{
+    static const std::string fn = "hps_engine_add_plasma_species: ";
+    HPS_REQUIRE(s && index_out, fn + "null argument");
+    HPS_REQUIRE(!step_begun && !el.tiling, fn + "call before the first hps_engine_begin_step");
+    if (d.beam_do_salame || species_salame) {
+        set_error(fn + "an engine with beam_do_salame or beam_species_salame is not supported: SALAME drives the electrons alone (as with ion_on)");
+        return HPS_ERR_UNSUPPORTED;
+    }
+    HPS_REQUIRE(n_sp < HPS_MAX_PLASMA_SPECIES, fn + "at most HPS_MAX_PLASMA_SPECIES plasma species (the deck's two included)");
+    HPS_REQUIRE(s->ppc[0] >= 1 && s->ppc[1] >= 1, fn + "ppc must be >= 1 in both directions");
+    HPS_REQUIRE(std::isfinite(s->density) && s->density > 0.0, fn + "density must be positive");
+    HPS_REQUIRE(std::isfinite(s->mass) && s->mass > 0.0, fn + "mass must be positive");
+    HPS_REQUIRE(std::isfinite(s->charge) && s->charge != 0.0, fn + "charge must not be 0");
+    const bool fine = s->fine_ppc[0] != 0 || s->fine_ppc[1] != 0;
+    HPS_REQUIRE(!fine || (s->fine_ppc[0] > 0 && s->fine_ppc[1] > 0 && s->fine_ppc[0] % s->ppc[0] == 0 && s->fine_ppc[1] % s->ppc[1] == 0),
+                fn + "fine_ppc must be {0, 0} or positive and divisible by ppc, component by component");
+    HPS_REQUIRE(!(fine && prevent_centered), fn + "prevent_centered_particle cannot be combined with the fine plasma patch (fine_ppc, fine_patch)");
+    Species& q = sp[n_sp];
+    q = Species{};
+    q.index = n_sp; q.can_ionize = 0; q.keyed = 0; q.init_level = 0; q.temp_push = pc;
+    std::copy(s->ppc, s->ppc + 2, q.ppc); std::copy(s->fine_ppc, s->fine_ppc + 2, q.fine_ppc);
+    q.density = s->density; q.charge = s->charge; q.mass = s->mass; q.neutralize = s->neutralize_background != 0;
+    q.n_init = q.cap = sheet_slots(q); q.pl.n = q.n_init;
+    if (int e = alloc_soa(q.pl, q.real, q.cap, q.alias_prev())) { free_soa(q.pl, q.real); q = Species{}; return e; }
+    *index_out = n_sp++;
+    return HPS_OK;
+}
+
 int Engine::setup_tiling ()
 {
     if (tile_size == 0 || el.cap == 0 || el.tiling) return HPS_OK;
@@ -463,6 +495,13 @@ int Engine::setup_tiling ()
         {   const char* v = std::getenv("HPS_ION_TILE_SKIP");
             if (!(v && std::atoi(v) == 0)) HPS_HIP_CHECK(hipMalloc(&ion.d_fbound, (size_t)5*ions.tiling->g.ntiles*sizeof(double))); }
     }
+    // a further species on the engine's tile size; its push keeps reading idcpu (valid_by_psi stays off in its tiling)
+    for (int k = 2; k < n_sp; ++k) {
+        Species& s = sp[k];
+        if (s.cap == 0) continue;
+        if (int e = tiling_create(d.nx, d.ny, tile_size, s.cap, &s.tiling)) return e;
+        if (int e = alloc_soa(s.pl_alt, s.real_alt, s.cap, s.alias_prev())) return e;
+    }
     return HPS_OK;
 }
 
@@ -478,6 +517,7 @@ int Engine::sort_sheet (Species& s)
 int Engine::resort ()
 {
     if (int e = sort_sheet(el)) return e;
+    for (int k = 2; k < n_sp; ++k) if (sp[k].tiling && sp[k].pl.n > 0) { if (int e = sort_sheet(sp[k])) return e; }      // (the ions are sorted once per step)
     since_sort = 0; ++n_sorts;
     fb_at_sort = h_nfallback ? *h_nfallback : 0;
     return HPS_OK;
@@ -504,7 +544,9 @@ int Engine::begin_step ()
     HPS_REQUIRE(!(d.dt_adaptive && steps_begun == 0 && d.beam_profile < 0 && !host_beam),
                 "hps_engine_begin_step: hipace.dt = adaptive needs a beam (beam_profile = -1 and no hps_engine_set_beam_particles: the sum of weights is 0)");
     // (PlasmaParticleContainer.cpp:167-169)
-    HPS_REQUIRE(fine_patch_set == (el.fine_ppc[0] > 0 || ions.fine_ppc[0] > 0),
+    bool any_fine = false;
+    for (const Species& s : sp) any_fine = any_fine || s.fine_ppc[0] > 0;
+    HPS_REQUIRE(fine_patch_set == any_fine,
                 "hps_engine_begin_step: both fine_ppc (hps_engine_set_plasma_init) and the fine patch (hps_engine_set_fine_patch) must be given to use the fine plasma patch");
     HPS_REQUIRE(!(laser && laser_pulses_set && laser_pulses.empty() && laser_samples.empty() && !step_begun),
                 "hps_engine_begin_step: hps_engine_set_laser_pulses with n = 0 needs at least one hps_engine_add_laser_samples");
@@ -513,6 +555,10 @@ int Engine::begin_step ()
     if (laser && !step_begun) { for (const LaserSamples& S : laser_samples) { if (int e = laser_check_samples(*this, S)) return e; } }
     if (int e = setup_tiling()) return e;
     el.keyed = coll.empty() ? 0 : 1;      // collisions (all added before the first step): the lattice index in the id bits
+    for (int k = 2; k < n_sp; ++k) {      // ... a further species: only if it takes part in one
+        sp[k].keyed = 0;
+        for (const Collision& c : coll) if ((!c.beam && c.a == k) || c.b == k) sp[k].keyed = 1;
+    }
     step_begun = true;
     if (moving && steps_begun > 0) {
         // a slice that outgrew the hand-off capacity during the previous step lost particles: refuse to go on
@@ -547,12 +593,18 @@ int Engine::begin_step ()
     // charges cancel to rounding only, it iterates on that residue itself, and the literal rule on the engine's residue is its
     // match (any non-zero byte pattern reads as "disturbed")
     // A warm plasma deposits real jx, jy from the first slice on.
-    if (d_pc_dist) HPS_HIP_CHECK(hipMemsetAsync(d_pc_dist, (d.grid_current_on || d.ion_on || d.plasma_no_neutralize || el.thermal.warm() || ions.thermal.warm()) ? 1 : 0, sizeof(int), st));
+    // (a further species is a second species as particles)
+    if (d_pc_dist) HPS_HIP_CHECK(hipMemsetAsync(d_pc_dist, (d.grid_current_on || d.ion_on || further() || d.plasma_no_neutralize || el.thermal.warm() || ions.thermal.warm()) ? 1 : 0, sizeof(int), st));
     HPS_HIP_CHECK(hipMemsetAsync(d_checksum, 0, HPS_PC_NCOMP_MAX*sizeof(double), st));
     HPS_HIP_CHECK(hipMemsetAsync(d_laser_sum, 0, sizeof(double), st));
     if (int e = join_laser()) return e;        // the time levels rotate: the last slice's envelope must be in
     if (laser) { if (int e = laser_begin_step(*this)) return e; }
     if (d_insitu_pl) HPS_HIP_CHECK(hipMemsetAsync(d_insitu_pl, 0, (size_t)15*d.nz*sizeof(double), st));
+    if (d_insitu_pl && further()) {
+        const size_t bytes = (size_t)(n_sp - 2)*15*d.nz*sizeof(double);
+        if (!d_insitu_pl_more) HPS_HIP_CHECK(hipMalloc(&d_insitu_pl_more, bytes));
+        HPS_HIP_CHECK(hipMemsetAsync(d_insitu_pl_more, 0, bytes, st));
+    }
     if (d_insitu_bm) HPS_HIP_CHECK(hipMemsetAsync(d_insitu_bm, 0, (size_t)23*d.nz*n_beam_species()*sizeof(double), st));
     if (d_insitu) HPS_HIP_CHECK(hipMemsetAsync(d_insitu, 0, (size_t)10*d.nz*sizeof(double), st));
     if (insitu_laser && laser) { if (int e = laser_clear_insitu(*this)) return e; }
@@ -583,7 +635,9 @@ int Engine::begin_step ()
     if (int e = ionize_collect()) return e;
     el.pl.n = el.n_init;
     if (int e = init_sheet(el)) return e;
-    if (el.tiling) { if (int e = resort()) return e; }
+    // the further species: back on their lattice too, ahead of the sort that takes them along
+    for (int k = 2; k < n_sp; ++k) { sp[k].pl.n = sp[k].n_init; if (int e = init_sheet(sp[k])) return e; }
+    if (el.tiling) { if (int e = resort()) return e; }      // (tilings exist only beside the electrons': setup_tiling)
     if (el.pl.n > 0 && !d.plasma_no_neutralize) {
         // neutralising ion background, deposited once per step with charge -q (MultiPlasma.cpp:106-118)
         const int comp[6] = {-1, -1, -1, -1, -1, pc ? (int)HPS_PC_ION_RHOMJZ : (int)HPS_C_ION_RHOMJZ};
@@ -591,6 +645,17 @@ int Engine::begin_step ()
             if (int e = deposit_current_tiled(slab, el.pl, gm, comp, -el.charge, el.mass, d.order, d.max_qsa, 0, d_nqsa, el.tiling, d_nfallback, st)) return e;
         } else {
             if (int e = hps_deposit_current(slab, el.pl, gm, comp, -el.charge, el.mass, d.order, d.max_qsa, 0, d_nqsa, st)) return e;
+        }
+    }
+    for (int k = 2; k < n_sp; ++k) {
+        // DepositNeutralizingBackground per species (MultiPlasma.cpp:106-118): its initial sheet with charge -q
+        const Species& s = sp[k];
+        if (!s.neutralize || s.pl.n == 0) continue;
+        const int comp[6] = {-1, -1, -1, -1, -1, pc ? (int)HPS_PC_ION_RHOMJZ : (int)HPS_C_ION_RHOMJZ};
+        if (s.tiling) {
+            if (int e = deposit_current_tiled(slab, s.pl, gm, comp, -s.charge, s.mass, d.order, d.max_qsa, 0, d_nqsa, s.tiling, d_nfallback, st)) return e;
+        } else {
+            if (int e = hps_deposit_current(slab, s.pl, gm, comp, -s.charge, s.mass, d.order, d.max_qsa, 0, d_nqsa, st)) return e;
         }
     }
     if (ions.present()) {
@@ -643,7 +708,7 @@ int Engine::species_deposit (const Species& s, const int comp[6], const BeamPair
     if (p.n == 0) return HPS_OK;
     if (!T) return hps_deposit_current_laser(slab, p, gm, comp, c_aabs, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, st);
     long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = deposit_current_tiled(slab, p, gm, comp, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, beam, go, valid_by_w && !s.can_ionize)) return e; }
+    if (T->sorted_n > 0) { if (int e = deposit_current_tiled(slab, p, gm, comp, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, beam, go, valid_by_w && &s == &el)) return e; }
     if (p.n > covered) return hps_deposit_current_laser(slab, tail_of(p, covered, p.n - covered), gm, comp, c_aabs, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, st);
     return HPS_OK;
 }
@@ -653,7 +718,7 @@ int Engine::species_explicit (const Species& s, const int cache[4], const int de
     if (p.n == 0) return HPS_OK;
     if (!T) return hps_explicit_deposit_laser(slab, p, gm, cache, c_aabs, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, st);
     long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = explicit_deposit_tiled(slab, p, gm, cache, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, valid_by_w && !s.can_ionize)) return e; }
+    if (T->sorted_n > 0) { if (int e = explicit_deposit_tiled(slab, p, gm, cache, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, valid_by_w && &s == &el)) return e; }
     if (p.n > covered) return hps_explicit_deposit_laser(slab, tail_of(p, covered, p.n - covered), gm, cache, c_aabs, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, st);
     return HPS_OK;
 }
@@ -770,7 +835,7 @@ int Engine::solve_slice_begin (int islice)
     ahead_for = -2;
     // HPS_EARLY_INIT: a slice of the plain path -- nothing but the kernels below and the push touches the re-initialised planes --
     // runs on whichever set of them is live; any other slice runs on the slab's own, with the zeroing pass of its own
-    const bool plain = n_alt > 0 && !moving && coll.empty() && c_aabs < 0 && !ions.present() && !salame_now() && !fuse_push_deposit && !ahead
+    const bool plain = n_alt > 0 && !moving && coll.empty() && c_aabs < 0 && !ions.present() && !further() && !salame_now() && !fuse_push_deposit && !ahead
                        && lazy_shift && !aux_on && !diagnostics && !d_fd && !d_insitu;
     if (!plain && (alt_live || init_done)) {
         flush_shift();
@@ -838,7 +903,7 @@ int Engine::solve_slice_begin (int islice)
     {   const int comp[6] = {HPS_C_JX, HPS_C_JY, -1, L.rho, L.chi, L.rhomjz};
         if ((e = species_deposit(el, comp, beam_folded ? &bw : nullptr))) return e;
         // MultiPlasma::DepositCurrent: every species in turn (MultiPlasma.cpp:78-87); an ion weighs in with its level
-        if ((e = species_deposit(ions, comp))) return e; }
+        for (int k = 1; k < n_sp; ++k) { if ((e = species_deposit(sp[k], comp))) return e; } }
     mark();   // b2
     if (pair) {
         if (!beam_folded && bw.nwg > 0) {
@@ -927,11 +992,11 @@ int Engine::solve_slice_begin (int islice)
     // species, nothing that reads the fields between the solve and the push) enqueues the push BEHIND the speculated
     // V-cycles, gated on the solve's own stopping rule, and only then waits for the norms: the device goes from the last
     // V-cycle straight into the push instead of idling until the host has seen the norms and launched it.
-    const bool fuse = fuse_push_deposit && coll.empty() && el.tiling && islice > 0 && !moving && c_aabs < 0 && !ions.present() && el.pl.n > 0 && el.tiling->sorted_n == el.pl.n && !sal;
-    const bool gated = gate_push && el.tiling && !fuse && !ions.present() && el.pl.n > 0 && el.tiling->sorted_n == el.pl.n && !diagnostics && !d_fd && !d_insitu && !sal;
+    const bool fuse = fuse_push_deposit && coll.empty() && el.tiling && islice > 0 && !moving && c_aabs < 0 && !ions.present() && !further() && el.pl.n > 0 && el.tiling->sorted_n == el.pl.n && !sal;
+    const bool gated = gate_push && el.tiling && !fuse && !ions.present() && !further() && el.pl.n > 0 && el.tiling->sorted_n == el.pl.n && !diagnostics && !d_fd && !d_insitu && !sal;
     // ... and with an ionisable species on tiles: its field bounds, its push (which takes the ADK decisions and appends the
     // electrons) and the electrons' push, all behind the speculated V-cycles; the two pushes are gated (HPS_GATED_ION_PUSH=0: off)
-    const bool gated_ion = gate_push && gate_ion_push && el.tiling && !fuse && ions.present() && ions.tiling && el.pl.n > 0 && el.tiling->sorted_n > 0 && fold_tail
+    const bool gated_ion = gate_push && gate_ion_push && el.tiling && !fuse && ions.present() && !further() && ions.tiling && el.pl.n > 0 && el.tiling->sorted_n > 0 && fold_tail
                            && !diagnostics && !d_fd && !d_insitu && !sal;
     const int comp_push[5] = {HPS_C_PSI, HPS_C_EZ, HPS_C_BX, HPS_C_BY, HPS_C_BZ};
     {
@@ -1058,7 +1123,9 @@ int Engine::solve_slice_finish (int islice)
             if (el.pl.n > body_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(el.pl, body_covered, el.pl.n - body_covered), gm, comp, c_aabs, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
         } else {
             if ((e = species_advance(el, comp, 0))) return e;
-        } }
+        }
+        // the further species (a slice that holds one is never gated or fused)
+        for (int k = 2; k < n_sp; ++k) { if ((e = species_advance(sp[k], comp, 0))) return e; } }
     }
 
     // beam push and hand-off of the slipped particles (Hipace.cpp:704-706)
@@ -1183,6 +1250,28 @@ extern "C" hps_plasma hps_engine_ions (void* h)
     Engine* E = static_cast<Engine*>(h);
     (void)hipStreamSynchronize(E->st);
     return E->ions.pl;
+}
+extern "C" int hps_engine_add_plasma_species (void* h, const hps_plasma_species* s, int* index_out)
+{
+    HPS_REQUIRE(h, "hps_engine_add_plasma_species: null engine");
+    return static_cast<Engine*>(h)->add_plasma_species(s, index_out);
+}
+extern "C" int hps_engine_plasma_species_info (void* h, int* n, long* counts)
+{
+    HPS_REQUIRE(h, "hps_engine_plasma_species_info: null engine");
+    Engine* E = static_cast<Engine*>(h);
+    HPS_HIP_CHECK(hipStreamSynchronize(E->st));
+    if (int e = E->ionize_collect()) return e;
+    if (n) *n = E->n_sp;
+    for (int k = 0; counts && k < E->n_sp; ++k) counts[k] = E->sp[k].pl.n;
+    return HPS_OK;
+}
+extern "C" hps_plasma hps_engine_plasma_species (void* h, int k)
+{
+    Engine* E = static_cast<Engine*>(h);
+    if (!E || !E->plasma_species_ok(k)) return hps_plasma{};
+    (void)hipStreamSynchronize(E->st);
+    return E->sp[k].pl;
 }
 extern "C" int hps_engine_ion_stats (void* h, long* n_ionized, long* n_product)
 {

@@ -363,6 +363,29 @@ void k_laser_chi_initial_prog (double* __restrict__ out, int nxl, int nyl, doubl
     out[(long)j*nxl + i] = n0*f0 + n1*f1;
 }
 
+// ... and one further species (hps_engine_add_plasma_species) on top of the two: += n f, n its program's value or the
+// tables', as above.  One launch per further species: the two kernels above stay what an engine without one launches.
+__global__ __launch_bounds__(256)
+void k_laser_chi_initial_add (double* __restrict__ out, int nxl, int nyl, double dxl, double dyl, double xoffl, double yoffl, double f,
+                              DensityProgram p, const double* __restrict__ prof, int nr, double ft, double radius_sq, double hollow_sq)
+{
+    extern __shared__ double s_chi_stack[];
+    const int i = blockIdx.x*blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
+    if (i >= nxl) return;
+    const double x = i*dxl + xoffl, y = j*dyl + yoffl;
+    const double rsq = x*x + y*y;
+    const bool in = !(rsq > radius_sq || rsq < hollow_sq);
+    double n = in ? ft*table_value(prof, prof + nr, nr, sqrt(rsq)) : 0.0;
+    if (p.n_ins > 0) {
+        ExprLdsStack st{s_chi_stack + threadIdx.x, (int)blockDim.x};
+        const ExprXyz v{x, y, p.z};
+        const double val = expr_run(p.ins, p.n_ins, p.consts, v, st);
+        n = in ? val : 0.0;
+    }
+    out[(long)j*nxl + i] += n*f;
+}
+
 // InterpolateChi (:334-407): one thread per laser cell.  Inside x_lo .. x_hi, y_lo .. y_hi (the laser cells on the field box
 // shrunk by the guard width, :358-372) chi of the slab, interpolated; outside, chi of the unperturbed plasma.
 template <int ORDER>
@@ -689,22 +712,36 @@ int laser_chi_initial (Engine& E)
     // per species: n q^2 mu0 / m, an ionisable one at its initial level; a program's value is the density itself
     const DensityProgram p[2] = {E.density_program(0), E.density_program(1)};
     double fac[2] = {0.0, 0.0};
-    for (const Engine::Species& s : E.sp) if (s.present()) {
+    for (int k = 0; k < 2; ++k) if (E.sp[k].present()) {
+        const Engine::Species& s = E.sp[k];
         const double n = p[s.index].n_ins > 0 ? 1.0 : s.density, lev = s.can_ionize ? (double)s.init_level : 1.0;
         fac[s.index] = n*s.charge*s.charge*E.gm.mu0/s.mass*lev*lev;
     }
     const double radius_sq = d.plasma_radius > 0.0 ? d.plasma_radius*d.plasma_radius : INFINITY;
+    // the further species are added on top of the two, in index order, behind whichever kernel writes the two
+    auto add_further = [&] () -> int {
+        for (int k = 2; k < E.n_sp; ++k) {
+            const Engine::Species& s = E.sp[k];
+            const DensityProgram q = E.density_program(k);
+            const double f = (q.n_ins > 0 ? 1.0 : s.density)*s.charge*s.charge*E.gm.mu0/s.mass;
+            hipLaunchKernelGGL(k_laser_chi_initial_add, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), E.density_lds(k), E.st, L->chi_initial, L->nx, L->ny,
+                               L->dx, L->dy, L->xoff, L->yoff, f, q, E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, radius_sq,
+                               E.hollow_core_radius*E.hollow_core_radius);
+            HPS_HIP_CHECK(hipGetLastError());
+        }
+        return HPS_OK;
+    };
     if (p[0].n_ins > 0 || p[1].n_ins > 0) {
         hipLaunchKernelGGL(k_laser_chi_initial_prog, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), std::max(E.density_lds(0), E.density_lds(1)), E.st,
                            L->chi_initial, L->nx, L->ny, L->dx, L->dy, L->xoff, L->yoff, fac[0], fac[1], p[0], p[1], E.d_prof_r, (int)E.prof_r.size(), E.prof_ft,
                            radius_sq, E.hollow_core_radius*E.hollow_core_radius);
         HPS_HIP_CHECK(hipGetLastError());
-        return HPS_OK;
+        return add_further();
     }
     hipLaunchKernelGGL(k_laser_chi_initial, dim3(ceil_div(L->nx, 256), L->ny), dim3(256), 0, E.st, L->chi_initial, L->nx, L->ny, L->dx, L->dy,
                        L->xoff, L->yoff, fac[0], fac[1], E.d_prof_r, (int)E.prof_r.size(), E.prof_ft, radius_sq, E.hollow_core_radius*E.hollow_core_radius);
     HPS_HIP_CHECK(hipGetLastError());
-    return HPS_OK;
+    return add_further();
 }
 
 static int launch_interp_aabs (SlabView f, int c_aabs, const double2* a, int nxl, int nyl, double dxl, double dyl, double xoffl, double yoffl,

@@ -257,7 +257,7 @@ int Engine::set_plasma_init (const int* plasma_fine, const int* ion_fine, double
 int Engine::set_plasma_momentum (int species, const double* u_mean, const double* u_std, unsigned long long seed)
 {
     HPS_REQUIRE(!step_begun && !el.tiling, "hps_engine_set_plasma_momentum: call before the first hps_engine_begin_step");
-    HPS_REQUIRE(species == 0 || species == 1, "hps_engine_set_plasma_momentum: species must be 0 (plasma) or 1 (ion)");
+    HPS_REQUIRE(plasma_species_ok(species), "hps_engine_set_plasma_momentum: species must be 0 (plasma), 1 (ion) or the index of an added species");
     HPS_REQUIRE(sp[species].present(), "hps_engine_set_plasma_momentum: the deck does not have this species (no plasma, or no ion species)");
     HPS_REQUIRE(u_mean && u_std, "hps_engine_set_plasma_momentum: null argument");
     for (int q = 0; q < 3; ++q)
@@ -271,7 +271,9 @@ int Engine::set_plasma_momentum (int species, const double* u_mean, const double
 int Engine::set_plasma_symmetry (int symmetrize, int prevent_centered_particle)
 {
     HPS_REQUIRE(!step_begun && !el.tiling, "hps_engine_set_plasma_symmetry: call before the first hps_engine_begin_step");
-    HPS_REQUIRE(!(prevent_centered_particle && (fine_patch_set || el.fine_ppc[0] > 0 || ions.fine_ppc[0] > 0)), PREVENT_VS_PATCH);
+    bool any_fine = fine_patch_set;
+    for (const Species& q : sp) any_fine = any_fine || q.fine_ppc[0] > 0;
+    HPS_REQUIRE(!(prevent_centered_particle && any_fine), PREVENT_VS_PATCH);
     do_symmetrize = symmetrize != 0; prevent_centered = prevent_centered_particle != 0;
     HPS_HIP_CHECK(hipStreamSynchronize(st));
     return alloc_sheets();
@@ -326,12 +328,12 @@ int Engine::set_fine_patch (const unsigned char* mask_host, int transition_cells
 }
 
 // hps_engine_set_density_expr: every program is checked before anything changes; then the engine's one image is
-// rebuilt from both species' programs
+// rebuilt from every species' programs
 int Engine::set_density_expr (int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density)
 {
     static const char* const fn = "hps_engine_set_density_expr";
     HPS_REQUIRE(!step_begun, std::string(fn) + ": call before the first hps_engine_begin_step");
-    HPS_REQUIRE(species == 0 || species == 1, std::string(fn) + ": species must be 0 (plasma) or 1 (ion)");
+    HPS_REQUIRE(plasma_species_ok(species), std::string(fn) + ": species must be 0 (plasma), 1 (ion) or the index of an added species");
     HPS_REQUIRE(sp[species].present(), std::string(fn) + ": the deck does not have this species (no plasma, or no ion species)");
     HPS_REQUIRE(n_progs >= 1 && progs, std::string(fn) + ": n_progs must be >= 1 (at least one program)");
     HPS_REQUIRE(n_progs == 1 || z_pos, std::string(fn) + ": several programs need their positions (z_pos)");

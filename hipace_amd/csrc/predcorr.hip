@@ -235,7 +235,7 @@ int Engine::solve_slice_pc_begin (int islice)
     // the loop (Hipace.cpp:935-1031)
     HPS_HIP_CHECK(hipMemsetAsync(d_pc, 0, 2*sizeof(double), st));
     hipLaunchKernelGGL(k_rel_b_error, dim3(128), b256, 0, st, f, HPS_PC_P_BX, HPS_PC_PIT_BX, d_pc, (volatile double*)nullptr, 0.0);
-    const bool spec = pc_speculate && el.tiling && !moving && !ions.present();      // (a second species: the host-controlled loop)
+    const bool spec = pc_speculate && el.tiling && !moving && !ions.present() && !further();      // (a second species: the host-controlled loop)
     hipLaunchKernelGGL(k_pc_guess, gplane, b256, 0, st, slab.p, slab.nstride, plane, d_pc, pc_tol, spec ? d_pc_go : (int*)nullptr, pc_floor);
     pc_islice = islice;
     if (spec) {
@@ -282,7 +282,7 @@ int Engine::pc_enqueue_iteration (int it)
     const dim3 gplane(ceil_div(plane, 256));
     const long nval = (long)d.nx*d.ny;
     const int islice = pc_islice;
-    const bool spec = pc_speculate && el.tiling && !moving && !ions.present();
+    const bool spec = pc_speculate && el.tiling && !moving && !ions.present() && !further();
     int* go = spec ? d_pc_go + it : nullptr;
     const int comp_push[5] = {HPS_PC_PSI, HPS_PC_EZ, HPS_PC_BX, HPS_PC_BY, HPS_PC_BZ};
     int e;
@@ -332,7 +332,7 @@ int Engine::solve_slice_pc_finish (int islice)
     const int comp_push[5] = {HPS_PC_PSI, HPS_PC_EZ, HPS_PC_BX, HPS_PC_BY, HPS_PC_BZ};
     int e;
     double err = pc_last_err;
-    if (pc_speculate && el.tiling && !moving && !ions.present()) {
+    if (pc_speculate && el.tiling && !moving && !ions.present() && !further()) {
         int it = 0;
         err = 1.0;
         while (err > pc_tol && it < pc_max_iter) {
@@ -367,6 +367,7 @@ int Engine::solve_slice_pc_finish (int islice)
         if ((e = ionize_collect())) return e;
     }
     if ((e = species_advance(el, comp_push, 0))) return e;
+    for (int k = 2; k < n_sp; ++k) { if ((e = species_advance(sp[k], comp_push, 0))) return e; }      // the further species
     insitu_beam(islice);
     if (moving && nbeam > 0) { if ((e = beam_push_moving(*this, islice))) return e; }
     if (!coll.empty()) { if ((e = collide_slice(islice))) return e; }      // doCoulombCollision (Hipace.cpp:711-712)
@@ -386,7 +387,7 @@ int Engine::pc_slice_ready () const
 {
     // device-controlled loop: ready when the host's walk over the posted errors (solve_slice_pc_finish) would not wait --
     // an iteration that met the tolerance has been posted, or every iteration enqueued so far has
-    if (!(pc_speculate && el.tiling && !moving && !ions.present()) || pc_islice < 0 || pc_enqueued <= 0) return 1;
+    if (!(pc_speculate && el.tiling && !moving && !ions.present() && !further()) || pc_islice < 0 || pc_enqueued <= 0) return 1;
     for (int it = 1; it <= pc_enqueued; ++it) {
         const volatile double* hp = h_pc + 8*it;
         const double seq = pc_base_seq + it;

@@ -184,6 +184,7 @@ int Engine::set_beam_species_salame (int on)
     HPS_REFUSE(pc, "beam_species_salame needs the explicit solver (Hipace.cpp:152), not the predictor-corrector");
     HPS_REFUSE(d.ion_on, "beam_species_salame with the ionisable species (ion_on) is not supported");
     HPS_REFUSE(d.laser_on, "beam_species_salame with a laser is not supported");
+    HPS_REFUSE(further(), "beam_species_salame with a further plasma species (hps_engine_add_plasma_species) is not supported: SALAME drives the electrons alone");
 #undef HPS_REFUSE
     HPS_REQUIRE(!step_begun && !el.tiling && steps_begun == 0 && bsp.empty() && coll.empty() && !fine_patch_set,
                 fn + "call behind hps_engine_create, ahead of the other setters, of hps_engine_add_beam_species and of the first hps_engine_begin_step");

@@ -413,6 +413,86 @@ def thermal_u_std(deck, species="plasma"):
     return (((float(T) * q_e_SI) / (mass * c_SI * c_SI)) ** 0.5,) * 3
 
 
+# Further plasma species (plasmas.names beyond the two; MultiPlasma.cpp): the deck's optional entry plasma_species is a
+# list of dicts over PLASMA_SPECIES_DEFAULT, one per fixed-charge species behind "plasma" (0) and "ion" (1).  Like "collisions" it
+# is no member of hps_deck: SliceEngine applies it through hps_engine_add_plasma_species and the per-species setters.  charge and
+# mass in the deck's units (default: the opposite of the plasma's charge; no default mass), density required; u_std and
+# temperature_in_ev exclude each other (thermal_u_std's rule); density_expr and density_table likewise (density_exprs' rule).
+PLASMA_SPECIES_DEFAULT = dict(name=None, charge=None, mass=None, density=None, ppc=(1, 1), fine_ppc=(0, 0), neutralize_background=True,
+                              u_mean=(0.0, 0.0, 0.0), u_std=None, temperature_in_ev=None, seed=0,
+                              density_expr=None, density_table=None, density_constants=None, min_density=None)
+MAX_PLASMA_SPECIES = 6
+PLASMA_SPECIES_NAMES = ("plasma", "ion")      # the names of species 0 and 1
+
+
+def plasma_species_spec(deck, spec, where="plasma_species"):
+    """One further plasma species over PLASMA_SPECIES_DEFAULT -> dict(name, record, u_mean, u_std, seed, density): record = the
+    fields of hps_plasma_species, u_std from u_std or temperature_in_ev, density = None or (expression or table, constants,
+    min_density) as density_exprs gives it.  ValueError: unknown keys, a missing density or mass, a name of the deck's own
+    species, both a temperature and a u_std, both an expression and a table, a min_density without either."""
+    if not isinstance(spec, dict):
+        raise ValueError(f"{where}: a dict over decks.PLASMA_SPECIES_DEFAULT")
+    unknown = set(spec) - set(PLASMA_SPECIES_DEFAULT)
+    if unknown:
+        raise ValueError(f"{where}: unknown entries {sorted(unknown)}")
+    s = dict(PLASMA_SPECIES_DEFAULT, **spec)
+    if s["density"] is None:
+        raise ValueError(f"{where}: density is required")
+    if s["mass"] is None:
+        raise ValueError(f"{where}: mass is required")
+    if s["name"] in PLASMA_SPECIES_NAMES:
+        raise ValueError(f"{where}: the name {s['name']!r} belongs to species {PLASMA_SPECIES_NAMES.index(s['name'])} of the deck")
+    charge = -float(deck.get("plasma_charge", -1.0)) if s["charge"] is None else float(s["charge"])
+    record = dict(charge=charge, mass=float(s["mass"]), density=float(s["density"]), ppc=tuple(int(v) for v in s["ppc"]),
+                  fine_ppc=tuple(int(v) for v in s["fine_ppc"]), neutralize_background=int(bool(s["neutralize_background"])))
+    u_std = thermal_u_std(dict(q_u_std=s["u_std"], q_temperature_in_ev=s["temperature_in_ev"], q_mass=record["mass"],
+                               si_units=deck.get("si_units", 0)), "q")
+    text, table, mind = s["density_expr"], s["density_table"], s["min_density"]
+    if text is not None and table is not None:
+        raise ValueError(f"{where}: can only use one plasma density from either 'density_expr' or 'density_table', not both")
+    if table is not None:
+        text = read_density_table(table) if isinstance(table, (str, bytes)) or hasattr(table, "__fspath__") else list(table)
+    if text is None and mind is not None:
+        raise ValueError(f"{where}: min_density needs density_expr or density_table")
+    density = None if text is None else (text, s["density_constants"], 0.0 if mind is None else float(mind))
+    return dict(name=s["name"], record=record, u_mean=tuple(float(v) for v in s["u_mean"]), u_std=u_std, seed=int(s["seed"]),
+                density=density)
+
+
+def plasma_species(deck):
+    """The deck's entry plasma_species as a list of plasma_species_spec results ([] for a deck without it).  ValueError: what
+    plasma_species_spec refuses, more species than the engine holds behind the deck's two, a name given twice."""
+    entry = deck.get("plasma_species")
+    if entry is None:
+        return []
+    if isinstance(entry, dict) or not hasattr(entry, "__len__"):
+        raise ValueError("plasma_species: a list of dicts, one per species")
+    if len(entry) > MAX_PLASMA_SPECIES - 2:
+        raise ValueError(f"plasma_species: at most {MAX_PLASMA_SPECIES - 2} species behind the deck's plasma and ion")
+    out = [plasma_species_spec(deck, s, f"plasma_species[{k}]") for k, s in enumerate(entry)]
+    names = [s["name"] for s in out if s["name"] is not None]
+    if len(set(names)) != len(names):
+        raise ValueError(f"plasma_species: a name is given twice ({names})")
+    return out
+
+
+def plasma_species_names(deck):
+    """The names of the deck's plasma species in index order: "plasma", "ion", then the further species' (species<k> unnamed)"""
+    return list(PLASMA_SPECIES_NAMES) + [s["name"] or f"species{2 + k}" for k, s in enumerate(plasma_species(deck))]
+
+
+def plasma_species_index(names, species):
+    """A species given as an index or a name of `names` -> its index.  ValueError: an unknown name, an index out of range."""
+    if isinstance(species, str):
+        if species not in names:
+            raise ValueError(f"no plasma species named {species!r} (have {list(names)})")
+        return list(names).index(species)
+    k = int(species)
+    if not 0 <= k < len(names):
+        raise ValueError(f"no plasma species {k} (the engine holds {len(names)})")
+    return k
+
+
 # Ionisation energies in eV of a few elements: NIST Atomic Spectra Database (Kramida, Ralchenko, Reader and NIST ASD
 # Team, ver. 5.2), the values the reference tabulates in utils/IonizationEnergiesTable.H.
 IONIZATION_ENERGIES_EV = {
@@ -1003,6 +1083,22 @@ def ion_motion_SI(nz=200):
              n_steps=1, dt=0.0, bc=1)
     with_ion_species(d, "H", ne, ppc=(1, 1), initial_level=1)
     d["ion_mass"] = 5.0 * m_e
+    return d
+
+
+def blowout_wake_three_species(nz=24, dopant="N", dopant_density=0.1, background_density_SI=1.0e24):
+    """Three plasma species in one engine: the blowout wake's electrons (species 0, no neutralising background),
+    a neutral dopant that the wake's field ionises (species 1, "ion": ADK, its electrons join species 0) and mobile hydrogen
+    ions in the electrons' place of a background (species 2, "H_ion": fixed charge +1, 1836.15 electron masses, one particle
+    per cell on the electrons' lattice, so that the two cancel ahead of the driver).  A flat-top driver that leaves the head
+    of the box empty; rho is deposited."""
+    d = copy.deepcopy(_DEFAULT)
+    d.update(nz=nz, lo=(-8.0, -8.0, -6.0), hi=(8.0, 8.0, 6.0), plasma_no_neutralize=1, deposit_rho=1, n_steps=1,
+             beam_profile=1, beam_zmin=-4.0, beam_zmax=4.0, beam_radius=1.2, beam_density=3.0,
+             background_density_SI=background_density_SI)
+    with_ion_species(d, dopant, dopant_density, ppc=(1, 1), initial_level=0, seed=7)
+    d["plasma_species"] = [dict(name="H_ion", charge=1.0, mass=1836.15267343, density=d["plasma_density"], ppc=(1, 1),
+                                neutralize_background=False)]
     return d
 
 

@@ -601,7 +601,8 @@ int hps_engine_set_plasma_init (void* handle, const int* plasma_fine_ppc, const 
 int hps_engine_set_fine_patch (void* handle, const unsigned char* mask_host, int transition_cells);
 /* Warm plasmas (InitParticles, PlasmaParticleContainerInit.cpp:52-64, 173-177, 246-313, 317-370; get_gaussian_random_momentum,
  * ParticleUtil.H:113-124).  Not members of hps_deck either; all zero = off: such a deck launches the kernels it launched before.
- *   hps_engine_set_plasma_momentum: <plasma>.u_mean and u_std ([3] each, in units of c) of species 0 (plasma) or 1 (ion).  Every
+ *   hps_engine_set_plasma_momentum: <plasma>.u_mean and u_std ([3] each, in units of c) of species 0 (plasma), 1 (ion) or an
+ *     added species (hps_engine_add_plasma_species: its index enters the key of the draws like 0 and 1).  Every
  *     slot starts with u = u_mean + u_std n, n three standard normal deviates: ux = u_x c, uy = u_y c, psi = sqrt(1 + u.u) - u_z,
  *     the half-step copies equal.  The deviates are counter based: with z(draw) = hash(hash(hash(hash(seed, species), step),
  *     slot), draw) (the generator of the collisions) Box-Muller on draws (0, 1) gives n_x, n_y and its cosine branch on draws
@@ -609,7 +610,7 @@ int hps_engine_set_fine_patch (void* handle, const unsigned char* mask_host, int
  *     does not depend on the launch or on the tiling.  A component with u_std = 0 is exactly u_mean.  temperature_in_ev is the
  *     caller's conversion to u_std = sqrt(T q_e / (M c^2)) (PlasmaParticleContainer.cpp:138-145).  The predictor-corrector
  *     iterates from the first slice on, and an ionisable species with momentum takes no neutral-tile skip: its atoms move.
- *   hps_engine_set_plasma_symmetry, one value for both species:
+ *   hps_engine_set_plasma_symmetry, one value for every species:
  *     do_symmetrize: the slots [0, n/4) are the sheet as it is without the key, the fine patch included, with a quarter of the
  *     weight; copy m = 1, 2, 3 of slot k is slot k + m n/4 at (x_mid2 - x, y), (x, y_mid2 - y), (x_mid2 - x, y_mid2 - y) with
  *     the signs (-,+), (+,-), (-,-) on (ux, uy); x_mid2 = lo + hi.  The copy of an invalid slot is invalid.  hps_engine_info,
@@ -902,7 +903,8 @@ int hps_collide_plasma (hps_plasma a, void* tiling_a, hps_plasma b, void* tiling
                         double charge_a, double mass_a, int can_ionize_a, double charge_b, double mass_b, int can_ionize_b,
                         double coulomb_log, double background_density_SI, unsigned long long seed, int collision,
                         int step, int islice, long* pairs_collided_host, long* overfull_cells_host, hps_stream stream);
-/* Engine: one more collision between species_a and species_b (0 = the plasma, 1 = the species "ion"), run in the order of
+/* Engine: one more collision between species_a and species_b (0 = the plasma, 1 = the species "ion", 2 ... = the species of
+ * hps_engine_add_plasma_species, which must have been added before), run in the order of
  * the calls at the end of every slice, behind the plasma and beam pushes and ahead of ShiftSlices (Hipace.cpp:711-712); the
  * predictor-corrector loop collides once per slice, behind its committing push.  Call after hps_engine_create and before the
  * first hps_engine_begin_step.  coulomb_log <= 0: automatic.  With a collision configured the plasma's particles carry their
@@ -1003,7 +1005,8 @@ int hps_expr_eval (const hps_expr* prog, int n_vars, long n, const double* const
  * hps_engine_begin_step, a program hps_expr_check refuses (with its message). */
 int hps_engine_set_beam_external_fields (void* handle, const hps_expr* E3, const hps_expr* B3);
 /* Engine: <plasma>.density(x,y,z), min_density and density_table_file (PlasmaParticleContainer.cpp:90-119, 211-217;
- * InitParticles, PlasmaParticleContainerInit.cpp:246-313) for species 0 (plasma) or 1 (ion): progs are n_progs >= 1
+ * InitParticles, PlasmaParticleContainerInit.cpp:246-313) for species 0 (plasma), 1 (ion) or an added species
+ * (hps_engine_add_plasma_species; its programs join the engine's one image): progs are n_progs >= 1
  * programs over exactly (x, y, z).  z_pos = NULL with n_progs = 1 is density(x,y,z); otherwise z_pos holds n_progs strictly
  * ascending positions and the call is the density table: on a step with z = c t the program in force is the first entry with
  * z_pos >= z, the last one beyond the table (std::map::lower_bound, UpdateDensityFunction).  The program's value at a lattice
@@ -1019,7 +1022,7 @@ int hps_engine_set_beam_external_fields (void* handle, const hps_expr* E3, const
  * message). */
 int hps_engine_set_density_expr (void* handle, int species, int n_progs, const hps_expr* progs, const double* z_pos, double min_density);
 /* The same programs for the adaptive time step's controller (host only): rho_max(z) takes |charge * prog(0, 0, z)| for that
- * species (0 plasma, 1 ion) with the program in force at z, evaluated by the routine of hps_expr_eval_host, in place of
+ * species (0 plasma, 1 ion, 2 ... of hps_adaptive_add_species) with the program in force at z, evaluated by the routine of hps_expr_eval_host, in place of
  * |charge density f_r(0) f_t(z)|. */
 int hps_adaptive_set_density_expr (void* handle, int species, int n_progs, const hps_expr* progs, const double* z_pos);
 /* *out_host = rho_max(z) (MultiPlasma::maxChargeDensity, see hps_adaptive_create); changes nothing */
@@ -1165,6 +1168,50 @@ int hps_engine_beam_tags (void* handle, unsigned char* tags_host /* [nbeam] */);
 int hps_engine_insitu_beam_species (void* handle, int species, double* out_host /* [23][nz] */);
 int hps_engine_beam_moments_species (void* handle, double* out_host /* [n][4] */);
 int hps_engine_beam_kernels (void* handle, char* buf, long cap, long* len, int* tagged);
+
+/* ---- further plasma species in one engine (plasmas.names beyond two; MultiPlasma.cpp) -----------------------------
+ * Species 0 is the deck's plasma (the electrons), species 1 the deck's species "ion" (the ionisable one).
+ * hps_engine_add_plasma_species appends a FIXED-CHARGE species behind the two (*index_out: 2, 3, ... HPS_MAX_PLASMA_SPECIES - 1,
+ * also in a deck without the species "ion"): charge and mass in the deck's units, its charge is not multiplied by an ion
+ * level and it never ionises.  It has a sheet, a tiling (the engine's tile size) and a second sort buffer of its own, all sized
+ * by what InitParticles creates for it (ppc, fine_ppc and the engine's patch, do_symmetrize); every hps_engine_begin_step puts
+ * it back on its lattice, it is re-sorted whenever the electrons are, and every per-species operator of the slice -- the
+ * deposition, the explicit deposition, the committing and the temporary push, the laser's initial chi -- takes the present
+ * species in index order, one launch of the tile kernels per species and phase.  fine_ppc = {0, 0}: no fine patch.
+ * neutralize_background != 0: begin_step deposits the species' initial sheet with -charge into the ion rhomjz plane
+ * (DepositNeutralizingBackground, MultiPlasma.cpp:106-118); species 0 keeps plasma_no_neutralize, species 1 has no background.
+ * The index is accepted by hps_engine_set_plasma_momentum, hps_engine_set_density_expr and hps_engine_add_collision (either
+ * side; a species that collides carries its lattice index in the id bits, as the electrons do); the tabulated density profile
+ * (hps_engine_set_density_profile) is the engine's and holds for every species without a program.
+ * With a further species the slice takes the general schedule: no early shift / zero pass in the multigrid, no fused push +
+ * deposit, no push gated behind the V-cycles, and the predictor-corrector's loop is controlled by the host and iterates from
+ * the first slice on (as with the species "ion").  An engine that never calls it allocates and launches what it always did.
+ * Refused, each with its reason in hps_last_error -- HPS_ERR_ARG: a null argument; a call after the first
+ * hps_engine_begin_step; a species beyond HPS_MAX_PLASMA_SPECIES; ppc < 1; density <= 0, mass <= 0 or charge == 0 (or not
+ * finite); fine_ppc that is not {0, 0} and not divisible by ppc, component by component, or given together with
+ * prevent_centered_particle.  HPS_ERR_UNSUPPORTED: an engine with beam_do_salame or hps_engine_set_beam_species_salame (SALAME
+ * drives the electrons alone; hps_engine_set_beam_species_salame refuses an engine with a further species in turn);
+ * hps_engine_add_beam_collision with a species index >= 2.
+ *
+ * hps_engine_plasma_species_info: *n = 2 + the species added, counts [n] = the particles of each sheet now (0: absent); either
+ * may be NULL.  hps_engine_plasma_species(k): the sheet of species k (synchronises the stream; n = 0 and null arrays for an
+ * absent or unknown species).  hps_engine_insitu_plasma_species: hps_engine_insitu_plasma for species k = 0 or k >= 2 (the
+ * further species' buffers are allocated by the first hps_engine_begin_step behind hps_engine_set_insitu_plasma). */
+#define HPS_MAX_PLASMA_SPECIES 6
+typedef struct {
+    double charge, mass, density;
+    int ppc[2];
+    int fine_ppc[2];
+    int neutralize_background;
+} hps_plasma_species;
+int hps_engine_add_plasma_species (void* handle, const hps_plasma_species* species, int* index_out);
+int hps_engine_plasma_species_info (void* handle, int* n_host, long* counts_host);
+hps_plasma hps_engine_plasma_species (void* handle, int k);
+int hps_engine_insitu_plasma_species (void* handle, int k, double* out_host /* [15*nz] */);
+/* The adaptive time step's controller: one more species for rho_max(z) (MultiPlasma::maxChargeDensity takes the maximum over
+ * all species): |charge density f_r(0) f_t(z)|, or its program after hps_adaptive_set_density_expr with the returned index
+ * (2, 3, ...).  Returns the index, or -1 (a null handle, a seventh species, a charge or density that is not finite). */
+int hps_adaptive_add_species (void* handle, double charge, double density);
 
 /* ---- utilities ---------------------------------------------------------------------------- */
 int hps_memcpy_d2h (void* dst_host, const void* src_dev, long bytes);
