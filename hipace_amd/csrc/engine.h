@@ -147,13 +147,18 @@ struct Engine {
         int ppc[2] = {0, 0}, fine_ppc[2] = {0, 0}; double density = 0.0, charge = 0.0, mass = 0.0;
         int init_level = 0, can_ionize = 0, keyed = 0;  // keyed: the lattice index in the id bits (the ions; electrons that collide)
         bool temp_push = false;                         // pushed to temporary slices from x_prev: predictor-corrector; the plasma under SALAME
-        bool neutralize = false;                        // a further species: its initial sheet with -charge into the ion rhomjz plane
+        bool neutralize = false;                        // its initial sheet with -charge into the ion rhomjz plane (the electrons: unless plasma_no_neutralize)
+        bool grows_tail = false;                        // particles are appended behind the tile-sorted body (the electrons alone): fold_tail_of
+        bool by_weight = false;                         // Engine::valid_by_w holds for its depositions (the electrons alone)
+        const int* tile_flag = nullptr;                 // per tile "holds charged particles" (the ions': Ions::d_tile_flag, setup_tiling); null: every tile is worked
         Thermal thermal; DensityExpr dens;
         bool present () const { return density > 0.0; } // is the species in the deck
         // Without pushes to a temporary slice every push commits its state, so x_prev == x and y_prev == y at all times
         // (PlasmaParticleAdvance.cpp:176-188): alias them -- two arrays less to write per push and to move per re-sort.
         // The C ABI keeps 11 pointers; the kernels skip the second store when two coincide.
         bool alias_prev () const { return !temp_push; }
+        // the sheet as the tile launchers take it (particles_tiled.h); sign = -1: the neutralising background
+        TileSheet sheet (double sign = 1.0) const { return {pl, sign*charge, mass, can_ionize, tiling}; }
     } sp[HPS_MAX_PLASMA_SPECIES];
     Species &el = sp[0], &ions = sp[1];
     // Further species: the slots behind the two (absent slots hold no particles and every per-species loop passes them by).
@@ -194,6 +199,11 @@ struct Engine {
     int ion_field_bounds ();                   // ...: per-tile field maxima for the tile skip of the ions' push
     bool fold_tail = true;                     // the particles behind the tile-sorted body ride in the tile kernels' launches (HPS_FOLD_TAIL=0: off)
     TailWork fold_tail_of (const Species& s, long margin, long* covered) const;
+    // the engine-wide part of the tile launchers' record (particles_tiled.h); every launch of the engine builds it here
+    TileEnv tile_env () const { return {slab, gm, d.order, st, d_nfallback, c_aabs}; }
+    // the skeleton of the three operators below: tiled(tail's workgroups) over the sorted body, plain(sheet) over a sheet without tiles and over what
+    // lies behind the body and its tail.  live_tail: the caller's tail, whose count is read on the device -- what lies behind it is the caller's too
+    template <class Tiled, class Plain> int species_op (const Species& s, const TailWork* live_tail, Tiled&& tiled, Plain&& plain);
     // (go: the gate word of an iteration of the predictor-corrector loop's device-side control, null otherwise)
     int species_deposit (const Species& s, const int comp[6], const BeamPairWork* beam = nullptr, const int* go = nullptr);
     bool valid_by_w = true;                    // HPS_VALID_BY_W=0: off.  The depositions take "weight != 0" for the valid bit of idcpu and do not read it (PartConsts::valid_by_w:
@@ -204,7 +214,9 @@ struct Engine {
     bool fold_hierarchy = true;                // the multigrid's coefficient hierarchy in the -grad Psi / Sx, Sy launch (HPS_FOLD_HIERARCHY=0: in mg_solve1_begin)
     bool fold_beam = true;                     // the static beam's two deposits of a slice as extra workgroups of the plasma's deposition (HPS_FOLD_BEAM=0: a launch of their own)
     int species_explicit (const Species& s, const int cache[4], const int depos[2]);
-    int species_advance (const Species& s, const int comp[5], int temp_slice, const int* go = nullptr);
+    // (ion: the ADK decisions of the committing push of the ionisable species, taken inside its tile kernel -- push_with_ionization)
+    int species_advance (const Species& s, const int comp[5], int temp_slice, const int* go = nullptr, const IonArgs* ion = nullptr,
+                         const TailWork* live_tail = nullptr);
     // the tile sort (sort.hip) and the plasma's re-sort rule
     int tile_size = 16, sort_period = 128, since_sort = 0;
     int* d_nfallback = nullptr;                 // word 0 of the multigrid norm buffer's header slot (mg_rider)
@@ -332,8 +344,12 @@ struct Engine {
     int solve_slice_begin (int islice);      // ... in two halves: everything up to the Bx/By solve's norm read-back is enqueued,
     int solve_slice_finish (int islice);     // then the host waits for the norms and enqueues the rest
     int pending_slice = -1; bool pend_fuse = false, pend_gated = false, pend_gated_ion = false;
-    bool gate_ion_push = true; IonArgs pend_ia{}; long pend_covered = 0;      // the ionisable species' push + the electrons' push behind the V-cycles (HPS_GATED_ION_PUSH=0: off)
-    int push_with_ionization (int islice, const int comp[5], const int* go, bool first);
+    bool gate_ion_push = true; IonArgs pend_ia{};      // the ionisable species' push + the electrons' push behind the V-cycles (HPS_GATED_ION_PUSH=0: off)
+    long pend_covered = 0;                             // the electrons the gated push_with_ionization's launch has room for (solve_slice_begin -> _finish)
+    // (*covered: the electrons its launch has room for; -1: it launched none of them -- no tiling, or nothing sorted)
+    int push_with_ionization (int islice, const int comp[5], const int* go, bool first, long* covered);
+    int push_ions (int islice, const int comp[5], const int* go, bool first);      // ... its first half: the decisions and the ions' push
+    int push_leftover (const int comp[5], long covered);      // the electrons behind `covered`, once ionize_collect has their count
     bool lazy_shift = true, shift_pending = false;      // ShiftSlices deferred to the next slice's InitializeSlices pass (HPS_LAZY_SHIFT=0: off)
     void flush_shift ();
     // HPS_EARLY_INIT (=0: off): on the plain path the next slice's shift / zero pass rides in the launch of the Bx/By solve's first

@@ -423,6 +423,7 @@ int Engine::create (const hps_deck& deck, int device)
     // the species' records: the one place that reads the deck's plasma_* / ion_* spellings.  An absent species keeps density 0
     // (the plasma's charge and mass also hold for the electrons the species "ion" releases into a deck without plasma)
     for (int k = 0; k < 2; ++k) { sp[k].index = k; sp[k].can_ionize = k; sp[k].keyed = k; sp[k].temp_push = pc || (k == 0 && c_sal >= 0); }
+    el.grows_tail = el.by_weight = true; el.neutralize = !d.plasma_no_neutralize;      // (the ions' tile_flag: setup_tiling)
     std::copy(d.plasma_ppc, d.plasma_ppc + 2, el.ppc); el.density = d.plasma_density; el.charge = d.plasma_charge; el.mass = d.plasma_mass;
     if (d.ion_on) { std::copy(d.ion_ppc, d.ion_ppc + 2, ions.ppc); ions.density = d.ion_density; ions.charge = d.ion_charge; ions.mass = d.ion_mass; ions.init_level = d.ion_init_level; }
     if (int e = alloc_sheets()) return e;
@@ -465,7 +466,7 @@ int Engine::add_plasma_species (const hps_plasma_species* s, int* index_out)
     HPS_REQUIRE(!(fine && prevent_centered), fn + "prevent_centered_particle cannot be combined with the fine plasma patch (fine_ppc, fine_patch)");
     Species& q = sp[n_sp];
     q = Species{};
-    q.index = n_sp; q.can_ionize = 0; q.keyed = 0; q.init_level = 0; q.temp_push = pc;
+    q.index = n_sp; q.can_ionize = 0; q.keyed = 0; q.init_level = 0; q.temp_push = pc;      // (no tail, no tile flags, not by weight)
     std::copy(s->ppc, s->ppc + 2, q.ppc); std::copy(s->fine_ppc, s->fine_ppc + 2, q.fine_ppc);
     q.density = s->density; q.charge = s->charge; q.mass = s->mass; q.neutralize = s->neutralize_background != 0;
     q.n_init = q.cap = sheet_slots(q); q.pl.n = q.n_init;
@@ -477,30 +478,26 @@ int Engine::add_plasma_species (const hps_plasma_species* s, int* index_out)
 int Engine::setup_tiling ()
 {
     if (tile_size == 0 || el.cap == 0 || el.tiling) return HPS_OK;
-    if (int e = tiling_create(d.nx, d.ny, tile_size, el.cap, &el.tiling)) return e;
-    // the electrons' push without its idcpu read (tiling.h): every path that creates or invalidates an electron keeps
-    // "valid <=> psi_half != 0" (DESIGN section 6 "Round 10")
-    el.tiling->valid_by_psi = valid_by_psi;
-    if (int e = alloc_soa(el.pl_alt, el.real_alt, el.cap, el.alias_prev())) return e;      // (its n: sort_sheet)
-    if (ions.present()) {
-        // the ionisable species on the engine's tile size.  (Round 2 gave a species with at most one particle per cell 32 x 32-cell
-        // tiles -- 256 particles in a 16 x 16 tile, one per thread, against the tile's fixed cost.  With the tile skip most of
-        // its tiles cost nothing, and its kernels last as long as the few workgroups around the laser's axis that do have
-        // charged ions: four times as many of them, a quarter as long -- config 5 989 -> 1004 slices/s.  HPS_ION_TILE=32)
-        int ion_ts = tile_size;
-        if (const char* v = std::getenv("HPS_ION_TILE")) { const int t = std::atoi(v); if (t == 16 || t == 32) ion_ts = t; }
-        if (int e = tiling_create(d.nx, d.ny, ion_ts, ions.cap, &ions.tiling)) return e;
-        if (int e = alloc_soa(ions.pl_alt, ions.real_alt, ions.cap, ions.alias_prev())) return e;
-        HPS_HIP_CHECK(hipMalloc(&ion.d_tile_flag, (size_t)ions.tiling->g.ntiles*sizeof(int)));
-        {   const char* v = std::getenv("HPS_ION_TILE_SKIP");
-            if (!(v && std::atoi(v) == 0)) HPS_HIP_CHECK(hipMalloc(&ion.d_fbound, (size_t)5*ions.tiling->g.ntiles*sizeof(double))); }
-    }
-    // a further species on the engine's tile size; its push keeps reading idcpu (valid_by_psi stays off in its tiling)
-    for (int k = 2; k < n_sp; ++k) {
+    for (int k = 0; k < n_sp; ++k) {
         Species& s = sp[k];
         if (s.cap == 0) continue;
-        if (int e = tiling_create(d.nx, d.ny, tile_size, s.cap, &s.tiling)) return e;
-        if (int e = alloc_soa(s.pl_alt, s.real_alt, s.cap, s.alias_prev())) return e;
+        // every species on the engine's tile size, the ionisable one too.  (Round 2 gave a species with at most one particle per
+        // cell 32 x 32-cell tiles -- 256 particles in a 16 x 16 tile, one per thread, against the tile's fixed cost.  With the tile
+        // skip most of its tiles cost nothing, and its kernels last as long as the few workgroups around the laser's axis that do
+        // have charged ions: four times as many of them, a quarter as long -- config 5 989 -> 1004 slices/s.  HPS_ION_TILE=32)
+        int ts = tile_size;
+        if (const char* v = s.can_ionize ? std::getenv("HPS_ION_TILE") : nullptr) { const int t = std::atoi(v); if (t == 16 || t == 32) ts = t; }
+        if (int e = tiling_create(d.nx, d.ny, ts, s.cap, &s.tiling)) return e;
+        if (int e = alloc_soa(s.pl_alt, s.real_alt, s.cap, s.alias_prev())) return e;      // (its n: sort_sheet)
+    }
+    // the electrons' push without its idcpu read (tiling.h): every path that creates or invalidates an electron keeps
+    // "valid <=> psi_half != 0" (DESIGN section 6 "Round 10"); every other species' push keeps reading idcpu
+    el.tiling->valid_by_psi = valid_by_psi;
+    if (ions.tiling) {
+        HPS_HIP_CHECK(hipMalloc(&ion.d_tile_flag, (size_t)ions.tiling->g.ntiles*sizeof(int)));
+        ions.tile_flag = ion.d_tile_flag;
+        {   const char* v = std::getenv("HPS_ION_TILE_SKIP");
+            if (!(v && std::atoi(v) == 0)) HPS_HIP_CHECK(hipMalloc(&ion.d_fbound, (size_t)5*ions.tiling->g.ntiles*sizeof(double))); }
     }
     return HPS_OK;
 }
@@ -638,22 +635,16 @@ int Engine::begin_step ()
     // the further species: back on their lattice too, ahead of the sort that takes them along
     for (int k = 2; k < n_sp; ++k) { sp[k].pl.n = sp[k].n_init; if (int e = init_sheet(sp[k])) return e; }
     if (el.tiling) { if (int e = resort()) return e; }      // (tilings exist only beside the electrons': setup_tiling)
-    if (el.pl.n > 0 && !d.plasma_no_neutralize) {
-        // neutralising ion background, deposited once per step with charge -q (MultiPlasma.cpp:106-118)
-        const int comp[6] = {-1, -1, -1, -1, -1, pc ? (int)HPS_PC_ION_RHOMJZ : (int)HPS_C_ION_RHOMJZ};
-        if (el.tiling) {
-            if (int e = deposit_current_tiled(slab, el.pl, gm, comp, -el.charge, el.mass, d.order, d.max_qsa, 0, d_nqsa, el.tiling, d_nfallback, st)) return e;
-        } else {
-            if (int e = hps_deposit_current(slab, el.pl, gm, comp, -el.charge, el.mass, d.order, d.max_qsa, 0, d_nqsa, st)) return e;
-        }
-    }
-    for (int k = 2; k < n_sp; ++k) {
-        // DepositNeutralizingBackground per species (MultiPlasma.cpp:106-118): its initial sheet with charge -q
+    for (int k = 0; k < n_sp; ++k) {
+        // DepositNeutralizingBackground per species (MultiPlasma.cpp:106-118): its initial sheet, deposited once per step with
+        // charge -q and without the laser's |a|^2; the electrons first, then the further species (one plane takes the sums)
         const Species& s = sp[k];
         if (!s.neutralize || s.pl.n == 0) continue;
         const int comp[6] = {-1, -1, -1, -1, -1, pc ? (int)HPS_PC_ION_RHOMJZ : (int)HPS_C_ION_RHOMJZ};
         if (s.tiling) {
-            if (int e = deposit_current_tiled(slab, s.pl, gm, comp, -s.charge, s.mass, d.order, d.max_qsa, 0, d_nqsa, s.tiling, d_nfallback, st)) return e;
+            TileEnv env = tile_env(); env.aabs_comp = -1;
+            DepositArgs a(comp); a.max_qsa = d.max_qsa; a.n_qsa = d_nqsa;
+            if (int e = deposit_current_tiled(env, s.sheet(-1.0), a)) return e;
         } else {
             if (int e = hps_deposit_current(slab, s.pl, gm, comp, -s.charge, s.mass, d.order, d.max_qsa, 0, d_nqsa, st)) return e;
         }
@@ -694,43 +685,46 @@ TailWork Engine::fold_tail_of (const Species& s, long margin, long* covered) con
     const Tiling* T = s.tiling;
     TailWork tw;
     *covered = T->sorted_n;
-    if (!fold_tail || &s != &el || T->sorted_n <= 0) return tw;      // (only the plasma's sheet grows a tail)
+    if (!fold_tail || !s.grows_tail || T->sorted_n <= 0) return tw;      // (only the plasma's sheet grows a tail)
     const long nt = s.pl.n - T->sorted_n + margin;
     if (nt <= 0) return tw;
     tw.first = (int)T->sorted_n; tw.nwg = (int)std::min<long>(ceil_div(nt, 256), 64);
     *covered = T->sorted_n + 256L*tw.nwg;
     return tw;
 }
+template <class Tiled, class Plain> int Engine::species_op (const Species& s, const TailWork* live_tail, Tiled&& tiled, Plain&& plain)
+{
+    const hps_plasma& p = s.pl;
+    if (p.n == 0) return HPS_OK;
+    if (!s.tiling) return plain(p);
+    long covered = 0; const TailWork tw = live_tail ? *live_tail : fold_tail_of(s, 0, &covered);
+    if (s.tiling->sorted_n > 0) { if (int e = tiled(tw)) return e; }
+    if (!live_tail && p.n > covered) return plain(tail_of(p, covered, p.n - covered));
+    return HPS_OK;
+}
 // (`go` gates the tile kernels only: the device-side loop control that passes it has neither a tail nor a sheet without tiles)
 int Engine::species_deposit (const Species& s, const int comp[6], const BeamPairWork* beam, const int* go)
 {
-    const hps_plasma& p = s.pl; Tiling* T = s.tiling;
-    if (p.n == 0) return HPS_OK;
-    if (!T) return hps_deposit_current_laser(slab, p, gm, comp, c_aabs, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, st);
-    long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = deposit_current_tiled(slab, p, gm, comp, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, beam, go, valid_by_w && &s == &el)) return e; }
-    if (p.n > covered) return hps_deposit_current_laser(slab, tail_of(p, covered, p.n - covered), gm, comp, c_aabs, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, st);
-    return HPS_OK;
+    return species_op(s, nullptr,
+        [&] (const TailWork& tw) { DepositArgs a(comp); a.max_qsa = d.max_qsa; a.n_qsa = d_nqsa; a.tile_flag = s.tile_flag; a.tw = tw;
+                                   a.beam = beam; a.go = go; a.valid_by_w = valid_by_w && s.by_weight;
+                                   return deposit_current_tiled(tile_env(), s.sheet(), a); },
+        [&] (const hps_plasma& p) { return hps_deposit_current_laser(slab, p, gm, comp, c_aabs, s.charge, s.mass, d.order, d.max_qsa, s.can_ionize, d_nqsa, st); });
 }
 int Engine::species_explicit (const Species& s, const int cache[4], const int depos[2])
 {
-    const hps_plasma& p = s.pl; Tiling* T = s.tiling;
-    if (p.n == 0) return HPS_OK;
-    if (!T) return hps_explicit_deposit_laser(slab, p, gm, cache, c_aabs, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, st);
-    long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = explicit_deposit_tiled(slab, p, gm, cache, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, T, d_nfallback, st, c_aabs, &s == &ions ? ion.d_tile_flag : nullptr, tw, valid_by_w && &s == &el)) return e; }
-    if (p.n > covered) return hps_explicit_deposit_laser(slab, tail_of(p, covered, p.n - covered), gm, cache, c_aabs, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, st);
-    return HPS_OK;
+    return species_op(s, nullptr,
+        [&] (const TailWork& tw) { ExplicitArgs a(cache, depos); a.dtype = d.deriv_type; a.tile_flag = s.tile_flag; a.tw = tw;
+                                   a.valid_by_w = valid_by_w && s.by_weight;
+                                   return explicit_deposit_tiled(tile_env(), s.sheet(), a); },
+        [&] (const hps_plasma& p) { return hps_explicit_deposit_laser(slab, p, gm, cache, c_aabs, depos, s.charge, s.mass, d.order, d.deriv_type, s.can_ionize, st); });
 }
-int Engine::species_advance (const Species& s, const int comp[5], int temp_slice, const int* go)
+int Engine::species_advance (const Species& s, const int comp[5], int temp_slice, const int* go, const IonArgs* ion, const TailWork* live_tail)
 {
-    const hps_plasma& p = s.pl; Tiling* T = s.tiling;
-    if (p.n == 0) return HPS_OK;
-    if (!T) return hps_advance_plasma_laser(slab, p, gm, comp, c_aabs, s.charge, s.mass, d.order, temp_slice, d.n_subcycles, s.can_ionize, st);
-    long covered; const TailWork tw = fold_tail_of(s, 0, &covered);
-    if (T->sorted_n > 0) { if (int e = advance_plasma_tiled(slab, p, gm, comp, s.charge, s.mass, d.order, temp_slice, d.n_subcycles, s.can_ionize, T, d_nfallback, st, c_aabs, nullptr, go, tw)) return e; }
-    if (p.n > covered) return hps_advance_plasma_laser(slab, tail_of(p, covered, p.n - covered), gm, comp, c_aabs, s.charge, s.mass, d.order, temp_slice, d.n_subcycles, s.can_ionize, st);
-    return HPS_OK;
+    return species_op(s, live_tail,
+        [&] (const TailWork& tw) { PushArgs a(comp); a.temp_slice = temp_slice; a.n_subcycles = d.n_subcycles; a.ion = ion; a.go = go; a.tw = tw;
+                                   return advance_plasma_tiled(tile_env(), s.sheet(), a); },
+        [&] (const hps_plasma& p) { return hps_advance_plasma_laser(slab, p, gm, comp, c_aabs, s.charge, s.mass, d.order, temp_slice, d.n_subcycles, s.can_ionize, st); });
 }
 
 // HPS_EVENT_FENCE: 0 = HIP's default system-scope release at every event, 1 (default) = none at the engine's own
@@ -1011,15 +1005,15 @@ int Engine::solve_slice_begin (int islice)
         if (gated_ion) {
             mark();   // b6
             mark();   // b7
-            if ((e = push_with_ionization(islice, comp_push, mg_gate_after_enqueued(mg), true))) return e;
+            if ((e = push_with_ionization(islice, comp_push, mg_gate_after_enqueued(mg), true, &pend_covered))) return e;
         }
         if (gated) {
             mark();   // b6
             mark();   // b7
             MgPost mp{};
             const bool posting = mg_take_deferred_post(mg, &mp);
-            if ((e = advance_plasma_tiled(slab, el.pl, gm, comp_push, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, el.tiling, d_nfallback, st, c_aabs, nullptr,
-                                          posting ? nullptr : mg_gate_after_enqueued(mg), TailWork{}, posting ? &mp : nullptr))) return e;
+            PushArgs a(comp_push); a.n_subcycles = d.n_subcycles; if (posting) a.post = &mp; else a.go = mg_gate_after_enqueued(mg);
+            if ((e = advance_plasma_tiled(tile_env(), el.sheet(), a))) return e;
         }
         if (laser_split && d.laser_solver == 2) { if ((e = laser_advance_slice(*this, islice)) || (e = laser_done())) return e; }
         pending_slice = islice; pend_fuse = fuse; pend_gated = gated; pend_gated_ion = gated_ion;
@@ -1028,20 +1022,44 @@ int Engine::solve_slice_begin (int islice)
     }
 }
 
+// DoFieldIonization (Hipace.cpp:693-696), then the ions' own committing push; the host learns how many electrons the slice has
+// released while that push runs (ionize_collect).  go, first: as push_with_ionization's.  (The tiled branch relies on the ions'
+// sheet having no tail -- it is sorted whole once per step and nothing is appended to it: particles behind the sorted body
+// would go through species_advance's per-particle kernel, which takes no ADK decisions.)
+int Engine::push_ions (int islice, const int comp[5], const int* go, bool first)
+{
+    if (ions.tiling) {       // decided inside the ions' LDS-tile push, on the fields it gathers anyway
+        if (int e = ion_field_bounds()) return e;
+        if (first) pend_ia = ion_args(islice);
+        return species_advance(ions, comp, 0, go, &pend_ia);
+    }
+    if (int e = ionize_slice(islice)) return e;       // k_ionize ahead of the per-particle push
+    return species_advance(ions, comp, 0);
+}
+
 // DoFieldIonization + the ions' push + the electrons' push (Hipace.cpp:693-701) of a slice on tiles, enqueued without a word from
 // the host in between: the ions' field bounds, the ions' push (ADK decisions on the fields it gathers, electrons appended on the
 // device), the electrons' tile-sorted body with the tail's workgroups reading the live particle count.  `go`: the multigrid
 // solve's gate word (both pushes do nothing unless the solve is over); first = false: the same launches again, ungated, after
 // the host has added V-cycles (same ADK sequence number: the count is posted once).
-int Engine::push_with_ionization (int islice, const int comp[5], const int* go, bool first)
+int Engine::push_with_ionization (int islice, const int comp[5], const int* go, bool first, long* covered)
 {
-    int e;
-    if ((e = ion_field_bounds())) return e;
-    if (first) pend_ia = ion_args(islice);
-    if ((e = advance_plasma_tiled(slab, ions.pl, gm, comp, ions.charge, ions.mass, d.order, 0, d.n_subcycles, 1, ions.tiling, d_nfallback, st, c_aabs, &pend_ia, go))) return e;
-    TailWork tw = fold_tail_of(el, 256, &pend_covered);
+    if (int e = push_ions(islice, comp, go, first)) return e;
+    // the electrons' tile-sorted body does not depend on how many electrons the slice has released: push it while the count travels
+    // to the host (ionize_collect), then the rest with the new count (push_leftover).  The tail's workgroups in that launch read the
+    // count on the device -- the ions' push is ahead of them on the stream --, with room for 256 electrons more than the host knows of
+    *covered = -1;
+    if (!el.tiling || el.tiling->sorted_n <= 0) return HPS_OK;
+    TailWork tw = fold_tail_of(el, 256, covered);
     if (tw.nwg) tw.live_n = ion.d_cnt;
-    return advance_plasma_tiled(slab, el.pl, gm, comp, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, el.tiling, d_nfallback, st, c_aabs, nullptr, go, tw);
+    return species_advance(el, comp, 0, go, nullptr, &tw);
+}
+
+// the electrons the slice has released beyond the room (`covered`) that push_with_ionization's launch had for them
+int Engine::push_leftover (const int comp[5], long covered)
+{
+    if (el.pl.n <= covered) return HPS_OK;
+    return hps_advance_plasma_laser(slab, tail_of(el.pl, covered, el.pl.n - covered), gm, comp, c_aabs, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, st);
 }
 
 int Engine::solve_slice_finish (int islice)
@@ -1062,10 +1080,8 @@ int Engine::solve_slice_finish (int islice)
         // the speculated V-cycles were not enough (the gated push has not run): the host has added the rest, push now
         if (gated && extra) { if ((e = species_advance(el, comp_push, 0))) return e; }
         if (gated_ion) {
-            if (extra) { if ((e = push_with_ionization(islice, comp_push, nullptr, false))) return e; }
-            // the electrons the slice has released beyond the room the body's launch had for them
-            if ((e = ionize_collect())) return e;
-            if (el.pl.n > pend_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(el.pl, pend_covered, el.pl.n - pend_covered), gm, comp_push, c_aabs, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
+            if (extra) { if ((e = push_with_ionization(islice, comp_push, nullptr, false, &pend_covered))) return e; }
+            if ((e = ionize_collect()) || (e = push_leftover(comp_push, pend_covered))) return e;      // (a gated slice has a body: pend_covered >= 0)
         } }
 
     // SalameModule (Hipace.cpp:673-678): behind the Bx/By solve, ahead of the diagnostics and the push, on a slice whose beam
@@ -1088,39 +1104,17 @@ int Engine::solve_slice_finish (int islice)
     mark();   // b7
     // gather + push (Hipace.cpp:699-701)
     {   const int* comp = comp_push;
-        bool body_done = false; long body_covered = 0;
-        if (ions.present()) {
-            // DoFieldIonization (Hipace.cpp:693-696), then the ions' own push; the host learns how many electrons the
-            // slice has released while that push runs
-            if (ions.tiling) {       // decided inside the ions' LDS-tile push, on the fields it gathers anyway
-                if ((e = ion_field_bounds())) return e;
-                const IonArgs ia = ion_args(islice);
-                if ((e = advance_plasma_tiled(slab, ions.pl, gm, comp, ions.charge, ions.mass, d.order, 0, d.n_subcycles, 1, ions.tiling, d_nfallback, st, c_aabs, &ia))) return e;
-            } else {
-                if ((e = ionize_slice(islice))) return e;
-                if ((e = species_advance(ions, comp, 0))) return e;
-            }
-            // the electrons' tile-sorted body does not depend on how many electrons the slice has released: push it while the
-            // count travels to the host, then the tail with the new count
-            // (the tail's workgroups in that launch read the count on the device -- the ions' push is ahead of them on the
-            //  stream --, with room for 256 electrons more than the host knows of; whoever is beyond that is pushed below)
-            if (el.tiling && el.tiling->sorted_n > 0 && !fuse) {
-                TailWork tw = fold_tail_of(el, 256, &body_covered);
-                if (tw.nwg) tw.live_n = ion.d_cnt;
-                if ((e = advance_plasma_tiled(slab, el.pl, gm, comp, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, el.tiling, d_nfallback, st, c_aabs, nullptr, nullptr, tw))) return e;
-                body_done = true;
-            }
-            if ((e = ionize_collect())) return e;
-        }
+        long covered = -1;      // the electrons that push_with_ionization has launched; -1: none, the whole sheet is still to push
+        if (ions.present()) { if ((e = push_with_ionization(islice, comp, nullptr, true, &covered)) || (e = ionize_collect())) return e; }
         // push of this slice and deposition of the next one in one pass over the sheet (static beam, no laser, one
         // plasma species, the whole sheet inside the tile-sorted body)
         if (fuse) {
             hipLaunchKernelGGL(k_shift_zero, gplane, b256, 0, st, ShiftInit{slab.p, slab.nstride, plane, (int)slab.jstride, bb, set_canon, set_canon, (int)HPS_C_ION_RHOMJZ});
             const int dep[6] = {HPS_C_JX, HPS_C_JY, -1, d.deposit_rho ? HPS_C_RHO : -1, HPS_C_CHI, HPS_C_RHOMJZ};
-            if ((e = advance_deposit_tiled(slab, el.pl, gm, comp, dep, el.charge, el.mass, d.order, d.n_subcycles, d.max_qsa, d_nqsa, el.tiling, d_nfallback, st))) return e;
+            if ((e = advance_deposit_tiled(tile_env(), el.sheet(), comp, dep, d.n_subcycles, d.max_qsa, d_nqsa))) return e;
             ahead_for = islice - 1;
-        } else if (body_done) {
-            if (el.pl.n > body_covered) { if ((e = hps_advance_plasma_laser(slab, tail_of(el.pl, body_covered, el.pl.n - body_covered), gm, comp, c_aabs, el.charge, el.mass, d.order, 0, d.n_subcycles, 0, st))) return e; }
+        } else if (covered >= 0) {
+            if ((e = push_leftover(comp, covered))) return e;
         } else {
             if ((e = species_advance(el, comp, 0))) return e;
         }

@@ -1086,40 +1086,38 @@ static int set_lds (K kernel, size_t bytes)
         case  316: { CALL(3, 16); } break;  case  332: { CALL(3, 32); } break;    \
         default: set_error("tiled kernels: unsupported order / tile size"); return HPS_ERR_ARG; }
 
-int deposit_current_tiled (const hps_slab& slab, const hps_plasma& pl, const hps_geom& g, const int comp[6], double charge,
-                           double mass, int order, double max_qsa, int can_ionize, int* n_qsa, Tiling* T, int* n_fallback,
-                           hipStream_t st, int aabs_comp, const int* tile_flag, TailWork tw, const BeamPairWork* beam, const int* go,
-                           bool valid_by_w)
+int deposit_current_tiled (const TileEnv& env, const TileSheet& sh, const DepositArgs& a)
 {
-    if (pl.n == 0) return HPS_OK;
-    const BeamPairWork bw = beam ? *beam : BeamPairWork{};
+    if (sh.pl.n == 0) return HPS_OK;
+    const BeamPairWork bw = a.beam ? *a.beam : BeamPairWork{};
+    TailWork tw = a.tw;
     tw.extra = bw.nwg;
     // the per-tile skip indexes the launch order by blockIdx: only valid while the grid holds tile workgroups alone
-    HPS_REQUIRE(!(tile_flag && (tw.nwg || bw.nwg)), "deposit_current_tiled: tile flags cannot be combined with tail or beam workgroups");
-    HPS_REQUIRE(pl.n + 256L*tw.nwg < (1L << 28), "deposit_current_tiled: the tile kernels address at most 2^28 particles per sheet");
-    PartConsts k = base_consts(g);
-    k.a = charge*invvol_of(g); k.b = charge*g.mu0/mass; k.max_qsa = max_qsa; k.can_ionize = can_ionize;
-    k.aabs = aabs_comp; k.laser_fac = (charge/g.q_e)*(g.m_e/mass)*(charge/g.q_e)*(g.m_e/mass);
-    DepComps cm{comp[0], comp[1], comp[2], comp[3], comp[4], comp[5]};
-    int na = 0; for (int c = 0; c < 6; ++c) na += comp[c] >= 0;
-    {   int m = 0; for (int c = 0; c < 6; ++c) m |= (comp[c] >= 0) << c;
+    HPS_REQUIRE(!(a.tile_flag && (tw.nwg || bw.nwg)), "deposit_current_tiled: tile flags cannot be combined with tail or beam workgroups");
+    HPS_REQUIRE(sh.pl.n + 256L*tw.nwg < (1L << 28), "deposit_current_tiled: the tile kernels address at most 2^28 particles per sheet");
+    PartConsts k = base_consts(env.g);
+    k.a = sh.charge*invvol_of(env.g); k.b = sh.charge*env.g.mu0/sh.mass; k.max_qsa = a.max_qsa; k.can_ionize = sh.can_ionize;
+    k.aabs = env.aabs_comp; k.laser_fac = (sh.charge/env.g.q_e)*(env.g.m_e/sh.mass)*(sh.charge/env.g.q_e)*(env.g.m_e/sh.mass);
+    DepComps cm{a.comp[0], a.comp[1], a.comp[2], a.comp[3], a.comp[4], a.comp[5]};
+    int na = 0; for (int c = 0; c < 6; ++c) na += a.comp[c] >= 0;
+    {   int m = 0; for (int c = 0; c < 6; ++c) m |= (a.comp[c] >= 0) << c;
         // (kernel variants exist for the hot component sets without a laser; the tail's released electrons keep idcpu)
-        k.valid_by_w = valid_by_w && !tw.nwg && aabs_comp < 0 && (m == 51 || m == 3); }
-    const int R = T->g.ts + 2*TILE_HALO;
-    const size_t lds = ((size_t)na*R*R + (aabs_comp >= 0 ? (size_t)R*R : 0))*sizeof(double);
-    SlabView f(slab);
-    int mask = 0; for (int c = 0; c < 6; ++c) mask |= (comp[c] >= 0) << c;
+        k.valid_by_w = a.valid_by_w && !tw.nwg && env.aabs_comp < 0 && (m == 51 || m == 3); }
+    const int R = sh.T->g.ts + 2*TILE_HALO;
+    const size_t lds = ((size_t)na*R*R + (env.aabs_comp >= 0 ? (size_t)R*R : 0))*sizeof(double);
+    SlabView f(env.slab);
+    int mask = 0; for (int c = 0; c < 6; ++c) mask |= (a.comp[c] >= 0) << c;
 #define CALLM(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M>, lds)) return e; HPS_RECORD("k_deposit_tiled", O, S, M, 0, 0); \
-        hipLaunchKernelGGL((k_deposit_tiled<O, S, M>), dim3(T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, cm, k, n_qsa, n_fallback, tile_flag, tw, bw, go); }
+        hipLaunchKernelGGL((k_deposit_tiled<O, S, M>), dim3(sh.T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx, cm, k, a.n_qsa, env.n_fallback, a.tile_flag, tw, bw, a.go); }
 #define CALLL(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M, true>, lds)) return e; HPS_RECORD("k_deposit_tiled", O, S, M, 1, 0); \
-        hipLaunchKernelGGL((k_deposit_tiled<O, S, M, true>), dim3(T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, cm, k, n_qsa, n_fallback, tile_flag, tw, bw, go); }
+        hipLaunchKernelGGL((k_deposit_tiled<O, S, M, true>), dim3(sh.T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx, cm, k, a.n_qsa, env.n_fallback, a.tile_flag, tw, bw, a.go); }
 #define CALLV(O, S, M) { if (int e = set_lds(k_deposit_tiled<O, S, M, false, true>, lds)) return e; HPS_RECORD("k_deposit_tiled", O, S, M, 0, 1); \
-        hipLaunchKernelGGL((k_deposit_tiled<O, S, M, false, true>), dim3(T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, cm, k, n_qsa, n_fallback, tile_flag, tw, bw, go); }
-#define CALL(O, S) { if (aabs_comp >= 0) { if (mask == 51) CALLL(O, S, 51) else CALLL(O, S, -1) } \
+        hipLaunchKernelGGL((k_deposit_tiled<O, S, M, false, true>), dim3(sh.T->g.ntiles + tw.nwg + bw.nwg), dim3(256), lds, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx, cm, k, a.n_qsa, env.n_fallback, a.tile_flag, tw, bw, a.go); }
+#define CALL(O, S) { if (env.aabs_comp >= 0) { if (mask == 51) CALLL(O, S, 51) else CALLL(O, S, -1) } \
                      else if (k.valid_by_w && mask == 51) CALLV(O, S, 51) else if (k.valid_by_w && mask == 3) CALLV(O, S, 3) \
                      else if (mask == 51) CALLM(O, S, 51) else if (mask == 59) CALLM(O, S, 59) else if (mask == 32) CALLM(O, S, 32) \
                      else if (mask == 3) CALLM(O, S, 3) else if (mask == 39) CALLM(O, S, 39) else if (mask == 47) CALLM(O, S, 47) else CALLM(O, S, -1) }
-    HPS_DISPATCH_ORDER_TS(order, T->g.ts, CALL)
+    HPS_DISPATCH_ORDER_TS(env.order, sh.T->g.ts, CALL)
 #undef CALL
 #undef CALLM
 #undef CALLL
@@ -1128,32 +1126,30 @@ int deposit_current_tiled (const hps_slab& slab, const hps_plasma& pl, const hps
     return HPS_OK;
 }
 
-int explicit_deposit_tiled (const hps_slab& slab, const hps_plasma& pl, const hps_geom& g, const int cache[4], const int depos[2],
-                            double charge, double mass, int order, int dtype, int can_ionize, Tiling* T, int* n_fallback,
-                            hipStream_t st, int aabs_comp, const int* tile_flag, TailWork tw, bool valid_by_w)
+int explicit_deposit_tiled (const TileEnv& env, const TileSheet& sh, const ExplicitArgs& a)
 {
-    if (pl.n == 0) return HPS_OK;
-    HPS_REQUIRE(!(tile_flag && tw.nwg), "explicit_deposit_tiled: tile flags cannot be combined with tail workgroups");
-    HPS_REQUIRE(pl.n + 256L*tw.nwg < (1L << 28), "explicit_deposit_tiled: the tile kernels address at most 2^28 particles per sheet");
-    PartConsts k = base_consts(g);
-    k.a = charge*invvol_of(g)*g.mu0; k.b = charge/mass; k.can_ionize = can_ionize;
-    k.valid_by_w = valid_by_w && !tw.nwg && aabs_comp < 0 && dtype == 2;      // (the kernel variant that exists)
-    k.aabs = aabs_comp; k.laser_fac = (g.m_e/g.q_e)*(g.m_e/g.q_e);
-    const int R = T->g.ts + 2*TILE_HALO;
+    if (sh.pl.n == 0) return HPS_OK;
+    HPS_REQUIRE(!(a.tile_flag && a.tw.nwg), "explicit_deposit_tiled: tile flags cannot be combined with tail workgroups");
+    HPS_REQUIRE(sh.pl.n + 256L*a.tw.nwg < (1L << 28), "explicit_deposit_tiled: the tile kernels address at most 2^28 particles per sheet");
+    PartConsts k = base_consts(env.g);
+    k.a = sh.charge*invvol_of(env.g)*env.g.mu0; k.b = sh.charge/sh.mass; k.can_ionize = sh.can_ionize;
+    k.valid_by_w = a.valid_by_w && !a.tw.nwg && env.aabs_comp < 0 && a.dtype == 2;      // (the kernel variant that exists)
+    k.aabs = env.aabs_comp; k.laser_fac = (env.g.m_e/env.g.q_e)*(env.g.m_e/env.g.q_e);
+    const int R = sh.T->g.ts + 2*TILE_HALO;
     const int pad = expl_pad();
-    const size_t lds = (size_t)(aabs_comp >= 0 ? 7 : 6)*R*(R + pad)*sizeof(double);
-    SlabView f(slab);
+    const size_t lds = (size_t)(env.aabs_comp >= 0 ? 7 : 6)*R*(R + pad)*sizeof(double);
+    SlabView f(env.slab);
 #define HPS_EXPL_LAUNCH(O, D, S, L, P, V) { if (int e = set_lds(k_explicit_tiled<O, D, S, L, P, V>, lds)) return e; HPS_RECORD("k_explicit_tiled", O, D, S, L, P, V); \
-        hipLaunchKernelGGL((k_explicit_tiled<O, D, S, L, P, V>), dim3(T->g.ntiles + tw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, \
-                           cache[0], cache[1], cache[2], cache[3], depos[0], depos[1], k, n_fallback, tile_flag, tw); }
+        hipLaunchKernelGGL((k_explicit_tiled<O, D, S, L, P, V>), dim3(sh.T->g.ntiles + a.tw.nwg), dim3(256), lds, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx, \
+                           a.cache[0], a.cache[1], a.cache[2], a.cache[3], a.depos[0], a.depos[1], k, env.n_fallback, a.tile_flag, a.tw); }
 #define HPS_EXPL_PADS(O, D, S, L) { if (pad == 8) HPS_EXPL_LAUNCH(O, D, S, L, 8, false) else if (!L && D == 2 && k.valid_by_w) HPS_EXPL_LAUNCH(O, D, S, false, 2, true) else HPS_EXPL_LAUNCH(O, D, S, L, 2, false) }
-    if (dtype == 2) {
-#define CALL(O, S) { if (aabs_comp >= 0) HPS_EXPL_PADS(O, 2, S, true) else HPS_EXPL_PADS(O, 2, S, false) }
-        HPS_DISPATCH_ORDER_TS(order, T->g.ts, CALL)
+    if (a.dtype == 2) {
+#define CALL(O, S) { if (env.aabs_comp >= 0) HPS_EXPL_PADS(O, 2, S, true) else HPS_EXPL_PADS(O, 2, S, false) }
+        HPS_DISPATCH_ORDER_TS(env.order, sh.T->g.ts, CALL)
 #undef CALL
     } else {
-#define CALL(O, S) { if (aabs_comp >= 0) HPS_EXPL_PADS(O, 1, S, true) else HPS_EXPL_PADS(O, 1, S, false) }
-        HPS_DISPATCH_ORDER_TS(order, T->g.ts, CALL)
+#define CALL(O, S) { if (env.aabs_comp >= 0) HPS_EXPL_PADS(O, 1, S, true) else HPS_EXPL_PADS(O, 1, S, false) }
+        HPS_DISPATCH_ORDER_TS(env.order, sh.T->g.ts, CALL)
 #undef CALL
     }
 #undef HPS_EXPL_PADS
@@ -1162,34 +1158,32 @@ int explicit_deposit_tiled (const hps_slab& slab, const hps_plasma& pl, const hp
     return HPS_OK;
 }
 
-int advance_plasma_tiled (const hps_slab& slab, const hps_plasma& pl, const hps_geom& g, const int comp[5], double charge,
-                          double mass, int order, int temp_slice, int n_subcycles, int can_ionize, Tiling* T,
-                          int* n_fallback, hipStream_t st, int aabs_comp, const IonArgs* ion, const int* go, TailWork tw, const MgPost* post)
+int advance_plasma_tiled (const TileEnv& env, const TileSheet& sh, const PushArgs& a)
 {
-    if (pl.n == 0) return HPS_OK;
+    if (sh.pl.n == 0) return HPS_OK;
     // 32-bit byte offsets into the SoA arrays (ip*8u, __builtin_assume(ip < 2^28) in the kernel); the tail's live count is
     // read on the device but bounded by the workgroups it was given
-    HPS_REQUIRE(pl.n + 256L*tw.nwg < (1L << 28), "advance_plasma_tiled: the tile kernels address at most 2^28 particles per sheet");
-    HPS_REQUIRE(!(ion && ion->tile_flag && tw.nwg), "advance_plasma_tiled: an ionisable species' tile flags cannot be combined with tail workgroups");
-    PartConsts k = base_consts(g);
-    k.a = charge/(mass*g.c); k.dz = g.dz/n_subcycles;
-    k.aabs = aabs_comp; k.laser_fac = (charge/g.q_e)*(g.m_e/mass)*(charge/g.q_e)*(g.m_e/mass);
-    k.temp_slice = temp_slice; k.n_subcycles = n_subcycles; k.can_ionize = can_ionize;
-    const int R = T->g.ts + 2*TILE_HALO;
-    const size_t lds = (size_t)(aabs_comp >= 0 ? 6 : 5)*R*R*sizeof(double);
-    SlabView f(slab);
-    const IonArgs ia = ion ? *ion : IonArgs{};
-    HPS_REQUIRE(!(post && (tw.nwg || tw.extra)), "advance_plasma_tiled: the launch that posts the multigrid's norms has tile workgroups only");
-    const MgPost mp = post ? *post : MgPost{};
+    HPS_REQUIRE(sh.pl.n + 256L*a.tw.nwg < (1L << 28), "advance_plasma_tiled: the tile kernels address at most 2^28 particles per sheet");
+    HPS_REQUIRE(!(a.ion && a.ion->tile_flag && a.tw.nwg), "advance_plasma_tiled: an ionisable species' tile flags cannot be combined with tail workgroups");
+    PartConsts k = base_consts(env.g);
+    k.a = sh.charge/(sh.mass*env.g.c); k.dz = env.g.dz/a.n_subcycles;
+    k.aabs = env.aabs_comp; k.laser_fac = (sh.charge/env.g.q_e)*(env.g.m_e/sh.mass)*(sh.charge/env.g.q_e)*(env.g.m_e/sh.mass);
+    k.temp_slice = a.temp_slice; k.n_subcycles = a.n_subcycles; k.can_ionize = sh.can_ionize;
+    const int R = sh.T->g.ts + 2*TILE_HALO;
+    const size_t lds = (size_t)(env.aabs_comp >= 0 ? 6 : 5)*R*R*sizeof(double);
+    SlabView f(env.slab);
+    const IonArgs ia = a.ion ? *a.ion : IonArgs{};
+    HPS_REQUIRE(!(a.post && (a.tw.nwg || a.tw.extra)), "advance_plasma_tiled: the launch that posts the multigrid's norms has tile workgroups only");
+    const MgPost mp = a.post ? *a.post : MgPost{};
     // (the variant without the idcpu read exists for order 2 on 16 x 16 tiles, as the depositions' <.., VBW>)
-    const bool vbp = T->valid_by_psi && !ion && !can_ionize && order == 2 && T->g.ts == 16;
+    const bool vbp = sh.T->valid_by_psi && !a.ion && !sh.can_ionize && env.order == 2 && sh.T->g.ts == 16;
 #define HPS_ADV(O, S, L, I, V) { if (int e = set_lds(k_advance_tiled<O, S, L, I, V>, lds)) return e; HPS_RECORD("k_advance_tiled", O, S, L, I, V, 0); \
-        hipLaunchKernelGGL((k_advance_tiled<O, S, L, I, V>), dim3(T->g.ntiles + tw.nwg), dim3(256), lds, st, f, pl, T->offsets, T->g.ntx, \
-                           comp[0], comp[1], comp[2], comp[3], comp[4], k, n_fallback, ia, go, tw, mp, DepTail{}); }
-#define CALL(O, S) { if (ion) { if (aabs_comp >= 0) HPS_ADV(O, S, true, true, false) else HPS_ADV(O, S, false, true, false) } \
-                     else if (vbp && O == 2 && S == 16) { if (aabs_comp >= 0) HPS_ADV(2, 16, true, false, true) else HPS_ADV(2, 16, false, false, true) } \
-                     else     { if (aabs_comp >= 0) HPS_ADV(O, S, true, false, false) else HPS_ADV(O, S, false, false, false) } }
-    HPS_DISPATCH_ORDER_TS(order, T->g.ts, CALL)
+        hipLaunchKernelGGL((k_advance_tiled<O, S, L, I, V>), dim3(sh.T->g.ntiles + a.tw.nwg), dim3(256), lds, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx, \
+                           a.comp[0], a.comp[1], a.comp[2], a.comp[3], a.comp[4], k, env.n_fallback, ia, a.go, a.tw, mp, DepTail{}); }
+#define CALL(O, S) { if (a.ion) { if (env.aabs_comp >= 0) HPS_ADV(O, S, true, true, false) else HPS_ADV(O, S, false, true, false) } \
+                     else if (vbp && O == 2 && S == 16) { if (env.aabs_comp >= 0) HPS_ADV(2, 16, true, false, true) else HPS_ADV(2, 16, false, false, true) } \
+                     else     { if (env.aabs_comp >= 0) HPS_ADV(O, S, true, false, false) else HPS_ADV(O, S, false, false, false) } }
+    HPS_DISPATCH_ORDER_TS(env.order, sh.T->g.ts, CALL)
 #undef CALL
 #undef HPS_ADV
     HPS_HIP_CHECK(hipGetLastError());
@@ -1197,34 +1191,33 @@ int advance_plasma_tiled (const hps_slab& slab, const hps_plasma& pl, const hps_
 }
 
 // push of this slice + deposition into the next one (k_advance_deposit_tiled); dep_comp as DepositCurrent's comp[6]
-int advance_deposit_tiled (const hps_slab& slab, const hps_plasma& pl, const hps_geom& g, const int comp[5], const int dep_comp[6],
-                           double charge, double mass, int order, int n_subcycles, double max_qsa, int* n_qsa, Tiling* T,
-                           int* n_fallback, hipStream_t st)
+int advance_deposit_tiled (const TileEnv& env, const TileSheet& sh, const int comp[5], const int dep_comp[6], int n_subcycles,
+                           double max_qsa, int* n_qsa)
 {
-    if (pl.n == 0) return HPS_OK;
-    PartConsts k = base_consts(g);
-    k.a = charge/(mass*g.c); k.dz = g.dz/n_subcycles; k.temp_slice = 0; k.n_subcycles = n_subcycles; k.can_ionize = 0;
-    PartConsts kd = base_consts(g);
-    kd.a = charge*invvol_of(g); kd.b = charge*g.mu0/mass; kd.max_qsa = max_qsa; kd.can_ionize = 0;
+    if (sh.pl.n == 0) return HPS_OK;
+    PartConsts k = base_consts(env.g);
+    k.a = sh.charge/(sh.mass*env.g.c); k.dz = env.g.dz/n_subcycles; k.temp_slice = 0; k.n_subcycles = n_subcycles; k.can_ionize = 0;
+    PartConsts kd = base_consts(env.g);
+    kd.a = sh.charge*invvol_of(env.g); kd.b = sh.charge*env.g.mu0/sh.mass; kd.max_qsa = max_qsa; kd.can_ionize = 0;
     DepComps cm{dep_comp[0], dep_comp[1], dep_comp[2], dep_comp[3], dep_comp[4], dep_comp[5]};
     int mask = 0, na = 0; for (int c = 0; c < 6; ++c) { mask |= (dep_comp[c] >= 0) << c; na += dep_comp[c] >= 0; }
     if (mask != 51 && mask != 59) { set_error("advance_deposit_tiled: deposits jx jy chi rhomjz [rho] only"); return HPS_ERR_UNSUPPORTED; }
-    const int R = T->g.ts + 2*TILE_HALO;
-    SlabView f(slab);
+    const int R = sh.T->g.ts + 2*TILE_HALO;
+    SlabView f(env.slab);
     // round 5: the push kernel of the separate schedule with the deposition as its tail (k_advance_tiled<.., DEP>); HPS_FUSED_KERNEL=old:
     // round 2's kernel that holds image and accumulators together
     static const bool modern = [] { const char* e = std::getenv("HPS_FUSED_KERNEL"); return !(e && std::string(e) == "old"); }();
-    if (modern && (order == 2 && T->g.ts == 16)) {
+    if (modern && (env.order == 2 && sh.T->g.ts == 16)) {
         const size_t lds5 = (size_t)5*R*R*sizeof(double);
         DepTail dt{cm, kd.a, kd.b, max_qsa, n_qsa};
         const IonArgs ia{}; const TailWork tw0{}; const MgPost mp0{};
         HPS_RECORD("k_advance_tiled", 2, 16, 0, 0, 0, mask);
         if (mask == 51) { if (int e = set_lds(k_advance_tiled<2, 16, false, false, false, 51>, lds5)) return e;
-            hipLaunchKernelGGL((k_advance_tiled<2, 16, false, false, false, 51>), dim3(T->g.ntiles), dim3(256), lds5, st, f, pl, T->offsets, T->g.ntx,
-                               comp[0], comp[1], comp[2], comp[3], comp[4], k, n_fallback, ia, (const int*)nullptr, tw0, mp0, dt); }
+            hipLaunchKernelGGL((k_advance_tiled<2, 16, false, false, false, 51>), dim3(sh.T->g.ntiles), dim3(256), lds5, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx,
+                               comp[0], comp[1], comp[2], comp[3], comp[4], k, env.n_fallback, ia, (const int*)nullptr, tw0, mp0, dt); }
         else            { if (int e = set_lds(k_advance_tiled<2, 16, false, false, false, 59>, lds5)) return e;
-            hipLaunchKernelGGL((k_advance_tiled<2, 16, false, false, false, 59>), dim3(T->g.ntiles), dim3(256), lds5, st, f, pl, T->offsets, T->g.ntx,
-                               comp[0], comp[1], comp[2], comp[3], comp[4], k, n_fallback, ia, (const int*)nullptr, tw0, mp0, dt); }
+            hipLaunchKernelGGL((k_advance_tiled<2, 16, false, false, false, 59>), dim3(sh.T->g.ntiles), dim3(256), lds5, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx,
+                               comp[0], comp[1], comp[2], comp[3], comp[4], k, env.n_fallback, ia, (const int*)nullptr, tw0, mp0, dt); }
         HPS_HIP_CHECK(hipGetLastError());
         return HPS_OK;
     }
@@ -1233,11 +1226,11 @@ int advance_deposit_tiled (const hps_slab& slab, const hps_plasma& pl, const hps
     // (measured at 1024^2 x 4 ppc: 256 threads 285 us, 512 threads 316 us -- against 175 + 77 us for the two kernels)
     if (nt == 0) { nt = 256; if (const char* e = std::getenv("HPS_FUSED_THREADS")) { const int v = std::atoi(e); if (v == 256 || v == 512) nt = v; } }
 #define HPS_AD(O, S, M, N) { if (int e = set_lds(k_advance_deposit_tiled<O, S, M, N>, lds)) return e; HPS_RECORD("k_advance_deposit_tiled", O, S, M, N); \
-        hipLaunchKernelGGL((k_advance_deposit_tiled<O, S, M, N>), dim3(T->g.ntiles), dim3(N), lds, st, f, pl, T->offsets, T->g.ntx, \
-                           comp[0], comp[1], comp[2], comp[3], comp[4], k, cm, kd, n_qsa, n_fallback); }
+        hipLaunchKernelGGL((k_advance_deposit_tiled<O, S, M, N>), dim3(sh.T->g.ntiles), dim3(N), lds, env.st, f, sh.pl, sh.T->offsets, sh.T->g.ntx, \
+                           comp[0], comp[1], comp[2], comp[3], comp[4], k, cm, kd, n_qsa, env.n_fallback); }
 #define CALL(O, S) { if (nt == 512) { if (mask == 51) HPS_AD(O, S, 51, 512) else HPS_AD(O, S, 59, 512) } \
                      else           { if (mask == 51) HPS_AD(O, S, 51, 256) else HPS_AD(O, S, 59, 256) } }
-    HPS_DISPATCH_ORDER_TS(order, T->g.ts, CALL)
+    HPS_DISPATCH_ORDER_TS(env.order, sh.T->g.ts, CALL)
 #undef CALL
 #undef HPS_AD
     HPS_HIP_CHECK(hipGetLastError());
@@ -1285,8 +1278,8 @@ static int deposit_current_tiled_entry (hps_slab slab, hps_plasma pl, hps_geom g
     if (int e = check_tiling(tiling, slab, pl, "hps_deposit_current_tiled")) return e;
     for (int c = 0; c < 6; ++c) HPS_REQUIRE(comp[c] >= -1 && comp[c] < slab.ncomp, "hps_deposit_current_tiled: bad component");
     Tiling* T = static_cast<Tiling*>(tiling);
-    return deposit_current_tiled(slab, pl, g, comp, charge, mass, order, max_qsa, can_ionize, n_qsa,
-                                 T, n_fallback, (hipStream_t)stream, aabs_comp, nullptr, TailWork{}, nullptr, nullptr, T->valid_by_w);
+    DepositArgs a(comp); a.max_qsa = max_qsa; a.n_qsa = n_qsa; a.valid_by_w = T->valid_by_w;
+    return deposit_current_tiled({slab, g, order, (hipStream_t)stream, n_fallback, aabs_comp}, {pl, charge, mass, can_ionize, T}, a);
 }
 
 extern "C" int hps_deposit_current_tiled (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[6], double charge,
@@ -1312,8 +1305,8 @@ static int explicit_deposit_tiled_entry (hps_slab slab, hps_plasma pl, hps_geom 
     if (int e = check_stencil(slab, (order + 1)/2 + 1, "hps_explicit_deposit_tiled")) return e;
     if (int e = check_tiling(tiling, slab, pl, "hps_explicit_deposit_tiled")) return e;
     Tiling* T = static_cast<Tiling*>(tiling);
-    return explicit_deposit_tiled(slab, pl, g, cache, depos, charge, mass, order, dtype, can_ionize,
-                                  T, n_fallback, (hipStream_t)stream, aabs_comp, nullptr, TailWork{}, T->valid_by_w);
+    ExplicitArgs a(cache, depos); a.dtype = dtype; a.valid_by_w = T->valid_by_w;
+    return explicit_deposit_tiled({slab, g, order, (hipStream_t)stream, n_fallback, aabs_comp}, {pl, charge, mass, can_ionize, T}, a);
 }
 
 extern "C" int hps_explicit_deposit_tiled (hps_slab slab, hps_plasma pl, hps_geom g, const int cache[4], const int depos[2],
@@ -1338,8 +1331,8 @@ static int advance_plasma_tiled_entry (hps_slab slab, hps_plasma pl, hps_geom g,
     HPS_REQUIRE(n_subcycles >= 1, "hps_advance_plasma_tiled: n_subcycles must be >= 1");
     if (int e = check_stencil(slab, (order + 1)/2 + 1, "hps_advance_plasma_tiled")) return e;
     if (int e = check_tiling(tiling, slab, pl, "hps_advance_plasma_tiled")) return e;
-    return advance_plasma_tiled(slab, pl, g, comp, charge, mass, order, temp_slice, n_subcycles, can_ionize,
-                                static_cast<Tiling*>(tiling), n_fallback, (hipStream_t)stream, aabs_comp, nullptr, nullptr, TailWork{}, nullptr);
+    PushArgs a(comp); a.temp_slice = temp_slice; a.n_subcycles = n_subcycles;
+    return advance_plasma_tiled({slab, g, order, (hipStream_t)stream, n_fallback, aabs_comp}, {pl, charge, mass, can_ionize, static_cast<Tiling*>(tiling)}, a);
 }
 
 extern "C" int hps_advance_plasma_tiled (hps_slab slab, hps_plasma pl, hps_geom g, const int comp[5], double charge,

@@ -356,15 +356,7 @@ int Engine::solve_slice_pc_finish (int islice)
         // DoFieldIonization (Hipace.cpp:693-696) and the committing pushes of both species (:699-701): the decisions on the tiles'
         // gathered fields inside the ions' push (or k_ionize ahead of the per-particle push), the electron count back on the host,
         // then every electron -- the ones this slice has released included
-        if (ions.tiling) {
-            if ((e = ion_field_bounds())) return e;
-            const IonArgs ia = ion_args(islice);
-            if ((e = advance_plasma_tiled(slab, ions.pl, gm, comp_push, ions.charge, ions.mass, d.order, 0, d.n_subcycles, 1, ions.tiling, d_nfallback, st, -1, &ia))) return e;
-        } else {
-            if ((e = ionize_slice(islice))) return e;
-            if ((e = species_advance(ions, comp_push, 0))) return e;
-        }
-        if ((e = ionize_collect())) return e;
+        if ((e = push_ions(islice, comp_push, nullptr, true)) || (e = ionize_collect())) return e;
     }
     if ((e = species_advance(el, comp_push, 0))) return e;
     for (int k = 2; k < n_sp; ++k) { if ((e = species_advance(sp[k], comp_push, 0))) return e; }      // the further species
